@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- molecules/sec of MolDiff's 1000-step denoising loop on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--headline-only]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the check of what the chain left
+behind, the outputs (--dump-outputs) and the result line.  --full adds everything else described below: the one-rank RCCL
+group, the end-of-run gather, a short pass with hipEvents on every kernel (roofline_edge_b, aggregation, kernel_ms_per_step),
+and on one GPU the other configurations, sample(), B = 2048, the split paths, the training step and the CPU baselines.
+--dump-outputs DIR writes what the last timed step left to a caller (rank 0's batch) as DIR/<name>.npy, float32: the step's
+predictions pred_node (N,8), pred_pos (N,3), pred_halfedge (Eh,6) and the new state h_node, pos, h_halfedge, log_node,
+log_halfedge.  The inputs (sizes, weights, noise seed) are fixed, so two builds given the same arguments can be compared file by file.
 
 One "step" = one iteration of the reverse chain (models/model.py:272-372: noise draw, denoiser forward,
 3 posteriors, 2 Gumbel-max draws) over one packed batch of `--batch` molecules per GPU
@@ -18,7 +26,7 @@ HBM before the timed region; weights are synthetic "recipe" weights (no checkpoi
 `python bench.py --train [--model MolDiff|bondpred] [--precision f32|fp16|bf16] ...` runs the training-step benchmark instead
 (BASELINE.json configs[4]; same launch contract, its own JSON line; see main_train).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but roofline with --full only):
   roofline     -- dominant kernel = fused edge kernel A (fp32 MFMA): algorithmic FLOPs (617,088 per directed
                   edge) / its average launch duration measured with hipEvents on its launch stream
                   during the timed region, against the 157.3 TFLOP/s fp32-matrix peak.
@@ -372,6 +380,9 @@ def cpu_baseline(kind, batch, budget_s=20.0):
     import shutil
     import subprocess
     node, cpus = numa_physical_cores()
+    budget = int(os.environ.get('OMP_NUM_THREADS') or 0)   # a host shared with other jobs states its thread budget there
+    if budget > 0:
+        cpus = cpus[:budget]
     spec = {'kind': kind, 'batch': batch, 'budget_s': budget_s, 'ncores': len(cpus)}
     cmd = [sys.executable, os.path.abspath(__file__), '--cpu-worker', json.dumps(spec)]
     if shutil.which('taskset'):
@@ -760,19 +771,54 @@ def segment_sum_line(sm, dev):
             'operand_mib': E * 1024.0 / 2 ** 20}
 
 
-def main():
+OUTPUT_NAMES = ('pred_node', 'pred_pos', 'pred_halfedge', 'h_node', 'pos', 'h_halfedge', 'log_node', 'log_halfedge')
+DUMP_LIMIT = 64 << 20       # bytes written by --dump-outputs at most
+
+
+def step_outputs(sm):
+    """What the sampler's last step hands a caller: its predictions (sm.result()['pred']) and the new state, as float32 host arrays."""
+    pred, st = sm.result()['pred'], sm.state()
+    arrays = dict(zip(OUTPUT_NAMES[:3], pred), **{k: st[k] for k in ('h_node', 'pos', 'h_halfedge', 'log_node', 'log_halfedge')})
+    return {k: arrays[k].detach().float().cpu().numpy() for k in OUTPUT_NAMES}
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT):
+    """arrays -> out_dir/<name>.npy (float32 or float64 kept, anything else as float32).  A set larger than `limit` bytes keeps a
+    fixed, seeded sample of rows of every array (the same rows from run to run) and records the row ids as <name>.rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for k, v in arrays.items():
+        if total > limit and v.ndim and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * limit / total))
+            rows = np.sort(np.random.Generator(np.random.PCG64(2920)).choice(v.shape[0], keep, replace=False))
+            v = v[rows]
+            np.save(os.path.join(out_dir, k + '.rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, k + '.npy'), v)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=1000)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256, help='molecules per GPU')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: the one-rank RCCL group and the gather, per-kernel durations, '
+                         'and on one GPU the other configurations, sizes, precisions and the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
     ap.add_argument('--cpu-budget', type=float, default=20.0)
     ap.add_argument('--guided', action='store_true',
                     help="make BASELINE config #3 (full model + bond-predictor 'uncertainty' guidance) the headline instead of "
-                         "config #2; by default config #3 is reported under configs.guided of the same line")
-    ap.add_argument('--headline-only', action='store_true', help='skip the extra single-GPU measurements (configs, sample(), B=2048)')
-    args = ap.parse_args()
+                         "config #2; with --full config #3 is otherwise reported under configs.guided of the same line")
+    ap.add_argument('--headline-only', action='store_true',
+                    help='with --full: skip the extra single-GPU measurements (configs, sample(), B=2048)')
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     world, rank, local_rank = launch_env(args.gpus)
     own_stdout()
@@ -784,11 +830,11 @@ def main():
     dev_index = local_rank if backend == 'nccl' else local_rank % torch.cuda.device_count()
     torch.cuda.set_device(dev_index)
     dev = torch.device('cuda', dev_index)
-    # The group is created for ONE rank too (round 4): the N = 1 line then runs the same RCCL code as N = 8 -- communicator
-    # setup, the max-over-ranks all-reduce, the end-of-run gather on device tensors -- instead of skipping it.  A single rank
-    # whose group cannot be created (no RCCL on the box) still reports its line, with `backend` saying why.
-    dist, backend_note = None, None
-    if world > 1 or backend != 'none':
+    # With --full the group is created for ONE rank too (round 4): the N = 1 line then runs the same RCCL code as N = 8 --
+    # communicator setup, the max-over-ranks all-reduce, the end-of-run gather on device tensors -- instead of skipping it.  A single
+    # rank whose group cannot be created (no RCCL on the box) still reports its line, with `backend` saying why.
+    dist, backend_note = None, (None if args.full else 'none (single rank; the one-rank group is created under --full)')
+    if world > 1 or (args.full and backend != 'none'):
         import torch.distributed as dist
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
@@ -849,11 +895,11 @@ def main():
     sizes_head = torch.bincount(ph_cpu['batch_node'], minlength=args.batch).numpy()
     N, E = sm.N, 2 * sm.Eh
     # Timed region: only the roofline kernel (edge kernel A) carries hipEvent brackets -- 25 event pairs per step on every kernel
-    # cost 0.17 ms of a 7.3 ms step (tools/profile_overhead.py).  The other kernels' durations come from a short second pass
-    # OUTSIDE the timed region (same chain, continued).
+    # cost 0.17 ms of a 7.3 ms step (tools/profile_overhead.py).  With --full the other kernels' durations come from a short second
+    # pass OUTSIDE the timed region (same chain, continued after the outputs are checked and written).
     elapsed, prof = run_chain(sm, args.steps, args.warmup, barrier, prof=2 << 0, whole_run=whole)
-    _, prof_all = run_chain(sm, min(args.steps, 40), 0, barrier, start=args.steps + args.warmup)
-    steps_all = min(args.steps, 40)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(sm), args.dump_outputs)
     multi = None
     if dist is not None:
         comm_dev = dev if backend == 'nccl' else torch.device('cpu')
@@ -863,6 +909,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+        multi = {'ranks_seen': dist.get_world_size(), 'backend': 'rccl (torch "nccl")' if backend == 'nccl' else backend,
+                 'per_rank_ms_per_step': [float(x.item()) for x in per_rank]}
+    if dist is not None and args.full:
         # the path's ONLY data collective: the end-of-run gather of every rank's last-step predictions to rank 0
         # (moldiff_amd/distributed.gather_pred = what sample_drug3d does once per batch).  Timed twice, outside the step
         # loop's timed region: the first call pays the communicator's lazy setup, the second is the steady cost.
@@ -881,12 +930,10 @@ def main():
         dist.all_reduce(nrows)
         if rank == 0:
             assert got[0].shape[0] == int(nrows[0]) and got[2].shape[0] == int(nrows[1]), 'gather_pred lost rows'
-        multi = {'ranks_seen': dist.get_world_size(), 'backend': 'rccl (torch "nccl")' if backend == 'nccl' else backend,
-                 'per_rank_ms_per_step': [float(x.item()) for x in per_rank], 'gather_first_ms': gt[0], 'gather_ms': gt[1],
-                 'gather_rows': [int(nrows[0]), int(nrows[1])],
-                 'gather_bytes': int(nrows[0]) * (8 + 3) * 4 + int(nrows[1]) * 6 * 4,
-                 'gather_what': 'one distributed.gather_pred of all ranks\' last-step predictions to rank 0 (1 count all_gather + ONE padded '
-                                'gather-to-rank-0 of a flat buffer holding all three tensors), max over ranks; happens once per 1000-step run, outside ms_per_step'}
+        multi.update({'gather_first_ms': gt[0], 'gather_ms': gt[1], 'gather_rows': [int(nrows[0]), int(nrows[1])],
+                      'gather_bytes': int(nrows[0]) * (8 + 3) * 4 + int(nrows[1]) * 6 * 4,
+                      'gather_what': 'one distributed.gather_pred of all ranks\' last-step predictions to rank 0 (1 count all_gather + ONE padded '
+                                     'gather-to-rank-0 of a flat buffer holding all three tensors), max over ranks; happens once per 1000-step run, outside ms_per_step'})
     ms_per_step = elapsed / args.steps * 1e3
     value = args.batch * world / (ms_per_step * T_STEPS / 1e3)
     # a timing of garbage is worth nothing: after the timed region, every rank checks what its chain left behind
@@ -897,13 +944,18 @@ def main():
     if not ok:
         raise SystemExit('bench.py: rank %d: the chain left non-finite predictions / positions or a state that is not one-hot after '
                          '%d steps -- no line is reported for that' % (rank, args.steps + args.warmup))
+    steps_all, prof_all = 0, {}
+    if args.full:
+        steps_all = min(args.steps, 40)
+        _, prof_all = run_chain(sm, steps_all, 0, barrier, start=args.steps + args.warmup)
 
     out = None
     if rank == 0:
         head = config_line(head_kind, sm, args.steps, args.warmup, elapsed, prof, world)
         head['kernel_ms_per_step'] = dict({k: v[1] / steps_all for k, v in prof_all.items() if v[0]}, edge_a=prof['edge_a'][1] / args.steps)
         head['kernel_ms_note'] = ('edge_a: hipEvents inside the timed region; the others: a %d-step pass right after it (event pairs on '
-                                  'every kernel would add 0.17 ms to each timed step)' % steps_all)
+                                  'every kernel would add 0.17 ms to each timed step)' % steps_all if args.full else
+                                  'edge_a: hipEvents inside the timed region; the other kernels are timed under --full')
         out = {
             'metric': 'molecules/sec (1000-step GEOM-Drugs sampling)', 'value': value, 'unit': 'molecules/sec',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
@@ -914,23 +966,26 @@ def main():
                                         'set-up (graph plan, buffers)' if whole else
                                         '%d iterations of the reverse chain, trajectory frames recorded as in MolDiff.sample' % args.steps)},
             'roofline': roofline_mfma('edge_a', EDGE_A_NAME, FLOP_EDGE_A, E, prof),
-            'roofline_edge_b': roofline_mfma('edge_b', EDGE_B_NAME, FLOP_EDGE_B, E, prof_all),
-            'aggregation': aggregation_line(N, E, prof_all, sizes_head, True),
             'kernel_ms_per_step': head['kernel_ms_per_step'], 'kernel_ms_note': head['kernel_ms_note'],
             'ranks_seen': 1, 'backend': backend_note or 'none',
             'outputs_checked': 'after the timed region, on every rank: predictions and positions finite, |pos| < 1e3, atom / bond states one-hot',
         }
+        if args.full:
+            out['roofline_edge_b'] = roofline_mfma('edge_b', EDGE_B_NAME, FLOP_EDGE_B, E, prof_all)
+            out['aggregation'] = aggregation_line(N, E, prof_all, sizes_head, True)
         from moldiff_amd import _lib as _lp
         if _lp.resolve_matrix_path(None) != 'exact_f32':
             # MOLDIFF_MATRIX_PATH selected the opt-in split path for the WHOLE run (profiling / A-B use; never the driver's command):
             # say so on the line instead of reporting split numbers under the exact path's labels
             out['dtype'], out['matrix_path'] = SPLIT_DTYPE, _lp.resolve_matrix_path(None)
             out['roofline'] = roofline_split('edge_a', 'edge_a2s_kernel (split float16 build of edge kernel A)', FLOP_EDGE_A, E, prof)
-            out['roofline_edge_b'] = roofline_split('edge_b', 'edge_b2s_kernel (split float16 build of edge kernel B)', FLOP_EDGE_B, E, prof_all)
+            if args.full:
+                out['roofline_edge_b'] = roofline_split('edge_b', 'edge_b2s_kernel (split float16 build of edge kernel B)', FLOP_EDGE_B, E, prof_all)
         if multi is not None:
             out.update(multi)
-            # a complete 1000-step run of every rank plus the gather, i.e. what the entry point's batch loop costs
-            out['value_incl_gather'] = args.batch * world / (ms_per_step * T_STEPS / 1e3 + multi['gather_ms'] / 1e3)
+            if 'gather_ms' in multi:
+                # a complete 1000-step run of every rank plus the gather, i.e. what the entry point's batch loop costs
+                out['value_incl_gather'] = args.batch * world / (ms_per_step * T_STEPS / 1e3 + multi['gather_ms'] / 1e3)
         # HBM traffic per launch comes from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in their own runs,
         # gfx950 correction applied) committed under profiles/; a Python process cannot collect PMCs on itself.  The figure is
         # quoted only when the summary was taken with THIS build's kernels (the library names the kernel each timing slot
@@ -940,7 +995,9 @@ def main():
             from moldiff_amd import _lib
             L = _lib.lib()
             name_a, name_g = (L.mdx_profile_kernel_name(k).decode() for k in (0, 3))
-            out['roofline']['kernel_symbol'], out['aggregation']['kernel_symbol'] = name_a, name_g
+            out['roofline']['kernel_symbol'] = name_a
+            if 'aggregation' in out:
+                out['aggregation']['kernel_symbol'] = name_g
             # newest summary of THIS configuration first: the round-4 directory also holds summaries of the guided step and of the
             # split-float16 build, which know other kernels
             pm = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_summary.json')))
@@ -954,7 +1011,7 @@ def main():
                     out['roofline']['traffic_source'] = src + ' (PMC passes of the same command; not measured in this run)'
                 else:
                     out['roofline']['traffic_source'] = f'refused: {src} has no kernel {name_a} (taken with another kernel set: {sorted(ks)})'
-                if name_g in ks:
+                if name_g in ks and 'aggregation' in out:
                     out['aggregation']['traffic'] = ks[name_g]['hbm_bytes_per_launch']
         except Exception:
             pass
@@ -966,7 +1023,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         dist = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and args.full and not args.headline_only:
         configs = {'guided' if args.guided else 'simple': dict(head, roofline=out['roofline'])}
         out['segment_sum'] = segment_sum_line(sm, dev)
         other_kind = 'MolDiff_simple' if args.guided else 'MolDiff'

@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,3 +100,37 @@ def test_round6_tree_keeps_the_training_probe_on_the_line():
     full['configs']['train']['loss_fixed_probe_before_after'] = ['RuntimeError(' + 'x' * 500 + ')'] * 2      # a failed probe: clipped text
     line = bench.compact_line(full)
     assert len(json.dumps(line)) < bench.LINE_LIMIT and all(len(x) <= 40 for x in line['configs']['train']['loss_fixed_probe'])
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    a = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(['--full', '--dump-outputs', 'out', '--no-cpu-baseline'])
+    assert a.full and a.dump_outputs == 'out' and a.no_cpu_baseline
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    g = np.random.Generator(np.random.PCG64(1))
+    arrays = {'pred_pos': g.standard_normal((50, 3)).astype(np.float32), 'ids': np.arange(12, dtype=np.int64),
+              'wide': g.standard_normal((7, 2))}
+    bench.dump_outputs(arrays, str(tmp_path / 'd'))
+    assert sorted(os.listdir(tmp_path / 'd')) == ['ids.npy', 'pred_pos.npy', 'wide.npy']
+    back = {k: np.load(tmp_path / 'd' / (k + '.npy')) for k in arrays}
+    assert back['pred_pos'].dtype == np.float32 and np.array_equal(back['pred_pos'], arrays['pred_pos'])
+    assert back['ids'].dtype == np.float32 and np.array_equal(back['ids'], np.arange(12))
+    assert back['wide'].dtype == np.float64 and np.array_equal(back['wide'], arrays['wide'])
+
+
+def test_dump_outputs_samples_the_same_rows_above_the_limit(tmp_path):
+    big = {'a': np.arange(4000 * 8, dtype=np.float32).reshape(4000, 8), 'b': np.ones((4000, 3), np.float32)}
+    limit = 20000
+    for d in ('x', 'y'):
+        bench.dump_outputs(big, str(tmp_path / d), limit=limit)
+    files = sorted(os.listdir(tmp_path / 'x'))
+    assert files == ['a.npy', 'a.rows.npy', 'b.npy', 'b.rows.npy']
+    assert sum(os.path.getsize(tmp_path / 'x' / f) for f in ('a.npy', 'b.npy')) <= limit + 2 * 128     # .npy headers
+    for f in files:
+        x, y = np.load(tmp_path / 'x' / f), np.load(tmp_path / 'y' / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    rows = np.load(tmp_path / 'x' / 'a.rows.npy').astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 'x' / 'a.npy'), big['a'][rows])

@@ -148,7 +148,7 @@ def test_bench_headline_line_comes_from_a_real_rccl_group():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'MDX_BENCH_BACKEND'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--batch', '32',
-                        '--headline-only', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        '--full', '--headline-only', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['ranks_seen'] == 1 and line['backend'].startswith('rccl'), line.get('backend')

@@ -249,7 +249,7 @@ def test_bench_two_ranks_over_rccl_when_two_gpus_are_visible():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'MDX_BENCH_BACKEND'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '16',
-                        '--headline-only'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        '--full', '--headline-only'], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['ranks_seen'] == 2 and line['backend'].startswith('rccl')

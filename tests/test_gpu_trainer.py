@@ -1,4 +1,6 @@
 """Optimizer step and whole training steps on the GPU (reference: scripts/train_drug3d.py:88-109, utils/train.py:64-70)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -9,6 +11,7 @@ from moldiff_amd.trainer import Trainer, FlatParams
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_clip_and_adamw_kernels_match_torch_optim():
@@ -137,7 +140,7 @@ def test_train_entry_point_end_to_end(tmp_path, use_amp):
     iterations; steps + skipped = iterations, and the scale ends at 65536 / 2^skipped."""
     import yaml
     from moldiff_amd import train_drug3d, MolDiff
-    cfg = yaml.safe_load(open('configs/train_MolDiff_simple.yml'))
+    cfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', 'train_MolDiff_simple.yml')))
     iters = 12 if use_amp else 4
     cfg['train'].update(batch_size=6, max_iters=iters, val_freq=iters // 2, use_amp=use_amp)
     p = tmp_path / 'cfg.yml'
@@ -167,7 +170,7 @@ def test_train_entry_point_on_processed_records(tmp_path):
     from moldiff_amd.data import synthetic_records
     recs = synthetic_records(24, seed=9)
     torch.save({'train': recs[:20], 'val': recs[20:]}, tmp_path / 'records.pt')
-    cfg = yaml.safe_load(open('configs/train_MolDiff_simple.yml'))
+    cfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', 'train_MolDiff_simple.yml')))
     cfg['train'].update(batch_size=5, max_iters=3, val_freq=3)
     cfg['dataset'] = {'name': 'records', 'path': str(tmp_path / 'records.pt')}
     p = tmp_path / 'cfg.yml'
@@ -224,13 +227,13 @@ def test_checkpoint_written_by_training_is_sampled_by_the_sampling_entry_point(t
     """train_drug3d -> checkpoints/<it>.pt -> sample_drug3d --config (model.checkpoint = that file): the loop closes."""
     import yaml
     from moldiff_amd import sample_drug3d, train_drug3d
-    cfg = yaml.safe_load(open('configs/train_MolDiff_simple.yml'))
+    cfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', 'train_MolDiff_simple.yml')))
     cfg['train'].update(batch_size=4, max_iters=2, val_freq=2)
     tp = tmp_path / 'train.yml'
     tp.write_text(yaml.safe_dump(cfg))
     assert train_drug3d.main(['--config', str(tp), '--device', DEV, '--logdir', str(tmp_path / 'logs'), '--val_batches', '1',
                               '--recipe-weights']) == 0
-    scfg = yaml.safe_load(open('configs/sample_MolDiff_simple.yml'))
+    scfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', 'sample_MolDiff_simple.yml')))
     scfg['model']['checkpoint'] = str(tmp_path / 'logs' / 'checkpoints' / '2.pt')
     scfg['sample'].update(num_mols=3, batch_size=3)
     sp = tmp_path / 'sample.yml'

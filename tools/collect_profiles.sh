@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): bash tools/collect_profiles.sh r3   -> gpurun_out/<tag>_* (copy what is to be judged into profiles/)
 # One pass per evidence kind, never a PMC pass together with a trace domain:
-#   <tag>_bench.json                      python bench.py (the driver's command)
+#   <tag>_bench.json                      python bench.py --full (every configuration on one line)
 #   <tag>_kernel_stats.csv                rocprofv3 --kernel-trace --stats over bench.py --steps 95 --headline-only      (config #2)
 #   <tag>_bench_under_rocprof.json        the JSON line of that same run (its hipEvent durations must agree with the csv)
 #   <tag>_guided_kernel_stats.csv         the same with --guided                                                          (config #3)
@@ -13,7 +13,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python $ROOT/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 for cfg in simple guided; do
   flag=""; name=${TAG}_kernel_stats; jn=${TAG}_bench_under_rocprof
   if [ $cfg = guided ]; then flag="--guided"; name=${TAG}_guided_kernel_stats; jn=${TAG}_guided_bench_under_rocprof; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box, via gpurun, from the repo root): bash tools/collect_r4.sh   -> gpurun_out/r4_*  (copy what is to be judged into profiles/)
 # Everything profiles/r4_* holds, taken at one HEAD on one box.  One pass per evidence kind; PMC passes never share a run with a trace.
-#   r4_bench.json                              python bench.py -- the driver's command (exact headline + configs.{simple,guided,simple_split,guided_split,train})
+#   r4_bench.json                              python bench.py --full -- the driver's command of round 4 (exact headline + configs.{simple,guided,simple_split,guided_split,train})
 #   r4_kernel_stats.csv / r4_guided_*          rocprofv3 --kernel-trace --stats, exact fp32 path (configs #2 / #3), + the JSON line of the same run
 #   r4_split_kernel_stats.csv / r4_split_guided_*   the same with MOLDIFF_MATRIX_PATH=split_f16
 #   r4_pmc_summary.json / r4_split_pmc_summary.json / r4_guided_* / r4_split_guided_*   tools/pmc_summary.py: three separate --pmc passes each
@@ -12,7 +12,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py > $OUT/r4_bench.json 2> $OUT/r4_bench.err
+python $ROOT/bench.py --full > $OUT/r4_bench.json 2> $OUT/r4_bench.err
 for path in exact_f32 split_f16; do
   for cfg in simple guided; do
     pre=r4_; [ $path = split_f16 ] && pre=r4_split_

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box, via gpurun, from the repo root): bash tools/collect_r5.sh   -> gpurun_out/r5_*  (copy what is to be judged into profiles/)
 # Everything profiles/r5_* holds, taken at one HEAD on one box.  One pass per evidence kind; PMC passes never share a run with a trace.
-#   r5_bench.json                              python bench.py -- the driver's command (exact headline + configs.{simple,guided,simple_split,guided_split,guided_mixed,train})
+#   r5_bench.json                              python bench.py --full -- the driver's command of round 5 (exact headline + configs.{simple,guided,simple_split,guided_split,guided_mixed,train})
 #   r5_kernel_stats.csv / r5_guided_*          rocprofv3 --kernel-trace --stats, exact fp32 path (configs #2 / #3), + the JSON line of the same run
 #   r5_split_kernel_stats.csv / r5_split_guided_*   the same with MOLDIFF_MATRIX_PATH=split_f16
 #   r5_pmc_summary.json / r5_split_pmc_summary.json / r5_guided_* / r5_split_guided_*   tools/pmc_summary.py: three separate --pmc passes each
@@ -12,7 +12,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py > $OUT/r5_bench.json 2> $OUT/r5_bench.err
+python $ROOT/bench.py --full > $OUT/r5_bench.json 2> $OUT/r5_bench.err
 for path in exact_f32 split_f16; do
   for cfg in simple guided; do
     pre=r5_; [ $path = split_f16 ] && pre=r5_split_

@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage (GPU box, via gpurun, from the repo root): bash tools/collect_r6.sh   -> gpurun_out/r6_*  (copy what is to be judged into profiles/)
 # Everything profiles/r6_* holds, taken at one HEAD on one box.  One pass per evidence kind; PMC passes never share a run with a trace.
-#   r6_bench.json / r6_bench_full.json         python bench.py (default: one whole 1000-step run) -- the stdout line (<= 6 KB) and the full tree
-#   r6_bench_driver.json                       python bench.py --gpus 1 --steps 20 --warmup 5 -- the driver's command
+#   r6_bench.json / r6_bench_full.json         python bench.py --full (default: one whole 1000-step run) -- the stdout line (<= 6 KB) and the full tree
+#   r6_bench_driver.json                       python bench.py --gpus 1 --steps 20 --warmup 5 --full -- the driver's command of round 6
 #   r6_kernel_stats.csv / r6_guided_*          rocprofv3 --kernel-trace --stats, exact fp32 path (configs #2 / #3), + the JSON line of the same run
 #   r6_pmc_summary.json / r6_guided_pmc_summary.json    tools/pmc_summary.py: three separate --pmc passes each
 #   r6_train_fp16_kernel_stats.csv             kernel statistics of 10 fp16 training steps (fused EdgeBlock kernels on) + the unfused twin
@@ -14,9 +14,9 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py > $OUT/r6_bench.json 2> $OUT/r6_bench.err
+python $ROOT/bench.py --full > $OUT/r6_bench.json 2> $OUT/r6_bench.err
 cp $ROOT/bench_full.json $OUT/r6_bench_full.json
-python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r6_bench_driver.json 2> /dev/null
+python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/r6_bench_driver.json 2> /dev/null
 for cfg in simple guided; do
   flag=""; name=r6_kernel_stats; jn=r6_bench_under_rocprof
   if [ $cfg = guided ]; then flag="--guided"; name=r6_guided_kernel_stats; jn=r6_guided_bench_under_rocprof; fi
