@@ -245,7 +245,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void BW_KERNEL(const EdgeBwdArgs a
 #pragma unroll
       for (int ft = 0; ft < 4; ++ft)
 #pragma unroll
-        for (int rt = 0; rt < RR; ++rt) sgt[ft][rt] = row_sigmoid4(sgt[ft][rt]);
+        for (int rt = 0; rt < RR; ++rt) sgt[ft][rt] = fast_sigmoid4(sgt[ft][rt]);
       STAMPW(14 + 3 * s);
       // backward: f = o * sigmoid(gate);  gf = A[oidx]
       f32x4 go[4][RR];

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void edge_a2s_kernel(const EdgeAAr
       for (int ft = 0; ft < 16; ++ft)
 #pragma unroll
         for (int rt = 0; rt < RR; ++rt) {
-          const f32x4 sg = row_sigmoid4(z[ft][rt]);
+          const f32x4 sg = fast_sigmoid4(z[ft][rt]);
           if (a.tSG && t.valid[rt]) TAPE_ST(a.tSG + (size_t)t.row[rt] * MDX_ND + 16 * ft + 4 * q, sg);
           park[(ft * RR + rt) * 64] = sg;
         }
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void edge_a2s_kernel(const EdgeAAr
 #pragma unroll
         for (int ft = 0; ft < 4; ++ft)
 #pragma unroll
-          for (int rt = 0; rt < RR; ++rt) o[ft][rt] = o[ft][rt] * row_sigmoid4(g2[ft][rt]);
+          for (int rt = 0; rt < RR; ++rt) o[ft][rt] = o[ft][rt] * fast_sigmoid4(g2[ft][rt]);
         if constexpr (do_agg) {
           if (s == 1) {
             if (a.F[1]) row_store<4, RR>(o, a.F[1], t.row, t.valid, 64, q);

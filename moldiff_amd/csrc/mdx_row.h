@@ -19,10 +19,6 @@
 #include <type_traits>
 #include "mdx_tile.h"
 
-#ifndef MDX_ABL
-#define MDX_ABL 0  // timing-only ablations (wrong results): 1 no stores, 2 no row gathers, 4 weight stream served from L1, 8 / 16 / 32 (split
-                   // kernels, mdx_split.h): no operand conversion arithmetic / one MFMA in eight / no weight loads at all
-#endif
 #ifndef MDX_RING
 #define MDX_RING 2  // steps (2 KiB each) of the weight stream in flight per wave
 #endif
@@ -50,7 +46,6 @@ __device__ __forceinline__ f32x4 ws_frag(const WS& w, int frag) {
 // first MDX_RING steps of a stream (every stream pack ends in MDX_RING_PAD zero steps, so priming a stream shorter than the
 // ring stays in bounds)
 __device__ __forceinline__ void ring_prime(WRing& r, const WS& w) {
-  if (MDX_ABL & 32) return;  // timing-only ablation: no weight loads at all (the ring keeps whatever it held)
 #pragma unroll
   for (int p = 0; p < MDX_RING; ++p) {
     r.a[p][0] = ws_frag(w, 2 * p);
@@ -68,10 +63,6 @@ __device__ __forceinline__ f32x4 fast_sigmoid4(f32x4 v) {
   f32x4 r = {fast_sigmoid(v[0]), fast_sigmoid(v[1]), fast_sigmoid(v[2]), fast_sigmoid(v[3])};
   return r;
 }
-#ifndef MDX_FAST_SIGMOID
-#define MDX_FAST_SIGMOID 1
-#endif
-__device__ __forceinline__ f32x4 row_sigmoid4(f32x4 v) { return MDX_FAST_SIGMOID ? fast_sigmoid4(v) : sigmoid4(v); }
 
 struct NoHook {
   template <class P>
@@ -96,8 +87,8 @@ __device__ __forceinline__ void rgemm(f32x4 (&y)[FT][R], const f32x4 (&x)[KG][R]
     constexpr int ftp = p / KG, g = p % KG;
     const f32x4 a0 = ring.a[p % MDX_RING][0], a1 = ring.a[p % MDX_RING][1];
     if constexpr (p + MDX_RING < NP) {
-      ring.a[p % MDX_RING][0] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING));
-      ring.a[p % MDX_RING][1] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING) + 1);
+      ring.a[p % MDX_RING][0] = ws_frag(w, 2 * (p + MDX_RING));
+      ring.a[p % MDX_RING][1] = ws_frag(w, 2 * (p + MDX_RING) + 1);
     }
     if constexpr (p == PRIME_AT) ring_prime(nx, wnext);
     hook(pc);
@@ -145,7 +136,7 @@ template <int FT, int R>
 __device__ __forceinline__ void row_gather(f32x4 (&v)[FT][R], const float* __restrict__ base, const int (&idx)[R], int ld, int q) {
 #pragma unroll
   for (int rt = 0; rt < R; ++rt) {
-    const float* p = base + (size_t)((MDX_ABL & 2) ? 0 : idx[rt]) * ld + 4 * q;
+    const float* p = base + (size_t)idx[rt] * ld + 4 * q;
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) v[ft][rt] = ldg4(p + 16 * ft);
   }
@@ -158,7 +149,7 @@ __device__ __forceinline__ void row_store(const f32x4 (&v)[FT][R], float* __rest
                                           const bool (&valid)[R], int ld, int q) {
 #pragma unroll
   for (int rt = 0; rt < R; ++rt) {
-    if (!valid[rt] || (MDX_ABL & 1)) continue;
+    if (!valid[rt]) continue;
     float* p = base + (size_t)row[rt] * ld + 4 * q;
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
@@ -425,7 +416,7 @@ __device__ __forceinline__ void seg_sum_flush(float* wbuf, int lane, int cnt, in
           acc = acc + v[r - RB * h];
           if (r + 1 == cnt || k_next != k_r) {  // last row of a run
             const int row = __builtin_amdgcn_readlane(prow, r);
-            if ((C4 == 64 || lane < C4) && !(MDX_ABL & 1)) stg4(out + (size_t)row * (16 * FT) + 4 * col, acc);
+            if (C4 == 64 || lane < C4) stg4(out + (size_t)row * (16 * FT) + 4 * col, acc);
             acc = splat4(0.f);
           }
         }

@@ -56,11 +56,6 @@ __device__ __forceinline__ void to_xs(XS<(FT + 1) / 2>& o, const f32x4 (&y)[FT][
       for (int t = 0; t < 8; ++t) {
         const int ft = 2 * g + t / 4;
         const float v = ft < FT ? y[ft][rt][t % 4] : 0.f;
-        if (MDX_ABL & 8) {  // timing-only ablation: no conversion arithmetic (wrong results)
-          o.hi[g][rt][t] = __builtin_bit_cast(_Float16, (unsigned short)(__float_as_uint(v) >> 16));
-          o.lo[g][rt][t] = __builtin_bit_cast(_Float16, (unsigned short)(__float_as_uint(v)));
-          continue;
-        }
         const _Float16 h = (_Float16)v;
         o.hi[g][rt][t] = h;
         o.lo[g][rt][t] = (_Float16)((v - (float)h) * MDX_LO_UP);
@@ -85,9 +80,9 @@ __device__ __forceinline__ void rgemm_s_primed(f32x4 (&y)[FT][RR], const XS<KG>&
     constexpr int p = decltype(pc)::value;
     constexpr int ftp = p / (2 * KG), g = (p / 2) % KG, h = p % 2;
     const h8 a0 = __builtin_bit_cast(h8, ring.a[p % MDX_RING][0]), a1 = __builtin_bit_cast(h8, ring.a[p % MDX_RING][1]);
-    if constexpr (p + MDX_RING < NP && !(MDX_ABL & 32)) {
-      ring.a[p % MDX_RING][0] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING));
-      ring.a[p % MDX_RING][1] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING) + 1);
+    if constexpr (p + MDX_RING < NP) {
+      ring.a[p % MDX_RING][0] = ws_frag(w, 2 * (p + MDX_RING));
+      ring.a[p % MDX_RING][1] = ws_frag(w, 2 * (p + MDX_RING) + 1);
     }
     if constexpr (p == PRIME_AT) ring_prime(nx, wnext);
     if constexpr (g == 0 && h == 0) {
@@ -95,7 +90,6 @@ __device__ __forceinline__ void rgemm_s_primed(f32x4 (&y)[FT][RR], const XS<KG>&
       for (int rt = 0; rt < RR; ++rt) t0[rt] = t1[rt] = u0[rt] = u1[rt] = splat4(0.f);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr ((MDX_ABL & 16) != 0 && (p % 8) != 0) return;  // timing-only ablation: 1/8 of the MFMAs
     // MFMAs on the same accumulator are kept two instructions apart
     if constexpr (h == 0) {
 #pragma unroll
@@ -163,14 +157,12 @@ __device__ __forceinline__ void rgemm_s_seamless(f32x4 (&y)[FT][RR], const XS<KG
     constexpr int p = decltype(pc)::value;
     constexpr int ftp = p / (2 * KG), g = (p / 2) % KG, h = p % 2;
     const h8 a0 = __builtin_bit_cast(h8, ring.a[p % MDX_RING][0]), a1 = __builtin_bit_cast(h8, ring.a[p % MDX_RING][1]);
-    if constexpr (!(MDX_ABL & 32)) {
-      if constexpr (p + MDX_RING < NPL) {
-        ring.a[p % MDX_RING][0] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING));
-        ring.a[p % MDX_RING][1] = ws_frag(w, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING) + 1);
-      } else {
-        ring.a[p % MDX_RING][0] = ws_frag(wnext, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING - NPL));
-        ring.a[p % MDX_RING][1] = ws_frag(wnext, 2 * ((MDX_ABL & 4) ? p % 4 : p + MDX_RING - NPL) + 1);
-      }
+    if constexpr (p + MDX_RING < NPL) {
+      ring.a[p % MDX_RING][0] = ws_frag(w, 2 * (p + MDX_RING));
+      ring.a[p % MDX_RING][1] = ws_frag(w, 2 * (p + MDX_RING) + 1);
+    } else {
+      ring.a[p % MDX_RING][0] = ws_frag(wnext, 2 * (p + MDX_RING - NPL));
+      ring.a[p % MDX_RING][1] = ws_frag(wnext, 2 * (p + MDX_RING - NPL) + 1);
     }
     if constexpr (p >= NP) return;  // idle step
     if constexpr (g == 0 && h == 0) {
@@ -178,7 +170,6 @@ __device__ __forceinline__ void rgemm_s_seamless(f32x4 (&y)[FT][RR], const XS<KG
       for (int rt = 0; rt < RR; ++rt) t0[rt] = t1[rt] = splat4(0.f);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr ((MDX_ABL & 16) != 0 && (p % 8) != 0) return;
     if constexpr (h == 0) {
 #pragma unroll
       for (int rt = 0; rt < RR; ++rt) {

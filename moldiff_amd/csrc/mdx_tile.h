@@ -21,9 +21,6 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define MDX_WG 256
-#ifndef MDX_GEMM_PINNED
-#define MDX_GEMM_PINNED 1  // pin the two-stage prefetch of gemm_tile with sched_barriers (A/B in DESIGN.md)
-#endif
 #define MDX_LN_EPS 1e-5f
 
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -117,10 +114,6 @@ __device__ __forceinline__ void gemm_tile_impl(f32x4 (&acc)[FTW][ET], f32x4 (&a0
     if constexpr (g + D - 1 < G) load_a(a[(g + D - 1) % D], g + D - 1);
     if constexpr (g + 1 < G) load_b(b[(g + 1) & 1], g + 1);
     __builtin_amdgcn_sched_barrier(0);
-#ifdef MDX_TILE_ABL_MFMA  // timing-only ablation (wrong results): one MFMA in eight
-    if constexpr (g % 2 == 0)
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g % D][0][0], b[g & 1][0][0], acc[0][0], 0, 0, 0);
-#else
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -128,7 +121,6 @@ __device__ __forceinline__ void gemm_tile_impl(f32x4 (&acc)[FTW][ET], f32x4 (&a0
 #pragma unroll
         for (int et = 0; et < ET; ++et)
           acc[ft][et] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g % D][ft][s], b[g & 1][et][s], acc[ft][et], 0, 0, 0);
-#endif
     __builtin_amdgcn_sched_barrier(0);
   });
 }
@@ -149,11 +141,7 @@ __device__ __forceinline__ void gemm_tile_impl(f32x4 (&acc)[FTW][ET], f32x4 (&a0
   f32x4 a1[FTW], b0[ET], b1[ET];
   auto load_a = [&](f32x4(&a)[FTW], int g) {
 #pragma unroll
-#ifdef MDX_ABL_WL1  // ablation: every group re-reads group 0 (weights stay in L1); results are wrong, timing only
-    for (int ft = 0; ft < FTW; ++ft) a[ft] = wp[((size_t)(g & 0) * FT + ft) * 64];
-#else
     for (int ft = 0; ft < FTW; ++ft) a[ft] = wp[((size_t)g * FT + ft) * 64];
-#endif
   };
   auto load_b = [&](f32x4(&b)[ET], int g) {
 #pragma unroll
@@ -176,24 +164,16 @@ __device__ __forceinline__ void gemm_tile_impl(f32x4 (&acc)[FTW][ET], f32x4 (&a0
       load_a(a1, g + 1);
       load_b(b1, g + 1);
     }
-#if MDX_GEMM_PINNED
     __builtin_amdgcn_sched_barrier(0);
-#endif
     mfma_group(a0, b0);
-#if MDX_GEMM_PINNED
     __builtin_amdgcn_sched_barrier(0);
-#endif
     if (g + 2 < G) {
       load_a(a0, g + 2);
       load_b(b0, g + 2);
     }
-#if MDX_GEMM_PINNED
     __builtin_amdgcn_sched_barrier(0);
-#endif
     if (g + 1 < G) mfma_group(a1, b1);
-#if MDX_GEMM_PINNED
     __builtin_amdgcn_sched_barrier(0);
-#endif
   }
 }
 

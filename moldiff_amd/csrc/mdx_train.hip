@@ -210,7 +210,6 @@ __device__ __forceinline__ uint16_t to_bf16(float a) {
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
-__device__ __forceinline__ bf16x8_t lds_bf16x8(const uint16_t* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
 // The low-precision operand type of the mixed-precision GEMMs: HT = 0 bfloat16 (round 2's mode), HT = 1 IEEE half -- the type the
 // reference's torch.autocast(dtype=torch.float16) casts Linear operands to (scripts/train_drug3d.py:93).  cvt rounds to nearest
 // even; a float16 overflows to infinity beyond 65504 like the cast autocast inserts (GradScaler's found_inf then skips the step).
@@ -580,93 +579,6 @@ static void launch_hgemm_nt_rows(const _Float16* A, int lda, const float* B, int
                      ln);
 }
 
-#ifdef MDX_EXPERIMENTAL
-// EXPERIMENT (tools/ubench_bf16x3.py): fp32 product emulated with three-way bf16 splits x = h + m + l (each piece
-// exactly representable, so x is reproduced to 24 bits); six of the nine cross products (h*h, h*m, m*h, m*m, h*l, l*h;
-// the dropped ones are below 2^-32 relative) run on the bf16 matrix pipe, smallest first, fp32 accumulation.  Measures
-// what an "fp32-accurate" GEMM costs on the 16x faster pipe; not used by any product path.
-constexpr int H3_KC = 32, H3_LD = H3_KC + 8;
-__device__ __forceinline__ void split3(float x, uint16_t& h, uint16_t& m, uint16_t& l) {
-  h = to_bf16(x);
-  const float r1 = x - __uint_as_float((uint32_t)h << 16);
-  m = to_bf16(r1);
-  const float r2 = r1 - __uint_as_float((uint32_t)m << 16);
-  l = to_bf16(r2);
-}
-__global__ __launch_bounds__(256) void hgemm3_nt_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
-                                                         float* __restrict__ C, int ldc, int M, int N, int K) {
-  constexpr int ASZ = G_TM * H3_LD, BSZ = G_TN * H3_LD;
-  __shared__ __attribute__((aligned(16))) uint16_t As[3 * ASZ];   // pieces h, m, l
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[3 * BSZ];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = lane & 15, q = lane >> 4;
-  const int m0 = blockIdx.y * G_TM, n0 = blockIdx.x * G_TN;
-  const bool veca = ((lda & 3) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-  const bool vecb = ((ldb & 3) == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
-  f32x4 acc[4][2];
-  acc_zero<4, 2>(acc);
-  f32x4 ra[4], rb[2];   // 8 float4 per row of 32 k
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int slot = tid + 256 * j, row = slot >> 3, k4 = (slot & 7) * 4;
-      ra[j] = load4_guard(A + (size_t)(m0 + row) * lda, k0 + k4, K, m0 + row < M, veca);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int slot = tid + 256 * j, row = slot >> 3, k4 = (slot & 7) * 4;
-      rb[j] = load4_guard(B + (size_t)(n0 + row) * ldb, k0 + k4, K, n0 + row < N, vecb);
-    }
-  };
-  auto stage = [&](uint16_t* dst, int piece_stride, const f32x4& v, int slot) {
-    uint16_t h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) split3(v[e], h[e], m[e], l[e]);
-    const int o = (slot >> 3) * H3_LD + (slot & 7) * 4;
-    *reinterpret_cast<uint2*>(dst + o) = uint2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
-    *reinterpret_cast<uint2*>(dst + piece_stride + o) = uint2{(uint32_t)m[0] | ((uint32_t)m[1] << 16), (uint32_t)m[2] | ((uint32_t)m[3] << 16)};
-    *reinterpret_cast<uint2*>(dst + 2 * piece_stride + o) = uint2{(uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16)};
-  };
-  if (K > 0) fetch(0);
-  for (int k0 = 0; k0 < K; k0 += H3_KC) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) stage(As, ASZ, ra[j], tid + 256 * j);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) stage(Bs, BSZ, rb[j], tid + 256 * j);
-    __syncthreads();
-    if (k0 + H3_KC < K) fetch(k0 + H3_KC);
-    bf16x8_t a[3][4], b[3][2];   // [piece][tile]: a = features (matrix B), b = rows (matrix A)
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int ft = 0; ft < 4; ++ft) a[p][ft] = lds_bf16x8(Bs + p * BSZ + (16 * ft + c) * H3_LD + 8 * q);
-#pragma unroll
-      for (int et = 0; et < 2; ++et) b[p][et] = lds_bf16x8(As + p * ASZ + (32 * wave + 16 * et + c) * H3_LD + 8 * q);
-    }
-    // smallest terms first: (h,l) (l,h) (m,m) (h,m) (m,h) (h,h); pieces: 0 = h, 1 = m, 2 = l
-    constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-        for (int et = 0; et < 2; ++et)
-          acc[ft][et] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[PA[t]][ft], b[PB[t]][et], acc[ft][et], 0, 0, 0);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-    for (int et = 0; et < 2; ++et)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + 32 * wave + 16 * et + c, col = n0 + 16 * ft + 4 * q + r;
-        if (row < M && col < N) C[(size_t)row * ldc + col] = acc[ft][et][r];
-      }
-}
-
-#endif  // MDX_EXPERIMENTAL
-
 // bf16 weight gradient: 64 rows of G and X per step are transposed into LDS ([column][row], so that the 8 consecutive
 // contraction values a lane needs are one 16-byte read); otherwise the structure of sgemm_tn_split_kernel.
 constexpr int HW_MC = 64;
@@ -969,7 +881,7 @@ __device__ __forceinline__ void wgrad_colsum_body(const TP s_, const TP A_, int 
 }
 
 template <int KIND>
-__global__ __launch_bounds__(256) void wgrad_grouped_kernel(const long long* __restrict__ desc, int n, int xcd_deal) {
+__global__ __launch_bounds__(256) void wgrad_grouped_kernel(const long long* __restrict__ desc, int n) {
   const long long blk = blockIdx.x;
   int lo = 0, hi = n - 1;
   while (lo < hi) {
@@ -982,17 +894,11 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const long long* __r
   // XCD-aware numbering: workgroup ids go round-robin over the 8 XCDs (id % 8) and each XCD has its own L2, so the gx * gy tiles of
   // one row range -- which read the same rows of G and X -- must sit on ids that are EQUAL mod 8, close in dispatch order.  Blocks are
   // dealt in chunks of 8 row ranges: inside a chunk, id i works on row range i % 8 and tile i / 8 (the last, short chunk deals over
-  // what is left).  Which block computes a (tile, row range) does not change its result.  MDX_WGRAD_XCD=0 (xcd_deal = 0): the plain order.
-  int bz, t;
-  const int T = gx * gy;
-  if (xcd_deal && T > 1) {
-    const int S = (int)d[12];
-    const int chunk = rel / (8 * T), i = rel - chunk * 8 * T;
-    const int w = min(8, S - 8 * chunk);
-    bz = 8 * chunk + i % w, t = i / w;
-  } else {
-    bz = rel / T, t = rel - bz * T;
-  }
+  // what is left; with one tile per row range this is the plain order).  Which block computes a (tile, row range) does not change its result.
+  const int T = gx * gy, S = (int)d[12];
+  const int chunk = rel / (8 * T), i = rel - chunk * 8 * T;
+  const int w = min(8, S - 8 * chunk);
+  const int bz = 8 * chunk + i % w, t = i / w;
   const int bx = t % gx, by = t / gx;
   float* P = reinterpret_cast<float*>(d[2]);
   float* Pb = reinterpret_cast<float*>(d[3]);
@@ -2257,15 +2163,13 @@ extern "C" int mdx_op_segsum_rows_t(const void* src, const int64_t* order, const
   const TPW to{out, (dt >> 1) & 1};
   if ((F & 3) == 0 && tp_vec_ok(src, ts.h, 4) && tp_vec_ok(out, to.h, 4)) {
     const size_t items = (size_t)R * (F / 4);
-    static const bool split_off = getenv("MDX_SEGSUM_SPLIT") && atoi(getenv("MDX_SEGSUM_SPLIT")) == 0;
     // float16 rows only: the fp32 mode keeps the sequential CSR order -- the order of torch's index_add on the CPU, i.e. of the reference
     // and the oracle, which its parity tests rely on (a 32-wide LayerNorm gain's gradient moved from 4.8e-5 to 1.6e-4 of its norm at
     // 256 molecules with the dealt order; both are fp32 rounding, but the contract there is 1e-4)
-    static const bool wide_off = getenv("MDX_SEGSUM_WIDE") && atoi(getenv("MDX_SEGSUM_WIDE")) == 0;
-    if (!split_off && !wide_off && ts.h && (F & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && items < ((size_t)1 << 22))
+    if (ts.h && (F & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && items < ((size_t)1 << 22))
       hipLaunchKernelGGL(segsum_rows8s_kernel, dim3((unsigned)(((size_t)R * (F / 8) + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
                          reinterpret_cast<const _Float16*>(src), order, ptr, R, F / 8, to);
-    else if (!split_off && (ts.h || (dt & 4)) && items < ((size_t)1 << 22))
+    else if ((ts.h || (dt & 4)) && items < ((size_t)1 << 22))
       hipLaunchKernelGGL(segsum_rows4s_kernel, dim3((unsigned)((items + 63) / 64)), dim3(256), 0, (hipStream_t)stream, ts, order, ptr, R, F / 4, to);
     else
       hipLaunchKernelGGL(segsum_rows4_kernel, dim3(nblk(items)), dim3(256), 0, (hipStream_t)stream, ts, order, ptr, R, F / 4, to);
@@ -2531,10 +2435,10 @@ extern "C" int mdx_op_xgemm_nt_t(const void* Av, int64_t lda, const float* B, in
   const TPW C{Cv, (dt >> 2) & 1};
   if (half_kind != 1 && half_kind != 2) return bad("xgemm_nt: half_kind must be 1 (bfloat16) or 2 (float16)");
   hipStream_t s = (hipStream_t)stream;
-  // float16 rows, widths the row-owner kernel is instantiated for: whole weight resident in LDS, no K loop over barriers
-  constexpr bool no_rows = false;   // (round 3 A/B knob MDX_HGEMM_ROWS removed: the row-owner kernel is 84 -> 47 us on 256 -> 256)
+  // float16 rows, widths the row-owner kernel is instantiated for: whole weight resident in LDS, no K loop over barriers (measured in
+  // round 3: 84 -> 47 us on 256 -> 256 against the tiled kernel)
   const int kt = (int)(K / 32), ftn = (int)(N / 16);
-  if (!no_rows && half_kind == 2 && A.h && M >= 1024 && K % 32 == 0 && N % 16 == 0 && (kt == 1 || kt == 2 || kt == 4 || kt == 8) &&
+  if (half_kind == 2 && A.h && M >= 1024 && K % 32 == 0 && N % 16 == 0 && (kt == 1 || kt == 2 || kt == 4 || kt == 8) &&
       (ftn == 2 || ftn == 4 || ftn == 8 || ftn == 16) && (lda & 7) == 0 && (reinterpret_cast<uintptr_t>(Av) & 15) == 0) {
     const _Float16* Ah = reinterpret_cast<const _Float16*>(Av);
 #define MDX_HR(KTv, FTv)                                                                                                     \
@@ -2548,8 +2452,7 @@ extern "C" int mdx_op_xgemm_nt_t(const void* Av, int64_t lda, const float* B, in
     else launch_hgemm_nt_rows<KTv, FTv, false>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, LnEpi{}, Gv);   \
   } while (0)
     // few rows (the per-node layers): column groups, see the kernel
-    static const bool no_groups = getenv("MDX_ROWS_GROUPS") && atoi(getenv("MDX_ROWS_GROUPS")) == 0;
-    const bool few = !no_groups && (M + 127) / 128 <= mdx_num_cus() / 2;
+    const bool few = (M + 127) / 128 <= mdx_num_cus() / 2;
 #define MDX_HR_F(KTv)                                  \
   do {                                                 \
     if (ftn == 2) MDX_HR(KTv, 2);                      \
@@ -2713,15 +2616,6 @@ extern "C" int mdx_op_xgemm_tn_t(const void* Gv, int64_t ldg, const void* Xv, in
 // partial area (products, first reduction stage, bias partials and theirs: the layout of mdx_op_xgemm_tn_t), blocks.  `aligned` = both
 // operands start on 16 bytes.  mdx_op_wgrad_grouped: one launch over a device table of `n` records of one kind (16 x int64 each, layout
 // at the kernel), `total_blocks` = sum of their blocks; the partials are left for mdx_op_reduce_deferred.
-#ifndef MDX_KROWS_2
-// measured per class (us per step, 2,048 -> shipped): 64x128 170 -> 165, 64x64 171 -> 156, converting 64x64 318 -> 240, 32x64 133 -> 113,
-// 64x32 72 -> 81; the deferred reduction 214 -> 227 (profiles/HISTORY.md, round 6 third session)
-#define MDX_KROWS_2 1024
-#define MDX_KROWS_3 1024
-#define MDX_KROWS_4 512
-#define MDX_KROWS_5 1024
-#define MDX_KROWS_6 1024
-#endif
 extern "C" int mdx_op_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t splits, int32_t dt, int64_t ldg, int64_t ldx, int32_t aligned,
                                  int64_t* out) {
   if (!out || N <= 0 || K <= 0) return bad("wgrad_plan: bad arguments");
@@ -2732,11 +2626,9 @@ extern "C" int mdx_op_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t splits
   int64_t nc = (S + RED_CHUNK - 1) / RED_CHUNK;
   int kind = 4, tn = 64, tk = 64;
   if ((dt & 3) == 3 && N % 64 == 0 && K % 64 == 0 && ldg % 8 == 0 && ldx % 8 == 0 && aligned) {
-    // MDX_WGRAD_TILE: 0 (default) 128-wide tiles where the layer allows; 1: n x k = 128 x 64; 2: 64 x 64 (A/B knob: the 128 x 128 class runs
-    // at two waves per SIMD, 172 registers)
-    static const int tile_knob = getenv("MDX_WGRAD_TILE") ? atoi(getenv("MDX_WGRAD_TILE")) : 0;
-    tn = (N % 128 == 0 && tile_knob < 2) ? 128 : 64;
-    tk = (K % 128 == 0 && tile_knob < 1) ? 128 : 64;
+    // 128-wide tiles where the layer allows (the 128 x 128 class runs at two waves per SIMD, 172 registers)
+    tn = N % 128 == 0 ? 128 : 64;
+    tk = K % 128 == 0 ? 128 : 64;
     kind = (tn == 128 ? 0 : 2) + (tk == 128 ? 0 : 1);
   } else if ((dt & 3) == 3 && ldg % 8 == 0 && ldx % 8 == 0 && aligned && ((N == 32 && K == 64) || (N == 64 && K == 32))) {
     tn = (int)N, tk = (int)K;
@@ -2744,38 +2636,18 @@ extern "C" int mdx_op_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t splits
   } else if ((N == 1 && K % 4 == 0 && K <= 256) || (K == 1 && N % 4 == 0 && N <= 256)) {
     tn = (int)N, tk = (int)K;   // one block per row range
     kind = 7;
-    // a scaled column sum has ONE block per row range and a partial of at most 256 floats: with the queue's 2,048 rows per block the six
-    // 154,666 x 256 jobs of a step were 456 blocks on 256 CUs (two blocks = 32 KB of loads in flight per CU, 1.6 TB/s); 256 rows per
-    // block give eight times the blocks for 0.6 MB of partials per job (MDX_WGRAD_COLSUM_ROWS)
-    static const int cs_rows = getenv("MDX_WGRAD_COLSUM_ROWS") ? std::max(HW_MC, atoi(getenv("MDX_WGRAD_COLSUM_ROWS")) / HW_MC * HW_MC) : 256;
-    if (mper > cs_rows) {
-      mper = cs_rows;
-      S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
-      nc = (S + RED_CHUNK - 1) / RED_CHUNK;
-    }
   }
-  if (kind != 7) {
-    // rows per block by tile class (MDX_WGRAD_KROWS = eight comma-separated values, 0 = the caller's): the classes with few, small tiles
-    // per row range do not fill the chip at the queue's 2,048 rows per block
-    struct KRows { int v[8]; };
-    static const KRows krows = [] {   // (a function-local static: initialised once, also when the first calls come from two threads)
-      KRows r{{0, 0, MDX_KROWS_2, MDX_KROWS_3, MDX_KROWS_4, MDX_KROWS_5, MDX_KROWS_6, 0}};
-      if (const char* e = getenv("MDX_WGRAD_KROWS")) {
-        int i = 0;
-        for (const char* p = e; *p && i < 8; ++i) {
-          r.v[i] = atoi(p);
-          while (*p && *p != ',') ++p;
-          if (*p == ',') ++p;
-        }
-      }
-      return r;
-    }();
-    const int kr = krows.v[kind] / HW_MC * HW_MC;
-    if (kr > 0 && mper > kr) {
-      mper = kr;
-      S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
-      nc = (S + RED_CHUNK - 1) / RED_CHUNK;
-    }
+  // Rows per block by tile class (0 = the caller's): the classes with few, small tiles per row range do not fill the chip at the queue's
+  // 2,048 rows per block.  Measured per class (us per step, 2,048 -> shipped): 64x128 170 -> 165, 64x64 171 -> 156, converting 64x64
+  // 318 -> 240, 32x64 133 -> 113, 64x32 72 -> 81; the deferred reduction 214 -> 227 (profiles/HISTORY.md, round 6 third session).
+  // A scaled column sum (class 7) has ONE block per row range and a partial of at most 256 floats: with 2,048 rows per block the six
+  // 154,666 x 256 jobs of a step were 456 blocks on 256 CUs (two blocks = 32 KB of loads in flight per CU, 1.6 TB/s); 256 rows per block
+  // give eight times the blocks for 0.6 MB of partials per job.
+  constexpr int krows[8] = {0, 0, 1024, 1024, 512, 1024, 1024, 256};
+  if (krows[kind] > 0 && mper > krows[kind]) {
+    mper = krows[kind];
+    S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
+    nc = (S + RED_CHUNK - 1) / RED_CHUNK;
   }
   const int64_t gx = (K + tk - 1) / tk, gy = (N + tn - 1) / tn;
   out[0] = kind, out[1] = gx, out[2] = gy, out[3] = S, out[4] = mper;
@@ -2791,16 +2663,15 @@ extern "C" int mdx_op_wgrad_grouped(const int64_t* desc, int32_t n, int64_t tota
   hipStream_t s = (hipStream_t)stream;
   const long long* d = reinterpret_cast<const long long*>(desc);
   const dim3 grid((unsigned)total_blocks);
-  static const int xcd = getenv("MDX_WGRAD_XCD") ? atoi(getenv("MDX_WGRAD_XCD")) : 1;
   switch (kind) {
-    case 0: hipLaunchKernelGGL(wgrad_grouped_kernel<0>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 1: hipLaunchKernelGGL(wgrad_grouped_kernel<1>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 2: hipLaunchKernelGGL(wgrad_grouped_kernel<2>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 3: hipLaunchKernelGGL(wgrad_grouped_kernel<3>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 4: hipLaunchKernelGGL(wgrad_grouped_kernel<4>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 5: hipLaunchKernelGGL(wgrad_grouped_kernel<5>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 6: hipLaunchKernelGGL(wgrad_grouped_kernel<6>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
-    case 7: hipLaunchKernelGGL(wgrad_grouped_kernel<7>, grid, dim3(256), 0, s, d, (int)n, xcd); break;
+    case 0: hipLaunchKernelGGL(wgrad_grouped_kernel<0>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 1: hipLaunchKernelGGL(wgrad_grouped_kernel<1>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 2: hipLaunchKernelGGL(wgrad_grouped_kernel<2>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 3: hipLaunchKernelGGL(wgrad_grouped_kernel<3>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 4: hipLaunchKernelGGL(wgrad_grouped_kernel<4>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 5: hipLaunchKernelGGL(wgrad_grouped_kernel<5>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 6: hipLaunchKernelGGL(wgrad_grouped_kernel<6>, grid, dim3(256), 0, s, d, (int)n); break;
+    case 7: hipLaunchKernelGGL(wgrad_grouped_kernel<7>, grid, dim3(256), 0, s, d, (int)n); break;
     default: return bad("wgrad_grouped: kind must be 0..7");
   }
   return launched();
@@ -2817,18 +2688,6 @@ extern "C" int mdx_op_hgemm_tn(const float* G, int64_t ldg, const float* X, int6
                                int64_t N, int64_t K, int32_t splits, float* partial, void* stream) {
   return mdx_op_xgemm_tn(G, ldg, X, ldx, dW, ldw, db, M, N, K, splits, partial, 1, 0, stream);
 }
-
-// Experimental: fp32-accurate product on the bf16 matrix pipe (three-way operand split, 6 MFMAs per k-step); benchmark only,
-// compiled with `make EXTRA=-DMDX_EXPERIMENTAL` (tools/ubench_bf16x3.py), absent from the shipped library.
-#ifdef MDX_EXPERIMENTAL
-extern "C" int mdx_debug_hgemm3_nt(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N,
-                                   int64_t K, void* stream) {
-  if (M <= 0 || N <= 0) return MDX_OK;
-  dim3 grid((unsigned)((N + G_TN - 1) / G_TN), (unsigned)((M + G_TM - 1) / G_TM), 1);
-  hipLaunchKernelGGL(hgemm3_nt_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, (int)lda, B, (int)ldb, C, (int)ldc, (int)M, (int)N, (int)K);
-  return launched();
-}
-#endif
 
 // y = a * t[idx] (rows of F floats, F % 4 == 0) and its gradients; see mulg_*_kernel.
 // F: feature count in its low 16 bits; bits 16.. = rounding kind of the product (0 fp32, 1 bfloat16, 2 float16; mixed precision)

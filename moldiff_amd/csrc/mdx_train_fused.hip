@@ -89,12 +89,7 @@ __device__ __forceinline__ void sth8_pair(_Float16* row_base, int g2, uint2 ha, 
   const auto sy = __builtin_amdgcn_permlane16_swap(ha.y, hb.y, false, false);
   const uint4 v = {sx[0], sy[0], sx[1], sy[1]};
   const int col = (q & 1) ? 32 * g2 + 16 + 4 * (q - 1) : 32 * g2 + 4 * q;
-#ifdef MDX_TRAIN_NT
-  typedef unsigned int nt_u32x4_t __attribute__((__vector_size__(4 * sizeof(unsigned int))));
-  if (ok) __builtin_nontemporal_store(__builtin_bit_cast(nt_u32x4_t, v), reinterpret_cast<nt_u32x4_t*>(row_base + col));
-#else
   if (ok) *reinterpret_cast<uint4*>(row_base + col) = v;
-#endif
 }
 
 // FT (even) packed tiles of one row block: FT / 2 paired stores
@@ -525,17 +520,9 @@ __global__ __launch_bounds__(BF_THREADS) void bondffn_bwd_kernel(const mdx_bondf
   const uint16_t* wg2t = S + BwdLds::WG2T + c * LDO + 8 * q;
   const uint16_t* wg1t = S + BwdLds::WG1T + c * LDG + 8 * q;
 
-#ifndef MDX_BF_LNP_DPP
-#define MDX_BF_LNP_DPP 1
-#endif
-#if MDX_BF_LNP_DPP
   float acc1[4] = {0.f, 0.f, 0.f, 0.f};   // inter LayerNorm: d gamma, d beta of features 16 (c >> 1) + 4 q + 2 (c & 1) + {0, 1} (colsum8x2)
   f32x4 dgg[2], dgb[2];
   zero<2>(dgg); zero<2>(dgb);
-#else
-  f32x4 dg1[8], db1[8], dgg[2], dgb[2];
-  zero<8>(dg1); zero<8>(db1); zero<2>(dgg); zero<2>(dgb);
-#endif
 
 #pragma unroll 1
   for (int tile = blockIdx.x * BF_WAVES + wave; tile < ntiles; tile += nw) {
@@ -573,11 +560,7 @@ __global__ __launch_bounds__(BF_THREADS) void bondffn_bwd_kernel(const mdx_bondf
       mm<8, 2, LDO>(g, wi2t, b2);
 #pragma unroll
       for (int ft = 0; ft < 8; ++ft) g[ft] = rh4(g[ft]);
-#if MDX_BF_LNP_DPP
       ln_relu_bwd8_rs(g, xp, C + BwdLds::C_G1, C + BwdLds::C_BE1, q, c, ok, acc1);
-#else
-      ln_relu_bwd<8>(g, xp, C + BwdLds::C_G1, C + BwdLds::C_BE1, q, ok, dg1, db1);
-#endif
       uint2 pg[8];
 #pragma unroll
       for (int ft = 0; ft < 8; ++ft) {
@@ -648,24 +631,11 @@ __global__ __launch_bounds__(BF_THREADS) void bondffn_bwd_kernel(const mdx_bondf
   // partial row per workgroup; the caller's deferred reduction sums the gridDim.x rows
   __syncthreads();   // every wave is done with the weights: the LDS area is free
   float* R = reinterpret_cast<float*>(bf_smem);
-#if MDX_BF_LNP_DPP
   {
     const int f = 16 * (c >> 1) + 4 * q + 2 * (c & 1);
     R[wave * BF_LNP + f] = acc1[0], R[wave * BF_LNP + f + 1] = acc1[1];
     R[wave * BF_LNP + 128 + f] = acc1[2], R[wave * BF_LNP + 128 + f + 1] = acc1[3];
   }
-#else
-#pragma unroll
-  for (int ft = 0; ft < 8; ++ft)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float v1 = sum_c(dg1[ft][s]), v2 = sum_c(db1[ft][s]);
-      if (c == 0) {
-        R[wave * BF_LNP + 16 * ft + 4 * q + s] = v1;
-        R[wave * BF_LNP + 128 + 16 * ft + 4 * q + s] = v2;
-      }
-    }
-#endif
 #pragma unroll
   for (int ft = 0; ft < 2; ++ft)
 #pragma unroll
@@ -1399,11 +1369,7 @@ __device__ __forceinline__ void ts_flush_b(const uint16_t* T, __amdgpu_buffer_rs
     for (int i = 0; i < B; ++i) {
       const int ii = i0 + i;
       typedef unsigned int u32x4_t __attribute__((__vector_size__(4 * sizeof(unsigned int))));
-#ifdef MDX_TRAIN_NT
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v[i]), rs, vo, so + (unsigned)ii * 1024u, 2);   // nt
-#else
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v[i]), rs, vo, so + (unsigned)ii * 1024u, 0);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -1440,11 +1406,7 @@ __global__ __launch_bounds__(NMF_THREADS, NMF_WPS) void nodemsg_fwd_kernel(const
   for (int it = 0; it < iters; ++it) {
     const int tile = it * nw + blockIdx.x * NMF_WAVES + wave;
     const int row = 16 * tile + c;
-#ifdef MDX_NM_NOSTORE            // ablation (timing only, results are garbage): no epilogue stores -- profiles/r6_ab_nodemsg_stores.txt
-    const bool ok = row < E && a.E < 0;
-#else
     const bool ok = row < E;      // (a wave past the last tile computes on the clamped last row and stores nothing)
-#endif
     const size_t r = (size_t)min(row, E - 1), ro = r * KW + 4 * q, rb = r * KW;
     const int64_t nc = a.col[r];
     const _Float16* px = X + r * a.ldx + 8 * q;
@@ -1568,40 +1530,18 @@ __global__ __launch_bounds__(NMF_THREADS, NMF_WPS) void nodemsg_fwd_kernel(const
   }
 }
 
-// Column sums over the 16 rows of a tile (fp32, accumulator layout: lane (q, c) holds features 16 ft + 4 q .. of row c), added to acc
-// (lane L owns features 4 L .. 4 L + 3): the tile goes through the wave's LDS area T [16][NM_TLD] one feature tile at a time (cs_put),
-// then every lane adds its four features of rows 0..15 in order (cs_sum).
-constexpr int NM_TLD = 132;   // half a row (128 features) + 4: the 256 columns go through in two halves (LDS: 8.25 KiB per wave)
-__device__ __forceinline__ void cs_put(float* T, int ft8, f32x4 v, int c, int q) { *reinterpret_cast<f32x4*>(T + c * NM_TLD + 16 * ft8 + 4 * q) = v; }
-// lanes 32 hf .. 32 hf + 31 own the features of half hf: lane L adds features 4 L .. 4 L + 3 of rows 0..15 in order
-__device__ __forceinline__ void cs_sum(f32x4& acc, const float* T, int lane, int hf) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  {
-    // every lane reads (lanes of the other half read the same words and add zero: no divergent branch around the sums)
-    const float keep = ((lane >> 5) == hf) ? 1.0f : 0.0f;
-    f32x4 part = splat4(0.f);
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {   // four rows in flight (all 16 at once cost 64 registers where the kernel has none to spare):
-      part = part + *reinterpret_cast<const volatile f32x4*>(T + rr * NM_TLD + 4 * (lane & 31));
-      if (rr % 4 == 3) asm volatile("" : "+v"(part));   // pinned every four rows, so the reads cannot all be hoisted above the adds
-    }
-    acc = acc + part * splat4(keep);
-  }
-  __builtin_amdgcn_wave_barrier();   // the area is rewritten only after every lane has read it
-}
+// Each wave of the backward once had an LDS area of 16 x NM_TLD floats for its tile's column sums (rows written as fp32, then summed per
+// lane); the butterfly below replaced them.  The areas are still reserved in front of the parameter sums (see NM_BWD_LDS).
+constexpr int NM_TLD = 132;   // half a row (128 features) + 4 (LDS: 8.25 KiB per wave)
 
-// Column sums over the 16 rows of a tile WITHOUT the LDS transposition (round 6, third session): a reduce-scatter butterfly over the 16
-// lanes c of a lane row (= one DPP row; q, the feature quad, is the same in all of them).  Step 1 pairs c with c ^ 8 (row_ror:8): a lane
+// Column sums over the 16 rows of a tile (fp32, accumulator layout: lane (q, c) holds features 16 ft + 4 q .. of row c) without an LDS
+// transposition (round 6, third session): a reduce-scatter butterfly over the 16 lanes c of a lane row (= one DPP row; q, the feature
+// quad, is the same in all of them).  Step 1 pairs c with c ^ 8 (row_ror:8): a lane
 // keeps the eight tiles whose bit 3 equals its own and adds the partner's values of them; step 2 (row_half_mirror: c ^ 7, same bit 3,
 // other bit 2) halves again, steps 3 / 4 (quad_perm: c ^ 2, c ^ 1) end with ONE tile per lane: lane (c, q) holds the sum over the 16
 // rows of features 16 c + 4 q .. + 3.  60 DPP adds + 120 selects per call instead of 8 LDS writes, a wave barrier and 16 dependent LDS
 // reads per half (the LDS version cost the backward 71 us of 458 per launch and the registers that made it spill).  Deterministic; the
 // order of additions is the butterfly's (pairs of rows), not rows 0..15 in sequence.
-#ifndef MDX_NM_LNP_DPP
-#define MDX_NM_LNP_DPP 1
-#endif
 // depth first (a tile pair is folded as soon as both halves exist): at most ~6 tiles of temporaries alive instead of the 8 + 4 of a
 // step-by-step butterfly -- the kernel has no registers to spare
 template <class F>
@@ -1630,76 +1570,30 @@ __device__ __forceinline__ f32x4 colsum16(F&& val, int c) {
   return rs_comb<QP_X1>(a, b, b0);
 }
 
-// A 16 x 256 float16 tile of a stored tensor into the wave's LDS area, the inverse of ts_flush (round 6, third session): eight buffer loads
-// of two complete 512-byte rows each (lanes 0..31 row 2 i, lanes 32..63 row 2 i + 1, 16 bytes per lane; rows past the end read as zero
-// through the bounds check), written as they are; ts_get then returns the accumulator-layout chunk (row c, columns 16 ft + 4 q .. + 3)
-// the direct 8-byte loads fetched -- 16 rows x 32 bytes per instruction, which cost the backward 48 us per launch (profiles/HISTORY.md:
-// row-0 ablation).  The tile STAYS in LDS while the LayerNorm backward reads it six times: 32 registers less than holding it.
-typedef unsigned int tsu4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int tsu2_t __attribute__((ext_vector_type(2)));
-template <int B>
-__device__ __forceinline__ void ts_load(uint16_t* T, const _Float16* src, int E, int tile, int lane) {
-  const __amdgpu_buffer_rsrc_t rs = ts_rsrc(const_cast<_Float16*>(src), E);
-  const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane(tile) * (unsigned)(16 * KW * 2);
-  const unsigned vo = (unsigned)(lane >> 5) * (unsigned)(KW * 2) + 16u * (unsigned)(lane & 31);
-  uint16_t* dst = T + (lane >> 5) * TS_LD + 8 * (lane & 31);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // every lane has finished with the area's previous content
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i0 = 0; i0 < 8; i0 += B) {
-    uint4 v[B];
-#pragma unroll
-    for (int i = 0; i < B; ++i) v[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, so + (unsigned)(i0 + i) * 1024u, 0));
-#pragma unroll
-    for (int i = 0; i < B; ++i) *reinterpret_cast<volatile tsu4_t*>(dst + 2 * (i0 + i) * TS_LD) = __builtin_bit_cast(tsu4_t, v[i]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint2 ts_get(const uint16_t* T, int ft, int c, int q) {
-  const tsu2_t v = *reinterpret_cast<const volatile tsu2_t*>(T + c * TS_LD + 16 * ft + 4 * q);
-  return uint2{v.x, v.y};
-}
-// Measured (third session): with the running sums in LDS the kernel does not spill either way (228 VGPRs direct, 250 staged), and the
-// staged tile's LDS traffic and wave barriers cost more than its load pattern saves: 392.6 us direct against 418.7 us staged on the same
-// box.  The direct 8-byte loads are the default; 1 keeps the staged form.
-#ifndef MDX_NM_TSLOAD
-#define MDX_NM_TSLOAD 0
-#endif
-static_assert(!MDX_NM_TSLOAD || MDX_NM_LNP_DPP, "the staged tile lives in the area the LDS column sums would use");
-
-// 256-wide LayerNorm + ReLU backward in place (g: dL/d output -> dL/d pre-activation); xsrc = the stored pre-activation (E x 256
-// float16), read through the wave's LDS area (MDX_NM_TSLOAD) or directly (xrow = this lane's row + 4 q); the rows' contributions to
-// d gamma / d beta are summed over the tile by the DPP butterfly (or the LDS column sums)
-__device__ __forceinline__ void ln256_relu_bwd(f32x4 (&g)[16], const _Float16* xsrc, const _Float16* xrow, int E, int tile, const float* gam,
-                                               const float* bet, int q, bool ok, float* pgam, float* pbet, float* T, int lane) {
+// 256-wide LayerNorm + ReLU backward in place (g: dL/d output -> dL/d pre-activation); xrow = the stored pre-activation (E x 256 float16)
+// at this lane's row + 4 q, read directly with 8-byte loads.  Measured (round 6, third session): staging the tile through the wave's LDS
+// area with full-row loads instead (32 registers less than holding it) ran 418.7 us against 392.6 us direct on the same box -- with the
+// running sums in LDS neither form spills (250 against 228 VGPRs), and the staged tile's LDS traffic and wave barriers cost more than its
+// load pattern saves; removed.  The rows' contributions to d gamma / d beta are summed over the tile by the DPP butterfly.
+__device__ __forceinline__ void ln256_relu_bwd(f32x4 (&g)[16], const _Float16* xrow, const float* gam, const float* bet, int q, int c, bool ok,
+                                               float* pgam, float* pbet) {
   constexpr float inv_n = 1.0f / 256;
-  const int c = lane & 15;
-#if MDX_NM_TSLOAD
-  const uint16_t* Th = reinterpret_cast<const uint16_t*>(T);
-  ts_load<4>(reinterpret_cast<uint16_t*>(T), xsrc, E, tile, lane);
-#define XP(ft) ts_get(Th, (ft), c, q)
-#else
   uint2 xp[16];
 #pragma unroll
   for (int ft = 0; ft < 16; ++ft) xp[ft] = *reinterpret_cast<const uint2*>(xrow + 16 * ft);
-#define XP(ft) xp[ft]
-#endif
   float mean, rstd;
   {
     float sm = 0.f;
 #pragma unroll
     for (int ft = 0; ft < 16; ++ft) {
-      const f32x4 v = unpack4(XP(ft));
+      const f32x4 v = unpack4(xp[ft]);
       sm += (v[0] + v[1]) + (v[2] + v[3]);
     }
     mean = sumq(sm) * inv_n;
     float d2 = 0.f;
 #pragma unroll
     for (int ft = 0; ft < 16; ++ft) {
-      const f32x4 v = unpack4(XP(ft));
+      const f32x4 v = unpack4(xp[ft]);
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const float d = v[s] - mean;
@@ -1712,41 +1606,24 @@ __device__ __forceinline__ void ln256_relu_bwd(f32x4 (&g)[16], const _Float16* x
 #pragma unroll
   for (int ft = 0; ft < 16; ++ft) {
     const f32x4 gm = lds4(gam + 16 * ft + 4 * q), bt = lds4(bet + 16 * ft + 4 * q);
-    const f32x4 xh = (unpack4(XP(ft)) - splat4(mean)) * splat4(rstd);
+    const f32x4 xh = (unpack4(xp[ft]) - splat4(mean)) * splat4(rstd);
     const f32x4 yv = xh * gm + bt;
 #pragma unroll
     for (int s = 0; s < 4; ++s) g[ft][s] = (ok && yv[s] > 0.f) ? g[ft][s] : 0.f;
     if (ft % 4 == 3) __builtin_amdgcn_sched_barrier(0);
   }
-#if defined(MDX_NM_NOLNP)         // (ablation, timing only: without the LayerNorm-parameter column sums)
-#elif MDX_NM_LNP_DPP              // lane (c, q) accumulates features 16 c + 4 q .. + 3
-  // the running sums live in LDS (this lane's own four floats per vector: no other lane touches them): as registers they were alive
-  // across the whole tile loop -- 16 of them were the difference between no spills and ~60
+  // lane (c, q) accumulates features 16 c + 4 q .. + 3.  The running sums live in LDS (this lane's own four floats per vector: no other
+  // lane touches them): as registers they were alive across the whole tile loop -- 16 of them were the difference between no spills and ~60
   *reinterpret_cast<f32x4*>(pbet) = *reinterpret_cast<const f32x4*>(pbet) + colsum16([&](int ft) { return g[ft]; }, c);
   __builtin_amdgcn_sched_barrier(0);
   *reinterpret_cast<f32x4*>(pgam) = *reinterpret_cast<const f32x4*>(pgam) +
-                                    colsum16([&](int ft) { return g[ft] * ((unpack4(XP(ft)) - splat4(mean)) * splat4(rstd)); }, c);
+                                    colsum16([&](int ft) { return g[ft] * ((unpack4(xp[ft]) - splat4(mean)) * splat4(rstd)); }, c);
   __builtin_amdgcn_sched_barrier(0);
-#else                             // lane L accumulates features 4 L .. 4 L + 3 (LDS column sums)
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-#pragma unroll
-    for (int f8 = 0; f8 < 8; ++f8) cs_put(T, f8, g[8 * hf + f8], c, q);
-    f32x4 acc = *reinterpret_cast<const f32x4*>(pbet);
-    cs_sum(acc, T, lane, hf);
-    *reinterpret_cast<f32x4*>(pbet) = acc;
-#pragma unroll
-    for (int f8 = 0; f8 < 8; ++f8) cs_put(T, f8, g[8 * hf + f8] * ((unpack4(XP(8 * hf + f8)) - splat4(mean)) * splat4(rstd)), c, q);
-    acc = *reinterpret_cast<const f32x4*>(pgam);
-    cs_sum(acc, T, lane, hf);
-    *reinterpret_cast<f32x4*>(pgam) = acc;
-  }
-#endif
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int ft = 0; ft < 16; ++ft) {
     const f32x4 gm = lds4(gam + 16 * ft + 4 * q);
-    const f32x4 xh = (unpack4(XP(ft)) - splat4(mean)) * splat4(rstd);
+    const f32x4 xh = (unpack4(xp[ft]) - splat4(mean)) * splat4(rstd);
     g[ft] = g[ft] * gm;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -1758,17 +1635,15 @@ __device__ __forceinline__ void ln256_relu_bwd(f32x4 (&g)[16], const _Float16* x
   const float m1 = sumq(s1) * inv_n, m2 = sumq(s2) * inv_n;
 #pragma unroll
   for (int ft = 0; ft < 16; ++ft) {
-    const f32x4 xh = (unpack4(XP(ft)) - splat4(mean)) * splat4(rstd);
+    const f32x4 xh = (unpack4(xp[ft]) - splat4(mean)) * splat4(rstd);
     g[ft] = (g[ft] - splat4(m1) - xh * splat4(m2)) * splat4(rstd);
   }
 }
-#undef XP
 
 __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodemsg_bwd_args a) {
   extern __shared__ __attribute__((aligned(16))) uint16_t bf_smem[];
   uint16_t* wbuf = bf_smem;                                  // two k-steps of weight fragments (mmw), 32 KiB
   float* C = reinterpret_cast<float*>(bf_smem + 2 * 8192);    // 4 x 256 LayerNorm parameters
-  float* Tall = C + 1024;                                     // NM_WAVES areas of 16 x NM_TLD floats (>= NM_WAVES x NM_LNP floats for the end)
   int par = 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 15, q = lane >> 4;
@@ -1777,7 +1652,6 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
     for (int i = tid; i < 1024; i += NM_THREADS) C[i] = src[i >> 8][i & 255];
   }
   __syncthreads();
-  float* T = Tall + (size_t)wave * 16 * NM_TLD;
   const int E = (int)a.f.E, ntiles = (E + 15) >> 4, nw = gridDim.x * NM_WAVES;
   const int iters = (ntiles + nw - 1) / nw;
   const _Float16* HN = reinterpret_cast<const _Float16*>(a.f.HN);
@@ -1791,27 +1665,18 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
            *o_ggpre = reinterpret_cast<_Float16*>(a.g_gpre), *o_ghne = reinterpret_cast<_Float16*>(a.g_hne),
            *o_ghe = reinterpret_cast<_Float16*>(a.g_he), *o_gpre = reinterpret_cast<_Float16*>(a.g_pre), *o_gx = reinterpret_cast<_Float16*>(a.g_x);
   // this lane's running LayerNorm-parameter sums: four floats in each of the wave's four vectors of R (d gamma_e | d beta_e | d gamma_g | d beta_g)
-  float* R = Tall + (size_t)NM_WAVES * 16 * NM_TLD;   // [NM_WAVES][NM_LNP], behind the waves' tile areas
-  float* racc = R + wave * NM_LNP + (MDX_NM_LNP_DPP ? 16 * c + 4 * q : 4 * lane);
+  float* R = C + 1024 + (size_t)NM_WAVES * 16 * NM_TLD;   // [NM_WAVES][NM_LNP], behind the reserved tile areas
+  float* racc = R + wave * NM_LNP + (16 * c + 4 * q);
 #pragma unroll
   for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(racc + 256 * k) = splat4(0.f);
 #pragma unroll 1
   for (int it = 0; it < iters; ++it) {
     const int tile = it * nw + blockIdx.x * NM_WAVES + wave;
     const int row = 16 * tile + c;
-#ifdef MDX_NM_NOSTORE_B
-    const bool ok = row < E && a.f.E < 0;
-#else
     const bool ok = row < E;
-#endif
     const size_t r = (size_t)min(row, E - 1), ro = r * KW + 4 * q;
     const size_t rb = r * KW;
-#ifdef MDX_NM_ROW0_B             // ablation (timing only): every tile reads the tape rows of tile 0 (1: cache-hot, same pattern) or row 0 (2)
-    const size_t rl = MDX_NM_ROW0_B == 1 ? (size_t)c : 0, rol = rl * KW + 4 * q;
-#else
-    const size_t rl = r, rol = ro;
-#endif
-    const int64_t nc = a.f.col[rl], nr = a.row[rl];
+    const int64_t nc = a.f.col[r], nr = a.row[r];
     f32x4 y[16];
     f16x8_t b8[8];
     f32x4 gx1[4];
@@ -1824,7 +1689,7 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
       for (int j = 0; j < 2; ++j) {
         const int ft = 2 * g2 + j;
         const f32x4 g = rh4(ldg4(a.gA + (size_t)nr * a.ldga + 16 * ft + 4 * q));
-        const f32x4 m0 = ldh4(s_m0 + rol + 16 * ft), sg = sigmoid4(ldh4(s_gt + rol + 16 * ft));
+        const f32x4 m0 = ldh4(s_m0 + ro + 16 * ft), sg = sigmoid4(ldh4(s_gt + ro + 16 * ft));
         h[j] = pack4(g * m0 * sg * (splat4(1.f) - sg));      // d gt
         if (ok) {
           sth4(o_gm0 + ro + 16 * ft, pack4(g * sg));        // d m0 (formed again below: the registers go to the gate chain first)
@@ -1839,7 +1704,7 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
     mmw<16, 8>(y, wg2t, wbuf, par, tid, lane, b8);
 #pragma unroll
     for (int ft = 0; ft < 16; ++ft) y[ft] = rh4(y[ft]);
-    ln256_relu_bwd(y, s_gpre, s_gpre + rol, E, tile, C + 512, C + 768, q, ok, racc + 512, racc + 768, T, lane);
+    ln256_relu_bwd(y, s_gpre + ro, C + 512, C + 768, q, c, ok, racc + 512, racc + 768);
 #pragma unroll
     for (int g2 = 0; g2 < 8; ++g2) {
       const uint2 h0 = pack4(y[2 * g2]), h1 = pack4(y[2 * g2 + 1]);
@@ -1876,7 +1741,7 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
         const int ft = 2 * g2 + j;
         const f32x4 gp = rh4(y[ft]);
         h[j] = pack4(gp * ldh4(HN + (size_t)nc * a.f.ldhn + 16 * ft + 4 * q));       // d he
-        hn[j] = pack4(gp * ldh4(s_he + rol + 16 * ft));                               // per-edge d hn[col]
+        hn[j] = pack4(gp * ldh4(s_he + ro + 16 * ft));                               // per-edge d hn[col]
       }
       sth8_pair(o_ghne + rb, g2, hn[0], hn[1], q, ok);
       sth8_pair(o_ghe + rb, g2, h[0], h[1], q, ok);
@@ -1888,7 +1753,7 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
     mmw<16, 8>(y, w2et, wbuf, par, tid, lane, b8);
 #pragma unroll
     for (int ft = 0; ft < 16; ++ft) y[ft] = rh4(y[ft]);
-    ln256_relu_bwd(y, s_hepre, s_hepre + rol, E, tile, C + 0, C + 256, q, ok, racc, racc + 256, T, lane);
+    ln256_relu_bwd(y, s_hepre + ro, C + 0, C + 256, q, c, ok, racc, racc + 256);
 #pragma unroll
     for (int g2 = 0; g2 < 8; ++g2) {
       const uint2 h0 = pack4(y[2 * g2]), h1 = pack4(y[2 * g2 + 1]);
@@ -1913,7 +1778,7 @@ __global__ __launch_bounds__(NM_THREADS) void nodemsg_bwd_kernel(const mdx_nodem
   }
 }
 
-constexpr int NM_BWD_LDS = 2 * 16384 + (1024 + NM_WAVES * 16 * NM_TLD + NM_WAVES * NM_LNP) * 4;   // weights, constants, tile areas, parameter sums: 135.6 KiB
+constexpr int NM_BWD_LDS = 2 * 16384 + (1024 + NM_WAVES * 16 * NM_TLD + NM_WAVES * NM_LNP) * 4;   // weights, constants, reserved tile areas, parameter sums: 135.6 KiB
 static bool g_attr_nb = false;
 
 extern "C" int mdx_op_nodemsg_lnp_floats(void) { return NM_LNP; }

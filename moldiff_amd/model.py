@@ -30,9 +30,6 @@ from .diffusion import get_beta_schedule
 from .graph import NodeEdgeNet, _sig, synth_gates
 from .transition import ContigousTransition, GeneralCategoricalTransition
 
-_FUSED_LOSS = os.environ.get('MDX_TRAIN_FUSED_LOSS', '1') != '0'   # training: categorical loss tail as one launch (train_ops.cat_loss)
-
-
 class MolDiff(Module):
     def __getstate__(self):
         # the packed-weight engine is a device handle: never copied or pickled (deepcopy / torch.save of the module
@@ -194,7 +191,7 @@ class MolDiff(Module):
         for name, tr, logits, log_t, log_0, batch in (
                 ('loss_node', self.node_transition, preds['pred_node'], log_node_t, log_node_0, batch_node),
                 ('loss_edge', self.edge_transition, preds['pred_halfedge'], log_half_t, log_half_0, batch_halfedge)):
-            if train and _FUSED_LOSS and logits.is_cuda and 2 <= logits.shape[-1] <= 8 and logits.shape[0] > 0:
+            if train and logits.is_cuda and 2 <= logits.shape[-1] <= 8 and logits.shape[0] > 0:
                 from . import train_ops      # round 6: the whole tail and its backward as one launch (csrc cat_loss_kernel)
                 out[name] = train_ops.cat_loss(tr, logits, log_t, log_0, t, batch)
                 continue

@@ -71,7 +71,7 @@ def _c(t):
 #   store = True ('fp16'): those half VALUES also live in float16 CONTAINERS (every Linear / LayerNorm / product result and its
 #     gradient) -- the operators are memory-bound, so this halves what limits them; 'fp16_f32store' keeps fp32 containers (round 3's
 #     first cut; the two differ only where the half container rounds a LayerNorm output one operator earlier -- the node residual stream
-#     stays fp32 in both, as under the reference's autocast: train_graph.res_add).
+#     is not promoted to fp32 in either, unlike under the reference's autocast: see train_graph.node_edge_net).
 _AMP = None
 KINDS = {'f32': None, 'bf16': (1, False, False), 'fp16': (2, True, True), 'fp16_f32store': (2, True, False),
          'bf16_autocast': (1, True, False)}
@@ -380,9 +380,6 @@ def sgemm_tn(g, x, splits, want_bias=False, defer=None):
         dt = _h(g) | (_h(x) << 1)
         plan = _wgrad_plan(M, N, K, dt, g.stride(0), x.stride(0), int(g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0))
         sk = _SINK
-        if sk['fast'] is not None:
-            sk['fast'].wq_append(g, x, dst_w, ldw, (dst_b or 0) if want_bias else 0, _AMP[0] if _AMP[1] else 0)
-            return None
         sk['wq'].append((g, x, plan, (M, N, K, dt), dst_w, ldw, dst_b if want_bias else None, _AMP[0] if _AMP[1] else 0))
         sk['wq_bytes'] += g.numel() * g.element_size() + x.numel() * x.element_size()
         if sk['wq_bytes'] > WGRAD_QUEUE_BYTES:
@@ -795,9 +792,6 @@ def gate(a, b):
     return _ew(GATE, a, b)
 
 
-_FANOUT = __import__('os').environ.get('MDX_TRAIN_FANOUT', '1') != '0'
-
-
 class _Fanout(torch.autograd.Function):
     """k aliases of x for its k consumers; the backward sums their gradients in ONE launch (csrc sum_n4_kernel: fp32 sum in consumer
     order, one rounding to x's container) where autograd would run k - 1 element-wise adds."""
@@ -827,7 +821,7 @@ class _Fanout(torch.autograd.Function):
 
 def fanout(x, k):
     """k aliases of x, one per consumer (see _Fanout); plain repetition when there is nothing to gain"""
-    if k < 3 or k > 12 or not _FANOUT or not x.is_cuda or not x.requires_grad or not torch.is_grad_enabled():
+    if k < 3 or k > 12 or not x.is_cuda or not x.requires_grad or not torch.is_grad_enabled():
         return (x,) * k
     return _Fanout.apply(x, k)
 
@@ -1030,7 +1024,7 @@ def force(w, rel, dist):
 # A whole BondFFN of the EdgeBlock + the scatter_sum that follows it as ONE autograd node: 2 launches forward (fused chain, segment sum)
 # and 9 backward (fused data-gradient chain, 6 weight-gradient contractions, 2 segment sums) where the per-operator composition issues
 # 12 and ~28.  float16 autocast mode with float16 containers only; every other mode keeps the per-operator path.
-FUSED_MIN_ROWS = int(__import__('os').environ.get('MDX_TRAIN_FUSED_MIN_ROWS', '1024'))   # below this the per-operator path runs (tests lower it to cover the fused path on small graphs)
+FUSED_MIN_ROWS = 1024   # below this the per-operator path runs (tests lower it to cover the fused path on small graphs)
 _FUSED = __import__('os').environ.get('MDX_TRAIN_FUSED', '1') != '0'
 
 
@@ -1166,7 +1160,7 @@ def _wgrad_into(grads, need, refs, E, gy, xin, wname, bname):
             grads[bname] = gb_
 
 
-_FUSED_TAIL = __import__('os').environ.get('MDX_TRAIN_FUSED_TAIL', '1') != '0'
+_FUSED_TAIL = True
 
 
 def edge_tail_fused_ok(h_bond, by_left, by_right):
@@ -1256,7 +1250,7 @@ def edge_tail(h, by_left, by_right, plan_l, plan_r, params):
     return _EdgeTail.apply(h, by_left, by_right, plan_l, plan_r, *ps)
 
 
-_FUSED_POS = __import__('os').environ.get('MDX_TRAIN_FUSED_POS', '1') != '0'
+_FUSED_POS = True
 
 
 def posffn_fused_ok(h_edge, lf, rf, dims):
@@ -1360,7 +1354,7 @@ def posffn_front(h_edge, lf, rf, time, plan_l, plan_r, params):
     return _PosFfnFront.apply(h_edge, lf, rf, time, plan_l, plan_r, *ps)
 
 
-_FUSED_NODE = __import__('os').environ.get('MDX_TRAIN_FUSED_NODE', '1') != '0'
+_FUSED_NODE = True
 
 
 def nodemsg_fused_ok(edge_attr, hn, pn, shapes):

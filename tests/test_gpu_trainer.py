@@ -102,7 +102,7 @@ def test_fp16_autocast_training_steps_reduce_the_loss(fused_rows):
             mod._eng, mod._eng_sig = None, None
     # lr = the shipped configs' 1e-4 (configs/train_MolDiff*.yml).  At 2e-4 this 4-molecule batch is not a descent any more but an
     # oscillation (AdamW's first steps are sign-like): 12 steps end above or below the start depending on float16 rounding of single
-    # gradients (tools/probe_catloss_descent.py: both loss-tail variants oscillate at 2e-4, both fall 1.66 -> 1.10-1.13 at 1e-4)
+    # gradients (round-6 probe, profiles/HISTORY.md: both loss-tail variants oscillate at 2e-4, both fall 1.66 -> 1.10-1.13 at 1e-4)
     tr = Trainer(m, lr=1e-4, max_grad_norm=50.0, precision='fp16', init_scale=1024.0)
     batch = _tiny_batch(7)
     t = torch.tensor([120, 480, 700, 930], device=DEV)
