@@ -1,14 +1,17 @@
-// Host-side fast path of the training step (round 6): the operator BODIES of moldiff_amd/train_ops.py in C++.
+// Host-side fast path of the training step (round 6): the operator BODIES of moldiff_amd/train_ops.py in C++, and the only
+// implementation of the gradient sink and the weight-gradient queue.
 //
 // A training step issues ~850 launches through ~190 autograd nodes; with the bodies in Python (tensor normalisation, output allocation,
 // ctypes marshalling, gradient-sink bookkeeping) the host needs ~20 ms per step -- as long as the GPU does (profiles/r6_train_host_profile.txt:
 // a Linear node 32 us, a fused BondFFN node 110 us forward).  This module is the same logic against the same C ABI (include/moldiff_hip.h,
 // libmoldiff_hip.so), a pybind11 extension of the torch build in this image:
-//   * the gradient sink and the weight-gradient queue (train_ops.grad_sink / _flush_wgrads / flush_grad_sink) as C++ state,
+//   * the gradient sink and the weight-gradient queue as C++ state (train_ops.grad_sink / flush_grad_sink / sgemm_tn forward to it; every
+//     sink record and queue entry of every precision mode is made here),
 //   * Linear, Linear+LayerNorm+ReLU and the element-wise operators as torch::autograd::Function nodes,
 //   * forward / backward bodies of the four fused row-owner operators (argument structs, buffers, queue entries, segment sums).
-// It covers the float16 autocast mode with float16 containers inside a gradient sink (Trainer.step with precision='fp16', the reference's
-// use_amp: True); every other mode keeps the Python bodies.  torch is plumbing here too: allocation, autograd edges, the current stream.
+// The nodes and bodies cover the float16 autocast mode with float16 containers inside a gradient sink (Trainer.step with precision='fp16',
+// the reference's use_amp: True); every other mode keeps the Python bodies.  torch is plumbing here too: allocation, autograd edges, the
+// current stream.
 // Reference lines replaced are those the Python bodies cite (models/common.py:181-201, models/graph.py:29-55,133-141,268-295,384-396).
 #include <torch/extension.h>
 #include <torch/csrc/autograd/custom_function.h>
@@ -120,7 +123,8 @@ void sink_add(std::vector<int64_t>& recs, int64_t& counter, int64_t Pp, int64_t 
   counter += nchunks * ((rows_ * cols + 127) / 128);
 }
 
-// train_ops._sink_record
+// one gradient record: a repeated destination flushes what is recorded first (the reduction's read-modify-writes are not atomic); more
+// than RED_CHUNK partials take the two fixed-order stages of the per-layer reduction (a chunked record, then one over the chunk sums)
 void sink_record(int64_t Pp, int64_t dst, int64_t Sn, int64_t rows_, int64_t cols, int64_t ld, int64_t pstride, int64_t rkind,
                  const Tensor& keep) {
   TORCH_CHECK(S.sink, "sink_record outside a gradient sink");
@@ -145,7 +149,7 @@ Tensor to_device_i64(const std::vector<int64_t>& v) {
   return dev;
 }
 
-// train_ops._flush_wgrads
+// run the queued weight gradients (one launch per tile class, the long blocks first) and hand their partials to the sink
 void flush_wgrads() {
   if (!S.sink || S.wq.empty()) return;
   std::vector<Job> jobs;
@@ -201,7 +205,7 @@ void flush_wgrads() {
   // the operands (jobs) are released here: the launches above are enqueued, the allocator reuses memory in stream order
 }
 
-// train_ops.flush_grad_sink
+// every recorded gradient summed into its slot of the flat gradient buffer (train_ops.flush_grad_sink)
 void flush_sink() {
   if (!S.sink) return;
   flush_wgrads();
@@ -831,7 +835,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_precision", [](int a0, int autoc, int store) { S.amp0 = a0, S.amp_auto = autoc, S.amp_store = store; });
   m.def("set_options", [](bool wq_on, int64_t rows_, int64_t cap_bytes) { S.wq_on = wq_on, S.wgrad_rows = rows_, S.wq_cap = cap_bytes; });
   m.def("sink_begin", [](const Tensor& data, const Tensor& grad) {
-    TORCH_CHECK(!S.sink, "gradient sinks do not nest in the fast path");
+    TORCH_CHECK(!S.sink, "gradient sinks do not nest");
     S.sink = true, S.s_data = A(data), S.s_grad = A(grad), S.s_nbytes = data.numel() * 4, S.like = data;
     S.recs.clear(), S.recs2.clear(), S.keep.clear(), S.seen.clear(), S.wq.clear();
     S.blocks = S.blocks2 = S.wq_bytes = 0;

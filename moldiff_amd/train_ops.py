@@ -16,28 +16,27 @@ ADD, SUB, MUL, GATE = 0, 1, 2, 3
 
 # ---- C++ fast path (round 6; csrc/mdx_fast.cpp -> moldiff_amd/_mdx_fast.so) ------------------------------------------------------------
 # The operator bodies below cost the host ~20 ms per training step in Python (a Linear node 32 us, a fused BondFFN node 110 us) -- as
-# long as the GPU needs for the step.  `_mdx_fast` holds the same logic in C++ against the same C ABI: the gradient sink and the
-# weight-gradient queue as C++ state, Linear / Linear+LayerNorm+ReLU / element-wise nodes as C++ autograd functions, the fused operators'
-# forward / backward bodies.  With it loaded, EVERY sink record and queue entry goes through the C++ state (any precision mode); the fast
-# nodes themselves cover the float16 autocast mode with float16 containers inside a sink (Trainer.step, precision='fp16').  MDX_TRAIN_FAST=0
-# keeps the Python bodies (the two are bit-identical: tests/test_gpu_trainer.py).  A missing extension is an error, not a silent slow path.
-_FAST_ON = __import__('os').environ.get('MDX_TRAIN_FAST', '1') != '0'
+# long as the GPU needs for the step.  `_mdx_fast` holds the same logic in C++ against the same C ABI: Linear / Linear+LayerNorm+ReLU /
+# element-wise nodes as C++ autograd functions and the fused operators' forward / backward bodies, for the float16 autocast mode with
+# float16 containers inside a sink (Trainer.step, precision='fp16'); the Python bodies serve every other mode.  The gradient sink and the
+# weight-gradient queue exist only there, as C++ state: every sink record and queue entry goes through it, in any precision mode.  A
+# missing extension is an error, not a silent slow path.
 _FASTMOD = None
+# False: the Python operator bodies also serve the float16 sink (the sink and the queue stay in C++).  For the test that holds the two
+# bit-identical (tests/test_gpu_trainer.py); not an environment switch.
+_CPP_NODES = True
 
 
 def _fast():
-    """the C++ extension, or None when MDX_TRAIN_FAST=0"""
+    """the C++ extension"""
     global _FASTMOD
-    if not _FAST_ON:
-        return None
     if _FASTMOD is None:
         _lib.lib()      # libmoldiff_hip.so first (the extension links it)
         try:
             from . import _mdx_fast
         except ImportError as e:
             raise RuntimeError('moldiff_amd/_mdx_fast.so (the C++ fast path of the training operators) is not built or does not load: run '
-                               '`python -c "import __graft_entry__ as g; g.build()"` (make -C moldiff_amd/csrc), or set MDX_TRAIN_FAST=0 for '
-                               f'the Python operator bodies.  [{e}]') from e
+                               f'`python -c "import __graft_entry__ as g; g.build()"` (make -C moldiff_amd/csrc).  [{e}]') from e
         _FASTMOD = _mdx_fast
         _FASTMOD.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
     return _FASTMOD
@@ -144,98 +143,56 @@ def _t4(t):
 # per-wave partial rows) where they are, records {partials, destination slot in the flat GRADIENT buffer, sizes} and returns None.
 # `flush_grad_sink()` -- called once after backward -- sums every record in ONE launch (`mdx_op_reduce_deferred`, same fixed order as
 # the per-layer reduction kernels) straight into the flat gradient buffer.  That replaces ~660 reduction launches and ~540 of torch's
-# accumulation / slice-gradient kernels per step.  Without a sink everything goes through autograd as before.
-_SINK = None
+# accumulation / slice-gradient kernels per step.  Without a sink everything goes through autograd as before.  The records live in
+# the extension (csrc/mdx_fast.cpp sink_record / flush_sink: the chunked two-stage records, a repeated destination flushing first).
+_SINK = None      # (parameter buffer address, gradient buffer address, bytes) of the active sink
 
 
 class grad_sink:
+    """Sinks do not nest; the flat buffers must be on the GPU."""
+
     def __init__(self, flat):
         self.flat = flat
 
     def __enter__(self):
         global _SINK
         f = self.flat
-        self.prev = _SINK
-        _SINK = {'data': f.data.data_ptr(), 'grad': f.grad.data_ptr(), 'nbytes': f.data.numel() * 4, 'recs': [], 'recs2': [], 'keep': [], 'blocks': 0, 'blocks2': 0,
-                 'device': f.data.device, 'seen': set(), 'wq': [], 'wq_bytes': 0, 'fast': None}
-        F = _fast() if (f.data.is_cuda and self.prev is None) else None     # (a nested sink keeps the Python bookkeeping)
-        if F is not None and not F.sink_active():
-            _fast_sync_precision()
-            F.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
-            F.sink_begin(f.data, f.grad)
-            _SINK['fast'] = F
+        _lib._need_gpu(f.data)
+        F = _fast()
+        _fast_sync_precision()
+        F.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
+        F.sink_begin(f.data, f.grad)          # (raises inside an active sink)
+        _SINK = (f.data.data_ptr(), f.grad.data_ptr(), f.data.numel() * 4)
         return self
 
     def __exit__(self, *exc):
         global _SINK
-        if _SINK is not None and _SINK['fast'] is not None:
-            _SINK['fast'].sink_end()          # (flushes what is left)
-        elif _SINK is not None and (_SINK['recs'] or _SINK['wq']):
-            flush_grad_sink()
-        _SINK = self.prev
+        _SINK = None
+        _FASTMOD.sink_end()                   # (flushes what is left)
+
+
+def _cpp():
+    """the extension where the C++ operator nodes may run (inside a gradient sink), else None"""
+    return _FASTMOD if (_SINK is not None and _CPP_NODES) else None
 
 
 def _sink_dst(t):
     """address of `t`'s slot in the flat gradient buffer when t (a parameter or a view of one) lives in the sink's parameter buffer"""
     if _SINK is None or t is None:
         return None
-    off = t.data_ptr() - _SINK['data']
-    return _SINK['grad'] + off if 0 <= off < _SINK['nbytes'] else None
+    off = t.data_ptr() - _SINK[0]
+    return _SINK[1] + off if 0 <= off < _SINK[2] else None
 
 
 def _sink_record(part_ptr, dst, S, rows, cols, ld, pstride, rkind, keep):
-    sk = _SINK
-    if sk['fast'] is not None:
-        sk['fast'].sink_record(part_ptr, dst, S, rows, cols, ld, pstride, rkind, keep)
-        return
-    # The reduction launch sums all records of a flush with plain (non-atomic) read-modify-writes, one half wave per 128-element
-    # block of a record: two records for the SAME slot (a layer applied twice, tied weights, a second backward() inside one sink)
-    # would race and lose a contribution.  A repeated destination therefore flushes what has been recorded first -- launches are
-    # stream-ordered, so the second gradient is added on top of the first like autograd's AccumulateGrad would.
-    if dst in sk['seen']:
-        flush_grad_sink()
-    sk['seen'].add(dst)
-    if S > _RED_CHUNK:
-        # more partials than one chunk (a LayerNorm over the E edge rows leaves E / 64 partial rows): the two fixed-order stages of the
-        # per-layer reduction (csrc launch_reduce_partials) -- a `chunked` record (bit 6) makes the first launch store the sum of each
-        # chunk of 256 in the scratch planes the workspace / wgrad layouts keep right behind the partials; their sum is a second launch
-        nc = (S + _RED_CHUNK - 1) // _RED_CHUNK
-        _sink_add(sk['recs'], 'blocks', part_ptr, dst, S, rows, cols, ld, pstride, 64, nc)
-        _sink_add(sk['recs2'], 'blocks2', part_ptr + 4 * S * pstride, dst, nc, rows, cols, ld, pstride, rkind)
-    else:
-        _sink_add(sk['recs'], 'blocks', part_ptr, dst, S, rows, cols, ld, pstride, rkind)
-    sk['keep'].append(keep)
-
-
-_RED_CHUNK = 256     # = RED_CHUNK of csrc/mdx_train.hip
-
-
-def _sink_add(recs, counter, P, dst, S, rows, cols, ld, pstride, rkind, nchunks=1):
-    sk = _SINK
-    recs.append((P, dst, S, rows, cols, ld, pstride, rkind | (sk[counter] << 8)))
-    sk[counter] += nchunks * ((rows * cols + 127) // 128)
+    _FASTMOD.sink_record(part_ptr, dst, S, rows, cols, ld, pstride, rkind, keep)
 
 
 def flush_grad_sink():
     """every recorded gradient summed into its slot of the flat gradient buffer: one launch, plus one over the chunk sums of the
     records that had more than 256 partials"""
-    sk = _SINK
-    if sk is None:
-        return
-    if sk['fast'] is not None:
-        sk['fast'].flush()
-        return
-    _flush_wgrads()
-    if not sk['recs']:
-        return
-    for recs, counter in ((sk['recs'], 'blocks'), (sk['recs2'], 'blocks2')):
-        if recs:
-            desc = torch.tensor(recs, dtype=torch.int64).to(sk['device'], non_blocking=True)
-            check(_L().mdx_op_reduce_deferred(ptr(desc), len(recs), sk[counter], stream()))
-            sk['keep'].append(desc)
-    # the partial buffers may be reused once the launches above have been enqueued (stream order); drop the references
-    sk['recs'], sk['recs2'], sk['keep'], sk['blocks'], sk['blocks2'] = [], [], [], 0, 0
-    sk['seen'] = set()
+    if _SINK is not None:
+        _FASTMOD.flush()
 
 
 def sgemm_nt(a, b, bias=None, splits=1, addend=None, keep32=False, out_dtype=None):
@@ -303,66 +260,15 @@ def _wgrad_layout(M, N, K, splits, half):
 
 # ---- queued weight gradients (round 6) -----------------------------------------------------------------------------------------
 # Inside a gradient sink, in the float16 autocast mode, a deferred weight gradient is not launched where autograd reaches it: the
-# contraction is QUEUED (operands kept alive) and `_flush_wgrads` -- at the end of backward, or when the queue holds WGRAD_QUEUE_BYTES
-# of operands -- runs the whole queue as one launch per tile class (csrc wgrad_grouped_kernel) with the partials in ONE buffer; the
-# sink records are made then.  ~260 launches (and as many partial-buffer allocations) per step become <= 5; the row ranges are chosen
-# for the queue as a whole (WGRAD_ROWS rows per block; a stand-alone launch needs ~512 blocks of its own to fill the chip, i.e. up to
-# 128 row ranges = 33 MB of partials for one 256 x 256 weight).  MDX_WGRAD_GROUPED=0 keeps the per-call launches.
+# contraction is QUEUED in the extension (operands kept alive) and its flush -- at the end of backward, or when the queue holds
+# WGRAD_QUEUE_BYTES of operands -- runs the whole queue as one launch per tile class (csrc wgrad_grouped_kernel) with the partials in ONE
+# buffer; the sink records are made then (csrc/mdx_fast.cpp wq_append / flush_wgrads).  ~260 launches (and as many partial-buffer
+# allocations) per step become <= 5; the row ranges are chosen for the queue as a whole (WGRAD_ROWS rows per block; a stand-alone launch
+# needs ~512 blocks of its own to fill the chip, i.e. up to 128 row ranges = 33 MB of partials for one 256 x 256 weight).
+# MDX_WGRAD_GROUPED=0 keeps the per-call launches.
 _WG_ON = __import__('os').environ.get('MDX_WGRAD_GROUPED', '1') != '0'
 WGRAD_ROWS = int(__import__('os').environ.get('MDX_WGRAD_ROWS', '2048'))
 WGRAD_QUEUE_BYTES = int(float(__import__('os').environ.get('MDX_WGRAD_QUEUE_GB', '24')) * 2 ** 30)
-_PLANS = {}
-
-
-def _wgrad_plan(M, N, K, dt, ldg, ldx, aligned):
-    """(kind, gx, gy, S, mper, bias offset, partial floats, blocks) of a queued weight gradient (csrc mdx_op_wgrad_plan), cached per shape"""
-    key = (M, N, K, dt, ldg, ldx, aligned, WGRAD_ROWS)
-    r = _PLANS.get(key)
-    if r is None:
-        import ctypes
-        out = (ctypes.c_int64 * 8)()
-        check(_L().mdx_op_wgrad_plan(M, N, K, max(1, (M + WGRAD_ROWS - 1) // WGRAD_ROWS), dt, ldg, ldx, aligned, out))
-        r = _PLANS[key] = tuple(out)
-    return r
-
-
-def _flush_wgrads():
-    """run the queued weight gradients (one launch per tile class) and hand their partials to the gradient sink"""
-    sk = _SINK
-    if sk is None or not sk['wq']:
-        return
-    jobs, sk['wq'], sk['wq_bytes'] = sk['wq'], [], 0
-    total = sum((j[2][6] + 3) // 4 * 4 for j in jobs)
-    part = torch.empty(total, dtype=torch.float32, device=sk['device'])
-    base, off = part.data_ptr(), 0
-    by_kind, placed = {}, []
-    for g, x, plan, dims, dst_w, ldw, dst_b, rk in jobs:
-        kind, gx, gy, S, mper, boff, psize, blocks = plan
-        M, N, K, dt = dims
-        P = base + 4 * off
-        by_kind.setdefault(kind, []).append([g.data_ptr(), x.data_ptr(), P, (P + 4 * boff) if dst_b is not None else 0, g.stride(0), x.stride(0),
-                                             M, N, K, mper, gx, gy, S, dt, 0, blocks])
-        placed.append((P, S, N, K, boff, dst_w, ldw, dst_b, rk))
-        off += (psize + 3) // 4 * 4
-    rows, launches = [], []
-    for kind in sorted(by_kind):
-        recs = by_kind[kind]
-        recs.sort(key=lambda r: -r[9])       # the long blocks first (no tail of E-row blocks behind the N-row jobs)
-        fb = 0
-        for r in recs:
-            r[14], fb = fb, fb + r[15]
-        launches.append((kind, len(rows), len(recs), fb))
-        rows += recs
-    desc = torch.tensor(rows, dtype=torch.int64).to(sk['device'], non_blocking=True)
-    st = stream()
-    for kind, start, n, tb in launches:
-        check(_L().mdx_op_wgrad_grouped(desc.data_ptr() + 128 * start, n, tb, kind, st))
-    sk['keep'] += [part, desc]
-    for P, S, N, K, boff, dst_w, ldw, dst_b, rk in placed:
-        _sink_record(P, dst_w, S, N, K, ldw, N * K, rk, None)
-        if dst_b is not None:
-            _sink_record(P + 4 * boff, dst_b, S, 1, N, N, N, rk, None)
-    sk['keep'] += [part, desc]       # (again: a repeated destination above flushes the sink, which drops its references)
 
 
 def sgemm_tn(g, x, splits, want_bias=False, defer=None):
@@ -374,16 +280,7 @@ def sgemm_tn(g, x, splits, want_bias=False, defer=None):
     splits = max(1, int(splits))
     if defer is not None and _WG_ON and _SINK is not None and _AMP is not None and _AMP[0] == 2 and g.stride(1) == 1 and x.stride(1) == 1:
         dst_w, ldw, dst_b = defer
-        if _SINK['fast'] is not None:
-            _SINK['fast'].wq_append(g, x, dst_w, ldw, (dst_b or 0) if want_bias else 0, _AMP[0] if _AMP[1] else 0)
-            return None
-        dt = _h(g) | (_h(x) << 1)
-        plan = _wgrad_plan(M, N, K, dt, g.stride(0), x.stride(0), int(g.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0))
-        sk = _SINK
-        sk['wq'].append((g, x, plan, (M, N, K, dt), dst_w, ldw, dst_b if want_bias else None, _AMP[0] if _AMP[1] else 0))
-        sk['wq_bytes'] += g.numel() * g.element_size() + x.numel() * x.element_size()
-        if sk['wq_bytes'] > WGRAD_QUEUE_BYTES:
-            _flush_wgrads()
+        _FASTMOD.wq_append(g, x, dst_w, ldw, (dst_b or 0) if want_bias else 0, _AMP[0] if _AMP[1] else 0)
         return None
     part = torch.empty((splits + (splits + 255) // 256) * (N * K + N), dtype=torch.float32, device=g.device)
     if defer is not None:
@@ -602,9 +499,9 @@ def linear(x, w, b=None, addend=None, keep32=False):
     (used for the per-node part of a layer whose reference input is a concatenation [edge part | node part | time]).
     keep32: the result is itself such a partial sum -- an autocast mode must not round it (the reference rounds the WHOLE layer's
     result once)."""
-    sk = _SINK
-    if sk is not None and sk['fast'] is not None and sk['fast'].linear_fast_ok(x, w, b):
-        return sk['fast'].linear(x, w, b, addend, bool(keep32))
+    F = _cpp()
+    if F is not None and F.linear_fast_ok(x, w, b):
+        return F.linear(x, w, b, addend, bool(keep32))
     return _Linear.apply(x, w, b, addend, keep32)
 
 
@@ -722,9 +619,9 @@ class _LinearLnRelu(torch.autograd.Function):
 def linear_ln_relu(x, w, b, gamma, beta, addend=None):
     """relu(LayerNorm(x @ w.T + b + addend)): one launch where the fused kernel is built, the two operators otherwise"""
     if linear_ln_ok(x, w, addend):
-        sk = _SINK
-        if sk is not None and sk['fast'] is not None and sk['fast'].linear_ln_fast_ok(x, w, b, gamma, beta):
-            return sk['fast'].linear_ln_relu(x, w, b, addend, gamma, beta)
+        F = _cpp()
+        if F is not None and F.linear_ln_fast_ok(x, w, b, gamma, beta):
+            return F.linear_ln_relu(x, w, b, addend, gamma, beta)
         return _LinearLnRelu.apply(x, w, b, addend, gamma, beta)
     return ln_relu(linear(x, w, b, addend=addend), gamma, beta, True)
 
@@ -733,10 +630,10 @@ def linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2):
     """linear(relu(LayerNorm(x @ w.T + b)), w2, b2) with w2 of ONE row -- common.MLP(…, 1) as PosUpdate's inter module uses it.  On the
     C++ fast path (float16 mode inside a sink) one node whose backward forms the second Linear's rank-1 data gradient inside the LayerNorm
     backward (csrc mdx_op_ln_relu_bwd_r1_t); otherwise the two operators."""
-    sk = _SINK
-    if (sk is not None and sk['fast'] is not None and b is not None and b2 is not None and linear_ln_ok(x, w, None)
-            and sk['fast'].linear_ln_dot_fast_ok(x, w, b, gamma, beta, w2, b2)):
-        return sk['fast'].linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2)
+    F = _cpp()
+    if (F is not None and b is not None and b2 is not None and linear_ln_ok(x, w, None)
+            and F.linear_ln_dot_fast_ok(x, w, b, gamma, beta, w2, b2)):
+        return F.linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2)
     return linear(linear_ln_relu(x, w, b, gamma, beta), w2, b2)
 
 
@@ -769,9 +666,9 @@ class _Ew(torch.autograd.Function):
 
 
 def _ew(op, a, b):
-    sk = _SINK
-    if sk is not None and sk['fast'] is not None and a.is_cuda and sk['fast'].fast_mode():
-        return sk['fast'].ew(op, a, b)
+    F = _cpp()
+    if F is not None and a.is_cuda and F.fast_mode():
+        return F.ew(op, a, b)
     return _Ew.apply(op, a, b)
 
 
@@ -1295,16 +1192,19 @@ class _PosFfnFront(torch.autograd.Function):
         bufs = {'a': h(64), 'prod': h(256), 'gpre': h(32), 'gpost': h(32), 'gate': h(1)}
         a = _PosFfnFront._args(x, LFc, RFc, tc, plan_l, plan_r, P, bufs, E)
         check(_L().mdx_op_posffn_fwd(ctypes.byref(a), stream()))
+        prod, gate = bufs.pop('prod'), bufs.pop('gate')
+        ctx.save_for_backward(prod, gate)     # (the outputs: on ctx itself they would form a cycle output -> grad_fn -> ctx -> output)
         ctx.x, ctx.LF, ctx.RF, ctx.tc, ctx.P, ctx.bufs = x, LFc, RFc, tc, P, bufs
         ctx.plan_l, ctx.plan_r, ctx.prec, ctx.x_dtype = plan_l, plan_r, _AMP, h_edge.dtype
         ctx.refs = {k: v.detach() for k, v in zip(_PosFfnFront.PARAMS, params)}
         ctx.time2d = time.detach().reshape(-1, 1)
-        return bufs['prod'], bufs['gate']
+        return prod, gate
 
     @staticmethod
     def backward(ctx, g_prod, g_gate):
         import ctypes
-        x, P, bufs, E, dev = ctx.x, ctx.P, ctx.bufs, ctx.x.shape[0], ctx.x.device
+        prod, gate = ctx.saved_tensors
+        x, P, bufs, E, dev = ctx.x, ctx.P, dict(ctx.bufs, prod=prod, gate=gate), ctx.x.shape[0], ctx.x.device
         f16 = lambda t, f: (torch.zeros(E, f, dtype=torch.float16, device=dev) if t is None else
                             (t if t.dtype == torch.float16 else t.to(torch.float16)).contiguous())
         g_prod, g_gate = f16(g_prod, 256), f16(g_gate, 1)
@@ -1510,8 +1410,7 @@ def cat_loss(transition, logits, log_vt, log_v0, t, batch):
 # allocates, launches, queues the weight gradients and runs the segment sums.  Parameter gradients never pass through autograd here (every
 # parameter lives in the gradient sink: `all_in_sink`), so the shells return None for them.
 def _fast_for(params):
-    sk = _SINK
-    F = sk['fast'] if sk is not None else None
+    F = _cpp()
     return F if (F is not None and F.all_in_sink(params)) else None
 
 
@@ -1566,8 +1465,9 @@ class _PosFfnFrontF(torch.autograd.Function):
         ps = list(params)
         ctx.prec = _AMP
         r = F.posffn_fwd(h_edge, LF, RF, time, plan_l.index, plan_r.index, ps)
-        # saved for the backward: [x, LF, RF, te, a, gpre, gpost, prod, gate]
-        ctx.F, ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r, ctx.x_dtype = F, r[2:] + [r[0], r[1]], ps, plan_l, plan_r, h_edge.dtype
+        # saved for the backward: [x, LF, RF, te, a, gpre, gpost] on ctx, the outputs [prod, gate] through save_for_backward (no cycle)
+        ctx.save_for_backward(r[0], r[1])
+        ctx.F, ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r, ctx.x_dtype = F, r[2:], ps, plan_l, plan_r, h_edge.dtype
         ctx.time2d = time.detach().reshape(-1, 1)
         return r[0], r[1]
 
@@ -1575,8 +1475,8 @@ class _PosFfnFrontF(torch.autograd.Function):
     def backward(ctx, g_prod, g_gate):
         ni, pl, pr = ctx.needs_input_grad, ctx.plan_l, ctx.plan_r
         with precision(ctx.prec):
-            g = ctx.F.posffn_bwd(g_prod, g_gate, ctx.saved, pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr, pl.n, ctx.time2d, ctx.ps,
-                                 ni[1], ni[2], ni[3])
+            g = ctx.F.posffn_bwd(g_prod, g_gate, ctx.saved + list(ctx.saved_tensors), pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr,
+                                 pl.n, ctx.time2d, ctx.ps, ni[1], ni[2], ni[3])
         gx = g[0]
         if gx is not None and gx.dtype != ctx.x_dtype:
             gx = gx.to(ctx.x_dtype)

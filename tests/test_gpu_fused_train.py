@@ -291,3 +291,44 @@ def test_fused_node_block_equals_the_per_operator_composition(sizes):
     for k in gr0:
         assert torch.isfinite(gr1[k]).all(), k
         assert _rel2(gr1[k], gr0[k]) < 1e-2, (k, _rel2(gr1[k], gr0[k]))
+
+
+@pytest.mark.parametrize('sink', [True, False])
+def test_posffn_front_outputs_are_freed_without_backward(sink):
+    """The fused PosUpdate front keeps its outputs prod (E,256) and gate (E,1) for the backward.  Held on the autograd context they
+    formed a cycle (output -> grad_fn -> ctx -> output): a forward that is never back-propagated kept them until the cyclic collector
+    ran.  Saved through save_for_backward they are freed as soon as the caller drops them -- on the C++ shell (fp16 sink) and on the
+    Python body (no sink)."""
+    import gc
+    import weakref
+    from moldiff_amd.trainer import FlatParams
+    g = U.rng(37)
+    bn, hei, bh, ei, be = U.graph_from_sizes([24, 31, 18, 27])
+    N, E = len(bn), ei.shape[1]
+    m = G.PosUpdate(256, 64, 64, True).to(DEV)
+    flat = FlatParams(m)
+    ff = m.edge_lin
+    g0, gt = ff.gate.net[0], ff.gate.net
+    params = dict(Wb=ff.bond_linear.weight, Wn=ff.node_linear.weight, Wg1x=g0.weight[:, :64], Wg1a=g0.weight[:, 64:128],
+                  Wt=g0.weight[:, 128:], bg1=g0.bias, gg=gt[1].weight, gbe=gt[1].bias, Wg2=gt[3].weight, bg2=gt[3].bias)
+    he = torch.from_numpy(g.standard_normal((E, 64)).astype(np.float32)).to(DEV).half().requires_grad_(True)
+    lf, rf = (torch.from_numpy(g.standard_normal((N, 64)).astype(np.float32)).to(DEV).half() for _ in range(2))
+    te = torch.from_numpy(g.random((E, 1)).astype(np.float32)).to(DEV)
+    tg = TG.TrainGraph(ei.to(DEV), N)
+    old_rows, was_enabled = T.FUSED_MIN_ROWS, gc.isenabled()
+    T.FUSED_MIN_ROWS = 1
+    gc.disable()
+    try:
+        with T.grad_sink(flat) if sink else torch.enable_grad(), T.precision('fp16'):
+            assert T.posffn_fused_ok(he, lf, rf, (64, 64, 256, 32, 1))
+            prod, gate = T.posffn_front(he, lf, rf, te, tg.left, tg.right, params)
+            name = type(prod.grad_fn).__name__
+            refs = weakref.ref(prod), weakref.ref(gate)
+            del prod, gate
+        torch.cuda.synchronize()
+        assert name == ('_PosFfnFrontFBackward' if sink else '_PosFfnFrontBackward'), name
+        assert refs[0]() is None and refs[1]() is None
+    finally:
+        T.FUSED_MIN_ROWS = old_rows
+        if was_enabled:
+            gc.enable()

@@ -47,6 +47,21 @@ def test_flat_views_alias_the_parameters():
     assert float(m.weight.grad.abs().sum()) == 0.0
 
 
+def test_gradient_sinks_do_not_nest():
+    """The sink's records and queue are one C++ state: a second sink inside an active one raises and leaves the first one working."""
+    from moldiff_amd import train_ops
+    m = torch.nn.Linear(64, 64).to(DEV)
+    f = FlatParams(m)
+    x = torch.randn(300, 64, device=DEV)
+    with train_ops.grad_sink(f):
+        with pytest.raises(RuntimeError, match='do not nest'):
+            with train_ops.grad_sink(FlatParams(torch.nn.Linear(4, 4).to(DEV))):
+                pass
+        train_ops.linear(x, m.weight, m.bias).sum().backward()
+    assert train_ops._SINK is None
+    assert float((m.weight.grad - x.sum(0).expand(64, 64)).abs().max()) <= 1e-4 * float(x.abs().sum(0).max())
+
+
 def _tiny_batch(seed, sizes=(6, 9, 5, 11)):
     g = U.rng(seed)
     bn, hei, bh, _, _ = U.graph_from_sizes(list(sizes), DEV)
@@ -423,7 +438,7 @@ def test_class_range_assert_is_postponed_not_dropped():
 @pytest.mark.parametrize('rows', [64, 2048])
 def test_queued_weight_gradients_equal_the_per_call_launches(rows):
     """Round 6: inside a gradient sink the float16 mode queues every weight-gradient contraction and runs the queue as one launch per
-    tile class (train_ops._flush_wgrads, csrc wgrad_grouped_kernel).  The flat gradient buffer must be what the per-call launches
+    tile class (csrc/mdx_fast.cpp flush_wgrads, csrc wgrad_grouped_kernel).  The flat gradient buffer must be what the per-call launches
     produce: same contraction bodies, fp32 partials; only the row ranges differ (rows per block instead of ~512 blocks per call), so
     the two agree to fp32 summation-order rounding before the final float16 rounding of each sum (<= 1 float16 ulp on an element)."""
     import copy
@@ -497,11 +512,12 @@ def test_fused_categorical_loss_equals_the_torch_tail():
 
 
 @pytest.mark.parametrize('fused_rows', [1024, 1])
-def test_cpp_fast_path_is_bit_identical_to_the_python_bodies(fused_rows):
-    """Round 6: csrc/mdx_fast.cpp (moldiff_amd/_mdx_fast.so) holds the training operators' host logic in C++ -- gradient sink, weight-
-    gradient queue, Linear / Linear+LayerNorm / element-wise autograd nodes, the fused operators' bodies.  Same kernels, same buffers,
-    same row ranges: the loss, the flat gradient buffer and the updated weights of two optimisation steps must be BIT-identical with
-    MDX_TRAIN_FAST on and off (fused_rows = 1: with the fused row-owner kernels forced on at this size, so their C++ bodies run)."""
+def test_cpp_nodes_are_bit_identical_to_the_python_bodies(fused_rows):
+    """Round 6: csrc/mdx_fast.cpp (moldiff_amd/_mdx_fast.so) holds the training operators' host logic in C++ -- Linear / Linear+LayerNorm
+    / element-wise autograd nodes, the fused operators' bodies -- next to the gradient sink and weight-gradient queue it alone implements.
+    Same kernels, same buffers, same row ranges: the loss, the flat gradient buffer and the updated weights of two optimisation steps
+    must be BIT-identical with the C++ nodes (train_ops._CPP_NODES) on and off (fused_rows = 1: with the fused row-owner kernels forced
+    on at this size, so their C++ bodies run)."""
     import copy
     from moldiff_amd import train_ops
     base = U.moldiff('MolDiff', DEV)
@@ -512,11 +528,11 @@ def test_cpp_fast_path_is_bit_identical_to_the_python_bodies(fused_rows):
     noise = dict(eps_pos=U.t32(g.standard_normal((N, 3))).to(DEV), u_node=U.t32(g.random((N, 8))).to(DEV),
                  u_halfedge=U.t32(g.random((Eh, 6))).to(DEV))
     res = {}
-    old = (train_ops._FAST_ON, train_ops.FUSED_MIN_ROWS)
+    old = (train_ops._CPP_NODES, train_ops.FUSED_MIN_ROWS)
     try:
         train_ops.FUSED_MIN_ROWS = fused_rows
         for fast in (False, True):
-            train_ops._FAST_ON = fast
+            train_ops._CPP_NODES = fast
             m = copy.deepcopy(base)
             for mod in m.modules():
                 if hasattr(mod, '_eng'):
@@ -530,7 +546,7 @@ def test_cpp_fast_path_is_bit_identical_to_the_python_bodies(fused_rows):
             if fast:
                 assert train_ops._fast().launches() - n0 > 100        # the C++ bodies did run
     finally:
-        train_ops._FAST_ON, train_ops.FUSED_MIN_ROWS = old
+        train_ops._CPP_NODES, train_ops.FUSED_MIN_ROWS = old
     a, b = res[False], res[True]
     assert a[0] == b[0] and a[1] == b[1] and a[5] == b[5], (a[0], b[0], a[1], b[1])
     assert float(a[2].abs().max()) > 0

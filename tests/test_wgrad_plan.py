@@ -1,7 +1,7 @@
 """mdx_op_wgrad_plan (csrc/mdx_train.hip) is host logic: which tile class a queued weight-gradient contraction takes and how its rows
-are cut into blocks.  Checked here without a GPU through the C ABI: the classes of the training step's shapes (tools/dump_wgrad_jobs.py),
-the rows per block each class gets (round 6: 2,048 for the 128-wide classes, 1,024 for the 64- / 32-wide ones, 512 for the converting
-kernel, 256 for the scaled column sums) and the consistency of the block / partial-area arithmetic the host code relies on."""
+are cut into blocks.  Checked here without a GPU through the C ABI: the classes of the training step's shapes, the rows per block
+each class gets (round 6: 2,048 for the 128-wide classes, 1,024 for the 64- / 32-wide ones, 512 for the converting kernel, 256 for the
+scaled column sums) and the consistency of the block / partial-area arithmetic the host code relies on."""
 import ctypes
 import os
 
