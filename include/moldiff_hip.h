@@ -254,6 +254,37 @@ int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tables,
                          float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise, int64_t* t_buf, uint8_t* node_cls,
                          uint8_t* halfedge_cls, const mdx_guidance* guide, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- scaffold-constrained sampling (replacement conditioning; NO reference line: the reference has no conditional sampling).
+ * Overwrites the FIXED rows of the state `next` with a draw from q(x_level | x_0) of a known molecule, in one launch and without
+ * a host synchronisation; free rows are neither read nor written.  A conditioned chain calls it after every
+ * mdx_sample_step_full (and after the caller's guidance) with level = step - 1, and once on the prior draw with level = T - 1.
+ *   level >= 0  : pos = sqrt(alphas_bar[level]) x0 + sqrt(1 - alphas_bar[level]) eps in fp32 (ContigousTransition.add_noise,
+ *                 models/transition.py:28-37); class = the Gumbel-max draw of GeneralCategoricalTransition.add_noise
+ *                 (transition.py:245-283) at t = level with the row's uniforms -- the row function of mdx_op_cat_add_noise.  A fixed
+ *                 row receives its one-hot row, its log row log(clamp(onehot, 1e-30)) (log_off as for mdx_prior_draw), its uint8
+ *                 class id (node_cls / halfedge_cls, optional) and its position.
+ *   level == -1 : the end of the chain: fixed rows receive x0 bit for bit and onehot(v0), and the fixed rows of pred_node / pred_pos /
+ *                 pred_halfedge (optional; ignored for level >= 0) the log-one-hot row of v0 and x0, so that mdx_decode_output returns
+ *                 the known atoms and bonds as given, with confidence 1.
+ *   scaffold    : node_mask (N) / halfedge_mask (Eh) bytes, non-zero = fixed, NULL = every row; node_type (N) / halfedge_type (Eh)
+ *                 int64 class ids in [0, K) (checked by the caller; clamped here); node_pos (N,3).  Values on free rows are not read.
+ *   noise       : draw >= 0: the buffers are filled with Philox draw `draw` first (mdx_noise with `seed`; one more launch) -- the
+ *                 chain's own draws are 0..T, a conditioned chain uses T + 1 + i after loop iteration i and 2T + 1 for the initial
+ *                 state; draw < 0: the buffers already hold the noise.  Not read at level -1. */
+typedef struct {
+  const float* alphas_bar;                 /* pos_transition.alphas_bar (T) */
+  const float *node_q_mats, *edge_q_mats;  /* node / edge_transition.q_mats (T,Kn,Kn) / (T,Ke,Ke) */
+  int32_t Kn, Ke, T;                       /* class counts in 2..8 */
+} mdx_scaffold_tables;
+typedef struct {
+  const uint8_t *node_mask, *halfedge_mask;
+  const int64_t *node_type, *halfedge_type;
+  const float* node_pos;
+} mdx_scaffold;
+int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tables, int32_t level, const mdx_scaffold* scaffold,
+                       const mdx_step_noise* noise, const mdx_state* next, float log_off, uint8_t* node_cls, uint8_t* halfedge_cls,
+                       float* pred_node, float* pred_pos, float* pred_halfedge, void* stream);
+
 /* ---- harness consumer of the path's outputs (next-row) ---------------------------------------
  * seperate_outputs (utils/sample.py:4-30) + FeaturizeMol.decode_output (utils/transforms.py:65-122) on the device:
  * arg-max class + soft-max confidence per atom / half-edge, mask-type atoms (class >= num_element) dropped and the

@@ -9,7 +9,8 @@ from .common import AttrDict  # noqa: F401
 from .graph import NodeEdgeNet  # noqa: F401
 from .model import MolDiff  # noqa: F401
 from .bond_predictor import BondPredictor  # noqa: F401
+from .scaffold import Scaffold  # noqa: F401
 from .harness import make_data_placeholder, load_config, seed_all, recipe_state_dict, is_frozen_key  # noqa: F401
 
 __all__ = ['MolDiff', 'BondPredictor', 'NodeEdgeNet', 'make_data_placeholder', 'load_config', 'seed_all',
-           'recipe_state_dict', 'is_frozen_key', 'AttrDict']
+           'recipe_state_dict', 'is_frozen_key', 'AttrDict', 'Scaffold']

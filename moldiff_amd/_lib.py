@@ -22,7 +22,7 @@ EXPORTS = [
     'mdx_net_forward', 'mdx_node_block', 'mdx_edge_block', 'mdx_bond_ffn', 'mdx_pos_update', 'mdx_segment_sum',
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
-    'mdx_guidance_uncertainty_grad', 'mdx_add_inplace', 'mdx_decode_output',
+    'mdx_guidance_uncertainty_grad', 'mdx_add_inplace', 'mdx_decode_output', 'mdx_scaffold_merge',
     'mdx_profile_enable', 'mdx_profile_read', 'mdx_profile_kernel_name',
     'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_hgemm_nt', 'mdx_op_hgemm_tn', 'mdx_op_xgemm_nt', 'mdx_op_xgemm_tn', 'mdx_op_amp_adamw',
     'mdx_op_xgemm_nt_t', 'mdx_op_xgemm_nt_ln_t', 'mdx_op_xgemm_nt_ln_supported', 'mdx_op_xgemm_tn_t', 'mdx_op_ln_relu_fwd_t', 'mdx_op_ln_relu_bwd_t', 'mdx_op_ew_fwd_t', 'mdx_op_ew_bwd_t',
@@ -54,6 +54,15 @@ class MdxGuidance(ctypes.Structure):   # == struct mdx_guidance
 
 class MdxStepNoise(ctypes.Structure):  # == struct mdx_step_noise
     _fields_ = [('seed', c_uint64), ('draw', c_int32), ('eps_pos', c_void_p), ('u_node', c_void_p), ('u_halfedge', c_void_p)]
+
+
+class MdxScaffoldTables(ctypes.Structure):  # == struct mdx_scaffold_tables
+    _fields_ = [('alphas_bar', c_void_p), ('node_q_mats', c_void_p), ('edge_q_mats', c_void_p), ('Kn', c_int32), ('Ke', c_int32),
+                ('T', c_int32)]
+
+
+class MdxScaffold(ctypes.Structure):  # == struct mdx_scaffold
+    _fields_ = [(n, c_void_p) for n in ('node_mask', 'halfedge_mask', 'node_type', 'halfedge_type', 'node_pos')]
 
 
 class MdxBondFfnArgs(ctypes.Structure):   # == mdx_bondffn_args
@@ -178,6 +187,8 @@ def lib():
         L.mdx_add_inplace.argtypes = [c_void_p, c_void_p, c_int64, c_void_p]
         L.mdx_decode_output.argtypes = ([c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32] +
                                         [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p])
+        L.mdx_scaffold_merge.argtypes = [c_void_p, POINTER(MdxScaffoldTables), c_int32, POINTER(MdxScaffold), POINTER(MdxStepNoise),
+                                         POINTER(MdxState), c_float] + [c_void_p] * 6
         L.mdx_device_count.argtypes = [POINTER(c_int)]
         L.mdx_profile_enable.argtypes = [c_int32]
         L.mdx_profile_read.argtypes = [c_int32, POINTER(c_int64), POINTER(ctypes.c_double)]
@@ -515,12 +526,19 @@ def cat_posterior(q_mats, qT, in0, log_vt, t, batch, is_logits=False):
 _LOG_EPS32 = None
 
 
+def log_eps32():
+    """log(1e-30) as torch evaluates it in fp32: the off-class value of a log-one-hot row (models/diffusion.py:53-57)"""
+    global _LOG_EPS32
+    if _LOG_EPS32 is None:
+        _LOG_EPS32 = float(torch.log(torch.tensor([1e-30], dtype=torch.float32))[0])
+    return _LOG_EPS32
+
+
 def cat_add_noise(q_mats, v, t, batch, u, K):
     """GeneralCategoricalTransition.add_noise's arithmetic in one launch (csrc cat_add_noise_kernel) -> (onehot, log_vt, log_v0)"""
     global _LOG_EPS32
     _need_gpu(v, t, batch, u, q_mats)
-    if _LOG_EPS32 is None:
-        _LOG_EPS32 = float(torch.log(torch.tensor([1e-30], dtype=torch.float32))[0])
+    log_eps32()
     v, t, batch, u = i64c(v), i64c(t), i64c(batch), f32c(u)
     n = v.shape[0]
     oh, lvt, lv0 = (torch.empty(n, K, dtype=torch.float32, device=v.device) for _ in range(3))

@@ -1421,6 +1421,40 @@ extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tabl
                           noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream);
 }
 
+extern "C" int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tb, int32_t level, const mdx_scaffold* sc,
+                                  const mdx_step_noise* noise, const mdx_state* next, float log_off, uint8_t* node_cls,
+                                  uint8_t* halfedge_cls, float* pred_node, float* pred_pos, float* pred_halfedge, void* stream) {
+  if (!g || !tb || !sc || !next) return fail(MDX_ERR_ARG, "null argument");
+  if (tb->Kn < 2 || tb->Kn > 8 || tb->Ke < 2 || tb->Ke > 8) return fail(MDX_ERR_UNSUPPORTED, "class counts must be in 2..8");
+  if (level < -1 || level >= tb->T) return fail(MDX_ERR_ARG, "level %d outside [-1, %d)", level, tb->T);
+  const int N = (int)g->N, Eh = (int)g->Eh;
+  if (N == 0) return MDX_OK;
+  if (!sc->node_type || !sc->node_pos || (Eh > 0 && !sc->halfedge_type) || !next->h_node || !next->pos || !next->log_node ||
+      (Eh > 0 && (!next->h_halfedge || !next->log_halfedge)))
+    return fail(MDX_ERR_ARG, "null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  ScaffoldMergeArgs a{};
+  if (level >= 0) {
+    if (!noise || !noise->eps_pos || !noise->u_node || (Eh > 0 && !noise->u_halfedge) || !tb->alphas_bar || !tb->node_q_mats ||
+        (Eh > 0 && !tb->edge_q_mats))
+      return fail(MDX_ERR_ARG, "null noise buffer / table");
+    if (noise->draw >= 0)
+      launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, N, Eh, tb->Kn,
+                          tb->Ke, noise->eps_pos, noise->u_node, noise->u_halfedge, s);
+    a.eps = noise->eps_pos; a.u_node = noise->u_node; a.u_half = noise->u_halfedge;
+  }
+  a.N = N; a.Eh = Eh; a.Kn = tb->Kn; a.Ke = tb->Ke; a.level = level; a.log_off = log_off;
+  a.alphas_bar = tb->alphas_bar; a.node_q = tb->node_q_mats; a.edge_q = tb->edge_q_mats;
+  a.node_mask = sc->node_mask; a.half_mask = sc->halfedge_mask; a.node_type = sc->node_type; a.half_type = sc->halfedge_type;
+  a.node_pos = sc->node_pos;
+  a.pos = next->pos; a.h_node = next->h_node; a.log_node = next->log_node; a.h_half = next->h_halfedge; a.log_half = next->log_halfedge;
+  a.node_cls = node_cls; a.half_cls = halfedge_cls;
+  a.pred_node = pred_node; a.pred_pos = pred_pos; a.pred_half = pred_halfedge;
+  launch_scaffold_merge(a, s);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // bond predictor: forward with a per-block tape, and the data-gradient backward w.r.t. positions
 // ------------------------------------------------------------------------------------------------

@@ -340,6 +340,18 @@ struct StepTransArgs {  // mdx_transition.hip: the transitions of one sampling s
   uint8_t *node_cls, *half_cls;
 };
 void launch_step_transition(const StepTransArgs& a, hipStream_t s);
+struct ScaffoldMergeArgs {  // mdx_transition.hip: fixed rows of a sampler state <- q(x_level | x_0) of a known molecule (level -1: x_0 itself)
+  int N, Eh, Kn, Ke, level;
+  float log_off;
+  const float *alphas_bar, *node_q, *edge_q;
+  const uint8_t *node_mask, *half_mask;  // nullptr = every row is fixed
+  const int64_t *node_type, *half_type;
+  const float *node_pos, *eps, *u_node, *u_half;
+  float *pos, *h_node, *log_node, *h_half, *log_half;
+  uint8_t *node_cls, *half_cls;              // may be nullptr
+  float *pred_node, *pred_pos, *pred_half;   // written at level -1 only; may be nullptr
+};
+void launch_scaffold_merge(const ScaffoldMergeArgs& a, hipStream_t s);
 // the same three sums after an EA_AGG edge kernel A: aggr / SR combine each node's partial rows pbase[v] .. pbase[v+1] of P / PR
 // in order, SL is still the indexed sum over FL
 void launch_seg_reduce_block2(const float* P, const float* PR, const float* FL, const int* pbase, const int* col_ptr,

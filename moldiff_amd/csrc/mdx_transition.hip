@@ -293,21 +293,18 @@ void launch_cat_posterior(const float* qmats, const float* qT1, int K, int T, co
 // cls = argmax(logits + Gumbel(u)); outputs onehot(cls), log(clamp(onehot(cls), 1e-30)), log_v0.  One thread per row, the sum over the K
 // source classes in index order; log_off = log(1e-30) as torch computes it in fp32 (the caller passes torch's value).  Class ids >= K are
 // clamped to K - 1 (the caller's range check reports them: diffusion.deferred_class_checks).
+// The row function: the Gumbel-max draw of q(v_t | v_0 = cv) over the K logits of row Q = q_mats[t] with the row's K uniforms; writes
+// log_v0 (K values) when given and returns the drawn class.  Shared with scaffold_merge_kernel below, so that the conditioned sampler
+// draws its fixed rows with the arithmetic training perturbs them with.
 template <int K>
-__global__ void cat_add_noise_kernel(const float* __restrict__ qmats, const int64_t* __restrict__ v, const int64_t* __restrict__ t,
-                                     const int64_t* __restrict__ batch, const float* __restrict__ u, int n, float log_off,
-                                     float* __restrict__ onehot, float* __restrict__ log_vt, float* __restrict__ log_v0) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int64_t cv = v[i];
-  cv = cv < 0 ? 0 : (cv >= K ? K - 1 : cv);
-  const float* Q = qmats + (size_t)t[batch[i]] * K * K;
+__device__ __forceinline__ int cat_add_noise_row(const float* __restrict__ Q, int cv, const float* __restrict__ u, float log_off,
+                                                 float* __restrict__ log_v0) {
   float l0[K], e0[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    l0[k] = (k == (int)cv) ? 0.f : log_off;
+    l0[k] = (k == cv) ? 0.f : log_off;
     e0[k] = expf(l0[k]);
-    log_v0[(size_t)i * K + k] = l0[k];
+    if (log_v0) log_v0[k] = l0[k];
   }
   int best = 0;
   float bv = -INFINITY;
@@ -317,13 +314,24 @@ __global__ void cat_add_noise_kernel(const float* __restrict__ qmats, const int6
 #pragma unroll
     for (int j = 0; j < K; ++j) f += e0[j] * Q[j * K + k];
     const float lg = fmaxf(logf(f + 1e-30f), -32.f);
-    const float g = -logf(-logf(u[(size_t)i * K + k] + 1e-30f) + 1e-30f);
+    const float g = -logf(-logf(u[k] + 1e-30f) + 1e-30f);
     const float z = g + lg;
     if (k == 0 || z > bv) {  // first maximum wins, like torch.argmax
       bv = z;
       best = k;
     }
   }
+  return best;
+}
+template <int K>
+__global__ void cat_add_noise_kernel(const float* __restrict__ qmats, const int64_t* __restrict__ v, const int64_t* __restrict__ t,
+                                     const int64_t* __restrict__ batch, const float* __restrict__ u, int n, float log_off,
+                                     float* __restrict__ onehot, float* __restrict__ log_vt, float* __restrict__ log_v0) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int64_t cv = v[i];
+  cv = cv < 0 ? 0 : (cv >= K ? K - 1 : cv);
+  const int best = cat_add_noise_row<K>(qmats + (size_t)t[batch[i]] * K * K, (int)cv, u + (size_t)i * K, log_off, log_v0 + (size_t)i * K);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     onehot[(size_t)i * K + k] = (k == best) ? 1.f : 0.f;
@@ -529,4 +537,71 @@ void launch_philox_noise(uint64_t seed, int draw, const int* node_graph, const i
   if (n <= 0) return;
   hipLaunchKernelGGL(philox_noise_kernel, dim3((n + 255) / 256), dim3(256), 0, s, seed, draw, node_graph, node_local,
                      he_graph, he_local, mol_ids, N, Eh, Kn, Ke, eps_pos, u_node, u_half, t_buf, t_val, B);
+}
+
+// ---- scaffold-constrained sampling: replacement conditioning of the reverse chain ---------------------------------------------------------
+// No reference line: the reference has no conditional sampling.  After a step has written its state x_k, the FIXED rows (mask != 0, or every
+// row when the mask is null) are overwritten with a draw from q(x_k | x_0) of the known molecule: positions by the arithmetic of
+// ContigousTransition.add_noise (models/transition.py:28-37: sqrt(abar) x0 + sqrt(1 - abar) eps, separate mul / add), classes through
+// cat_add_noise_row, i.e. exactly as training perturbs them.  All four things the step writes for a row are replaced: one-hot row, log row
+// log(clamp(onehot, 1e-30)), the uint8 class id of the compact trajectory frame and the position.  level = -1 is the end of the chain: the
+// fixed rows receive x_0 itself and the fixed rows of the last prediction (what decode_batch reads) the log-one-hot of v_0 and x_0.
+// Free rows are neither read nor written.  Thread i does atom i and half-edge i.  KT > 0: compile-time class count, 0: dispatch on K.
+template <int KT>
+__device__ __forceinline__ void scaffold_cat_row(int K, const float* __restrict__ qmats, int level, int64_t v, const float* __restrict__ u,
+                                                 float log_off, float* __restrict__ onehot, float* __restrict__ log_row,
+                                                 uint8_t* __restrict__ cls8, float* __restrict__ pred, int i) {
+  const int cv = v < 0 ? 0 : (v >= K ? K - 1 : (int)v);
+  int best = cv;
+  if (level >= 0) {
+    const float* Q = qmats + (size_t)level * K * K;
+    const float* ur = u + (size_t)i * K;
+    if constexpr (KT > 0) {
+      best = cat_add_noise_row<KT>(Q, cv, ur, log_off, nullptr);
+    } else {
+      switch (K) {
+        case 2: best = cat_add_noise_row<2>(Q, cv, ur, log_off, nullptr); break;
+        case 3: best = cat_add_noise_row<3>(Q, cv, ur, log_off, nullptr); break;
+        case 4: best = cat_add_noise_row<4>(Q, cv, ur, log_off, nullptr); break;
+        case 5: best = cat_add_noise_row<5>(Q, cv, ur, log_off, nullptr); break;
+        case 6: best = cat_add_noise_row<6>(Q, cv, ur, log_off, nullptr); break;
+        case 7: best = cat_add_noise_row<7>(Q, cv, ur, log_off, nullptr); break;
+        case 8: best = cat_add_noise_row<8>(Q, cv, ur, log_off, nullptr); break;
+        default: break;
+      }
+    }
+  }
+  for (int k = 0; k < K; ++k) {
+    onehot[(size_t)i * K + k] = (k == best) ? 1.f : 0.f;
+    log_row[(size_t)i * K + k] = (k == best) ? 0.f : log_off;
+    if (level < 0 && pred) pred[(size_t)i * K + k] = (k == best) ? 0.f : log_off;
+  }
+  if (cls8) cls8[i] = (uint8_t)best;
+}
+template <int KN, int KE>
+__global__ void scaffold_merge_kernel(const ScaffoldMergeArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.N && (!a.node_mask || a.node_mask[i])) {
+    if (a.level >= 0) {
+      const float ab = a.alphas_bar[a.level];
+      const float sa = sqrtf(ab), sb = sqrtf(1.f - ab);
+      for (int c = 0; c < 3; ++c) a.pos[3 * (size_t)i + c] = sa * a.node_pos[3 * (size_t)i + c] + sb * a.eps[3 * (size_t)i + c];
+    } else {
+      for (int c = 0; c < 3; ++c) {
+        const float x = a.node_pos[3 * (size_t)i + c];
+        a.pos[3 * (size_t)i + c] = x;
+        if (a.pred_pos) a.pred_pos[3 * (size_t)i + c] = x;
+      }
+    }
+    scaffold_cat_row<KN>(a.Kn, a.node_q, a.level, a.node_type[i], a.u_node, a.log_off, a.h_node, a.log_node, a.node_cls, a.pred_node, i);
+  }
+  if (i < a.Eh && (!a.half_mask || a.half_mask[i]))
+    scaffold_cat_row<KE>(a.Ke, a.edge_q, a.level, a.half_type[i], a.u_half, a.log_off, a.h_half, a.log_half, a.half_cls, a.pred_half, i);
+}
+void launch_scaffold_merge(const ScaffoldMergeArgs& a, hipStream_t s) {
+  const int n = std::max(a.N, a.Eh);
+  if (n <= 0) return;
+  const dim3 g((n + 255) / 256), b(256);
+  if (a.Kn == 8 && a.Ke == 6) hipLaunchKernelGGL((scaffold_merge_kernel<8, 6>), g, b, 0, s, a);  // MolDiff's class counts
+  else hipLaunchKernelGGL((scaffold_merge_kernel<0, 0>), g, b, 0, s, a);
 }

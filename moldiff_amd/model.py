@@ -10,7 +10,8 @@ the fused sampling kernels; with grad enabled it runs layer by layer on the diff
 All arithmetic runs in ``libmoldiff_hip.so``; torch is used for device memory, streams and the output
 containers only.  Differences a caller can see, all opt-in keyword arguments with reference defaults:
 ``sample(..., seed=, mol_ids=, noise=, return_traj=)`` (per-molecule Philox noise instead of torch's
-global generator, see DESIGN.md "noise").
+global generator, see DESIGN.md "noise") and ``sample(..., scaffold=, start_step=)`` (scaffold-constrained sampling and partial
+chains, an addition beyond the reference: ``moldiff_amd/scaffold.py``).
 """
 import ctypes
 import os
@@ -231,8 +232,9 @@ class MolDiff(Module):
         return {'pred_node': pn, 'pred_pos': pp, 'pred_halfedge': ph}
 
     def sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, *, seed=None, mol_ids=None, noise=None,
-                return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False):
+                return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False, scaffold=None, start_step=None):
         """Stateful driver of the reverse chain (``init()`` then ``step(i)`` for i = 0..T-1); ``sample`` wraps it.
+        scaffold / start_step: see ``sample``; with start_step = s the loop iterations are i = T-s..T-1.
         overlap_guidance=True runs the guidance chain on a side stream concurrently with the denoiser forward of the same step
         (same results).  It paid in round 1 (0.7 ms per step, the kernels left tails for each other); with the round-2 kernels
         filling every CU by themselves it costs 0.5 ms (27.6 vs 28.1 ms per step), so in line is the default."""
@@ -240,13 +242,16 @@ class MolDiff(Module):
             if guidance is not None and guidance[1] > 0:
                 raise NotImplementedError('guidance in the continuous categorical space: the reference objectives that read the sampled '
                                           'bond classes do not exist there (models/model.py:340-359); not built')
+            if scaffold is not None or start_step is not None:
+                raise NotImplementedError('scaffold / start_step in the continuous categorical space: not built (no shipped config '
+                                          'uses that space)')
             return _ContinuousSampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj)
         return _Sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                        bond_predictor, guidance, overlap_guidance)
+                        bond_predictor, guidance, overlap_guidance, scaffold, start_step)
 
     @torch.no_grad()
     def sample(self, n_graphs, batch_node, halfedge_index, batch_halfedge, bond_predictor=None, guidance=None, *,
-               seed=None, mol_ids=None, noise=None, return_traj=True):
+               seed=None, mol_ids=None, noise=None, return_traj=True, scaffold=None, start_step=None):
         """Run the T-step reverse chain for a packed batch of fully-connected molecule graphs.
 
         Returns {'pred': [node logits (N,Kn), pos (N,3), halfedge logits (Eh,Ke)] of the last step,
@@ -255,11 +260,19 @@ class MolDiff(Module):
         mol_ids: global molecule ids (noise is keyed per molecule => results do not depend on sharding);
         noise: optional callable draw -> (eps_pos, u_node, u_halfedge) to inject explicit noise (tests);
         return_traj=False skips the (large) trajectory buffers.
+        scaffold: a ``moldiff_amd.Scaffold`` -- its fixed atoms and half-edges are held on the known molecule (after every step they are
+        re-drawn from q(x_k | x_0) of it, and end exactly on it), the free rows are generated around them.  Noise for it comes from the
+        same per-molecule streams under draw indices of its own: T + 1 + i after loop iteration i, 2T + 1 for the initial state
+        (`noise` is called with those too).
+        start_step = s (0 < s <= T; needs a scaffold that carries the whole molecule): start from that molecule noised to level s - 1
+        instead of the prior and run diffusion steps s-1 .. 0; the trajectory then has s + 1 frames.  An all-false mask gives an
+        SDEdit-style perturbation of the molecule.
         """
         sm = self.sampler(n_graphs, batch_node, halfedge_index, batch_halfedge, seed=seed, mol_ids=mol_ids, noise=noise,
-                          return_traj=return_traj, bond_predictor=bond_predictor, guidance=guidance)
+                          return_traj=return_traj, bond_predictor=bond_predictor, guidance=guidance, scaffold=scaffold,
+                          start_step=start_step)
         sm.init()
-        for i in range(self.num_timesteps):
+        for i in range(0 if start_step is None else self.num_timesteps - start_step, self.num_timesteps):
             sm.step(i)
         return sm.result()
 
@@ -274,8 +287,13 @@ class _Sampler:
     edge (``traj.LazyOneHot``): 0.16 GB instead of 2.1 GB at 256 molecules."""
 
     def __init__(self, model, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                 bond_predictor, guidance, overlap_guidance=False):
+                 bond_predictor, guidance, overlap_guidance=False, scaffold=None, start_step=None):
         _lib._need_gpu(batch_node, halfedge_index, batch_halfedge)
+        if start_step is not None:
+            if scaffold is None:
+                raise ValueError('start_step needs a scaffold that carries the molecule to start from')
+            if not 0 < int(start_step) <= model.num_timesteps:
+                raise ValueError(f'start_step {start_step} outside (0, {model.num_timesteps}]')
         self.guidance = None
         if guidance is not None:
             gui_type, gui_scale = guidance
@@ -307,7 +325,8 @@ class _Sampler:
         f32 = dict(dtype=torch.float32, device=dev)
         N, Eh, Kn, Ke, T = self.N, self.Eh, self.Kn, self.Ke, self.T
         self.eps, self.u_n, self.u_h = torch.empty(N, 3, **f32), torch.empty(N, Kn, **f32), torch.empty(Eh, Ke, **f32)
-        nT = T + 1 if return_traj else 2
+        self.i0 = 0 if start_step is None else T - int(start_step)   # first loop iteration (a partial chain starts part-way)
+        nT = T - self.i0 + 1 if return_traj else 2
         self.h_node = torch.zeros(2, N, Kn, **f32)        # one-hot state, frames ping-pong
         self.h_half = torch.zeros(2, Eh, Ke, **f32)
         self.pos_traj = torch.zeros(nT, N, 3, **f32)
@@ -346,14 +365,43 @@ class _Sampler:
         self.tables = _lib.MdxTables(*(_lib.ptr(x) for x in (pt.coef_x0, pt.coef_xt, pt.std, ntr.q_mats, ntr.transpopse_q_onestep_mats,
                                                              etr.q_mats, etr.transpopse_q_onestep_mats)))
         self.cur, self.lcur, self.pcur = 0, 0, 0  # one-hot frame / log-prob frame / position (and id) frame of the current state
+        self.sc = None
+        if scaffold is not None:
+            _lib._need_gpu(scaffold.node_mask, scaffold.node_type, scaffold.node_pos, scaffold.halfedge_type, scaffold.halfedge_mask)
+            # validated once, here (one host read); the tensors are kept alive next to the struct that points at them
+            self._sc_t = nm, nt, npos, ht, hm = scaffold.resolve(N, halfedge_index, Kn, Ke, every_row=start_step is not None)
+            P = _lib.ptr
+            self.sc = _lib.MdxScaffold(P(nm), P(hm), P(nt), P(ht), P(npos))
+            self.sc_all = _lib.MdxScaffold(None, None, P(nt), P(ht), P(npos))   # every row: the start molecule of a partial chain
+            self.sc_tabs = _lib.MdxScaffoldTables(P(pt.alphas_bar), P(ntr.q_mats), P(etr.q_mats), Kn, Ke, T)
+        self.start_step = start_step
 
     def _pframe(self, j):
-        return j if self.return_traj else j % 2
+        return j - self.i0 if self.return_traj else (j - self.i0) % 2
+
+    def _merge(self, sc, level, draw, n, ln, pn):
+        """Overwrite the fixed rows of state frames (n, ln, pn) with q(x_level | x_0) of the scaffold (level -1: x_0 itself, and the
+        prediction's rows with it) -- one library call, at most two launches (noise, merge)."""
+        P = _lib.ptr
+        if level >= 0 and self.noise is not None:
+            e, a, b = self.noise(draw)
+            self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
+            draw = -1
+        nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
+        nz = _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
+        _lib.check(_lib.lib().mdx_scaffold_merge(self.g.h, ctypes.byref(self.sc_tabs), level, ctypes.byref(sc), ctypes.byref(nz),
+                                                 ctypes.byref(nxt), _lib.log_eps32(), P(self.node_ids[pn]), P(self.half_ids[pn]),
+                                                 P(self.preds[0]), P(self.preds[1]), P(self.preds[2]), _lib.stream()))
 
     @torch.no_grad()
     def init(self):
-        """Prior draw (models/model.py:244-263): classes ~ init_prob by Gumbel-max, positions ~ N(0, I)."""
+        """Prior draw (models/model.py:244-263): classes ~ init_prob by Gumbel-max, positions ~ N(0, I).  With a scaffold its fixed
+        rows are then merged in at level T - 1; a partial chain starts from the whole scaffold molecule noised to level start_step - 1."""
         m, L, dev = self.m, _lib.lib(), self.dev
+        if self.start_step is not None:
+            self.cur, self.lcur, self.pcur = 0, 0, 0
+            self._merge(self.sc_all, self.start_step - 1, 2 * self.T + 1, 0, 0, 0)
+            return
         u_n, u_h = self.u_n, self.u_h
         if self.noise is not None:
             e, a, b = self.noise(0)
@@ -371,10 +419,13 @@ class _Sampler:
             _lib.prior_draw(tr.init_prob, u, n, onehot=oh[0], log_onehot=logs[0], cls8=ids[0])
         self.pos_traj[0].copy_(self.eps)
         self.cur, self.lcur, self.pcur = 0, 0, 0
+        if self.sc is not None:
+            self._merge(self.sc, self.T - 1, 2 * self.T + 1, 0, 0, 0)
 
     @torch.no_grad()
     def step(self, i):
-        """Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call."""
+        """Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call; with a scaffold a second one merges
+        its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold")."""
         L, T = _lib.lib(), self.T
         draw = i + 1
         if self.noise is not None:
@@ -398,6 +449,8 @@ class _Sampler:
                                           ctypes.byref(self.gd) if self.gd is not None else None, ws, nb, _lib.stream()))
         if self.guidance is not None and self.gd is None:  # the seven objectives that are torch expressions on the logits
             self._guide(self.h_node[c], self.pos_traj[pc], self.pos_traj[pn], self.h_half[n], self.log_half[ln])
+        if self.sc is not None:
+            self._merge(self.sc, T - 2 - i, T + 1 + i, n, ln, pn)
         self.cur, self.lcur, self.pcur = n, ln, pn
 
     def _guide(self, h_node, pos, pos_prev, h_half_prev, log_half):

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -20,6 +20,9 @@ give-up rule (:106-108).  What differs, deliberately:
   * with WORLD_SIZE > 1 every rank samples a contiguous slice of each batch's cost-balanced molecule order (noise keyed by
     global molecule id); per batch the last-step predictions travel to rank 0 as tensors (``distributed.gather_pred``:
     one count all_gather + ONE padded gather-to-rank-0 of a flat buffer holding all three) and one 2-element all-reduce carries the loop condition.
+``--scaffold PATH`` (config key ``sample.scaffold``), an addition beyond the reference: PATH is a V2000 mol block as this module
+writes them; every sampled molecule gets it as its first atoms, held fixed with the bonds among them, and the rest is grown around
+it (``moldiff_amd/scaffold.py``).  Sizes are drawn as usual and raised to the scaffold's atom count where they fall below it.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -36,6 +39,7 @@ from .distributed import balanced_order, gather_pred, shard_bounds
 from .harness import default_config, load_config, placeholder_from_sizes, recipe_state_dict, seed_all
 from .harness import GEOM_DRUGS_MEAN_ATOMS, GEOM_DRUGS_STD_ATOMS
 from .postprocess import FeaturizeMol
+from .scaffold import scaffold_for_sizes
 
 ELEMENT_SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
 
@@ -69,6 +73,34 @@ def mol_block(info, name='moldiff_amd'):
         lines.append('%3d%3d%3d  0' % (info['bond_index'][0, k] + 1, info['bond_index'][1, k] + 1, info['bond_type'][k]))
     lines.append('M  END')
     return '\n'.join(lines) + '\n'
+
+
+def read_mol_block(text):
+    """Inverse of ``mol_block``: a V2000 mol block -> dict(element (n) atomic numbers, atom_pos (n,3) float32, bond_index (2,2b),
+    bond_type (2b)) in decode_output's layout (each bond once in file order, then all of them flipped).  Host code; coordinates carry
+    the four decimals the block prints.  An element symbol this module does not write raises."""
+    lines = text.splitlines()
+    counts = next((k for k, ln in enumerate(lines) if ln.rstrip().endswith('V2000')), None)
+    if counts is None:
+        raise ValueError('not a V2000 mol block (no counts line)')
+    na, nb = int(lines[counts][0:3]), int(lines[counts][3:6])
+    number = {sym: z for z, sym in ELEMENT_SYMBOL.items()}
+    ele, pos = [], []
+    for ln in lines[counts + 1:counts + 1 + na]:
+        sym = ln[31:34].strip()
+        if sym not in number:
+            raise ValueError(f'unknown element {sym!r} in mol block (known: {sorted(number)})')
+        ele.append(number[sym])
+        pos.append([float(ln[0:10]), float(ln[10:20]), float(ln[20:30])])
+    bi, bt = [], []
+    for ln in lines[counts + 1 + na:counts + 1 + na + nb]:
+        bi.append([int(ln[0:3]) - 1, int(ln[3:6]) - 1])
+        bt.append(int(ln[6:9]))
+    if len(ele) != na or len(bt) != nb:
+        raise ValueError('truncated mol block')
+    idx = np.asarray(bi, dtype=np.int64).reshape(nb, 2).T
+    return {'element': np.asarray(ele, dtype=np.int64), 'atom_pos': np.asarray(pos, dtype=np.float32).reshape(na, 3),
+            'bond_index': np.concatenate([idx, idx[::-1]], axis=1), 'bond_type': np.asarray(bt + bt, dtype=np.int64)}
 
 
 def build_models(config, device, recipe):
@@ -138,6 +170,8 @@ def main(argv=None):
     ap.add_argument('--batch_size', type=int, default=0)
     ap.add_argument('--recipe-weights', action='store_true')
     ap.add_argument('--num_mols', type=int, default=0, help='override sample.num_mols')
+    ap.add_argument('--scaffold', type=str, default='', help='V2000 mol block held fixed as the first atoms of every molecule '
+                                                             '(overrides sample.scaffold)')
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -179,6 +213,11 @@ def main(argv=None):
     num_mols = args.num_mols or config.sample.num_mols
     batch_size = args.batch_size if args.batch_size > 0 else config.sample.batch_size
     save_traj_prob = float(getattr(config.sample, 'save_traj_prob', 0.0) or 0.0)
+    scaffold_path = args.scaffold or config.sample.get('scaffold') or ''
+    scaffold_info = None
+    if scaffold_path:
+        with open(scaffold_path) as f:
+            scaffold_info = read_mol_block(f.read())
     pool = {'finished': [], 'failed': []}
     n_finished, n_failed = 0, 0
     next_id, i_batch = 0, 0
@@ -191,13 +230,17 @@ def main(argv=None):
         # every rank draws the same sizes (same numpy stream) and takes a contiguous slice of the cost-balanced order
         sizes = np.random.normal(GEOM_DRUGS_MEAN_ATOMS, GEOM_DRUGS_STD_ATOMS, size=n_graphs).astype('int64')
         sizes = np.maximum(sizes, 2)  # the reference's harness cannot handle molecules without half-edges
+        if scaffold_info is not None:
+            sizes = np.maximum(sizes, len(scaffold_info['element']))
         order = balanced_order(sizes, world) if world > 1 else np.arange(n_graphs)
         lo, hi = shard_bounds(n_graphs, world, rank)
         mine = order[lo:hi]
         ph = placeholder_from_sizes(sizes[mine], device)
         ids = next_id + mine.astype(np.int64)
+        # each rank builds the scaffold of its own slice; its noise is keyed by global molecule id like the chain's
+        scaffold = scaffold_for_sizes(scaffold_info, sizes[mine], featurizer, device) if scaffold_info is not None else None
         out = model.sample(hi - lo, ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], bond_predictor, guidance,
-                           seed=seed + i_batch, mol_ids=ids, return_traj=save_traj_prob > 0)
+                           seed=seed + i_batch, mol_ids=ids, return_traj=save_traj_prob > 0, scaffold=scaffold)
         # trajectories stay rank-local (scripts/sample_drug3d.py:155 looks at ~2 % of them): the owner decodes and writes
         # them, named by global molecule id; whether a molecule is drawn depends only on (seed, id), not on the sharding
         if save_traj_prob > 0:
