@@ -160,6 +160,20 @@ int mdx_gauss_posterior(const float* coef_x0, const float* coef_xt, const float*
 int mdx_cat_posterior(const float* q_mats, const float* qT_onestep, int32_t K, int32_t T, const float* in0,
                       int32_t is_logits, const float* log_vt, const int64_t* t, const int64_t* batch, int64_t n,
                       float* out, void* stream);
+/* Jump forms of the two posteriors above, for strided sampling: q(x_s | x_t, x0_hat) of the SAME forward process for any level s < t
+ * (NO reference line: models/transition.py:44-63 and :285-315 know s = t - 1 only; DESIGN.md "strided sampling").  The caller builds
+ * one table row per (t, s) pair it asks for (moldiff_amd/transition.py jump_coefs / jump_mats): c0 = sqrt(abar_s) (1 - a) / (1 - abar_t),
+ * ct = sqrt(a) (1 - abar_s) / (1 - abar_t), sd = sqrt((1 - abar_s) (1 - a) / (1 - abar_t)) with a = abar_t / abar_s, and
+ * qT_jump = (Q_{s+1} ... Q_t)^T; rows with s = t - 1 are copies of the one-step tables.  Per graph, int64: t (B) the level read and
+ * row (B) the table row of the graph's pair, for both entries; t_prev (B) the level written (< 0 where t == 0: read as 0) for the
+ * categorical entry only, which indexes q_mats with it -- the position entry needs nothing but its table row.  Same row arithmetic
+ * as the one-step kernels; where t == 0 the output is the posterior mean / log v0_hat. */
+int mdx_pos_posterior_jump(const float* jump_coef_x0, const float* jump_coef_xt, const float* jump_std, const float* x_t,
+                           const float* x_recon, const float* eps, const int64_t* t, const int64_t* row, const int64_t* batch,
+                           int64_t n, float* out, void* stream);
+int mdx_cat_posterior_jump(const float* q_mats, const float* qT_jump, int32_t K, const float* in0, int32_t is_logits,
+                           const float* log_vt, const int64_t* t, const int64_t* t_prev, const int64_t* row, const int64_t* batch,
+                           int64_t n, float* out, void* stream);
 /* Training / add_noise: GeneralCategoricalTransition.add_noise (models/transition.py:266-283: index_to_log_onehot, q_vt_pred, the
  * Gumbel-max draw of q_vt_sample with the uniforms u (n,K) passed in, onehot_encode) in one launch: v (n) class ids of the clean batch
  * -> onehot (n,K) of the drawn classes, log_vt = log(clamp(onehot, 1e-30)), log_v0 = log(clamp(onehot(v), 1e-30)).  log_off = log(1e-30)
@@ -253,6 +267,29 @@ int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tables,
                          const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
                          float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise, int64_t* t_buf, uint8_t* node_cls,
                          uint8_t* halfedge_cls, const mdx_guidance* guide, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- strided sampling: one iteration of a reverse chain that visits a subset tau_0 > tau_1 > ... > tau_{num-1} = 0 of the levels
+ * (NO reference line: the loop of models/model.py:271-372 visits every level).  The same single call as the entry above -- Philox launch
+ * that also fills the time tensor with step = tau_position, denoiser forward at that time, ONE transition launch, optional guidance in
+ * line or on the side stream -- with the transition reading row `position` of the jump tables and q_mats[tau_{position+1}], i.e. drawing
+ * from q(x_{tau_{position+1}} | x_{tau_position}, x0_hat).  The last position (level 0) is the ordinary t == 0 step.
+ *   jump     : one row per schedule position (moldiff_amd/transition.py jump_coefs / jump_mats; rows of stride-1 pairs and the last
+ *              row are copies of `tables`, so a schedule T-1, T-2, ..., 0 reproduces the loop above bit for bit); `levels` is a HOST array
+ *   step     : must equal levels[position]
+ *   noise    : the draw index of the move leaving level t is T - t under every schedule (what the full chain uses there); a scaffold
+ *              merge after it uses T + (T - t), with level = levels[position + 1], or -1 after the last position
+ * A C caller: for (j = 0; j < num; ++j) the call with position j, step levels[j], frames j and j + 1. */
+typedef struct {
+  const float *pos_coef_x0, *pos_coef_xt, *pos_std;   /* (num) device */
+  const float *node_qT_jump, *edge_qT_jump;           /* (num,Kn,Kn) / (num,Ke,Ke) device: (Q_{s+1} ... Q_t)^T, row-major */
+  const int32_t* levels;                              /* (num) host: the schedule, strictly decreasing, ends at 0 */
+  int32_t num;
+} mdx_jump_tables;
+int mdx_sample_jump_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tables, const mdx_jump_tables* jump, int32_t position,
+                         int32_t step, const int64_t* batch_node, const int64_t* batch_halfedge, const mdx_state* cur,
+                         const mdx_state* next, float* pred_node, float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise,
+                         int64_t* t_buf, uint8_t* node_cls, uint8_t* halfedge_cls, const mdx_guidance* guide, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* ---- scaffold-constrained sampling (replacement conditioning; NO reference line: the reference has no conditional sampling).
  * Overwrites the FIXED rows of the state `next` with a draw from q(x_level | x_0) of a known molecule, in one launch and without

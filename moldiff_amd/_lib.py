@@ -23,6 +23,7 @@ EXPORTS = [
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
     'mdx_guidance_uncertainty_grad', 'mdx_add_inplace', 'mdx_decode_output', 'mdx_scaffold_merge',
+    'mdx_sample_jump_full', 'mdx_pos_posterior_jump', 'mdx_cat_posterior_jump',
     'mdx_profile_enable', 'mdx_profile_read', 'mdx_profile_kernel_name',
     'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_hgemm_nt', 'mdx_op_hgemm_tn', 'mdx_op_xgemm_nt', 'mdx_op_xgemm_tn', 'mdx_op_amp_adamw',
     'mdx_op_xgemm_nt_t', 'mdx_op_xgemm_nt_ln_t', 'mdx_op_xgemm_nt_ln_supported', 'mdx_op_xgemm_tn_t', 'mdx_op_ln_relu_fwd_t', 'mdx_op_ln_relu_bwd_t', 'mdx_op_ew_fwd_t', 'mdx_op_ew_bwd_t',
@@ -40,6 +41,11 @@ EXPORTS = [
 class MdxTables(ctypes.Structure):   # == struct mdx_tables
     _fields_ = [(n, c_void_p) for n in ('pos_coef_x0', 'pos_coef_xt', 'pos_std', 'node_q_mats', 'node_qT_onestep', 'edge_q_mats',
                                         'edge_qT_onestep')]
+
+
+class MdxJumpTables(ctypes.Structure):   # == struct mdx_jump_tables
+    _fields_ = [(n, c_void_p) for n in ('pos_coef_x0', 'pos_coef_xt', 'pos_std', 'node_qT_jump', 'edge_qT_jump')] + [
+        ('levels', POINTER(c_int32)), ('num', c_int32)]
 
 
 class MdxState(ctypes.Structure):    # == struct mdx_state
@@ -167,6 +173,10 @@ def lib():
         L.mdx_sample_step_full.argtypes = [c_void_p, c_void_p, POINTER(MdxTables), c_int32, c_void_p, c_void_p, POINTER(MdxState),
                                            POINTER(MdxState), c_void_p, c_void_p, c_void_p, POINTER(MdxStepNoise), c_void_p,
                                            c_void_p, c_void_p, POINTER(MdxGuidance), c_void_p, c_size_t, c_void_p]
+        L.mdx_sample_jump_full.argtypes = (L.mdx_sample_step_full.argtypes[:3] + [POINTER(MdxJumpTables), c_int32] +
+                                           L.mdx_sample_step_full.argtypes[3:])
+        L.mdx_pos_posterior_jump.argtypes = [c_void_p] * 9 + [c_int64, c_void_p, c_void_p]
+        L.mdx_cat_posterior_jump.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]
         L.mdx_bondpred_forward.argtypes = [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]
         L.mdx_bondpred_backward.argtypes = [c_void_p] * 4 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
                                                             c_void_p]
@@ -520,6 +530,26 @@ def cat_posterior(q_mats, qT, in0, log_vt, t, batch, is_logits=False):
     out = torch.empty_like(in0)
     check(lib().mdx_cat_posterior(ptr(q_mats), ptr(qT), in0.shape[1], q_mats.shape[0], ptr(in0), int(is_logits),
                                   ptr(log_vt), ptr(t), ptr(batch), in0.shape[0], ptr(out), stream()))
+    return out
+
+
+def pos_posterior_jump(c0, ct, sd, x_t, x_recon, eps, t, row, batch):
+    """jump form of pos_posterior: (c0, ct, sd) are jump-table rows, `row` (B) the row of every graph's (t, t_prev) pair"""
+    _need_gpu(x_t, x_recon, eps, t, row, batch, c0)
+    x_t, x_recon, eps, t, row, batch = f32c(x_t), f32c(x_recon), f32c(eps), i64c(t), i64c(row), i64c(batch)
+    out = torch.empty_like(x_t)
+    check(lib().mdx_pos_posterior_jump(ptr(c0), ptr(ct), ptr(sd), ptr(x_t), ptr(x_recon), ptr(eps), ptr(t), ptr(row), ptr(batch),
+                                       x_t.shape[0], ptr(out), stream()))
+    return out
+
+
+def cat_posterior_jump(q_mats, qT_jump, in0, log_vt, t, t_prev, row, batch, is_logits=False):
+    """jump form of cat_posterior: qT_jump (P,K,K) jump-table rows, `row` (B) the row of every graph's (t, t_prev) pair"""
+    _need_gpu(in0, log_vt, t, t_prev, row, batch, q_mats, qT_jump)
+    in0, log_vt, t, t_prev, row, batch = f32c(in0), f32c(log_vt), i64c(t), i64c(t_prev), i64c(row), i64c(batch)
+    out = torch.empty_like(in0)
+    check(lib().mdx_cat_posterior_jump(ptr(q_mats), ptr(qT_jump), in0.shape[1], ptr(in0), int(is_logits), ptr(log_vt), ptr(t),
+                                       ptr(t_prev), ptr(row), ptr(batch), in0.shape[0], ptr(out), stream()))
     return out
 
 

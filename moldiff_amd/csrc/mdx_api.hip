@@ -1309,7 +1309,7 @@ static int sample_step_core(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, 
                             const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
                             float* pred_pos, float* pred_halfedge, const float* eps_pos, const float* u_node,
                             const float* u_halfedge, uint8_t* node_cls, uint8_t* halfedge_cls, void* ws, size_t ws_bytes,
-                            void* stream) {
+                            void* stream, const StepJumpRows* jr = nullptr) {  // jr: the move is a jump (strided sampling)
   if (!tb || !cur || !next) return fail(MDX_ERR_ARG, "null tables / state");
   if (!m || !g) return fail(MDX_ERR_ARG, "null handle");
   const int N = (int)g->N, Eh = (int)g->Eh;
@@ -1331,7 +1331,23 @@ static int sample_step_core(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, 
     ta.log_half = cur->log_halfedge; ta.u_half = u_halfedge; ta.pos_next = next->pos; ta.log_node_next = next->log_node;
     ta.h_node_next = next->h_node; ta.log_half_next = next->log_halfedge; ta.h_half_next = next->h_halfedge; ta.node_cls = node_cls;
     ta.half_cls = halfedge_cls;
-    launch_step_transition(ta, s);
+    if (jr) launch_step_jump(ta, *jr, s);
+    else launch_step_transition(ta, s);
+    HIPCHK(hipGetLastError());
+    return MDX_OK;
+  }
+  if (jr) {  // other class counts: the stand-alone jump posteriors with the schedule position as a launch scalar
+    if (cf.num_node_types < 2 || cf.num_node_types > 8 || cf.num_edge_types < 2 || cf.num_edge_types > 8)
+      return fail(MDX_ERR_UNSUPPORTED, "jump posteriors: class counts %d / %d outside 2..8", cf.num_node_types, cf.num_edge_types);
+    launch_pos_posterior_jump(jr->c0, jr->ct, jr->sd, cur->pos, pred_pos, eps_pos, t, nullptr, jr->row, batch_node, N, next->pos, s);
+    launch_cat_posterior_jump(tb->node_q_mats, jr->node_qT, cf.num_node_types, pred_node, 1, cur->log_node, t, nullptr, nullptr, jr->s,
+                              jr->row, batch_node, N, next->log_node, s);
+    launch_gumbel_argmax(next->log_node, u_node, cf.num_node_types, N, nullptr, next->h_node, s, node_cls);
+    if (Eh > 0) {
+      launch_cat_posterior_jump(tb->edge_q_mats, jr->edge_qT, cf.num_edge_types, pred_halfedge, 1, cur->log_halfedge, t, nullptr,
+                                nullptr, jr->s, jr->row, batch_halfedge, Eh, next->log_halfedge, s);
+      launch_gumbel_argmax(next->log_halfedge, u_halfedge, cf.num_edge_types, Eh, nullptr, next->h_halfedge, s, halfedge_cls);
+    }
     HIPCHK(hipGetLastError());
     return MDX_OK;
   }
@@ -1356,11 +1372,12 @@ extern "C" int mdx_sample_step(mdx_model_t m, mdx_graph_t g, const mdx_tables* t
                           u_halfedge, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
-extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, int32_t step, const int64_t* batch_node,
-                                    const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
-                                    float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise, int64_t* t_buf,
-                                    uint8_t* node_cls, uint8_t* halfedge_cls, const mdx_guidance* gd, void* ws, size_t ws_bytes,
-                                    void* stream) {
+// the body of mdx_sample_step_full and mdx_sample_jump_full: jr == nullptr is the chain's ordinary move step -> step - 1
+static int sample_step_full_impl(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, int32_t step, const int64_t* batch_node,
+                                 const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
+                                 float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise, int64_t* t_buf,
+                                 uint8_t* node_cls, uint8_t* halfedge_cls, const mdx_guidance* gd, void* ws, size_t ws_bytes,
+                                 void* stream, const StepJumpRows* jr) {
   if (!m || !g || !tb || !cur || !next || !noise || !t_buf) return fail(MDX_ERR_ARG, "null argument");
   if (m->cfg.kind != MDX_KIND_MOLDIFF) return fail(MDX_ERR_STATE, "not a MolDiff model handle");
   if (step < 0 || step >= m->cfg.num_timesteps) return fail(MDX_ERR_ARG, "step %d outside [0, %d)", step, m->cfg.num_timesteps);
@@ -1405,7 +1422,7 @@ extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tabl
       HIPCHK(hipEventRecord(g->ev_done, gs));
     }
     int rc = sample_step_core(m, g, tb, t_buf, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge,
-                              noise->eps_pos, noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream);
+                              noise->eps_pos, noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream, jr);
     if (rc != MDX_OK) return rc;
     if (gd->side_stream) {
       HIPCHK(hipStreamWaitEvent(s, g->ev_done, 0));
@@ -1418,7 +1435,37 @@ extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tabl
     return MDX_OK;
   }
   return sample_step_core(m, g, tb, t_buf, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, noise->eps_pos,
-                          noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream);
+                          noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream, jr);
+}
+
+extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, int32_t step, const int64_t* batch_node,
+                                    const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
+                                    float* pred_pos, float* pred_halfedge, const mdx_step_noise* noise, int64_t* t_buf,
+                                    uint8_t* node_cls, uint8_t* halfedge_cls, const mdx_guidance* gd, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  return sample_step_full_impl(m, g, tb, step, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, noise, t_buf,
+                               node_cls, halfedge_cls, gd, ws, ws_bytes, stream, nullptr);
+}
+
+extern "C" int mdx_sample_jump_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, const mdx_jump_tables* jt, int32_t position,
+                                    int32_t step, const int64_t* batch_node, const int64_t* batch_halfedge, const mdx_state* cur,
+                                    const mdx_state* next, float* pred_node, float* pred_pos, float* pred_halfedge,
+                                    const mdx_step_noise* noise, int64_t* t_buf, uint8_t* node_cls, uint8_t* halfedge_cls,
+                                    const mdx_guidance* gd, void* ws, size_t ws_bytes, void* stream) {
+  if (!m || !jt) return fail(MDX_ERR_ARG, "null argument");
+  if (!jt->levels || !jt->pos_coef_x0 || !jt->pos_coef_xt || !jt->pos_std || !jt->node_qT_jump || !jt->edge_qT_jump)
+    return fail(MDX_ERR_ARG, "incomplete mdx_jump_tables");
+  if (position < 0 || position >= jt->num) return fail(MDX_ERR_ARG, "schedule position %d outside [0, %d)", position, jt->num);
+  const int T = m->cfg.num_timesteps;
+  const int32_t t = jt->levels[position], sl = position + 1 < jt->num ? jt->levels[position + 1] : -1;
+  if (t != step) return fail(MDX_ERR_ARG, "schedule position %d is level %d, not step %d", position, t, step);
+  if (t < 0 || t >= T || sl >= t || sl < -1 || (sl < 0 && t != 0))
+    return fail(MDX_ERR_ARG, "schedule levels %d -> %d at position %d: not a downward move inside [0, %d) that ends at 0", t, sl, position, T);
+  StepJumpRows jr{};
+  jr.c0 = jt->pos_coef_x0; jr.ct = jt->pos_coef_xt; jr.sd = jt->pos_std; jr.node_qT = jt->node_qT_jump; jr.edge_qT = jt->edge_qT_jump;
+  jr.row = position; jr.s = sl > 0 ? sl : 0;
+  return sample_step_full_impl(m, g, tb, step, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, noise, t_buf,
+                               node_cls, halfedge_cls, gd, ws, ws_bytes, stream, &jr);
 }
 
 extern "C" int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tb, int32_t level, const mdx_scaffold* sc,
@@ -1690,6 +1737,27 @@ extern "C" int mdx_gauss_posterior(const float* c0, const float* ct, const float
   if (n < 0 || C < 1 || (n > 0 && (!c0 || !ct || !sd || !x_t || !x_recon || !eps || !t || !batch || !out)))
     return fail(MDX_ERR_ARG, "bad argument");
   launch_gauss_posterior(c0, ct, sd, x_t, x_recon, eps, t, batch, (int)n, (int)C, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
+extern "C" int mdx_pos_posterior_jump(const float* c0, const float* ct, const float* sd, const float* x_t, const float* x_recon,
+                                      const float* eps, const int64_t* t, const int64_t* row, const int64_t* batch, int64_t n, float* out,
+                                      void* stream) {
+  if (n == 0) return MDX_OK;
+  if (!c0 || !ct || !sd || !x_t || !x_recon || !eps || !t || !row || !batch || !out) return fail(MDX_ERR_ARG, "null buffer");
+  launch_pos_posterior_jump(c0, ct, sd, x_t, x_recon, eps, t, row, 0, batch, (int)n, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
+extern "C" int mdx_cat_posterior_jump(const float* q_mats, const float* qT_jump, int32_t K, const float* in0, int32_t is_logits,
+                                      const float* log_vt, const int64_t* t, const int64_t* t_prev, const int64_t* row,
+                                      const int64_t* batch, int64_t n, float* out, void* stream) {
+  if (K < 2 || K > 8) return fail(MDX_ERR_UNSUPPORTED, "class count %d outside 2..8", K);
+  if (n == 0) return MDX_OK;
+  if (!q_mats || !qT_jump || !in0 || !log_vt || !t || !t_prev || !row || !batch || !out) return fail(MDX_ERR_ARG, "null buffer");
+  launch_cat_posterior_jump(q_mats, qT_jump, K, in0, is_logits, log_vt, t, t_prev, row, 0, 0, batch, (int)n, out, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MDX_OK;
 }

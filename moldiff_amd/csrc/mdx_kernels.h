@@ -340,6 +340,11 @@ struct StepTransArgs {  // mdx_transition.hip: the transitions of one sampling s
   uint8_t *node_cls, *half_cls;
 };
 void launch_step_transition(const StepTransArgs& a, hipStream_t s);
+struct StepJumpRows {  // strided sampling: the jump tables (one row per schedule position) and the rows one move t -> s reads
+  const float *c0, *ct, *sd, *node_qT, *edge_qT;  // (num) x 3, (num,Kn,Kn), (num,Ke,Ke); c0 / ct / sd of the StepTransArgs are not read
+  int row, s;                                     // schedule position; the level written, >= 0 (index into q_mats)
+};
+void launch_step_jump(const StepTransArgs& a, const StepJumpRows& j, hipStream_t s);  // Kn = 8, Ke = 6, like launch_step_transition
 struct ScaffoldMergeArgs {  // mdx_transition.hip: fixed rows of a sampler state <- q(x_level | x_0) of a known molecule (level -1: x_0 itself)
   int N, Eh, Kn, Ke, level;
   float log_off;
@@ -392,6 +397,13 @@ void launch_pos_posterior(const float* c0, const float* ct, const float* sd, con
                           const float* eps, const int64_t* t, const int64_t* batch, int n, float* out, hipStream_t s);
 void launch_cat_posterior(const float* qmats, const float* qT1, int K, int T, const float* logits_or_log_v0, int is_logits,
                           const float* log_vt, const int64_t* t, const int64_t* batch, int n, float* out, hipStream_t s);
+// jump forms: table row `row[g]` and level `t_prev[g]` per graph, or the scalars row_s / s_s for every graph when `row` is null
+void launch_pos_posterior_jump(const float* c0, const float* ct, const float* sd, const float* xt, const float* x0, const float* eps,
+                               const int64_t* t, const int64_t* row, int64_t row_s, const int64_t* batch, int n, float* out,
+                               hipStream_t s);
+void launch_cat_posterior_jump(const float* qmats, const float* qTj, int K, const float* logits_or_log_v0, int is_logits,
+                               const float* log_vt, const int64_t* t, const int64_t* t_prev, const int64_t* row, int64_t s_s,
+                               int64_t row_s, const int64_t* batch, int n, float* out, hipStream_t s);
 void launch_uncertainty_grad(const float* logits, int K, int n, float* glogits, hipStream_t s);
 void launch_cat_add_noise(const float* qmats, int K, const int64_t* v, const int64_t* t, const int64_t* batch, const float* u, int n,
                           float log_off, float* onehot, float* log_vt, float* log_v0, hipStream_t s);

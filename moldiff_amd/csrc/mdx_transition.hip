@@ -14,24 +14,37 @@
 
 namespace {
 
-__device__ __forceinline__ void pos_posterior_elem(const float* __restrict__ c0, const float* __restrict__ ct,
-                                                   const float* __restrict__ sd, const float* __restrict__ xt,
+// One position component: mu = c0 x0_hat + ct x_t; x = mu + sd eps, and exactly mu on the last move (t == 0).  The three coefficients
+// are the CALLER's table row: coef_x0 / coef_xt / std at t for the chain's ordinary move t -> t - 1, the jump tables' row for t -> s.
+__device__ __forceinline__ void pos_posterior_elem(float c0, float ct, float sd, bool last, const float* __restrict__ xt,
                                                    const float* __restrict__ x0, const float* __restrict__ eps,
-                                                   const int64_t* __restrict__ t, const int64_t* __restrict__ batch, int n,
                                                    float* __restrict__ out, int i) {
-  if (i >= 3 * n) return;
-  const int v = i / 3;
-  const int64_t tv = t[batch[v]];
-  const float mu = c0[tv] * x0[i] + ct[tv] * xt[i];
-  const float x = mu + sd[tv] * eps[i];
-  out[i] = (tv == 0) ? mu : x;
+  const float mu = c0 * x0[i] + ct * xt[i];
+  const float x = mu + sd * eps[i];
+  out[i] = last ? mu : x;
 }
 __global__ void pos_posterior_kernel(const float* __restrict__ c0, const float* __restrict__ ct,
                                      const float* __restrict__ sd, const float* __restrict__ xt,
                                      const float* __restrict__ x0, const float* __restrict__ eps,
                                      const int64_t* __restrict__ t, const int64_t* __restrict__ batch, int n,
                                      float* __restrict__ out) {
-  pos_posterior_elem(c0, ct, sd, xt, x0, eps, t, batch, n, out, blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * n) return;
+  const int64_t tv = t[batch[i / 3]];
+  pos_posterior_elem(c0[tv], ct[tv], sd[tv], tv == 0, xt, x0, eps, out, i);
+}
+// jump form (strided sampling, no reference line): the move t -> s < t - 1 reads row `row` of the jump tables (moldiff_amd/transition.py
+// jump_coefs); row / t per graph, or the launch scalar row_s for every graph when `row` is null
+__global__ void pos_posterior_jump_kernel(const float* __restrict__ c0, const float* __restrict__ ct,
+                                          const float* __restrict__ sd, const float* __restrict__ xt,
+                                          const float* __restrict__ x0, const float* __restrict__ eps,
+                                          const int64_t* __restrict__ t, const int64_t* __restrict__ row, int64_t row_s,
+                                          const int64_t* __restrict__ batch, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * n) return;
+  const int64_t g = batch[i / 3];
+  const int64_t r = row ? row[g] : row_s;
+  pos_posterior_elem(c0[r], ct[r], sd[r], t[g] == 0, xt, x0, eps, out, i);
 }
 
 // the same posterior for rows of any width C (continuous categorical space: atom / bond features are real vectors, model.py:301-304)
@@ -47,14 +60,13 @@ __global__ void gauss_posterior_kernel(const float* __restrict__ c0, const float
   out[i] = (tv == 0) ? mu : x;
 }
 
+// One row of log q(v_s | v_t, v0_hat).  Q1: the row-major (K,K) TRANSPOSE of the forward matrix from s to t, Q0: the cumulative matrix
+// Qbar_s -- both the CALLER's table rows: transpopse_q_onestep_mats[t] and q_mats[t - 1] for the chain's ordinary move, the jump
+// tables' Q_{t|s}^T and q_mats[s] for a jump.  last (t == 0): the row is log v0_hat itself.
 template <int K>
-__device__ __forceinline__ void cat_posterior_row(const float* __restrict__ qmats, const float* __restrict__ qT1, int T,
+__device__ __forceinline__ void cat_posterior_row(const float* __restrict__ Q1, const float* __restrict__ Q0, bool last,
                                                   const float* __restrict__ in0, int is_logits, const float* __restrict__ log_vt,
-                                                  const int64_t* __restrict__ t, const int64_t* __restrict__ batch, int n,
                                                   float* __restrict__ out, int i) {
-  if (i >= n) return;
-  const int64_t tv = t[batch[i]];
-  const int64_t tm1 = tv > 0 ? tv - 1 : 0;
   float l0[K], lt[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -72,8 +84,6 @@ __device__ __forceinline__ void cat_posterior_row(const float* __restrict__ qmat
 #pragma unroll
     for (int k = 0; k < K; ++k) l0[k] = (l0[k] - m) - ls;
   }
-  const float* Q1 = qT1 + (size_t)tv * K * K;
-  const float* Q0 = qmats + (size_t)tm1 * K * K;
   float e0[K], et[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -98,14 +108,34 @@ __device__ __forceinline__ void cat_posterior_row(const float* __restrict__ qmat
   for (int k = 0; k < K; ++k) s += expf(o[k] - m);
   const float lse = m + logf(s);
 #pragma unroll
-  for (int k = 0; k < K; ++k) out[(size_t)i * K + k] = (tv == 0) ? l0[k] : (o[k] - lse);
+  for (int k = 0; k < K; ++k) out[(size_t)i * K + k] = last ? l0[k] : (o[k] - lse);
 }
 template <int K>
 __global__ void cat_posterior_kernel(const float* __restrict__ qmats, const float* __restrict__ qT1, int T,
                                      const float* __restrict__ in0, int is_logits, const float* __restrict__ log_vt,
                                      const int64_t* __restrict__ t, const int64_t* __restrict__ batch, int n,
                                      float* __restrict__ out) {
-  cat_posterior_row<K>(qmats, qT1, T, in0, is_logits, log_vt, t, batch, n, out, blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t tv = t[batch[i]];
+  const int64_t tm1 = tv > 0 ? tv - 1 : 0;
+  cat_posterior_row<K>(qT1 + (size_t)tv * K * K, qmats + (size_t)tm1 * K * K, tv == 0, in0, is_logits, log_vt, out, i);
+}
+// jump form: Q1 = row `row` of the jump tables' Q_{t|s}^T, Q0 = q_mats[s]; (t, s, row) per graph, or the launch scalars (s_s, row_s) for
+// every graph when `row` is null.  s < 0 (nothing below level 0) is read as 0, like tm1 above.
+template <int K>
+__global__ void cat_posterior_jump_kernel(const float* __restrict__ qmats, const float* __restrict__ qTj,
+                                          const float* __restrict__ in0, int is_logits, const float* __restrict__ log_vt,
+                                          const int64_t* __restrict__ t, const int64_t* __restrict__ t_prev,
+                                          const int64_t* __restrict__ row, int64_t s_s, int64_t row_s,
+                                          const int64_t* __restrict__ batch, int n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t g = batch[i];
+  const int64_t r = row ? row[g] : row_s;
+  int64_t sv = row ? t_prev[g] : s_s;
+  sv = sv > 0 ? sv : 0;
+  cat_posterior_row<K>(qTj + (size_t)r * K * K, qmats + (size_t)sv * K * K, t[g] == 0, in0, is_logits, log_vt, out, i);
 }
 
 __device__ __forceinline__ void gumbel_argmax_row(const float* __restrict__ logits, const float* __restrict__ u, int K, int n,
@@ -166,13 +196,42 @@ __global__ void prior_draw_kernel(const PriorLogits lg, const U* __restrict__ u,
 // back by the same thread).  MolDiff's class counts (8 atom types, 6 bond types) only; other counts take the separate kernels.
 __global__ void step_transition_kernel(const StepTransArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  pos_posterior_elem(a.c0, a.ct, a.sd, a.pos, a.pred_pos, a.eps, a.t, a.batch_node, a.N, a.pos_next, i);
+  if (i < 3 * a.N) {
+    const int64_t tv = a.t[a.batch_node[i / 3]];
+    pos_posterior_elem(a.c0[tv], a.ct[tv], a.sd[tv], tv == 0, a.pos, a.pred_pos, a.eps, a.pos_next, i);
+  }
   if (i < a.N) {
-    cat_posterior_row<8>(a.node_q, a.node_qT1, a.T, a.pred_node, 1, a.log_node, a.t, a.batch_node, a.N, a.log_node_next, i);
+    const int64_t tv = a.t[a.batch_node[i]];
+    const int64_t tm1 = tv > 0 ? tv - 1 : 0;
+    cat_posterior_row<8>(a.node_qT1 + (size_t)tv * 64, a.node_q + (size_t)tm1 * 64, tv == 0, a.pred_node, 1, a.log_node, a.log_node_next, i);
     gumbel_argmax_row(a.log_node_next, a.u_node, 8, a.N, nullptr, a.h_node_next, a.node_cls, i);
   }
   if (i < a.Eh) {
-    cat_posterior_row<6>(a.edge_q, a.edge_qT1, a.T, a.pred_half, 1, a.log_half, a.t, a.batch_half, a.Eh, a.log_half_next, i);
+    const int64_t tv = a.t[a.batch_half[i]];
+    const int64_t tm1 = tv > 0 ? tv - 1 : 0;
+    cat_posterior_row<6>(a.edge_qT1 + (size_t)tv * 36, a.edge_q + (size_t)tm1 * 36, tv == 0, a.pred_half, 1, a.log_half, a.log_half_next, i);
+    gumbel_argmax_row(a.log_half_next, a.u_half, 6, a.Eh, nullptr, a.h_half_next, a.half_cls, i);
+  }
+}
+
+// Its sibling for strided sampling (no reference line: the reference visits every level): the same launch moving the state from level
+// t = tau_j to s = tau_{j+1} < t - 1.  Same row functions, same reads of the time tensor; the table rows are those of schedule position
+// j.row -- a launch scalar, all molecules of a batch share the schedule -- of the jump tables, and q_mats[j.s].  The t == 0 branch is
+// the row functions' own.
+__global__ void step_jump_kernel(const StepTransArgs a, const StepJumpRows j) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 3 * a.N) {
+    const int64_t tv = a.t[a.batch_node[i / 3]];
+    pos_posterior_elem(j.c0[j.row], j.ct[j.row], j.sd[j.row], tv == 0, a.pos, a.pred_pos, a.eps, a.pos_next, i);
+  }
+  if (i < a.N) {
+    const int64_t tv = a.t[a.batch_node[i]];
+    cat_posterior_row<8>(j.node_qT + (size_t)j.row * 64, a.node_q + (size_t)j.s * 64, tv == 0, a.pred_node, 1, a.log_node, a.log_node_next, i);
+    gumbel_argmax_row(a.log_node_next, a.u_node, 8, a.N, nullptr, a.h_node_next, a.node_cls, i);
+  }
+  if (i < a.Eh) {
+    const int64_t tv = a.t[a.batch_half[i]];
+    cat_posterior_row<6>(j.edge_qT + (size_t)j.row * 36, a.edge_q + (size_t)j.s * 36, tv == 0, a.pred_half, 1, a.log_half, a.log_half_next, i);
     gumbel_argmax_row(a.log_half_next, a.u_half, 6, a.Eh, nullptr, a.h_half_next, a.half_cls, i);
   }
 }
@@ -285,6 +344,31 @@ void launch_cat_posterior(const float* qmats, const float* qT1, int K, int T, co
     default: break;
   }
 #undef MDX_CP
+}
+
+void launch_pos_posterior_jump(const float* c0, const float* ct, const float* sd, const float* xt, const float* x0, const float* eps,
+                               const int64_t* t, const int64_t* row, int64_t row_s, const int64_t* batch, int n, float* out,
+                               hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pos_posterior_jump_kernel, dim3((3 * n + 255) / 256), dim3(256), 0, s, c0, ct, sd, xt, x0, eps, t, row, row_s,
+                     batch, n, out);
+}
+
+void launch_cat_posterior_jump(const float* qmats, const float* qTj, int K, const float* in0, int is_logits, const float* log_vt,
+                               const int64_t* t, const int64_t* t_prev, const int64_t* row, int64_t s_s, int64_t row_s,
+                               const int64_t* batch, int n, float* out, hipStream_t s) {
+  if (n <= 0) return;
+  dim3 g((n + 255) / 256), b(256);
+#define MDX_CPJ(KK)                                                                                                                  \
+  case KK:                                                                                                                           \
+    hipLaunchKernelGGL(cat_posterior_jump_kernel<KK>, g, b, 0, s, qmats, qTj, in0, is_logits, log_vt, t, t_prev, row, s_s, row_s,    \
+                       batch, n, out);                                                                                               \
+    break;
+  switch (K) {
+    MDX_CPJ(2) MDX_CPJ(3) MDX_CPJ(4) MDX_CPJ(5) MDX_CPJ(6) MDX_CPJ(7) MDX_CPJ(8)
+    default: break;
+  }
+#undef MDX_CPJ
 }
 
 // ---- training: q(v_t | v_0) draw of a clean batch in one launch (round 6) -------------------------------------------------------------
@@ -491,6 +575,11 @@ void launch_cat_loss(const float* qmats, const float* qT1, int K, const float* l
 void launch_step_transition(const StepTransArgs& a, hipStream_t s) {
   const int n = std::max(3 * a.N, a.Eh);
   if (n > 0) hipLaunchKernelGGL(step_transition_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a);
+}
+
+void launch_step_jump(const StepTransArgs& a, const StepJumpRows& j, hipStream_t s) {
+  const int n = std::max(3 * a.N, a.Eh);
+  if (n > 0) hipLaunchKernelGGL(step_jump_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, j);
 }
 
 void launch_uncertainty_grad(const float* logits, int K, int n, float* glogits, hipStream_t s) {

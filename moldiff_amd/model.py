@@ -10,8 +10,9 @@ the fused sampling kernels; with grad enabled it runs layer by layer on the diff
 All arithmetic runs in ``libmoldiff_hip.so``; torch is used for device memory, streams and the output
 containers only.  Differences a caller can see, all opt-in keyword arguments with reference defaults:
 ``sample(..., seed=, mol_ids=, noise=, return_traj=)`` (per-molecule Philox noise instead of torch's
-global generator, see DESIGN.md "noise") and ``sample(..., scaffold=, start_step=)`` (scaffold-constrained sampling and partial
-chains, an addition beyond the reference: ``moldiff_amd/scaffold.py``).
+global generator, see DESIGN.md "noise"), ``sample(..., scaffold=, start_step=)`` (scaffold-constrained sampling and partial
+chains, an addition beyond the reference: ``moldiff_amd/scaffold.py``) and ``sample(..., num_steps=, timesteps=)`` (strided sampling:
+the reverse chain on a subset of the levels, an addition beyond the reference: ``moldiff_amd/schedule.py``).
 """
 import ctypes
 import os
@@ -29,6 +30,7 @@ GUIDANCE_TYPES = ('entropy', 'uncertainty', 'uncertainty_bond', 'entropy_bond', 
 from .common import MLP, GaussianSmearing
 from .diffusion import get_beta_schedule
 from .graph import NodeEdgeNet, _sig, synth_gates
+from .schedule import pairs, resolve_schedule
 from .transition import ContigousTransition, GeneralCategoricalTransition
 
 class MolDiff(Module):
@@ -232,9 +234,12 @@ class MolDiff(Module):
         return {'pred_node': pn, 'pred_pos': pp, 'pred_halfedge': ph}
 
     def sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, *, seed=None, mol_ids=None, noise=None,
-                return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False, scaffold=None, start_step=None):
+                return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False, scaffold=None, start_step=None,
+                num_steps=None, timesteps=None):
         """Stateful driver of the reverse chain (``init()`` then ``step(i)`` for i = 0..T-1); ``sample`` wraps it.
         scaffold / start_step: see ``sample``; with start_step = s the loop iterations are i = T-s..T-1.
+        num_steps / timesteps: see ``sample``; with a schedule of m levels the loop iterations are j = 0..m-1, ``step(j)`` is schedule
+        iteration j and ``set_state(frame=j)`` addresses schedule positions, whether or not start_step is given.
         overlap_guidance=True runs the guidance chain on a side stream concurrently with the denoiser forward of the same step
         (same results).  It paid in round 1 (0.7 ms per step, the kernels left tails for each other); with the round-2 kernels
         filling every CU by themselves it costs 0.5 ms (27.6 vs 28.1 ms per step), so in line is the default."""
@@ -245,13 +250,16 @@ class MolDiff(Module):
             if scaffold is not None or start_step is not None:
                 raise NotImplementedError('scaffold / start_step in the continuous categorical space: not built (no shipped config '
                                           'uses that space)')
+            if num_steps is not None or timesteps is not None:
+                raise NotImplementedError('num_steps / timesteps in the continuous categorical space: not built (no shipped config '
+                                          'uses that space)')
             return _ContinuousSampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj)
         return _Sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                        bond_predictor, guidance, overlap_guidance, scaffold, start_step)
+                        bond_predictor, guidance, overlap_guidance, scaffold, start_step, num_steps, timesteps)
 
     @torch.no_grad()
     def sample(self, n_graphs, batch_node, halfedge_index, batch_halfedge, bond_predictor=None, guidance=None, *,
-               seed=None, mol_ids=None, noise=None, return_traj=True, scaffold=None, start_step=None):
+               seed=None, mol_ids=None, noise=None, return_traj=True, scaffold=None, start_step=None, num_steps=None, timesteps=None):
         """Run the T-step reverse chain for a packed batch of fully-connected molecule graphs.
 
         Returns {'pred': [node logits (N,Kn), pos (N,3), halfedge logits (Eh,Ke)] of the last step,
@@ -267,11 +275,22 @@ class MolDiff(Module):
         start_step = s (0 < s <= T; needs a scaffold that carries the whole molecule): start from that molecule noised to level s - 1
         instead of the prior and run diffusion steps s-1 .. 0; the trajectory then has s + 1 frames.  An all-false mask gives an
         SDEdit-style perturbation of the molecule.
+        num_steps = m (2 <= m <= T, or <= start_step): strided sampling -- run the chain on m uniformly spaced levels T-1 (or
+        start_step-1) .. 0 (``schedule.make_schedule``) instead of all of them; timesteps = an explicit strictly decreasing list of
+        levels with those ends (one of the two).  Iteration j evaluates the denoiser and the guidance at t = tau_j and draws the state at
+        tau_{j+1} from the exact posterior q(x_{tau_{j+1}} | x_{tau_j}, x0_hat) of the same forward process; the trajectory has m + 1
+        frames.  The noise of the move leaving level t is draw T - t under every schedule (a scaffold's: T + (T - t)), so a schedule
+        that visits every level is the full chain bit for bit.  The guidance displacement is added once per iteration and is NOT
+        rescaled: fewer iterations, less total displacement.  Sample quality at reduced step counts has not been measured.
         """
         sm = self.sampler(n_graphs, batch_node, halfedge_index, batch_halfedge, seed=seed, mol_ids=mol_ids, noise=noise,
                           return_traj=return_traj, bond_predictor=bond_predictor, guidance=guidance, scaffold=scaffold,
-                          start_step=start_step)
+                          start_step=start_step, num_steps=num_steps, timesteps=timesteps)
         sm.init()
+        if getattr(sm, 'sched', None) is not None:
+            for j in range(len(sm.sched)):
+                sm.step(j)
+            return sm.result()
         for i in range(0 if start_step is None else self.num_timesteps - start_step, self.num_timesteps):
             sm.step(i)
         return sm.result()
@@ -287,13 +306,15 @@ class _Sampler:
     edge (``traj.LazyOneHot``): 0.16 GB instead of 2.1 GB at 256 molecules."""
 
     def __init__(self, model, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                 bond_predictor, guidance, overlap_guidance=False, scaffold=None, start_step=None):
+                 bond_predictor, guidance, overlap_guidance=False, scaffold=None, start_step=None, num_steps=None, timesteps=None):
         _lib._need_gpu(batch_node, halfedge_index, batch_halfedge)
         if start_step is not None:
             if scaffold is None:
                 raise ValueError('start_step needs a scaffold that carries the molecule to start from')
             if not 0 < int(start_step) <= model.num_timesteps:
                 raise ValueError(f'start_step {start_step} outside (0, {model.num_timesteps}]')
+        # strided sampling: the levels the chain visits (None: every level, on the full chain's own code path)
+        self.sched = resolve_schedule((model.num_timesteps if start_step is None else int(start_step)) - 1, num_steps, timesteps)
         self.guidance = None
         if guidance is not None:
             gui_type, gui_scale = guidance
@@ -327,6 +348,9 @@ class _Sampler:
         self.eps, self.u_n, self.u_h = torch.empty(N, 3, **f32), torch.empty(N, Kn, **f32), torch.empty(Eh, Ke, **f32)
         self.i0 = 0 if start_step is None else T - int(start_step)   # first loop iteration (a partial chain starts part-way)
         nT = T - self.i0 + 1 if return_traj else 2
+        if self.sched is not None:                                   # iterations are schedule positions 0..m-1
+            self.i0 = 0
+            nT = len(self.sched) + 1 if return_traj else 2
         self.h_node = torch.zeros(2, N, Kn, **f32)        # one-hot state, frames ping-pong
         self.h_half = torch.zeros(2, Eh, Ke, **f32)
         self.pos_traj = torch.zeros(nT, N, 3, **f32)
@@ -364,6 +388,14 @@ class _Sampler:
         pt, ntr, etr = m.pos_transition, m.node_transition, m.edge_transition
         self.tables = _lib.MdxTables(*(_lib.ptr(x) for x in (pt.coef_x0, pt.coef_xt, pt.std, ntr.q_mats, ntr.transpopse_q_onestep_mats,
                                                              etr.q_mats, etr.transpopse_q_onestep_mats)))
+        self.jump = None
+        if self.sched is not None:
+            # one row per schedule position, built once per sampler; plain tensors (not buffers: state_dict keys are untouched),
+            # kept alive next to the struct that points at them
+            tt, ss = (list(x) for x in zip(*pairs(self.sched)))
+            self._jump_t = (*pt.jump_coefs(tt, ss), ntr.jump_mats(tt, ss), etr.jump_mats(tt, ss))
+            self._levels = (ctypes.c_int32 * len(self.sched))(*self.sched)
+            self.jump = _lib.MdxJumpTables(*(_lib.ptr(x) for x in self._jump_t), self._levels, len(self.sched))
         self.cur, self.lcur, self.pcur = 0, 0, 0  # one-hot frame / log-prob frame / position (and id) frame of the current state
         self.sc = None
         if scaffold is not None:
@@ -425,9 +457,18 @@ class _Sampler:
     @torch.no_grad()
     def step(self, i):
         """Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call; with a scaffold a second one merges
-        its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold")."""
+        its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold").  With a schedule: schedule iteration i,
+        one call of ``mdx_sample_jump_full`` instead (same launches, the transition reads the jump tables' row i)."""
         L, T = _lib.lib(), self.T
-        draw = i + 1
+        if self.sched is None:
+            t, below = T - 1 - i, T - 2 - i
+        else:
+            # schedule iteration i: level tau_i -> tau_{i+1} (-1 after the last).  Noise is keyed by the level left, not by the
+            # iteration: draw T - t is what the full chain uses at level t (i + 1 with t = T - 1 - i), the merge's T + (T - t) likewise
+            if not 0 <= i < len(self.sched):
+                raise IndexError(f'schedule iteration {i} outside [0, {len(self.sched)})')
+            t, below = self.sched[i], (self.sched[i + 1] if i + 1 < len(self.sched) else -1)
+        draw = T - t
         if self.noise is not None:
             e, a, b = self.noise(draw)
             self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
@@ -443,14 +484,17 @@ class _Sampler:
         self.eng.use_matrix_path(self._path)
         if self._bp_path is not None:
             self.bp_eng.use_matrix_path(self._bp_path)
-        _lib.check(L.mdx_sample_step_full(self.eng.h, self.g.h, ctypes.byref(self.tables), T - 1 - i, P(self.bn), P(self.bh),
-                                          ctypes.byref(cur), ctypes.byref(nxt), P(self.preds[0]), P(self.preds[1]), P(self.preds[2]),
-                                          ctypes.byref(nz), P(self.t), P(self.node_ids[pn]), P(self.half_ids[pn]),
-                                          ctypes.byref(self.gd) if self.gd is not None else None, ws, nb, _lib.stream()))
+        tail = (t, P(self.bn), P(self.bh), ctypes.byref(cur), ctypes.byref(nxt), P(self.preds[0]), P(self.preds[1]), P(self.preds[2]),
+                ctypes.byref(nz), P(self.t), P(self.node_ids[pn]), P(self.half_ids[pn]),
+                ctypes.byref(self.gd) if self.gd is not None else None, ws, nb, _lib.stream())
+        if self.jump is None:
+            _lib.check(L.mdx_sample_step_full(self.eng.h, self.g.h, ctypes.byref(self.tables), *tail))
+        else:
+            _lib.check(L.mdx_sample_jump_full(self.eng.h, self.g.h, ctypes.byref(self.tables), ctypes.byref(self.jump), i, *tail))
         if self.guidance is not None and self.gd is None:  # the seven objectives that are torch expressions on the logits
             self._guide(self.h_node[c], self.pos_traj[pc], self.pos_traj[pn], self.h_half[n], self.log_half[ln])
         if self.sc is not None:
-            self._merge(self.sc, T - 2 - i, T + 1 + i, n, ln, pn)
+            self._merge(self.sc, below, T + (T - t), n, ln, pn)
         self.cur, self.lcur, self.pcur = n, ln, pn
 
     def _guide(self, h_node, pos, pos_prev, h_half_prev, log_half):

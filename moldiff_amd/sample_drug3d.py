@@ -172,6 +172,8 @@ def main(argv=None):
     ap.add_argument('--num_mols', type=int, default=0, help='override sample.num_mols')
     ap.add_argument('--scaffold', type=str, default='', help='V2000 mol block held fixed as the first atoms of every molecule '
                                                              '(overrides sample.scaffold)')
+    ap.add_argument('--num_steps', type=int, default=0, help='strided sampling: run the reverse chain on this many uniformly spaced '
+                                                             'levels instead of all of them (overrides sample.num_steps)')
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -214,6 +216,7 @@ def main(argv=None):
     batch_size = args.batch_size if args.batch_size > 0 else config.sample.batch_size
     save_traj_prob = float(getattr(config.sample, 'save_traj_prob', 0.0) or 0.0)
     scaffold_path = args.scaffold or config.sample.get('scaffold') or ''
+    num_steps = args.num_steps or config.sample.get('num_steps') or None   # trajectory files then hold num_steps + 1 frames
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -240,7 +243,8 @@ def main(argv=None):
         # each rank builds the scaffold of its own slice; its noise is keyed by global molecule id like the chain's
         scaffold = scaffold_for_sizes(scaffold_info, sizes[mine], featurizer, device) if scaffold_info is not None else None
         out = model.sample(hi - lo, ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], bond_predictor, guidance,
-                           seed=seed + i_batch, mol_ids=ids, return_traj=save_traj_prob > 0, scaffold=scaffold)
+                           seed=seed + i_batch, mol_ids=ids, return_traj=save_traj_prob > 0, scaffold=scaffold,
+                           **({} if num_steps is None else {'num_steps': int(num_steps)}))
         # trajectories stay rank-local (scripts/sample_drug3d.py:155 looks at ~2 % of them): the owner decodes and writes
         # them, named by global molecule id; whether a molecule is drawn depends only on (seed, id), not on the sharding
         if save_traj_prob > 0:

@@ -17,6 +17,27 @@ from . import _lib
 _FUSED_NOISE = True   # add_noise as one launch (tests turn it off to compare against the per-operator form)
 
 
+def _check_pairs(t, s, T):
+    """level pairs of a downward move as int64 numpy arrays: 0 <= s < t < T, or (0, -1) for the last move"""
+    t, s = np.atleast_1d(np.asarray(t, dtype=np.int64)), np.atleast_1d(np.asarray(s, dtype=np.int64))
+    if t.shape != s.shape or t.ndim != 1:
+        raise ValueError('t and s must be 1-d and of the same length')
+    if ((t < 0) | (t >= T)).any() or (s >= t).any() or ((s < 0) & ~((t == 0) & (s == -1))).any():
+        raise ValueError(f'every pair must satisfy 0 <= s < t < {T} (or t = 0, s = -1 for the last move)')
+    return t, s
+
+
+def _unique_pairs(t, t_prev):
+    """per-graph device tensors (t, t_prev) -> the distinct pairs (numpy) and every graph's row among them (one host read; where
+    t == 0 the level below is -1 whatever was passed: nothing is read from it)"""
+    tc, sc = t.detach().to('cpu', torch.int64).reshape(-1), t_prev.detach().to('cpu', torch.int64).reshape(-1)
+    if tc.shape != sc.shape:
+        raise ValueError('t and t_prev must have the same length')
+    sc = torch.where(tc == 0, torch.full_like(sc, -1), sc)
+    uniq, row = torch.unique(torch.stack([tc, sc], dim=1), dim=0, return_inverse=True)
+    return uniq[:, 0].numpy(), uniq[:, 1].numpy(), row.contiguous()
+
+
 class ContigousTransition(nn.Module):
     """Gaussian diffusion over R^d (used for atom positions)."""
 
@@ -35,6 +56,7 @@ class ContigousTransition(nn.Module):
         self.coef_x0 = to_torch_const(np.sqrt(abar_prev) * betas / (1 - abar))
         self.coef_xt = to_torch_const(np.sqrt(alphas) * (1 - abar_prev) / (1 - abar))
         self.std = to_torch_const(np.sqrt((1 - abar_prev) * betas / (1 - abar)))
+        self._abar64 = np.asarray(abar, dtype=np.float64)   # host copy for jump_coefs; a plain attribute: state_dict keys are untouched
 
     def add_noise(self, x, time_step, batch, eps=None):
         """q(x_t | x_0); loss-side helper (not on the sampling path), plain torch ops on `x`'s device.
@@ -46,11 +68,42 @@ class ContigousTransition(nn.Module):
         pert = a_bar.sqrt() * x + (1 - a_bar).sqrt() * (torch.randn_like(x) if eps is None else eps)
         return pert if self.num_classes is None else (pert, x)
 
-    def get_prev_from_recon(self, x_t, x_recon, t, batch, eps=None):
+    def jump_coefs(self, t, s):
+        """Coefficients of q(x_s | x_t, x_0) for the level pairs (t[i], s[i]), s[i] < t[i] (strided sampling; an addition beyond the
+        reference): fp32 tensors (c0, ct, sd), one entry per pair, on the device of the module's tables.  With a = abar_t / abar_s:
+            c0 = sqrt(abar_s) (1 - a) / (1 - abar_t),  ct = sqrt(a) (1 - abar_s) / (1 - abar_t),  sd = sqrt((1 - abar_s) (1 - a) / (1 - abar_t))
+        in float64, rounded once.  Pairs with s == t - 1 (the last move (0, -1) included) are COPIED from coef_x0 / coef_xt / std:
+        abar_t / abar_{t-1} need not round to alphas[t], and a schedule that visits every level must be the full chain bit for bit."""
+        t, s = _check_pairs(t, s, len(self._abar64))
+        ab = self._abar64
+        out = np.zeros((3, len(t)), dtype=np.float32)
+        far = s < t - 1
+        if far.any():
+            at, as_ = ab[t[far]], ab[s[far]]
+            a = at / as_
+            out[0, far] = np.sqrt(as_) * (1 - a) / (1 - at)
+            out[1, far] = np.sqrt(a) * (1 - as_) / (1 - at)
+            out[2, far] = np.sqrt((1 - as_) * (1 - a) / (1 - at))
+        c = torch.from_numpy(out).to(self.coef_x0.device)
+        if (~far).any():
+            near = torch.from_numpy(np.nonzero(~far)[0]).to(c.device)
+            tn = torch.from_numpy(t[~far]).to(c.device)
+            for j, tab in enumerate((self.coef_x0, self.coef_xt, self.std)):
+                c[j, near] = tab.detach()[tn]
+        return c[0].contiguous(), c[1].contiguous(), c[2].contiguous()
+
+    def get_prev_from_recon(self, x_t, x_recon, t, batch, eps=None, *, t_prev=None):
         """mu = coef_x0[t] x0_hat + coef_xt[t] x_t ; x_{t-1} = mu + std[t] eps, and exactly mu where t == 0.
-        `eps` may be injected (parity tests); otherwise it is drawn with torch's generator like the reference."""
+        `eps` may be injected (parity tests); otherwise it is drawn with torch's generator like the reference.
+        t_prev (per graph, < t; ignored where t == 0): draw x_{t_prev} instead, from the jump posterior of `jump_coefs` (positions only)."""
         if eps is None:
             eps = torch.randn_like(x_t)
+        if t_prev is not None:
+            if x_t.shape[-1] != 3:
+                raise NotImplementedError('t_prev for class features of the continuous categorical space: not built')
+            tt, ss, row = _unique_pairs(t, t_prev)
+            c0, ct, sd = self.jump_coefs(tt, ss)
+            return _lib.pos_posterior_jump(c0, ct, sd, x_t, x_recon, eps, t, row.to(x_t.device), batch)
         return _lib.pos_posterior(self.coef_x0, self.coef_xt, self.std, x_t, x_recon, eps, t, batch)
 
     def sample_init(self, shape):
@@ -94,12 +147,38 @@ class GeneralCategoricalTransition(nn.Module):
     def onehot_encode(self, v):
         return F.one_hot(v, self.num_classes).float()
 
-    def q_v_posterior(self, log_v0, log_vt, t, batch, v0_prob):
-        """log q(v_{t-1} | v_t, v_0); `log_v0` holds log-probabilities when `v0_prob` else is arg-maxed."""
+    def jump_mats(self, t, s):
+        """Q_{t|s}^T = (Q_{s+1} ... Q_t)^T for the level pairs (t[i], s[i]), s[i] < t[i] (strided sampling; an addition beyond the
+        reference): fp32 (P,K,K) on the device of the module's tables, stored transposed like `transpopse_q_onestep_mats` and paired with
+        q_mats[s] in the posterior.  The product is formed in float64 from the float64 one-step matrices and rounded once.  Pairs with
+        s == t - 1 (the last move (0, -1) included) are COPIED from transpopse_q_onestep_mats, see ContigousTransition.jump_coefs."""
+        t, s = _check_pairs(t, s, self.num_timesteps)
+        K = self.num_classes
+        out = np.zeros((len(t), K, K), dtype=np.float32)
+        far = s < t - 1
+        for i in np.nonzero(far)[0]:
+            q = self._get_transition_mat(int(s[i]) + 1)
+            for l in range(int(s[i]) + 2, int(t[i]) + 1):
+                q = q @ self._get_transition_mat(l)
+            out[i] = q.T
+        m = torch.from_numpy(out).to(self.q_mats.device)
+        if (~far).any():
+            near = torch.from_numpy(np.nonzero(~far)[0]).to(m.device)
+            m[near] = self.transpopse_q_onestep_mats.detach()[torch.from_numpy(t[~far]).to(m.device)]
+        return m.contiguous()
+
+    def q_v_posterior(self, log_v0, log_vt, t, batch, v0_prob, *, t_prev=None):
+        """log q(v_{t-1} | v_t, v_0); `log_v0` holds log-probabilities when `v0_prob` else is arg-maxed.
+        t_prev (per graph, < t; ignored where t == 0): log q(v_{t_prev} | v_t, v_0) instead, the jump posterior of `jump_mats`."""
         if not v0_prob:
             log_v0 = index_to_log_onehot(log_v0.argmax(dim=-1), self.num_classes, checked=False)
         if log_v0.ndim != 2:
             raise NotImplementedError('ndim not supported')
+        if t_prev is not None:
+            tt, ss, row = _unique_pairs(t, t_prev)
+            dev = log_v0.device
+            return _lib.cat_posterior_jump(self.q_mats, self.jump_mats(tt, ss), log_v0, log_vt, t,
+                                           torch.from_numpy(ss)[row].to(dev), row.to(dev), batch)
         return _lib.cat_posterior(self.q_mats, self.transpopse_q_onestep_mats, log_v0, log_vt, t, batch)
 
     def q_v_posterior_autograd(self, log_v0, log_vt, t, batch):
