@@ -2714,9 +2714,17 @@ extern "C" int mdx_op_mul_gather_bwd_t(const void* g, const void* a, const void*
   hipStream_t s = (hipStream_t)stream;
   const TP tg{g, dt & 1}, ta{a, (dt >> 1) & 1}, tt{t, (dt >> 2) & 1};
   const TPW tda{da, (dt >> 3) & 1}, tdt{dtab, (dt >> 4) & 1};
-  if (da && M > 0)
+  const bool want_da = da && M > 0, want_dt = dtab && R > 0;
+  // operands of the launches below (no rows: every segment is empty and g / a are never read)
+  if (want_da && (!g || !t || !idx)) return bad("mul_gather_bwd: null operand");
+  if (want_dt && (!order || !ptr || (M > 0 && (!g || !a)))) return bad("mul_gather_bwd: null operand");
+  // the 4-wide kernels read and write 16-byte (float16: 8-byte) vectors: refuse a misaligned base like the forward does
+  if ((want_da && !(tp_vec_ok(g, tg.h, 4) && tp_vec_ok(t, tt.h, 4) && tp_vec_ok(da, tda.h, 4))) ||
+      (want_dt && !(tp_vec_ok(g, tg.h, 4) && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(dtab, tdt.h, 4))))
+    return bad("mul_gather: rows must be aligned");
+  if (want_da)
     hipLaunchKernelGGL(mulg_fwd_kernel, dim3(nblk((size_t)M * (F / 4))), dim3(256), 0, s, tg, tt, idx, M, F / 4, tda, 0);
-  if (dtab && R > 0)
+  if (want_dt)
     hipLaunchKernelGGL(mulg_segsum_kernel, dim3(nblk((size_t)R * (F / 4))), dim3(256), 0, s, tg, ta, order, ptr, R, F / 4, tdt);
   return launched();
 }
