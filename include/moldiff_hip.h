@@ -322,6 +322,35 @@ int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tables, int32_t
                        const mdx_step_noise* noise, const mdx_state* next, float log_off, uint8_t* node_cls, uint8_t* halfedge_cls,
                        float* pred_node, float* pred_pos, float* pred_halfedge, void* stream);
 
+/* ---- resampling (RePaint's loop around replacement conditioning; NO reference line: the reference's chain only walks down).
+ * Moves EVERY row of a sampler state UP from level s to level t > s, i.e. draws x_t ~ q(x_t | x_s) of the forward process, in one launch
+ * and without a host synchronisation.  A resampling chain calls it between two walks down the same block of levels
+ * (moldiff_amd/schedule.py resampling_path); fixed rows of a scaffold move too -- their x_s is a draw of q(x_s | x_0), pushed forward it
+ * is a draw of q(x_t | x_0), and the merge after the next step overwrites them anyway -- so the call is valid without a scaffold.
+ *   tables  : one row per (s, t) pair the caller asks for, with a = abar_t / abar_s: pos_coef_a = sqrt(a), pos_coef_s = sqrt(1 - a)
+ *             (ContigousTransition.forward_coefs: float64, rounded once); node / edge_qT_jump = (Q_{s+1} ... Q_t)^T, the SAME tables as
+ *             the node / edge_qT_jump of strided sampling, jump_mats(t, s): column x_s of the stored matrix is q(x_t | x_s)
+ *   row     : the pair's table row
+ *   reads   : node_cls_cur (N) / halfedge_cls_cur (Eh) uint8 class ids of the current state (a frame of the compact trajectory; ids >= K
+ *             are clamped) and pos_cur (N,3)
+ *   position: x_t = pos_coef_a x_s + pos_coef_s eps in fp32, two products and one sum, each rounded once (no contraction)
+ *   class   : Gumbel-max over log(Q_{t|s}[x_s, k] + 1e-30).clamp_min(-32) with the row's K uniforms -- the row function of
+ *             mdx_op_cat_add_noise (GeneralCategoricalTransition.add_noise, transition.py:245-283) with the jump matrix in place of the
+ *             cumulative one, so a forward jump from a one-hot x_s and training's add_noise are one arithmetic
+ *   writes  : for every row of `next` its one-hot row, its log row log(clamp(onehot, 1e-30)) (log_off as for mdx_prior_draw), its
+ *             position and (optional) its uint8 class id node_cls / halfedge_cls.  `next` must not overlap the buffers read.
+ *   noise   : as for mdx_scaffold_merge (draw >= 0: one Philox launch first); a resampling chain uses draw 2T + 2 + t for the move that
+ *             ARRIVES at level t, plus k (3T + 2) in the k-th walk of a block (moldiff_amd/schedule.py draw_index).
+ * Row-local: a row's result depends on that row's inputs and noise only, hence not on how a batch is sharded.  Class counts in 2..8. */
+typedef struct {
+  const float *pos_coef_a, *pos_coef_s;               /* (num) device */
+  const float *node_qT_jump, *edge_qT_jump;           /* (num,Kn,Kn) / (num,Ke,Ke) device, row-major */
+  int32_t Kn, Ke, num;
+} mdx_forward_tables;
+int mdx_forward_jump(mdx_graph_t g, const mdx_forward_tables* tables, int32_t row, const uint8_t* node_cls_cur,
+                     const uint8_t* halfedge_cls_cur, const float* pos_cur, const mdx_step_noise* noise, const mdx_state* next,
+                     float log_off, uint8_t* node_cls, uint8_t* halfedge_cls, void* stream);
+
 /* ---- harness consumer of the path's outputs (next-row) ---------------------------------------
  * seperate_outputs (utils/sample.py:4-30) + FeaturizeMol.decode_output (utils/transforms.py:65-122) on the device:
  * arg-max class + soft-max confidence per atom / half-edge, mask-type atoms (class >= num_element) dropped and the

@@ -23,7 +23,7 @@ EXPORTS = [
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
     'mdx_guidance_uncertainty_grad', 'mdx_add_inplace', 'mdx_decode_output', 'mdx_scaffold_merge',
-    'mdx_sample_jump_full', 'mdx_pos_posterior_jump', 'mdx_cat_posterior_jump',
+    'mdx_sample_jump_full', 'mdx_pos_posterior_jump', 'mdx_cat_posterior_jump', 'mdx_forward_jump',
     'mdx_profile_enable', 'mdx_profile_read', 'mdx_profile_kernel_name',
     'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_hgemm_nt', 'mdx_op_hgemm_tn', 'mdx_op_xgemm_nt', 'mdx_op_xgemm_tn', 'mdx_op_amp_adamw',
     'mdx_op_xgemm_nt_t', 'mdx_op_xgemm_nt_ln_t', 'mdx_op_xgemm_nt_ln_supported', 'mdx_op_xgemm_tn_t', 'mdx_op_ln_relu_fwd_t', 'mdx_op_ln_relu_bwd_t', 'mdx_op_ew_fwd_t', 'mdx_op_ew_bwd_t',
@@ -69,6 +69,11 @@ class MdxScaffoldTables(ctypes.Structure):  # == struct mdx_scaffold_tables
 
 class MdxScaffold(ctypes.Structure):  # == struct mdx_scaffold
     _fields_ = [(n, c_void_p) for n in ('node_mask', 'halfedge_mask', 'node_type', 'halfedge_type', 'node_pos')]
+
+
+class MdxForwardTables(ctypes.Structure):  # == struct mdx_forward_tables
+    _fields_ = [(n, c_void_p) for n in ('pos_coef_a', 'pos_coef_s', 'node_qT_jump', 'edge_qT_jump')] + [
+        ('Kn', c_int32), ('Ke', c_int32), ('num', c_int32)]
 
 
 class MdxBondFfnArgs(ctypes.Structure):   # == mdx_bondffn_args
@@ -199,6 +204,8 @@ def lib():
                                         [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p])
         L.mdx_scaffold_merge.argtypes = [c_void_p, POINTER(MdxScaffoldTables), c_int32, POINTER(MdxScaffold), POINTER(MdxStepNoise),
                                          POINTER(MdxState), c_float] + [c_void_p] * 6
+        L.mdx_forward_jump.argtypes = [c_void_p, POINTER(MdxForwardTables), c_int32, c_void_p, c_void_p, c_void_p, POINTER(MdxStepNoise),
+                                       POINTER(MdxState), c_float, c_void_p, c_void_p, c_void_p]
         L.mdx_device_count.argtypes = [POINTER(c_int)]
         L.mdx_profile_enable.argtypes = [c_int32]
         L.mdx_profile_read.argtypes = [c_int32, POINTER(c_int64), POINTER(ctypes.c_double)]
@@ -575,6 +582,34 @@ def cat_add_noise(q_mats, v, t, batch, u, K):
     check(lib().mdx_op_cat_add_noise(ptr(q_mats), K, q_mats.shape[0], ptr(v), ptr(t), ptr(batch), ptr(u), n, _LOG_EPS32, ptr(oh), ptr(lvt), ptr(lv0),
                                      stream()))
     return oh, lvt, lv0
+
+
+def forward_jump(graph, tables, row, node_ids, half_ids, pos, *, noise=None, seed=0, draw=-1):
+    """One up-move of resampling (``mdx_forward_jump``) on free-standing tensors: the state (uint8 class ids, positions) at level s ->
+    dict(h_node, log_node, h_halfedge, log_halfedge, pos, node_ids, half_ids) at level t.  tables = (c_a, c_s, node_qT, edge_qT) with
+    one row per (s, t) pair (ContigousTransition.forward_coefs, GeneralCategoricalTransition.jump_mats); noise = (eps, u_node,
+    u_halfedge) with draw < 0, or the library's Philox draw `draw` >= 0 of `seed`.  The sampler calls the entry point itself."""
+    ca, cs, qn, qe = (f32c(x) for x in tables)
+    _need_gpu(ca, cs, qn, qe, node_ids, half_ids, pos)
+    dev, N, Eh, Kn, Ke = pos.device, graph.N, graph.Eh, int(qn.shape[-1]), int(qe.shape[-1])
+    f32 = dict(dtype=torch.float32, device=dev)
+    if noise is None:
+        if draw < 0:
+            raise ValueError('give explicit noise or a draw index >= 0')
+        noise = (torch.empty(N, 3, **f32), torch.empty(N, Kn, **f32), torch.empty(Eh, Ke, **f32))
+    else:
+        noise, draw = tuple(f32c(x) for x in noise), -1
+    ids_n, ids_h, pos = node_ids.to(torch.uint8).contiguous(), half_ids.to(torch.uint8).contiguous(), f32c(pos)
+    out = {'h_node': torch.empty(N, Kn, **f32), 'log_node': torch.empty(N, Kn, **f32), 'h_halfedge': torch.empty(Eh, Ke, **f32),
+           'log_halfedge': torch.empty(Eh, Ke, **f32), 'pos': torch.empty(N, 3, **f32),
+           'node_ids': torch.empty(N, dtype=torch.uint8, device=dev), 'half_ids': torch.empty(Eh, dtype=torch.uint8, device=dev)}
+    tb = MdxForwardTables(ptr(ca), ptr(cs), ptr(qn), ptr(qe), Kn, Ke, int(ca.numel()))
+    nxt = MdxState(ptr(out['h_node']), ptr(out['pos']), ptr(out['h_halfedge']), ptr(out['log_node']), ptr(out['log_halfedge']))
+    nz = MdxStepNoise(int(seed), int(draw), *(ptr(x) for x in noise))
+    check(lib().mdx_forward_jump(graph.h, ctypes.byref(tb), int(row), ptr(ids_n), ptr(ids_h), ptr(pos), ctypes.byref(nz), ctypes.byref(nxt),
+                                 log_eps32(), ptr(out['node_ids']), ptr(out['half_ids']), stream()))
+    out['noise'] = noise
+    return out
 
 
 def prior_draw(init_prob, u, n, cls=None, onehot=None, log_onehot=None, cls8=None):

@@ -1502,6 +1502,34 @@ extern "C" int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tb, 
   return MDX_OK;
 }
 
+extern "C" int mdx_forward_jump(mdx_graph_t g, const mdx_forward_tables* tb, int32_t row, const uint8_t* node_cls_cur,
+                                const uint8_t* halfedge_cls_cur, const float* pos_cur, const mdx_step_noise* noise,
+                                const mdx_state* next, float log_off, uint8_t* node_cls, uint8_t* halfedge_cls, void* stream) {
+  if (!g || !tb || !noise || !next) return fail(MDX_ERR_ARG, "null argument");
+  if (tb->Kn < 2 || tb->Kn > 8 || tb->Ke < 2 || tb->Ke > 8) return fail(MDX_ERR_UNSUPPORTED, "class counts must be in 2..8");
+  if (row < 0 || row >= tb->num) return fail(MDX_ERR_ARG, "table row %d outside [0, %d)", row, tb->num);
+  const int N = (int)g->N, Eh = (int)g->Eh;
+  if (N == 0) return MDX_OK;
+  if (!tb->pos_coef_a || !tb->pos_coef_s || !tb->node_qT_jump || (Eh > 0 && !tb->edge_qT_jump)) return fail(MDX_ERR_ARG, "incomplete mdx_forward_tables");
+  if (!node_cls_cur || !pos_cur || (Eh > 0 && !halfedge_cls_cur) || !next->h_node || !next->pos || !next->log_node ||
+      (Eh > 0 && (!next->h_halfedge || !next->log_halfedge)) || !noise->eps_pos || !noise->u_node || (Eh > 0 && !noise->u_halfedge))
+    return fail(MDX_ERR_ARG, "null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  if (noise->draw >= 0)
+    launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, N, Eh, tb->Kn,
+                        tb->Ke, noise->eps_pos, noise->u_node, noise->u_halfedge, s);
+  ForwardJumpArgs a{};
+  a.N = N; a.Eh = Eh; a.Kn = tb->Kn; a.Ke = tb->Ke; a.row = row; a.log_off = log_off;
+  a.ca = tb->pos_coef_a; a.cs = tb->pos_coef_s; a.node_qT = tb->node_qT_jump; a.edge_qT = tb->edge_qT_jump;
+  a.node_cls = node_cls_cur; a.half_cls = halfedge_cls_cur; a.pos = pos_cur;
+  a.eps = noise->eps_pos; a.u_node = noise->u_node; a.u_half = noise->u_halfedge;
+  a.pos_next = next->pos; a.h_node = next->h_node; a.log_node = next->log_node; a.h_half = next->h_halfedge; a.log_half = next->log_halfedge;
+  a.node_cls_next = node_cls; a.half_cls_next = halfedge_cls;
+  launch_forward_jump(a, s);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // bond predictor: forward with a per-block tape, and the data-gradient backward w.r.t. positions
 // ------------------------------------------------------------------------------------------------

@@ -357,6 +357,16 @@ struct ScaffoldMergeArgs {  // mdx_transition.hip: fixed rows of a sampler state
   float *pred_node, *pred_pos, *pred_half;   // written at level -1 only; may be nullptr
 };
 void launch_scaffold_merge(const ScaffoldMergeArgs& a, hipStream_t s);
+struct ForwardJumpArgs {  // mdx_transition.hip: every row of a sampler state moves UP from level s to level t > s (resampling)
+  int N, Eh, Kn, Ke, row;                    // row: the (s -> t) pair's row of the four tables
+  float log_off;
+  const float *ca, *cs, *node_qT, *edge_qT;  // (num), (num), (num,Kn,Kn), (num,Ke,Ke): forward_coefs / jump_mats of the pairs
+  const uint8_t *node_cls, *half_cls;        // the current state's class ids (N) / (Eh)
+  const float *pos, *eps, *u_node, *u_half;  // (N,3), (N,3), (N,Kn), (Eh,Ke)
+  float *pos_next, *h_node, *log_node, *h_half, *log_half;
+  uint8_t *node_cls_next, *half_cls_next;    // may be nullptr
+};
+void launch_forward_jump(const ForwardJumpArgs& a, hipStream_t s);
 // the same three sums after an EA_AGG edge kernel A: aggr / SR combine each node's partial rows pbase[v] .. pbase[v+1] of P / PR
 // in order, SL is still the indexed sum over FL
 void launch_seg_reduce_block2(const float* P, const float* PR, const float* FL, const int* pbase, const int* col_ptr,

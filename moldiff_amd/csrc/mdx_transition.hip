@@ -380,7 +380,9 @@ void launch_cat_posterior_jump(const float* qmats, const float* qTj, int K, cons
 // The row function: the Gumbel-max draw of q(v_t | v_0 = cv) over the K logits of row Q = q_mats[t] with the row's K uniforms; writes
 // log_v0 (K values) when given and returns the drawn class.  Shared with scaffold_merge_kernel below, so that the conditioned sampler
 // draws its fixed rows with the arithmetic training perturbs them with.
-template <int K>
+// QT: Q is stored transposed (the jump tables' Q_{t|s}^T of a forward jump, forward_jump_kernel below) -- the same sum over the
+// same source classes in the same order, only the element's address differs.
+template <int K, bool QT = false>
 __device__ __forceinline__ int cat_add_noise_row(const float* __restrict__ Q, int cv, const float* __restrict__ u, float log_off,
                                                  float* __restrict__ log_v0) {
   float l0[K], e0[K];
@@ -396,7 +398,7 @@ __device__ __forceinline__ int cat_add_noise_row(const float* __restrict__ Q, in
   for (int k = 0; k < K; ++k) {
     float f = 0.f;
 #pragma unroll
-    for (int j = 0; j < K; ++j) f += e0[j] * Q[j * K + k];
+    for (int j = 0; j < K; ++j) f += e0[j] * (QT ? Q[k * K + j] : Q[j * K + k]);
     const float lg = fmaxf(logf(f + 1e-30f), -32.f);
     const float g = -logf(-logf(u[k] + 1e-30f) + 1e-30f);
     const float z = g + lg;
@@ -693,4 +695,71 @@ void launch_scaffold_merge(const ScaffoldMergeArgs& a, hipStream_t s) {
   const dim3 g((n + 255) / 256), b(256);
   if (a.Kn == 8 && a.Ke == 6) hipLaunchKernelGGL((scaffold_merge_kernel<8, 6>), g, b, 0, s, a);  // MolDiff's class counts
   else hipLaunchKernelGGL((scaffold_merge_kernel<0, 0>), g, b, 0, s, a);
+}
+
+// ---- resampling (RePaint): the forward move of the WHOLE state from level s up to level t > s -----------------------------------------------
+// No reference line: the reference's chain only walks down.  Every row moves (a fixed row's x_s is a draw of q(x_s | x_0), pushed forward
+// it is a draw of q(x_t | x_0); the next scaffold merge overwrites it anyway), so the move needs no mask and is valid without a scaffold.
+//   positions: x_t = c_a x_s + c_s eps, (c_a, c_s) = (sqrt(a), sqrt(1 - a)), a = abar_t / abar_s: the caller's table row
+//              (ContigousTransition.forward_coefs); two products and one sum, each rounded once (this file is built without contraction)
+//   classes  : Gumbel-max over log(Q_{t|s}[x_s, k] + 1e-30).clamp_min(-32) with the row's K uniforms -- cat_add_noise_row with row
+//              `row` of the jump tables' Q_{t|s}^T in place of q_mats[t], i.e. the arithmetic training's add_noise has from a one-hot x_s
+// It reads the class ids of the current state (the uint8 frame) and its positions and writes all four things a step writes for a row.
+// Thread i does position component i, atom row i and half-edge row i.  A row's K uniforms are read and its one-hot / log rows written by
+// unrolled loops over a compile-time K: the compiler merges them into 16- and 8-byte accesses (global accesses need 4-byte alignment
+// only), so a wave's accesses are contiguous without any vector types here.
+template <int K>
+__device__ __forceinline__ void forward_cat_row_k(const float* __restrict__ QT, int cv, const float* __restrict__ u, float log_off,
+                                                  float* __restrict__ onehot, float* __restrict__ log_row, uint8_t* __restrict__ cls8, int i) {
+  float ur[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) ur[k] = u[(size_t)i * K + k];
+  const int best = cat_add_noise_row<K, true>(QT, cv < K ? cv : K - 1, ur, log_off, nullptr);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    onehot[(size_t)i * K + k] = (k == best) ? 1.f : 0.f;
+    log_row[(size_t)i * K + k] = (k == best) ? 0.f : log_off;
+  }
+  if (cls8) cls8[i] = (uint8_t)best;
+}
+// KT > 0: compile-time class count, 0: dispatch on K
+template <int KT>
+__device__ __forceinline__ void forward_cat_row(int K, const float* __restrict__ QT, int cv, const float* __restrict__ u, float log_off,
+                                                float* __restrict__ onehot, float* __restrict__ log_row, uint8_t* __restrict__ cls8, int i) {
+  if constexpr (KT > 0) {
+    forward_cat_row_k<KT>(QT, cv, u, log_off, onehot, log_row, cls8, i);
+  } else {
+    switch (K) {
+      case 2: forward_cat_row_k<2>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 3: forward_cat_row_k<3>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 4: forward_cat_row_k<4>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 5: forward_cat_row_k<5>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 6: forward_cat_row_k<6>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 7: forward_cat_row_k<7>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      case 8: forward_cat_row_k<8>(QT, cv, u, log_off, onehot, log_row, cls8, i); break;
+      default: break;
+    }
+  }
+}
+template <int KN, int KE>
+__global__ void forward_jump_kernel(const ForwardJumpArgs a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 3 * a.N) {
+    const float pa = a.ca[a.row] * a.pos[i];
+    const float pb = a.cs[a.row] * a.eps[i];
+    a.pos_next[i] = pa + pb;
+  }
+  if (i < a.N)
+    forward_cat_row<KN>(a.Kn, a.node_qT + (size_t)a.row * a.Kn * a.Kn, a.node_cls[i], a.u_node, a.log_off, a.h_node, a.log_node,
+                             a.node_cls_next, i);
+  if (i < a.Eh)
+    forward_cat_row<KE>(a.Ke, a.edge_qT + (size_t)a.row * a.Ke * a.Ke, a.half_cls[i], a.u_half, a.log_off, a.h_half, a.log_half,
+                             a.half_cls_next, i);
+}
+void launch_forward_jump(const ForwardJumpArgs& a, hipStream_t s) {
+  const int n = std::max(3 * a.N, a.Eh);
+  if (n <= 0) return;
+  const dim3 g((n + 255) / 256), b(256);
+  if (a.Kn == 8 && a.Ke == 6) hipLaunchKernelGGL((forward_jump_kernel<8, 6>), g, b, 0, s, a);  // MolDiff's class counts
+  else hipLaunchKernelGGL((forward_jump_kernel<0, 0>), g, b, 0, s, a);
 }

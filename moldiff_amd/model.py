@@ -12,7 +12,9 @@ containers only.  Differences a caller can see, all opt-in keyword arguments wit
 ``sample(..., seed=, mol_ids=, noise=, return_traj=)`` (per-molecule Philox noise instead of torch's
 global generator, see DESIGN.md "noise"), ``sample(..., scaffold=, start_step=)`` (scaffold-constrained sampling and partial
 chains, an addition beyond the reference: ``moldiff_amd/scaffold.py``) and ``sample(..., num_steps=, timesteps=)`` (strided sampling:
-the reverse chain on a subset of the levels, an addition beyond the reference: ``moldiff_amd/schedule.py``).
+the reverse chain on a subset of the levels, an addition beyond the reference: ``moldiff_amd/schedule.py``) and
+``sample(..., resample=, jump_length=)`` (RePaint-style resampling: every block of levels is walked several times with a forward jump
+in between, an addition beyond the reference: ``schedule.resampling_path``, ``mdx_forward_jump``).
 """
 import ctypes
 import os
@@ -30,7 +32,7 @@ GUIDANCE_TYPES = ('entropy', 'uncertainty', 'uncertainty_bond', 'entropy_bond', 
 from .common import MLP, GaussianSmearing
 from .diffusion import get_beta_schedule
 from .graph import NodeEdgeNet, _sig, synth_gates
-from .schedule import pairs, resolve_schedule
+from .schedule import check_draw_range, draw_index, pairs, path_windows, resolve_path, resolve_schedule, window_width
 from .transition import ContigousTransition, GeneralCategoricalTransition
 
 class MolDiff(Module):
@@ -235,11 +237,13 @@ class MolDiff(Module):
 
     def sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, *, seed=None, mol_ids=None, noise=None,
                 return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False, scaffold=None, start_step=None,
-                num_steps=None, timesteps=None):
+                num_steps=None, timesteps=None, resample=None, jump_length=None):
         """Stateful driver of the reverse chain (``init()`` then ``step(i)`` for i = 0..T-1); ``sample`` wraps it.
         scaffold / start_step: see ``sample``; with start_step = s the loop iterations are i = T-s..T-1.
         num_steps / timesteps: see ``sample``; with a schedule of m levels the loop iterations are j = 0..m-1, ``step(j)`` is schedule
         iteration j and ``set_state(frame=j)`` addresses schedule positions, whether or not start_step is given.
+        resample / jump_length: see ``sample``; the sampler then has a ``path`` (the list of moves) and is driven by ``move(k)`` for
+        k = 0..len(path)-1 instead of ``step``; move k writes trajectory frame k + 1 and ``set_state(frame=k)`` addresses those frames.
         overlap_guidance=True runs the guidance chain on a side stream concurrently with the denoiser forward of the same step
         (same results).  It paid in round 1 (0.7 ms per step, the kernels left tails for each other); with the round-2 kernels
         filling every CU by themselves it costs 0.5 ms (27.6 vs 28.1 ms per step), so in line is the default."""
@@ -253,13 +257,17 @@ class MolDiff(Module):
             if num_steps is not None or timesteps is not None:
                 raise NotImplementedError('num_steps / timesteps in the continuous categorical space: not built (no shipped config '
                                           'uses that space)')
+            if resample is not None or jump_length is not None:
+                raise NotImplementedError('resample / jump_length in the continuous categorical space: not built (no shipped config '
+                                          'uses that space)')
             return _ContinuousSampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj)
         return _Sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                        bond_predictor, guidance, overlap_guidance, scaffold, start_step, num_steps, timesteps)
+                        bond_predictor, guidance, overlap_guidance, scaffold, start_step, num_steps, timesteps, resample, jump_length)
 
     @torch.no_grad()
     def sample(self, n_graphs, batch_node, halfedge_index, batch_halfedge, bond_predictor=None, guidance=None, *,
-               seed=None, mol_ids=None, noise=None, return_traj=True, scaffold=None, start_step=None, num_steps=None, timesteps=None):
+               seed=None, mol_ids=None, noise=None, return_traj=True, scaffold=None, start_step=None, num_steps=None, timesteps=None,
+               resample=None, jump_length=None):
         """Run the T-step reverse chain for a packed batch of fully-connected molecule graphs.
 
         Returns {'pred': [node logits (N,Kn), pos (N,3), halfedge logits (Eh,Ke)] of the last step,
@@ -282,11 +290,26 @@ class MolDiff(Module):
         frames.  The noise of the move leaving level t is draw T - t under every schedule (a scaffold's: T + (T - t)), so a schedule
         that visits every level is the full chain bit for bit.  The guidance displacement is added once per iteration and is NOT
         rescaled: fewer iterations, less total displacement.  Sample quality at reduced step counts has not been measured.
+        resample = R, jump_length = J (both or neither; R >= 1, 1 <= J <= m - 1 with m the number of levels the chain visits): RePaint's
+        resampling loop (Lugmayr et al. 2022) -- the levels are cut into blocks of J moves, every block is walked down R times, and between
+        two walks the WHOLE state is diffused forward again from the block's last level to its first (``mdx_forward_jump``: x_t ~
+        q(x_t | x_s), fixed rows included), so that the free rows are denoised against a scaffold they have already seen
+        (``schedule.resampling_path``).  Combines with scaffold, start_step, num_steps / timesteps and guidance (a down-move is the
+        unchanged step: denoiser, guidance, merge; an up-move touches neither the prediction nor the guidance).  Cost: R (m - 1) + 1
+        denoiser evaluations.  With return_traj=True the trajectory has ONE FRAME PER MOVE + 1, up-moves included: len(path) + 1 =
+        R (m - 1) + 1 + (R - 1) ceil((m - 1) / J) + 1 frames, not m + 1.  Noise: the k-th walk of a block (k = 0..R-1) uses the draw
+        indices of the plain chain plus k (3T + 2), the up-move arriving at level t that opens it 2T + 2 + t plus the same
+        (``schedule.draw_index``); the first walk, hence R = 1, is the plain chain bit for bit.  RePaint's published defaults are J = 10,
+        R = 10 on 250 levels -- theirs, for images; nothing has been tuned here and sample quality with resampling is unmeasured.
         """
         sm = self.sampler(n_graphs, batch_node, halfedge_index, batch_halfedge, seed=seed, mol_ids=mol_ids, noise=noise,
                           return_traj=return_traj, bond_predictor=bond_predictor, guidance=guidance, scaffold=scaffold,
-                          start_step=start_step, num_steps=num_steps, timesteps=timesteps)
+                          start_step=start_step, num_steps=num_steps, timesteps=timesteps, resample=resample, jump_length=jump_length)
         sm.init()
+        if getattr(sm, 'path', None) is not None:
+            for k in range(len(sm.path)):
+                sm.move(k)
+            return sm.result()
         if getattr(sm, 'sched', None) is not None:
             for j in range(len(sm.sched)):
                 sm.step(j)
@@ -306,7 +329,8 @@ class _Sampler:
     edge (``traj.LazyOneHot``): 0.16 GB instead of 2.1 GB at 256 molecules."""
 
     def __init__(self, model, n_graphs, batch_node, halfedge_index, batch_halfedge, seed, mol_ids, noise, return_traj,
-                 bond_predictor, guidance, overlap_guidance=False, scaffold=None, start_step=None, num_steps=None, timesteps=None):
+                 bond_predictor, guidance, overlap_guidance=False, scaffold=None, start_step=None, num_steps=None, timesteps=None,
+                 resample=None, jump_length=None):
         _lib._need_gpu(batch_node, halfedge_index, batch_halfedge)
         if start_step is not None:
             if scaffold is None:
@@ -314,7 +338,15 @@ class _Sampler:
             if not 0 < int(start_step) <= model.num_timesteps:
                 raise ValueError(f'start_step {start_step} outside (0, {model.num_timesteps}]')
         # strided sampling: the levels the chain visits (None: every level, on the full chain's own code path)
-        self.sched = resolve_schedule((model.num_timesteps if start_step is None else int(start_step)) - 1, num_steps, timesteps)
+        top = (model.num_timesteps if start_step is None else int(start_step)) - 1
+        self.sched = resolve_schedule(top, num_steps, timesteps)
+        # resampling: the moves over the positions of that schedule (None: the chain's own loop, driven by step(i))
+        self.levels = list(self.sched) if self.sched is not None else list(range(top, -1, -1))
+        if resample is not None and jump_length is not None:
+            check_draw_range(model.num_timesteps, resample)          # before the path is built: its length grows with resample
+        self.path = resolve_path(len(self.levels), jump_length, resample)
+        if self.path is not None:
+            self._windows = path_windows(self.path)
         self.guidance = None
         if guidance is not None:
             gui_type, gui_scale = guidance
@@ -351,6 +383,10 @@ class _Sampler:
         if self.sched is not None:                                   # iterations are schedule positions 0..m-1
             self.i0 = 0
             nT = len(self.sched) + 1 if return_traj else 2
+        self._it0 = self.i0                                          # loop iteration of position 0 (step(i) of a down-move on a path)
+        if self.path is not None:                                    # frames are counted in moves, up-moves included
+            self.i0 = 0
+            nT = len(self.path) + 1 if return_traj else 2
         self.h_node = torch.zeros(2, N, Kn, **f32)        # one-hot state, frames ping-pong
         self.h_half = torch.zeros(2, Eh, Ke, **f32)
         self.pos_traj = torch.zeros(nT, N, 3, **f32)
@@ -396,6 +432,14 @@ class _Sampler:
             self._jump_t = (*pt.jump_coefs(tt, ss), ntr.jump_mats(tt, ss), etr.jump_mats(tt, ss))
             self._levels = (ctypes.c_int32 * len(self.sched))(*self.sched)
             self.jump = _lib.MdxJumpTables(*(_lib.ptr(x) for x in self._jump_t), self._levels, len(self.sched))
+        self.fwd = None
+        if self.path is not None and any(mv[0] == 'up' for mv in self.path):
+            # one row per block (the distinct up-moves), like the jump tables: built once, kept alive next to the struct
+            ups = sorted({mv[1:] for mv in self.path if mv[0] == 'up'})
+            self._fwd_row = {ba: r for r, ba in enumerate(ups)}
+            tt, ss = [self.levels[a] for _, a in ups], [self.levels[b] for b, _ in ups]
+            self._fwd_t = (*pt.forward_coefs(tt, ss), ntr.jump_mats(tt, ss), etr.jump_mats(tt, ss))
+            self.fwd = _lib.MdxForwardTables(*(_lib.ptr(x) for x in self._fwd_t), Kn, Ke, len(ups))
         self.cur, self.lcur, self.pcur = 0, 0, 0  # one-hot frame / log-prob frame / position (and id) frame of the current state
         self.sc = None
         if scaffold is not None:
@@ -456,7 +500,43 @@ class _Sampler:
 
     @torch.no_grad()
     def step(self, i):
-        """Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call; with a scaffold a second one merges
+        """Loop iteration i (see ``_down``); the new state is trajectory frame i + 1.  A sampler with a path is driven by ``move``."""
+        if self.path is not None:
+            raise RuntimeError('this sampler walks a resampling path: drive it with move(k), k = 0..len(path)-1')
+        self._down(i, self._pframe(i + 1), 0)
+
+    @torch.no_grad()
+    def move(self, k):
+        """Move k of the resampling path, written to trajectory frame k + 1: a down-move ('down', p) is loop iteration p of the chain
+        (``_down``: denoiser, guidance, merge -- unchanged) with the draw indices of its walk's window; an up-move ('up', b, a) is one
+        call of ``mdx_forward_jump`` from level levels[b] to levels[a] (at most two launches: noise, jump).  The up-move reads the
+        current state's class ids and positions only; predictions, the time tensor and the guidance workspace are left alone."""
+        if self.path is None:
+            raise RuntimeError('this sampler has no resampling path (resample= / jump_length=): drive it with step(i)')
+        if not 0 <= k < len(self.path):
+            raise IndexError(f'move {k} outside [0, {len(self.path)})')
+        mv, off = self.path[k], self._windows[k] * window_width(self.T)
+        pn = self._pframe(k + 1)
+        if mv[0] == 'down':
+            self._down(self._it0 + mv[1], pn, off)
+            return
+        draw = draw_index(self.T, 'up', self.levels[mv[2]], self._windows[k])
+        if self.noise is not None:
+            e, a, b = self.noise(draw)
+            self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
+            draw = -1
+        n, ln, pc = 1 - self.cur, 1 - self.lcur, self.pcur
+        P = _lib.ptr
+        nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
+        nz = _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
+        _lib.check(_lib.lib().mdx_forward_jump(self.g.h, ctypes.byref(self.fwd), self._fwd_row[mv[1:]], P(self.node_ids[pc]),
+                                               P(self.half_ids[pc]), P(self.pos_traj[pc]), ctypes.byref(nz), ctypes.byref(nxt),
+                                               _lib.log_eps32(), P(self.node_ids[pn]), P(self.half_ids[pn]), _lib.stream()))
+        self.cur, self.lcur, self.pcur = n, ln, pn
+
+    def _down(self, i, pn, off):
+        """Loop iteration i written to position / id frame pn, with `off` added to its draw indices (a resampling window; 0 otherwise).
+        Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call; with a scaffold a second one merges
         its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold").  With a schedule: schedule iteration i,
         one call of ``mdx_sample_jump_full`` instead (same launches, the transition reads the jump tables' row i)."""
         L, T = _lib.lib(), self.T
@@ -468,14 +548,14 @@ class _Sampler:
             if not 0 <= i < len(self.sched):
                 raise IndexError(f'schedule iteration {i} outside [0, {len(self.sched)})')
             t, below = self.sched[i], (self.sched[i + 1] if i + 1 < len(self.sched) else -1)
-        draw = T - t
+        draw = T - t + off
         if self.noise is not None:
             e, a, b = self.noise(draw)
             self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
             draw = -1
         c, n = self.cur, 1 - self.cur
         lc, ln = self.lcur, 1 - self.lcur
-        pc, pn = self.pcur, self._pframe(i + 1)
+        pc = self.pcur
         P = _lib.ptr
         cur = _lib.MdxState(P(self.h_node[c]), P(self.pos_traj[pc]), P(self.h_half[c]), P(self.log_node[lc]), P(self.log_half[lc]))
         nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
@@ -494,7 +574,7 @@ class _Sampler:
         if self.guidance is not None and self.gd is None:  # the seven objectives that are torch expressions on the logits
             self._guide(self.h_node[c], self.pos_traj[pc], self.pos_traj[pn], self.h_half[n], self.log_half[ln])
         if self.sc is not None:
-            self._merge(self.sc, below, T + (T - t), n, ln, pn)
+            self._merge(self.sc, below, T + (T - t) + off, n, ln, pn)
         self.cur, self.lcur, self.pcur = n, ln, pn
 
     def _guide(self, h_node, pos, pos_prev, h_half_prev, log_half):

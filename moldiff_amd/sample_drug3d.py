@@ -174,6 +174,9 @@ def main(argv=None):
                                                              '(overrides sample.scaffold)')
     ap.add_argument('--num_steps', type=int, default=0, help='strided sampling: run the reverse chain on this many uniformly spaced '
                                                              'levels instead of all of them (overrides sample.num_steps)')
+    ap.add_argument('--resample', type=int, default=0, help='resampling: walk every block of --jump_length levels this many times, with a '
+                                                            'forward jump in between (overrides sample.resample; needs --jump_length)')
+    ap.add_argument('--jump_length', type=int, default=0, help='resampling: moves per block (overrides sample.jump_length)')
     args = ap.parse_args(argv)
 
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -217,6 +220,12 @@ def main(argv=None):
     save_traj_prob = float(getattr(config.sample, 'save_traj_prob', 0.0) or 0.0)
     scaffold_path = args.scaffold or config.sample.get('scaffold') or ''
     num_steps = args.num_steps or config.sample.get('num_steps') or None   # trajectory files then hold num_steps + 1 frames
+    # resampling: trajectory files then hold one frame per move + 1 (schedule.resampling_path), up-moves included
+    resample = args.resample or config.sample.get('resample') or None
+    jump_length = args.jump_length or config.sample.get('jump_length') or None
+    extra = {} if num_steps is None else {'num_steps': int(num_steps)}
+    if resample is not None or jump_length is not None:
+        extra.update(resample=None if resample is None else int(resample), jump_length=None if jump_length is None else int(jump_length))
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -244,7 +253,7 @@ def main(argv=None):
         scaffold = scaffold_for_sizes(scaffold_info, sizes[mine], featurizer, device) if scaffold_info is not None else None
         out = model.sample(hi - lo, ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], bond_predictor, guidance,
                            seed=seed + i_batch, mol_ids=ids, return_traj=save_traj_prob > 0, scaffold=scaffold,
-                           **({} if num_steps is None else {'num_steps': int(num_steps)}))
+                           **extra)
         # trajectories stay rank-local (scripts/sample_drug3d.py:155 looks at ~2 % of them): the owner decodes and writes
         # them, named by global molecule id; whether a molecule is drawn depends only on (seed, id), not on the sharding
         if save_traj_prob > 0:

@@ -4,6 +4,10 @@ A schedule is a strictly decreasing list of levels tau_0 > tau_1 > ... > tau_{m-
 for a partial chain).  Loop iteration j of the sampler takes the state at level tau_j, evaluates the denoiser (and the guidance)
 with t = tau_j and writes the state at level tau_{j+1}; the last iteration (level 0) is the chain's ordinary t == 0 step.  The
 reference has no such thing (its loop visits every level): an addition, like scaffolds.  Host code, integers only.
+
+Resampling (RePaint's loop around replacement conditioning, another addition) makes the walk non-monotone: ``resampling_path`` lists the
+moves -- down-moves between neighbouring schedule POSITIONS and up-moves back to the start of a block -- and ``draw_index`` /
+``path_draws`` say which noise draw each of them uses.
 """
 import numbers
 
@@ -58,3 +62,105 @@ def resolve_schedule(top, num_steps=None, timesteps=None):
 def pairs(schedule):
     """(t, s) of every iteration: (tau_j, tau_{j+1}), and (0, -1) for the last one (nothing below level 0)."""
     return list(zip(schedule, list(schedule[1:]) + [-1]))
+
+
+# ---- resampling: a path over schedule positions that walks every block of levels several times ---------------------------------------
+
+def _int(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise ValueError(f'{name} must be an int, got {v!r}')
+    return int(v)
+
+
+def resampling_path(m, jump_length, resample):
+    """The moves of a resampling chain over `m` schedule positions p = 0..m-1 (position p is level tau_p of a schedule, or level
+    top - p of the full chain; position m-1 is level 0).
+
+    Block boundaries are the multiples of `jump_length` and, last, position m-1 (the final block is shorter when m-1 is no multiple).
+    Every block [a, b] is walked a -> b `resample` times: one walk is the down-moves ('down', p), p = a..b-1 (the state at position p
+    goes to position p + 1); between two walks comes one up-move ('up', b, a), the forward diffusion from position b back to position
+    a.  After the last block comes the chain's ordinary final move ('down', m-1): level 0 to x_0, once.
+    Denoiser evaluations: resample (m-1) + 1; up-moves: (resample-1) ceil((m-1) / jump_length); resample = 1 gives the m down-moves of
+    the plain chain."""
+    m, J, R = _int('m', m), _int('jump_length', jump_length), _int('resample', resample)
+    if m < 2:
+        raise ValueError(f'a path needs at least 2 schedule positions, got {m}')
+    if R < 1:
+        raise ValueError(f'resample must be >= 1, got {R}')
+    if not 1 <= J <= m - 1:
+        raise ValueError(f'jump_length {J} outside [1, {m - 1}] for a chain of {m} positions')
+    path = []
+    for a in range(0, m - 1, J):
+        b = min(a + J, m - 1)
+        for k in range(R):
+            if k:
+                path.append(('up', b, a))
+            path.extend(('down', p) for p in range(a, b))
+    path.append(('down', m - 1))
+    return path
+
+
+def resolve_path(m, jump_length=None, resample=None):
+    """The path the keywords of ``MolDiff.sample`` ask for, or None when neither is given (the chain's own loop).  The two come
+    together: one without the other raises (resample = 1 with a jump_length is allowed and is the plain chain)."""
+    if jump_length is None and resample is None:
+        return None
+    if jump_length is None or resample is None:
+        raise ValueError('resample and jump_length come together: give both or neither')
+    return resampling_path(m, jump_length, resample)
+
+
+def path_windows(path):
+    """The noise window of every move of a path: the k-th walk of a block (k = 0, 1, ..) uses window k, and so does the up-move that
+    opens it.  Read off the path itself: a down-move at position p is in the walk numbered by the earlier down-moves at p, an up-move
+    (b, a) opens the walk numbered 1 + the earlier up-moves (b, a).  The final move is made once: window 0."""
+    seen, out = {}, []
+    for mv in path:
+        k = seen.get(mv, 0)
+        seen[mv] = k + 1
+        out.append(k + 1 if mv[0] == 'up' else k)
+    return out
+
+
+def window_width(T):
+    """W = 3T + 2 draw indices per window: 0 the prior, T - t the move leaving level t, T + (T - t) its scaffold merge, 2T + 1 the initial
+    merge, 2T + 2 + t an up-move arriving at level t (t < T, so the last index used is 3T + 1)."""
+    return 3 * int(T) + 2
+
+
+def draw_index(T, kind, level=None, window=0):
+    """Philox draw index of one piece of a chain's noise.  kind: 'prior' | 'init_merge' (no level) | 'down' (the move LEAVING `level`) |
+    'merge' (the scaffold merge after the move leaving `level`) | 'up' (an up-move ARRIVING at `level`).  Window 0 is what the plain,
+    strided and scaffold chains use; the k-th walk of a resampling block adds k W."""
+    T, window = int(T), int(window)
+    if kind in ('prior', 'init_merge'):
+        base = 0 if kind == 'prior' else 2 * T + 1
+    else:
+        t = int(level)
+        if not 0 <= t < T:
+            raise ValueError(f'level {level} outside [0, {T})')
+        base = {'down': T - t, 'merge': T + (T - t), 'up': 2 * T + 2 + t}[kind]
+    if window < 0:
+        raise ValueError(f'window {window} < 0')
+    return base + window * window_width(T)
+
+
+def check_draw_range(T, resample):
+    """`draw` is an int32 that the Philox key takes as uint32: every index of `resample` windows must stay below 2^31."""
+    if int(resample) * window_width(T) >= 2 ** 31:
+        raise ValueError(f'resample {resample} x {window_width(T)} draw indices per window does not fit the 31-bit draw index')
+
+
+def path_draws(path, levels, T, scaffold=False, partial=False):
+    """The draw indices a chain over `path` asks for, in order.  levels[p]: the level of position p.  scaffold: a merge follows every
+    down-move but the last and the prior draw; partial (start_step): the chain starts from the initial merge alone."""
+    out = [draw_index(T, 'init_merge')] if partial else [draw_index(T, 'prior')] + ([draw_index(T, 'init_merge')] if scaffold else [])
+    for mv, w in zip(path, path_windows(path)):
+        if mv[0] == 'up':
+            out.append(draw_index(T, 'up', levels[mv[2]], w))
+        else:
+            t = levels[mv[1]]
+            out.append(draw_index(T, 'down', t, w))
+            if scaffold and mv[1] + 1 < len(levels):
+                out.append(draw_index(T, 'merge', t, w))
+    return out

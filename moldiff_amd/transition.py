@@ -92,6 +92,18 @@ class ContigousTransition(nn.Module):
                 c[j, near] = tab.detach()[tn]
         return c[0].contiguous(), c[1].contiguous(), c[2].contiguous()
 
+    def forward_coefs(self, t, s):
+        """Coefficients of q(x_t | x_s) for the level pairs 0 <= s[i] < t[i] < T (the up-moves of resampling; an addition beyond the
+        reference, the counterpart of `jump_coefs`): fp32 tensors (c_a, c_s) = (sqrt(a), sqrt(1 - a)), a = abar_t / abar_s, one entry per
+        pair, on the device of the module's tables; float64 from `_abar64`, rounded once.  x_t = c_a x_s + c_s eps."""
+        t, s = _check_pairs(t, s, len(self._abar64))
+        if (s < 0).any():
+            raise ValueError('a forward move starts at a level >= 0')
+        a = self._abar64[t] / self._abar64[s]
+        out = np.stack([np.sqrt(a), np.sqrt(1.0 - a)]).astype(np.float32)
+        c = torch.from_numpy(out).to(self.coef_x0.device)
+        return c[0].contiguous(), c[1].contiguous()
+
     def get_prev_from_recon(self, x_t, x_recon, t, batch, eps=None, *, t_prev=None):
         """mu = coef_x0[t] x0_hat + coef_xt[t] x_t ; x_{t-1} = mu + std[t] eps, and exactly mu where t == 0.
         `eps` may be injected (parity tests); otherwise it is drawn with torch's generator like the reference.

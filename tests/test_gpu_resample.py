@@ -1,0 +1,402 @@
+"""GPU tests of RePaint-style resampling (MolDiff.sample(..., resample=, jump_length=), mdx_forward_jump).
+
+There is no reference to compare with (the reference's chain only walks down).  What is pinned: the up-move follows the formulas of
+q(x_t | x_s) -- a float64 restatement on every row, and the product's own training-side add_noise bit for bit where the two coincide;
+it is row-local (sharding cannot matter); resample = 1 and absent keywords are the existing chains bit for bit; the path, its draw
+indices and its frames are what the host functions say; the invariants of replacement conditioning survive the up-moves; guidance and
+the command-line entry point run with it.  What resampling does to sample QUALITY is not tested: no trained checkpoint is available.
+"""
+import glob
+import time
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from moldiff_amd import Scaffold, _lib
+from moldiff_amd.schedule import path_draws, resampling_path
+from tests import test_resample_host as H
+from tests import util as U
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+T = 1000
+SIZES8 = [9, 14, 11, 7, 16, 12, 10, 13]
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _wall_time():
+    t0 = time.time()
+    yield
+    torch.cuda.synchronize()
+    print(f'\n[test_gpu_resample] wall time of this file: {time.time() - t0:.1f} s')
+
+
+def _model():
+    return U.moldiff('MolDiff_simple', DEV)
+
+
+def _random_scaffold(sizes, seed, frac=0.5, all_rows=None):
+    g = U.rng(seed)
+    bn, hei, bh, _, _ = U.graph_from_sizes(sizes, DEV)
+    N, Eh = int(bn.numel()), int(bh.numel())
+    mask = g.random(N) < frac if all_rows is None else np.full(N, all_rows)
+    sc = Scaffold(torch.from_numpy(mask).to(DEV), torch.from_numpy(g.integers(0, 7, N)).to(DEV),
+                  U.t32(1.5 * g.standard_normal((N, 3))).to(DEV), torch.from_numpy(g.integers(0, 5, Eh)).to(DEV))
+    return (bn, hei, bh), sc
+
+
+def _snapshot(sm, frames):
+    st = {k: v.clone() for k, v in sm.state().items()}
+    st.update(node_ids=sm.node_ids[:frames].clone(), half_ids=sm.half_ids[:frames].clone(), pos_traj=sm.pos_traj[:frames].clone(),
+              t=sm.t.clone(), **{f'pred{j}': p.clone() for j, p in enumerate(sm.preds)})
+    return st
+
+
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k, v in a.items():
+        assert torch.equal(v, b[k]), k
+
+
+def _recorded_noise(N, Eh, asked):
+    def noise(draw):   # fresh values per draw index, the same whoever asks
+        asked.append(draw)
+        gd = U.rng(1000 + draw)
+        return (U.t32(gd.standard_normal((N, 3))).to(DEV), U.t32(gd.random((N, 8), dtype=np.float32)).to(DEV),
+                U.t32(gd.random((Eh, 6), dtype=np.float32)).to(DEV))
+    return noise
+
+
+# ---- 1. the kernel against the formula ------------------------------------------------------------------------------------------------
+
+def test_forward_jump_follows_the_formula_of_q_xt_given_xs():
+    """Explicit noise, the inputs and level pairs of tests/test_resample_host.py.
+    Classes: bit-equal to the float64 restatement on EVERY row (the host test established that no row of these inputs lies within the
+    1e-4 margin of a tie: nothing is skipped), and bit-equal to the training-side add_noise on the device (the shared row function)
+    where the two coincide: with the cumulative matrix q_mats[t] swapped in for the jump matrix, a forward jump from x_s = v is
+    add_noise(v, t) with the same uniforms.
+    Positions against float64 from the stored fp32 coefficients: a = c_a x, b = c_s eps and a + b are each rounded once (two products
+    and one sum; the file is built without contraction, so there is no FMA that would make it two), so
+    |err| <= 2^-24 (|a| + |b| + |a + b|) (1 + 2^-24) <= 3 * 2^-24 (|c_a x| + |c_s eps|).
+    The one-hot, log one-hot and uint8 outputs agree with the ids."""
+    m = _model()
+    inp = H.forward_inputs()
+    bn, hei, bh = (inp[k].to(DEV) for k in ('bn', 'hei', 'bh'))
+    B = len(H.FORWARD_SIZES)
+    g = _lib.Graph(torch.cat([hei, hei.flip(0)], dim=1), bn, B)
+    ss, tt = [p[0] for p in H.FORWARD_PAIRS], [p[1] for p in H.FORWARD_PAIRS]
+    pt, ntr, etr = m.pos_transition, m.node_transition, m.edge_transition
+    ca, cs = pt.forward_coefs(tt, ss)
+    tables = (ca, cs, ntr.jump_mats(tt, ss), etr.jump_mats(tt, ss))
+    # the same entry point with the cumulative matrices (transposed, like the jump tables) in place of the jump matrices
+    cum = (ca, cs, ntr.q_mats.detach()[tt].transpose(-1, -2).contiguous(), etr.q_mats.detach()[tt].transpose(-1, -2).contiguous())
+    log_off = float(torch.log(torch.tensor([1e-30], dtype=torch.float32))[0])
+    for row, (s, t) in enumerate(H.FORWARD_PAIRS):
+        d = inp['pairs'][(s, t)]
+        dd = {k: v.to(DEV) for k, v in d.items()}
+        noise = (dd['eps'], dd['u_n'], dd['u_h'])
+        out = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in
+               _lib.forward_jump(g, tables, row, dd['ids_n'], dd['ids_h'], dd['pos'], noise=noise).items()}
+        ref = _lib.forward_jump(g, cum, row, dd['ids_n'], dd['ids_h'], dd['pos'], noise=noise)
+        tv = torch.full((B,), t, dtype=torch.int64, device=DEV)
+        for tr, qT, ids0, u, batch, oh, lg, ids8, K, rk in (
+                (ntr, tables[2][row], d['ids_n'], d['u_n'], bn, out['h_node'], out['log_node'], out['node_ids'], 8, 'h_node'),
+                (etr, tables[3][row], d['ids_h'], d['u_h'], bh, out['h_halfedge'], out['log_halfedge'], out['half_ids'], 6, 'h_halfedge')):
+            cls = oh.argmax(-1)
+            c64, margin = H.classes_fp64(qT.cpu(), ids0, u)
+            assert bool((margin >= H.MARGIN).all())                # skipped share: 0
+            assert torch.equal(cls, c64)
+            assert torch.equal(oh, F.one_hot(cls, K).float())
+            assert torch.equal(lg, torch.where(oh > 0, torch.zeros(()), torch.full((), log_off)))
+            assert ids8.dtype == torch.uint8 and torch.equal(ids8.long(), cls)
+            an_oh, an_lvt, _ = tr.add_noise(ids0.to(DEV), tv, batch, u.to(DEV))
+            assert torch.equal(ref[rk], an_oh) and torch.equal(ref['log_' + rk[2:]], an_lvt)
+        want, scale = H.positions_fp64(ca[row].cpu(), cs[row].cpu(), d['pos'], d['eps'])
+        err, bound = (out['pos'].double() - want).abs(), 3 * 2.0 ** -24 * scale
+        print(f'({s} -> {t}): max position error / bound = {float((err / bound).max()):.3f}')
+        assert bool((err <= bound).all())
+        assert torch.equal(ref['pos'].cpu(), out['pos'])
+
+
+def test_forward_jump_with_other_class_counts_and_bad_arguments():
+    """7 atom / 5 bond classes take the scalar-access instantiation: same formula, every row."""
+    g0 = U.rng(77)
+    sizes = [4, 6, 3]
+    bn, hei, bh, _, _ = U.graph_from_sizes(sizes, DEV)
+    N, Eh = int(bn.numel()), int(bh.numel())
+    g = _lib.Graph(torch.cat([hei, hei.flip(0)], dim=1), bn, len(sizes))
+    from moldiff_amd.diffusion import get_beta_schedule
+    from moldiff_amd.transition import GeneralCategoricalTransition
+    from moldiff_amd.harness import default_config
+    diff = default_config('MolDiff_simple').diff
+    trs = [GeneralCategoricalTransition(get_beta_schedule(num_timesteps=T, **c), K, init_prob=c.init_prob).to(DEV)
+           for c, K in ((diff.diff_atom, 7), (diff.diff_bond, 5))]
+    ca, cs = _model().pos_transition.forward_coefs([640], [120])
+    tables = (ca, cs, trs[0].jump_mats([640], [120]), trs[1].jump_mats([640], [120]))
+    ids_n, ids_h = torch.from_numpy(g0.integers(0, 7, N)), torch.from_numpy(g0.integers(0, 5, Eh))
+    pos, eps = U.t32(g0.standard_normal((N, 3))), U.t32(g0.standard_normal((N, 3)))
+    u_n, u_h = U.t32(g0.random((N, 7), dtype=np.float32)), U.t32(g0.random((Eh, 5), dtype=np.float32))
+    out = _lib.forward_jump(g, tables, 0, ids_n.to(DEV), ids_h.to(DEV), pos.to(DEV), noise=(eps.to(DEV), u_n.to(DEV), u_h.to(DEV)))
+    for qT, ids0, u, oh, ids8 in ((tables[2][0], ids_n, u_n, out['h_node'], out['node_ids']), (tables[3][0], ids_h, u_h, out['h_halfedge'], out['half_ids'])):
+        c64, margin = H.classes_fp64(qT.cpu(), ids0, u)
+        assert bool((margin >= H.MARGIN).all()) and torch.equal(oh.argmax(-1).cpu(), c64)
+        assert torch.equal(ids8.long(), oh.argmax(-1))
+    want, scale = H.positions_fp64(ca[0].cpu(), cs[0].cpu(), pos, eps)
+    assert bool(((out['pos'].cpu().double() - want).abs() <= 3 * 2.0 ** -24 * scale).all())
+    with pytest.raises(RuntimeError, match='table row'):
+        _lib.forward_jump(g, tables, 1, ids_n.to(DEV), ids_h.to(DEV), pos.to(DEV), draw=3)
+
+
+# ---- 2. row-locality ------------------------------------------------------------------------------------------------------------------
+
+def test_forward_jump_is_row_local_under_library_noise():
+    """draw >= 0: a 4-molecule batch with global molecule ids equals, bit for bit, the same molecules run as two 2-molecule batches."""
+    m = _model()
+    sizes, ids = [9, 14, 11, 7], np.arange(700, 704)
+    g0 = U.rng(21)
+    N, Eh = sum(sizes), sum(s * (s - 1) // 2 for s in sizes)
+    ids_n, ids_h = torch.from_numpy(g0.integers(0, 8, N)).to(DEV), torch.from_numpy(g0.integers(0, 6, Eh)).to(DEV)
+    pos = U.t32(g0.standard_normal((N, 3))).to(DEV)
+    tt, ss = [640], [120]
+    tables = (*m.pos_transition.forward_coefs(tt, ss), m.node_transition.jump_mats(tt, ss), m.edge_transition.jump_mats(tt, ss))
+
+    def run(sz, mol_ids, ns, es):
+        bn, hei, bh, _, _ = U.graph_from_sizes(sz, DEV)
+        g = _lib.Graph(torch.cat([hei, hei.flip(0)], dim=1), bn, len(sz), mol_ids)
+        return _lib.forward_jump(g, tables, 0, ids_n[ns], ids_h[es], pos[ns], seed=99, draw=2 * T + 2 + 640)
+
+    n_lo, e_lo = sum(sizes[:2]), sum(s * (s - 1) // 2 for s in sizes[:2])
+    full = run(sizes, ids, slice(None), slice(None))
+    lo = run(sizes[:2], ids[:2], slice(0, n_lo), slice(0, e_lo))
+    hi = run(sizes[2:], ids[2:], slice(n_lo, None), slice(e_lo, None))
+    for k, cut in (('h_node', n_lo), ('log_node', n_lo), ('pos', n_lo), ('node_ids', n_lo), ('h_halfedge', e_lo), ('log_halfedge', e_lo),
+                   ('half_ids', e_lo)):
+        assert torch.equal(full[k][:cut], lo[k]) and torch.equal(full[k][cut:], hi[k]), k
+    assert not torch.equal(full['pos'], pos) and not torch.equal(full['node_ids'].long(), ids_n)    # and the rows did move
+
+
+# ---- 3. resample = 1 and absent keywords are today's chains ------------------------------------------------------------------------------
+
+@U.both_paths
+@pytest.mark.parametrize('variant', ['plain', 'scaffold'])
+def test_resample_one_and_absent_keywords_are_the_existing_chain_bit_for_bit(variant):
+    m = _model()
+    (bn, hei, bh), sc = _random_scaffold(SIZES8, 1)
+    extra = {} if variant == 'plain' else dict(scaffold=sc)
+    runs = []
+    for kw in ({}, dict(resample=None, jump_length=None), dict(resample=1, jump_length=2)):
+        sm = m.sampler(len(SIZES8), bn, hei, bh, seed=17, num_steps=6, **extra, **kw)
+        assert (sm.path is None) == (kw.get('resample') is None)
+        sm.init()
+        for j in range(6):
+            sm.step(j) if sm.path is None else sm.move(j)
+        runs.append(_snapshot(sm, 7))
+        out = m.sample(len(SIZES8), bn, hei, bh, seed=17, num_steps=6, **extra, **kw)
+        assert out['traj'][1].shape[0] == 7 and torch.equal(out['traj'][1], runs[-1]['pos_traj'])
+        assert all(torch.equal(a, runs[-1][f'pred{j}']) for j, a in enumerate(out['pred']))
+    _same(runs[0], runs[1])
+    _same(runs[0], runs[2])
+    assert torch.isfinite(runs[0]['pos']).all()
+
+
+def test_resample_one_on_the_full_chain_and_a_partial_chain():
+    """without a schedule the positions are the levels top .. 0: the first moves of resample = 1 are loop iterations 0.. of the full
+    chain, and of a partial chain started at level 11"""
+    m = _model()
+    (bn, hei, bh), sc = _random_scaffold(SIZES8, 3, all_rows=True)
+    for extra, first in ((dict(), 0), (dict(scaffold=sc, start_step=12), T - 12)):
+        a = m.sampler(len(SIZES8), bn, hei, bh, seed=5, **extra)
+        b = m.sampler(len(SIZES8), bn, hei, bh, seed=5, resample=1, jump_length=4, **extra)
+        assert len(b.path) == (T if not extra else 12)
+        a.init(); b.init()
+        for j in range(8):
+            a.step(first + j); b.move(j)
+        _same(_snapshot(a, 9), _snapshot(b, 9))
+
+
+# ---- 4. the path is what runs -------------------------------------------------------------------------------------------------------------
+
+def test_the_path_its_draw_indices_and_its_frames_are_what_runs():
+    m = _model()
+    sizes = [9, 14, 11, 7]
+    (bn, hei, bh), sc = _random_scaffold(sizes, 2)
+    N, Eh = int(bn.numel()), int(bh.numel())
+    asked = []
+    noise = _recorded_noise(N, Eh, asked)
+    kw = dict(noise=noise, scaffold=sc, num_steps=7, jump_length=3, resample=2)
+    out = m.sample(len(sizes), bn, hei, bh, **kw)
+    path = resampling_path(7, 3, 2)
+    sm = m.sampler(len(sizes), bn, hei, bh, **kw)
+    assert sm.path == path and len(path) == 15
+    assert asked == path_draws(path, sm.levels, T, scaffold=True) and len(set(asked)) == len(asked)
+    assert [x.shape[0] for x in out['traj']] == [len(path) + 1] * 3
+    # by hand: init() + move(k); the time tensor the denoiser saw is the level of the position left, also right after an up-move
+    asked.clear()
+    sm.init()
+    after_up = 0
+    for k, mv in enumerate(path):
+        before = {kk: v.clone() for kk, v in sm.state().items()}
+        t_before, preds_before = sm.t.clone(), [p.clone() for p in sm.preds]
+        sm.move(k)
+        if mv[0] == 'down':
+            assert bool((sm.t[:len(sizes)] == sm.levels[mv[1]]).all())
+            if k and path[k - 1][0] == 'up':
+                assert mv[1] == path[k - 1][2]                     # the level the up-move arrived at
+                after_up += 1
+        else:
+            assert torch.equal(sm.t, t_before) and all(torch.equal(a, b) for a, b in zip(sm.preds, preds_before))
+            assert not torch.equal(sm.state()['pos'], before['pos'])
+    assert after_up == 2 and asked == path_draws(path, sm.levels, T, scaffold=True)
+    res = sm.result()
+    assert torch.equal(res['traj'][1], out['traj'][1])
+    assert torch.equal(res['traj'][0].dense(), out['traj'][0].dense()) and torch.equal(res['traj'][2].dense(), out['traj'][2].dense())
+    assert all(torch.equal(a, b) for a, b in zip(res['pred'], out['pred']))
+    # every frame of the compact trajectory is the state after its move: ids and one-hot rows agree at the end
+    assert torch.equal(sm.state()['h_node'], F.one_hot(sm.node_ids[len(path)].long(), 8).float())
+    with pytest.raises(IndexError):
+        sm.move(len(path))
+    with pytest.raises(RuntimeError, match='move'):
+        sm.step(0)
+    # return_traj=False: two ping-pong frames, same result
+    short = m.sample(len(sizes), bn, hei, bh, return_traj=False, **kw)
+    assert short['traj'][1].shape[0] == 1 and all(torch.equal(a, b) for a, b in zip(short['pred'], out['pred']))
+    assert torch.equal(short['traj'][1][0], out['traj'][1][-1])
+    for bad in (dict(resample=2), dict(jump_length=3), dict(resample=0, jump_length=3), dict(resample=2, jump_length=7),
+                dict(resample=2 ** 20, jump_length=3)):
+        with pytest.raises(ValueError):
+            m.sampler(len(sizes), bn, hei, bh, num_steps=7, **bad)
+    with pytest.raises(RuntimeError, match='step'):
+        m.sampler(len(sizes), bn, hei, bh, num_steps=7).move(0)
+
+
+# ---- 5. replacement invariants survive ----------------------------------------------------------------------------------------------------
+
+def test_fixed_rows_end_on_the_scaffold_and_the_up_moves_did_happen():
+    m = _model()
+    sizes = [9, 14, 11, 7, 16, 12]
+    (bn, hei, bh), sc = _random_scaffold(sizes, 4)
+    N, Eh = int(bn.numel()), int(bh.numel())
+    nm, nt, x0, ht, hm = sc.resolve(N, hei, 8, 6)
+    out = m.sample(len(sizes), bn, hei, bh, seed=11, scaffold=sc, num_steps=6, resample=2, jump_length=2)
+    assert bool(nm.any()) and not bool(nm.all())
+    assert torch.equal(out['traj'][1][-1][nm], x0[nm]) and torch.equal(out['pred'][1][nm], x0[nm])
+    assert torch.equal(out['traj'][0][-1].dense()[nm], F.one_hot(nt[nm], 8).float())
+    assert torch.equal(out['traj'][2][-1].dense()[hm], F.one_hot(ht[hm], 6).float())
+    for pred, v0, msk in ((out['pred'][0], nt, nm), (out['pred'][2], ht, hm)):
+        p = torch.softmax(pred[msk], dim=-1)
+        assert torch.equal(p.argmax(-1), v0[msk]) and bool((p.max(-1).values == 1.0).all())
+    assert all(bool(torch.isfinite(p).all()) for p in out['pred']) and not torch.equal(out['pred'][1][~nm], x0[~nm])
+    # an all-false mask: nothing is held, but the up-moves still happen -- the result differs from the plain chain, reproducibly
+    free = Scaffold(torch.zeros_like(sc.node_mask), sc.node_type, sc.node_pos, sc.halfedge_type)
+    plain = m.sample(len(sizes), bn, hei, bh, seed=11, scaffold=free, num_steps=6)
+    r1 = m.sample(len(sizes), bn, hei, bh, seed=11, scaffold=free, num_steps=6, resample=2, jump_length=2)
+    r2 = m.sample(len(sizes), bn, hei, bh, seed=11, scaffold=free, num_steps=6, resample=2, jump_length=2)
+    none = m.sample(len(sizes), bn, hei, bh, seed=11, num_steps=6, resample=2, jump_length=2)      # valid without a scaffold too
+    assert not torch.equal(plain['pred'][1], r1['pred'][1])
+    assert torch.equal(plain['traj'][1][:3], r1['traj'][1][:3])      # the first walk of the first block IS the plain chain
+    for a, b in ((r1, r2), (r1, none)):
+        assert all(torch.equal(x, y) for x, y in zip(a['pred'], b['pred'])) and torch.equal(a['traj'][1], b['traj'][1])
+        assert torch.equal(a['traj'][0].dense(), b['traj'][0].dense()) and torch.equal(a['traj'][2].dense(), b['traj'][2].dense())
+
+
+def test_resampled_chain_is_shard_invariant():
+    m = _model()
+    sizes, ids = [9, 14, 11, 7], np.arange(400, 404)
+    _, sc = _random_scaffold(sizes, 8)
+    n_lo, e_lo = sum(sizes[:2]), sum(s * (s - 1) // 2 for s in sizes[:2])
+
+    def run(sz, mol_ids, ns, es):
+        bn, hei, bh, _, _ = U.graph_from_sizes(sz, DEV)
+        part = Scaffold(sc.node_mask[ns], sc.node_type[ns], sc.node_pos[ns], sc.halfedge_type[es])
+        return m.sample(len(sz), bn, hei, bh, seed=99, mol_ids=mol_ids, scaffold=part, num_steps=5, resample=2, jump_length=2,
+                        return_traj=False)['pred']
+
+    full = run(sizes, ids, slice(None), slice(None))
+    lo, hi = run(sizes[:2], ids[:2], slice(0, n_lo), slice(0, e_lo)), run(sizes[2:], ids[2:], slice(n_lo, None), slice(e_lo, None))
+    for k, cut in ((0, n_lo), (1, n_lo), (2, e_lo)):
+        assert torch.equal(full[k][:cut], lo[k]) and torch.equal(full[k][cut:], hi[k])
+
+
+# ---- 6. with guidance ---------------------------------------------------------------------------------------------------------------------
+
+def test_guided_resampling_runs_and_the_up_move_leaves_the_guidance_alone():
+    """default 'uncertainty' objective, MolDiff with the recipe bond predictor, a 4-level schedule with one up-move:
+    d0 d1 d2 up(3 -> 0) d0 d1 d2 d3"""
+    m, bp = U.moldiff('MolDiff', DEV), U.bondpred(DEV)
+    sizes = [9, 14, 11, 7]
+    (bn, hei, bh), sc = _random_scaffold(sizes, 6)
+    kw = dict(seed=13, bond_predictor=bp, guidance=['uncertainty', 1e-4], scaffold=sc, num_steps=4, jump_length=3, resample=2)
+    out = m.sample(len(sizes), bn, hei, bh, **kw)
+    assert out['traj'][1].shape[0] == 9
+    assert all(bool(torch.isfinite(p).all()) for p in out['pred']) and bool(torch.isfinite(out['traj'][1]).all())
+    a = m.sampler(len(sizes), bn, hei, bh, **kw)
+    assert a.gd is not None and [mv[0] for mv in a.path] == ['down'] * 3 + ['up'] + ['down'] * 4
+    a.init()
+    for k in range(3):
+        a.move(k)
+    ws = [x.clone() for x in (a.delta, a.bp_logits, a.bp_glogits, a.t, *a.preds)]
+    a.move(3)                                                      # the up-move
+    assert all(torch.equal(x, y) for x, y in zip(ws, (a.delta, a.bp_logits, a.bp_glogits, a.t, *a.preds)))
+    assert bool(a.delta.abs().max() > 0)
+    post = {k: v.clone() for k, v in a.state().items()}
+    a.move(4)
+    b = m.sampler(len(sizes), bn, hei, bh, **kw)
+    b.set_state(post['h_node'], post['pos'], post['h_halfedge'], post['log_node'], post['log_halfedge'], frame=4)
+    b.move(4)
+    sa, sb = a.state(), b.state()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    assert torch.equal(a.delta, b.delta) and all(torch.equal(x, y) for x, y in zip(a.preds, b.preds))
+    assert bool((a.t[:len(sizes)] == a.levels[0]).all())
+
+
+def test_continuous_space_refuses_the_keywords():
+    import copy
+    import moldiff_amd as M
+    from moldiff_amd.harness import default_config
+    cfg = copy.deepcopy(default_config('MolDiff_simple'))
+    cfg.diff.categorical_space = 'continuous'
+    cfg.diff.scaling = [1., 4., 8.]
+    mc = M.MolDiff(cfg, 8, 6).eval().to(DEV)
+    bn, hei, bh, _, _ = U.graph_from_sizes([5, 6], DEV)
+    with pytest.raises(NotImplementedError):
+        mc.sampler(2, bn, hei, bh, resample=2, jump_length=3)
+    with pytest.raises(NotImplementedError):
+        mc.sample(2, bn, hei, bh, jump_length=3)
+
+
+# ---- 7. the entry point ---------------------------------------------------------------------------------------------------------------------
+
+def test_cli_resample_runs_end_to_end(tmp_path):
+    import os
+    import yaml
+    from moldiff_amd import sample_drug3d
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cfg = yaml.safe_load(open(os.path.join(root, 'configs', 'sample_MolDiff_simple.yml')))
+    assert 'resample' not in cfg['sample'] and 'jump_length' not in cfg['sample']      # the shipped defaults stay absent
+    cfg['sample'].update(save_traj_prob=1)
+    cp = tmp_path / 'sample.yml'
+    cp.write_text(yaml.safe_dump(cfg))
+    frames = len(resampling_path(6, 2, 2)) + 1                       # one frame per move + 1: 11 down-moves, 3 up-moves
+    assert frames == 15
+    base = ['--config', str(cp), '--device', DEV, '--recipe-weights', '--num_steps', '6', '--num_mols', '2', '--batch_size', '4']
+    log_dir = sample_drug3d.main(base + ['--outdir', str(tmp_path / 'out'), '--resample', '2', '--jump_length', '2'])
+    pool = torch.load(str(log_dir) + '/samples_all.pt', weights_only=False)
+    assert len(pool['finished']) + len(pool['failed']) >= 4
+    assert len(glob.glob(str(log_dir) + '_SDF/[0-9]*.sdf')) == len(pool['finished'])
+    files = glob.glob(str(log_dir) + '_SDF/traj_mol*.sdf')
+    assert len(files) >= len(pool['finished']) and (files or not pool['finished'])
+    for f in files:
+        assert open(f).read().count('$$$$') == frames
+    # the config keys do the same, and one of the two alone is refused
+    cfg['sample'].update(resample=2, jump_length=2)
+    cp.write_text(yaml.safe_dump(cfg))
+    log_dir = sample_drug3d.main(base + ['--outdir', str(tmp_path / 'out2')])
+    for f in glob.glob(str(log_dir) + '_SDF/traj_mol*.sdf'):
+        assert open(f).read().count('$$$$') == frames
+    del cfg['sample']['jump_length']
+    cp.write_text(yaml.safe_dump(cfg))
+    with pytest.raises(ValueError, match='both or neither'):
+        sample_drug3d.main(base + ['--outdir', str(tmp_path / 'out3')])
