@@ -364,6 +364,38 @@ int mdx_decode_output(mdx_graph_t g, const float* pred_node, int32_t Kn, const f
                       float* atom_pos, int32_t* n_atoms, int32_t* bond_type, float* bond_prob, int32_t* bond_index,
                       int32_t* n_bonds, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- quality check of the decoded molecules -------------------------------------------------------------------
+ * Stands in, as far as that goes without RDKit, for the reference's test of a finished molecule (scripts/sample_drug3d.py:141-153:
+ * the molecule sanitises and its SMILES has no '.') and for the valence half of Chem.SanitizeMol (utils/reconstruct.py:245-271).
+ * Reads the compact arrays mdx_decode_output wrote (same graph handle), one workgroup per molecule, and writes
+ *   per compact atom : component (N) = molecule-local index of the smallest atom of the atom's fragment; valence2 (N) = TWICE the
+ *                      bond-order sum (types 1, 2, 3 count 2, 4, 6; the last type num_bond_types, aromatic, counts 3) -- integers;
+ *   per molecule     : n_components (0 without atoms), largest_size, largest_label (component value of the largest fragment, ties
+ *                      to the smaller label, -1 without atoms), n_overvalent = atoms with valence2 / 2 (integer division: half
+ *                      bonds round down) > max_valence[atom_type], min_dist = shortest distance over ALL pairs of distinct atoms
+ *                      (+inf below two atoms), max_bond_len (0 without bonds); distances are sqrt(dx*dx + dy*dy + dz*dz) in fp32.
+ * max_valence: num_element int32 on the device, supplied by the caller (chemistry is data).  Results do not depend on the order
+ * atomic updates land in, nor on a molecule's place in the batch.
+ * What it does NOT do: no kekulisation, no aromaticity perception, no formal charges, no hydrogens, no bond-length rule.  A clean
+ * molecule here is one RDKit's valence check cannot refuse for the explicit valences above -- a NECESSARY condition of the
+ * reference's sanitisation, not a restatement: a molecule the reference fails on kekulisation passes here.
+ * ws: at least 12 * max(N, 1) bytes (any mdx_workspace_bytes() workspace is enough); too small is MDX_ERR_ARG. */
+int mdx_mol_check(mdx_graph_t g, const int32_t* atom_type, const float* atom_pos, const int32_t* n_atoms, const int32_t* bond_type,
+                  const int32_t* bond_index, const int32_t* n_bonds, int32_t num_element, int32_t num_bond_types,
+                  const int32_t* max_valence, int32_t* component, int32_t* valence2, int32_t* n_components, int32_t* largest_size,
+                  int32_t* largest_label, int32_t* n_overvalent, float* min_dist, float* max_bond_len, void* ws, size_t ws_bytes,
+                  void* stream);
+/* Restricts every molecule m with select[m] != 0 (select, label: n_graphs int32, device) to the atoms whose `component` (from
+ * mdx_mol_check) equals label[m]; the others are untouched.  Rewrites the compact arrays IN PLACE -- atom_type / atom_prob /
+ * atom_pos / n_atoms and bond_type / bond_prob / bond_index / n_bonds -- with order preserved and bonds re-indexed; label -1
+ * empties the molecule.  This is what "keep the largest fragment" pipelines do after the reference's '.' test
+ * (scripts/sample_drug3d.py:141-153); the reference itself discards such molecules.  It does NOT re-run the check (`component`
+ * and `valence2` keep describing the molecule as decoded; a kept atom's valence is unchanged, its bonds all lie in its fragment)
+ * and does not choose the fragment: the caller forms `select` and `label`.  ws as for mdx_mol_check. */
+int mdx_mol_keep_component(mdx_graph_t g, const int32_t* select, const int32_t* label, const int32_t* component, int32_t* atom_type,
+                           float* atom_prob, float* atom_pos, int32_t* n_atoms, int32_t* bond_type, float* bond_prob,
+                           int32_t* bond_index, int32_t* n_bonds, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

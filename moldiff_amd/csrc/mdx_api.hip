@@ -1866,6 +1866,50 @@ extern "C" int mdx_decode_output(mdx_graph_t g, const float* pred_node, int32_t 
   return MDX_OK;
 }
 
+// both entries use the first 3N ints of the workspace: labels | fragment sizes (mdx_mol_check), old -> new atom index (keep)
+static int molcheck_scratch(mdx_graph_t g, void* ws, size_t ws_bytes, int** scratch) {
+  const size_t need = (size_t)std::max<int64_t>(g->N, 1) * 3 * sizeof(int);
+  if (!ws || ws_bytes < need) return fail(MDX_ERR_ARG, "workspace too small: need %zu bytes", need);
+  if (reinterpret_cast<uintptr_t>(ws) & 3) return fail(MDX_ERR_ARG, "workspace must be 4-byte aligned");
+  *scratch = reinterpret_cast<int*>(ws);
+  return MDX_OK;
+}
+
+extern "C" int mdx_mol_check(mdx_graph_t g, const int32_t* atom_type, const float* atom_pos, const int32_t* n_atoms,
+                             const int32_t* bond_type, const int32_t* bond_index, const int32_t* n_bonds, int32_t num_element,
+                             int32_t num_bond_types, const int32_t* max_valence, int32_t* component, int32_t* valence2,
+                             int32_t* n_components, int32_t* largest_size, int32_t* largest_label, int32_t* n_overvalent,
+                             float* min_dist, float* max_bond_len, void* ws, size_t ws_bytes, void* stream) {
+  if (!g || !atom_type || !atom_pos || !n_atoms || !bond_type || !bond_index || !n_bonds || !max_valence || !component ||
+      !valence2 || !n_components || !largest_size || !largest_label || !n_overvalent || !min_dist || !max_bond_len)
+    return fail(MDX_ERR_ARG, "null argument");
+  if (num_element < 1 || num_bond_types < 1) return fail(MDX_ERR_ARG, "bad class count");
+  int* scratch = nullptr;
+  if (int rc = molcheck_scratch(g, ws, ws_bytes, &scratch)) return rc;
+  MolCheckArgs a{(int)g->N, (int)g->Eh, (int)g->B, num_element, num_bond_types, g->node_ptr, g->he_ptr, atom_type, atom_pos,
+                 n_atoms, bond_type, bond_index, n_bonds, max_valence, scratch, component, valence2, n_components,
+                 largest_size, largest_label, n_overvalent, min_dist, max_bond_len};
+  launch_mol_check(a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
+extern "C" int mdx_mol_keep_component(mdx_graph_t g, const int32_t* select, const int32_t* label, const int32_t* component,
+                                      int32_t* atom_type, float* atom_prob, float* atom_pos, int32_t* n_atoms,
+                                      int32_t* bond_type, float* bond_prob, int32_t* bond_index, int32_t* n_bonds, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  if (!g || !select || !label || !component || !atom_type || !atom_prob || !atom_pos || !n_atoms || !bond_type || !bond_prob ||
+      !bond_index || !n_bonds)
+    return fail(MDX_ERR_ARG, "null argument");
+  int* scratch = nullptr;
+  if (int rc = molcheck_scratch(g, ws, ws_bytes, &scratch)) return rc;
+  MolKeepArgs a{(int)g->N, (int)g->Eh, (int)g->B, g->node_ptr, g->he_ptr, select, label, component, scratch + 2 * g->N,
+                atom_type, atom_prob, atom_pos, n_atoms, bond_type, bond_prob, bond_index, n_bonds};
+  launch_mol_keep_component(a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
 extern "C" int mdx_guidance_uncertainty_grad(const float* logits, int32_t K, int64_t n, float* glogits, void* stream) {
   if (K < 1 || n < 0 || (n > 0 && (!logits || !glogits))) return fail(MDX_ERR_ARG, "bad argument");
   launch_uncertainty_grad(logits, K, (int)n, glogits, (hipStream_t)stream);

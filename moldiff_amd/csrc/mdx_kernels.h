@@ -367,6 +367,30 @@ struct ForwardJumpArgs {  // mdx_transition.hip: every row of a sampler state mo
   uint8_t *node_cls_next, *half_cls_next;    // may be nullptr
 };
 void launch_forward_jump(const ForwardJumpArgs& a, hipStream_t s);
+struct MolCheckArgs {  // mdx_molcheck.hip: fragments / valences / distances of the compact arrays mdx_decode_output leaves
+  int N, Eh, B, num_element, num_bond_types;
+  const int *node_ptr, *he_ptr;
+  const int* atom_type;    // (N) compact
+  const float* atom_pos;   // (N,3) compact
+  const int *n_atoms, *bond_type, *bond_index, *n_bonds;  // (B), (Eh), (2,Eh), (B)
+  const int* max_valence;  // (num_element)
+  int* scratch;            // 2N ints: labels | fragment sizes of molecules beyond the LDS capacity
+  int *component, *valence2;                                            // (N)
+  int *n_components, *largest_size, *largest_label, *n_overvalent;      // (B)
+  float *min_dist, *max_bond_len;                                       // (B)
+};
+void launch_mol_check(const MolCheckArgs& a, hipStream_t s);
+struct MolKeepArgs {  // mdx_molcheck.hip: molecules with select != 0 keep the atoms whose component == label, in place
+  int N, Eh, B;
+  const int *node_ptr, *he_ptr, *select, *label, *component;
+  int* scratch;  // N ints: old -> new atom index
+  int* atom_type;
+  float *atom_prob, *atom_pos;
+  int *n_atoms, *bond_type;
+  float* bond_prob;
+  int *bond_index, *n_bonds;
+};
+void launch_mol_keep_component(const MolKeepArgs& a, hipStream_t s);
 // the same three sums after an EA_AGG edge kernel A: aggr / SR combine each node's partial rows pbase[v] .. pbase[v+1] of P / PR
 // in order, SL is still the indexed sum over FL
 void launch_seg_reduce_block2(const float* P, const float* PR, const float* FL, const int* pbase, const int* col_ptr,

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .molcheck import fragment_fraction, valence_table
 
 
 def _softmax(x):
@@ -63,10 +64,8 @@ class FeaturizeMol(object):
                    bond_index=np.concatenate([bond_index, bond_index[::-1]], axis=1))
         return out
 
-    def decode_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None):
-        """Whole packed batch on the device -> list of per-molecule dicts identical to
-        [decode_output(*seperate_outputs(...)[i]) for i in range(n_graphs)].
-        pred = [pred_node (N,Kn), pred_pos (N,3), pred_halfedge (Eh,Ke)] device tensors (model.sample()['pred'])."""
+    def _decode_device(self, pred, batch_node, halfedge_index, n_graphs, graph):
+        """Launch ``mdx_decode_output`` -> (graph, dict of the compact device tensors); no copy, no sync."""
         pn, pp, ph = (_lib.f32c(t) for t in pred)
         _lib._need_gpu(pn, pp, ph, batch_node, halfedge_index)
         dev = pn.device
@@ -83,9 +82,14 @@ class FeaturizeMol(object):
             graph.h, _lib.ptr(pn), pn.shape[1], _lib.ptr(pp), _lib.ptr(ph), ph.shape[1], self.num_element,
             self.num_bond_types, _lib.ptr(atom_type), _lib.ptr(atom_prob), _lib.ptr(atom_pos), _lib.ptr(n_atoms),
             _lib.ptr(bond_type), _lib.ptr(bond_prob), _lib.ptr(bond_index), _lib.ptr(n_bonds), ws, nb, _lib.stream()))
-        at, ap, apos = atom_type.cpu().numpy(), atom_prob.cpu().numpy(), atom_pos.cpu().numpy()
-        bt, bp, bi = bond_type.cpu().numpy(), bond_prob.cpu().numpy(), bond_index.cpu().numpy()
-        na, nbd = n_atoms.cpu().numpy(), n_bonds.cpu().numpy()
+        return graph, dict(atom_type=atom_type, atom_prob=atom_prob, atom_pos=atom_pos, n_atoms=n_atoms, bond_type=bond_type,
+                           bond_prob=bond_prob, bond_index=bond_index, n_bonds=n_bonds)
+
+    def _slice_mols(self, d, batch_node, batch_halfedge, B):
+        """Copy the compact arrays to the host and slice them per molecule -> (list of dicts, node_ptr, n_atoms)."""
+        at, ap, apos = d['atom_type'].cpu().numpy(), d['atom_prob'].cpu().numpy(), d['atom_pos'].cpu().numpy()
+        bt, bp, bi = d['bond_type'].cpu().numpy(), d['bond_prob'].cpu().numpy(), d['bond_index'].cpu().numpy()
+        na, nbd = d['n_atoms'].cpu().numpy(), d['n_bonds'].cpu().numpy()
         node_ptr = np.concatenate([[0], np.cumsum(np.bincount(batch_node.cpu().numpy(), minlength=B))])
         he_ptr = np.concatenate([[0], np.cumsum(np.bincount(batch_halfedge.cpu().numpy(), minlength=B))])
         ele = np.asarray(self.atomic_numbers.numpy())
@@ -98,7 +102,71 @@ class FeaturizeMol(object):
                         'bond_type': np.concatenate([bt[b0:b1], bt[b0:b1]]).astype(np.int64),
                         'bond_prob': np.concatenate([bp[b0:b1], bp[b0:b1]]),
                         'bond_index': np.concatenate([idx, idx[::-1]], axis=1)})
-        return out
+        return out, node_ptr, na
+
+    def decode_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None):
+        """Whole packed batch on the device -> list of per-molecule dicts identical to
+        [decode_output(*seperate_outputs(...)[i]) for i in range(n_graphs)].
+        pred = [pred_node (N,Kn), pred_pos (N,3), pred_halfedge (Eh,Ke)] device tensors (model.sample()['pred'])."""
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        return self._slice_mols(d, batch_node, batch_halfedge, graph.B)[0]
+
+    def _check_device(self, graph, d, max_valence=None, largest_fragment=None):
+        """The device part of ``check_batch`` on the compact tensors `d` of ``_decode_device``: ``mdx_mol_check``, and with
+        `largest_fragment` the selection (device integer arithmetic, no host sync) + ``mdx_mol_keep_component``, which rewrites `d`
+        in place.  -> (ri (6,B) int32: n_components, largest_size, largest_label, n_overvalent, n_atoms as decoded,
+        salvaged; rf (2,B) float32: min_dist, max_bond_len; pa (2,N) int32: component, valence2)."""
+        dev = d['atom_type'].device
+        N, B = graph.N, graph.B
+        key = (str(dev), tuple(valence_table(self.atomic_numbers.tolist(), max_valence)))
+        if getattr(self, '_mv_key', None) != key:
+            self._mv, self._mv_key = torch.tensor(key[1], dtype=torch.int32, device=dev), key
+        ri = torch.zeros(6, max(B, 1), dtype=torch.int32, device=dev)
+        rf = torch.empty(2, max(B, 1), dtype=torch.float32, device=dev)
+        pa = torch.empty(2, max(N, 1), dtype=torch.int32, device=dev)
+        ws, nb = graph.workspace(dev)
+        _lib.check(_lib.lib().mdx_mol_check(
+            graph.h, _lib.ptr(d['atom_type']), _lib.ptr(d['atom_pos']), _lib.ptr(d['n_atoms']), _lib.ptr(d['bond_type']),
+            _lib.ptr(d['bond_index']), _lib.ptr(d['n_bonds']), self.num_element, self.num_bond_types, _lib.ptr(self._mv),
+            _lib.ptr(pa[0]), _lib.ptr(pa[1]), _lib.ptr(ri[0]), _lib.ptr(ri[1]), _lib.ptr(ri[2]), _lib.ptr(ri[3]), _lib.ptr(rf[0]),
+            _lib.ptr(rf[1]), ws, nb, _lib.stream()))
+        ri[4].copy_(d['n_atoms'])
+        if largest_fragment is not None:
+            p, q = fragment_fraction(largest_fragment)
+            # more than one fragment, and largest_size / n_atoms >= p / q in int64
+            ri[5] = ((ri[0] > 1) & (ri[1].long() * q >= ri[4].long() * p)).to(torch.int32)
+            _lib.check(_lib.lib().mdx_mol_keep_component(
+                graph.h, _lib.ptr(ri[5]), _lib.ptr(ri[2]), _lib.ptr(pa[0]), _lib.ptr(d['atom_type']), _lib.ptr(d['atom_prob']),
+                _lib.ptr(d['atom_pos']), _lib.ptr(d['n_atoms']), _lib.ptr(d['bond_type']), _lib.ptr(d['bond_prob']),
+                _lib.ptr(d['bond_index']), _lib.ptr(d['n_bonds']), ws, nb, _lib.stream()))
+        return ri, rf, pa
+
+    def check_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, max_valence=None,
+                    largest_fragment=None):
+        """``decode_batch`` + the quality check of every molecule on the device (``mdx_mol_check``) -> (mols, report).
+        mols: as from decode_batch, plus per atom ``component`` (index of the smallest atom of the atom's fragment) and ``valence``
+        (float, bond-order sum; aromatic bonds count 1.5).  report: numpy arrays of length n_graphs -- n_components, largest_size,
+        largest_label, n_overvalent, min_dist, max_bond_len, n_atoms, salvaged -- that always describe the molecule AS DECODED.
+        max_valence: dict atomic number -> largest permitted valence (None = molcheck.DEFAULT_MAX_VALENCE, unchecked against RDKit).
+        largest_fragment = f in (0, 1]: a molecule with more than one fragment whose largest fragment holds at least f * n_atoms
+        atoms is restricted to that fragment on the device (``mdx_mol_keep_component``): mols[m] is then the fragment (its atoms'
+        valences are those they had in the whole molecule) and report['salvaged'][m] is True.
+        The valence rule is a necessary condition of the reference's RDKit sanitisation only: see moldiff_amd/molcheck.py."""
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        ri, rf, pa = self._check_device(graph, d, max_valence, largest_fragment)
+        B = graph.B
+        mols, node_ptr, na = self._slice_mols(d, batch_node, batch_halfedge, B)
+        ri, rf, pa = ri.cpu().numpy(), rf.cpu().numpy(), pa.cpu().numpy()
+        report = {'n_components': ri[0, :B], 'largest_size': ri[1, :B], 'largest_label': ri[2, :B], 'n_overvalent': ri[3, :B],
+                  'min_dist': rf[0, :B], 'max_bond_len': rf[1, :B], 'n_atoms': ri[4, :B], 'salvaged': ri[5, :B] != 0}
+        for m in range(B):
+            a0 = node_ptr[m]
+            comp, val = pa[0, a0:a0 + ri[4, m]].astype(np.int64), pa[1, a0:a0 + ri[4, m]] / 2.0
+            if ri[5, m]:   # the fragment's atoms in their new numbering: its smallest atom is atom 0
+                keep = comp == ri[2, m]
+                comp, val = np.zeros(int(keep.sum()), dtype=np.int64), val[keep]
+            mols[m]['component'], mols[m]['valence'] = comp, val
+        return mols, report
 
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -23,10 +23,18 @@ give-up rule (:106-108).  What differs, deliberately:
 ``--scaffold PATH`` (config key ``sample.scaffold``), an addition beyond the reference: PATH is a V2000 mol block as this module
 writes them; every sampled molecule gets it as its first atoms, held fixed with the bonds among them, and the rest is grown around
 it (``moldiff_amd/scaffold.py``).  Sizes are drawn as usual and raised to the scaffold's atom count where they fall below it.
+``--accept {connected,valence}`` / ``--largest_fragment FRAC`` (config keys ``sample.accept``, ``sample.largest_fragment``), additions
+beyond the reference: with either, acceptance comes from the device-side quality check (``FeaturizeMol.check_batch``) instead of the
+Python union-find -- 'connected' is the rule above, 'valence' adds "no atom above its largest permitted valence" (a NECESSARY
+condition of the reference's RDKit sanitisation, from a table that is unchecked against RDKit: moldiff_amd/molcheck.py); FRAC in
+(0, 1], no default, replaces a disconnected molecule whose largest fragment holds at least FRAC of its atoms by that fragment before
+it is judged.  Pool entries then carry n_components / n_overvalent / min_dist / max_bond_len (of the molecule as decoded) and
+salvaged, and rank 0 writes ``quality.json`` into the log directory.  Without both options nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
 import argparse
+import json
 import os
 import shutil
 import time
@@ -38,6 +46,7 @@ from . import BondPredictor, MolDiff, _lib
 from .distributed import balanced_order, gather_pred, shard_bounds
 from .harness import default_config, load_config, placeholder_from_sizes, recipe_state_dict, seed_all
 from .harness import GEOM_DRUGS_MEAN_ATOMS, GEOM_DRUGS_STD_ATOMS
+from .molcheck import accept_rule, fragment_fraction, judge, quality_summary
 from .postprocess import FeaturizeMol
 from .scaffold import scaffold_for_sizes
 
@@ -162,6 +171,20 @@ def traj_blocks(featurizer, traj, sel, sizes, device):
     return {m: [frames[t][j] for t in range(len(frames))] for j, m in enumerate(sel)}
 
 
+def quality_options(accept, largest_fragment, sample_cfg):
+    """(rule, FRAC or None, active) from the command line's values (None = not given) and the config's ``sample`` section; a value
+    outside what the options admit raises ValueError.  active = either option was given: acceptance then comes from check_batch."""
+    if accept is None:
+        accept = sample_cfg.get('accept')
+    if largest_fragment is None:
+        largest_fragment = sample_cfg.get('largest_fragment')
+    active = accept is not None or largest_fragment is not None
+    if largest_fragment is not None:
+        fragment_fraction(largest_fragment)
+        largest_fragment = float(largest_fragment)
+    return accept_rule('connected' if accept is None else accept), largest_fragment, active
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -177,7 +200,16 @@ def main(argv=None):
     ap.add_argument('--resample', type=int, default=0, help='resampling: walk every block of --jump_length levels this many times, with a '
                                                             'forward jump in between (overrides sample.resample; needs --jump_length)')
     ap.add_argument('--jump_length', type=int, default=0, help='resampling: moves per block (overrides sample.jump_length)')
+    ap.add_argument('--accept', type=str, default=None, help="'connected' (one fragment) or 'valence' (that and no over-valent atom); "
+                                                             'judged by the device-side check (overrides sample.accept)')
+    ap.add_argument('--largest_fragment', type=float, default=None,
+                    help='FRAC in (0, 1]: a disconnected molecule whose largest fragment holds at least FRAC of its atoms is replaced '
+                         'by that fragment before it is judged (overrides sample.largest_fragment; no default)')
     args = ap.parse_args(argv)
+    if args.accept is not None:
+        accept_rule(args.accept)
+    if args.largest_fragment is not None:
+        fragment_fraction(args.largest_fragment)
 
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     dist = None
@@ -226,6 +258,7 @@ def main(argv=None):
     extra = {} if num_steps is None else {'num_steps': int(num_steps)}
     if resample is not None or jump_length is not None:
         extra.update(resample=None if resample is None else int(resample), jump_length=None if jump_length is None else int(jump_length))
+    rule, frac, checked = quality_options(args.accept, args.largest_fragment, config.sample)
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -257,9 +290,15 @@ def main(argv=None):
         # trajectories stay rank-local (scripts/sample_drug3d.py:155 looks at ~2 % of them): the owner decodes and writes
         # them, named by global molecule id; whether a molecule is drawn depends only on (seed, id), not on the sharding
         if save_traj_prob > 0:
-            local = featurizer.decode_batch(out['pred'], ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], hi - lo)
+            if checked:   # the same rule as rank 0 below: a function of the molecule alone
+                local, rep = featurizer.check_batch(out['pred'], ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], hi - lo,
+                                                    largest_fragment=frac)
+                done = [judge(info, rep, j, rule)[0] for j, info in enumerate(local)]
+            else:
+                local = featurizer.decode_batch(out['pred'], ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], hi - lo)
+                done = [is_connected(len(info['element']), info['bond_index']) for info in local]
             sel = [j for j, info in enumerate(local)
-                   if is_connected(len(info['element']), info['bond_index'])
+                   if done[j]
                    and np.random.default_rng([seed, int(ids[j])]).random() < save_traj_prob]
             if sel:
                 for j, frames in traj_blocks(featurizer, out['traj'], sel, sizes[mine], device).items():
@@ -275,14 +314,19 @@ def main(argv=None):
         counts = torch.zeros(2, dtype=torch.int64, device=comm_dev)
         if rank == 0:
             full = placeholder_from_sizes(sizes[order], device)
-            mols = featurizer.decode_batch([p.to(device) for p in pred], full['batch_node'], full['halfedge_index'],
-                                           full['batch_halfedge'], n_graphs)
             inv = np.argsort(order)                       # back to the batch's original molecule order
+            if checked:
+                mols, rep = featurizer.check_batch([p.to(device) for p in pred], full['batch_node'], full['halfedge_index'],
+                                                   full['batch_halfedge'], n_graphs, largest_fragment=frac)
+                done = [judge(mols[inv[k]], rep, inv[k], rule, annotate=True)[0] for k in range(n_graphs)]
+            else:
+                mols = featurizer.decode_batch([p.to(device) for p in pred], full['batch_node'], full['halfedge_index'],
+                                               full['batch_halfedge'], n_graphs)
             mols = [mols[inv[k]] for k in range(n_graphs)]
             gen = []
             for k, info in enumerate(mols):
                 info['mol_id'] = next_id + k
-                if is_connected(len(info['element']), info['bond_index']):
+                if done[k] if checked else is_connected(len(info['element']), info['bond_index']):
                     gen.append(info)
                 else:
                     pool['failed'].append(info)
@@ -304,6 +348,10 @@ def main(argv=None):
         i_batch += 1
     if rank == 0:
         torch.save(pool, os.path.join(log_dir, 'samples_all.pt'))
+        if checked:
+            with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
+                json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),
+                               accept=rule, largest_fragment=frac), f, indent=1)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
