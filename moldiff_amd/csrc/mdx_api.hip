@@ -1305,6 +1305,47 @@ extern "C" int mdx_moldiff_forward(mdx_model_t m, mdx_graph_t g, const float* h_
   return MDX_OK;
 }
 
+// The transition of one move: position posterior, node posterior + Gumbel-max, half-edge posterior + Gumbel-max.  The rows come from the
+// one-step tables `tb`, or, when the move is a jump (strided sampling), from `jr`.  MolDiff's class counts 8 / 6 take all five launches
+// in one; other class counts the stand-alone ones.
+static int step_transition(const mdx_config& cf, const mdx_tables* tb, const StepJumpRows* jr, int N, int Eh, const int64_t* t,
+                           const int64_t* batch_node, const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next,
+                           const float* pred_node, const float* pred_pos, const float* pred_halfedge, const float* eps_pos,
+                           const float* u_node, const float* u_halfedge, uint8_t* node_cls, uint8_t* halfedge_cls, hipStream_t s) {
+  if (cf.num_node_types == 8 && cf.num_edge_types == 6) {
+    StepTransArgs ta{};
+    ta.N = N; ta.Eh = Eh; ta.T = cf.num_timesteps; ta.c0 = tb->pos_coef_x0; ta.ct = tb->pos_coef_xt; ta.sd = tb->pos_std;
+    ta.node_q = tb->node_q_mats; ta.node_qT1 = tb->node_qT_onestep; ta.edge_q = tb->edge_q_mats; ta.edge_qT1 = tb->edge_qT_onestep;
+    ta.t = t; ta.batch_node = batch_node; ta.batch_half = batch_halfedge; ta.pos = cur->pos; ta.pred_pos = pred_pos; ta.eps = eps_pos;
+    ta.pred_node = pred_node; ta.log_node = cur->log_node; ta.u_node = u_node; ta.pred_half = pred_halfedge;
+    ta.log_half = cur->log_halfedge; ta.u_half = u_halfedge; ta.pos_next = next->pos; ta.log_node_next = next->log_node;
+    ta.h_node_next = next->h_node; ta.log_half_next = next->log_halfedge; ta.h_half_next = next->h_halfedge; ta.node_cls = node_cls;
+    ta.half_cls = halfedge_cls;
+    if (jr) launch_step_jump(ta, *jr, s);
+    else launch_step_transition(ta, s);
+    return MDX_OK;
+  }
+  if (jr && (cf.num_node_types < 2 || cf.num_node_types > 8 || cf.num_edge_types < 2 || cf.num_edge_types > 8))
+    return fail(MDX_ERR_UNSUPPORTED, "jump posteriors: class counts %d / %d outside 2..8", cf.num_node_types, cf.num_edge_types);
+  // a jump reads its tables' row with the schedule position as a launch scalar
+  auto cat = [&](const float* q, const float* qT1, const float* qT_jump, int K, const float* pred, const float* log_vt,
+                 const int64_t* batch, int n, float* out) {
+    if (jr) launch_cat_posterior_jump(q, qT_jump, K, pred, 1, log_vt, t, nullptr, nullptr, jr->s, jr->row, batch, n, out, s);
+    else launch_cat_posterior(q, qT1, K, cf.num_timesteps, pred, 1, log_vt, t, batch, n, out, s);
+  };
+  if (jr) launch_pos_posterior_jump(jr->c0, jr->ct, jr->sd, cur->pos, pred_pos, eps_pos, t, nullptr, jr->row, batch_node, N, next->pos, s);
+  else launch_pos_posterior(tb->pos_coef_x0, tb->pos_coef_xt, tb->pos_std, cur->pos, pred_pos, eps_pos, t, batch_node, N, next->pos, s);
+  cat(tb->node_q_mats, tb->node_qT_onestep, jr ? jr->node_qT : nullptr, cf.num_node_types, pred_node, cur->log_node, batch_node, N,
+      next->log_node);
+  launch_gumbel_argmax(next->log_node, u_node, cf.num_node_types, N, nullptr, next->h_node, s, node_cls);
+  if (Eh > 0) {
+    cat(tb->edge_q_mats, tb->edge_qT_onestep, jr ? jr->edge_qT : nullptr, cf.num_edge_types, pred_halfedge, cur->log_halfedge,
+        batch_halfedge, Eh, next->log_halfedge);
+    launch_gumbel_argmax(next->log_halfedge, u_halfedge, cf.num_edge_types, Eh, nullptr, next->h_halfedge, s, halfedge_cls);
+  }
+  return MDX_OK;
+}
+
 static int sample_step_core(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, const int64_t* t, const int64_t* batch_node,
                             const int64_t* batch_halfedge, const mdx_state* cur, const mdx_state* next, float* pred_node,
                             float* pred_pos, float* pred_halfedge, const float* eps_pos, const float* u_node,
@@ -1317,49 +1358,10 @@ static int sample_step_core(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, 
   if (!pred_node || !pred_pos || (Eh > 0 && !pred_halfedge) || !eps_pos || !u_node || (Eh > 0 && !u_halfedge) || !batch_node ||
       (Eh > 0 && !batch_halfedge))
     return fail(MDX_ERR_ARG, "null buffer");
-  int rc = mdx_moldiff_forward(m, g, cur->h_node, cur->pos, nullptr, cur->h_halfedge, t, pred_node, pred_pos, pred_halfedge, ws,
-                               ws_bytes, stream);
-  if (rc != MDX_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const mdx_config& cf = m->cfg;
-  if (cf.num_node_types == 8 && cf.num_edge_types == 6) {  // MolDiff's class counts: all five transition launches in one
-    StepTransArgs ta{};
-    ta.N = N; ta.Eh = Eh; ta.T = cf.num_timesteps; ta.c0 = tb->pos_coef_x0; ta.ct = tb->pos_coef_xt; ta.sd = tb->pos_std;
-    ta.node_q = tb->node_q_mats; ta.node_qT1 = tb->node_qT_onestep; ta.edge_q = tb->edge_q_mats; ta.edge_qT1 = tb->edge_qT_onestep;
-    ta.t = t; ta.batch_node = batch_node; ta.batch_half = batch_halfedge; ta.pos = cur->pos; ta.pred_pos = pred_pos; ta.eps = eps_pos;
-    ta.pred_node = pred_node; ta.log_node = cur->log_node; ta.u_node = u_node; ta.pred_half = pred_halfedge;
-    ta.log_half = cur->log_halfedge; ta.u_half = u_halfedge; ta.pos_next = next->pos; ta.log_node_next = next->log_node;
-    ta.h_node_next = next->h_node; ta.log_half_next = next->log_halfedge; ta.h_half_next = next->h_halfedge; ta.node_cls = node_cls;
-    ta.half_cls = halfedge_cls;
-    if (jr) launch_step_jump(ta, *jr, s);
-    else launch_step_transition(ta, s);
-    HIPCHK(hipGetLastError());
-    return MDX_OK;
-  }
-  if (jr) {  // other class counts: the stand-alone jump posteriors with the schedule position as a launch scalar
-    if (cf.num_node_types < 2 || cf.num_node_types > 8 || cf.num_edge_types < 2 || cf.num_edge_types > 8)
-      return fail(MDX_ERR_UNSUPPORTED, "jump posteriors: class counts %d / %d outside 2..8", cf.num_node_types, cf.num_edge_types);
-    launch_pos_posterior_jump(jr->c0, jr->ct, jr->sd, cur->pos, pred_pos, eps_pos, t, nullptr, jr->row, batch_node, N, next->pos, s);
-    launch_cat_posterior_jump(tb->node_q_mats, jr->node_qT, cf.num_node_types, pred_node, 1, cur->log_node, t, nullptr, nullptr, jr->s,
-                              jr->row, batch_node, N, next->log_node, s);
-    launch_gumbel_argmax(next->log_node, u_node, cf.num_node_types, N, nullptr, next->h_node, s, node_cls);
-    if (Eh > 0) {
-      launch_cat_posterior_jump(tb->edge_q_mats, jr->edge_qT, cf.num_edge_types, pred_halfedge, 1, cur->log_halfedge, t, nullptr,
-                                nullptr, jr->s, jr->row, batch_halfedge, Eh, next->log_halfedge, s);
-      launch_gumbel_argmax(next->log_halfedge, u_halfedge, cf.num_edge_types, Eh, nullptr, next->h_halfedge, s, halfedge_cls);
-    }
-    HIPCHK(hipGetLastError());
-    return MDX_OK;
-  }
-  launch_pos_posterior(tb->pos_coef_x0, tb->pos_coef_xt, tb->pos_std, cur->pos, pred_pos, eps_pos, t, batch_node, N, next->pos, s);
-  launch_cat_posterior(tb->node_q_mats, tb->node_qT_onestep, cf.num_node_types, cf.num_timesteps, pred_node, 1, cur->log_node, t,
-                       batch_node, N, next->log_node, s);
-  launch_gumbel_argmax(next->log_node, u_node, cf.num_node_types, N, nullptr, next->h_node, s, node_cls);
-  if (Eh > 0) {
-    launch_cat_posterior(tb->edge_q_mats, tb->edge_qT_onestep, cf.num_edge_types, cf.num_timesteps, pred_halfedge, 1,
-                         cur->log_halfedge, t, batch_halfedge, Eh, next->log_halfedge, s);
-    launch_gumbel_argmax(next->log_halfedge, u_halfedge, cf.num_edge_types, Eh, nullptr, next->h_halfedge, s, halfedge_cls);
-  }
+  LCHK(mdx_moldiff_forward(m, g, cur->h_node, cur->pos, nullptr, cur->h_halfedge, t, pred_node, pred_pos, pred_halfedge, ws, ws_bytes,
+                           stream));
+  LCHK(step_transition(m->cfg, tb, jr, N, Eh, t, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, eps_pos,
+                       u_node, u_halfedge, node_cls, halfedge_cls, (hipStream_t)stream));
   HIPCHK(hipGetLastError());
   return MDX_OK;
 }
@@ -1370,6 +1372,24 @@ extern "C" int mdx_sample_step(mdx_model_t m, mdx_graph_t g, const mdx_tables* t
                                const float* u_halfedge, void* ws, size_t ws_bytes, void* stream) {
   return sample_step_core(m, g, tb, t, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, eps_pos, u_node,
                           u_halfedge, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+// every pointer of a state the transitions write (the half-edge ones only where there are half-edges)
+static bool state_complete(const mdx_state* st, int Eh) {
+  return st && st->h_node && st->pos && st->log_node && (Eh == 0 || (st->h_halfedge && st->log_halfedge));
+}
+
+// The noise of one move: drawn by the library into the caller's buffers (draw >= 0: one Philox launch, which also fills the time tensor
+// t_buf with `step` when given one), or the caller's buffers as they are (draw < 0; t_buf then takes a launch of its own).
+static int draw_or_use_noise(const mdx_graph_s* g, const mdx_step_noise* noise, int Kn, int Ke, hipStream_t s, int64_t* t_buf = nullptr,
+                             int32_t step = 0) {
+  if (!noise || !noise->eps_pos || !noise->u_node || (g->Eh > 0 && !noise->u_halfedge)) return fail(MDX_ERR_ARG, "null noise buffer");
+  if (noise->draw >= 0)
+    launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, (int)g->N,
+                        (int)g->Eh, Kn, Ke, noise->eps_pos, noise->u_node, noise->u_halfedge, s, t_buf, step, t_buf ? (int)g->B : 0);
+  else if (t_buf)
+    launch_fill_i64(t_buf, step, (int)g->B, s);
+  return MDX_OK;
 }
 
 // the body of mdx_sample_step_full and mdx_sample_jump_full: jr == nullptr is the chain's ordinary move step -> step - 1
@@ -1384,58 +1404,40 @@ static int sample_step_full_impl(mdx_model_t m, mdx_graph_t g, const mdx_tables*
   if (g->N == 0) return MDX_OK;
   hipStream_t s = (hipStream_t)stream;
   const mdx_config& cf = m->cfg;
-  if (noise->draw >= 0) {  // the Philox launch also fills the time tensor
-    if (cf.num_node_types > 8 || cf.num_edge_types > 8) return fail(MDX_ERR_ARG, "class counts must be in 1..8");
-    launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, (int)g->N,
-                        (int)g->Eh, cf.num_node_types, cf.num_edge_types, noise->eps_pos, noise->u_node, noise->u_halfedge, s, t_buf,
-                        step, (int)g->B);
-  } else {
-    launch_fill_i64(t_buf, step, (int)g->B, s);
+  if (noise->draw >= 0 && (cf.num_node_types > 8 || cf.num_edge_types > 8)) return fail(MDX_ERR_ARG, "class counts must be in 1..8");
+  LCHK(draw_or_use_noise(g, noise, cf.num_node_types, cf.num_edge_types, s, t_buf, step));
+  // the guidance chain (default 'uncertainty' objective): on a side stream it is enqueued BEFORE the denoiser, so that it runs under
+  // it; in line it comes after and reuses the denoiser's workspace
+  const bool side = gd && gd->side_stream;
+  hipStream_t gs = side ? (hipStream_t)gd->side_stream : s;
+  auto chain = [&]() -> int {
+    void* gws = side ? gd->ws2 : ws;
+    const size_t gwb = side ? gd->ws2_bytes : ws_bytes;
+    LCHK(mdx_bondpred_forward(gd->predictor, g, cur->h_node, cur->pos, t_buf, gd->logits, gws, gwb, gd->tape, gd->tape_bytes, gs));
+    launch_uncertainty_grad(gd->logits, gd->predictor->cfg.num_edge_types, (int)g->Eh, gd->glogits, gs);
+    return mdx_bondpred_backward(gd->predictor, g, cur->pos, gd->glogits, -gd->scale, gd->delta, gws, gwb, gd->tape, gd->tape_bytes, gs);
+  };
+  if (gd && (!gd->predictor || !gd->tape || !gd->logits || !gd->glogits || !gd->delta)) return fail(MDX_ERR_ARG, "incomplete mdx_guidance");
+  if (side) {
+    if (!gd->ws2) return fail(MDX_ERR_ARG, "a concurrent guidance chain needs its own workspace (ws2)");
+    if (!g->ev_in) {
+      HIPCHK(hipEventCreateWithFlags(&g->ev_in, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
+    }
+    // everything the chain reads (state, t_buf) and the previous step's use of `delta` is ordered before this point
+    HIPCHK(hipEventRecord(g->ev_in, s));
+    HIPCHK(hipStreamWaitEvent(gs, g->ev_in, 0));
+    LCHK(chain());
+    HIPCHK(hipEventRecord(g->ev_done, gs));
   }
-  hipStream_t gs = s;  // the stream the guidance chain runs on
-  if (gd) {
-    if (!gd->predictor || !gd->tape || !gd->logits || !gd->glogits || !gd->delta) return fail(MDX_ERR_ARG, "incomplete mdx_guidance");
-    if (gd->side_stream) {
-      if (!gd->ws2) return fail(MDX_ERR_ARG, "a concurrent guidance chain needs its own workspace (ws2)");
-      if (!g->ev_in) {
-        HIPCHK(hipEventCreateWithFlags(&g->ev_in, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
-      }
-      gs = (hipStream_t)gd->side_stream;
-      // everything the chain reads (state, t_buf) and the previous step's use of `delta` is ordered before this point
-      HIPCHK(hipEventRecord(g->ev_in, s));
-      HIPCHK(hipStreamWaitEvent(gs, g->ev_in, 0));
-    }
-    void* gws = gd->side_stream ? gd->ws2 : ws;
-    const size_t gwb = gd->side_stream ? gd->ws2_bytes : ws_bytes;
-    auto chain = [&]() -> int {
-      int rc = mdx_bondpred_forward(gd->predictor, g, cur->h_node, cur->pos, t_buf, gd->logits, gws, gwb, gd->tape, gd->tape_bytes, gs);
-      if (rc != MDX_OK) return rc;
-      const int Kb = gd->predictor->cfg.num_edge_types;
-      launch_uncertainty_grad(gd->logits, Kb, (int)g->Eh, gd->glogits, gs);
-      return mdx_bondpred_backward(gd->predictor, g, cur->pos, gd->glogits, -gd->scale, gd->delta, gws, gwb, gd->tape,
-                                   gd->tape_bytes, gs);
-    };
-    if (gd->side_stream) {  // enqueue the chain first: it then runs under the denoiser launched below
-      int rc = chain();
-      if (rc != MDX_OK) return rc;
-      HIPCHK(hipEventRecord(g->ev_done, gs));
-    }
-    int rc = sample_step_core(m, g, tb, t_buf, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge,
-                              noise->eps_pos, noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream, jr);
-    if (rc != MDX_OK) return rc;
-    if (gd->side_stream) {
-      HIPCHK(hipStreamWaitEvent(s, g->ev_done, 0));
-    } else {  // in line: the predictor reuses the denoiser's workspace after it
-      rc = chain();
-      if (rc != MDX_OK) return rc;
-    }
-    launch_add_inplace(next->pos, gd->delta, 3 * (int)g->N, s);
-    HIPCHK(hipGetLastError());
-    return MDX_OK;
-  }
-  return sample_step_core(m, g, tb, t_buf, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, noise->eps_pos,
-                          noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream, jr);
+  LCHK(sample_step_core(m, g, tb, t_buf, batch_node, batch_halfedge, cur, next, pred_node, pred_pos, pred_halfedge, noise->eps_pos,
+                        noise->u_node, noise->u_halfedge, node_cls, halfedge_cls, ws, ws_bytes, stream, jr));
+  if (!gd) return MDX_OK;
+  if (side) HIPCHK(hipStreamWaitEvent(s, g->ev_done, 0));
+  else LCHK(chain());
+  launch_add_inplace(next->pos, gd->delta, 3 * (int)g->N, s);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
 }
 
 extern "C" int mdx_sample_step_full(mdx_model_t m, mdx_graph_t g, const mdx_tables* tb, int32_t step, const int64_t* batch_node,
@@ -1476,18 +1478,13 @@ extern "C" int mdx_scaffold_merge(mdx_graph_t g, const mdx_scaffold_tables* tb, 
   if (level < -1 || level >= tb->T) return fail(MDX_ERR_ARG, "level %d outside [-1, %d)", level, tb->T);
   const int N = (int)g->N, Eh = (int)g->Eh;
   if (N == 0) return MDX_OK;
-  if (!sc->node_type || !sc->node_pos || (Eh > 0 && !sc->halfedge_type) || !next->h_node || !next->pos || !next->log_node ||
-      (Eh > 0 && (!next->h_halfedge || !next->log_halfedge)))
+  if (!sc->node_type || !sc->node_pos || (Eh > 0 && !sc->halfedge_type) || !state_complete(next, Eh))
     return fail(MDX_ERR_ARG, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   ScaffoldMergeArgs a{};
   if (level >= 0) {
-    if (!noise || !noise->eps_pos || !noise->u_node || (Eh > 0 && !noise->u_halfedge) || !tb->alphas_bar || !tb->node_q_mats ||
-        (Eh > 0 && !tb->edge_q_mats))
-      return fail(MDX_ERR_ARG, "null noise buffer / table");
-    if (noise->draw >= 0)
-      launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, N, Eh, tb->Kn,
-                          tb->Ke, noise->eps_pos, noise->u_node, noise->u_halfedge, s);
+    if (!tb->alphas_bar || !tb->node_q_mats || (Eh > 0 && !tb->edge_q_mats)) return fail(MDX_ERR_ARG, "null table");
+    LCHK(draw_or_use_noise(g, noise, tb->Kn, tb->Ke, s));
     a.eps = noise->eps_pos; a.u_node = noise->u_node; a.u_half = noise->u_halfedge;
   }
   a.N = N; a.Eh = Eh; a.Kn = tb->Kn; a.Ke = tb->Ke; a.level = level; a.log_off = log_off;
@@ -1511,13 +1508,9 @@ extern "C" int mdx_forward_jump(mdx_graph_t g, const mdx_forward_tables* tb, int
   const int N = (int)g->N, Eh = (int)g->Eh;
   if (N == 0) return MDX_OK;
   if (!tb->pos_coef_a || !tb->pos_coef_s || !tb->node_qT_jump || (Eh > 0 && !tb->edge_qT_jump)) return fail(MDX_ERR_ARG, "incomplete mdx_forward_tables");
-  if (!node_cls_cur || !pos_cur || (Eh > 0 && !halfedge_cls_cur) || !next->h_node || !next->pos || !next->log_node ||
-      (Eh > 0 && (!next->h_halfedge || !next->log_halfedge)) || !noise->eps_pos || !noise->u_node || (Eh > 0 && !noise->u_halfedge))
-    return fail(MDX_ERR_ARG, "null buffer");
+  if (!node_cls_cur || !pos_cur || (Eh > 0 && !halfedge_cls_cur) || !state_complete(next, Eh)) return fail(MDX_ERR_ARG, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (noise->draw >= 0)
-    launch_philox_noise(noise->seed, noise->draw, g->node_graph, g->node_local, g->he_graph, g->he_local, g->mol_ids, N, Eh, tb->Kn,
-                        tb->Ke, noise->eps_pos, noise->u_node, noise->u_halfedge, s);
+  LCHK(draw_or_use_noise(g, noise, tb->Kn, tb->Ke, s));
   ForwardJumpArgs a{};
   a.N = N; a.Eh = Eh; a.Kn = tb->Kn; a.Ke = tb->Ke; a.row = row; a.log_off = log_off;
   a.ca = tb->pos_coef_a; a.cs = tb->pos_coef_s; a.node_qT = tb->node_qT_jump; a.edge_qT = tb->edge_qT_jump;

@@ -32,7 +32,7 @@ GUIDANCE_TYPES = ('entropy', 'uncertainty', 'uncertainty_bond', 'entropy_bond', 
 from .common import MLP, GaussianSmearing
 from .diffusion import get_beta_schedule
 from .graph import NodeEdgeNet, _sig, synth_gates
-from .schedule import check_draw_range, draw_index, pairs, path_windows, resolve_path, resolve_schedule, window_width
+from .schedule import chain_moves, check_draw_range, pairs, resolve_path, resolve_schedule
 from .transition import ContigousTransition, GeneralCategoricalTransition
 
 class MolDiff(Module):
@@ -238,12 +238,9 @@ class MolDiff(Module):
     def sampler(self, n_graphs, batch_node, halfedge_index, batch_halfedge, *, seed=None, mol_ids=None, noise=None,
                 return_traj=True, bond_predictor=None, guidance=None, overlap_guidance=False, scaffold=None, start_step=None,
                 num_steps=None, timesteps=None, resample=None, jump_length=None):
-        """Stateful driver of the reverse chain (``init()`` then ``step(i)`` for i = 0..T-1); ``sample`` wraps it.
-        scaffold / start_step: see ``sample``; with start_step = s the loop iterations are i = T-s..T-1.
-        num_steps / timesteps: see ``sample``; with a schedule of m levels the loop iterations are j = 0..m-1, ``step(j)`` is schedule
-        iteration j and ``set_state(frame=j)`` addresses schedule positions, whether or not start_step is given.
-        resample / jump_length: see ``sample``; the sampler then has a ``path`` (the list of moves) and is driven by ``move(k)`` for
-        k = 0..len(path)-1 instead of ``step``; move k writes trajectory frame k + 1 and ``set_state(frame=k)`` addresses those frames.
+        """Stateful driver of the reverse chain; ``sample`` wraps it and documents the keywords.  ``init()``, then ``advance(k)`` for
+        k = 0..num_moves-1 executes the chain's move table (``schedule.chain_moves``) row by row; ``result()`` returns what ``sample``
+        returns.  ``step(i)`` and ``move(k)`` address the same rows by the index ``sample`` documents for each mode.
         overlap_guidance=True runs the guidance chain on a side stream concurrently with the denoiser forward of the same step
         (same results).  It paid in round 1 (0.7 ms per step, the kernels left tails for each other); with the round-2 kernels
         filling every CU by themselves it costs 0.5 ms (27.6 vs 28.1 ms per step), so in line is the default."""
@@ -279,15 +276,17 @@ class MolDiff(Module):
         scaffold: a ``moldiff_amd.Scaffold`` -- its fixed atoms and half-edges are held on the known molecule (after every step they are
         re-drawn from q(x_k | x_0) of it, and end exactly on it), the free rows are generated around them.  Noise for it comes from the
         same per-molecule streams under draw indices of its own: T + 1 + i after loop iteration i, 2T + 1 for the initial state
-        (`noise` is called with those too).
+        (`noise` is called with those too).  On the sampler, ``step(i)`` is loop iteration i = 0..T-1 (diffusion step T-1-i) and writes
+        trajectory frame i + 1.
         start_step = s (0 < s <= T; needs a scaffold that carries the whole molecule): start from that molecule noised to level s - 1
-        instead of the prior and run diffusion steps s-1 .. 0; the trajectory then has s + 1 frames.  An all-false mask gives an
-        SDEdit-style perturbation of the molecule.
+        instead of the prior and run diffusion steps s-1 .. 0; the trajectory then has s + 1 frames (``step(i)``: i = T-s..T-1).  An
+        all-false mask gives an SDEdit-style perturbation of the molecule.
         num_steps = m (2 <= m <= T, or <= start_step): strided sampling -- run the chain on m uniformly spaced levels T-1 (or
         start_step-1) .. 0 (``schedule.make_schedule``) instead of all of them; timesteps = an explicit strictly decreasing list of
         levels with those ends (one of the two).  Iteration j evaluates the denoiser and the guidance at t = tau_j and draws the state at
         tau_{j+1} from the exact posterior q(x_{tau_{j+1}} | x_{tau_j}, x0_hat) of the same forward process; the trajectory has m + 1
-        frames.  The noise of the move leaving level t is draw T - t under every schedule (a scaffold's: T + (T - t)), so a schedule
+        frames (``step(j)``: schedule iteration j = 0..m-1, and ``set_state(frame=j)`` addresses schedule positions, whether or not
+        start_step is given).  The noise of the move leaving level t is draw T - t under every schedule (a scaffold's: T + (T - t)), so a schedule
         that visits every level is the full chain bit for bit.  The guidance displacement is added once per iteration and is NOT
         rescaled: fewer iterations, less total displacement.  Sample quality at reduced step counts has not been measured.
         resample = R, jump_length = J (both or neither; R >= 1, 1 <= J <= m - 1 with m the number of levels the chain visits): RePaint's
@@ -297,7 +296,8 @@ class MolDiff(Module):
         (``schedule.resampling_path``).  Combines with scaffold, start_step, num_steps / timesteps and guidance (a down-move is the
         unchanged step: denoiser, guidance, merge; an up-move touches neither the prediction nor the guidance).  Cost: R (m - 1) + 1
         denoiser evaluations.  With return_traj=True the trajectory has ONE FRAME PER MOVE + 1, up-moves included: len(path) + 1 =
-        R (m - 1) + 1 + (R - 1) ceil((m - 1) / J) + 1 frames, not m + 1.  Noise: the k-th walk of a block (k = 0..R-1) uses the draw
+        R (m - 1) + 1 + (R - 1) ceil((m - 1) / J) + 1 frames, not m + 1; the sampler then has a ``path`` and is driven by ``move(k)``,
+        k = 0..len(path)-1, instead of ``step`` (move k writes frame k + 1, ``set_state(frame=k)`` addresses those frames).  Noise: the k-th walk of a block (k = 0..R-1) uses the draw
         indices of the plain chain plus k (3T + 2), the up-move arriving at level t that opens it 2T + 2 + t plus the same
         (``schedule.draw_index``); the first walk, hence R = 1, is the plain chain bit for bit.  RePaint's published defaults are J = 10,
         R = 10 on 250 levels -- theirs, for images; nothing has been tuned here and sample quality with resampling is unmeasured.
@@ -306,16 +306,8 @@ class MolDiff(Module):
                           return_traj=return_traj, bond_predictor=bond_predictor, guidance=guidance, scaffold=scaffold,
                           start_step=start_step, num_steps=num_steps, timesteps=timesteps, resample=resample, jump_length=jump_length)
         sm.init()
-        if getattr(sm, 'path', None) is not None:
-            for k in range(len(sm.path)):
-                sm.move(k)
-            return sm.result()
-        if getattr(sm, 'sched', None) is not None:
-            for j in range(len(sm.sched)):
-                sm.step(j)
-            return sm.result()
-        for i in range(0 if start_step is None else self.num_timesteps - start_step, self.num_timesteps):
-            sm.step(i)
+        for k in range(sm.num_moves):
+            sm.advance(k)
         return sm.result()
 
 
@@ -345,8 +337,9 @@ class _Sampler:
         if resample is not None and jump_length is not None:
             check_draw_range(model.num_timesteps, resample)          # before the path is built: its length grows with resample
         self.path = resolve_path(len(self.levels), jump_length, resample)
-        if self.path is not None:
-            self._windows = path_windows(self.path)
+        # the move table: one row per move, executed by _advance; step(i) / move(k) / advance(k) only look a row up
+        self.chain = chain_moves(model.num_timesteps, start_step, self.sched, self.path, scaffold is not None)
+        self.rows = self.chain.rows
         self.guidance = None
         if guidance is not None:
             gui_type, gui_scale = guidance
@@ -378,15 +371,7 @@ class _Sampler:
         f32 = dict(dtype=torch.float32, device=dev)
         N, Eh, Kn, Ke, T = self.N, self.Eh, self.Kn, self.Ke, self.T
         self.eps, self.u_n, self.u_h = torch.empty(N, 3, **f32), torch.empty(N, Kn, **f32), torch.empty(Eh, Ke, **f32)
-        self.i0 = 0 if start_step is None else T - int(start_step)   # first loop iteration (a partial chain starts part-way)
-        nT = T - self.i0 + 1 if return_traj else 2
-        if self.sched is not None:                                   # iterations are schedule positions 0..m-1
-            self.i0 = 0
-            nT = len(self.sched) + 1 if return_traj else 2
-        self._it0 = self.i0                                          # loop iteration of position 0 (step(i) of a down-move on a path)
-        if self.path is not None:                                    # frames are counted in moves, up-moves included
-            self.i0 = 0
-            nT = len(self.path) + 1 if return_traj else 2
+        nT = len(self.rows) + 1 if return_traj else 2                # one frame per move (up-moves included) + the initial state
         self.h_node = torch.zeros(2, N, Kn, **f32)        # one-hot state, frames ping-pong
         self.h_half = torch.zeros(2, Eh, Ke, **f32)
         self.pos_traj = torch.zeros(nT, N, 3, **f32)
@@ -433,9 +418,9 @@ class _Sampler:
             self._levels = (ctypes.c_int32 * len(self.sched))(*self.sched)
             self.jump = _lib.MdxJumpTables(*(_lib.ptr(x) for x in self._jump_t), self._levels, len(self.sched))
         self.fwd = None
-        if self.path is not None and any(mv[0] == 'up' for mv in self.path):
+        if any(r.kind == 'up' for r in self.rows):
             # one row per block (the distinct up-moves), like the jump tables: built once, kept alive next to the struct
-            ups = sorted({mv[1:] for mv in self.path if mv[0] == 'up'})
+            ups = sorted({r.table for r in self.rows if r.kind == 'up'})
             self._fwd_row = {ba: r for r, ba in enumerate(ups)}
             tt, ss = [self.levels[a] for _, a in ups], [self.levels[b] for b, _ in ups]
             self._fwd_t = (*pt.forward_coefs(tt, ss), ntr.jump_mats(tt, ss), etr.jump_mats(tt, ss))
@@ -450,21 +435,39 @@ class _Sampler:
             self.sc = _lib.MdxScaffold(P(nm), P(hm), P(nt), P(ht), P(npos))
             self.sc_all = _lib.MdxScaffold(None, None, P(nt), P(ht), P(npos))   # every row: the start molecule of a partial chain
             self.sc_tabs = _lib.MdxScaffoldTables(P(pt.alphas_bar), P(ntr.q_mats), P(etr.q_mats), Kn, Ke, T)
-        self.start_step = start_step
 
-    def _pframe(self, j):
-        return j - self.i0 if self.return_traj else (j - self.i0) % 2
+    def _pframe(self, frame):
+        return frame if self.return_traj else frame % 2
+
+    def _noise(self, draw, f64=False):
+        """Explicit noise, if the sampler has a `noise` callable: its values for `draw` go into the noise buffers.  Returns the draw
+        index to hand to the library: -1 (use the buffers) after copying, else `draw`.  f64 (the prior draw): float64 uniforms, the
+        reference's rand_like dtype at that point, are kept as they are for mdx_prior_draw (``_u0``)."""
+        if self.noise is None:
+            return draw
+        e, a, b = self.noise(draw)
+        self.eps.copy_(e)
+        if f64:
+            self._u0 = [x.to(self.dev).contiguous() if x.dtype == torch.float64 else u.copy_(x) for x, u in ((a, self.u_n), (b, self.u_h))]
+        else:
+            self.u_n.copy_(a); self.u_h.copy_(b)
+        return -1
+
+    def _step_noise(self, draw):
+        P = _lib.ptr
+        return _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
+
+    def _state(self, n, ln, pn):
+        """The state in one-hot frame n, log-prob frame ln and position frame pn, as the library takes it."""
+        P = _lib.ptr
+        return _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
 
     def _merge(self, sc, level, draw, n, ln, pn):
         """Overwrite the fixed rows of state frames (n, ln, pn) with q(x_level | x_0) of the scaffold (level -1: x_0 itself, and the
-        prediction's rows with it) -- one library call, at most two launches (noise, merge)."""
+        prediction's rows with it; no noise) -- one library call, at most two launches (noise, merge)."""
         P = _lib.ptr
-        if level >= 0 and self.noise is not None:
-            e, a, b = self.noise(draw)
-            self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
-            draw = -1
-        nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
-        nz = _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
+        nz = self._step_noise(self._noise(draw) if level >= 0 else draw)
+        nxt = self._state(n, ln, pn)
         _lib.check(_lib.lib().mdx_scaffold_merge(self.g.h, ctypes.byref(self.sc_tabs), level, ctypes.byref(sc), ctypes.byref(nz),
                                                  ctypes.byref(nxt), _lib.log_eps32(), P(self.node_ids[pn]), P(self.half_ids[pn]),
                                                  P(self.preds[0]), P(self.preds[1]), P(self.preds[2]), _lib.stream()))
@@ -472,109 +475,94 @@ class _Sampler:
     @torch.no_grad()
     def init(self):
         """Prior draw (models/model.py:244-263): classes ~ init_prob by Gumbel-max, positions ~ N(0, I).  With a scaffold its fixed
-        rows are then merged in at level T - 1; a partial chain starts from the whole scaffold molecule noised to level start_step - 1."""
-        m, L, dev = self.m, _lib.lib(), self.dev
-        if self.start_step is not None:
-            self.cur, self.lcur, self.pcur = 0, 0, 0
-            self._merge(self.sc_all, self.start_step - 1, 2 * self.T + 1, 0, 0, 0)
+        rows are then merged in at the chain's top level; a partial chain starts from the whole scaffold molecule noised to that level
+        (start_step - 1)."""
+        m, L, chain = self.m, _lib.lib(), self.chain
+        self.cur, self.lcur, self.pcur = 0, 0, 0
+        if chain.prior_draw is None:
+            self._merge(self.sc_all, self.levels[0], chain.merge_draw, 0, 0, 0)
             return
-        u_n, u_h = self.u_n, self.u_h
-        if self.noise is not None:
-            e, a, b = self.noise(0)
-            self.eps.copy_(e)
-            u_n = a.to(dev).contiguous() if a.dtype == torch.float64 else self.u_n.copy_(a)
-            u_h = b.to(dev).contiguous() if b.dtype == torch.float64 else self.u_h.copy_(b)
-        else:
-            _lib.check(L.mdx_noise(self.g.h, ctypes.c_uint64(self.seed), 0, self.Kn, self.Ke, _lib.ptr(self.eps),
+        self._u0 = [self.u_n, self.u_h]
+        draw = self._noise(chain.prior_draw, f64=True)
+        if draw >= 0:
+            _lib.check(L.mdx_noise(self.g.h, ctypes.c_uint64(self.seed), draw, self.Kn, self.Ke, _lib.ptr(self.eps),
                                    _lib.ptr(self.u_n), _lib.ptr(self.u_h), _lib.stream()))
         # the prior draw is the one place where the reference computes in float64 (models/transition.py:331-339: its logits are a
         # float64 numpy array moved to the device): mdx_prior_draw evaluates the Gumbel-max there in float64 too.  Explicit noise
         # may be float64 (the reference's rand_like dtype at this point) or float32.
-        for tr, n, u, oh, ids, logs in ((m.node_transition, self.N, u_n, self.h_node, self.node_ids, self.log_node),
-                                        (m.edge_transition, self.Eh, u_h, self.h_half, self.half_ids, self.log_half)):
+        for tr, n, u, oh, ids, logs in ((m.node_transition, self.N, self._u0[0], self.h_node, self.node_ids, self.log_node),
+                                        (m.edge_transition, self.Eh, self._u0[1], self.h_half, self.half_ids, self.log_half)):
             _lib.prior_draw(tr.init_prob, u, n, onehot=oh[0], log_onehot=logs[0], cls8=ids[0])
         self.pos_traj[0].copy_(self.eps)
-        self.cur, self.lcur, self.pcur = 0, 0, 0
         if self.sc is not None:
-            self._merge(self.sc, self.T - 1, 2 * self.T + 1, 0, 0, 0)
+            self._merge(self.sc, self.levels[0], chain.merge_draw, 0, 0, 0)
+
+    @property
+    def num_moves(self):
+        return len(self.rows)
+
+    @torch.no_grad()
+    def advance(self, k):
+        """Move k of the chain, k = 0..num_moves-1, whatever its mode: row k of the move table, written to trajectory frame k + 1."""
+        if not 0 <= k < len(self.rows):
+            raise IndexError(f'move {k} outside [0, {len(self.rows)})')
+        self._advance(self.rows[k])
 
     @torch.no_grad()
     def step(self, i):
-        """Loop iteration i (see ``_down``); the new state is trajectory frame i + 1.  A sampler with a path is driven by ``move``."""
+        """Loop iteration i of a chain without a resampling path: a down-move (see ``_advance``).  i counts schedule positions under a
+        schedule and diffusion steps from T - 1 without one (an unscheduled partial chain starts at i = T - start_step); the new state
+        is the trajectory frame after the one the iteration read.  A sampler with a path is driven by ``move``."""
         if self.path is not None:
             raise RuntimeError('this sampler walks a resampling path: drive it with move(k), k = 0..len(path)-1')
-        self._down(i, self._pframe(i + 1), 0)
+        first = self.rows[0].step
+        if not first <= i < first + len(self.rows):
+            raise IndexError(f'{"schedule" if self.sched is not None else "loop"} iteration {i} outside [{first}, {first + len(self.rows)})')
+        self._advance(self.rows[i - first])
 
     @torch.no_grad()
     def move(self, k):
         """Move k of the resampling path, written to trajectory frame k + 1: a down-move ('down', p) is loop iteration p of the chain
-        (``_down``: denoiser, guidance, merge -- unchanged) with the draw indices of its walk's window; an up-move ('up', b, a) is one
-        call of ``mdx_forward_jump`` from level levels[b] to levels[a] (at most two launches: noise, jump).  The up-move reads the
-        current state's class ids and positions only; predictions, the time tensor and the guidance workspace are left alone."""
+        with the draw indices of its walk's window, an up-move ('up', b, a) the forward diffusion from level levels[b] to levels[a]."""
         if self.path is None:
             raise RuntimeError('this sampler has no resampling path (resample= / jump_length=): drive it with step(i)')
-        if not 0 <= k < len(self.path):
-            raise IndexError(f'move {k} outside [0, {len(self.path)})')
-        mv, off = self.path[k], self._windows[k] * window_width(self.T)
-        pn = self._pframe(k + 1)
-        if mv[0] == 'down':
-            self._down(self._it0 + mv[1], pn, off)
-            return
-        draw = draw_index(self.T, 'up', self.levels[mv[2]], self._windows[k])
-        if self.noise is not None:
-            e, a, b = self.noise(draw)
-            self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
-            draw = -1
-        n, ln, pc = 1 - self.cur, 1 - self.lcur, self.pcur
-        P = _lib.ptr
-        nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
-        nz = _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
-        _lib.check(_lib.lib().mdx_forward_jump(self.g.h, ctypes.byref(self.fwd), self._fwd_row[mv[1:]], P(self.node_ids[pc]),
-                                               P(self.half_ids[pc]), P(self.pos_traj[pc]), ctypes.byref(nz), ctypes.byref(nxt),
-                                               _lib.log_eps32(), P(self.node_ids[pn]), P(self.half_ids[pn]), _lib.stream()))
-        self.cur, self.lcur, self.pcur = n, ln, pn
+        self.advance(k)
 
-    def _down(self, i, pn, off):
-        """Loop iteration i written to position / id frame pn, with `off` added to its draw indices (a resampling window; 0 otherwise).
-        Loop iteration i (diffusion step T-1-i), models/model.py:272-372: one library call; with a scaffold a second one merges
-        its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold").  With a schedule: schedule iteration i,
-        one call of ``mdx_sample_jump_full`` instead (same launches, the transition reads the jump tables' row i)."""
-        L, T = _lib.lib(), self.T
-        if self.sched is None:
-            t, below = T - 1 - i, T - 2 - i
-        else:
-            # schedule iteration i: level tau_i -> tau_{i+1} (-1 after the last).  Noise is keyed by the level left, not by the
-            # iteration: draw T - t is what the full chain uses at level t (i + 1 with t = T - 1 - i), the merge's T + (T - t) likewise
-            if not 0 <= i < len(self.sched):
-                raise IndexError(f'schedule iteration {i} outside [0, {len(self.sched)})')
-            t, below = self.sched[i], (self.sched[i + 1] if i + 1 < len(self.sched) else -1)
-        draw = T - t + off
-        if self.noise is not None:
-            e, a, b = self.noise(draw)
-            self.eps.copy_(e); self.u_n.copy_(a); self.u_h.copy_(b)
-            draw = -1
-        c, n = self.cur, 1 - self.cur
-        lc, ln = self.lcur, 1 - self.lcur
-        pc = self.pcur
-        P = _lib.ptr
-        cur = _lib.MdxState(P(self.h_node[c]), P(self.pos_traj[pc]), P(self.h_half[c]), P(self.log_node[lc]), P(self.log_half[lc]))
-        nxt = _lib.MdxState(P(self.h_node[n]), P(self.pos_traj[pn]), P(self.h_half[n]), P(self.log_node[ln]), P(self.log_half[ln]))
-        nz = _lib.MdxStepNoise(self.seed, draw, P(self.eps), P(self.u_n), P(self.u_h))
+    def _advance(self, row):
+        """Execute one row of the move table: the new state goes to the other one-hot / log-prob frame and to position / id frame
+        row.frame.
+        Down-move (diffusion step row.level -> row.arrive), models/model.py:272-372: one library call (``mdx_sample_step_full``; with a
+        schedule ``mdx_sample_jump_full``: same launches, the transition reads the jump tables' row row.table); with a scaffold a
+        second one merges its fixed rows into the new state (after the guidance: see DESIGN.md "scaffold").
+        Up-move: one call of ``mdx_forward_jump`` (at most two launches: noise, jump).  It reads the current state's class ids and
+        positions only; predictions, the time tensor and the guidance workspace are left alone."""
+        L, P = _lib.lib(), _lib.ptr
+        pn = self._pframe(row.frame)
+        nz = self._step_noise(self._noise(row.draw))
+        n, ln, pc = 1 - self.cur, 1 - self.lcur, self.pcur
+        nxt = self._state(n, ln, pn)
+        if row.kind == 'up':
+            _lib.check(L.mdx_forward_jump(self.g.h, ctypes.byref(self.fwd), self._fwd_row[row.table], P(self.node_ids[pc]),
+                                          P(self.half_ids[pc]), P(self.pos_traj[pc]), ctypes.byref(nz), ctypes.byref(nxt),
+                                          _lib.log_eps32(), P(self.node_ids[pn]), P(self.half_ids[pn]), _lib.stream()))
+            self.cur, self.lcur, self.pcur = n, ln, pn
+            return
+        cur = self._state(self.cur, self.lcur, pc)
         ws, nb = self.g.workspace(self.dev)
         self.eng.use_matrix_path(self._path)
         if self._bp_path is not None:
             self.bp_eng.use_matrix_path(self._bp_path)
-        tail = (t, P(self.bn), P(self.bh), ctypes.byref(cur), ctypes.byref(nxt), P(self.preds[0]), P(self.preds[1]), P(self.preds[2]),
-                ctypes.byref(nz), P(self.t), P(self.node_ids[pn]), P(self.half_ids[pn]),
+        tail = (row.level, P(self.bn), P(self.bh), ctypes.byref(cur), ctypes.byref(nxt), P(self.preds[0]), P(self.preds[1]),
+                P(self.preds[2]), ctypes.byref(nz), P(self.t), P(self.node_ids[pn]), P(self.half_ids[pn]),
                 ctypes.byref(self.gd) if self.gd is not None else None, ws, nb, _lib.stream())
         if self.jump is None:
             _lib.check(L.mdx_sample_step_full(self.eng.h, self.g.h, ctypes.byref(self.tables), *tail))
         else:
-            _lib.check(L.mdx_sample_jump_full(self.eng.h, self.g.h, ctypes.byref(self.tables), ctypes.byref(self.jump), i, *tail))
+            _lib.check(L.mdx_sample_jump_full(self.eng.h, self.g.h, ctypes.byref(self.tables), ctypes.byref(self.jump), row.table, *tail))
         if self.guidance is not None and self.gd is None:  # the seven objectives that are torch expressions on the logits
-            self._guide(self.h_node[c], self.pos_traj[pc], self.pos_traj[pn], self.h_half[n], self.log_half[ln])
+            self._guide(self.h_node[self.cur], self.pos_traj[pc], self.pos_traj[pn], self.h_half[n], self.log_half[ln])
         if self.sc is not None:
-            self._merge(self.sc, below, T + (T - t) + off, n, ln, pn)
+            self._merge(self.sc, row.arrive, row.merge_draw, n, ln, pn)
         self.cur, self.lcur, self.pcur = n, ln, pn
 
     def _guide(self, h_node, pos, pos_prev, h_half_prev, log_half):
@@ -618,8 +606,9 @@ class _Sampler:
                 'log_node': self.log_node[self.lcur], 'log_halfedge': self.log_half[self.lcur]}
 
     def set_state(self, h_node, pos, h_halfedge, log_node, log_halfedge, frame=0):
-        """Teacher-forcing hook for the parity tests: the state becomes trajectory frame `frame`."""
-        pf = self._pframe(frame)
+        """Teacher-forcing hook for the parity tests: the state becomes the one that ``step(frame)`` -- ``move(frame)`` on a path --
+        reads."""
+        pf = self._pframe(frame - (self.rows[0].step if self.path is None else 0))
         self.h_node[0].copy_(h_node); self.pos_traj[pf].copy_(pos); self.h_half[0].copy_(h_halfedge)
         self.node_ids[pf].copy_(h_node.argmax(-1)); self.half_ids[pf].copy_(h_halfedge.argmax(-1))
         self.log_node[0].copy_(log_node); self.log_half[0].copy_(log_halfedge)
@@ -703,6 +692,14 @@ class _ContinuousSampler:
         self.half_traj[n].copy_(m.edge_transition.get_prev_from_recon(h_half, preds['pred_halfedge'], t, self.bh, eps=b))
         self.preds = (preds['pred_node'], preds['pred_pos'], preds['pred_halfedge'])
         self.cur = n
+
+    @property
+    def num_moves(self):
+        return self.T
+
+    def advance(self, k):
+        """Move k of the chain: it only walks down, so move k is loop iteration k."""
+        self.step(k)
 
     def state(self):
         return {'h_node': self.node_traj[self.cur], 'pos': self.pos_traj[self.cur], 'h_halfedge': self.half_traj[self.cur]}

@@ -6,10 +6,12 @@ with t = tau_j and writes the state at level tau_{j+1}; the last iteration (leve
 reference has no such thing (its loop visits every level): an addition, like scaffolds.  Host code, integers only.
 
 Resampling (RePaint's loop around replacement conditioning, another addition) makes the walk non-monotone: ``resampling_path`` lists the
-moves -- down-moves between neighbouring schedule POSITIONS and up-moves back to the start of a block -- and ``draw_index`` /
-``path_draws`` say which noise draw each of them uses.
+moves -- down-moves between neighbouring schedule POSITIONS and up-moves back to the start of a block -- and ``draw_index`` says
+which noise draw each of them uses.  ``chain_moves`` puts all of it into one table: every chain, plain, partial, strided or resampled,
+is a list of ``Move`` rows that the sampler executes one after the other.
 """
 import numbers
+from collections import namedtuple
 
 
 def make_schedule(top, num_steps):
@@ -151,16 +153,55 @@ def check_draw_range(T, resample):
         raise ValueError(f'resample {resample} x {window_width(T)} draw indices per window does not fit the 31-bit draw index')
 
 
-def path_draws(path, levels, T, scaffold=False, partial=False):
-    """The draw indices a chain over `path` asks for, in order.  levels[p]: the level of position p.  scaffold: a merge follows every
-    down-move but the last and the prior draw; partial (start_step): the chain starts from the initial merge alone."""
-    out = [draw_index(T, 'init_merge')] if partial else [draw_index(T, 'prior')] + ([draw_index(T, 'init_merge')] if scaffold else [])
-    for mv, w in zip(path, path_windows(path)):
+Move = namedtuple('Move', 'kind pos pos_to level arrive table window draw merge_draw frame step')
+Move.__doc__ = """One row of a chain's move table.  kind: 'down' | 'up'; pos -> pos_to: the schedule positions left and arrived at (a
+down-move: p -> p + 1); level -> arrive: their levels (arrive = -1 below level 0); table: the jump-table row of a down-move (its
+position), the forward-table key (b, a) of an up-move; window: the noise window; draw: the draw index of the move; merge_draw: that
+of the scaffold merge after a down-move (None without a scaffold and after an up-move; the merge at arrive = -1 copies x_0 and
+consumes no noise); frame: the trajectory frame written; step: the loop iteration i of ``step(i)`` (None for an up-move)."""
+
+Chain = namedtuple('Chain', 'rows prior_draw merge_draw')
+Chain.__doc__ = """rows: the moves in order; prior_draw / merge_draw: the draw indices of the initial state -- the prior draw (None for a
+partial chain, which starts from the scaffold molecule) and the merge of the scaffold into it (None without a scaffold)."""
+
+
+def _rows(T, levels, path, scaffold, step0):
+    """The rows of `path` over positions of levels `levels`; step0: the loop iteration of position 0."""
+    m, rows = len(levels), []
+    for k, (mv, w) in enumerate(zip(path, path_windows(path))):
         if mv[0] == 'up':
-            out.append(draw_index(T, 'up', levels[mv[2]], w))
+            b, a = mv[1:]
+            rows.append(Move('up', b, a, levels[b], levels[a], (b, a), w, draw_index(T, 'up', levels[a], w), None, k + 1, None))
         else:
-            t = levels[mv[1]]
-            out.append(draw_index(T, 'down', t, w))
-            if scaffold and mv[1] + 1 < len(levels):
-                out.append(draw_index(T, 'merge', t, w))
+            p, t = mv[1], levels[mv[1]]
+            rows.append(Move('down', p, p + 1, t, levels[p + 1] if p + 1 < m else -1, p, w, draw_index(T, 'down', t, w),
+                             draw_index(T, 'merge', t, w) if scaffold else None, k + 1, step0 + p))
+    return rows
+
+
+def chain_moves(T, start_step=None, schedule=None, path=None, scaffold=False):
+    """The whole chain as a ``Chain`` of ``Move`` rows.  schedule: the levels of ``resolve_schedule`` (None: every level from the top,
+    T - 1 or start_step - 1, down to 0); path: the moves of ``resolve_path`` over their positions (None: the down-moves 0..m-1, the
+    plain chain, window 0).  Loop iterations count schedule positions under a schedule, and levels from T - 1 without one: ``step(i)``
+    of an unscheduled partial chain takes i = T - start_step .. T - 1.  This and ``draw_index`` are all that know how a chain's noise
+    is laid out."""
+    T = int(T)
+    top = (T if start_step is None else int(start_step)) - 1
+    levels = list(schedule) if schedule is not None else list(range(top, -1, -1))
+    if path is None:
+        path = [('down', p) for p in range(len(levels))]
+    rows = _rows(T, levels, path, scaffold, 0 if schedule is not None else T - 1 - top)
+    init_merge = draw_index(T, 'init_merge') if scaffold or start_step is not None else None
+    return Chain(rows, None if start_step is not None else draw_index(T, 'prior'), init_merge)
+
+
+def path_draws(path, levels, T, scaffold=False, partial=False):
+    """The draw indices a chain over `path` asks for, in order: a projection of its move table.  levels[p]: the level of position p.
+    scaffold: a merge follows every down-move and the prior draw (the one below level 0 asks for no noise); partial (start_step): the
+    chain starts from the initial merge alone."""
+    out = [draw_index(T, 'init_merge')] if partial else [draw_index(T, 'prior')] + ([draw_index(T, 'init_merge')] if scaffold else [])
+    for r in _rows(T, levels, path, scaffold, 0):
+        out.append(r.draw)
+        if r.merge_draw is not None and r.arrive >= 0:
+            out.append(r.merge_draw)
     return out

@@ -216,6 +216,38 @@ def test_resample_one_on_the_full_chain_and_a_partial_chain():
         _same(_snapshot(a, 9), _snapshot(b, 9))
 
 
+# ---- 3b. one loop for every mode -------------------------------------------------------------------------------------------------------------
+
+SIZES_SMALL = [3, 9, 5, 7, 4]        # 28 atoms, 73 half-edges: several graphs per batch, fixed and free rows in every molecule
+
+
+@pytest.mark.parametrize('mode', ['plain', 'partial', 'strided', 'resampled'])
+def test_sample_through_the_move_table_equals_the_modes_own_driver(mode):
+    """``sample`` runs ``advance(k)`` over the move table whatever the mode; every mode's public driver -- ``step(i)`` over its
+    documented index range, ``move(k)`` on a path -- executes the same rows: traj and pred agree bit for bit."""
+    m = _model()
+    (bn, hei, bh), sc = _random_scaffold(SIZES_SMALL, 9)
+    (_, _, _), whole = _random_scaffold(SIZES_SMALL, 9, all_rows=True)
+    kw, drive = {
+        'plain': (dict(), lambda sm: [sm.step(i) for i in range(T)]),
+        'partial': (dict(scaffold=whole, start_step=24), lambda sm: [sm.step(i) for i in range(T - 24, T)]),
+        'strided': (dict(scaffold=sc, num_steps=24), lambda sm: [sm.step(j) for j in range(24)]),
+        'resampled': (dict(scaffold=sc, num_steps=13, jump_length=4, resample=3), lambda sm: [sm.move(k) for k in range(len(sm.path))]),
+    }[mode]
+    out = m.sample(len(SIZES_SMALL), bn, hei, bh, seed=23, **kw)
+    sm = m.sampler(len(SIZES_SMALL), bn, hei, bh, seed=23, **kw)
+    frames = {'plain': T, 'partial': 24, 'strided': 24, 'resampled': 3 * 12 + 1 + 2 * 3}[mode] + 1
+    assert sm.num_moves == frames - 1 and (sm.path is not None) == (mode == 'resampled')
+    sm.init()
+    drive(sm)
+    res = sm.result()
+    assert [x.shape[0] for x in out['traj']] == [frames] * 3
+    assert torch.equal(res['traj'][1], out['traj'][1]) and bool(torch.isfinite(out['traj'][1]).all())
+    assert torch.equal(res['traj'][0].dense(), out['traj'][0].dense()) and torch.equal(res['traj'][2].dense(), out['traj'][2].dense())
+    assert all(torch.equal(a, b) for a, b in zip(res['pred'], out['pred']))
+    assert not torch.equal(out['traj'][1][0], out['traj'][1][-1])                      # and the chain did move
+
+
 # ---- 4. the path is what runs -------------------------------------------------------------------------------------------------------------
 
 def test_the_path_its_draw_indices_and_its_frames_are_what_runs():

@@ -47,16 +47,16 @@ def main():
     sm = model.sampler(args.batch, bn, hei, bh, seed=1, return_traj=False, scaffold=sc, num_steps=100, jump_length=10, resample=2)
     sm.init()
     P, L = _lib.ptr, _lib.lib()
-    nxt = _lib.MdxState(P(sm.h_node[1]), P(sm.pos_traj[1]), P(sm.h_half[1]), P(sm.log_node[1]), P(sm.log_half[1]))
+    nxt = sm._state(1, 1, 1)
 
     def jump(draw):
-        nz = _lib.MdxStepNoise(sm.seed, draw, P(sm.eps), P(sm.u_n), P(sm.u_h))
+        nz = sm._step_noise(draw)
         _lib.check(L.mdx_forward_jump(sm.g.h, ctypes.byref(sm.fwd), 0, P(sm.node_ids[0]), P(sm.half_ids[0]), P(sm.pos_traj[0]),
                                       ctypes.byref(nz), ctypes.byref(nxt), _lib.log_eps32(), P(sm.node_ids[1]), P(sm.half_ids[1]),
                                       _lib.stream()))
 
     def merge(draw):
-        nz = _lib.MdxStepNoise(sm.seed, draw, P(sm.eps), P(sm.u_n), P(sm.u_h))
+        nz = sm._step_noise(draw)
         _lib.check(L.mdx_scaffold_merge(sm.g.h, ctypes.byref(sm.sc_tabs), 500, ctypes.byref(sm.sc), ctypes.byref(nz), ctypes.byref(nxt),
                                         _lib.log_eps32(), P(sm.node_ids[1]), P(sm.half_ids[1]), None, None, None, _lib.stream()))
 
