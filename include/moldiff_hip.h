@@ -396,6 +396,46 @@ int mdx_mol_keep_component(mdx_graph_t g, const int32_t* select, const int32_t* 
                            float* atom_prob, float* atom_pos, int32_t* n_atoms, int32_t* bond_type, float* bond_prob,
                            int32_t* bond_index, int32_t* n_bonds, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- local 3D geometry statistics of decoded molecules ------------------------------------------------------------
+ * Bond lengths, bond angles and dihedral angles histogrammed per bond pattern -- what the reference's Local3D
+ * (utils/evaluation.py:156-329) collects per SMARTS such as c:c, [#6]-[#7]-[#6] or c:c:c:c -- without RDKit and of the molecule AS
+ * DECODED (the reference measures RDKit's reconstruction).  One workgroup per molecule over compact arrays: molecule m has its atoms
+ * at atom_ptr[m] .. + n_atoms[m] of atom_type (class index) / atom_pos, and its bonds at bond_ptr[m] .. + n_bonds[m] of bond_type
+ * (1 .. num_bond_types) / bond_index (row 0 at bond_index, row 1 at bond_index + Eh_stride; molecule-local atom indices, one
+ * direction per bond).  The four per-molecule arrays are device int32, so the entry serves mdx_decode_output's layout (molecules at
+ * their original offsets: atom_ptr / bond_ptr = the batch's node / half-edge offsets) and a densely packed list alike.  N_cap and
+ * Eh_stride are the extents of the atom and bond arrays; a molecule reaching past them is skipped.  A bond whose index lies outside
+ * its molecule, or with i = j, is ignored.
+ * Items: length = a bond; angle = a centre with two bonds to neighbours a < c; dihedral = a path a-b-c-d along three bonds with four
+ *   distinct atoms.  A path and its reverse are ONE item, counted once (RDKit's uniquified match of a linear pattern).
+ * Patterns (HOST): P rows of 7 int32 (e0, b01, e1, b12, e2, b23, e3), class indices and bond type ids; kind_ptr[4] (host) = rows of
+ *   lengths | angles | dihedrals; a length row uses 3 fields, an angle row 5.  An item belongs to the row whose chain equals the
+ *   item's chain or its reverse; no wildcards, so at most one row.  Rows are canonicalised here; two rows that are equal or each
+ *   other's reverse are MDX_ERR_ARG, more than 64 rows of one kind MDX_ERR_UNSUPPORTED.
+ * Values, fp32, every operation rounded on its own (no contraction), from coordinate differences:
+ *   length |i - j|; angle at b atan2f(|u x v|, u.v) * 180/pi with u = a - b, v = c - b; dihedral atan2f((n1 x n2).b2 / |b2|, n1.n2)
+ *   * 180/pi with b1 = b - a, b2 = c - b, b3 = d - c, n1 = b1 x b2, n2 = b2 x b3: IUPAC sign, in [-180, 180]; a = (1,0,0),
+ *   b = (0,0,0), c = (0,0,1), d = (0,1,1) gives +90.  Coincident or collinear atoms give whatever atan2f gives.
+ * Bins (HOST): bin_range = 3 x (lo, hi), bin_count = 3 x n, for lengths, angles, dihedrals.  Bin k holds lo + k w <= v < lo + (k+1) w,
+ *   w = (hi - lo) / n, the last bin includes hi (numpy.histogram's rule).  Which side a value within fp32 rounding of an edge falls
+ *   on is NOT specified.  A value outside [lo, hi], NaN included, adds 1 to outside[row] and nothing to hist.
+ * Outputs (device int64): hist = for each kind in turn (rows of the kind) x n_kind bins, and outside (P), are ADDED TO, so calls
+ *   over consecutive batches accumulate; n_items (3, B) is written: every enumerated item of the kind in molecule m, matched or not.
+ *   select (B int32, device, or NULL): a molecule with select[m] == 0 contributes nothing and its n_items are 0.
+ *   All results are integer counts: bit-reproducible and independent of a molecule's place in the batch.
+ * Storage: a molecule of at most 512 atoms and 2,048 bonds keeps its neighbour lists in LDS, a larger one in ws.  Histograms of at
+ *   most 8,192 bins in all are counted per workgroup in LDS and flushed with one atomic add per non-zero bin; larger ones are added
+ *   to in global memory item by item.
+ * ws: mdx_mol_local3d_ws_bytes(N_cap, Eh_stride) = 4 * (max(N_cap, 1) + 2 * max(Eh_stride, 1)) bytes; smaller is MDX_ERR_ARG.
+ * MDX_ERR_ARG, outputs untouched: a null operand (select excepted), B < 0, n <= 0, hi <= lo, a pattern field out of range,
+ * num_element > 255, num_bond_types > 254.  MDX_ERR_UNSUPPORTED: N_cap > 2^24. */
+size_t mdx_mol_local3d_ws_bytes(int64_t N_cap, int64_t Eh_stride);
+int mdx_mol_local3d(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                    const int32_t* atom_type, const float* atom_pos, int64_t N_cap, const int32_t* bond_type,
+                    const int32_t* bond_index, int64_t Eh_stride, int32_t num_element, int32_t num_bond_types, const int32_t* select,
+                    const int32_t* patterns, const int32_t* kind_ptr, const float* bin_range, const int32_t* bin_count, int64_t* hist,
+                    int64_t* outside, int64_t* n_items, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

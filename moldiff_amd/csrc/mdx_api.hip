@@ -1903,6 +1903,40 @@ extern "C" int mdx_mol_keep_component(mdx_graph_t g, const int32_t* select, cons
   return MDX_OK;
 }
 
+extern "C" size_t mdx_mol_local3d_ws_bytes(int64_t N_cap, int64_t Eh_stride) { return local3d_ws_bytes(N_cap, Eh_stride); }
+
+extern "C" int mdx_mol_local3d(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms,
+                               const int32_t* n_bonds, const int32_t* atom_type, const float* atom_pos, int64_t N_cap,
+                               const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride, int32_t num_element,
+                               int32_t num_bond_types, const int32_t* select, const int32_t* patterns, const int32_t* kind_ptr,
+                               const float* bin_range, const int32_t* bin_count, int64_t* hist, int64_t* outside, int64_t* n_items,
+                               void* ws, size_t ws_bytes, void* stream) {
+  if (!atom_ptr || !bond_ptr || !n_atoms || !n_bonds || !atom_type || !atom_pos || !bond_type || !bond_index || !patterns ||
+      !kind_ptr || !bin_range || !bin_count || !hist || !outside || !n_items)
+    return fail(MDX_ERR_ARG, "null argument");
+  if (B < 0 || N_cap < 0 || Eh_stride < 0) return fail(MDX_ERR_ARG, "negative size");
+  if (N_cap > L3_MAX_ATOMS) return fail(MDX_ERR_UNSUPPORTED, "more than 2^24 atoms in one call");
+  Local3DArgs a{};
+  const char* why = "";
+  if (int rc = local3d_prepare(&a, patterns, kind_ptr, bin_range, bin_count, num_element, num_bond_types, &why)) return fail(rc, "%s", why);
+  const size_t need = local3d_ws_bytes(N_cap, Eh_stride);
+  if (!ws || ws_bytes < need) return fail(MDX_ERR_ARG, "workspace too small: need %zu bytes", need);
+  if (reinterpret_cast<uintptr_t>(ws) & 3) return fail(MDX_ERR_ARG, "workspace must be 4-byte aligned");
+  a.B = B;
+  a.atom_ptr = atom_ptr, a.bond_ptr = bond_ptr, a.n_atoms = n_atoms, a.n_bonds = n_bonds;
+  a.atom_type = atom_type, a.atom_pos = atom_pos;
+  a.bond_type = bond_type, a.bond_i = bond_index, a.bond_j = bond_index + Eh_stride;
+  a.select = select;
+  a.N_cap = N_cap, a.E_cap = Eh_stride;
+  a.num_element = num_element, a.num_bond_types = num_bond_types;
+  a.hist = reinterpret_cast<unsigned long long*>(hist), a.outside = reinterpret_cast<unsigned long long*>(outside);
+  a.n_items = reinterpret_cast<long long*>(n_items);
+  a.ws_cur = reinterpret_cast<int*>(ws), a.ws_adj = a.ws_cur + std::max<int64_t>(N_cap, 1);
+  launch_mol_local3d(a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MDX_OK;
+}
+
 extern "C" int mdx_guidance_uncertainty_grad(const float* logits, int32_t K, int64_t n, float* glogits, void* stream) {
   if (K < 1 || n < 0 || (n > 0 && (!logits || !glogits))) return fail(MDX_ERR_ARG, "bad argument");
   launch_uncertainty_grad(logits, K, (int)n, glogits, (hipStream_t)stream);

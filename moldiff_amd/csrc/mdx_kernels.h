@@ -391,6 +391,8 @@ struct MolKeepArgs {  // mdx_molcheck.hip: molecules with select != 0 keep the a
   int *bond_index, *n_bonds;
 };
 void launch_mol_keep_component(const MolKeepArgs& a, hipStream_t s);
+#include "mdx_local3d_args.h"  // Local3DArgs and its host-side preparation: plain C++, also built on its own by tools/local3d_host_check.cpp
+void launch_mol_local3d(const Local3DArgs& a, hipStream_t s);
 // the same three sums after an EA_AGG edge kernel A: aggr / SR combine each node's partial rows pbase[v] .. pbase[v+1] of P / PR
 // in order, SL is still the indexed sum over FL
 void launch_seg_reduce_block2(const float* P, const float* PR, const float* FL, const int* pbase, const int* col_ptr,

@@ -168,6 +168,37 @@ class FeaturizeMol(object):
             mols[m]['component'], mols[m]['valence'] = comp, val
         return mols, report
 
+    def local3d_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, spec, graph=None, *, select=None, out=None):
+        """``decode_batch``'s device part + the local 3D geometry statistics of every decoded molecule (``mdx_mol_local3d``): bond
+        lengths, bond angles and dihedral angles histogrammed per pattern of `spec` (a ``local3d.Local3DSpec``).  Nothing is copied
+        to the host and nothing synchronises.  select: (n_graphs) device tensor, molecules with 0 are left out; out: a
+        ``Local3DStats`` with device arrays (``local3d.device_stats``) to add into.  -> Local3DStats with device arrays.
+        These are the molecules AS DECODED, not RDKit's reconstruction of them: see moldiff_amd/local3d.py.  Like ``decode_batch``,
+        it needs a batch with at least one half-edge (``mdx_decode_output`` refuses an empty prediction array)."""
+        from . import local3d
+        if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
+            raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        dev = d['atom_type'].device
+        if out is None:
+            out = local3d.device_stats(spec, dev)
+        elif out.spec != spec:
+            raise ValueError('`out` was made for another spec')
+        B = graph.B
+        if B == 0:
+            return out
+        ptrs = getattr(graph, '_mol_ptr', None)
+        if ptrs is None or ptrs.device != dev:   # first atom / first half-edge of every molecule, formed on the device
+            cnt = torch.zeros(2, B, dtype=torch.int64, device=dev)
+            cnt[0].scatter_add_(0, batch_node.to(dev, torch.int64), torch.ones(graph.N, dtype=torch.int64, device=dev))
+            cnt[1].scatter_add_(0, batch_halfedge.to(dev, torch.int64), torch.ones(graph.Eh, dtype=torch.int64, device=dev))
+            ptrs = graph._mol_ptr = (cnt.cumsum(1) - cnt).to(torch.int32).contiguous()
+        if select is not None:
+            select = select.to(dev, torch.int32).contiguous()
+        return local3d.launch(spec, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], d['atom_pos'], max(graph.N, 1),
+                              d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), out, select=select,
+                              ws=graph.workspace(dev))
+
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):
     """Split packed numpy outputs {'pred': [...], 'traj': [...]} per molecule (host, numpy -- like the reference)."""

@@ -30,6 +30,10 @@ condition of the reference's RDKit sanitisation, from a table that is unchecked 
 (0, 1], no default, replaces a disconnected molecule whose largest fragment holds at least FRAC of its atoms by that fragment before
 it is judged.  Pool entries then carry n_components / n_overvalent / min_dist / max_bond_len (of the molecule as decoded) and
 salvaged, and rank 0 writes ``quality.json`` into the log directory.  Without both options nothing changes.
+``--local3d PATTERNS.yml`` (config key ``sample.local3d``; the flag wins), an addition beyond the reference: rank 0 accumulates the bond
+length / bond angle / dihedral histograms of the FINISHED molecules of every batch on the device (``moldiff_amd/local3d.py``; with
+``--largest_fragment`` a salvaged molecule is its fragment) and writes ``local3d.npz`` beside ``samples_all.pt``; compare two runs with
+``python -m moldiff_amd.local3d compare``.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -185,7 +189,13 @@ def quality_options(accept, largest_fragment, sample_cfg):
     return accept_rule('connected' if accept is None else accept), largest_fragment, active
 
 
-def main(argv=None):
+def local3d_option(flag, sample_cfg):
+    """path of the pattern file from the command line's value (None or '' = not given) and the config's ``sample`` section, or None:
+    the flag wins over ``sample.local3d``"""
+    return flag or sample_cfg.get('local3d') or None
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
     ap.add_argument('--outdir', type=str, default='./outputs')
@@ -205,7 +215,14 @@ def main(argv=None):
     ap.add_argument('--largest_fragment', type=float, default=None,
                     help='FRAC in (0, 1]: a disconnected molecule whose largest fragment holds at least FRAC of its atoms is replaced '
                          'by that fragment before it is judged (overrides sample.largest_fragment; no default)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--local3d', type=str, default=None, help='pattern file (YAML: lengths / angles / dihedrals): accumulate the bond length / '
+                                                              'angle / dihedral histograms of the finished molecules on the device and '
+                                                              'write local3d.npz (overrides sample.local3d)')
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -259,6 +276,11 @@ def main(argv=None):
     if resample is not None or jump_length is not None:
         extra.update(resample=None if resample is None else int(resample), jump_length=None if jump_length is None else int(jump_length))
     rule, frac, checked = quality_options(args.accept, args.largest_fragment, config.sample)
+    local3d_path = local3d_option(args.local3d, config.sample)
+    l3d_spec, l3d_stats = None, None
+    if local3d_path:   # read on every rank, so that a bad file stops all of them
+        from . import local3d
+        l3d_spec = local3d.Local3DSpec.from_yaml(local3d_path)
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -339,6 +361,8 @@ def main(argv=None):
                 if save_traj_prob > 0 and np.random.default_rng([seed, int(info['mol_id'])]).random() < save_traj_prob:
                     info['traj_file'] = 'traj_mol%d.sdf' % info['mol_id']
             pool['finished'].extend(gen)
+            if l3d_spec is not None:
+                l3d_stats = local3d.local3d_mols(gen, l3d_spec, device, out=l3d_stats)
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -348,6 +372,8 @@ def main(argv=None):
         i_batch += 1
     if rank == 0:
         torch.save(pool, os.path.join(log_dir, 'samples_all.pt'))
+        if l3d_spec is not None:
+            (l3d_stats or local3d.device_stats(l3d_spec, device)).save(os.path.join(log_dir, 'local3d.npz'))
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),
