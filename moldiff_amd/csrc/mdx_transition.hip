@@ -449,7 +449,7 @@ void launch_cat_add_noise(const float* qmats, int K, const int64_t* v, const int
 //   t > 0: post_pred = o - logsumexp(o), o = A + B, B = max(log(f2 + eps), -32), f2 = exp(log_recon) Q[t-1]   (A: no logits inside)
 //          g_o = g_pp - exp(post_pred) sum(g_pp); g_f2 = g_o [log(f2 + eps) >= -32] / (f2 + eps); g_lr = exp(log_recon) (Q[t-1] g_f2)
 //   t = 0: post_pred = log_recon (torch.where routes the whole gradient there): g_lr = g_pp
-//   log_recon = x - logsumexp(x): g_x = g_lr - softmax(x) sum(g_lr)
+//   log_recon = x - logsumexp(x): g_x = g_lr - softmax(x) sum(g_lr)   (summed pair by pair, see the end of the kernel)
 // (what torch.autograd computes through transition.q_v_posterior_autograd, clamp_min passing the gradient where its input >= the bound).
 template <int K>
 __global__ void cat_loss_kernel(const float* __restrict__ qmats, const float* __restrict__ qT1, const float* __restrict__ logits,
@@ -552,11 +552,17 @@ __global__ void cat_loss_kernel(const float* __restrict__ qmats, const float* __
       glr[j] = er[j] * acc;
     }
   }
-  float gl = 0.f;
+  // g_x[k] = g_lr[k] - softmax[k] sum_j g_lr[j], summed pair by pair as sum_j (g_lr[k] er[j] - er[k] g_lr[j]) (sum_j er[j] = 1): the pair
+  // terms are exactly antisymmetric in (k, j), so a row of d logits sums to zero to a few ulp of its largest entry however confident the
+  // logits are.  Evaluated as written above, a confident correct row (softmax = 1 - 1e-10 on its class) lost that entry to cancellation
+  // against a sum of size 1 and the row summed to its own largest entry instead of zero.
 #pragma unroll
-  for (int k = 0; k < K; ++k) gl += glr[k];
+  for (int k = 0; k < K; ++k) {
+    float acc = 0.f;
 #pragma unroll
-  for (int k = 0; k < K; ++k) dlogits[(size_t)i * K + k] = glr[k] - er[k] * gl;
+    for (int j = 0; j < K; ++j) acc += glr[k] * er[j] - er[k] * glr[j];
+    dlogits[(size_t)i * K + k] = acc;
+  }
 }
 
 void launch_cat_loss(const float* qmats, const float* qT1, int K, const float* logits, const float* log_vt, const float* log_v0,
