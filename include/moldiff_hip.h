@@ -436,6 +436,58 @@ int mdx_mol_local3d(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr,
                     const int32_t* patterns, const int32_t* kind_ptr, const float* bin_range, const int32_t* bin_count, int64_t* hist,
                     int64_t* outside, int64_t* n_items, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- set-level similarity of decoded molecules: fingerprint, key, Tanimoto -----------------------------------------
+ * What the reference's `similarity` block (scripts/evaluate_all.py:164-174, utils/scoring_func.py:102-223) computes from RDKit
+ * fingerprints and canonical SMILES -- uniqueness, diversity, similarity to and novelty against a reference set -- needs, per
+ * molecule, a bit vector and an identity.  Both are defined HERE, by this project: the fingerprint is NOT Chem.RDKFingerprint and the
+ * key is NOT a canonical SMILES, and the molecule is the one AS DECODED.  All arithmetic below is unsigned 32-bit and wrapping.
+ *
+ * mdx_mol_fingerprint: one workgroup per molecule over the compact layout of mdx_mol_local3d -- molecule m has its atoms at
+ * atom_ptr[m] .. + n_atoms[m] of atom_type and its bonds at bond_ptr[m] .. + n_bonds[m] of bond_type / bond_index (row 0 at
+ * bond_index, row 1 at bond_index + Eh_stride; molecule-local atom indices, one direction per bond); the four per-molecule arrays
+ * are device int32, so mdx_decode_output's arrays and a densely packed list are served alike.  N_cap and Eh_stride are the extents
+ * of the atom and bond arrays.  A bond whose index lies outside its molecule, or with i = j, is ignored.  atom_type (class index)
+ * and bond_type (1 .. num_bond_types) enter as the unsigned values they are: the entry knows no featuriser.
+ *   mix(h)     = murmur3's fmix32: h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.
+ *   round 0    : id_0[a] = mix(class[a] + 1 + 0x9e3779b9 * (deg[a] + 1)), deg[a] = the number of valid bonds at a.
+ *   round r + 1: id_{r+1}[a] = mix(id_r[a] * 0x01000193 + (r + 1) + SUM over the valid bonds (a, b, t) of mix(id_r[b] + 0x9e3779b9 * t)).
+ *                The neighbour term is a plain wrapping sum: independent of the order of bonds and atoms.
+ *   bits       : for r = 0 .. radius and every atom, bit (id_r[a] mod nbits) of the row is set; bit k is bit k % 32 of word k / 32.
+ *                No duplicate-substructure removal as in ECFP.  nbits: a multiple of 32, 32 .. 32768; row m of `bits` holds
+ *                nbits / 32 words; n_on[m] = the row's popcount.
+ *   key        : the rounds continue to key_rounds (radius <= key_rounds <= 64);
+ *                key_lo = SUM over r <= key_rounds and a of mix(id_r[a] + r), key_hi = the same sum of mix(id_r[a] ^ 0x5bd1e995);
+ *                key[m] = key_hi << 32 | key_lo as one int64.  An isomorphism INVARIANT: relabelled copies of a molecule always
+ *                agree; two different molecules can agree, because colour refinement cannot tell them apart or by a hash collision.
+ *                The number of distinct keys is a lower bound of the number of distinct molecules, not a proof of identity.
+ *   A molecule without atoms has a zero row, n_on 0 and key 0.  So has one with select[m] == 0 (select: B int32, device, or NULL) and
+ *   one reaching past N_cap / Eh_stride.  Results do not depend on a molecule's place in the batch nor on the order atomics land in.
+ * Storage: a molecule of at most 1,024 atoms keeps its two id arrays in LDS (8 KB, with 4 KB of bits: 8 resident workgroups, the
+ *   most a CU's 32 waves allow, take 96 of its 160 KB); a larger one keeps them in ws.
+ * ws: mdx_mol_fingerprint_ws_bytes(N_cap) = 8 * max(N_cap, 1) bytes, 4-byte aligned; smaller is MDX_ERR_ARG.
+ * MDX_ERR_ARG, outputs untouched: a null operand (select excepted), a negative size, nbits or the rounds outside the above. */
+size_t mdx_mol_fingerprint_ws_bytes(int64_t N_cap);
+int mdx_mol_fingerprint(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                        const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index,
+                        int64_t Eh_stride, const int32_t* select, int32_t radius, int32_t key_rounds, int32_t nbits, int32_t* bits,
+                        int32_t* n_on, int64_t* key, void* ws, size_t ws_bytes, void* stream);
+/* mdx_fp_tanimoto: every row of set A (Na rows) against every row of set B (Nb rows); a row is nbits / 32 words, n_on_a / n_on_b
+ * (device int32) are the rows' popcounts as mdx_mol_fingerprint writes them.  For a pair: c = popcount(a & b), u = n_on_a + n_on_b - c,
+ * q = (float)c / (float)u, ONE correctly rounded fp32 division, and q = 0 where u <= 0 (two empty rows: this project's choice).
+ * With exclude_diagonal != 0 (legal for Na == Nb only: a set against itself) the pair i == j is left out.  Per row i of A:
+ *   row_max[i]    fp32: the largest q (0 without a partner);
+ *   row_argmax[i] int32: the SMALLEST j attaining it, -1 without a partner (Nb = 0, or Nb = 1 with the diagonal excluded);
+ *   row_sum[i]    int64: SUM over j of q * 2^40.  Every non-zero q is >= 2^-16 (c >= 1, u <= 2 * 32768), so its fp32 ulp is >= 2^-39
+ *                 and q * 2^40 is an exact integer below 2^41; the sum stays below 2^63 for Nb <= 2^22.  An integer sum is exact,
+ *                 bit-reproducible and independent of tiling and arrival order; form means from it on the host in float64.
+ * Every Na, Nb >= 0 is served.  ws: mdx_fp_tanimoto_ws_bytes(Na) = 8 * max(Na, 1) bytes, 8-byte aligned.
+ * MDX_ERR_ARG, outputs untouched: nbits not a multiple of 32 in 32 .. 32768, exclude_diagonal with Na != Nb, a negative size, a
+ * null operand of a non-empty set, a workspace too small.  MDX_ERR_UNSUPPORTED: Nb > 2^22, Na > 2^30. */
+size_t mdx_fp_tanimoto_ws_bytes(int64_t Na);
+int mdx_fp_tanimoto(const int32_t* bits_a, const int32_t* n_on_a, int64_t Na, const int32_t* bits_b, const int32_t* n_on_b, int64_t Nb,
+                    int32_t nbits, int32_t exclude_diagonal, float* row_max, int32_t* row_argmax, int64_t* row_sum, void* ws,
+                    size_t ws_bytes, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -187,17 +187,48 @@ class FeaturizeMol(object):
         B = graph.B
         if B == 0:
             return out
-        ptrs = getattr(graph, '_mol_ptr', None)
-        if ptrs is None or ptrs.device != dev:   # first atom / first half-edge of every molecule, formed on the device
-            cnt = torch.zeros(2, B, dtype=torch.int64, device=dev)
-            cnt[0].scatter_add_(0, batch_node.to(dev, torch.int64), torch.ones(graph.N, dtype=torch.int64, device=dev))
-            cnt[1].scatter_add_(0, batch_halfedge.to(dev, torch.int64), torch.ones(graph.Eh, dtype=torch.int64, device=dev))
-            ptrs = graph._mol_ptr = (cnt.cumsum(1) - cnt).to(torch.int32).contiguous()
+        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
         if select is not None:
             select = select.to(dev, torch.int32).contiguous()
         return local3d.launch(spec, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], d['atom_pos'], max(graph.N, 1),
                               d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), out, select=select,
                               ws=graph.workspace(dev))
+
+    @staticmethod
+    def _mol_ptrs(graph, batch_node, batch_halfedge, dev):
+        """(2, B) int32 on the device, kept with the graph: the first atom / first half-edge of every molecule, formed on the device"""
+        ptrs = getattr(graph, '_mol_ptr', None)
+        if ptrs is None or ptrs.device != dev:
+            cnt = torch.zeros(2, graph.B, dtype=torch.int64, device=dev)
+            cnt[0].scatter_add_(0, batch_node.to(dev, torch.int64), torch.ones(graph.N, dtype=torch.int64, device=dev))
+            cnt[1].scatter_add_(0, batch_halfedge.to(dev, torch.int64), torch.ones(graph.Eh, dtype=torch.int64, device=dev))
+            ptrs = graph._mol_ptr = (cnt.cumsum(1) - cnt).to(torch.int32).contiguous()
+        return ptrs
+
+    def fingerprint_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, spec, graph=None, *, select=None):
+        """``decode_batch``'s device part + the fingerprint and key of every decoded molecule (``mdx_mol_fingerprint``) for the
+        set-level numbers of ``moldiff_amd/similarity.py``; `spec` is a ``similarity.FingerprintSpec``.  Nothing is copied to the host
+        and nothing synchronises.  select: (n_graphs) device tensor; a molecule with 0 keeps its place with a zero row, key 0 and
+        n_atoms 0.  -> FingerprintSet with device tensors, one entry per molecule of the batch.
+        These are the molecules AS DECODED; the fingerprint is this project's, not RDKit's.  Like ``decode_batch``, it needs a batch
+        with at least one half-edge."""
+        from . import similarity
+        if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
+            raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        dev = d['atom_type'].device
+        B = graph.B
+        if B == 0:
+            return similarity.FingerprintSet.empty(spec).to(dev)
+        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
+        n_atoms = d['n_atoms'][:B]
+        if select is not None:
+            select = select.to(dev, torch.int32).contiguous()
+            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
+        bits, n_on, key = similarity.launch(spec, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1),
+                                            d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), select=select,
+                                            ws=graph.workspace(dev))
+        return similarity.FingerprintSet(spec, bits, n_on, key, n_atoms)
 
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):

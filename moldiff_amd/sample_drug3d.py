@@ -34,6 +34,10 @@ salvaged, and rank 0 writes ``quality.json`` into the log directory.  Without bo
 length / bond angle / dihedral histograms of the FINISHED molecules of every batch on the device (``moldiff_amd/local3d.py``; with
 ``--largest_fragment`` a salvaged molecule is its fragment) and writes ``local3d.npz`` beside ``samples_all.pt``; compare two runs with
 ``python -m moldiff_amd.local3d compare``.  Without the option nothing changes.
+``--similarity [REFERENCE.npz]`` (config key ``sample.similarity``: true or a path; the flag wins), an addition beyond the reference:
+rank 0 fingerprints the same FINISHED molecules on the device batch by batch (``moldiff_amd/similarity.py``: this project's fingerprint
+and key, not RDKit's) and writes ``fingerprints.npz`` and ``similarity.json`` -- uniqueness and diversity, and with a reference
+fingerprint file novelty and similarity against it -- beside ``samples_all.pt``.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -195,6 +199,24 @@ def local3d_option(flag, sample_cfg):
     return flag or sample_cfg.get('local3d') or None
 
 
+def similarity_option(flag, sample_cfg):
+    """(active, path of the reference fingerprint file or None) from the command line's value (None = not given, True = given bare)
+    and the config's ``sample`` section (``similarity``: true or a path); the flag wins"""
+    value = flag if flag is not None else sample_cfg.get('similarity')
+    if value is None or value is False or value == '':
+        return False, None
+    return True, (None if value is True else str(value))
+
+
+def add_similarity_argument(ap):
+    """``--similarity [REFERENCE.npz]`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--similarity', nargs='?', const=True, default=None, metavar='REFERENCE.npz',
+                    help='fingerprint the finished molecules on the device and write fingerprints.npz and similarity.json (uniqueness, '
+                         'diversity; with a reference fingerprint file also novelty and similarity against it; overrides '
+                         'sample.similarity)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -222,7 +244,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = add_similarity_argument(build_parser()).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -281,6 +303,15 @@ def main(argv=None):
     if local3d_path:   # read on every rank, so that a bad file stops all of them
         from . import local3d
         l3d_spec = local3d.Local3DSpec.from_yaml(local3d_path)
+    sim_active, sim_ref_path = similarity_option(args.similarity, config.sample)
+    sim_spec, sim_set, sim_ref = None, None, None
+    if sim_active:   # read on every rank, so that a bad file stops all of them
+        from . import similarity
+        sim_spec = similarity.FingerprintSpec(atomic_numbers=featurizer.atomic_numbers.tolist(), num_bond_types=featurizer.num_bond_types)
+        if sim_ref_path:
+            sim_ref = similarity.FingerprintSet.load(sim_ref_path)
+            if sim_ref.spec != sim_spec:
+                raise ValueError(f'{sim_ref_path} was made with another spec ({sim_ref.spec.to_dict()}) than this run\'s ({sim_spec.to_dict()})')
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -363,6 +394,9 @@ def main(argv=None):
             pool['finished'].extend(gen)
             if l3d_spec is not None:
                 l3d_stats = local3d.local3d_mols(gen, l3d_spec, device, out=l3d_stats)
+            if sim_spec is not None:
+                fps = similarity.fingerprint_mols(gen, sim_spec, device)
+                sim_set = fps if sim_set is None else sim_set.append(fps)
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -374,6 +408,11 @@ def main(argv=None):
         torch.save(pool, os.path.join(log_dir, 'samples_all.pt'))
         if l3d_spec is not None:
             (l3d_stats or local3d.device_stats(l3d_spec, device)).save(os.path.join(log_dir, 'local3d.npz'))
+        if sim_spec is not None:
+            sim_set = sim_set if sim_set is not None else similarity.FingerprintSet.empty(sim_spec).to(device)
+            sim_set.save(os.path.join(log_dir, 'fingerprints.npz'))
+            with open(os.path.join(log_dir, 'similarity.json'), 'w') as f:
+                json.dump(similarity.summary(sim_set, sim_ref.to(device) if sim_ref is not None else None), f, indent=1)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),
