@@ -488,6 +488,47 @@ int mdx_fp_tanimoto(const int32_t* bits_a, const int32_t* n_on_a, int64_t Na, co
                     int32_t nbits, int32_t exclude_diagonal, float* row_max, int32_t* row_argmax, int64_t* row_sum, void* ws,
                     size_t ws_bytes, void* stream);
 
+/* ---- ring perception and composition counts of decoded molecules ------------------------------------------------------
+ * The pure graph quantities of the reference's evaluation (utils/evaluation.py:24-37, 52-83: `count_prop`'s n_rings and n_rotatable,
+ * `frags_counts`' element, bond type and ring-size counts, `ring_topo`'s ring atoms) without RDKit, of the molecule AS DECODED.  Every
+ * output is defined so that its value is UNIQUE: no tie-break, atom order or traversal order enters, and a plain restatement
+ * (moldiff_amd/rings.py: rings_ref) must agree exactly.
+ *
+ * mdx_mol_rings: one workgroup per molecule over the compact layout of mdx_mol_fingerprint (atom_ptr, bond_ptr, n_atoms, n_bonds,
+ * atom_type, N_cap, bond_type, bond_index, Eh_stride, select: as there).  A bond whose index lies outside its molecule, or with
+ * i = j, is ignored.  Two bonds between the same pair of atoms are a PRECONDITION VIOLATION (mdx_decode_output cannot produce them):
+ * the results of such a molecule are unspecified, the kernel stays in bounds and ends.  With n atoms, b valid bonds, c fragments:
+ *   n_rings[m]      = b - n + c, the cyclomatic number.
+ *   ring_hist[m][k] , k = 0 .. ring_bins - 1 (1 .. 64; 7 = sizes 3 .. 9+ as the reference): the rings of size 3 + k of a MINIMUM CYCLE
+ *                     BASIS, the last bin also every larger ring.  Such a basis is not unique, the sorted list of its ring sizes is:
+ *                     the number of basis rings of size <= L is the GF(2) rank of all cycles of length <= L, and that is the
+ *                     definition.  SUM over k of ring_hist[m][k] = n_rings[m].  This is NOT RDKit's symmetrised SSSR
+ *                     (GetSymmSSSR): cubane has 5 four-rings here and 6 there.
+ *   bond_ring_min   per bond slot (Eh_stride): the size of the smallest ring through the bond = 1 + the distance between its ends with
+ *                     the bond removed; 0 for a bridge and for an ignored bond.  A bond is a RING BOND iff this is not 0.
+ *   atom_ring_min   per atom slot (N_cap): the smallest bond_ring_min > 0 over the atom's bonds, 0 for an atom without a ring bond.
+ *   n_ring_bonds[m] , n_ring_atoms[m]: the bonds / atoms with a non-zero entry.
+ *   n_rotatable[m]  this project's rule, not RDKit's SMARTS: the valid bonds of type 1 that are no ring bond, both of whose atoms have
+ *                     at least two valid bonds and neither of whose atoms carries a bond of type 3.  There is NO amide exclusion.
+ *   elem_count[m][k], k < num_element: the atoms of class k; bond_count[m][t - 1], t = 1 .. num_bond_types: the valid bonds of type t.
+ *                     An atom or bond of another class / type is counted in neither (the bond is still a bond of the graph).
+ *   status[m]       0 measured; 1 too large: n_atoms > 256 or n_bonds > 512 (ignored bonds included); 2 too many rings: n_rings > 64.
+ *                     With a non-zero status every other output of the molecule is 0, its slots of bond_ring_min / atom_ring_min
+ *                     included.  A molecule with select[m] == 0 has status 0 and all outputs 0; so has one reaching past N_cap /
+ *                     Eh_stride, whose slots are not written.  Slots of the two arrays that belong to no molecule are not written.
+ * The number of basis rings an atom lies in and ring SMILES are not offered: both depend on the basis chosen.
+ * Caps: 256 atoms, 512 bonds, 64 independent rings per molecule (GEOM-Drugs stays far below), so that a cycle is one 64-bit word and
+ * everything fits in LDS: 23.6 KB per workgroup of 256 threads -- 6 workgroups per CU by LDS, 8 by waves.  There is no workspace.
+ * All outputs are device int32, written with plain stores by the molecule's own workgroup: bit-reproducible and independent of a
+ * molecule's place in the batch.
+ * MDX_ERR_ARG, outputs untouched: a null operand (select excepted), a negative size, ring_bins outside 1 .. 64, num_element outside
+ * 1 .. 255, num_bond_types outside 1 .. 254. */
+int mdx_mol_rings(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                  const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                  const int32_t* select, int32_t num_element, int32_t num_bond_types, int32_t ring_bins, int32_t* n_rings,
+                  int32_t* ring_hist, int32_t* n_ring_atoms, int32_t* n_ring_bonds, int32_t* n_rotatable, int32_t* elem_count,
+                  int32_t* bond_count, int32_t* status, int32_t* bond_ring_min, int32_t* atom_ring_min, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -230,6 +230,32 @@ class FeaturizeMol(object):
                                             ws=graph.workspace(dev))
         return similarity.FingerprintSet(spec, bits, n_on, key, n_atoms)
 
+    def rings_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, ring_bins=7, select=None):
+        """``decode_batch``'s device part + the ring and composition counts of every decoded molecule (``mdx_mol_rings``; see
+        ``moldiff_amd/rings.py``).  Nothing is copied to the host and nothing synchronises.  select: (n_graphs) device tensor; a
+        molecule with 0 keeps its place with status 0, n_atoms 0 and every count 0.  -> results dict of int32 device tensors, one entry
+        (or row) per molecule of the batch: status, n_atoms, n_rings, ring_hist, n_ring_atoms, n_ring_bonds, n_rotatable, elem_count,
+        bond_count; bond_ring_min / atom_ring_min in the decode's own layout, molecule m at bond_ptr[m] / atom_ptr[m].
+        These are the molecules AS DECODED; the ring sizes are those of a minimum cycle basis, not RDKit's SSSR.  Like
+        ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import rings
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        dev = d['atom_type'].device
+        B = graph.B
+        if B == 0:
+            return {k: torch.from_numpy(v).to(dev) for k, v in
+                    rings.empty(self.num_bond_types, self.atomic_numbers.tolist(), ring_bins).items()}
+        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
+        n_atoms = d['n_atoms'][:B]
+        if select is not None:
+            select = select.to(dev, torch.int32).contiguous()
+            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
+        out = rings.launch(B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1), d['bond_type'],
+                           d['bond_index'], int(d['bond_index'].shape[1]), self.num_element, self.num_bond_types, ring_bins,
+                           select=select)
+        out.update(n_atoms=n_atoms, atom_ptr=ptrs[0], bond_ptr=ptrs[1])
+        return out
+
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):
     """Split packed numpy outputs {'pred': [...], 'traj': [...]} per molecule (host, numpy -- like the reference)."""

@@ -38,6 +38,10 @@ length / bond angle / dihedral histograms of the FINISHED molecules of every bat
 rank 0 fingerprints the same FINISHED molecules on the device batch by batch (``moldiff_amd/similarity.py``: this project's fingerprint
 and key, not RDKit's) and writes ``fingerprints.npz`` and ``similarity.json`` -- uniqueness and diversity, and with a reference
 fingerprint file novelty and similarity against it -- beside ``samples_all.pt``.  Without the option nothing changes.
+``--rings`` (config key ``sample.rings``; the flag wins), an addition beyond the reference: rank 0 measures the rings and the
+composition of the same FINISHED molecules on the device batch by batch (``moldiff_amd/rings.py``: ring sizes of a minimum cycle basis,
+not RDKit's SSSR; this project's rotatable-bond rule) and writes ``rings.npz`` (per-molecule arrays) and ``rings.json`` (their summary)
+beside ``samples_all.pt``.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -217,6 +221,19 @@ def add_similarity_argument(ap):
     return ap
 
 
+def rings_option(flag, sample_cfg):
+    """whether to measure rings: the command line's flag (None = not given) wins over the config's ``sample.rings``"""
+    return bool(flag if flag is not None else sample_cfg.get('rings'))
+
+
+def add_rings_argument(ap):
+    """``--rings`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--rings', action='store_true', default=None,
+                    help='measure ring sizes, ring atoms, rotatable bonds and the element / bond type counts of the finished molecules '
+                         'on the device and write rings.npz and rings.json (overrides sample.rings)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -244,7 +261,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = add_similarity_argument(build_parser()).parse_args(argv)
+    args = add_rings_argument(add_similarity_argument(build_parser())).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -312,6 +329,9 @@ def main(argv=None):
             sim_ref = similarity.FingerprintSet.load(sim_ref_path)
             if sim_ref.spec != sim_spec:
                 raise ValueError(f'{sim_ref_path} was made with another spec ({sim_ref.spec.to_dict()}) than this run\'s ({sim_spec.to_dict()})')
+    rings_active, rings_parts = rings_option(args.rings, config.sample), []
+    if rings_active:
+        from . import rings
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -397,6 +417,8 @@ def main(argv=None):
             if sim_spec is not None:
                 fps = similarity.fingerprint_mols(gen, sim_spec, device)
                 sim_set = fps if sim_set is None else sim_set.append(fps)
+            if rings_active and gen:
+                rings_parts.append(rings.to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -413,6 +435,11 @@ def main(argv=None):
             sim_set.save(os.path.join(log_dir, 'fingerprints.npz'))
             with open(os.path.join(log_dir, 'similarity.json'), 'w') as f:
                 json.dump(similarity.summary(sim_set, sim_ref.to(device) if sim_ref is not None else None), f, indent=1)
+        if rings_active:
+            res = rings.concat(rings_parts) if rings_parts else rings.empty(featurizer.num_bond_types, featurizer.atomic_numbers.tolist())
+            rings.save(res, os.path.join(log_dir, 'rings.npz'))
+            with open(os.path.join(log_dir, 'rings.json'), 'w') as f:
+                json.dump(rings.summary(res), f, indent=1)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),

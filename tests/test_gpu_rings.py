@@ -1,0 +1,264 @@
+"""GPU tests of the ring and composition counts (mdx_mol_rings through rings.rings_mols, rings.launch, FeaturizeMol.rings_batch and the
+sampling entry point's --rings).  The oracle is the plain Python restatement ``rings_ref``; every output is an integer that the
+definitions make unique, so every comparison is exact."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from moldiff_amd import _lib
+from moldiff_amd import rings as R
+from moldiff_amd.harness import placeholder_from_sizes
+from moldiff_amd.postprocess import FeaturizeMol
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+ELEMENTS = (6, 7, 8, 9, 15, 16, 17)
+FEAT = FeaturizeMol(list(ELEMENTS), [1, 2, 3, 4], use_mask_node=True, use_mask_edge=True)
+
+
+def mol(ele, bonds):
+    ele = [6] * ele if isinstance(ele, int) else ele
+    bonds = [tuple(b) + (1,) * (3 - len(b)) for b in bonds]
+    idx = np.asarray([(i, j) for i, j, _ in bonds], dtype=np.int64).reshape(-1, 2).T
+    bt = [t for _, _, t in bonds]
+    return {'element': np.asarray(ele, dtype=np.int64), 'bond_index': np.concatenate([idx, idx[::-1]], axis=1),
+            'bond_type': np.asarray(bt + bt, dtype=np.int64)}
+
+
+def ring(n, first=0, t=1):
+    return [(first + k, first + (k + 1) % n, t) for k in range(n)]
+
+
+def ladder(rungs):
+    return mol(2 * rungs, [(k, k + 1) for k in range(rungs - 1)] + [(rungs + k, rungs + k + 1) for k in range(rungs - 1)] +
+               [(k, rungs + k) for k in range(rungs)])
+
+
+def random_mol(seed, n, extra=0.3):
+    """connected: a random spanning tree plus extra * n further bonds; the first 7 atoms and 4 bonds carry every element and type"""
+    g = np.random.default_rng(seed)
+    bonds = {(int(g.integers(0, k)), k) for k in range(1, n)}
+    while len(bonds) < n - 1 + int(extra * n):
+        i, j = sorted(int(x) for x in g.choice(n, 2, replace=False))
+        bonds.add((i, j))
+    ele = g.choice(ELEMENTS, n)
+    ele[:7] = ELEMENTS[:n]
+    bt = g.integers(1, 5, len(bonds))
+    bt[:4] = [1, 2, 3, 4][:len(bonds)]
+    return mol(ele, [(i, j, int(t)) for (i, j), t in zip(sorted(bonds), bt)])
+
+
+RING = mol([6, 6, 7, 6, 6, 8], ring(6, t=4))
+BATCH = [mol(5, [(0, 1), (1, 2), (2, 3), (3, 4)]),                                   # 0 chain
+         mol(6, ring(6, t=4)),                                                       # 1 benzene
+         mol(10, ring(10, t=4) + [(0, 5, 4)]),                                       # 2 naphthalene
+         mol(7, ring(6) + [(0, 6), (6, 3)]),                                         # 3 norbornane
+         mol(8, ring(4) + ring(4, 4) + [(k, k + 4) for k in range(4)]),              # 4 cubane
+         mol(5, [(0, 1), (1, 2), (2, 0), (0, 3), (3, 4), (4, 0)]),                   # 5 spiro[2.2]pentane
+         mol(12, ring(6, t=4) + ring(6, 6, t=4) + [(0, 6, 1)]),                      # 6 two rings joined by a bridge bond
+         mol(10, ring(10)),                                                          # 7 a 10-ring
+         mol([6, 6, 6, 8, 7, 7], ring(3) + [(4, 5, 3)]),                             # 8 two fragments and a lone atom
+         mol(0, []),                                                                 # 9 no atom
+         RING,                                                                       # 10
+         mol([6, 6, 7, 6, 6, 8], [(0, 6, 1), (2, 2, 3)] + ring(6, t=4) + [(-1, 3, 2)]),   # 11 = the ring, with three ignored bonds
+         random_mol(41, 12),                                                         # 12 masked out in the second launch
+         random_mol(43, 12),                                                         # 13
+         random_mol(40, 40),                                                         # 14 every element and bond type
+         ladder(33), ladder(65), ladder(66),                                         # 15 16 17: 32, 64 and 65 rings
+         random_mol(42, 256, extra=0.1),                                             # 18 the largest molecule measured
+         mol(256, ring(256)),                                                        # 19 one ring of 256
+         mol(257, [(k, k + 1) for k in range(256)]),                                 # 20 one atom too many
+         mol(200, [(k, k + 1) for k in range(199)] + [(k, k + 2) for k in range(198)] + [(k, k + 3) for k in range(116)]),   # 21 513 bonds
+         RING]                                                                       # 22 the ring again, elsewhere
+MASKED = 12
+
+
+@pytest.fixture(scope='module')
+def want():
+    """rings_ref of every molecule of BATCH, computed once"""
+    return R.stack_ref(BATCH)
+
+
+def same(got, ref, what, keys=None):
+    got = R.to_host(got)
+    for k in keys or ref:
+        assert got[k].dtype == np.int32 and got[k].shape == ref[k].shape, (what, k, got[k].shape, ref[k].shape)
+        bad = np.flatnonzero((got[k] != ref[k]).reshape(len(ref[k]), -1).any(1)) if ref[k].size else []
+        assert len(bad) == 0, (what, k, bad[:8], got[k][bad[:4]], ref[k][bad[:4]])
+
+
+def test_one_launch_over_the_whole_list_equals_the_restatement(want):
+    assert want['status'].tolist() == [0] * 17 + [2, 0, 0, 1, 1, 0]
+    assert want['n_rings'][[15, 16, 17, 18, 19]].tolist() == [32, 64, 0, 25, 1] and want['ring_hist'][19].tolist() == [0] * 6 + [1]
+    assert sorted(set(BATCH[14]['element'])) == list(ELEMENTS) and sorted(set(BATCH[14]['bond_type'].tolist())) == [1, 2, 3, 4]
+    got = R.rings_mols(BATCH, DEV)
+    same(got, want, 'rings_mols')
+    g = R.to_host(got)
+    for k in R.MOL_KEYS:                                    # the same ring at three places, once with ignored bonds around it
+        assert np.array_equal(g[k][10], g[k][22]) and np.array_equal(g[k][10], g[k][11]), k
+    # the same arrays with a mask: the masked molecule has status 0 and zeros everywhere, its slots included; the others are unchanged
+    from moldiff_amd.similarity import pack_mols
+    import types
+    p = pack_mols(BATCH, types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
+    select = torch.ones(len(BATCH), dtype=torch.int32, device=DEV)
+    select[MASKED] = 0
+    N, E = int(p['n_atoms'].sum()), int(p['n_bonds'].sum())
+    out = R.launch(len(BATCH), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'], d['bond_index'],
+                   int(d['bond_index'].shape[1]), 7, 4, select=select)
+    ref = {k: v.copy() for k, v in want.items()}
+    for k in R.MOL_KEYS:
+        ref[k][MASKED] = 0
+    a0, b0 = int(p['atom_ptr'][MASKED]), int(p['bond_ptr'][MASKED])
+    ref['atom_ring_min'][a0:a0 + int(p['n_atoms'][MASKED])] = 0
+    ref['bond_ring_min'][b0:b0 + int(p['n_bonds'][MASKED])] = 0
+    assert want['n_rings'][MASKED] > 0
+    same(out, ref, 'select', keys=[k for k in R.MOL_KEYS + R.SLOT_KEYS if k != 'n_atoms'])
+    # a second call gives the same bytes
+    again = R.to_host(R.rings_mols(BATCH, DEV))
+    assert all(g[k].tobytes() == again[k].tobytes() for k in g)
+    # other bin counts
+    for bins in (1, 4, 64):
+        same(R.rings_mols(BATCH[:12], DEV, ring_bins=bins), R.stack_ref(BATCH[:12], ring_bins=bins), ('bins', bins))
+
+
+def test_no_molecule_and_host_side_refusals():
+    got = R.to_host(R.rings_mols([], DEV))
+    ref = R.empty()
+    assert set(got) == set(ref) and all(got[k].shape == ref[k].shape for k in ref)
+    with pytest.raises(ValueError, match='same pair'):
+        R.rings_mols([BATCH[1], mol(3, [(0, 1), (1, 2), (1, 0)])], DEV)
+    with pytest.raises(ValueError, match='element'):
+        R.rings_mols([mol([6, 5], [(0, 1)])], DEV)
+    with pytest.raises(ValueError, match='ring_bins'):
+        R.rings_mols(BATCH[:2], DEV, ring_bins=0)
+
+
+def test_argument_errors_leave_the_outputs_untouched():
+    L = _lib.lib()
+    ARG = 1
+    from moldiff_amd.similarity import pack_mols
+    import types
+    p = pack_mols(BATCH[:5], types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
+    N, E = int(p['n_atoms'].sum()), int(d['bond_index'].shape[1])
+    seven = lambda *shape: torch.full(shape, 7, dtype=torch.int32, device=DEV)
+    o = {'n_rings': seven(5), 'ring_hist': seven(5, 7), 'n_ring_atoms': seven(5), 'n_ring_bonds': seven(5), 'n_rotatable': seven(5),
+         'elem_count': seven(5, 7), 'bond_count': seven(5, 4), 'status': seven(5), 'bond_ring_min': seven(E), 'atom_ring_min': seven(N)}
+
+    def call(B=5, N_cap=N, stride=E, ne=7, nbt=4, bins=7, null=None):
+        q = lambda name, t: None if null == name else _lib.ptr(t)
+        return L.mdx_mol_rings(B, q('atom_ptr', d['atom_ptr']), _lib.ptr(d['bond_ptr']), _lib.ptr(d['n_atoms']), _lib.ptr(d['n_bonds']),
+                               _lib.ptr(d['atom_type']), N_cap, _lib.ptr(d['bond_type']), _lib.ptr(d['bond_index']), stride, None, ne, nbt,
+                               bins, *(q(k, o[k]) for k in ('n_rings', 'ring_hist', 'n_ring_atoms', 'n_ring_bonds', 'n_rotatable',
+                                                             'elem_count', 'bond_count', 'status', 'bond_ring_min', 'atom_ring_min')),
+                               _lib.stream())
+    assert call(bins=0) == ARG and b'ring_bins' in L.mdx_last_error()
+    assert call(bins=65) == ARG and call(B=-1) == ARG and call(N_cap=-1) == ARG and call(stride=-1) == ARG
+    assert call(null='atom_ptr') == ARG and b'null' in L.mdx_last_error()
+    assert call(null='status') == ARG and call(null='bond_ring_min') == ARG
+    assert call(ne=0) == ARG and call(ne=256) == ARG and call(nbt=255) == ARG
+    torch.cuda.synchronize()
+    assert all(bool((t == 7).all()) for t in o.values())
+    assert call(B=0) == 0                                              # no molecule: accepted, nothing written
+    torch.cuda.synchronize()
+    assert all(bool((t == 7).all()) for t in o.values())
+    assert call() == 0                                                 # and the same operands, unbroken, are accepted
+    torch.cuda.synchronize()
+    ref = R.stack_ref(BATCH[:5])
+    assert o['n_rings'].tolist() == ref['n_rings'].tolist() and o['ring_hist'].cpu().numpy().tolist() == ref['ring_hist'].tolist()
+    assert o['bond_ring_min'].tolist() == ref['bond_ring_min'].tolist() and o['status'].tolist() == [0] * 5
+
+
+def _pred_of(mols, masks):
+    """one-hot predictions that decode to `mols`, molecule k preceded by masks[k] mask-type atoms (which the decode drops)"""
+    cls = {z: i for i, z in enumerate(ELEMENTS)}
+    pn, pp, ph = [], [], []
+    for m, shift in zip(mols, masks):
+        ids = np.concatenate([np.full(shift, 7), [cls[int(z)] for z in m['element']]]).astype(np.int64)
+        n = len(ids)
+        T = np.zeros((n, n), dtype=np.int64)
+        nb = m['bond_index'].shape[1] // 2
+        for (i, j), t in zip(m['bond_index'][:, :nb].T, m['bond_type'][:nb]):
+            T[min(i, j) + shift, max(i, j) + shift] = t
+        iu, ju = np.triu_indices(n, 1)
+        pn.append((10.0 * np.eye(8)[ids]).astype(np.float32)), pp.append(np.zeros((n, 3), dtype=np.float32))
+        ph.append((10.0 * np.eye(6)[T[iu, ju]]).astype(np.float32).reshape(-1, 6))
+    ph_ = placeholder_from_sizes([len(x) for x in pn], DEV)
+    pred = [torch.from_numpy(np.concatenate(x)).to(DEV) for x in (pn, pp, ph)]
+    return (pred, ph_['batch_node'], ph_['halfedge_index'], ph_['batch_halfedge'], len(mols))
+
+
+def test_rings_batch_on_the_decode_layout_equals_rings_mols_of_its_molecules():
+    mols = [BATCH[9], BATCH[8], BATCH[2], BATCH[4], BATCH[14], BATCH[12], BATCH[6], BATCH[15]]
+    args = _pred_of(mols, masks=[2, 1, 0, 0, 3, 0, 1, 0])
+    decoded = FEAT.decode_batch(*args)
+    assert [len(d['element']) for d in decoded] == [0, 6, 10, 8, 40, 12, 12, 66]
+    listed, ref = R.to_host(R.rings_mols(decoded, DEV)), R.stack_ref(decoded)
+    same(listed, ref, 'rings_mols of the decoded list')
+    assert ref['n_rings'].tolist() == [0, 1, 2, 5, 12, 3, 2, 32]
+    nb = [d['bond_index'].shape[1] // 2 for d in decoded]
+
+    def check(got, masked=()):
+        got = R.to_host(got)
+        for m in range(len(mols)):
+            a0, b0 = int(got['atom_ptr'][m]), int(got['bond_ptr'][m])
+            la, lb = int(listed['atom_ptr'][m]), int(listed['bond_ptr'][m])
+            na = len(decoded[m]['element'])
+            zero = m in masked
+            for k in R.MOL_KEYS:
+                assert np.array_equal(got[k][m], np.zeros_like(listed[k][m]) if zero else listed[k][m]), (k, m)
+            assert np.array_equal(got['atom_ring_min'][a0:a0 + na], listed['atom_ring_min'][la:la + na] * (not zero)), m
+            assert np.array_equal(got['bond_ring_min'][b0:b0 + nb[m]], listed['bond_ring_min'][lb:lb + nb[m]] * (not zero)), m
+    check(FEAT.rings_batch(*args))
+    check(FEAT.rings_batch(*args, select=torch.tensor([1, 1, 1, 1, 1, 0, 1, 1], device=DEV)), masked=(5,))
+    got = R.to_host(FEAT.rings_batch(*args, ring_bins=3))
+    assert got['ring_hist'].shape == (8, 3) and got['ring_hist'][2].tolist() == [0, 0, 2] and got['ring_hist'][3].tolist() == [0, 5, 0]
+
+
+def _same_numbers(got, ref):
+    if isinstance(ref, dict):
+        assert set(got) == set(ref)
+        for k in ref:
+            _same_numbers(got[k], ref[k])
+    elif isinstance(ref, list):
+        assert len(got) == len(ref)
+        for a, b in zip(got, ref):
+            _same_numbers(a, b)
+    else:
+        assert got == ref or (np.isnan(got) and np.isnan(ref)), (got, ref)
+
+
+def _sample(tmp_path, name, extra):
+    from moldiff_amd import sample_drug3d
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    log_dir = sample_drug3d.main(['--config', os.path.join(root, 'configs', 'sample_MolDiff_simple.yml'), '--outdir', str(tmp_path / name),
+                                  '--device', DEV, '--recipe-weights', '--num_steps', '2', '--num_mols', '6', '--batch_size', '8'] + extra)
+    return log_dir, torch.load(os.path.join(log_dir, 'samples_all.pt'), weights_only=False)
+
+
+def test_entry_point_writes_rings_of_the_finished_molecules(tmp_path):
+    # the seed is sample.seed + sum(ord(outdir)): the two directory names are permutations of each other, so both runs sample the same
+    # molecules; the first run is without the option
+    d0, pool0 = _sample(tmp_path, 'ab', ['--largest_fragment', '0.2'])
+    d1, pool = _sample(tmp_path, 'ba', ['--largest_fragment', '0.2', '--rings'])
+    assert len(pool['finished']) >= 2 and [m['mol_id'] for m in pool['finished']] == [m['mol_id'] for m in pool0['finished']]
+    new = {'rings.json', 'rings.npz'}
+    assert not new & set(os.listdir(d0)) and sorted(os.listdir(d0)) == sorted(f for f in os.listdir(d1) if f not in new)
+    for f in sorted(os.listdir(d0 + '_SDF')):                    # without the option nothing changes: the molecules are the same bytes
+        with open(os.path.join(d0 + '_SDF', f), 'rb') as a, open(os.path.join(d1 + '_SDF', f), 'rb') as b:
+            assert a.read() == b.read(), f
+    assert sorted(os.listdir(d0 + '_SDF')) == sorted(os.listdir(d1 + '_SDF'))
+    ref = R.stack_ref(pool['finished'])
+    saved = R.load(os.path.join(d1, 'rings.npz'))
+    assert set(saved) == set(ref) and all(np.array_equal(saved[k], ref[k]) and saved[k].dtype == ref[k].dtype for k in ref)
+    with open(os.path.join(d1, 'rings.json')) as f:
+        got = json.load(f)
+    print('finished', len(pool['finished']), got)
+    _same_numbers(got, R.summary(ref))
+    # untrained weights bond nearly every pair of atoms: most of these molecules are beyond the caps and are counted as skipped
+    assert got['n_measured'] + sum(got['n_skipped'].values()) == len(pool['finished'])
+    assert sum(got['element']['counts']) == sum(len(m['element']) for m, s in zip(pool['finished'], ref['status']) if s == 0)
