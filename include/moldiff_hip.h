@@ -529,6 +529,76 @@ int mdx_mol_rings(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, c
                   int32_t* ring_hist, int32_t* n_ring_atoms, int32_t* n_ring_bonds, int32_t* n_rotatable, int32_t* elem_count,
                   int32_t* bond_count, int32_t* status, int32_t* bond_ring_min, int32_t* atom_ring_min, void* stream);
 
+/* ---- substructure matching on decoded molecules: functional-group counts ----------------------------------------------
+ * "Does this small labelled subgraph occur in the molecule, how often, and at which atoms" -- the primitive behind the reference's
+ * `groups_counts` (utils/evaluation.py:86-94), the donor / acceptor counts of `count_prop` (:27-28), the PAINS filter
+ * (utils/scoring_func.py:28-35) and the SMARTS counts of Local3D.get_counts (:308-313) -- without RDKit, of the molecule AS DECODED.
+ * The pattern language is THIS PROJECT'S OWN: it is NOT SMARTS (no negation, no recursion, no charges, implicit hydrogens from a
+ * caller-supplied table) and a pattern set written in it is not RDKit's `Fragments`.  Every output is defined so that its value is
+ * UNIQUE -- no atom order, bond order or traversal order enters -- and a plain restatement (moldiff_amd/groups.py: groups_ref) must
+ * agree exactly.
+ *
+ * The molecule: atoms of class atom_type[a]; its VALID bonds (both indices inside the molecule, i != j; the others are ignored).  A
+ *   bond type outside 1 .. num_bond_types leaves the bond in the graph, adds no valence and satisfies no pattern bond.  Per atom:
+ *   deg = its valid bonds; valence2 = mdx_mol_check's: types 1, 2, 3 count 2, 4, 6 and the last type (aromatic) counts 3;
+ *   h = max(0, normal_valence[class] - (valence2 + 1) / 2) in integer division, the IMPLICIT HYDROGENS (normal_valence: num_element
+ *   int32 on the HOST, 0 .. 64 each: chemistry is data); ring class of an atom / a bond from atom_ring_min / bond_ring_min of
+ *   mdx_mol_rings: 0 no ring bond, 1 .. 5 smallest ring 3 .. 7, 6 a ring of 8 or more.  Two bonds between one pair of atoms are a
+ *   PRECONDITION VIOLATION as for mdx_mol_rings: results unspecified, the kernel stays in bounds and ends.
+ * A pattern: a connected graph of 1 .. MDX_GROUPS_ATOMS atoms and 0 .. MDX_GROUPS_BONDS bonds, no two bonds between one pair of atoms.
+ *   Pattern atom: elem_mask (bit c allows class c, so num_element <= 32), deg_mask (bit d allows d bonds, bit 7: 7 or more), h_mask
+ *   (bit h allows h implicit hydrogens, bit 4: 4 or more), rsize_mask (bit r allows ring class r; 0x7f = any), arom (0 any, 1 the atom
+ *   carries a bond of the last type, 2 it carries none).  Pattern bond (i, j): type_mask (bit t allows bond type t, 1 .. num_bond_types
+ *   <= 16), rsize_mask over the bond's ring class.  All constraints of an atom / a bond must hold.  No negation, no recursion.
+ *   ORDER: every pattern atom k > 0 has a bond to an atom before it (a set that is not ordered so is refused); the earliest such atom
+ *   is k's PARENT.  Pattern atom 0 is the ANCHOR.
+ * Pattern table (HOST int32): P records of MDX_GROUPS_RECORD = 90 values, P in 1 .. MDX_GROUPS_PATTERNS:
+ *   [0] atoms, [1] bonds, [2 + 5 k ..] elem_mask, deg_mask, h_mask, rsize_mask, arom of atom k (8 slots), [42 + 4 e ..] i, j,
+ *   type_mask, rsize_mask of bond e (12 slots).  Slots beyond the counts are not read.  The table and normal_valence are validated,
+ *   translated and sent to `ws` as kernel arguments of this call: the caller may overwrite both arrays as soon as the call returns.
+ * An EMBEDDING is an injective map of pattern atoms to molecule atoms under which every pattern atom's constraints hold and every
+ *   pattern bond lands on a valid molecule bond that satisfies the bond's constraints.  Matching is NON-INDUCED: further molecule
+ *   bonds among the images are allowed.
+ * Outputs (device int32; [m][p] = element m * P + p):
+ *   n_embed[m][p]    the number of embeddings.  On the host n_match = n_embed / |Aut(pattern)|, Aut = the permutations of the pattern's
+ *                    atoms that preserve bonds and every constraint field exactly; Aut acts freely on embeddings, so the division is
+ *                    exact.  n_match equals RDKit's uniquified match count except where one atom set carries several inequivalent
+ *                    embeddings: a 3-atom path in a triangle gives 3 here and 1 there.
+ *   n_anchor[m][p]   the distinct molecule atoms that are the image of pattern atom 0 in at least one embedding.
+ *   atom_hit         per atom slot (N_cap): bit p is set iff the atom is such an anchor for pattern p.
+ *   steps[m][p]      the candidates tested = SUM over the start atoms a of steps_a; steps_a = 1 (the start candidate) + SUM over
+ *                    k = 1 .. atoms - 1 and over every PARTIAL EMBEDDING of pattern atoms 0 .. k - 1 with atom 0 at a (all constraints
+ *                    among them hold) of deg(image of k's parent).  Order-independent by construction.
+ *   pat_status[m][p] 0 measured; 3 budget exceeded: some start atom's steps_a > max_steps (1 .. 2^20).  Then n_embed, n_anchor and
+ *                    steps are 0 and bit p is clear in the molecule's atom_hit.  The budget is what lets a wildcard pattern meet
+ *                    the nearly complete bond graphs of untrained weights: a thread stops after max_steps candidates.
+ *   status[m]        0 measured; 1 too large: n_atoms > 256 or n_bonds > 512, the caps of mdx_mol_rings; 2 the ring data say "not
+ *                    measured": ring_status[m] != 0.  With a non-zero status every other output of the molecule is 0, its atom_hit
+ *                    slots included.  select, and a molecule reaching past N_cap / Eh_stride, as for mdx_mol_rings: status 0, all
+ *                    outputs 0 (the slots of the latter are not written).  Slots of atom_hit that belong to no molecule are not written.
+ * Ring inputs: atom_ring_min (N_cap), bond_ring_min (Eh_stride), ring_status (B), exactly as mdx_mol_rings wrote them for the same
+ *   arrays; all three or none.  None is legal iff every rsize_mask of the set is 0x7f.
+ * One workgroup of 256 threads per molecule, the molecule staged once in LDS (about 13 KB: 8 workgroups per CU, the bound of its
+ * waves), the patterns looped over inside; thread a searches from start atom a.  All outputs are written with plain stores by the
+ * molecule's own workgroup: bit-reproducible and independent of a molecule's place in the batch.
+ * ws: device, mdx_mol_groups_ws_bytes(P) = 128 * (1 + P) bytes, 4-byte aligned; written by this call, read by its kernel.
+ * MDX_ERR_ARG, every output untouched: a null operand (select and the ring inputs excepted), a negative size, P outside 1 .. 32,
+ * max_steps outside 1 .. 2^20, num_element outside 1 .. 32, num_bond_types outside 1 .. 16, a normal valence outside 0 .. 64, a
+ * pattern field out of range, an empty or out-of-range mask, a repeated or self bond, atoms not ordered as above (which covers a
+ * pattern that is not connected), one or two of the three ring inputs, a ring constraint without them, a workspace too small.
+ * B = 0 is accepted and writes nothing. */
+#define MDX_GROUPS_ATOMS 8
+#define MDX_GROUPS_BONDS 12
+#define MDX_GROUPS_PATTERNS 32
+#define MDX_GROUPS_RECORD 90
+size_t mdx_mol_groups_ws_bytes(int32_t P);
+int mdx_mol_groups(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                   const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                   const int32_t* select, int32_t num_element, int32_t num_bond_types, const int32_t* normal_valence,
+                   const int32_t* patterns, int32_t P, int32_t max_steps, const int32_t* atom_ring_min, const int32_t* bond_ring_min,
+                   const int32_t* ring_status, int32_t* n_embed, int32_t* n_anchor, int32_t* steps, int32_t* pat_status,
+                   int32_t* status, int32_t* atom_hit, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -256,6 +256,34 @@ class FeaturizeMol(object):
         out.update(n_atoms=n_atoms, atom_ptr=ptrs[0], bond_ptr=ptrs[1])
         return out
 
+    def groups_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, patterns, graph=None, *, select=None,
+                     max_steps=None, normal_valence=None):
+        """``decode_batch``'s device part + the pattern counts of every decoded molecule (``mdx_mol_groups``, after ``mdx_mol_rings``
+        when a pattern carries a ring constraint; see ``moldiff_amd/groups.py``).  patterns: a ``groups.PatternSet`` made for this
+        featuriser.  Nothing is copied to the host and nothing synchronises.  select: (n_graphs) device tensor; a molecule with 0
+        keeps its place with status 0, n_atoms 0 and every count 0.  -> results dict: int32 device tensors status, n_atoms (B),
+        n_embed, n_anchor, steps, pat_status (B, P), atom_hit in the decode's own layout, molecule m at atom_ptr[m]; the set's
+        ``aut`` / ``names`` as numpy.  These are the molecules AS DECODED; the pattern language is this project's, not SMARTS.  Like
+        ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import groups
+        if tuple(patterns.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or patterns.num_bond_types != self.num_bond_types:
+            raise ValueError('the pattern set was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        max_steps = groups.DEFAULT_MAX_STEPS if max_steps is None else max_steps
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        dev = d['atom_type'].device
+        B = graph.B
+        if B == 0:
+            return {k: torch.from_numpy(v).to(dev) if k not in groups.SET_KEYS else v for k, v in groups.empty(patterns).items()}
+        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
+        n_atoms = d['n_atoms'][:B]
+        if select is not None:
+            select = select.to(dev, torch.int32).contiguous()
+            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
+        out = groups.launch(patterns, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1), d['bond_type'],
+                            d['bond_index'], int(d['bond_index'].shape[1]), normal_valence, max_steps, select=select)
+        out.update(n_atoms=n_atoms, atom_ptr=ptrs[0], aut=patterns.automorphisms(), names=np.asarray(patterns.names, dtype=str))
+        return out
+
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):
     """Split packed numpy outputs {'pred': [...], 'traj': [...]} per molecule (host, numpy -- like the reference)."""

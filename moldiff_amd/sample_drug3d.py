@@ -42,6 +42,10 @@ fingerprint file novelty and similarity against it -- beside ``samples_all.pt``.
 composition of the same FINISHED molecules on the device batch by batch (``moldiff_amd/rings.py``: ring sizes of a minimum cycle basis,
 not RDKit's SSSR; this project's rotatable-bond rule) and writes ``rings.npz`` (per-molecule arrays) and ``rings.json`` (their summary)
 beside ``samples_all.pt``.  Without the option nothing changes.
+``--groups [PATTERNS.yml]`` (config key ``sample.groups``: true or a path; the flag wins), an addition beyond the reference: rank 0 counts
+the functional groups of the same FINISHED molecules on the device batch by batch (``moldiff_amd/groups.py``: a substructure matcher
+with this project's own pattern language, not SMARTS; bare, the default set ``configs/groups_default.yml``) and writes ``groups.npz``
+(per-molecule arrays) and ``groups.json`` (their summary) beside ``samples_all.pt``.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -234,6 +238,23 @@ def add_rings_argument(ap):
     return ap
 
 
+def groups_option(flag, sample_cfg):
+    """(active, path of the pattern file or None = the default set) from the command line's value (None = not given, True = given
+    bare) and the config's ``sample`` section (``groups``: true or a path); the flag wins"""
+    value = flag if flag is not None else sample_cfg.get('groups')
+    if value is None or value is False or value == '':
+        return False, None
+    return True, (None if value is True else str(value))
+
+
+def add_groups_argument(ap):
+    """``--groups [PATTERNS.yml]`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--groups', nargs='?', const=True, default=None, metavar='PATTERNS.yml',
+                    help='count the functional groups of the finished molecules on the device and write groups.npz and groups.json; '
+                         'bare: the default pattern set configs/groups_default.yml (overrides sample.groups)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -261,7 +282,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = add_rings_argument(add_similarity_argument(build_parser())).parse_args(argv)
+    args = add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -332,6 +353,13 @@ def main(argv=None):
     rings_active, rings_parts = rings_option(args.rings, config.sample), []
     if rings_active:
         from . import rings
+    groups_active, groups_path = groups_option(args.groups, config.sample)
+    groups_set, groups_parts = None, []
+    if groups_active:   # read on every rank, so that a bad file stops all of them
+        from . import groups
+        atomic_numbers = featurizer.atomic_numbers.tolist()
+        groups_set = (groups.PatternSet.from_yaml(groups_path, atomic_numbers, featurizer.num_bond_types) if groups_path else
+                      groups.PatternSet.default(atomic_numbers, featurizer.num_bond_types))
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -419,6 +447,8 @@ def main(argv=None):
                 sim_set = fps if sim_set is None else sim_set.append(fps)
             if rings_active and gen:
                 rings_parts.append(rings.to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
+            if groups_set is not None and gen:
+                groups_parts.append(groups.to_host(groups.groups_mols(gen, device, groups_set)))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -440,6 +470,11 @@ def main(argv=None):
             rings.save(res, os.path.join(log_dir, 'rings.npz'))
             with open(os.path.join(log_dir, 'rings.json'), 'w') as f:
                 json.dump(rings.summary(res), f, indent=1)
+        if groups_set is not None:
+            res = groups.concat(groups_parts) if groups_parts else groups.empty(groups_set)
+            groups.save(res, os.path.join(log_dir, 'groups.npz'))
+            with open(os.path.join(log_dir, 'groups.json'), 'w') as f:
+                json.dump(groups.summary(res), f, indent=1)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),
