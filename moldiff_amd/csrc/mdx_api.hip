@@ -1911,23 +1911,16 @@ extern "C" int mdx_mol_local3d(int32_t B, const int32_t* atom_ptr, const int32_t
                                int32_t num_bond_types, const int32_t* select, const int32_t* patterns, const int32_t* kind_ptr,
                                const float* bin_range, const int32_t* bin_count, int64_t* hist, int64_t* outside, int64_t* n_items,
                                void* ws, size_t ws_bytes, void* stream) {
-  if (!atom_ptr || !bond_ptr || !n_atoms || !n_bonds || !atom_type || !atom_pos || !bond_type || !bond_index || !patterns ||
-      !kind_ptr || !bin_range || !bin_count || !hist || !outside || !n_items)
-    return fail(MDX_ERR_ARG, "null argument");
-  if (B < 0 || N_cap < 0 || Eh_stride < 0) return fail(MDX_ERR_ARG, "negative size");
-  if (N_cap > L3_MAX_ATOMS) return fail(MDX_ERR_UNSUPPORTED, "more than 2^24 atoms in one call");
   Local3DArgs a{};
-  const char* why = "";
+  const char* why = mol_arrays_fill(&a.mol, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, select);
+  if (why) return fail(MDX_ERR_ARG, "%s", why);
+  if (!atom_pos || !patterns || !kind_ptr || !bin_range || !bin_count || !hist || !outside || !n_items) return fail(MDX_ERR_ARG, "null argument");
+  if (N_cap > L3_MAX_ATOMS) return fail(MDX_ERR_UNSUPPORTED, "more than 2^24 atoms in one call");
   if (int rc = local3d_prepare(&a, patterns, kind_ptr, bin_range, bin_count, num_element, num_bond_types, &why)) return fail(rc, "%s", why);
   const size_t need = local3d_ws_bytes(N_cap, Eh_stride);
   if (!ws || ws_bytes < need) return fail(MDX_ERR_ARG, "workspace too small: need %zu bytes", need);
   if (reinterpret_cast<uintptr_t>(ws) & 3) return fail(MDX_ERR_ARG, "workspace must be 4-byte aligned");
-  a.B = B;
-  a.atom_ptr = atom_ptr, a.bond_ptr = bond_ptr, a.n_atoms = n_atoms, a.n_bonds = n_bonds;
-  a.atom_type = atom_type, a.atom_pos = atom_pos;
-  a.bond_type = bond_type, a.bond_i = bond_index, a.bond_j = bond_index + Eh_stride;
-  a.select = select;
-  a.N_cap = N_cap, a.E_cap = Eh_stride;
+  a.B = B, a.atom_pos = atom_pos;
   a.num_element = num_element, a.num_bond_types = num_bond_types;
   a.hist = reinterpret_cast<unsigned long long*>(hist), a.outside = reinterpret_cast<unsigned long long*>(outside);
   a.n_items = reinterpret_cast<long long*>(n_items);

@@ -4,7 +4,7 @@
 // output are DEFINED in include/moldiff_hip.h; it is this project's own, NOT SMARTS.  moldiff_amd/groups.py restates the function in
 // plain Python and the GPU tests compare every output exactly.
 //
-// One workgroup of 256 threads (4 waves) per molecule over the compact arrays mdx_mol_rings takes; a molecule has at most 256 atoms
+// One workgroup of 256 threads (4 waves) per molecule over the compact arrays of mdx_mol.h; a molecule has at most 256 atoms
 // and 512 bonds (the caps of mdx_mol_rings), so it is staged ONCE in LDS -- neighbour lists of 16-bit entries (neighbour, bond type,
 // ring class of the bond), one attribute word per atom (class, degree, implicit hydrogens, ring class, aromatic flag) -- with the
 // translated pattern table beside it, about 13 KB in all: the 8 workgroups a CU's 32 waves allow take 104 of its 160 KB, so occupancy
@@ -23,6 +23,7 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_groups_args.h"
+#include "mdx_mol.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
 
@@ -34,10 +35,9 @@ constexpr int GP_MOL_ATOMS = 256, GP_MOL_BONDS = 512, GP_WAVES = 4;
 constexpr int GP_CHUNK = 448;  // table words carried by one launch of the upload kernel, as kernel arguments
 
 struct GpArgs {
-  const int *atom_ptr, *bond_ptr, *n_atoms, *n_bonds, *atom_type, *bond_type, *bond_i, *bond_j, *select;
+  MolArrays mol;
   const int *atom_ring_min, *bond_ring_min, *ring_status;  // all three or none
   const unsigned* table;                                   // GP_WORDS * (1 + P) words (mdx_groups_args.h)
-  long long N_cap, E_cap;
   int num_element, num_bond_types, P, max_steps;
   int *n_embed, *n_anchor, *steps, *pat_status, *status, *atom_hit;
 };
@@ -60,23 +60,18 @@ __global__ __launch_bounds__(256) void groups_table_kernel(const GpChunkArgs c, 
   for (int k = threadIdx.x; k < count; k += 256) dst[k] = c.w[k];
 }
 
-__device__ inline int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ inline unsigned ring_class(int r) { return r <= 0 ? 0u : (unsigned)(min(max(r, 3), 8) - 2); }
 
 // status and zeros for a molecule that is not measured; its atom_hit slots only when they are inside the array
-__device__ inline void write_unmeasured(const GpArgs& A, int m, int status, bool slots, long long n0, int n) {
+__device__ inline void write_unmeasured(const GpArgs& A, int m, int status, const MolView& v) {
   const int tid = threadIdx.x;
   if (tid == 0) A.status[m] = status;
   for (int p = tid; p < A.P; p += 256) {
     const size_t o = (size_t)m * A.P + p;
     A.n_embed[o] = 0, A.n_anchor[o] = 0, A.steps[o] = 0, A.pat_status[o] = 0;
   }
-  if (!slots) return;
-  for (int a = tid; a < n; a += 256) A.atom_hit[n0 + a] = 0;
+  if (v.outside) return;
+  for (int a = tid; a < v.n; a += 256) A.atom_hit[v.n0 + a] = 0;
 }
 
 // aw: the pattern atom's word [9 + k], em: its elem_mask
@@ -103,23 +98,22 @@ __device__ inline bool used(u64 img, int d, unsigned v) {
 __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
   __shared__ GpShared s;
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long n0 = A.atom_ptr[m], h0 = A.bond_ptr[m];
-  const int n = A.n_atoms[m], nb = A.n_bonds[m];
-  // a molecule whose extent leaves the arrays (never from mdx_decode_output) or that is masked out: status 0, everything 0
-  const bool outside = n < 0 || nb < 0 || n0 < 0 || h0 < 0 || n0 + n > A.N_cap || h0 + nb > A.E_cap;
-  if (outside || (A.select && A.select[m] == 0)) {  // uniform
-    write_unmeasured(A, m, 0, !outside, n0, n);
+  const MolView v = mol_view(A.mol, m);
+  const long long n0 = v.n0, h0 = v.h0;
+  const int n = v.n, nb = v.nb;
+  if (v.outside || v.masked) {  // uniform: status 0, everything 0
+    write_unmeasured(A, m, 0, v);
     return;
   }
   if (n > GP_MOL_ATOMS || nb > GP_MOL_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, true, n0, n);
+    write_unmeasured(A, m, 1, v);
     return;
   }
   if (A.ring_status && A.ring_status[m] != 0) {  // uniform
-    write_unmeasured(A, m, 2, true, n0, n);
+    write_unmeasured(A, m, 2, v);
     return;
   }
-  const int *atype = A.atom_type + n0, *bi = A.bond_i + h0, *bj = A.bond_j + h0, *bt = A.bond_type + h0;
+  const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
   const int nbt = A.num_bond_types;
 
   // ---- the molecule and the table into LDS
@@ -128,8 +122,7 @@ __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
   __syncthreads();
   for (int e = tid; e < nb; e += 256) {
     const int i = bi[e], j = bj[e];
-    const bool valid = (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j;
-    if (!valid) {
+    if (!mol_bond_ok(i, j, n)) {
       s.bond[e] = 0u;
       continue;
     }
@@ -145,20 +138,8 @@ __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
     if (t == nbt) atomicOr(&s.attr[i], 1u << 14), atomicOr(&s.attr[j], 1u << 14);
   }
   __syncthreads();
-  {  // exclusive scan of the degrees; an atom past n has degree 0, so off[n] is the total whatever n is
-    const int deg = s.cur[tid];
-    int inc = deg;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
-    if (lane == 63) s.wave_total[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += s.wave_total[w];
-    s.off[tid] = before + inc - deg;
-    s.cur[tid] = before + inc - deg;
-    if (tid == 255) s.off[256] = before + inc;
+  {
+    const int deg = block_exclusive_scan_256(s.off, s.cur, s.wave_total);  // an atom past n has degree 0: off[n] is the total whatever n is
     if (tid < n) {
       const int cls = atype[tid];
       const bool known = (unsigned)cls < (unsigned)A.num_element;
@@ -267,8 +248,6 @@ __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
   if (tid == 0) A.status[m] = 0;
 }
 
-int fail(int code, const char* msg) { return mdx_set_error(code, msg); }
-
 }  // namespace
 
 extern "C" size_t mdx_mol_groups_ws_bytes(int32_t P) { return groups_ws_bytes(P); }
@@ -280,22 +259,23 @@ extern "C" int mdx_mol_groups(int32_t B, const int32_t* atom_ptr, const int32_t*
                               const int32_t* atom_ring_min, const int32_t* bond_ring_min, const int32_t* ring_status, int32_t* n_embed,
                               int32_t* n_anchor, int32_t* steps, int32_t* pat_status, int32_t* status, int32_t* atom_hit, void* ws,
                               size_t ws_bytes, void* stream) {
-  if (!atom_ptr || !bond_ptr || !n_atoms || !n_bonds || !atom_type || !bond_type || !bond_index || !normal_valence || !patterns ||
-      !n_embed || !n_anchor || !steps || !pat_status || !status || !atom_hit || !ws)
-    return fail(MDX_ERR_ARG, "null argument");
-  if (B < 0 || N_cap < 0 || Eh_stride < 0) return fail(MDX_ERR_ARG, "negative size");
-  if (max_steps < 1 || max_steps > GP_MAX_STEPS) return fail(MDX_ERR_ARG, "max_steps must lie in 1 .. 2^20");
+  GpArgs a{};
+  if (const char* why = mol_arrays_fill(&a.mol, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, select))
+    return mdx_set_error(MDX_ERR_ARG, why);
+  if (!normal_valence || !patterns || !n_embed || !n_anchor || !steps || !pat_status || !status || !atom_hit || !ws)
+    return mdx_set_error(MDX_ERR_ARG, "null argument");
+  if (max_steps < 1 || max_steps > GP_MAX_STEPS) return mdx_set_error(MDX_ERR_ARG, "max_steps must lie in 1 .. 2^20");
   const int given = (atom_ring_min != nullptr) + (bond_ring_min != nullptr) + (ring_status != nullptr);
-  if (given != 0 && given != 3) return fail(MDX_ERR_ARG, "atom_ring_min, bond_ring_min and ring_status: all three or none");
+  if (given != 0 && given != 3) return mdx_set_error(MDX_ERR_ARG, "atom_ring_min, bond_ring_min and ring_status: all three or none");
   uint32_t table[GP_TABLE_WORDS];
   bool needs_rings = false;
   const char* why = "";
   if (groups_prepare(table, normal_valence, patterns, P, num_element, num_bond_types, &needs_rings, &why) != GP_PREP_OK)
-    return fail(MDX_ERR_ARG, why);
-  if (needs_rings && given == 0) return fail(MDX_ERR_ARG, "a pattern carries a ring constraint and there is no ring data");
+    return mdx_set_error(MDX_ERR_ARG, why);
+  if (needs_rings && given == 0) return mdx_set_error(MDX_ERR_ARG, "a pattern carries a ring constraint and there is no ring data");
   const int words = GP_WORDS * (1 + P);
   if (((uintptr_t)ws & 3u) != 0 || ws_bytes < sizeof(uint32_t) * (size_t)words)
-    return fail(MDX_ERR_ARG, "workspace misaligned or smaller than mdx_mol_groups_ws_bytes");
+    return mdx_set_error(MDX_ERR_ARG, "workspace misaligned or smaller than mdx_mol_groups_ws_bytes");
   if (B == 0) return MDX_OK;
   for (int first = 0; first < words; first += GP_CHUNK) {
     GpChunkArgs c;
@@ -303,16 +283,11 @@ extern "C" int mdx_mol_groups(int32_t B, const int32_t* atom_ptr, const int32_t*
     for (int k = 0; k < GP_CHUNK; ++k) c.w[k] = k < count ? table[first + k] : 0u;
     hipLaunchKernelGGL(groups_table_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, c, (unsigned*)ws + first, count);
   }
-  GpArgs a{};
-  a.atom_ptr = atom_ptr, a.bond_ptr = bond_ptr, a.n_atoms = n_atoms, a.n_bonds = n_bonds;
-  a.atom_type = atom_type, a.bond_type = bond_type, a.bond_i = bond_index, a.bond_j = bond_index + Eh_stride;
-  a.select = select;
   a.atom_ring_min = atom_ring_min, a.bond_ring_min = bond_ring_min, a.ring_status = ring_status;
   a.table = (const unsigned*)ws;
-  a.N_cap = N_cap, a.E_cap = Eh_stride;
   a.num_element = num_element, a.num_bond_types = num_bond_types, a.P = P, a.max_steps = max_steps;
   a.n_embed = n_embed, a.n_anchor = n_anchor, a.steps = steps, a.pat_status = pat_status, a.status = status, a.atom_hit = atom_hit;
   hipLaunchKernelGGL(mol_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return fail(MDX_ERR_HIP, "mol_groups_kernel: launch failed");
+  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_groups_kernel: launch failed");
   return MDX_OK;
 }

@@ -3,8 +3,7 @@
 // SMARTS such as c:c, [#6]-[#7]-[#6] or c:c:c:c matched with uniquify = True; here it is the chain (element, bond type, element, ...)
 // of class indices and bond type ids, and the molecule is the one the decode wrote, not RDKit's reconstruction of it.
 //
-// One workgroup of 256 threads per molecule, reading compact arrays (atom classes and positions at atom_ptr[m] .. + n_atoms[m], bonds
-// at bond_ptr[m] .. + n_bonds[m], one direction per bond, molecule-local atom indices).
+// One workgroup of 256 threads per molecule over the compact arrays of mdx_mol.h, with a position per compact atom beside them.
 //
 // Items.  A length item is a bond (i, j).  An angle item is a centre b with two bond entries to neighbours a < c.  A dihedral item is
 // a central bond (b, c), visited once, with a bond entry b-a (a != c) and a bond entry c-d (d != b, d != a): all four atoms distinct
@@ -30,9 +29,6 @@
 namespace {
 
 constexpr float L3_DEG = 57.29577951308232f;  // 180 / pi, rounded to fp32
-
-__device__ inline int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct V3 {
   float x, y, z;
@@ -76,11 +72,10 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   __shared__ int s_carry;
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long* items_out = A.n_items + m;  // (3, B)
-  const long long n0 = A.atom_ptr[m], h0 = A.bond_ptr[m];
-  const int n = A.n_atoms[m], nb = A.n_bonds[m];
-  // a molecule that is masked out, or whose extent leaves the arrays (never from mdx_decode_output), contributes nothing
-  const bool skip = (A.select && A.select[m] == 0) || n < 0 || nb < 0 || n0 < 0 || h0 < 0 || n0 + n > A.N_cap || h0 + nb > A.E_cap;
-  if (skip) {  // uniform
+  const MolView v = mol_view(A.mol, m);
+  const long long n0 = v.n0, h0 = v.h0;
+  const int n = v.n, nb = v.nb;
+  if (v.masked || v.outside) {  // uniform: the molecule contributes nothing
     if (tid < 3) items_out[(size_t)tid * A.B] = 0;
     return;
   }
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   int* cur = small ? s_cur : A.ws_cur + n0;
   int* adj = small ? s_adj : A.ws_adj + 2 * h0;
   const float* pos = small ? s_pos : A.atom_pos + 3 * (size_t)n0;
-  const int* atype = A.atom_type + n0;
-  const int *bi = A.bond_i + h0, *bj = A.bond_j + h0, *bt = A.bond_type + h0;
+  const int* atype = A.mol.atom_type + n0;
+  const int *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
   const unsigned num_element = A.num_element, num_bond_types = A.num_bond_types;
   auto el = [&](int i) -> unsigned long long {
     if (small) return s_el[i];
@@ -120,10 +115,9 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   __syncthreads();
 
   // ---- adjacency: degrees -> exclusive scan -> fill -------------------------------------------------------------------------------
-  auto valid = [&](int i, int j) { return (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j; };
   for (int b = tid; b < nb; b += 256) {
     const int i = bi[b], j = bj[b];
-    if (!valid(i, j)) continue;
+    if (!mol_bond_ok(i, j, n)) continue;
     atomicAdd(&cur[i], 1);
     atomicAdd(&cur[j], 1);
   }
@@ -131,11 +125,7 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   for (int c0 = 0; c0 < n; c0 += 256) {
     const int i = c0 + tid;
     const int d = i < n ? ld(&cur[i]) : 0;
-    int incl = d;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
+    const int incl = wave_inclusive_scan(d);
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
     int off = s_carry;
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   }
   for (int b = tid; b < nb; b += 256) {
     const int i = bi[b], j = bj[b];
-    if (!valid(i, j)) continue;
+    if (!mol_bond_ok(i, j, n)) continue;
     const int k = (int)(bkey(bt[b]) << 24);
     st(&adj[atomicAdd(&cur[i], 1)], k | j);  // slots stay below 2 * (valid bonds) <= 2 * nb: the degrees counted the same bonds
     st(&adj[atomicAdd(&cur[j], 1)], k | i);
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(256) void mol_local3d_kernel(const Local3DArgs A) {
   unsigned long long cnt_len = 0, cnt_ang = 0, cnt_dih = 0;
   for (int b = tid; b < nb; b += 256) {
     const int i = bi[b], j = bj[b];
-    if (!valid(i, j)) continue;
+    if (!mol_bond_ok(i, j, n)) continue;
     const unsigned long long ei = el(i), ej = el(j), t = bkey(bt[b]);
     // ---- length -------------------------------------------------------------------------------------------------------------------
     ++cnt_len;

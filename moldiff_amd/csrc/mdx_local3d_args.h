@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mdx_mol.h"
+
 constexpr int L3_MAX_ROWS = 64;        // pattern rows per kind (the key table lives in LDS)
 constexpr int L3_LDS_ATOMS = 512;      // a molecule within both limits keeps its neighbour lists, positions and element keys in LDS
 constexpr int L3_LDS_BONDS = 2048;
@@ -13,12 +15,8 @@ constexpr int L3_MAX_ATOMS = 1 << 24;  // a neighbour-list entry is (bond key <<
 
 struct Local3DArgs {  // passed to the kernel by value (about 1.8 KB of kernel arguments)
   int B;
-  const int *atom_ptr, *bond_ptr, *n_atoms, *n_bonds;  // (B) each
-  const int* atom_type;                                 // class index per compact atom
-  const float* atom_pos;                                // (.,3)
-  const int *bond_type, *bond_i, *bond_j;               // molecule-local atom indices, one direction per bond
-  const int* select;                                    // (B) or nullptr
-  long long N_cap, E_cap;                               // extents of the atom / bond arrays: a molecule reaching past them is skipped
+  MolArrays mol;                                        // a molecule reaching past the extents is skipped
+  const float* atom_pos;                                // (.,3) per compact atom
   int num_element, num_bond_types;
   int kptr[4];                                          // rows of lengths | angles | dihedrals
   float lo[3], hi[3], scale[3];                         // scale = n / (hi - lo)

@@ -34,9 +34,7 @@ __device__ inline float dist3(const float* __restrict__ p, int a, int b) {
 }
 
 // Labels, fragment sizes and valences are updated with atomics, which a large molecule's global-memory arrays see in L2: they
-// are read back with agent-scope loads so that no read is served from a stale line of the CU's vector L1.
-__device__ inline int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// are read back with the agent-scope ld / st of mdx_mol.h so that no read is served from a stale line of the CU's vector L1.
 
 __global__ __launch_bounds__(256) void mol_check_kernel(
     const int* __restrict__ node_ptr, const int* __restrict__ he_ptr, const int* __restrict__ atom_type,

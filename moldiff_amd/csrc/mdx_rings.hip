@@ -5,7 +5,7 @@
 // restates it in plain Python and the GPU tests compare every output exactly.  The ring sizes are those of a minimum cycle basis, NOT
 // of RDKit's symmetrised SSSR (cubane: 5 four-rings here, 6 there).
 //
-// One workgroup of 256 threads (4 waves) per molecule over the compact arrays mdx_mol_fingerprint takes; a molecule has at most 256
+// One workgroup of 256 threads (4 waves) per molecule over the compact arrays of mdx_mol.h; a molecule has at most 256
 // atoms, 512 bonds and 64 independent rings, so everything lives in LDS (about 24 KB: 6 workgroups per CU by LDS, 8 by waves) and a
 // cycle is one 64-bit word.  The graph work is a breadth-first search that ONE WAVE runs on its own: lane l owns atoms l, l + 64,
 // l + 128, l + 192, and per level every unreached atom looks among its neighbours for one of the previous level ("pull": no queue, no
@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/moldiff_hip.h"
+#include "mdx_mol.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
 
@@ -41,8 +42,7 @@ constexpr unsigned short RG_FAR = 0xffff;  // depth of an atom not reached; pare
 constexpr int RG_INF = 1 << 30;
 
 struct RgArgs {
-  const int *atom_ptr, *bond_ptr, *n_atoms, *n_bonds, *atom_type, *bond_type, *bond_i, *bond_j, *select;
-  long long N_cap, E_cap;
+  MolArrays mol;
   int num_element, num_bond_types, ring_bins;
   int *n_rings, *ring_hist, *n_ring_atoms, *n_ring_bonds, *n_rotatable, *elem_count, *bond_count, *status, *bond_ring_min,
       *atom_ring_min;
@@ -65,13 +65,8 @@ struct RgShared {
   unsigned char triple[RG_ATOMS];            // the atom carries a bond of type 3
 };
 
-__device__ inline int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // status and zeros for a molecule that is not measured; its slots of the per-bond / per-atom arrays only when they are inside the arrays
-__device__ inline void write_unmeasured(const RgArgs& A, int m, int status, bool slots, long long n0, int n, long long h0, int nb) {
+__device__ inline void write_unmeasured(const RgArgs& A, int m, int status, const MolView& v) {
   const int tid = threadIdx.x;
   if (tid == 0) {
     A.status[m] = status;
@@ -80,9 +75,9 @@ __device__ inline void write_unmeasured(const RgArgs& A, int m, int status, bool
   for (int k = tid; k < A.ring_bins; k += 256) A.ring_hist[(size_t)m * A.ring_bins + k] = 0;
   for (int k = tid; k < A.num_element; k += 256) A.elem_count[(size_t)m * A.num_element + k] = 0;
   for (int k = tid; k < A.num_bond_types; k += 256) A.bond_count[(size_t)m * A.num_bond_types + k] = 0;
-  if (!slots) return;
-  for (int a = tid; a < n; a += 256) A.atom_ring_min[n0 + a] = 0;
-  for (int e = tid; e < nb; e += 256) A.bond_ring_min[h0 + e] = 0;
+  if (v.outside) return;
+  for (int a = tid; a < v.n; a += 256) A.atom_ring_min[v.n0 + a] = 0;
+  for (int e = tid; e < v.nb; e += 256) A.bond_ring_min[v.h0 + e] = 0;
 }
 
 // Levels of one wave's breadth-first search until nothing new is reached, or until `target` is.  depth[] holds 0 at the root(s) and
@@ -176,19 +171,18 @@ __device__ inline void insert_candidates(RgShared& s, int nb, int lane, const vo
 __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
   __shared__ RgShared s;
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long n0 = A.atom_ptr[m], h0 = A.bond_ptr[m];
-  const int n = A.n_atoms[m], nb = A.n_bonds[m];
-  // a molecule whose extent leaves the arrays (never from mdx_decode_output) or that is masked out: status 0, everything 0
-  const bool outside = n < 0 || nb < 0 || n0 < 0 || h0 < 0 || n0 + n > A.N_cap || h0 + nb > A.E_cap;
-  if (outside || (A.select && A.select[m] == 0)) {  // uniform
-    write_unmeasured(A, m, 0, !outside, n0, n, h0, nb);
+  const MolView v = mol_view(A.mol, m);
+  const long long n0 = v.n0, h0 = v.h0;
+  const int n = v.n, nb = v.nb;
+  if (v.outside || v.masked) {  // uniform: status 0, everything 0
+    write_unmeasured(A, m, 0, v);
     return;
   }
   if (n > RG_ATOMS || nb > RG_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, true, n0, n, h0, nb);
+    write_unmeasured(A, m, 1, v);
     return;
   }
-  const int *atype = A.atom_type + n0, *bi = A.bond_i + h0, *bj = A.bond_j + h0, *bt = A.bond_type + h0;
+  const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
 
   // ---- (a) adjacency lists and the two histograms
   s.cur[tid] = 0, s.triple[tid] = 0, s.elem[tid] = 0, s.btc[tid] = 0;
@@ -197,7 +191,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
   __syncthreads();
   for (int e = tid; e < nb; e += 256) {
     const int i = bi[e], j = bj[e], t = bt[e];
-    const bool valid = (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j;
+    const bool valid = mol_bond_ok(i, j, n);
     s.bond[e] = valid ? (unsigned)i | (unsigned)j << 8 | 1u << 16 : 0u;
     if (!valid) continue;
     atomicAdd(&s.cur[i], 1);
@@ -210,21 +204,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
     if ((unsigned)c < (unsigned)A.num_element) atomicAdd(&s.elem[c], 1);
   }
   __syncthreads();
-  {  // exclusive scan of the degrees; an atom past n has degree 0, so off[n] is the total whatever n is
-    const int deg = s.cur[tid];
-    int inc = deg;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
-    if (lane == 63) s.wave_total[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += s.wave_total[w];
-    s.off[tid] = before + inc - deg;
-    s.cur[tid] = before + inc - deg;
-    if (tid == 255) s.off[256] = before + inc;
-  }
+  block_exclusive_scan_256(s.off, s.cur, s.wave_total);  // the degrees: an atom past n has 0, so off[n] is the total whatever n is
   __syncthreads();
   for (int e = tid; e < nb; e += 256) {
     const unsigned bd = s.bond[e];
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
   // without two bonds between one pair of atoms the two agree; with them (a precondition violation) the smaller guards the bit index
   const int mu = s.scal[S_MU], n_rings = s.scal[S_NRINGS];
   if (mu > RG_RINGS || n_rings > RG_RINGS) {  // uniform
-    write_unmeasured(A, m, 2, true, n0, n, h0, nb);
+    write_unmeasured(A, m, 2, v);
     return;
   }
 
@@ -372,8 +352,6 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
   for (int k = tid; k < A.num_bond_types; k += 256) A.bond_count[(size_t)m * A.num_bond_types + k] = s.btc[k];
 }
 
-int fail(int code, const char* msg) { return mdx_set_error(code, msg); }
-
 }  // namespace
 
 extern "C" int mdx_mol_rings(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
@@ -382,23 +360,20 @@ extern "C" int mdx_mol_rings(int32_t B, const int32_t* atom_ptr, const int32_t* 
                              int32_t* n_rings, int32_t* ring_hist, int32_t* n_ring_atoms, int32_t* n_ring_bonds, int32_t* n_rotatable,
                              int32_t* elem_count, int32_t* bond_count, int32_t* status, int32_t* bond_ring_min, int32_t* atom_ring_min,
                              void* stream) {
-  if (!atom_ptr || !bond_ptr || !n_atoms || !n_bonds || !atom_type || !bond_type || !bond_index || !n_rings || !ring_hist ||
-      !n_ring_atoms || !n_ring_bonds || !n_rotatable || !elem_count || !bond_count || !status || !bond_ring_min || !atom_ring_min)
-    return fail(MDX_ERR_ARG, "null argument");
-  if (B < 0 || N_cap < 0 || Eh_stride < 0) return fail(MDX_ERR_ARG, "negative size");
-  if (ring_bins < 1 || ring_bins > RG_RINGS) return fail(MDX_ERR_ARG, "ring_bins must lie in 1 .. 64");
-  if (num_element < 1 || num_element > RG_MAX_ELEMENTS || num_bond_types < 1 || num_bond_types > RG_MAX_BOND_TYPES)
-    return fail(MDX_ERR_ARG, "num_element must lie in 1 .. 255 and num_bond_types in 1 .. 254");
   RgArgs a{};
-  a.atom_ptr = atom_ptr, a.bond_ptr = bond_ptr, a.n_atoms = n_atoms, a.n_bonds = n_bonds;
-  a.atom_type = atom_type, a.bond_type = bond_type, a.bond_i = bond_index, a.bond_j = bond_index + Eh_stride;
-  a.select = select;
-  a.N_cap = N_cap, a.E_cap = Eh_stride;
+  if (const char* why = mol_arrays_fill(&a.mol, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, select))
+    return mdx_set_error(MDX_ERR_ARG, why);
+  if (!n_rings || !ring_hist || !n_ring_atoms || !n_ring_bonds || !n_rotatable || !elem_count || !bond_count || !status || !bond_ring_min ||
+      !atom_ring_min)
+    return mdx_set_error(MDX_ERR_ARG, "null argument");
+  if (ring_bins < 1 || ring_bins > RG_RINGS) return mdx_set_error(MDX_ERR_ARG, "ring_bins must lie in 1 .. 64");
+  if (num_element < 1 || num_element > RG_MAX_ELEMENTS || num_bond_types < 1 || num_bond_types > RG_MAX_BOND_TYPES)
+    return mdx_set_error(MDX_ERR_ARG, "num_element must lie in 1 .. 255 and num_bond_types in 1 .. 254");
   a.num_element = num_element, a.num_bond_types = num_bond_types, a.ring_bins = ring_bins;
   a.n_rings = n_rings, a.ring_hist = ring_hist, a.n_ring_atoms = n_ring_atoms, a.n_ring_bonds = n_ring_bonds;
   a.n_rotatable = n_rotatable, a.elem_count = elem_count, a.bond_count = bond_count, a.status = status;
   a.bond_ring_min = bond_ring_min, a.atom_ring_min = atom_ring_min;
   if (B > 0) hipLaunchKernelGGL(mol_rings_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return fail(MDX_ERR_HIP, "mol_rings_kernel: launch failed");
+  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_rings_kernel: launch failed");
   return MDX_OK;
 }

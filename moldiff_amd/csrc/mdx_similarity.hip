@@ -4,7 +4,7 @@
 // utils/scoring_func.py:102-223): uniqueness, diversity, similarity to and novelty against a reference set.  The functions are
 // DEFINED in include/moldiff_hip.h; moldiff_amd/similarity.py restates them in numpy and the GPU tests compare bit for bit.
 //
-// Fingerprint.  One workgroup of 256 threads per molecule over the compact arrays mdx_mol_local3d takes.  Two arrays of one uint32
+// Fingerprint.  One workgroup of 256 threads per molecule over the compact arrays of mdx_mol.h.  Two arrays of one uint32
 // per atom, `id` (the atom's identifier of the current round) and `acc` (the wrapping sum over its bonds of the hashed neighbour
 // identifiers), play ping-pong: a bond pass reads id and adds into acc with one integer atomic per bond end, an atom pass reads both,
 // writes the next id and clears acc.  A wrapping integer sum does not depend on the order the atomics land in, so there are no
@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "../../include/moldiff_hip.h"
+#include "mdx_mol.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
 
@@ -39,9 +40,7 @@ constexpr int FP_MAX_ROUNDS = 64;
 constexpr unsigned FP_GOLD = 0x9e3779b9u, FP_PRIME = 0x01000193u, FP_HI = 0x5bd1e995u;
 
 struct FpArgs {
-  int B;
-  const int *atom_ptr, *bond_ptr, *n_atoms, *n_bonds, *atom_type, *bond_type, *bond_i, *bond_j, *select;
-  long long N_cap, E_cap;
+  MolArrays mol;
   int radius, key_rounds, nbits;
   unsigned* bits;   // (B, nbits / 32)
   int* n_on;        // (B)
@@ -58,33 +57,12 @@ __device__ inline unsigned mix(unsigned h) {  // murmur3 fmix32
   return h;
 }
 
-__device__ inline unsigned wave_sum(unsigned v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// LDS: plain accesses between barriers.  Global: agent-scope accesses, so that no load is served from a line the CU cached before
-// another thread's atomic changed it.
-template <bool LDS>
-__device__ inline unsigned ld(const unsigned* p) {
-  if constexpr (LDS) return *p;
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool LDS>
-__device__ inline void st(unsigned* p, unsigned v) {
-  if constexpr (LDS)
-    *p = v;
-  else
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the rounds of one molecule; returns this thread's share of (key_lo, key_hi) and sets the bits of rounds 0 .. radius in s_bits
+// the rounds of one molecule (LDS: id and acc are in LDS, else in global memory: ld / st of mdx_mol.h); returns this thread's share of (key_lo, key_hi) and sets the bits of rounds 0 .. radius in s_bits
 template <bool LDS>
 __device__ inline void fp_rounds(const FpArgs& A, unsigned* id, unsigned* acc, unsigned* s_bits, int n, int nb, const int* atype,
                                  const int* bi, const int* bj, const int* bt, unsigned& klo, unsigned& khi) {
   const int tid = threadIdx.x;
   const unsigned nbits = (unsigned)A.nbits;
-  auto valid = [&](int i, int j) { return (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j; };
   auto tally = [&](unsigned v, int r) {
     if (r <= A.radius) atomicOr(&s_bits[(v % nbits) >> 5], 1u << (v & 31u));  // nbits % 32 == 0: (v % nbits) % 32 == v % 32
     klo += mix(v + (unsigned)r);
@@ -94,7 +72,7 @@ __device__ inline void fp_rounds(const FpArgs& A, unsigned* id, unsigned* acc, u
   __syncthreads();
   for (int b = tid; b < nb; b += 256) {  // degrees
     const int i = bi[b], j = bj[b];
-    if (!valid(i, j)) continue;
+    if (!mol_bond_ok(i, j, n)) continue;
     atomicAdd(&acc[i], 1u);
     atomicAdd(&acc[j], 1u);
   }
@@ -109,7 +87,7 @@ __device__ inline void fp_rounds(const FpArgs& A, unsigned* id, unsigned* acc, u
   for (int r = 0; r < A.key_rounds; ++r) {
     for (int b = tid; b < nb; b += 256) {
       const int i = bi[b], j = bj[b];
-      if (!valid(i, j)) continue;
+      if (!mol_bond_ok(i, j, n)) continue;
       const unsigned t = FP_GOLD * (unsigned)bt[b];
       atomicAdd(&acc[i], mix(ld<LDS>(&id[j]) + t));
       atomicAdd(&acc[j], mix(ld<LDS>(&id[i]) + t));
@@ -129,11 +107,10 @@ __global__ __launch_bounds__(256) void mol_fingerprint_kernel(const FpArgs A) {
   __shared__ unsigned s_id[FP_LDS_ATOMS], s_acc[FP_LDS_ATOMS], s_bits[FP_MAX_WORDS], s_red[3];
   const int m = blockIdx.x, tid = threadIdx.x, W = A.nbits >> 5;
   unsigned* row = A.bits + (size_t)m * W;
-  const long long n0 = A.atom_ptr[m], h0 = A.bond_ptr[m];
-  const int n = A.n_atoms[m], nb = A.n_bonds[m];
-  // a molecule that is masked out, or whose extent leaves the arrays (never from mdx_decode_output): zero row, n_on 0, key 0
-  const bool skip = (A.select && A.select[m] == 0) || n < 0 || nb < 0 || n0 < 0 || h0 < 0 || n0 + n > A.N_cap || h0 + nb > A.E_cap;
-  if (skip) {  // uniform
+  const MolView v = mol_view(A.mol, m);
+  const long long n0 = v.n0, h0 = v.h0;
+  const int n = v.n, nb = v.nb;
+  if (v.masked || v.outside) {  // uniform: zero row, n_on 0, key 0
     for (int w = tid; w < W; w += 256) row[w] = 0u;
     if (tid == 0) A.n_on[m] = 0, A.key[m] = 0;
     return;
@@ -142,7 +119,7 @@ __global__ __launch_bounds__(256) void mol_fingerprint_kernel(const FpArgs A) {
   if (tid < 3) s_red[tid] = 0u;
   // the first barrier inside fp_rounds orders these before the first atomicOr
   unsigned klo = 0u, khi = 0u;
-  const int *atype = A.atom_type + n0, *bi = A.bond_i + h0, *bj = A.bond_j + h0, *bt = A.bond_type + h0;
+  const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
   if (n <= FP_LDS_ATOMS)  // uniform
     fp_rounds<true>(A, s_id, s_acc, s_bits, n, nb, atype, bi, bj, bt, klo, khi);
   else
@@ -282,8 +259,6 @@ __global__ __launch_bounds__(256) void tanimoto_kernel(const TanArgs a) {
   }
 }
 
-int fail(int code, const char* msg) { return mdx_set_error(code, msg); }
-
 }  // namespace
 
 extern "C" size_t mdx_mol_fingerprint_ws_bytes(int64_t N_cap) { return 8 * (size_t)std::max<int64_t>(N_cap, 1); }
@@ -293,25 +268,20 @@ extern "C" int mdx_mol_fingerprint(int32_t B, const int32_t* atom_ptr, const int
                                    const int32_t* bond_index, int64_t Eh_stride, const int32_t* select, int32_t radius,
                                    int32_t key_rounds, int32_t nbits, int32_t* bits, int32_t* n_on, int64_t* key, void* ws,
                                    size_t ws_bytes, void* stream) {
-  if (!atom_ptr || !bond_ptr || !n_atoms || !n_bonds || !atom_type || !bond_type || !bond_index || !bits || !n_on || !key)
-    return fail(MDX_ERR_ARG, "null argument");
-  if (B < 0 || N_cap < 0 || Eh_stride < 0) return fail(MDX_ERR_ARG, "negative size");
-  if (nbits < 32 || nbits > 32 * FP_MAX_WORDS || nbits % 32) return fail(MDX_ERR_ARG, "nbits must be a multiple of 32 in 32 .. 32768");
-  if (radius < 0 || key_rounds < radius || key_rounds > FP_MAX_ROUNDS)
-    return fail(MDX_ERR_ARG, "rounds must satisfy 0 <= radius <= key_rounds <= 64");
-  if (!ws || ws_bytes < mdx_mol_fingerprint_ws_bytes(N_cap)) return fail(MDX_ERR_ARG, "workspace too small: need 8 * max(N_cap, 1) bytes");
-  if (reinterpret_cast<uintptr_t>(ws) & 3) return fail(MDX_ERR_ARG, "workspace must be 4-byte aligned");
   FpArgs a{};
-  a.B = B;
-  a.atom_ptr = atom_ptr, a.bond_ptr = bond_ptr, a.n_atoms = n_atoms, a.n_bonds = n_bonds;
-  a.atom_type = atom_type, a.bond_type = bond_type, a.bond_i = bond_index, a.bond_j = bond_index + Eh_stride;
-  a.select = select;
-  a.N_cap = N_cap, a.E_cap = Eh_stride;
+  if (const char* why = mol_arrays_fill(&a.mol, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, select))
+    return mdx_set_error(MDX_ERR_ARG, why);
+  if (!bits || !n_on || !key) return mdx_set_error(MDX_ERR_ARG, "null argument");
+  if (nbits < 32 || nbits > 32 * FP_MAX_WORDS || nbits % 32) return mdx_set_error(MDX_ERR_ARG, "nbits must be a multiple of 32 in 32 .. 32768");
+  if (radius < 0 || key_rounds < radius || key_rounds > FP_MAX_ROUNDS)
+    return mdx_set_error(MDX_ERR_ARG, "rounds must satisfy 0 <= radius <= key_rounds <= 64");
+  if (!ws || ws_bytes < mdx_mol_fingerprint_ws_bytes(N_cap)) return mdx_set_error(MDX_ERR_ARG, "workspace too small: need 8 * max(N_cap, 1) bytes");
+  if (reinterpret_cast<uintptr_t>(ws) & 3) return mdx_set_error(MDX_ERR_ARG, "workspace must be 4-byte aligned");
   a.radius = radius, a.key_rounds = key_rounds, a.nbits = nbits;
   a.bits = reinterpret_cast<unsigned*>(bits), a.n_on = n_on, a.key = reinterpret_cast<long long*>(key);
   a.ws_id = reinterpret_cast<unsigned*>(ws), a.ws_acc = a.ws_id + std::max<int64_t>(N_cap, 1);
   if (B > 0) hipLaunchKernelGGL(mol_fingerprint_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return fail(MDX_ERR_HIP, "mol_fingerprint_kernel: launch failed");
+  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_fingerprint_kernel: launch failed");
   return MDX_OK;
 }
 
@@ -320,15 +290,15 @@ extern "C" size_t mdx_fp_tanimoto_ws_bytes(int64_t Na) { return 8 * (size_t)std:
 extern "C" int mdx_fp_tanimoto(const int32_t* bits_a, const int32_t* n_on_a, int64_t Na, const int32_t* bits_b, const int32_t* n_on_b,
                                int64_t Nb, int32_t nbits, int32_t exclude_diagonal, float* row_max, int32_t* row_argmax,
                                int64_t* row_sum, void* ws, size_t ws_bytes, void* stream) {
-  if (Na < 0 || Nb < 0) return fail(MDX_ERR_ARG, "negative size");
-  if (nbits < 32 || nbits > 32 * FP_MAX_WORDS || nbits % 32) return fail(MDX_ERR_ARG, "nbits must be a multiple of 32 in 32 .. 32768");
-  if (exclude_diagonal && Na != Nb) return fail(MDX_ERR_ARG, "exclude_diagonal needs Na == Nb");
-  if (Nb > (1ll << 22)) return fail(MDX_ERR_UNSUPPORTED, "more than 2^22 columns: row_sum could leave int64");
-  if (Na > (1ll << 30)) return fail(MDX_ERR_UNSUPPORTED, "more than 2^30 rows");
+  if (Na < 0 || Nb < 0) return mdx_set_error(MDX_ERR_ARG, "negative size");
+  if (nbits < 32 || nbits > 32 * FP_MAX_WORDS || nbits % 32) return mdx_set_error(MDX_ERR_ARG, "nbits must be a multiple of 32 in 32 .. 32768");
+  if (exclude_diagonal && Na != Nb) return mdx_set_error(MDX_ERR_ARG, "exclude_diagonal needs Na == Nb");
+  if (Nb > (1ll << 22)) return mdx_set_error(MDX_ERR_UNSUPPORTED, "more than 2^22 columns: row_sum could leave int64");
+  if (Na > (1ll << 30)) return mdx_set_error(MDX_ERR_UNSUPPORTED, "more than 2^30 rows");
   if ((Na > 0 && (!bits_a || !n_on_a || !row_max || !row_argmax || !row_sum)) || (Nb > 0 && (!bits_b || !n_on_b)))
-    return fail(MDX_ERR_ARG, "null argument");
-  if (!ws || ws_bytes < mdx_fp_tanimoto_ws_bytes(Na)) return fail(MDX_ERR_ARG, "workspace too small: need 8 * max(Na, 1) bytes");
-  if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(MDX_ERR_ARG, "workspace must be 8-byte aligned");
+    return mdx_set_error(MDX_ERR_ARG, "null argument");
+  if (!ws || ws_bytes < mdx_fp_tanimoto_ws_bytes(Na)) return mdx_set_error(MDX_ERR_ARG, "workspace too small: need 8 * max(Na, 1) bytes");
+  if (reinterpret_cast<uintptr_t>(ws) & 7) return mdx_set_error(MDX_ERR_ARG, "workspace must be 8-byte aligned");
   if (Na == 0) return MDX_OK;
   TanArgs a{};
   a.A = reinterpret_cast<const unsigned*>(bits_a), a.Bm = reinterpret_cast<const unsigned*>(bits_b);
@@ -347,6 +317,6 @@ extern "C" int mdx_fp_tanimoto(const int32_t* bits_a, const int32_t* n_on_a, int
     hipLaunchKernelGGL(tanimoto_kernel, dim3((unsigned)row_tiles, gy), dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL(tanimoto_finish_kernel, dim3(flat), dim3(256), 0, s, a);
-  if (hipGetLastError() != hipSuccess) return fail(MDX_ERR_HIP, "tanimoto kernels: launch failed");
+  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "tanimoto kernels: launch failed");
   return MDX_OK;
 }

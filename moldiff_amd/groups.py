@@ -33,13 +33,12 @@ import argparse
 import json
 import os
 import sys
-import types
 
 import numpy as np
 
 from . import rings
 from .local3d import jsd_counts
-from .similarity import DEFAULT_ATOMIC_NUMBERS, _host, _mol_graph
+from .molpack import check_simple, CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
 
 MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
 PAT_ATOMS, PAT_BONDS, MAX_PATTERNS, RECORD = 8, 12, 32, 90        # include/moldiff_hip.h: MDX_GROUPS_*
@@ -321,7 +320,7 @@ def groups_ref(info, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS,
     max_steps = _check_steps(max_steps)
     nv = pset.valence_table(normal_valence)
     nbt = pset.num_bond_types
-    cls, bi, bt = _mol_graph(info, types.SimpleNamespace(atomic_numbers=pset.atomic_numbers))
+    cls, bi, bt = mol_graph(info, pset.atomic_numbers)
     n, nb, P = len(cls), bi.shape[1], len(pset)
     bonds = [(e, int(bi[0, e]), int(bi[1, e])) for e in range(nb) if 0 <= bi[0, e] < n and 0 <= bi[1, e] < n and bi[0, e] != bi[1, e]]
     pairs = [(min(x, y), max(x, y)) for _, x, y in bonds]
@@ -411,36 +410,31 @@ def stack_ref(mols, patterns=None, normal_valence=None, max_steps=DEFAULT_MAX_ST
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
 
-def launch(patterns, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, normal_valence=None,
-           max_steps=DEFAULT_MAX_STEPS, select=None, ring_data=None):
-    """``mdx_mol_groups`` on device tensors (int32, contiguous) -> dict of int32 device tensors: status (B), n_embed / n_anchor / steps /
+def launch(cm, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS, select=None, ring_data=None):
+    """``mdx_mol_groups`` on the device arrays `cm` (a ``CompactMols``) -> dict of int32 device tensors: status (B), n_embed / n_anchor / steps /
     pat_status (B, P) and ``atom_hit`` (N_cap) in the layout of the inputs, zero where no molecule has a slot; no sync.  ring_data: the
     dict ``rings.launch`` returned for the same arrays; when None and a pattern carries a ring constraint, ``rings.launch`` runs first;
     False = none, which a set with a ring constraint refuses."""
     import torch
     from . import _lib
     pset, max_steps = patterns, _check_steps(max_steps)
-    P, dev = len(pset), n_atoms.device
+    P, B, dev = len(pset), cm.B, cm.device
     z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    out = {'status': z(B), 'n_embed': z(B, P), 'n_anchor': z(B, P), 'steps': z(B, P), 'pat_status': z(B, P), 'atom_hit': z(max(N_cap, 1))}
+    out = {'status': z(B), 'n_embed': z(B, P), 'n_anchor': z(B, P), 'steps': z(B, P), 'pat_status': z(B, P), 'atom_hit': z(max(cm.N_cap, 1))}
     if B == 0:
         return out
     if ring_data is False:
         _no_ring_data(pset)
         ring_data = None
     elif ring_data is None and pset.needs_rings:
-        ring_data = rings.launch(B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride,
-                                 len(pset.atomic_numbers), pset.num_bond_types, select=select)
+        ring_data = rings.launch(cm, len(pset.atomic_numbers), pset.num_bond_types, select=select)
     table, nv = pset.pack(), pset.valence_table(normal_valence)
     L = _lib.lib()
     ws = torch.empty(L.mdx_mol_groups_ws_bytes(P), dtype=torch.uint8, device=dev)
-    # an empty tensor has no address and a NULL operand is refused: an array nothing will be read from is stood in for by 8 spare bytes
-    spare = torch.zeros(1, dtype=torch.int64, device=dev)
-    at = lambda t: _lib.ptr(t if t.numel() else spare)
+    ops, at = cm.operands()
     rd = (lambda k: at(ring_data[k])) if ring_data is not None else (lambda k: None)
     _lib.check(L.mdx_mol_groups(
-        B, at(atom_ptr), at(bond_ptr), at(n_atoms), at(n_bonds), at(atom_type), N_cap, at(bond_type), at(bond_index), Eh_stride,
-        _lib.ptr(select), len(pset.atomic_numbers), pset.num_bond_types, nv.ctypes.data, table.ctypes.data, P, max_steps,
+        *ops, _lib.ptr(select), len(pset.atomic_numbers), pset.num_bond_types, nv.ctypes.data, table.ctypes.data, P, max_steps,
         rd('atom_ring_min'), rd('bond_ring_min'), rd('status'), at(out['n_embed']), at(out['n_anchor']), at(out['steps']),
         at(out['pat_status']), at(out['status']), at(out['atom_hit']), _lib.ptr(ws), ws.numel(), _lib.stream()))
     return out
@@ -452,32 +446,16 @@ def groups_mols(mols, device, patterns=None, normal_valence=None, max_steps=DEFA
     patterns: a PatternSet, a YAML path, a dict, or None for the default set.  -> the results dict of ``stack_ref`` with device tensors
     (``aut`` / ``names`` stay numpy).  Two bonds between the same pair of atoms and unknown elements raise ValueError."""
     import torch
-    from .similarity import pack_mols
     device = torch.device(device)
     pset = _patterns(patterns)
     _check_steps(max_steps)
-    p = pack_mols(mols, types.SimpleNamespace(atomic_numbers=pset.atomic_numbers))
-    N, E = int(p['n_atoms'].sum()), int(p['n_bonds'].sum())
-    if N >= (1 << 31) or E >= (1 << 31):
-        raise ValueError('2^31 atoms or bonds in one call: split the list')
-    for m in range(len(mols)):      # the precondition the device cannot report
-        b0, nb, n = int(p['bond_ptr'][m]), int(p['n_bonds'][m]), int(p['n_atoms'][m])
-        i, j = p['bond_index'][:, b0:b0 + nb].astype(np.int64)
-        ok = (i >= 0) & (i < n) & (j >= 0) & (j < n) & (i != j)
-        key = np.minimum(i, j)[ok] * max(n, 1) + np.maximum(i, j)[ok]
-        if len(np.unique(key)) != len(key):
-            raise ValueError(f'molecule {m}: two bonds between the same pair of atoms')
-    d = {k: torch.from_numpy(v).to(device) for k, v in p.items()}
-    out = launch(pset, len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'],
-                 d['bond_index'], int(d['bond_index'].shape[1]), normal_valence, max_steps)
-    out['atom_hit'] = out['atom_hit'][:N]
-    out.update(n_atoms=d['n_atoms'], atom_ptr=d['atom_ptr'], aut=pset.automorphisms(), names=np.asarray(pset.names, dtype=str))
+    p = pack_mols(mols, pset.atomic_numbers)
+    check_simple(p)
+    cm = CompactMols.from_packed(to_device(p, device))
+    out = launch(cm, pset, normal_valence, max_steps)
+    out['atom_hit'] = out['atom_hit'][:cm.N_cap]
+    out.update(n_atoms=cm.n_atoms, atom_ptr=cm.atom_ptr, aut=pset.automorphisms(), names=np.asarray(pset.names, dtype=str))
     return out
-
-
-def to_host(results):
-    """a results dict with numpy arrays"""
-    return {k: np.ascontiguousarray(_host(v)) for k, v in results.items()}
 
 
 def concat(parts):
@@ -490,16 +468,6 @@ def concat(parts):
     out['atom_ptr'] = (np.cumsum(na) - na).astype(np.int32)
     out['aut'], out['names'] = parts[0]['aut'], parts[0]['names']
     return out
-
-
-def save(results, path):
-    with open(path, 'wb') as f:   # a file object: numpy appends no suffix
-        np.savez(f, **to_host(results))
-
-
-def load(path):
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
 
 
 def empty(patterns=None):
@@ -550,12 +518,6 @@ def compare(a, b):
 
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
-def _load_mols(path, part):
-    import torch
-    pool = torch.load(path, map_location='cpu', weights_only=False)
-    return list(pool[part]) if isinstance(pool, dict) else list(pool)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m moldiff_amd.groups', description=__doc__.split('\n\n')[0])
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -572,17 +534,17 @@ def main(argv=None):
     c.add_argument('b')
     args = ap.parse_args(argv)
     if args.cmd == 'stats':
-        mols, pset = _load_mols(args.samples, args.part), _patterns(args.patterns)
+        mols, pset = load_mols(args.samples, args.part), _patterns(args.patterns)
         if args.ref:
             res = stack_ref(mols, pset, max_steps=args.max_steps)
         else:
             import torch
             torch.cuda.set_device(torch.device(args.device))
             res = groups_mols(mols, args.device, pset, max_steps=args.max_steps)
-        save(res, args.out)
+        save_npz(res, args.out)
         print(json.dumps(summary(res), indent=1))
     else:
-        print(json.dumps(compare(load(args.a), load(args.b)), indent=1))
+        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
     return 0
 
 

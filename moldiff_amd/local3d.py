@@ -27,17 +27,17 @@ No trained checkpoint is available offline, so this is an instrument: nothing he
     python -m moldiff_amd.local3d frequent samples_all.pt [--top 20]        # writes a patterns.yml to stdout
 """
 import argparse
-import ctypes
 import json
 import sys
 from collections import Counter
 
 import numpy as np
 
+from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, host, load_mols, mol_graph, pack_mols, to_device
+
 KINDS = ('lengths', 'angles', 'dihedrals')
 BOND_SYMBOL = {1: '-', 2: '=', 3: '#', 4: ':'}
 ELEMENT_SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}   # the featuriser's atomic numbers
-DEFAULT_ATOMIC_NUMBERS = (6, 7, 8, 9, 15, 16, 17)
 MAX_PATTERNS = 64          # per kind: the device keeps the table in LDS
 _FIELDS = {'lengths': 3, 'angles': 5, 'dihedrals': 7}
 
@@ -182,25 +182,11 @@ class Local3DSpec:
 
 # ---- one molecule on the host --------------------------------------------------------------------------------------------------------
 
-def _mol_arrays(info):
-    """element (n), positions (n,3) float64, bonds once each: (2,b) indices and (b) types, the ignored ones dropped"""
-    ele = np.asarray(info['element'], dtype=np.int64).reshape(-1)
-    n = int(ele.shape[0])
-    pos = np.asarray(info['atom_pos'], dtype=np.float64).reshape(n, 3)
-    if 'bond_index' in info and np.asarray(info['bond_index']).size:
-        bi = np.asarray(info['bond_index'], dtype=np.int64)
-        nb = bi.shape[1] // 2
-        bi, bt = bi[:, :nb], np.asarray(info['bond_type'], dtype=np.int64)[:nb]
-    else:
-        bi, bt = np.zeros((2, 0), dtype=np.int64), np.zeros(0, dtype=np.int64)
-    return ele, pos, bi, bt
-
-
 def enumerate_items(info):
     """Every item of one molecule dict -> {kind: (atoms (k, 2|3|4) int64, chains (k, 3|5|7) int64 over atomic numbers and bond ids)}.
     Bonds with an index outside the molecule or with i = j are ignored.  Angles: centre b, neighbours a < c.  Dihedrals: each bond
     once as the central bond b-c, a over b's other neighbours, d over c's neighbours other than b and a."""
-    ele, pos, bi, bt = _mol_arrays(info)
+    ele, bi, bt = mol_graph(info)
     n = len(ele)
     ok = (bi[0] >= 0) & (bi[0] < n) & (bi[1] >= 0) & (bi[1] < n) & (bi[0] != bi[1])
     bi, bt = bi[:, ok], bt[ok]
@@ -268,7 +254,7 @@ def local3d_ref(info, spec):
     (2, 2b) with every bond once and then flipped, bond_type (2b)).  -> dict: ``values`` {kind: one float64 array per pattern},
     ``hist`` (flat int64, ``spec.hist_slice``'s layout, via ``numpy.histogram``), ``outside`` (one per pattern, all kinds in turn)
     and ``n_items`` (3: every enumerated item of the kind, matched or not)."""
-    _, pos, _, _ = _mol_arrays(info)
+    pos = np.asarray(info['atom_pos'], dtype=np.float64).reshape(np.asarray(info['element']).size, 3)
     items = enumerate_items(info)
     hist = np.zeros(spec.hist_size, dtype=np.int64)
     outside = np.zeros(spec.kind_ptr[3], dtype=np.int64)
@@ -316,10 +302,6 @@ def jsd_counts(p, q):
     return min(1.0, max(0.0, 0.5 * kl(p) + 0.5 * kl(q)))
 
 
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
-
-
 class Local3DStats:
     """Accumulated statistics: ``hist`` (flat int64, ``spec.hist_slice``'s layout), ``outside`` (one int64 per pattern), ``n_items``
     (3 int64: all enumerated items per kind, matched or not) and the ``spec``.  The arrays are numpy or, straight from the device
@@ -341,8 +323,8 @@ class Local3DStats:
         return out
 
     def cpu(self):
-        return Local3DStats(self.spec, _host(self.hist).astype(np.int64), _host(self.outside).astype(np.int64),
-                            _host(self.n_items).astype(np.int64))
+        return Local3DStats(self.spec, host(self.hist).astype(np.int64), host(self.outside).astype(np.int64),
+                            host(self.n_items).astype(np.int64))
 
     def __add__(self, other):
         if not isinstance(other, Local3DStats) or other.spec != self.spec:
@@ -352,10 +334,10 @@ class Local3DStats:
 
     def counts(self, kind, pattern):
         """the histogram row of one pattern (string or tuple, either direction) as a numpy array"""
-        return _host(self.hist)[self.spec.hist_slice(kind, self.spec.row_of(kind, pattern))].astype(np.int64)
+        return host(self.hist)[self.spec.hist_slice(kind, self.spec.row_of(kind, pattern))].astype(np.int64)
 
     def outside_of(self, kind, pattern):
-        return int(_host(self.outside)[self.spec.kind_ptr[KINDS.index(kind)] + self.spec.row_of(kind, pattern)])
+        return int(host(self.outside)[self.spec.kind_ptr[KINDS.index(kind)] + self.spec.row_of(kind, pattern)])
 
     def save(self, path):
         c = self.cpu()
@@ -389,61 +371,27 @@ def device_stats(spec, device):
     return Local3DStats(spec, z(spec.hist_size), z(spec.kind_ptr[3]), z(3))
 
 
-def launch(spec, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, atom_pos, N_cap, bond_type, bond_index, Eh_stride, out,
-           select=None, ws=None):
-    """``mdx_mol_local3d`` on device tensors (int32 / float32, contiguous), adding into the device Local3DStats `out`; no sync.
-    ws: (pointer, bytes) of a workspace, or None to allocate one."""
+def launch(cm, spec, out, select=None, ws=None):
+    """``mdx_mol_local3d`` on the device arrays `cm` (a ``CompactMols`` with atom_pos), adding into the device Local3DStats
+    `out`; no sync.  ws: (pointer, bytes) of a workspace, or None to allocate one."""
     import torch
     from . import _lib
     L = _lib.lib()
-    dev = atom_pos.device
+    B, dev = cm.B, cm.atom_pos.device
     if not all(torch.is_tensor(x) and x.device == dev and x.dtype == torch.int64 for x in (out.hist, out.outside, out.n_items)):
         raise ValueError('`out` must hold int64 tensors on the molecules\' device (local3d.device_stats)')
     if B == 0:
         return out
     rows, kptr, brange, bcount = spec.table()
-    need = L.mdx_mol_local3d_ws_bytes(N_cap, Eh_stride)
-    if ws is None or ws[1].value < need:
-        buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = (ctypes.c_void_p(buf.data_ptr()), ctypes.c_size_t(need))
+    ws = cm.workspace(L.mdx_mol_local3d_ws_bytes(cm.N_cap, cm.Eh_stride), ws, dev)
     n_items = torch.empty(3, B, dtype=torch.int64, device=dev)
-    # an empty tensor has no address and a NULL operand is refused: an array nothing will be read from or written to (no atoms, no
-    # half-edges, a spec without patterns) is stood in for by 8 spare bytes
-    spare = torch.zeros(1, dtype=torch.int64, device=dev)
-    at = lambda t: _lib.ptr(t if t.numel() else spare)
+    ops, at = cm.operands(positions=True)   # `at`: a spec without patterns has empty tables too
     _lib.check(L.mdx_mol_local3d(
-        B, at(atom_ptr), at(bond_ptr), at(n_atoms), at(n_bonds), at(atom_type), at(atom_pos), N_cap,
-        at(bond_type), at(bond_index), Eh_stride, len(spec.atomic_numbers), spec.num_bond_types, _lib.ptr(select),
-        rows.ctypes.data, kptr.ctypes.data, brange.ctypes.data, bcount.ctypes.data, at(out.hist), at(out.outside),
-        _lib.ptr(n_items), ws[0], ws[1], _lib.stream()))
+        *ops, len(spec.atomic_numbers), spec.num_bond_types, _lib.ptr(select), rows.ctypes.data, kptr.ctypes.data, brange.ctypes.data,
+        bcount.ctypes.data, at(out.hist), at(out.outside), _lib.ptr(n_items), ws[0], ws[1], _lib.stream()))
     out.n_items += n_items.sum(1)
     out.last_n_items = n_items     # per molecule, for callers that want it
     return out
-
-
-def pack_mols(mols, spec):
-    """a list of molecule dicts as the dense compact arrays of ``mdx_mol_local3d`` (numpy): atom_ptr, bond_ptr, n_atoms, n_bonds,
-    atom_type (class index), atom_pos (float32), bond_type, bond_index (2, max(total bonds, 1))"""
-    cls = {z: i for i, z in enumerate(spec.atomic_numbers)}
-    na, nb, at, ap, bt, bi = [], [], [], [], [], []
-    for info in mols:
-        ele, _, b_idx, b_typ = _mol_arrays(info)
-        unknown = sorted({int(z) for z in ele if int(z) not in cls})
-        if unknown:
-            raise ValueError(f'element(s) {unknown} are not among the spec\'s atomic numbers')
-        na.append(len(ele)), nb.append(b_idx.shape[1])
-        at.append(np.asarray([cls[int(z)] for z in ele], dtype=np.int32))
-        ap.append(np.asarray(info['atom_pos'], dtype=np.float32).reshape(len(ele), 3))
-        bt.append(b_typ.astype(np.int32)), bi.append(b_idx.astype(np.int32))
-    na, nb = np.asarray(na, dtype=np.int64), np.asarray(nb, dtype=np.int64)
-    ptr = lambda c: np.concatenate([[0], np.cumsum(c)[:-1]]).astype(np.int32) if len(c) else np.zeros(0, dtype=np.int32)
-    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dtype=dt)
-    bidx = np.concatenate(bi, axis=1) if bi else np.zeros((2, 0), dtype=np.int32)
-    if bidx.shape[1] == 0:
-        bidx = np.zeros((2, 1), dtype=np.int32)
-    return {'atom_ptr': ptr(na), 'bond_ptr': ptr(nb), 'n_atoms': na.astype(np.int32), 'n_bonds': nb.astype(np.int32),
-            'atom_type': cat(at, (0,), np.int32), 'atom_pos': cat(ap, (0, 3), np.float32), 'bond_type': cat(bt, (0,), np.int32),
-            'bond_index': np.ascontiguousarray(bidx)}
 
 
 def local3d_mols(mols, spec, device, out=None):
@@ -457,12 +405,10 @@ def local3d_mols(mols, spec, device, out=None):
         raise ValueError('`out` was made for another spec')
     if not len(mols):
         return out
-    p = pack_mols(mols, spec)
+    p = pack_mols(mols, spec.atomic_numbers, positions=True)
     if int(p['n_atoms'].sum()) > (1 << 24):
         raise ValueError('more than 2^24 atoms in one call: split the list')
-    d = {k: torch.from_numpy(v).to(device) for k, v in p.items()}
-    return launch(spec, len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], d['atom_pos'],
-                  int(p['n_atoms'].sum()), d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), out)
+    return launch(CompactMols.from_packed(to_device(p, device)), spec, out)
 
 
 # ---- command line --------------------------------------------------------------------------------------------------------------------
@@ -476,12 +422,6 @@ def compare_table(a, b):
             lines.append('%-10s %-24s %10d %10d %8.4f' % (kind, t, a.counts(kind, p).sum(), b.counts(kind, p).sum(), res[kind]['patterns'][t]))
         lines.append('%-10s %-24s %10s %10s %8.4f' % (kind, 'mean over non-empty', '', '', res[kind]['mean']))
     return '\n'.join(lines)
-
-
-def _load_mols(path, part):
-    import torch
-    pool = torch.load(path, map_location='cpu', weights_only=False)
-    return list(pool[part]) if isinstance(pool, dict) else list(pool)
 
 
 def main(argv=None):
@@ -505,14 +445,14 @@ def main(argv=None):
     if args.cmd == 'compare':
         print(compare_table(Local3DStats.load(args.a), Local3DStats.load(args.b)))
     elif args.cmd == 'frequent':
-        mols = _load_mols(args.samples, args.part)
+        mols = load_mols(args.samples, args.part)
         for kind in KINDS:
             print(f'{kind}:')
             for p, k in frequent_patterns(mols, kind, args.top):
                 print(f"  - '{pattern_text(p)}'   # {k}")
     else:
         spec = Local3DSpec.from_yaml(args.patterns)
-        mols = _load_mols(args.samples, args.part)
+        mols = load_mols(args.samples, args.part)
         if args.ref:
             stats = Local3DStats.from_ref(mols, spec)
         else:
@@ -520,7 +460,7 @@ def main(argv=None):
             torch.cuda.set_device(torch.device(args.device))
             stats = local3d_mols(mols, spec, args.device)
         stats.save(args.out)
-        print(f'{len(mols)} molecules -> {args.out}: items {_host(stats.n_items).tolist()} (lengths, angles, dihedrals)')
+        print(f'{len(mols)} molecules -> {args.out}: items {host(stats.n_items).tolist()} (lengths, angles, dihedrals)')
     return 0
 
 

@@ -178,21 +178,30 @@ class FeaturizeMol(object):
         from . import local3d
         if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
             raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
-        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
-        dev = d['atom_type'].device
+        cm, graph, select, _ = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if out is None:
-            out = local3d.device_stats(spec, dev)
+            out = local3d.device_stats(spec, cm.device)
         elif out.spec != spec:
             raise ValueError('`out` was made for another spec')
-        B = graph.B
-        if B == 0:
+        if cm.B == 0:
             return out
+        return local3d.launch(cm, spec, out, select=select, ws=graph.workspace(cm.device))
+
+    def _compact_mols(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select):
+        """The prologue of the ``*_batch`` methods below: ``mdx_decode_output``, then its compact tensors as the operands of an
+        evaluation entry point -> (cm: a ``molpack.CompactMols``; the graph; `select` as int32 on the device, or None; n_atoms (B) with
+        0 for a molecule `select` leaves out)."""
+        from .molpack import CompactMols
+        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
+        dev = d['atom_type'].device
         ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
+        n_atoms = d['n_atoms'][:graph.B]
         if select is not None:
             select = select.to(dev, torch.int32).contiguous()
-        return local3d.launch(spec, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], d['atom_pos'], max(graph.N, 1),
-                              d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), out, select=select,
-                              ws=graph.workspace(dev))
+            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
+        cm = CompactMols(graph.B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1), d['bond_type'],
+                         d['bond_index'], int(d['bond_index'].shape[1]), d['atom_pos'])
+        return cm, graph, select, n_atoms
 
     @staticmethod
     def _mol_ptrs(graph, batch_node, batch_halfedge, dev):
@@ -215,19 +224,10 @@ class FeaturizeMol(object):
         from . import similarity
         if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
             raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
-        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
-        dev = d['atom_type'].device
-        B = graph.B
-        if B == 0:
-            return similarity.FingerprintSet.empty(spec).to(dev)
-        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
-        n_atoms = d['n_atoms'][:B]
-        if select is not None:
-            select = select.to(dev, torch.int32).contiguous()
-            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
-        bits, n_on, key = similarity.launch(spec, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1),
-                                            d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), select=select,
-                                            ws=graph.workspace(dev))
+        cm, graph, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        if cm.B == 0:
+            return similarity.FingerprintSet.empty(spec).to(cm.device)
+        bits, n_on, key = similarity.launch(cm, spec, select=select, ws=graph.workspace(cm.device))
         return similarity.FingerprintSet(spec, bits, n_on, key, n_atoms)
 
     def rings_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, ring_bins=7, select=None):
@@ -239,21 +239,12 @@ class FeaturizeMol(object):
         These are the molecules AS DECODED; the ring sizes are those of a minimum cycle basis, not RDKit's SSSR.  Like
         ``decode_batch``, it needs a batch with at least one half-edge."""
         from . import rings
-        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
-        dev = d['atom_type'].device
-        B = graph.B
-        if B == 0:
-            return {k: torch.from_numpy(v).to(dev) for k, v in
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        if cm.B == 0:
+            return {k: torch.from_numpy(v).to(cm.device) for k, v in
                     rings.empty(self.num_bond_types, self.atomic_numbers.tolist(), ring_bins).items()}
-        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
-        n_atoms = d['n_atoms'][:B]
-        if select is not None:
-            select = select.to(dev, torch.int32).contiguous()
-            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
-        out = rings.launch(B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1), d['bond_type'],
-                           d['bond_index'], int(d['bond_index'].shape[1]), self.num_element, self.num_bond_types, ring_bins,
-                           select=select)
-        out.update(n_atoms=n_atoms, atom_ptr=ptrs[0], bond_ptr=ptrs[1])
+        out = rings.launch(cm, self.num_element, self.num_bond_types, ring_bins, select=select)
+        out.update(n_atoms=n_atoms, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
         return out
 
     def groups_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, patterns, graph=None, *, select=None,
@@ -269,19 +260,11 @@ class FeaturizeMol(object):
         if tuple(patterns.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or patterns.num_bond_types != self.num_bond_types:
             raise ValueError('the pattern set was made for another featuriser (atomic_numbers / num_bond_types differ)')
         max_steps = groups.DEFAULT_MAX_STEPS if max_steps is None else max_steps
-        graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
-        dev = d['atom_type'].device
-        B = graph.B
-        if B == 0:
-            return {k: torch.from_numpy(v).to(dev) if k not in groups.SET_KEYS else v for k, v in groups.empty(patterns).items()}
-        ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
-        n_atoms = d['n_atoms'][:B]
-        if select is not None:
-            select = select.to(dev, torch.int32).contiguous()
-            n_atoms = torch.where(select != 0, n_atoms, torch.zeros_like(n_atoms))
-        out = groups.launch(patterns, B, ptrs[0], ptrs[1], d['n_atoms'], d['n_bonds'], d['atom_type'], max(graph.N, 1), d['bond_type'],
-                            d['bond_index'], int(d['bond_index'].shape[1]), normal_valence, max_steps, select=select)
-        out.update(n_atoms=n_atoms, atom_ptr=ptrs[0], aut=patterns.automorphisms(), names=np.asarray(patterns.names, dtype=str))
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        if cm.B == 0:
+            return {k: torch.from_numpy(v).to(cm.device) if k not in groups.SET_KEYS else v for k, v in groups.empty(patterns).items()}
+        out = groups.launch(cm, patterns, normal_valence, max_steps, select=select)
+        out.update(n_atoms=n_atoms, atom_ptr=cm.atom_ptr, aut=patterns.automorphisms(), names=np.asarray(patterns.names, dtype=str))
         return out
 
 

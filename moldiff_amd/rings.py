@@ -27,12 +27,11 @@ With no trained checkpoint offline this is an instrument, not a measurement of q
 import argparse
 import json
 import sys
-import types
 
 import numpy as np
 
 from .local3d import jsd_counts
-from .similarity import DEFAULT_ATOMIC_NUMBERS, _host, _mol_graph
+from .molpack import check_simple, CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
 
 MAX_ATOMS, MAX_BONDS, MAX_RINGS = 256, 512, 64      # include/moldiff_hip.h: beyond them a molecule gets a status, not a result
 STATUS_OK, STATUS_TOO_LARGE, STATUS_TOO_MANY_RINGS = 0, 1, 2
@@ -76,7 +75,7 @@ def rings_ref(info, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, rin
     raise ValueError."""
     atomic_numbers = tuple(int(z) for z in atomic_numbers)
     _check_sizes(num_bond_types, len(atomic_numbers), ring_bins)
-    cls, bi, bt = _mol_graph(info, types.SimpleNamespace(atomic_numbers=atomic_numbers))
+    cls, bi, bt = mol_graph(info, atomic_numbers)
     n, nb = len(cls), bi.shape[1]
     bonds = [(e, int(bi[0, e]), int(bi[1, e])) for e in range(nb) if 0 <= bi[0, e] < n and 0 <= bi[1, e] < n and bi[0, e] != bi[1, e]]
     pairs = [(min(x, y), max(x, y)) for _, x, y in bonds]
@@ -171,27 +170,23 @@ def stack_ref(mols, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, rin
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
 
-def launch(B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, num_element, num_bond_types,
-           ring_bins=7, select=None):
-    """``mdx_mol_rings`` on device tensors (int32, contiguous) -> dict of int32 device tensors: the keys of MOL_KEYS but n_atoms, one
+def launch(cm, num_element, num_bond_types, ring_bins=7, select=None):
+    """``mdx_mol_rings`` on the device arrays `cm` (a ``CompactMols``) -> dict of int32 device tensors: the keys of MOL_KEYS but n_atoms, one
     entry (or row) per molecule, and ``bond_ring_min`` (Eh_stride) / ``atom_ring_min`` (N_cap) in the layout of the inputs, zero
     where no molecule has a slot; no sync"""
     import torch
     from . import _lib
     _check_sizes(num_bond_types, num_element, ring_bins)
-    dev = n_atoms.device
+    B, dev = cm.B, cm.device
     z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
     out = {'status': z(B), 'n_rings': z(B), 'ring_hist': z(B, ring_bins), 'n_ring_atoms': z(B), 'n_ring_bonds': z(B), 'n_rotatable': z(B),
-           'elem_count': z(B, num_element), 'bond_count': z(B, num_bond_types), 'bond_ring_min': z(max(Eh_stride, 1)),
-           'atom_ring_min': z(max(N_cap, 1))}
+           'elem_count': z(B, num_element), 'bond_count': z(B, num_bond_types), 'bond_ring_min': z(max(cm.Eh_stride, 1)),
+           'atom_ring_min': z(max(cm.N_cap, 1))}
     if B == 0:
         return out
-    # an empty tensor has no address and a NULL operand is refused: an array nothing will be read from is stood in for by 8 spare bytes
-    spare = torch.zeros(1, dtype=torch.int64, device=dev)
-    at = lambda t: _lib.ptr(t if t.numel() else spare)
+    ops, at = cm.operands()
     _lib.check(_lib.lib().mdx_mol_rings(
-        B, at(atom_ptr), at(bond_ptr), at(n_atoms), at(n_bonds), at(atom_type), N_cap, at(bond_type), at(bond_index), Eh_stride,
-        _lib.ptr(select), num_element, num_bond_types, ring_bins, at(out['n_rings']), at(out['ring_hist']), at(out['n_ring_atoms']),
+        *ops, _lib.ptr(select), num_element, num_bond_types, ring_bins, at(out['n_rings']), at(out['ring_hist']), at(out['n_ring_atoms']),
         at(out['n_ring_bonds']), at(out['n_rotatable']), at(out['elem_count']), at(out['bond_count']), at(out['status']),
         at(out['bond_ring_min']), at(out['atom_ring_min']), _lib.stream()))
     return out
@@ -202,32 +197,16 @@ def rings_mols(mols, device, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUM
     list is packed densely, copied and handed to ``mdx_mol_rings``.  -> the results dict of ``stack_ref`` with device tensors.  Two
     bonds between the same pair of atoms and unknown elements raise ValueError."""
     import torch
-    from .similarity import pack_mols
     device = torch.device(device)
     atomic_numbers = tuple(int(z) for z in atomic_numbers)
     _check_sizes(num_bond_types, len(atomic_numbers), ring_bins)
-    p = pack_mols(mols, types.SimpleNamespace(atomic_numbers=atomic_numbers))
-    N, E = int(p['n_atoms'].sum()), int(p['n_bonds'].sum())
-    if N >= (1 << 31) or E >= (1 << 31):
-        raise ValueError('2^31 atoms or bonds in one call: split the list')
-    for m in range(len(mols)):      # the precondition the device cannot report
-        b0, nb, n = int(p['bond_ptr'][m]), int(p['n_bonds'][m]), int(p['n_atoms'][m])
-        i, j = p['bond_index'][:, b0:b0 + nb].astype(np.int64)
-        ok = (i >= 0) & (i < n) & (j >= 0) & (j < n) & (i != j)
-        key = np.minimum(i, j)[ok] * max(n, 1) + np.maximum(i, j)[ok]
-        if len(np.unique(key)) != len(key):
-            raise ValueError(f'molecule {m}: two bonds between the same pair of atoms')
-    d = {k: torch.from_numpy(v).to(device) for k, v in p.items()}
-    out = launch(len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'], d['bond_index'],
-                 int(d['bond_index'].shape[1]), len(atomic_numbers), num_bond_types, ring_bins)
-    out['bond_ring_min'], out['atom_ring_min'] = out['bond_ring_min'][:E], out['atom_ring_min'][:N]
-    out.update(n_atoms=d['n_atoms'], atom_ptr=d['atom_ptr'], bond_ptr=d['bond_ptr'])
+    p = pack_mols(mols, atomic_numbers)
+    check_simple(p)
+    cm = CompactMols.from_packed(to_device(p, device))
+    out = launch(cm, len(atomic_numbers), num_bond_types, ring_bins)
+    out['bond_ring_min'], out['atom_ring_min'] = out['bond_ring_min'][:len(cm.bond_type)], out['atom_ring_min'][:cm.N_cap]
+    out.update(n_atoms=cm.n_atoms, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
     return out
-
-
-def to_host(results):
-    """a results dict with numpy arrays"""
-    return {k: np.ascontiguousarray(_host(v)) for k, v in results.items()}
 
 
 def concat(parts):
@@ -238,16 +217,6 @@ def concat(parts):
     nb = np.concatenate([np.diff(np.append(p['bond_ptr'].astype(np.int64), len(p['bond_ring_min']))) for p in parts])
     out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
     return out
-
-
-def save(results, path):
-    with open(path, 'wb') as f:   # a file object: numpy appends no suffix
-        np.savez(f, **to_host(results))
-
-
-def load(path):
-    with np.load(path, allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
 
 
 def empty(num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, ring_bins=7):
@@ -298,12 +267,6 @@ def compare(a, b):
 
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
-def _load_mols(path, part):
-    import torch
-    pool = torch.load(path, map_location='cpu', weights_only=False)
-    return list(pool[part]) if isinstance(pool, dict) else list(pool)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m moldiff_amd.rings', description=__doc__.split('\n\n')[0])
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -319,17 +282,17 @@ def main(argv=None):
     c.add_argument('b')
     args = ap.parse_args(argv)
     if args.cmd == 'stats':
-        mols = _load_mols(args.samples, args.part)
+        mols = load_mols(args.samples, args.part)
         if args.ref:
             res = stack_ref(mols, ring_bins=args.ring_bins)
         else:
             import torch
             torch.cuda.set_device(torch.device(args.device))
             res = rings_mols(mols, args.device, ring_bins=args.ring_bins)
-        save(res, args.out)
+        save_npz(res, args.out)
         print(json.dumps(summary(res), indent=1))
     else:
-        print(json.dumps(compare(load(args.a), load(args.b)), indent=1))
+        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
     return 0
 
 

@@ -62,6 +62,7 @@ from . import BondPredictor, MolDiff, _lib
 from .distributed import balanced_order, gather_pred, shard_bounds
 from .harness import default_config, load_config, placeholder_from_sizes, recipe_state_dict, seed_all
 from .harness import GEOM_DRUGS_MEAN_ATOMS, GEOM_DRUGS_STD_ATOMS
+from .molpack import save_npz, to_host
 from .molcheck import accept_rule, fragment_fraction, judge, quality_summary
 from .postprocess import FeaturizeMol
 from .scaffold import scaffold_for_sizes
@@ -446,9 +447,9 @@ def main(argv=None):
                 fps = similarity.fingerprint_mols(gen, sim_spec, device)
                 sim_set = fps if sim_set is None else sim_set.append(fps)
             if rings_active and gen:
-                rings_parts.append(rings.to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
+                rings_parts.append(to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
             if groups_set is not None and gen:
-                groups_parts.append(groups.to_host(groups.groups_mols(gen, device, groups_set)))
+                groups_parts.append(to_host(groups.groups_mols(gen, device, groups_set)))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -467,12 +468,12 @@ def main(argv=None):
                 json.dump(similarity.summary(sim_set, sim_ref.to(device) if sim_ref is not None else None), f, indent=1)
         if rings_active:
             res = rings.concat(rings_parts) if rings_parts else rings.empty(featurizer.num_bond_types, featurizer.atomic_numbers.tolist())
-            rings.save(res, os.path.join(log_dir, 'rings.npz'))
+            save_npz(res, os.path.join(log_dir, 'rings.npz'))
             with open(os.path.join(log_dir, 'rings.json'), 'w') as f:
                 json.dump(rings.summary(res), f, indent=1)
         if groups_set is not None:
             res = groups.concat(groups_parts) if groups_parts else groups.empty(groups_set)
-            groups.save(res, os.path.join(log_dir, 'groups.npz'))
+            save_npz(res, os.path.join(log_dir, 'groups.npz'))
             with open(os.path.join(log_dir, 'groups.json'), 'w') as f:
                 json.dump(groups.summary(res), f, indent=1)
         if checked:

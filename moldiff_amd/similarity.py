@@ -22,13 +22,13 @@ each other, not with the paper's table; and with no trained checkpoint offline t
     python -m moldiff_amd.similarity summary a.npz [--against train.npz] [--ref]
 """
 import argparse
-import ctypes
 import json
 import sys
 
 import numpy as np
 
-DEFAULT_ATOMIC_NUMBERS = (6, 7, 8, 9, 15, 16, 17)
+from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, host, load_mols, mol_graph, pack_mols, to_device
+
 MAX_COLUMNS = 1 << 22      # mdx_fp_tanimoto: more columns could take row_sum out of int64
 FIXED_ONE = 1 << 40        # row_sum's unit: q * 2^40 is an exact integer (include/moldiff_hip.h)
 _M = np.uint64(0xffffffff)
@@ -86,27 +86,10 @@ def mix(h):
     return h ^ (h >> np.uint64(16))
 
 
-def _mol_graph(info, spec):
-    """class index per atom (int64) and the bonds once each: (2, b) int64 indices, (b) types"""
-    ele = np.asarray(info['element'], dtype=np.int64).reshape(-1)
-    cls = {z: i for i, z in enumerate(spec.atomic_numbers)}
-    unknown = sorted({int(z) for z in ele if int(z) not in cls})
-    if unknown:
-        raise ValueError(f'element(s) {unknown} are not among the spec\'s atomic numbers')
-    n = len(ele)
-    if 'bond_index' in info and np.asarray(info['bond_index']).size:
-        bi = np.asarray(info['bond_index'], dtype=np.int64)
-        nb = bi.shape[1] // 2
-        bi, bt = bi[:, :nb], np.asarray(info['bond_type'], dtype=np.int64)[:nb]
-    else:
-        bi, bt = np.zeros((2, 0), dtype=np.int64), np.zeros(0, dtype=np.int64)
-    return np.asarray([cls[int(z)] for z in ele], dtype=np.int64), bi, bt
-
-
 def atom_ids(info, spec):
     """id_r[a] for r = 0 .. key_rounds -> (key_rounds + 1, n) uint64 array of 32-bit values: the refinement include/moldiff_hip.h
     defines.  Bonds with an index outside the molecule or with i = j are ignored."""
-    cls, bi, bt = _mol_graph(info, spec)
+    cls, bi, bt = mol_graph(info, spec.atomic_numbers)
     n = len(cls)
     ok = (bi[0] >= 0) & (bi[0] < n) & (bi[1] >= 0) & (bi[1] < n) & (bi[0] != bi[1])
     i, j, t = bi[0, ok], bi[1, ok], (bt[ok].astype(np.uint64) & _M)
@@ -144,7 +127,7 @@ def popcount(words):
 
 
 def _as_words(bits):
-    b = np.ascontiguousarray(_host(bits))
+    b = np.ascontiguousarray(host(bits))
     if b.dtype == np.int32:
         b = b.view(np.uint32)
     if b.dtype != np.uint32 or b.ndim != 2:
@@ -158,7 +141,7 @@ def tanimoto_ref(bits_a, n_on_a, bits_b, n_on_b, exclude_diagonal=False):
     row_max is the largest q over the row's partners, row_argmax the smallest j attaining it (-1 and 0.0 without a partner) and
     row_sum the sum of q * 2^40, an exact integer per pair.  exclude_diagonal (legal for equally many rows only) leaves i == j out."""
     a, b = _as_words(bits_a), _as_words(bits_b)
-    na, nb = np.asarray(_host(n_on_a), dtype=np.int64).reshape(-1), np.asarray(_host(n_on_b), dtype=np.int64).reshape(-1)
+    na, nb = np.asarray(host(n_on_a), dtype=np.int64).reshape(-1), np.asarray(host(n_on_b), dtype=np.int64).reshape(-1)
     if a.shape[1] != b.shape[1] or len(na) != len(a) or len(nb) != len(b):
         raise ValueError('the two sets differ in row width, or n_on does not fit its rows')
     if exclude_diagonal and len(a) != len(b):
@@ -190,10 +173,6 @@ def tanimoto_ref(bits_a, n_on_a, bits_b, n_on_b, exclude_diagonal=False):
 
 # ---- a set of fingerprints -------------------------------------------------------------------------------------------------------------
 
-def _host(x):
-    return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
-
-
 class FingerprintSet:
     """Fingerprints of n molecules: ``bits`` (n, nbits / 32) 32-bit words, ``n_on`` (n) int32, ``key`` (n) int64, ``n_atoms`` (n) int32
     and the ``spec``.  The arrays are numpy (``from_ref``, ``load``) or, straight from the device entry points, torch tensors on the
@@ -222,8 +201,8 @@ class FingerprintSet:
                    np.asarray([f['key'] for f in fps], dtype=np.int64), np.asarray([f['n_atoms'] for f in fps], dtype=np.int32))
 
     def cpu(self):
-        return FingerprintSet(self.spec, _as_words(self.bits), _host(self.n_on).astype(np.int32), _host(self.key).astype(np.int64),
-                              _host(self.n_atoms).astype(np.int32))
+        return FingerprintSet(self.spec, _as_words(self.bits), host(self.n_on).astype(np.int32), host(self.key).astype(np.int64),
+                              host(self.n_atoms).astype(np.int32))
 
     def to(self, device):
         """the same set as torch tensors on `device`"""
@@ -264,44 +243,22 @@ def _comparable(a, b):
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
 
-def launch(spec, B, atom_ptr, bond_ptr, n_atoms, n_bonds, atom_type, N_cap, bond_type, bond_index, Eh_stride, select=None, ws=None):
-    """``mdx_mol_fingerprint`` on device tensors (int32, contiguous) -> (bits (B, words) int32, n_on (B) int32, key (B) int64) on the
-    same device; no sync.  ws: (pointer, bytes) of a workspace, or None to allocate one."""
+def launch(cm, spec, select=None, ws=None):
+    """``mdx_mol_fingerprint`` on the device arrays `cm` (a ``CompactMols``) -> (bits (B, words) int32, n_on (B) int32, key (B)
+    int64) on the same device; no sync.  ws: (pointer, bytes) of a workspace, or None to allocate one."""
     import torch
     from . import _lib
     L = _lib.lib()
-    dev = n_atoms.device
+    B, dev = cm.B, cm.device
     bits = torch.empty(B, spec.words, dtype=torch.int32, device=dev)
     n_on, key = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int64, device=dev)
     if B == 0:
         return bits, n_on, key
-    need = L.mdx_mol_fingerprint_ws_bytes(N_cap)
-    if ws is None or ws[1].value < need:
-        buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = (ctypes.c_void_p(buf.data_ptr()), ctypes.c_size_t(need))
-    # an empty tensor has no address and a NULL operand is refused: an array nothing will be read from is stood in for by 8 spare bytes
-    spare = torch.zeros(1, dtype=torch.int64, device=dev)
-    at = lambda t: _lib.ptr(t if t.numel() else spare)
-    _lib.check(L.mdx_mol_fingerprint(B, at(atom_ptr), at(bond_ptr), at(n_atoms), at(n_bonds), at(atom_type), N_cap, at(bond_type),
-                                     at(bond_index), Eh_stride, _lib.ptr(select), spec.radius, spec.key_rounds, spec.nbits,
-                                     _lib.ptr(bits), _lib.ptr(n_on), _lib.ptr(key), ws[0], ws[1], _lib.stream()))
+    ws = cm.workspace(L.mdx_mol_fingerprint_ws_bytes(cm.N_cap), ws, dev)
+    ops, _ = cm.operands()
+    _lib.check(L.mdx_mol_fingerprint(*ops, _lib.ptr(select), spec.radius, spec.key_rounds, spec.nbits, _lib.ptr(bits), _lib.ptr(n_on),
+                                     _lib.ptr(key), ws[0], ws[1], _lib.stream()))
     return bits, n_on, key
-
-
-def pack_mols(mols, spec):
-    """a list of molecule dicts as the dense compact arrays of ``mdx_mol_fingerprint`` (numpy): atom_ptr, bond_ptr, n_atoms, n_bonds,
-    atom_type (class index), bond_type, bond_index (2, max(total bonds, 1))"""
-    graphs = [_mol_graph(m, spec) for m in mols]
-    na = np.asarray([len(g[0]) for g in graphs], dtype=np.int64)
-    nb = np.asarray([g[1].shape[1] for g in graphs], dtype=np.int64)
-    ptr = lambda c: (np.cumsum(c) - c).astype(np.int32)
-    cat = lambda xs, axis=0: np.concatenate(xs, axis=axis).astype(np.int32)
-    bidx = cat([g[1] for g in graphs], 1) if graphs else np.zeros((2, 0), dtype=np.int32)
-    if bidx.shape[1] == 0:
-        bidx = np.zeros((2, 1), dtype=np.int32)
-    return {'atom_ptr': ptr(na), 'bond_ptr': ptr(nb), 'n_atoms': na.astype(np.int32), 'n_bonds': nb.astype(np.int32),
-            'atom_type': cat([g[0] for g in graphs]) if graphs else np.zeros(0, dtype=np.int32),
-            'bond_type': cat([g[2] for g in graphs]) if graphs else np.zeros(0, dtype=np.int32), 'bond_index': np.ascontiguousarray(bidx)}
 
 
 def fingerprint_mols(mols, spec, device):
@@ -309,13 +266,9 @@ def fingerprint_mols(mols, spec, device):
     densely, copied and handed to ``mdx_mol_fingerprint``.  -> FingerprintSet with device tensors."""
     import torch
     device = torch.device(device)
-    p = pack_mols(mols, spec)
-    if int(p['n_atoms'].sum()) >= (1 << 31) or int(p['n_bonds'].sum()) >= (1 << 31):
-        raise ValueError('2^31 atoms or bonds in one call: split the list')
-    d = {k: torch.from_numpy(v).to(device) for k, v in p.items()}
-    bits, n_on, key = launch(spec, len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'],
-                             int(p['n_atoms'].sum()), d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]))
-    return FingerprintSet(spec, bits, n_on, key, d['n_atoms'])
+    cm = CompactMols.from_packed(to_device(pack_mols(mols, spec.atomic_numbers), device))
+    bits, n_on, key = launch(cm, spec)
+    return FingerprintSet(spec, bits, n_on, key, cm.n_atoms)
 
 
 def tanimoto(a, b, exclude_diagonal=False):
@@ -402,12 +355,6 @@ def summary_ref(fset, reference=None):
 
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
-def _load_mols(path, part):
-    import torch
-    pool = torch.load(path, map_location='cpu', weights_only=False)
-    return list(pool[part]) if isinstance(pool, dict) else list(pool)
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m moldiff_amd.similarity', description=__doc__.split('\n\n')[0])
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -430,7 +377,7 @@ def main(argv=None):
         torch.cuda.set_device(torch.device(args.device))
     if args.cmd == 'fingerprint':
         spec = FingerprintSpec(args.radius, args.nbits, args.key_rounds)
-        mols = _load_mols(args.samples, args.part)
+        mols = load_mols(args.samples, args.part)
         fset = FingerprintSet.from_ref(mols, spec) if args.ref else fingerprint_mols(mols, spec, args.device)
         fset.save(args.out)
         print(f'{len(mols)} molecules -> {args.out}: {spec.nbits} bits, radius {spec.radius}, {spec.key_rounds} key rounds')

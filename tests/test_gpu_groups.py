@@ -4,17 +4,15 @@ definitions make unique, so every comparison is exact."""
 import itertools
 import json
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from moldiff_amd import _lib
+from moldiff_amd import _lib, molpack
 from moldiff_amd import groups as G
 from moldiff_amd.harness import placeholder_from_sizes
 from moldiff_amd.postprocess import FeaturizeMol
-from moldiff_amd.similarity import pack_mols
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -123,7 +121,7 @@ def want():
 
 
 def same(got, ref, what, keys=None):
-    got = G.to_host(got)
+    got = molpack.to_host(got)
     for k in keys or ref:
         if k == 'names':
             assert got[k].tolist() == ref[k].tolist(), what
@@ -146,7 +144,7 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
     assert (nm['sulfonamide'], nm['amide'], nm['carbonyl'], nm['amine_1h']) == (1, 1, 1, 1)
     got = G.groups_mols(BATCH, DEV, BIG)
     same(got, want, 'groups_mols')
-    g = G.to_host(got)
+    g = molpack.to_host(got)
     for k in G.MOL_KEYS:                                  # one molecule at three places, once with ignored bonds around it
         assert np.array_equal(g[k][7], g[k][22]) and np.array_equal(g[k][7], g[k][8]), k
     ptr = g['atom_ptr']
@@ -156,13 +154,12 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
         assert np.array_equal(g[k][9], g[k][10]), k
     assert np.array_equal(hit(9), hit(10)[relabelled(RANDOM, 5)[1]]) and hit(9).any()
     # the same arrays with a mask: the masked molecule has status 0 and zeros everywhere, its slots included; the others are unchanged
-    p = pack_mols(BATCH, types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    p = molpack.pack_mols(BATCH, ELEMENTS)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     select = torch.ones(len(BATCH), dtype=torch.int32, device=DEV)
     select[MASKED] = 0
     N = int(p['n_atoms'].sum())
-    out = G.launch(BIG, len(BATCH), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'],
-                   d['bond_index'], int(d['bond_index'].shape[1]), select=select)
+    out = G.launch(molpack.CompactMols.from_packed(d), BIG, select=select)
     ref = {k: v.copy() for k, v in want.items()}
     for k in G.MOL_KEYS:
         ref[k][MASKED] = 0
@@ -171,7 +168,7 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
     assert want['n_embed'][MASKED].any()
     same(out, ref, 'select', keys=[k for k in G.MOL_KEYS + G.SLOT_KEYS if k != 'n_atoms'])
     # a second call gives the same bytes
-    again = G.to_host(G.groups_mols(BATCH, DEV, BIG))
+    again = molpack.to_host(G.groups_mols(BATCH, DEV, BIG))
     assert all(g[k].tobytes() == again[k].tobytes() for k in g)
 
 
@@ -202,7 +199,7 @@ def test_without_ring_constraints_no_ring_data_are_needed():
 
 
 def test_no_molecule_and_host_side_refusals():
-    got = G.to_host(G.groups_mols([], DEV, BIG))
+    got = molpack.to_host(G.groups_mols([], DEV, BIG))
     ref = G.empty(BIG)
     assert set(got) == set(ref) and all(got[k].shape == ref[k].shape for k in ref)
     with pytest.raises(ValueError, match='same pair'):
@@ -217,7 +214,7 @@ def test_argument_errors_leave_the_outputs_untouched():
     L = _lib.lib()
     ARG = 1
     pset = G.PatternSet([wild_path(3), wild('atom', 1, [])])
-    p = pack_mols(BATCH[:5], types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    p = molpack.pack_mols(BATCH[:5], ELEMENTS)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     N, E = int(p['n_atoms'].sum()), int(d['bond_index'].shape[1])
     seven = lambda *shape: torch.full(shape, 7, dtype=torch.int32, device=DEV)
@@ -291,12 +288,12 @@ def test_groups_batch_on_the_decode_layout_equals_groups_mols_of_its_molecules()
     args = _pred_of(mols, masks=[2, 1, 0, 0, 3, 0, 1, 2])
     decoded = FEAT.decode_batch(*args)
     assert [len(d['element']) for d in decoded] == [0, 6, 10, 8, 40, 14, 7, 4]
-    listed, ref = G.to_host(G.groups_mols(decoded, DEV, BIG)), G.stack_ref(decoded, BIG)
+    listed, ref = molpack.to_host(G.groups_mols(decoded, DEV, BIG)), G.stack_ref(decoded, BIG)
     same(listed, ref, 'groups_mols of the decoded list')
     assert ref['n_embed'].any(1).tolist() == [False] + [True] * 7
 
     def check(got, masked=()):
-        got = G.to_host(got)
+        got = molpack.to_host(got)
         assert got['names'].tolist() == BIG.names and np.array_equal(got['aut'], ref['aut'])
         for m in range(len(mols)):
             a0, la, na = int(got['atom_ptr'][m]), int(listed['atom_ptr'][m]), len(decoded[m]['element'])
@@ -306,7 +303,7 @@ def test_groups_batch_on_the_decode_layout_equals_groups_mols_of_its_molecules()
             assert np.array_equal(got['atom_hit'][a0:a0 + na], listed['atom_hit'][la:la + na] * (not zero)), m
     check(FEAT.groups_batch(*args, BIG))
     check(FEAT.groups_batch(*args, BIG, select=torch.tensor([1, 1, 1, 1, 1, 0, 1, 1], device=DEV)), masked=(5,))
-    got = G.to_host(FEAT.groups_batch(*args, G.PatternSet([wild_path(4)]), max_steps=30))
+    got = molpack.to_host(FEAT.groups_batch(*args, G.PatternSet([wild_path(4)]), max_steps=30))
     want = G.stack_ref(decoded, G.PatternSet([wild_path(4)]), max_steps=30)
     assert 0 < (want['pat_status'] == 3).sum() < 8 and np.array_equal(got['pat_status'], want['pat_status'])
     assert np.array_equal(got['n_embed'], want['n_embed'])
@@ -353,7 +350,7 @@ def test_entry_point_writes_groups_of_the_finished_molecules(tmp_path):
     for a, b in zip(pool0['finished'] + pool0['failed'], pool['finished'] + pool['failed']):
         assert set(a) == set(b) and all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in a)
     ref = G.stack_ref(pool['finished'])
-    saved = G.load(os.path.join(d1, 'groups.npz'))
+    saved = molpack.load_npz(os.path.join(d1, 'groups.npz'))
     assert set(saved) == set(ref) and all(np.array_equal(saved[k], ref[k]) and saved[k].dtype == ref[k].dtype for k in ref)
     with open(os.path.join(d1, 'groups.json')) as f:
         got = json.load(f)

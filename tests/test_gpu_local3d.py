@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from moldiff_amd import _lib
+from moldiff_amd import _lib, molpack
 from moldiff_amd import local3d as L3
 from moldiff_amd.harness import placeholder_from_sizes
 from moldiff_amd.postprocess import FeaturizeMol
@@ -237,7 +237,7 @@ def test_a_cutting_range_and_a_nan_coordinate_land_in_outside(batch):
 # ---- 5. select, accumulation, placement ---------------------------------------------------------------------------------------------------
 
 def _launch(spec, p, out, select=None, pad=0):
-    """mdx_mol_local3d on packed numpy arrays `p` (local3d.pack_mols); pad > 0 moves every molecule to an offset of its own with a gap
+    """mdx_mol_local3d on packed numpy arrays `p` (molpack.pack_mols); pad > 0 moves every molecule to an offset of its own with a gap
     after it, like mdx_decode_output's layout (atoms / bonds at the molecule's original offsets, fewer of them than the slots)"""
     if pad:
         na, nb = p['n_atoms'].astype(np.int64), p['n_bonds'].astype(np.int64)
@@ -252,13 +252,12 @@ def _launch(spec, p, out, select=None, pad=0):
         p = dict(p, atom_ptr=aptr[:-1].astype(np.int32), bond_ptr=bptr[:-1].astype(np.int32), atom_type=at, atom_pos=ap, bond_type=bt, bond_index=bi)
     d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in p.items()}
     sel = None if select is None else torch.as_tensor(select, dtype=torch.int32, device=DEV)
-    return L3.launch(spec, len(p['n_atoms']), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], d['atom_pos'],
-                     int(d['atom_type'].shape[0]), d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]), out, select=sel)
+    return L3.launch(molpack.CompactMols.from_packed(d), spec, out, select=sel)
 
 
 def test_select_accumulation_and_placement(batch):
     mols, spec, refs, want = batch
-    p = L3.pack_mols(mols, spec)
+    p = molpack.pack_mols(mols, spec.atomic_numbers, positions=True)
     # a masked call equals the oracle over the selected molecules; their n_items are 0
     select = np.array([1, 0, 1, 1, 0, 1, 0, 1, 0], dtype=np.int32)
     got = _launch(spec, p, L3.device_stats(spec, DEV), select)
@@ -359,7 +358,7 @@ def test_molecules_without_bonds_and_a_spec_without_patterns():
 def test_refusals_leave_the_outputs_untouched():
     L = _lib.lib()
     spec = L3.Local3DSpec(lengths=['C-C'], angles=['C-C-C'], dihedrals=['C-C-C-C'])
-    p = L3.pack_mols([DESIGNED[3], DESIGNED[4]], spec)
+    p = molpack.pack_mols([DESIGNED[3], DESIGNED[4]], spec.atomic_numbers, positions=True)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     hist = torch.full((spec.hist_size,), 7, dtype=torch.int64, device=DEV)
     outside, n_items = torch.full((3,), 7, dtype=torch.int64, device=DEV), torch.full((3, 2), 7, dtype=torch.int64, device=DEV)

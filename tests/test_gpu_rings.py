@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from moldiff_amd import _lib
+from moldiff_amd import _lib, molpack
 from moldiff_amd import rings as R
 from moldiff_amd.harness import placeholder_from_sizes
 from moldiff_amd.postprocess import FeaturizeMol
@@ -83,7 +83,7 @@ def want():
 
 
 def same(got, ref, what, keys=None):
-    got = R.to_host(got)
+    got = molpack.to_host(got)
     for k in keys or ref:
         assert got[k].dtype == np.int32 and got[k].shape == ref[k].shape, (what, k, got[k].shape, ref[k].shape)
         bad = np.flatnonzero((got[k] != ref[k]).reshape(len(ref[k]), -1).any(1)) if ref[k].size else []
@@ -96,19 +96,16 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
     assert sorted(set(BATCH[14]['element'])) == list(ELEMENTS) and sorted(set(BATCH[14]['bond_type'].tolist())) == [1, 2, 3, 4]
     got = R.rings_mols(BATCH, DEV)
     same(got, want, 'rings_mols')
-    g = R.to_host(got)
+    g = molpack.to_host(got)
     for k in R.MOL_KEYS:                                    # the same ring at three places, once with ignored bonds around it
         assert np.array_equal(g[k][10], g[k][22]) and np.array_equal(g[k][10], g[k][11]), k
     # the same arrays with a mask: the masked molecule has status 0 and zeros everywhere, its slots included; the others are unchanged
-    from moldiff_amd.similarity import pack_mols
-    import types
-    p = pack_mols(BATCH, types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    p = molpack.pack_mols(BATCH, ELEMENTS)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     select = torch.ones(len(BATCH), dtype=torch.int32, device=DEV)
     select[MASKED] = 0
     N, E = int(p['n_atoms'].sum()), int(p['n_bonds'].sum())
-    out = R.launch(len(BATCH), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'], d['bond_index'],
-                   int(d['bond_index'].shape[1]), 7, 4, select=select)
+    out = R.launch(molpack.CompactMols.from_packed(d), 7, 4, select=select)
     ref = {k: v.copy() for k, v in want.items()}
     for k in R.MOL_KEYS:
         ref[k][MASKED] = 0
@@ -118,7 +115,7 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
     assert want['n_rings'][MASKED] > 0
     same(out, ref, 'select', keys=[k for k in R.MOL_KEYS + R.SLOT_KEYS if k != 'n_atoms'])
     # a second call gives the same bytes
-    again = R.to_host(R.rings_mols(BATCH, DEV))
+    again = molpack.to_host(R.rings_mols(BATCH, DEV))
     assert all(g[k].tobytes() == again[k].tobytes() for k in g)
     # other bin counts
     for bins in (1, 4, 64):
@@ -126,7 +123,7 @@ def test_one_launch_over_the_whole_list_equals_the_restatement(want):
 
 
 def test_no_molecule_and_host_side_refusals():
-    got = R.to_host(R.rings_mols([], DEV))
+    got = molpack.to_host(R.rings_mols([], DEV))
     ref = R.empty()
     assert set(got) == set(ref) and all(got[k].shape == ref[k].shape for k in ref)
     with pytest.raises(ValueError, match='same pair'):
@@ -140,9 +137,7 @@ def test_no_molecule_and_host_side_refusals():
 def test_argument_errors_leave_the_outputs_untouched():
     L = _lib.lib()
     ARG = 1
-    from moldiff_amd.similarity import pack_mols
-    import types
-    p = pack_mols(BATCH[:5], types.SimpleNamespace(atomic_numbers=ELEMENTS))
+    p = molpack.pack_mols(BATCH[:5], ELEMENTS)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     N, E = int(p['n_atoms'].sum()), int(d['bond_index'].shape[1])
     seven = lambda *shape: torch.full(shape, 7, dtype=torch.int32, device=DEV)
@@ -197,13 +192,13 @@ def test_rings_batch_on_the_decode_layout_equals_rings_mols_of_its_molecules():
     args = _pred_of(mols, masks=[2, 1, 0, 0, 3, 0, 1, 0])
     decoded = FEAT.decode_batch(*args)
     assert [len(d['element']) for d in decoded] == [0, 6, 10, 8, 40, 12, 12, 66]
-    listed, ref = R.to_host(R.rings_mols(decoded, DEV)), R.stack_ref(decoded)
+    listed, ref = molpack.to_host(R.rings_mols(decoded, DEV)), R.stack_ref(decoded)
     same(listed, ref, 'rings_mols of the decoded list')
     assert ref['n_rings'].tolist() == [0, 1, 2, 5, 12, 3, 2, 32]
     nb = [d['bond_index'].shape[1] // 2 for d in decoded]
 
     def check(got, masked=()):
-        got = R.to_host(got)
+        got = molpack.to_host(got)
         for m in range(len(mols)):
             a0, b0 = int(got['atom_ptr'][m]), int(got['bond_ptr'][m])
             la, lb = int(listed['atom_ptr'][m]), int(listed['bond_ptr'][m])
@@ -215,7 +210,7 @@ def test_rings_batch_on_the_decode_layout_equals_rings_mols_of_its_molecules():
             assert np.array_equal(got['bond_ring_min'][b0:b0 + nb[m]], listed['bond_ring_min'][lb:lb + nb[m]] * (not zero)), m
     check(FEAT.rings_batch(*args))
     check(FEAT.rings_batch(*args, select=torch.tensor([1, 1, 1, 1, 1, 0, 1, 1], device=DEV)), masked=(5,))
-    got = R.to_host(FEAT.rings_batch(*args, ring_bins=3))
+    got = molpack.to_host(FEAT.rings_batch(*args, ring_bins=3))
     assert got['ring_hist'].shape == (8, 3) and got['ring_hist'][2].tolist() == [0, 0, 2] and got['ring_hist'][3].tolist() == [0, 5, 0]
 
 
@@ -253,7 +248,7 @@ def test_entry_point_writes_rings_of_the_finished_molecules(tmp_path):
             assert a.read() == b.read(), f
     assert sorted(os.listdir(d0 + '_SDF')) == sorted(os.listdir(d1 + '_SDF'))
     ref = R.stack_ref(pool['finished'])
-    saved = R.load(os.path.join(d1, 'rings.npz'))
+    saved = molpack.load_npz(os.path.join(d1, 'rings.npz'))
     assert set(saved) == set(ref) and all(np.array_equal(saved[k], ref[k]) and saved[k].dtype == ref[k].dtype for k in ref)
     with open(os.path.join(d1, 'rings.json')) as f:
         got = json.load(f)

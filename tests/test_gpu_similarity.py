@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from moldiff_amd import _lib
+from moldiff_amd import _lib, molpack
 from moldiff_amd import similarity as S
 from moldiff_amd.harness import placeholder_from_sizes
 from moldiff_amd.postprocess import FeaturizeMol
@@ -99,11 +99,9 @@ def test_fingerprints_of_the_dense_list_equal_the_restatement(refs):
         assert np.array_equal(g.bits[3], g.bits[8]) and np.array_equal(g.bits[3], g.bits[6]) and g.key[3] == g.key[8] == g.key[6]
         assert not g.bits[0].any() and g.n_on[0] == 0 and g.key[0] == 0
         # the same arrays with a mask: molecule 5 gets a zero row, n_on 0 and key 0, the others are unchanged
-        p = S.pack_mols(BATCH, spec)
+        p = molpack.pack_mols(BATCH, spec.atomic_numbers)
         d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
-        bits, n_on, key = S.launch(spec, len(BATCH), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'],
-                                   int(p['n_atoms'].sum()), d['bond_type'], d['bond_index'], int(d['bond_index'].shape[1]),
-                                   select=torch.from_numpy(SELECT).to(DEV))
+        bits, n_on, key = S.launch(molpack.CompactMols.from_packed(d), spec, select=torch.from_numpy(SELECT).to(DEV))
         same_set(S.FingerprintSet(spec, bits, n_on, key, d['n_atoms']), want, ('select', spec.nbits, spec.radius), masked=(5,))
 
 
@@ -239,7 +237,7 @@ def test_refusals_leave_the_outputs_untouched():
     assert call(96, 1) == ARG and b'Na == Nb' in L.mdx_last_error()
     assert call(96, 0, ws_bytes=39) == ARG and b'workspace' in L.mdx_last_error()
     spec = S.FingerprintSpec(nbits=96)
-    p = S.pack_mols(BATCH[:5], spec)
+    p = molpack.pack_mols(BATCH[:5], spec.atomic_numbers)
     d = {k: torch.from_numpy(v).to(DEV) for k, v in p.items()}
     bits, n_on, key = torch.full((5, 3), 7, dtype=torch.int32, device=DEV), torch.full((5,), 7, dtype=torch.int32, device=DEV), \
         torch.full((5,), 7, dtype=torch.int64, device=DEV)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from moldiff_amd import molpack
 from moldiff_amd import groups as G
 from moldiff_amd import rings as R
 
@@ -350,7 +351,7 @@ def test_summary_compare_concat_and_files(tmp_path, capsys):
     assert G.main(['stats', str(tmp_path / 'samples_all.pt'), '--out', str(tmp_path / 'a.npz'), '--ref']) == 0
     printed = json.loads(capsys.readouterr().out)
     assert printed['n_measured'] == 2 and printed['patterns']['benzene']['mean_matches'] == 0.5
-    saved, want = G.load(str(tmp_path / 'a.npz')), G.stack_ref(pool['finished'])
+    saved, want = molpack.load_npz(str(tmp_path / 'a.npz')), G.stack_ref(pool['finished'])
     assert set(saved) == set(want) and all(np.array_equal(saved[k], want[k]) for k in want)
     assert G.main(['stats', str(tmp_path / 'samples_all.pt'), '--out', str(tmp_path / 'b.npz'), '--ref', '--part', 'failed']) == 0
     capsys.readouterr()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from moldiff_amd import molpack
 from moldiff_amd import rings as R
 
 ELEMENTS = (6, 7, 8, 9, 15, 16, 17)
@@ -230,7 +231,7 @@ def test_command_line_with_ref(tmp_path, capsys):
     assert R.main(['stats', str(tmp_path / 'samples_all.pt'), '--out', str(tmp_path / 'a.npz'), '--ref']) == 0
     printed = json.loads(capsys.readouterr().out)
     assert printed['n_measured'] == 3 and printed['ring_size']['counts'] == [0, 0, 0, 3, 0, 0, 0]
-    saved = R.load(str(tmp_path / 'a.npz'))
+    saved = molpack.load_npz(str(tmp_path / 'a.npz'))
     want = R.stack_ref(pool['finished'])
     assert set(saved) == set(want) and all(np.array_equal(saved[k], want[k]) for k in want)
     assert R.main(['stats', str(tmp_path / 'samples_all.pt'), '--out', str(tmp_path / 'b.npz'), '--ref', '--part', 'failed']) == 0

@@ -10,15 +10,14 @@ import json
 import os
 import sys
 import time
-import types
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from moldiff_amd import groups as G  # noqa: E402
+from moldiff_amd import molpack  # noqa: E402
 from moldiff_amd import rings as R  # noqa: E402
-from moldiff_amd.similarity import pack_mols  # noqa: E402
 
 ELEMENTS = (6, 7, 8, 9, 15, 16, 17)
 
@@ -53,14 +52,13 @@ def main(argv=None):
     torch.cuda.set_device(torch.device(args.device))
     g = np.random.default_rng(0)
     mols = [drug_like(g, max(12, int(g.normal(args.atoms, 5)))) for _ in range(args.n)]
-    p = pack_mols(mols, types.SimpleNamespace(atomic_numbers=ELEMENTS))
-    d = {k: torch.from_numpy(v).to(args.device) for k, v in p.items()}
-    N, E = int(p['n_atoms'].sum()), int(d['bond_index'].shape[1])
+    p = molpack.pack_mols(mols, ELEMENTS)
+    cm = molpack.CompactMols.from_packed(molpack.to_device(p, args.device))
+    N = cm.N_cap
     pset = G.PatternSet.default()
-    shape = (len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'], d['bond_index'], E)
-    ring_data = R.launch(*shape, len(ELEMENTS), 4)
-    both = lambda: G.launch(pset, *shape)                          # mdx_mol_rings, then mdx_mol_groups
-    alone = lambda: G.launch(pset, *shape, ring_data=ring_data)    # mdx_mol_groups on ring data already there
+    ring_data = R.launch(cm, len(ELEMENTS), 4)
+    both = lambda: G.launch(cm, pset)                          # mdx_mol_rings, then mdx_mol_groups
+    alone = lambda: G.launch(cm, pset, ring_data=ring_data)    # mdx_mol_groups on ring data already there
 
     def timed(call):
         for _ in range(5):
@@ -79,8 +77,8 @@ def main(argv=None):
     want = G.stack_ref(mols, pset)
     host_s = time.perf_counter() - t0
     keys = ('status', 'n_embed', 'n_anchor', 'steps', 'pat_status')
-    same = all(np.array_equal(G.to_host(o)[k], want[k]) for o in (out, out2) for k in keys)
-    same = same and all(np.array_equal(G.to_host(o)['atom_hit'][:N], want['atom_hit']) for o in (out, out2))
+    same = all(np.array_equal(molpack.to_host(o)[k], want[k]) for o in (out, out2) for k in keys)
+    same = same and all(np.array_equal(molpack.to_host(o)['atom_hit'][:N], want['atom_hit']) for o in (out, out2))
     print(json.dumps({'molecules': len(mols), 'atoms': N, 'bonds': int(p['n_bonds'].sum()), 'patterns': len(pset),
                       'steps': int(want['steps'].astype(np.int64).sum()), 'embeddings': int(want['n_embed'].astype(np.int64).sum()),
                       'device_ms_per_batch_with_rings': round(both_ms, 4), 'device_ms_per_batch_groups_alone': round(alone_ms, 4),

@@ -9,14 +9,13 @@ import json
 import os
 import sys
 import time
-import types
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from moldiff_amd import molpack  # noqa: E402
 from moldiff_amd import rings as R  # noqa: E402
-from moldiff_amd.similarity import pack_mols  # noqa: E402
 
 ELEMENTS = (6, 7, 8, 9, 15, 16, 17)
 
@@ -51,11 +50,10 @@ def main(argv=None):
     torch.cuda.set_device(torch.device(args.device))
     g = np.random.default_rng(0)
     mols = [drug_like(g, max(12, int(g.normal(args.atoms, 5)))) for _ in range(args.n)]
-    p = pack_mols(mols, types.SimpleNamespace(atomic_numbers=ELEMENTS))
-    d = {k: torch.from_numpy(v).to(args.device) for k, v in p.items()}
-    N, E = int(p['n_atoms'].sum()), int(d['bond_index'].shape[1])
-    call = lambda: R.launch(len(mols), d['atom_ptr'], d['bond_ptr'], d['n_atoms'], d['n_bonds'], d['atom_type'], N, d['bond_type'],
-                            d['bond_index'], E, len(ELEMENTS), 4)
+    p = molpack.pack_mols(mols, ELEMENTS)
+    cm = molpack.CompactMols.from_packed(molpack.to_device(p, args.device))
+    N = cm.N_cap
+    call = lambda: R.launch(cm, len(ELEMENTS), 4)
     for _ in range(5):
         out = call()
     torch.cuda.synchronize()
@@ -69,7 +67,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     want = R.stack_ref(mols)
     host_s = time.perf_counter() - t0
-    got = R.to_host(out)
+    got = molpack.to_host(out)
     same = all(np.array_equal(got[k], want[k]) for k in got)
     print(json.dumps({'molecules': len(mols), 'atoms': N, 'bonds': int(p['n_bonds'].sum()), 'rings': int(want['n_rings'].sum()),
                       'device_ms_per_batch': round(device_ms, 4), 'includes': 'the zero-fill of the ten output tensors', 'host_ref_s': round(host_s, 3),
