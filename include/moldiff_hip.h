@@ -599,6 +599,73 @@ int mdx_mol_groups(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, 
                    const int32_t* ring_status, int32_t* n_embed, int32_t* n_anchor, int32_t* steps, int32_t* pat_status,
                    int32_t* status, int32_t* atom_hit, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Kekulé assignment of the aromatic bonds of decoded molecules ---------------------------------------------------------
+ * The reference hands its decoded bond graph, aromatic bonds included, to RDKit's sanitisation (utils/reconstruct.py:245-271) and
+ * counts a molecule as generated only if that succeeds; it fails when an atom is above its valence (mdx_mol_check) or when the
+ * aromatic system has no Kekulé structure, and `fix_valence` / `fix_aromatic` (:295-387) retry with a hydrogen or a positive charge on
+ * ring N and S.  mdx_mol_kekulize is THIS PROJECT'S OWN MODEL of that second test, without RDKit and UNVERIFIED AGAINST IT, of the
+ * molecule AS DECODED.  The structure it reports is the FIRST ONE FOUND in the search order below, not a charge-minimal one.  Every
+ * output is defined so that its value is unique, and a plain restatement (moldiff_amd/kekule.py: kekulize_ref) must agree exactly.
+ *
+ * The molecule: the compact layout of mdx_mol_rings (atom_ptr .. select: as there); its VALID bonds only (both indices inside the
+ *   molecule, i != j; the others are ignored).  A bond type outside 1 .. num_bond_types leaves the bond in the graph, adds nothing and
+ *   is not aromatic.  The last type, num_bond_types, is AROMATIC.  Two bonds between one pair of atoms are a PRECONDITION VIOLATION as
+ *   for mdx_mol_rings: results unspecified, the kernel stays in bounds and ends.
+ * Chemistry is data: three HOST tables indexed by atom class, validated by the call and sent as kernel arguments (the caller may
+ *   overwrite them as soon as the call returns).  normal_valence V[c], 0 .. 64; charged_valence Vc[c], 0 .. 64: 0 = none, otherwise
+ *   the valence with one positive charge; flexible: bit c set = class c takes a hydrogen instead of a double bond.  An atom of a class
+ *   outside 0 .. num_element - 1 has V = Vc = 0 and is not flexible.  (The shipped featuriser's defaults, moldiff_amd/kekule.py:
+ *   V = C 4, N 3, O 2, F 1, P 3, S 2, Cl 1; Vc = N 4, S 3; flexible = {N}: this project's choice.)
+ * Per atom: sigma = the sum of the orders of its valid non-aromatic bonds (types 1 .. num_bond_types - 1 count their number) + the
+ *   number of its aromatic bonds; adeg = the number of its aromatic bonds.  An atom with adeg >= 1 has one ROLE:
+ *     NOT  (1)  adeg > 3; or neither case below applies (no room, or over-valent);
+ *     MUST (2)  V - sigma >= 1 and the class is not flexible;
+ *     MAY  (3)  V - sigma >= 1 and the class is flexible (it takes a hydrogen instead); or V - sigma < 1 and Vc - sigma >= 1 (it takes
+ *               a charge if matched).
+ *   An atom without an aromatic bond has role 0.
+ * The connected components of the aromatic bonds are treated independently.  Within a component a KEKULÉ STRUCTURE is a matching on
+ *   aromatic bonds: both ends of every bond in it have a role other than NOT, and it covers every MUST atom.
+ * THE CANONICAL STRUCTURE is the first one found by this search; the order is part of the definition:
+ *   1. walk the component's atoms in ascending index;
+ *   2. skip an atom that is NOT or already matched;
+ *   3. otherwise its options are, in this order: "stay unmatched" (MAY atoms only), then each aromatic neighbour with a higher index
+ *      that is not NOT and not yet matched, in ascending index;
+ *   4. try the next option and go on to the next atom;
+ *   5. with no option left, undo and return to the previous deciding atom;
+ *   6. passing the last atom is success; exhausting the first deciding atom's options is "no structure".
+ *   steps counts the options tried, each try one step, up to the success or the exhaustion.  A component whose steps would exceed
+ *   max_steps (1 .. 2^20, per component) is OVER BUDGET.  A component is UNSOLVED when it has no structure or is over budget.
+ * Outputs (device int32, plain stores by the molecule's own workgroup: bit-reproducible, independent of the place in the batch):
+ *   kek_order  per bond slot (Eh_stride): types 1 .. num_bond_types - 1 unchanged; an aromatic bond 2 if in the matching, else 1; an
+ *              ignored bond, a type outside 1 .. num_bond_types and an aromatic bond of an unsolved component 0.
+ *   val        per atom slot (N_cap): sigma + 1 if the atom is matched, else sigma.
+ *   charge     1 iff V < val <= Vc, else 0 (a non-aromatic four-valent N gets its charge too, as fix_valence does).
+ *   kek_h      max(0, (Vc if charge else V) - val): the hydrogens of the assignment.
+ *   atom_flag  bits 0-1 the role, bit 2 matched, bit 3 val > max(V, Vc), bit 4 the atom's component is unsolved.  Atoms of an unsolved
+ *              component have kek_h 0, charge 0, bit 2 clear and bit 4 set; all other atoms of the molecule are still measured.
+ *   mol_stats  [m][k], k < MDX_KEKULE_STATS = 11:
+ *     0 status         0 measured; 1 too large: n_atoms > 256 or n_bonds > 512 (the caps of mdx_mol_rings; ignored bonds included), or
+ *                      an aromatic component of more than 64 atoms.  Every other output of the molecule is then 0, its slots included.
+ *     1 n_arom_atoms   atoms with adeg >= 1             2 n_arom_bonds    valid aromatic bonds
+ *     3 n_components   aromatic components              4 n_failed        components with no structure
+ *     5 n_over_budget  components over budget           6 n_double        aromatic bonds in the matchings
+ *     7 n_charged      atoms with charge 1              8 n_hydrogens     the sum of kek_h
+ *     9 n_overvalent   atoms with flag bit 3           10 steps           summed over the components; one over budget adds 0
+ *   select, and a molecule reaching past N_cap / Eh_stride, as for mdx_mol_rings: status 0, all outputs 0 (the slots of the latter are
+ *   not written).  Slots that belong to no molecule are not written.  A molecule is KEKULIZABLE iff status == 0 and n_failed ==
+ *   n_over_budget == 0.
+ * One workgroup of 256 threads per molecule, the molecule staged once in LDS (about 8 KB); each component is searched by one thread
+ * with its state in registers, which is what the cap of 64 atoms per component is for.  There is no workspace.
+ * MDX_ERR_ARG, every output untouched: a null operand (select excepted), a negative size, num_element outside 1 .. 32, num_bond_types
+ * outside 1 .. 16, a table value outside 0 .. 64, a flexible bit at or above num_element, max_steps outside 1 .. 2^20.
+ * B = 0 is accepted and writes nothing. */
+#define MDX_KEKULE_STATS 11
+int mdx_mol_kekulize(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                     const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                     const int32_t* select, int32_t num_element, int32_t num_bond_types, const int32_t* normal_valence,
+                     const int32_t* charged_valence, uint32_t flexible, int32_t max_steps, int32_t* kek_order, int32_t* val,
+                     int32_t* charge, int32_t* kek_h, int32_t* atom_flag, int32_t* mol_stats, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -1,4 +1,4 @@
-// The compact molecule arrays every evaluation kernel walks (mdx_mol_local3d, mdx_mol_fingerprint, mdx_mol_rings, mdx_mol_groups), defined
+// The compact molecule arrays every evaluation kernel walks (mdx_mol_local3d, mdx_mol_fingerprint, mdx_mol_rings, mdx_mol_groups, mdx_mol_kekulize), defined
 // once: molecule m has its atoms at atom_ptr[m] .. + n_atoms[m] and its bonds at bond_ptr[m] .. + n_bonds[m], one direction per bond,
 // molecule-local atom indices -- what mdx_decode_output leaves and what moldiff_amd/molpack.py packs from a list of molecule dicts.
 // The first part is plain C++ (mdx_local3d_args.h includes it and tools/local3d_host_check.cpp builds that without HIP); the second
@@ -15,7 +15,7 @@ struct MolArrays {
   long long N_cap, E_cap;                               // extents of the atom / bond arrays
 };
 
-// Validates the operands the four C entry points share and fills `a` from them.  -> nullptr, or the reason the call is refused.
+// Validates the operands the C entry points share and fills `a` from them.  -> nullptr, or the reason the call is refused.
 inline const char* mol_arrays_fill(MolArrays* a, int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms,
                                    const int32_t* n_bonds, const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type,
                                    const int32_t* bond_index, int64_t Eh_stride, const int32_t* select) {

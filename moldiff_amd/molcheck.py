@@ -6,9 +6,12 @@ dict (an entry of ``samples_all.pt``, or what ``decode_output`` / ``decode_batch
 
 What the check is: the reference finishes a molecule when RDKit sanitises it and its SMILES has no '.'
 (scripts/sample_drug3d.py:141-153, utils/reconstruct.py:245-271).  "One fragment" is the second condition exactly.  "No atom
-above its largest permitted valence" is a NECESSARY condition of the first, not a restatement of it: there is no kekulisation,
-no aromaticity perception, no formal charge and no hydrogen here, so a molecule the reference would refuse on kekulisation
-passes.  The two distances are descriptive; no rule is built on them.
+above its largest permitted valence" is a NECESSARY condition of the first, not a restatement of it: there is no aromaticity
+perception, no formal charge and no hydrogen in this check, so a molecule the reference would refuse on kekulisation passes it.
+The kekulisation test is a separate instrument, ``mdx_mol_kekulize`` (moldiff_amd/kekule.py): the rule 'kekule' is 'valence' and
+"every aromatic system has a Kekulé structure" by THIS PROJECT'S MODEL of that step -- default tables unverified against RDKit, the
+first structure in search order rather than a charge-minimal one -- so it too models the reference's test and does not restate it.
+The two distances are descriptive; no rule is built on them.
 
 ``DEFAULT_MAX_VALENCE`` maps an atomic number to the largest explicit valence the reference's pipeline can let through for that
 element -- written down from memory of RDKit's element table (nitrogen is 4 because ``fix_valence`` charges a four-valent N).
@@ -20,7 +23,7 @@ from fractions import Fraction
 import numpy as np
 
 DEFAULT_MAX_VALENCE = {6: 4, 7: 4, 8: 2, 9: 1, 15: 7, 16: 6, 17: 1}
-ACCEPT_RULES = ('connected', 'valence')
+ACCEPT_RULES = ('connected', 'valence', 'kekule')
 
 
 def valence_table(atomic_numbers, max_valence=None):
@@ -131,7 +134,8 @@ def restrict_ref(info, component, label):
 
 def judge(info, report, m, rule, max_valence=None, annotate=False):
     """The sampling entry point's verdict on molecule `m` of a ``check_batch`` result (info = mols[m]) -> (finished, n_components,
-    n_overvalent) of the molecule AS IT STANDS: 'connected' = one fragment, 'valence' = that and no over-valent atom.  A salvaged
+    n_overvalent) of the molecule AS IT STANDS: 'connected' = one fragment, 'valence' = that and no over-valent atom; 'kekule' is
+    judged here as 'valence', and the caller adds "kekulizable" from ``kekule.kekulizable``.  A salvaged
     molecule is one fragment by construction and its atoms keep the valences they had, so its count comes from info['valence'];
     every other molecule's figures are the report's.  annotate: write the report's figures (of the molecule as decoded) and
     ``salvaged`` into `info` as plain Python numbers."""
@@ -146,14 +150,17 @@ def judge(info, report, m, rule, max_valence=None, annotate=False):
     return ncomp == 1 and (rule == 'connected' or nover == 0), ncomp, nover
 
 
-def quality_summary(rows, n_finished, n_failed):
+def quality_summary(rows, n_finished, n_failed, kekule=False):
     """The entry point's quality report from one dict per SAMPLED molecule (n_components, n_overvalent, min_dist, max_bond_len,
-    salvaged -- all of the molecule as decoded): counts, their fractions of sampled, and medians of the two distances."""
+    salvaged -- all of the molecule as decoded): counts, their fractions of sampled, and medians of the two distances.  kekule: the
+    rows carry ``kekulizable`` (of the molecule as it stands), and the counts gain it."""
     n = len(rows)
     counts = {'sampled': n,
               'connected': sum(1 for r in rows if r['n_components'] == 1),
               'valence_clean': sum(1 for r in rows if r['n_components'] >= 1 and r['n_overvalent'] == 0),
               'finished': int(n_finished), 'salvaged': sum(1 for r in rows if r['salvaged']), 'failed': int(n_failed)}
+    if kekule:
+        counts['kekulizable'] = sum(1 for r in rows if r['kekulizable'])
     md = [r['min_dist'] for r in rows if np.isfinite(r['min_dist'])]
     return {'counts': counts, 'fractions': {k: (v / n if n else 0.0) for k, v in counts.items() if k != 'sampled'},
             'median_min_dist': float(np.median(md)) if md else None,

@@ -1,6 +1,6 @@
 """The compact molecule arrays of the evaluation kernels (csrc/mdx_mol.h) on the Python side: a list of molecule dicts parsed and packed
 into them, the packed arrays as the operands of a C entry point (``CompactMols``), and the small host helpers the evaluation modules
-(local3d, similarity, rings, groups) share.  Nothing here needs torch at import.
+(local3d, similarity, rings, groups, kekule) share.  Nothing here needs torch at import.
 
 A molecule dict holds ``element`` (atomic numbers), ``bond_index`` (2, 2b) with every bond once and then flipped, ``bond_type`` (2b) and,
 for the geometry statistics, ``atom_pos`` (n, 3): what ``FeaturizeMol.decode_batch`` returns and ``samples_all.pt`` stores.

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -46,6 +46,13 @@ beside ``samples_all.pt``.  Without the option nothing changes.
 the functional groups of the same FINISHED molecules on the device batch by batch (``moldiff_amd/groups.py``: a substructure matcher
 with this project's own pattern language, not SMARTS; bare, the default set ``configs/groups_default.yml``) and writes ``groups.npz``
 (per-molecule arrays) and ``groups.json`` (their summary) beside ``samples_all.pt``.  Without the option nothing changes.
+``--kekulize`` (config key ``sample.kekulize``; the flag wins) and ``--accept kekule``, additions beyond the reference: rank 0 assigns a
+Kekulé structure to the aromatic bonds of the decoded molecules on the device batch by batch (``moldiff_amd/kekule.py``: this project's
+model of the kekulisation step of RDKit's sanitisation, default tables unverified against RDKit, the first structure in search order and
+not a charge-minimal one).  ``--kekulize`` writes ``kekule.npz`` (per-molecule, per-atom and per-bond arrays of the FINISHED molecules),
+``kekule.json`` (their summary) and ``samples_kekule.sdf`` (the finished molecules that are kekulizable, bond orders 1 / 2 / 3 and
+``M  CHG`` lines) beside ``samples_all.pt``; ``--accept kekule`` is 'valence' and kekulizable.  With either, pool entries carry
+``kekulizable`` and ``quality.json`` (written with ``--accept`` / ``--largest_fragment``) gains its count.  Without both nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -256,6 +263,19 @@ def add_groups_argument(ap):
     return ap
 
 
+def kekulize_option(flag, sample_cfg):
+    """whether to write the Kekulé files: the command line's flag (None = not given) wins over the config's ``sample.kekulize``"""
+    return bool(flag if flag is not None else sample_cfg.get('kekulize'))
+
+
+def add_kekulize_argument(ap):
+    """``--kekulize`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--kekulize', action='store_true', default=None,
+                    help='assign a Kekulé structure to the aromatic bonds of the finished molecules on the device and write kekule.npz, '
+                         'kekule.json and samples_kekule.sdf (overrides sample.kekulize)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -271,7 +291,8 @@ def build_parser():
     ap.add_argument('--resample', type=int, default=0, help='resampling: walk every block of --jump_length levels this many times, with a '
                                                             'forward jump in between (overrides sample.resample; needs --jump_length)')
     ap.add_argument('--jump_length', type=int, default=0, help='resampling: moves per block (overrides sample.jump_length)')
-    ap.add_argument('--accept', type=str, default=None, help="'connected' (one fragment) or 'valence' (that and no over-valent atom); "
+    ap.add_argument('--accept', type=str, default=None, help="'connected' (one fragment), 'valence' (that and no over-valent atom) or "
+                                                             "'kekule' (that and a Kekulé structure for every aromatic system); "
                                                              'judged by the device-side check (overrides sample.accept)')
     ap.add_argument('--largest_fragment', type=float, default=None,
                     help='FRAC in (0, 1]: a disconnected molecule whose largest fragment holds at least FRAC of its atoms is replaced '
@@ -283,7 +304,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))).parse_args(argv)
+    args = add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -361,6 +382,11 @@ def main(argv=None):
         atomic_numbers = featurizer.atomic_numbers.tolist()
         groups_set = (groups.PatternSet.from_yaml(groups_path, atomic_numbers, featurizer.num_bond_types) if groups_path else
                       groups.PatternSet.default(atomic_numbers, featurizer.num_bond_types))
+    kek_write, kek_parts, kek_mols = kekulize_option(args.kekulize, config.sample), [], []
+    kek_active = kek_write or rule == 'kekule'
+    if kek_active:
+        from . import kekule
+        kek_tables = kekule.KekuleTables(featurizer.atomic_numbers.tolist(), featurizer.num_bond_types)
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -396,6 +422,9 @@ def main(argv=None):
                 local, rep = featurizer.check_batch(out['pred'], ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], hi - lo,
                                                     largest_fragment=frac)
                 done = [judge(info, rep, j, rule)[0] for j, info in enumerate(local)]
+                if rule == 'kekule':
+                    ok = kekule.kekulizable(kekule.kekulize_mols(local, device, kek_tables))
+                    done = [d and bool(k) for d, k in zip(done, ok)]
             else:
                 local = featurizer.decode_batch(out['pred'], ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'], hi - lo)
                 done = [is_connected(len(info['element']), info['bond_index']) for info in local]
@@ -425,6 +454,12 @@ def main(argv=None):
                 mols = featurizer.decode_batch([p.to(device) for p in pred], full['batch_node'], full['halfedge_index'],
                                                full['batch_halfedge'], n_graphs)
             mols = [mols[inv[k]] for k in range(n_graphs)]
+            if kek_active:   # of every molecule as it stands (with --largest_fragment a salvaged molecule is its fragment)
+                ok = kekule.kekulizable(kekule.kekulize_mols(mols, device, kek_tables))
+                for k, info in enumerate(mols):
+                    info['kekulizable'] = bool(ok[k])
+                if rule == 'kekule':
+                    done = [d and bool(k) for d, k in zip(done, ok)]
             gen = []
             for k, info in enumerate(mols):
                 info['mol_id'] = next_id + k
@@ -450,6 +485,8 @@ def main(argv=None):
                 rings_parts.append(to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
             if groups_set is not None and gen:
                 groups_parts.append(to_host(groups.groups_mols(gen, device, groups_set)))
+            if kek_write and gen:
+                kek_parts.append(to_host(kekule.kekulize_mols(gen, device, kek_tables)))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -476,9 +513,16 @@ def main(argv=None):
             save_npz(res, os.path.join(log_dir, 'groups.npz'))
             with open(os.path.join(log_dir, 'groups.json'), 'w') as f:
                 json.dump(groups.summary(res), f, indent=1)
+        if kek_write:
+            res = kekule.concat(kek_parts) if kek_parts else kekule.empty()
+            save_npz(res, os.path.join(log_dir, 'kekule.npz'))
+            with open(os.path.join(log_dir, 'kekule.json'), 'w') as f:
+                json.dump(kekule.summary(res), f, indent=1)
+            kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
-                json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed'])),
+                json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed']),
+                                               kekule=kek_active),
                                accept=rule, largest_fragment=frac), f, indent=1)
     if dist is not None:
         dist.barrier()
