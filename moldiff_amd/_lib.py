@@ -78,66 +78,6 @@ class MdxForwardTables(ctypes.Structure):  # == struct mdx_forward_tables
         ('Kn', c_int32), ('Ke', c_int32), ('num', c_int32)]
 
 
-class MdxBondFfnArgs(ctypes.Structure):   # == mdx_bondffn_args
-    _fields_ = [('X', c_void_p), ('ldx', c_int64), ('Wb', c_void_p), ('ldwb', c_int64),
-                ('Wi1', c_void_p), ('ldwi1', c_int64), ('bi1', c_void_p), ('g1', c_void_p), ('be1', c_void_p),
-                ('Wi2', c_void_p), ('ldwi2', c_int64), ('bi2', c_void_p),
-                ('Wg1', c_void_p), ('ldwg1', c_int64), ('bg1', c_void_p), ('gg', c_void_p), ('gbe', c_void_p),
-                ('Wt', c_void_p), ('ldwt', c_int64), ('Wg2', c_void_p), ('ldwg2', c_int64), ('bg2', c_void_p),
-                ('NL', c_void_p), ('ldnl', c_int64), ('GN', c_void_p), ('ldgn', c_int64), ('idx', c_void_p), ('te', c_void_p),
-                ('prod', c_void_p), ('pre1', c_void_p), ('post1', c_void_p), ('inter', c_void_p), ('gpre', c_void_p), ('gpost', c_void_p),
-                ('gate', c_void_p), ('out', c_void_p), ('E', c_int64)]
-
-
-class MdxBondFfnBwdArgs(ctypes.Structure):   # == mdx_bondffn_bwd_args
-    _fields_ = [('f', MdxBondFfnArgs), ('gS', c_void_p), ('ldgs', c_int64), ('oidx', c_void_p),
-                ('g_inter', c_void_p), ('g_gate', c_void_p), ('g_pre1', c_void_p), ('g_bf', c_void_p), ('g_nl', c_void_p),
-                ('g_gpre', c_void_p), ('g_x', c_void_p), ('lnp', c_void_p)]
-
-
-class MdxEdgeTailArgs(ctypes.Structure):   # == mdx_edge_tail_args
-    _fields_ = [('H', c_void_p), ('ldh', c_int64), ('BL', c_void_p), ('ldbl', c_int64), ('BR', c_void_p), ('ldbr', c_int64),
-                ('il', c_void_p), ('ir', c_void_p), ('Ws', c_void_p), ('ldws', c_int64), ('bs', c_void_p), ('lng', c_void_p), ('lnb', c_void_p),
-                ('Wo', c_void_p), ('ldwo', c_int64), ('bo', c_void_p), ('pre', c_void_p), ('post', c_void_p), ('out', c_void_p), ('E', c_int64)]
-
-
-class MdxEdgeTailBwdArgs(ctypes.Structure):   # == mdx_edge_tail_bwd_args
-    _fields_ = [('f', MdxEdgeTailArgs), ('g_out', c_void_p), ('ldg', c_int64), ('g_pre', c_void_p), ('g_h', c_void_p), ('lnp', c_void_p)]
-
-
-class MdxPosFfnArgs(ctypes.Structure):   # == mdx_posffn_args
-    _fields_ = [('X', c_void_p), ('ldx', c_int64), ('LF', c_void_p), ('ldlf', c_int64), ('RF', c_void_p), ('ldrf', c_int64),
-                ('il', c_void_p), ('ir', c_void_p), ('te', c_void_p), ('Wb', c_void_p), ('ldwb', c_int64), ('Wn', c_void_p), ('ldwn', c_int64),
-                ('Wg1x', c_void_p), ('ldwg1x', c_int64), ('Wg1a', c_void_p), ('ldwg1a', c_int64), ('Wt', c_void_p), ('ldwt', c_int64),
-                ('bg1', c_void_p), ('gg', c_void_p), ('gbe', c_void_p), ('Wg2', c_void_p), ('bg2', c_void_p),
-                ('a', c_void_p), ('prod', c_void_p), ('gpre', c_void_p), ('gpost', c_void_p), ('gate', c_void_p), ('E', c_int64)]
-
-
-class MdxPosFfnBwdArgs(ctypes.Structure):   # == mdx_posffn_bwd_args
-    _fields_ = [('f', MdxPosFfnArgs), ('g_prod', c_void_p), ('ldgp', c_int64), ('g_gate', c_void_p), ('g_bf', c_void_p), ('g_nf', c_void_p),
-                ('g_gpre', c_void_p), ('g_x', c_void_p), ('g_lf', c_void_p), ('g_rf', c_void_p), ('lnp', c_void_p)]
-
-
-class MdxPackJob(ctypes.Structure):   # == mdx_pack_job
-    _fields_ = [('W', c_void_p), ('ld', c_int64), ('n_out', c_int32), ('n_in', c_int32), ('perm', c_int32), ('trans', c_int32), ('out', c_void_p)]
-
-
-class MdxPackJobs(ctypes.Structure):   # == mdx_pack_jobs
-    _fields_ = [('job', MdxPackJob * 10), ('n', c_int32)]
-
-
-class MdxNodeMsgArgs(ctypes.Structure):   # == mdx_nodemsg_args
-    _fields_ = ([('X', c_void_p), ('ldx', c_int64), ('HN', c_void_p), ('ldhn', c_int64), ('PN', c_void_p), ('ldpn', c_int64), ('col', c_void_p)] +
-                [(n, c_void_p) for n in ('pk_w1e', 'pk_w2e', 'pk_wm', 'pk_wg1', 'pk_wg2', 'b1e', 'lng_e', 'lnb_e', 'b2e', 'bm', 'bg1', 'lng_g',
-                                         'lnb_g', 'bg2', 'he_pre', 'he_post', 'he', 'p', 'm0', 'g_pre', 'g_post', 'gt', 'msg')] + [('E', c_int64)])
-
-
-class MdxNodeMsgBwdArgs(ctypes.Structure):   # == mdx_nodemsg_bwd_args
-    _fields_ = ([('f', MdxNodeMsgArgs), ('gA', c_void_p), ('ldga', c_int64), ('row', c_void_p)] +
-                [(n, c_void_p) for n in ('pk_wg2t', 'pk_wg1t', 'pk_wmt', 'pk_w2et', 'pk_w1et', 'g_m0', 'g_gt', 'g_gpre', 'g_hne', 'g_he', 'g_pre',
-                                         'g_x', 'lnp')])
-
-
 class MdxConfig(ctypes.Structure):
     _fields_ = [('kind', c_int32), ('node_dim', c_int32), ('edge_dim', c_int32), ('num_blocks', c_int32),
                 ('cutoff', c_float), ('num_gaussians', c_int32), ('update_pos', c_int32), ('time_dim', c_int32),
@@ -291,15 +231,7 @@ def lib():
         L.mdx_op_sumsq.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
         L.mdx_op_adamw.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                    c_int64, c_void_p, c_float, c_void_p]
-        L.mdx_op_bondffn_fwd.argtypes = [POINTER(MdxBondFfnArgs), c_void_p]
-        L.mdx_op_bondffn_bwd.argtypes = [POINTER(MdxBondFfnBwdArgs), c_void_p]
-        L.mdx_op_edge_tail_fwd.argtypes = [POINTER(MdxEdgeTailArgs), c_void_p]
-        L.mdx_op_edge_tail_bwd.argtypes = [POINTER(MdxEdgeTailBwdArgs), c_void_p]
-        L.mdx_op_posffn_fwd.argtypes = [POINTER(MdxPosFfnArgs), c_void_p]
-        L.mdx_op_posffn_bwd.argtypes = [POINTER(MdxPosFfnBwdArgs), c_void_p]
-        L.mdx_op_pack_a.argtypes = [POINTER(MdxPackJobs), c_void_p]
-        L.mdx_op_nodemsg_fwd.argtypes = [POINTER(MdxNodeMsgArgs), c_void_p]
-        L.mdx_op_nodemsg_bwd.argtypes = [POINTER(MdxNodeMsgBwdArgs), c_void_p]
+        # (the fused training operators mdx_op_bondffn_* / edge_tail_* / posffn_* / nodemsg_* / pack_a are called from csrc/mdx_fast.cpp alone)
         _lib = L
     return _lib
 

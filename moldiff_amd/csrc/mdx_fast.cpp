@@ -1,18 +1,16 @@
-// Host-side fast path of the training step (round 6): the operator BODIES of moldiff_amd/train_ops.py in C++, and the only
-// implementation of the gradient sink and the weight-gradient queue.
-//
-// A training step issues ~850 launches through ~190 autograd nodes; with the bodies in Python (tensor normalisation, output allocation,
-// ctypes marshalling, gradient-sink bookkeeping) the host needs ~20 ms per step -- as long as the GPU does (profiles/r6_train_host_profile.txt:
-// a Linear node 32 us, a fused BondFFN node 110 us forward).  This module is the same logic against the same C ABI (include/moldiff_hip.h,
-// libmoldiff_hip.so), a pybind11 extension of the torch build in this image:
-//   * the gradient sink and the weight-gradient queue as C++ state (train_ops.grad_sink / flush_grad_sink / sgemm_tn forward to it; every
-//     sink record and queue entry of every precision mode is made here),
-//   * Linear, Linear+LayerNorm+ReLU and the element-wise operators as torch::autograd::Function nodes,
-//   * forward / backward bodies of the four fused row-owner operators (argument structs, buffers, queue entries, segment sums).
-// The nodes and bodies cover the float16 autocast mode with float16 containers inside a gradient sink (Trainer.step with precision='fp16',
-// the reference's use_amp: True); every other mode keeps the Python bodies.  torch is plumbing here too: allocation, autograd edges, the
-// current stream.
-// Reference lines replaced are those the Python bodies cite (models/common.py:181-201, models/graph.py:29-55,133-141,268-295,384-396).
+// Host side of the training step in C++ (round 6): a pybind11 extension of the torch build in this image over the C ABI of
+// libmoldiff_hip.so (include/moldiff_hip.h).  torch is plumbing here too: allocation, autograd edges, the current stream.
+//   * The gradient sink and the weight-gradient queue, as C++ state.  They exist only here: train_ops.grad_sink / flush_grad_sink /
+//     sgemm_tn forward to it, and every sink record and queue entry of every precision mode is made here.
+//   * Linear, Linear+LayerNorm+ReLU and the element-wise operators as torch::autograd::Function nodes, for the float16 autocast mode
+//     with float16 containers inside a gradient sink (Trainer.step with precision='fp16', the reference's use_amp: True).  Every other
+//     mode keeps their Python bodies in train_ops.py; the two are held bit-identical (tests/test_gpu_trainer.py).
+//   * The ONE host body of each of the four fused row-owner operators (*_fwd / *_bwd: argument blocks, buffers, launches, segment sums),
+//     in any mode that runs them.  Only the disposal of their parameter gradients has two routes: queued and recorded here when the
+//     sink holds every parameter, else handed back to train_ops as lists of tensors (param_grads below).
+// With these bodies in Python the host needed ~20 ms per step -- as long as the GPU (profiles/r6_train_host_profile.txt: a Linear node
+// 32 us, a fused BondFFN node 110 us forward) -- for ~850 launches through ~190 autograd nodes.
+// Reference lines replaced are those train_ops.py cites (models/common.py:181-201, models/graph.py:29-55,133-141,268-295,384-396).
 #include <torch/extension.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <c10/hip/HIPStream.h>
@@ -36,6 +34,8 @@ inline void* cur_stream() { return (void*)c10::hip::getCurrentHIPStream().stream
 inline void* P(const Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
 inline int64_t A(const Tensor& t) { return t.defined() ? (int64_t)(uintptr_t)t.data_ptr() : 0; }
 inline int H(const Tensor& t) { return (t.defined() && t.scalar_type() == at::kHalf) ? 1 : 0; }
+inline const float* F32(const Tensor& t) { return reinterpret_cast<const float*>(t.data_ptr()); }
+inline const int64_t* I64(const Tensor& t) { return reinterpret_cast<const int64_t*>(t.data_ptr()); }
 inline void need_gpu(const Tensor& t) {
   TORCH_CHECK(!t.defined() || t.is_cuda(), "moldiff_amd runs on a ROCm device only (got a CPU tensor); there is no CPU fallback.");
 }
@@ -532,24 +532,22 @@ class EwFn : public torch::autograd::Function<EwFn> {
 Tensor segsum_raw(const Tensor& src, const Tensor& order, const Tensor& ptr, int64_t n, bool out_half) {
   const int64_t F = src.size(1);
   Tensor out = at::empty({n, F}, src.options().dtype(out_half ? at::kHalf : at::kFloat));
-  chk(mdx_op_segsum_rows_t(src.data_ptr(), reinterpret_cast<const int64_t*>(order.data_ptr()), reinterpret_cast<const int64_t*>(ptr.data_ptr()), n,
-                           (int32_t)F, out.data_ptr(), H(src) | (H(out) << 1), cur_stream()));
+  chk(mdx_op_segsum_rows_t(src.data_ptr(), I64(order), I64(ptr), n, (int32_t)F, out.data_ptr(), H(src) | (H(out) << 1), cur_stream()));
   ++S.n_launch;
   return out;
 }
 
-// LayerNorm-parameter partial rows of a fused backward -> sink records
-void lnp_records(const Tensor& lnp, int64_t nwg, int64_t lnf, const std::vector<std::pair<const Tensor*, std::pair<int64_t, int64_t>>>& items) {
-  for (auto& it : items) {
-    const int64_t dst = sink_dst(*it.first);
-    TORCH_CHECK(dst, "fused backward: LayerNorm parameter not in the gradient sink");
-    sink_record(A(lnp) + 4 * it.second.first, dst, nwg, 1, it.second.second, it.second.second, lnf, 0, lnp);
-  }
+// ---- the four fused row-owner operators (csrc/mdx_train_fused.hip): the one host body of each ------------------------------------------
+// train_ops._BondFfnScatter / _EdgeTail / _PosFfnFront / _NodeMsg are autograd shells around *_fwd / *_bwd below; nothing else fills a
+// fused operator's argument block.  The forward halves need neither a sink nor the float16 sink mode.  A backward half launches, then
+// disposes of the parameter gradients by one of two routes (param_grads), then runs the segment sums.
+void check_params(const std::vector<Tensor>& p) {
+  for (auto& t : p) TORCH_CHECK(t.scalar_type() == at::kFloat && t.stride(-1) == 1, "fused operator: fp32 parameters with unit column stride expected");
 }
-inline void wg(const Tensor& gy, const Tensor& xin, const Tensor& w, const Tensor* b) {
-  const int64_t dst_w = sink_dst(w), dst_b = b ? sink_dst(*b) : 0;
-  TORCH_CHECK(dst_w && (!b || dst_b), "fused backward: weight not in the gradient sink");
-  wq_append(gy, xin, dst_w, w.stride(0), dst_b, rk_now());
+// one partial row of LayerNorm-parameter gradients per workgroup of a fused backward
+inline Tensor lnp_empty(int64_t lnf, const Tensor& like) { return at::empty({mdx_op_bondffn_workgroups(), lnf}, like.options().dtype(at::kFloat)); }
+inline Tensor seg(bool need, const Tensor& src, const Tensor& order, const Tensor& ptr, int64_t n, bool out_half) {
+  return need ? segsum_raw(src, order, ptr, n, out_half) : Tensor();
 }
 bool all_in_sink(const std::vector<Tensor>& ps) {
   if (!fast_mode() || !S.wq_on) return false;
@@ -557,11 +555,48 @@ bool all_in_sink(const std::vector<Tensor>& ps) {
     if (!sink_dst(p) || !p.requires_grad()) return false;
   return true;
 }
-inline const float* F32(const Tensor& t) { return reinterpret_cast<const float*>(t.data_ptr()); }
+
+// The parameter-gradient work of a fused backward, stated once per operator as two tables over its parameter list `p`:
+struct WGrad { int gy, xin, w, b; };      // dW[w] = ops[gy]^T ops[xin], its column sums -> bias b (-1: none); ops = the backward's operand list
+struct LnSlice { int p, off, width; };    // d p = column sums of lnp[:, off : off + width]
+// dispose (every parameter in the sink, float16 sink mode: all_in_sink): the contractions are queued and the slices recorded here, in table
+// order -> None.  Otherwise the tables resolved to tensors, for train_ops._fused_param_grads to defer or return each through autograd:
+// ([(gy, xin, w, b)], lnp, [(p, off, width)]).
+template <size_t NW, size_t NL>
+py::object param_grads(bool dispose, const std::vector<Tensor>& p, const Tensor* const* ops, const WGrad (&wgs)[NW], const LnSlice (&lns)[NL],
+                       const Tensor& lnp) {
+  if (!dispose) {
+    std::vector<std::tuple<Tensor, Tensor, int, int>> cs;
+    std::vector<std::tuple<int, int, int>> ls;
+    for (auto& c : wgs) cs.emplace_back(*ops[c.gy], *ops[c.xin], c.w, c.b);
+    for (auto& s : lns) ls.emplace_back(s.p, s.off, s.width);
+    return py::make_tuple(cs, lnp, ls);
+  }
+  for (auto& c : wgs) {
+    const Tensor& w = p[c.w];
+    const int64_t dst_w = sink_dst(w), dst_b = c.b >= 0 ? sink_dst(p[c.b]) : 0;
+    TORCH_CHECK(dst_w && (c.b < 0 || dst_b), "fused backward: weight not in the gradient sink");
+    wq_append(*ops[c.gy], *ops[c.xin], dst_w, w.stride(0), dst_b, rk_now());
+  }
+  for (auto& s : lns) {
+    const int64_t dst = sink_dst(p[s.p]);
+    TORCH_CHECK(dst, "fused backward: LayerNorm parameter not in the gradient sink");
+    sink_record(A(lnp) + 4 * s.off, dst, lnp.size(0), 1, s.width, s.width, lnp.size(1), 0, lnp);
+  }
+  return py::none();
+}
+// what a *_bwd returns: [g_x, g_a, g_b] after disposal here, else ([g_x, g_a, g_b], contractions, lnp, slices)
+inline py::object bwd_result(const py::object& tables, std::vector<Tensor> grads) {
+  return tables.is_none() ? py::cast(grads) : py::object(py::make_tuple(grads) + py::tuple(tables));
+}
 
 // ---- fused BondFFN + scatter_sum (train_ops._BondFfnScatter) -----------------------------------------------------------------------------
 // params: Wb, Wi1, bi1, g1, be1, Wi2, bi2, Wg1, bg1, gg, gbe, Wt, Wg2, bg2
 enum { B_Wb, B_Wi1, B_bi1, B_g1, B_be1, B_Wi2, B_bi2, B_Wg1, B_bg1, B_gg, B_gbe, B_Wt, B_Wg2, B_bg2 };
+enum { BO_g_inter, BO_g_gate, BO_g_pre1, BO_g_bf, BO_g_gpre, BO_post1, BO_gpost, BO_prod, BO_x, BO_time };   // bondffn_bwd's `ops`
+constexpr WGrad B_WG[] = {{BO_g_inter, BO_post1, B_Wi2, B_bi2}, {BO_g_gate, BO_gpost, B_Wg2, B_bg2}, {BO_g_pre1, BO_prod, B_Wi1, B_bi1},
+                          {BO_g_bf, BO_x, B_Wb, -1},            {BO_g_gpre, BO_x, B_Wg1, B_bg1},     {BO_g_gpre, BO_time, B_Wt, -1}};
+constexpr LnSlice B_LN[] = {{B_g1, 0, 128}, {B_be1, 128, 128}, {B_gg, 256, 32}, {B_gbe, 288, 32}};
 void bondffn_fill(mdx_bondffn_args& a, const Tensor& x, const Tensor& NL, const Tensor& GN, const Tensor& te, const Tensor& idx,
                   const std::vector<Tensor>& p, const std::vector<Tensor>& bufs) {
   a.X = x.data_ptr(), a.ldx = x.stride(0);
@@ -572,13 +607,10 @@ void bondffn_fill(mdx_bondffn_args& a, const Tensor& x, const Tensor& NL, const 
   a.Wt = F32(p[B_Wt]), a.ldwt = p[B_Wt].stride(0);
   a.Wg2 = F32(p[B_Wg2]), a.ldwg2 = p[B_Wg2].stride(0), a.bg2 = F32(p[B_bg2]);
   a.NL = NL.data_ptr(), a.ldnl = NL.stride(0), a.GN = F32(GN), a.ldgn = GN.stride(0);
-  a.idx = reinterpret_cast<const int64_t*>(idx.data_ptr()), a.te = F32(te);
+  a.idx = I64(idx), a.te = F32(te);
   a.prod = bufs[0].data_ptr(), a.pre1 = bufs[1].data_ptr(), a.post1 = bufs[2].data_ptr(), a.inter = bufs[3].data_ptr();
   a.gpre = bufs[4].data_ptr(), a.gpost = bufs[5].data_ptr(), a.gate = bufs[6].data_ptr(), a.out = bufs[7].data_ptr();
   a.E = x.size(0);
-}
-void check_params(const std::vector<Tensor>& p) {
-  for (auto& t : p) TORCH_CHECK(t.scalar_type() == at::kFloat && t.stride(-1) == 1, "fused operator: fp32 parameters with unit column stride expected");
 }
 // -> [S (n_out,64) fp32, x, NL, GN, te, prod, pre1, post1, inter, gpre, gpost, gate, out]
 std::vector<Tensor> bondffn_fwd(const Tensor& bond_in, const Tensor& NL, const Tensor& GN, const Tensor& time, const Tensor& idx,
@@ -596,45 +628,41 @@ std::vector<Tensor> bondffn_fwd(const Tensor& bond_in, const Tensor& NL, const T
   r.insert(r.end(), bufs.begin(), bufs.end());
   return r;
 }
-// saved = what bondffn_fwd returned after S; -> [g_x, g_NL, g_GN]
-std::vector<Tensor> bondffn_bwd(const Tensor& gS_in, const std::vector<Tensor>& saved, const Tensor& idx, const Tensor& i_order,
-                                const Tensor& i_ptr, int64_t n_in, const Tensor& oidx, const Tensor& time2d, const std::vector<Tensor>& params,
-                                bool need_x, bool need_nl, bool need_gn) {
+// saved = what bondffn_fwd returned after S; -> [g_x, g_NL, g_GN] (see bwd_result)
+py::object bondffn_bwd(const Tensor& gS_in, const std::vector<Tensor>& saved, const Tensor& idx, const Tensor& i_order, const Tensor& i_ptr,
+                       int64_t n_in, const Tensor& oidx, const Tensor& time2d, const std::vector<Tensor>& params, bool need_x, bool need_nl,
+                       bool need_gn, bool dispose) {
   const Tensor &x = saved[0], &NL = saved[1], &GN = saved[2], &te = saved[3];
   std::vector<Tensor> bufs(saved.begin() + 4, saved.begin() + 12);
   const int64_t E = x.size(0);
   Tensor gS = fc(gS_in);
   Tensor g_inter = half_empty(E, 64, x), g_gate = half_empty(E, 64, x), g_pre1 = half_empty(E, 128, x), g_bf = half_empty(E, 128, x),
          g_nl = half_empty(E, 128, x), g_gpre = half_empty(E, 32, x), g_x = half_empty(E, 64, x);
-  const int64_t nwg = mdx_op_bondffn_workgroups(), lnf = mdx_op_bondffn_lnp_floats();
-  Tensor lnp = at::empty({nwg, lnf}, x.options().dtype(at::kFloat));
+  Tensor lnp = lnp_empty(mdx_op_bondffn_lnp_floats(), x);
   mdx_bondffn_bwd_args b;
   bondffn_fill(b.f, x, NL, GN, te, idx, params, bufs);
-  b.gS = F32(gS), b.ldgs = gS.stride(0), b.oidx = reinterpret_cast<const int64_t*>(oidx.data_ptr());
+  b.gS = F32(gS), b.ldgs = gS.stride(0), b.oidx = I64(oidx);
   b.g_inter = g_inter.data_ptr(), b.g_gate = g_gate.data_ptr(), b.g_pre1 = g_pre1.data_ptr(), b.g_bf = g_bf.data_ptr();
   b.g_nl = g_nl.data_ptr(), b.g_gpre = g_gpre.data_ptr(), b.g_x = g_x.data_ptr(), b.lnp = reinterpret_cast<float*>(lnp.data_ptr());
   chk(mdx_op_bondffn_bwd(&b, cur_stream()));
   ++S.n_launch;
-  const auto& p = params;
-  wg(g_inter, bufs[2], p[B_Wi2], &p[B_bi2]);
-  wg(g_gate, bufs[5], p[B_Wg2], &p[B_bg2]);
-  wg(g_pre1, bufs[0], p[B_Wi1], &p[B_bi1]);
-  wg(g_bf, x, p[B_Wb], nullptr);
-  wg(g_gpre, x, p[B_Wg1], &p[B_bg1]);
-  wg(g_gpre, time2d, p[B_Wt], nullptr);
-  lnp_records(lnp, nwg, lnf, {{&p[B_g1], {0, 128}}, {&p[B_be1], {128, 128}}, {&p[B_gg], {256, 32}}, {&p[B_gbe], {288, 32}}});
-  return {need_x ? g_x : Tensor(), need_nl ? segsum_raw(g_nl, i_order, i_ptr, n_in, true) : Tensor(),
-          need_gn ? segsum_raw(g_gpre, i_order, i_ptr, n_in, false) : Tensor()};
+  const Tensor* ops[] = {&g_inter, &g_gate, &g_pre1, &g_bf, &g_gpre, &bufs[2], &bufs[5], &bufs[0], &x, &time2d};
+  py::object tables = param_grads(dispose, params, ops, B_WG, B_LN, lnp);
+  return bwd_result(tables, {need_x ? g_x : Tensor(), seg(need_nl, g_nl, i_order, i_ptr, n_in, true), seg(need_gn, g_gpre, i_order, i_ptr, n_in, false)});
 }
 
 // ---- fused EdgeBlock tail (train_ops._EdgeTail) ---------------------------------------------------------------------------------------------
 // params: Ws, bs, lng, lnb, Wo, bo
+enum { T_Ws, T_bs, T_lng, T_lnb, T_Wo, T_bo };
+enum { TO_g_out, TO_g_pre, TO_post, TO_x };   // edge_tail_bwd's `ops`
+constexpr WGrad T_WG[] = {{TO_g_out, TO_post, T_Wo, T_bo}, {TO_g_pre, TO_x, T_Ws, T_bs}};
+constexpr LnSlice T_LN[] = {{T_lng, 0, 64}, {T_lnb, 64, 64}};
 void edge_tail_fill(mdx_edge_tail_args& a, const Tensor& x, const Tensor& BL, const Tensor& BR, const Tensor& il, const Tensor& ir,
                     const std::vector<Tensor>& p, const Tensor& pre, const Tensor& post, const Tensor& out) {
   a.H = x.data_ptr(), a.ldh = x.stride(0), a.BL = BL.data_ptr(), a.ldbl = BL.stride(0), a.BR = BR.data_ptr(), a.ldbr = BR.stride(0);
-  a.il = reinterpret_cast<const int64_t*>(il.data_ptr()), a.ir = reinterpret_cast<const int64_t*>(ir.data_ptr());
-  a.Ws = F32(p[0]), a.ldws = p[0].stride(0), a.bs = F32(p[1]), a.lng = F32(p[2]), a.lnb = F32(p[3]);
-  a.Wo = F32(p[4]), a.ldwo = p[4].stride(0), a.bo = F32(p[5]);
+  a.il = I64(il), a.ir = I64(ir);
+  a.Ws = F32(p[T_Ws]), a.ldws = p[T_Ws].stride(0), a.bs = F32(p[T_bs]), a.lng = F32(p[T_lng]), a.lnb = F32(p[T_lnb]);
+  a.Wo = F32(p[T_Wo]), a.ldwo = p[T_Wo].stride(0), a.bo = F32(p[T_bo]);
   a.pre = pre.data_ptr(), a.post = post.data_ptr(), a.out = out.defined() ? out.data_ptr() : nullptr;
   a.E = x.size(0);
 }
@@ -651,62 +679,70 @@ std::vector<Tensor> edge_tail_fwd(const Tensor& h, const Tensor& BL, const Tenso
   ++S.n_launch;
   return {out, x, BLc, BRc, pre, post};
 }
-// -> [g_h, g_BL, g_BR]
-std::vector<Tensor> edge_tail_bwd(const Tensor& g_out_in, const std::vector<Tensor>& saved, const Tensor& il, const Tensor& ir,
-                                  const Tensor& l_order, const Tensor& l_ptr, const Tensor& r_order, const Tensor& r_ptr, int64_t n,
-                                  const std::vector<Tensor>& params, bool need_h, bool need_bl, bool need_br) {
+// -> [g_h, g_BL, g_BR] (see bwd_result)
+py::object edge_tail_bwd(const Tensor& g_out_in, const std::vector<Tensor>& saved, const Tensor& il, const Tensor& ir, const Tensor& l_order,
+                         const Tensor& l_ptr, const Tensor& r_order, const Tensor& r_ptr, int64_t n, const std::vector<Tensor>& params,
+                         bool need_h, bool need_bl, bool need_br, bool dispose) {
   const Tensor &x = saved[0], &BL = saved[1], &BR = saved[2], &pre = saved[3], &post = saved[4];
   const int64_t E = x.size(0);
   Tensor g_out = rows(g_out_in);
   if (g_out.scalar_type() != at::kHalf) g_out = g_out.to(at::kHalf);
   if (g_out.stride(0) % 4 || ((uintptr_t)g_out.data_ptr()) % 8) g_out = g_out.contiguous();
   Tensor g_pre = half_empty(E, 64, x), g_h = half_empty(E, 64, x);
-  const int64_t nwg = mdx_op_bondffn_workgroups(), lnf = mdx_op_edge_tail_lnp_floats();
-  Tensor lnp = at::empty({nwg, lnf}, x.options().dtype(at::kFloat));
+  Tensor lnp = lnp_empty(mdx_op_edge_tail_lnp_floats(), x);
   mdx_edge_tail_bwd_args b;
   edge_tail_fill(b.f, x, BL, BR, il, ir, params, pre, post, Tensor());
   b.g_out = g_out.data_ptr(), b.ldg = g_out.stride(0), b.g_pre = g_pre.data_ptr(), b.g_h = g_h.data_ptr();
   b.lnp = reinterpret_cast<float*>(lnp.data_ptr());
   chk(mdx_op_edge_tail_bwd(&b, cur_stream()));
   ++S.n_launch;
-  wg(g_out, post, params[4], &params[5]);
-  wg(g_pre, x, params[0], &params[1]);
-  lnp_records(lnp, nwg, lnf, {{&params[2], {0, 64}}, {&params[3], {64, 64}}});
-  return {need_h ? g_h : Tensor(), need_bl ? segsum_raw(g_pre, l_order, l_ptr, n, true) : Tensor(),
-          need_br ? segsum_raw(g_pre, r_order, r_ptr, n, true) : Tensor()};
+  const Tensor* ops[] = {&g_out, &g_pre, &post, &x};
+  py::object tables = param_grads(dispose, params, ops, T_WG, T_LN, lnp);
+  return bwd_result(tables, {need_h ? g_h : Tensor(), seg(need_bl, g_pre, l_order, l_ptr, n, true), seg(need_br, g_pre, r_order, r_ptr, n, true)});
 }
 
 // ---- fused PosUpdate front (train_ops._PosFfnFront) -----------------------------------------------------------------------------------------
 // params: Wb, Wn, Wg1x, Wg1a, Wt, bg1, gg, gbe, Wg2, bg2
+enum { P_Wb, P_Wn, P_Wg1x, P_Wg1a, P_Wt, P_bg1, P_gg, P_gbe, P_Wg2, P_bg2 };
+enum { PO_g_bf, PO_g_nf, PO_g_gpre, PO_g_gate, PO_x, PO_a, PO_gpost, PO_time };   // posffn_bwd's `ops`
+constexpr WGrad P_WG[] = {{PO_g_bf, PO_x, P_Wb, -1},     {PO_g_nf, PO_a, P_Wn, -1},      {PO_g_gpre, PO_x, P_Wg1x, P_bg1},
+                          {PO_g_gpre, PO_a, P_Wg1a, -1}, {PO_g_gpre, PO_time, P_Wt, -1}, {PO_g_gate, PO_gpost, P_Wg2, P_bg2}};
+constexpr LnSlice P_LN[] = {{P_gg, 0, 32}, {P_gbe, 32, 32}};
+// the kernel reads gate.net.3's weight row and bias without a stride: contiguous copies where they are not
+std::vector<Tensor> posffn_params(const std::vector<Tensor>& params) {
+  check_params(params);
+  std::vector<Tensor> p = params;
+  p[P_Wg2] = fc(p[P_Wg2]), p[P_bg2] = fc(p[P_bg2]);
+  return p;
+}
 void posffn_fill(mdx_posffn_args& a, const Tensor& x, const Tensor& LF, const Tensor& RF, const Tensor& te, const Tensor& il, const Tensor& ir,
                  const std::vector<Tensor>& p, const std::vector<Tensor>& bufs) {
   a.X = x.data_ptr(), a.ldx = x.stride(0), a.LF = LF.data_ptr(), a.ldlf = LF.stride(0), a.RF = RF.data_ptr(), a.ldrf = RF.stride(0);
-  a.il = reinterpret_cast<const int64_t*>(il.data_ptr()), a.ir = reinterpret_cast<const int64_t*>(ir.data_ptr()), a.te = F32(te);
-  a.Wb = F32(p[0]), a.ldwb = p[0].stride(0), a.Wn = F32(p[1]), a.ldwn = p[1].stride(0);
-  a.Wg1x = F32(p[2]), a.ldwg1x = p[2].stride(0), a.Wg1a = F32(p[3]), a.ldwg1a = p[3].stride(0), a.Wt = F32(p[4]), a.ldwt = p[4].stride(0);
-  a.bg1 = F32(p[5]), a.gg = F32(p[6]), a.gbe = F32(p[7]), a.Wg2 = F32(p[8]), a.bg2 = F32(p[9]);
+  a.il = I64(il), a.ir = I64(ir), a.te = F32(te);
+  a.Wb = F32(p[P_Wb]), a.ldwb = p[P_Wb].stride(0), a.Wn = F32(p[P_Wn]), a.ldwn = p[P_Wn].stride(0);
+  a.Wg1x = F32(p[P_Wg1x]), a.ldwg1x = p[P_Wg1x].stride(0), a.Wg1a = F32(p[P_Wg1a]), a.ldwg1a = p[P_Wg1a].stride(0);
+  a.Wt = F32(p[P_Wt]), a.ldwt = p[P_Wt].stride(0);
+  a.bg1 = F32(p[P_bg1]), a.gg = F32(p[P_gg]), a.gbe = F32(p[P_gbe]), a.Wg2 = F32(p[P_Wg2]), a.bg2 = F32(p[P_bg2]);
   a.a = bufs[0].data_ptr(), a.prod = bufs[1].data_ptr(), a.gpre = bufs[2].data_ptr(), a.gpost = bufs[3].data_ptr(), a.gate = bufs[4].data_ptr();
   a.E = x.size(0);
 }
 // -> [prod, gate, x, LF, RF, te, a, gpre, gpost]
 std::vector<Tensor> posffn_fwd(const Tensor& h_edge, const Tensor& LF, const Tensor& RF, const Tensor& time, const Tensor& il, const Tensor& ir,
                                const std::vector<Tensor>& params) {
-  check_params(params);
-  TORCH_CHECK(params[8].is_contiguous() && params[9].is_contiguous(), "posffn: gate.net.3 parameters must be contiguous");
+  const std::vector<Tensor> p = posffn_params(params);
   Tensor x = aligned_rows(h_edge, 8, 16), LFc = aligned_rows(LF, 8, 16), RFc = aligned_rows(RF, 8, 16), te = fc(time).reshape({-1});
   const int64_t E = x.size(0);
   std::vector<Tensor> bufs = {half_empty(E, 64, x), half_empty(E, 256, x), half_empty(E, 32, x), half_empty(E, 32, x), half_empty(E, 1, x)};
   mdx_posffn_args a;
-  posffn_fill(a, x, LFc, RFc, te, il, ir, params, bufs);
+  posffn_fill(a, x, LFc, RFc, te, il, ir, p, bufs);
   chk(mdx_op_posffn_fwd(&a, cur_stream()));
   ++S.n_launch;
   return {bufs[1], bufs[4], x, LFc, RFc, te, bufs[0], bufs[2], bufs[3]};
 }
-// saved = [x, LF, RF, te, a, gpre, gpost, prod, gate]; -> [g_x, g_LF, g_RF]
-std::vector<Tensor> posffn_bwd(const c10::optional<Tensor>& g_prod_in, const c10::optional<Tensor>& g_gate_in, const std::vector<Tensor>& saved,
-                               const Tensor& il, const Tensor& ir, const Tensor& l_order, const Tensor& l_ptr, const Tensor& r_order,
-                               const Tensor& r_ptr, int64_t n, const Tensor& time2d, const std::vector<Tensor>& params, bool need_x, bool need_lf,
-                               bool need_rf) {
+// saved = [x, LF, RF, te, a, gpre, gpost, prod, gate]; -> [g_x, g_LF, g_RF] (see bwd_result)
+py::object posffn_bwd(const c10::optional<Tensor>& g_prod_in, const c10::optional<Tensor>& g_gate_in, const std::vector<Tensor>& saved,
+                      const Tensor& il, const Tensor& ir, const Tensor& l_order, const Tensor& l_ptr, const Tensor& r_order, const Tensor& r_ptr,
+                      int64_t n, const Tensor& time2d, const std::vector<Tensor>& params, bool need_x, bool need_lf, bool need_rf, bool dispose) {
   const Tensor &x = saved[0], &LF = saved[1], &RF = saved[2], &te = saved[3];
   std::vector<Tensor> bufs = {saved[4], saved[7], saved[5], saved[6], saved[8]};
   const int64_t E = x.size(0);
@@ -718,30 +754,27 @@ std::vector<Tensor> posffn_bwd(const c10::optional<Tensor>& g_prod_in, const c10
   Tensor g_prod = f16(g_prod_in, 256), g_gate = f16(g_gate_in, 1);
   Tensor g_bf = half_empty(E, 256, x), g_nf = half_empty(E, 256, x), g_gpre = half_empty(E, 32, x), g_x = half_empty(E, 64, x),
          g_lf = half_empty(E, 64, x), g_rf = half_empty(E, 64, x);
-  const int64_t nwg = mdx_op_bondffn_workgroups(), lnf = mdx_op_posffn_lnp_floats();
-  Tensor lnp = at::empty({nwg, lnf}, x.options().dtype(at::kFloat));
+  Tensor lnp = lnp_empty(mdx_op_posffn_lnp_floats(), x);
   mdx_posffn_bwd_args b;
-  posffn_fill(b.f, x, LF, RF, te, il, ir, params, bufs);
+  posffn_fill(b.f, x, LF, RF, te, il, ir, posffn_params(params), bufs);
   b.g_prod = g_prod.data_ptr(), b.ldgp = g_prod.stride(0), b.g_gate = g_gate.data_ptr(), b.lnp = reinterpret_cast<float*>(lnp.data_ptr());
   b.g_bf = g_bf.data_ptr(), b.g_nf = g_nf.data_ptr(), b.g_gpre = g_gpre.data_ptr(), b.g_x = g_x.data_ptr(), b.g_lf = g_lf.data_ptr(),
   b.g_rf = g_rf.data_ptr();
   chk(mdx_op_posffn_bwd(&b, cur_stream()));
   ++S.n_launch;
-  const auto& p = params;
-  wg(g_bf, x, p[0], nullptr);
-  wg(g_nf, bufs[0], p[1], nullptr);
-  wg(g_gpre, x, p[2], &p[5]);
-  wg(g_gpre, bufs[0], p[3], nullptr);
-  wg(g_gpre, time2d, p[4], nullptr);
-  wg(g_gate, bufs[3], p[8], &p[9]);
-  lnp_records(lnp, nwg, lnf, {{&p[6], {0, 32}}, {&p[7], {32, 32}}});
-  return {need_x ? g_x : Tensor(), need_lf ? segsum_raw(g_lf, l_order, l_ptr, n, true) : Tensor(),
-          need_rf ? segsum_raw(g_rf, r_order, r_ptr, n, true) : Tensor()};
+  const Tensor* ops[] = {&g_bf, &g_nf, &g_gpre, &g_gate, &x, &bufs[0], &bufs[3], &time2d};
+  py::object tables = param_grads(dispose, params, ops, P_WG, P_LN, lnp);
+  return bwd_result(tables, {need_x ? g_x : Tensor(), seg(need_lf, g_lf, l_order, l_ptr, n, true), seg(need_rf, g_rf, r_order, r_ptr, n, true)});
 }
 
 // ---- fused NodeBlock message path (train_ops._NodeMsg) ----------------------------------------------------------------------------------------
 // params: W1e, b1e, lng_e, lnb_e, W2e, b2e, Wm, bm, Wg1, bg1, lng_g, lnb_g, Wg2, bg2
 enum { N_W1e, N_b1e, N_lng_e, N_lnb_e, N_W2e, N_b2e, N_Wm, N_bm, N_Wg1, N_bg1, N_lng_g, N_lnb_g, N_Wg2, N_bg2 };
+enum { NO_g_m0, NO_g_gt, NO_g_gpre, NO_g_he, NO_g_pre, NO_p, NO_g_post, NO_he_post, NO_x };   // nodemsg_bwd's `ops`
+constexpr WGrad N_WG[] = {{NO_g_m0, NO_p, N_Wm, N_bm},          {NO_g_gt, NO_g_post, N_Wg2, N_bg2}, {NO_g_gpre, NO_x, N_Wg1, N_bg1},
+                          {NO_g_he, NO_he_post, N_W2e, N_b2e}, {NO_g_pre, NO_x, N_W1e, N_b1e}};
+constexpr LnSlice N_LN[] = {{N_lng_e, 0, 256}, {N_lnb_e, 256, 256}, {N_lng_g, 512, 256}, {N_lnb_g, 768, 256}};
+// the ten A-operand packs of a call (one buffer, one launch): five forward, then their five transposes for the backward
 struct PackSpec { int w, n_out, n_in, perm, trans; };
 constexpr PackSpec PACKS[10] = {{N_W1e, 256, 64, 0, 0},  {N_W2e, 256, 256, 1, 0}, {N_Wm, 256, 256, 1, 0},  {N_Wg1, 256, 64, 0, 0},
                                 {N_Wg2, 256, 256, 1, 0}, {N_Wg2, 256, 256, 1, 1}, {N_Wg1, 64, 256, 1, 1},  {N_Wm, 256, 256, 1, 1},
@@ -749,7 +782,7 @@ constexpr PackSpec PACKS[10] = {{N_W1e, 256, 64, 0, 0},  {N_W2e, 256, 256, 1, 0}
 void nodemsg_fill(mdx_nodemsg_args& a, const Tensor& x, const Tensor& HN, const Tensor& PN, const Tensor& col, const std::vector<Tensor>& p,
                   const int64_t* packs, const std::vector<Tensor>& bufs) {
   a.X = x.data_ptr(), a.ldx = x.stride(0), a.HN = HN.data_ptr(), a.ldhn = HN.stride(0), a.PN = F32(PN), a.ldpn = PN.stride(0);
-  a.col = reinterpret_cast<const int64_t*>(col.data_ptr());
+  a.col = I64(col);
   a.pk_w1e = (const void*)packs[0], a.pk_w2e = (const void*)packs[1], a.pk_wm = (const void*)packs[2], a.pk_wg1 = (const void*)packs[3],
   a.pk_wg2 = (const void*)packs[4];
   a.b1e = F32(p[N_b1e]), a.lng_e = F32(p[N_lng_e]), a.lnb_e = F32(p[N_lnb_e]), a.b2e = F32(p[N_b2e]), a.bm = F32(p[N_bm]), a.bg1 = F32(p[N_bg1]);
@@ -794,9 +827,9 @@ std::vector<Tensor> nodemsg_fwd(const Tensor& edge_attr, const Tensor& HN, const
   r.insert(r.end(), bufs.begin(), bufs.begin() + 8);   // (msg is not kept)
   return r;
 }
-// saved = [x, HN, PN, packbuf, he_pre, he_post, he, p, m0, g_pre, g_post, gt]; -> [g_x, g_HN, g_PN]
-std::vector<Tensor> nodemsg_bwd(const Tensor& gA_in, const std::vector<Tensor>& saved, const Tensor& col, const Tensor& c_order, const Tensor& c_ptr,
-                                int64_t n, const Tensor& row, const std::vector<Tensor>& params, bool need_x, bool need_hn, bool need_pn) {
+// saved = [x, HN, PN, packbuf, he_pre, he_post, he, p, m0, g_pre, g_post, gt]; -> [g_x, g_HN, g_PN] (see bwd_result)
+py::object nodemsg_bwd(const Tensor& gA_in, const std::vector<Tensor>& saved, const Tensor& col, const Tensor& c_order, const Tensor& c_ptr,
+                       int64_t n, const Tensor& row, const std::vector<Tensor>& params, bool need_x, bool need_hn, bool need_pn, bool dispose) {
   const Tensor &x = saved[0], &HN = saved[1], &PN = saved[2], &buf = saved[3];
   std::vector<Tensor> bufs(saved.begin() + 4, saved.begin() + 12);
   bufs.push_back(saved[8]);   // (the forward's msg buffer is gone; the backward does not read it)
@@ -804,34 +837,27 @@ std::vector<Tensor> nodemsg_bwd(const Tensor& gA_in, const std::vector<Tensor>& 
   Tensor gA = fc(gA_in);
   Tensor g_m0 = half_empty(E, 256, x), g_gt = half_empty(E, 256, x), g_gpre = half_empty(E, 256, x), g_hne = half_empty(E, 256, x),
          g_he = half_empty(E, 256, x), g_pre = half_empty(E, 256, x), g_x = half_empty(E, 64, x);
-  const int64_t nwg = mdx_op_bondffn_workgroups(), lnf = mdx_op_nodemsg_lnp_floats();
-  Tensor lnp = at::empty({nwg, lnf}, x.options().dtype(at::kFloat));
+  Tensor lnp = lnp_empty(mdx_op_nodemsg_lnp_floats(), x);
   int64_t packs[10];
   pack_ptrs(buf, packs);
   mdx_nodemsg_bwd_args b;
   nodemsg_fill(b.f, x, HN, PN, col, params, packs, bufs);
-  b.gA = F32(gA), b.ldga = gA.stride(0), b.row = reinterpret_cast<const int64_t*>(row.data_ptr());
+  b.gA = F32(gA), b.ldga = gA.stride(0), b.row = I64(row);
   b.pk_wg2t = (const void*)packs[5], b.pk_wg1t = (const void*)packs[6], b.pk_wmt = (const void*)packs[7], b.pk_w2et = (const void*)packs[8],
   b.pk_w1et = (const void*)packs[9];
   b.g_m0 = g_m0.data_ptr(), b.g_gt = g_gt.data_ptr(), b.g_gpre = g_gpre.data_ptr(), b.g_hne = g_hne.data_ptr(), b.g_he = g_he.data_ptr(),
   b.g_pre = g_pre.data_ptr(), b.g_x = g_x.data_ptr(), b.lnp = reinterpret_cast<float*>(lnp.data_ptr());
   chk(mdx_op_nodemsg_bwd(&b, cur_stream()));
   ++S.n_launch;
-  const auto& p = params;
-  wg(g_m0, bufs[3], p[N_Wm], &p[N_bm]);
-  wg(g_gt, bufs[6], p[N_Wg2], &p[N_bg2]);
-  wg(g_gpre, x, p[N_Wg1], &p[N_bg1]);
-  wg(g_he, bufs[1], p[N_W2e], &p[N_b2e]);
-  wg(g_pre, x, p[N_W1e], &p[N_b1e]);
-  lnp_records(lnp, nwg, lnf, {{&p[N_lng_e], {0, 256}}, {&p[N_lnb_e], {256, 256}}, {&p[N_lng_g], {512, 256}}, {&p[N_lnb_g], {768, 256}}});
-  return {need_x ? g_x : Tensor(), need_hn ? segsum_raw(g_hne, c_order, c_ptr, n, true) : Tensor(),
-          need_pn ? segsum_raw(g_gpre, c_order, c_ptr, n, false) : Tensor()};
+  const Tensor* ops[] = {&g_m0, &g_gt, &g_gpre, &g_he, &g_pre, &bufs[3], &bufs[6], &bufs[1], &x};
+  py::object tables = param_grads(dispose, params, ops, N_WG, N_LN, lnp);
+  return bwd_result(tables, {need_x ? g_x : Tensor(), seg(need_hn, g_hne, c_order, c_ptr, n, true), seg(need_pn, g_gpre, c_order, c_ptr, n, false)});
 }
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.doc() = "moldiff_amd training fast path: operator bodies, gradient sink and weight-gradient queue in C++ (csrc/mdx_fast.cpp)";
+  m.doc() = "moldiff_amd training host side in C++: operator bodies, gradient sink and weight-gradient queue (csrc/mdx_fast.cpp)";
   m.def("set_precision", [](int a0, int autoc, int store) { S.amp0 = a0, S.amp_auto = autoc, S.amp_store = store; });
   m.def("set_options", [](bool wq_on, int64_t rows_, int64_t cap_bytes) { S.wq_on = wq_on, S.wgrad_rows = rows_, S.wq_cap = cap_bytes; });
   m.def("sink_begin", [](const Tensor& data, const Tensor& grad) {

@@ -1,12 +1,20 @@
 """Differentiable layer operators of the training path: ``torch.autograd.Function`` shells around the HIP forward /
-backward kernels of ``csrc/mdx_train.hip`` (C-ABI ``mdx_op_*``).
+backward kernels of ``csrc/mdx_train.hip`` and ``csrc/mdx_train_fused.hip`` (C-ABI ``mdx_op_*``).
 
 torch is the graph engine and the allocator here (it records which operator produced which tensor and calls the
 backward entry points in reverse order); every O(rows x features) computation -- Linear forward, data and weight
 gradients (MFMA SGEMM), LayerNorm(+ReLU), gates, gathers / segmented sums, edge geometry -- runs in the library.  There
 is no CPU fallback: CPU tensors raise.  Replaces, for training, ``torch.nn.functional.linear / layer_norm / relu``,
 ``torch_scatter.scatter_sum`` and index_select as used by the reference's models/graph.py and models/common.py.
+
+The per-operator nodes (Linear, LayerNorm, element-wise, gather / segment sum) have their host bodies here, over ctypes.  The
+four fused row-owner operators have ONE host body each, in the C++ extension (``csrc/mdx_fast.cpp``); their classes here
+marshal the index plans, call it, and choose between the two routes by which the parameter gradients leave a backward.
 """
+import bisect
+import ctypes
+import os
+
 import torch
 
 from . import _lib
@@ -14,16 +22,18 @@ from ._lib import ptr, stream, check
 
 ADD, SUB, MUL, GATE = 0, 1, 2, 3
 
-# ---- C++ fast path (round 6; csrc/mdx_fast.cpp -> moldiff_amd/_mdx_fast.so) ------------------------------------------------------------
-# The operator bodies below cost the host ~20 ms per training step in Python (a Linear node 32 us, a fused BondFFN node 110 us) -- as
-# long as the GPU needs for the step.  `_mdx_fast` holds the same logic in C++ against the same C ABI: Linear / Linear+LayerNorm+ReLU /
-# element-wise nodes as C++ autograd functions and the fused operators' forward / backward bodies, for the float16 autocast mode with
-# float16 containers inside a sink (Trainer.step, precision='fp16'); the Python bodies serve every other mode.  The gradient sink and the
-# weight-gradient queue exist only there, as C++ state: every sink record and queue entry goes through it, in any precision mode.  A
-# missing extension is an error, not a silent slow path.
+# ---- the C++ extension (round 6; csrc/mdx_fast.cpp -> moldiff_amd/_mdx_fast.so) --------------------------------------------------------
+# With every operator body in Python the host needed ~20 ms per training step (a Linear node 32 us, a fused BondFFN node 110 us) -- as
+# long as the GPU needs for the step.  `_mdx_fast` holds, against the same C ABI:
+#   * the gradient sink and the weight-gradient queue, which exist only there, as C++ state: every sink record and queue entry goes
+#     through it, in any precision mode;
+#   * Linear / Linear+LayerNorm+ReLU / element-wise nodes as C++ autograd functions for the float16 autocast mode with float16 containers
+#     inside a sink (Trainer.step, precision='fp16'); the Python bodies below serve every other mode;
+#   * the only host body of the four fused row-owner operators, in every mode that runs them (see "fused row-owner operators" below).
+# A missing extension is an error, not a silent slow path.
 _FASTMOD = None
-# False: the Python operator bodies also serve the float16 sink (the sink and the queue stay in C++).  For the test that holds the two
-# bit-identical (tests/test_gpu_trainer.py); not an environment switch.
+# False: the Python operator bodies, and the Python route of the fused operators' parameter gradients, also serve the float16 sink (the
+# sink and the queue stay in C++).  For the test that holds the two bit-identical (tests/test_gpu_trainer.py); not an environment switch.
 _CPP_NODES = True
 
 
@@ -39,6 +49,7 @@ def _fast():
                                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C moldiff_amd/csrc).  [{e}]') from e
         _FASTMOD = _mdx_fast
         _FASTMOD.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
+        _fast_sync_precision()
     return _FASTMOD
 
 
@@ -251,7 +262,6 @@ def _wgrad_layout(M, N, K, splits, half):
     key = (M, N, K, splits, half)
     r = _LAYOUTS.get(key)
     if r is None:
-        import ctypes
         S, boff = ctypes.c_int64(), ctypes.c_int64()
         check(_L().mdx_op_wgrad_layout(M, N, K, splits, half, ctypes.byref(S), ctypes.byref(boff)))
         r = _LAYOUTS[key] = (S.value, boff.value)
@@ -266,9 +276,9 @@ def _wgrad_layout(M, N, K, splits, half):
 # allocations) per step become <= 5; the row ranges are chosen for the queue as a whole (WGRAD_ROWS rows per block; a stand-alone launch
 # needs ~512 blocks of its own to fill the chip, i.e. up to 128 row ranges = 33 MB of partials for one 256 x 256 weight).
 # MDX_WGRAD_GROUPED=0 keeps the per-call launches.
-_WG_ON = __import__('os').environ.get('MDX_WGRAD_GROUPED', '1') != '0'
-WGRAD_ROWS = int(__import__('os').environ.get('MDX_WGRAD_ROWS', '2048'))
-WGRAD_QUEUE_BYTES = int(float(__import__('os').environ.get('MDX_WGRAD_QUEUE_GB', '24')) * 2 ** 30)
+_WG_ON = os.environ.get('MDX_WGRAD_GROUPED', '1') != '0'
+WGRAD_ROWS = int(os.environ.get('MDX_WGRAD_ROWS', '2048'))
+WGRAD_QUEUE_BYTES = int(float(os.environ.get('MDX_WGRAD_QUEUE_GB', '24')) * 2 ** 30)
 
 
 def sgemm_tn(g, x, splits, want_bias=False, defer=None):
@@ -341,7 +351,6 @@ class TransposedParams:
 
     def view(self, w):
         """W^T of a parameter matrix or of a column slice of one, as a view into the transposed buffer; None if `w` is neither."""
-        import bisect
         rel = w.data_ptr() - self.base
         if rel < 0 or rel >= self.nbytes or w.dim() != 2 or w.dtype != torch.float32 or w.stride(1) != 1:
             return None
@@ -406,31 +415,16 @@ def colreduce(x, y=None):
     return out
 
 
-_ENV = None
-
-
-def _env():
-    """constants of the weight-gradient split (round 3's A/B environment knobs are gone: transpose-read kernel on, 512 workgroups
-    targeted, 64-wide tiles for the conversion kernel)"""
-    global _ENV
-    if _ENV is None:
-        _ENV = (True, 512, False)
-    return _ENV
-
-
 def _splits_for(rows, n, k, half=False):
     """row ranges of a weight gradient (the contraction runs over `rows`): enough of them to fill the chip with workgroups, each >= 128
     rows.  fp32 / converting kernels: 64 x 64 tiles, ~1024 workgroups (flat between 512 and 4096; each loops over its rows in short
     steps, many short loops hide the load latency better than few long ones).  float16 containers with tile-aligned widths take the
     transpose-read kernel (csrc hgemm_tn_tr_kernel): 128-wide tiles where the layer allows, ~512 workgroups = one resident set
     (two per CU); more ranges mean more split partials to write and reduce (measured per step: 384 -> 34.2, 512 -> 33.5, 768 -> 34.1, 1024 -> 34.8 ms)."""
-    use_tr, target, wide = _env()
-    if half and use_tr and n % 64 == 0 and k % 64 == 0:
+    if half and n % 64 == 0 and k % 64 == 0:
         tiles = (n // (128 if n % 128 == 0 else 64)) * (k // (128 if k % 128 == 0 else 64))
-        return max(1, min(rows // 128, (target + tiles - 1) // tiles))
-    tn = 128 if (wide and _AMP is not None and n >= 128) else 64
-    tk = 128 if (wide and _AMP is not None and k >= 128) else 64
-    tiles = ((n + tn - 1) // tn) * ((k + tk - 1) // tk)
+        return max(1, min(rows // 128, (512 + tiles - 1) // tiles))
+    tiles = ((n + 63) // 64) * ((k + 63) // 64)
     return max(1, min(rows // 128, (1024 + tiles - 1) // tiles))
 
 
@@ -700,7 +694,6 @@ class _Fanout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        import ctypes
         gs = [_t(g) for g in gs if g is not None]
         if not gs:
             return None, None
@@ -918,25 +911,90 @@ def force(w, rel, dist):
 
 
 # ---- fused row-owner operators (round 6; csrc/mdx_train_fused.hip) -------------------------------------------------------------------
-# A whole BondFFN of the EdgeBlock + the scatter_sum that follows it as ONE autograd node: 2 launches forward (fused chain, segment sum)
-# and 9 backward (fused data-gradient chain, 6 weight-gradient contractions, 2 segment sums) where the per-operator composition issues
-# 12 and ~28.  float16 autocast mode with float16 containers only; every other mode keeps the per-operator path.
+# BondFFN + the scatter_sum that follows it, the EdgeBlock tail, the PosUpdate front and the NodeBlock message path, each as ONE autograd
+# node.  The BondFFN: 2 launches forward (fused chain, segment sum) and 9 backward (fused data-gradient chain, 6 weight-gradient
+# contractions, 2 segment sums) where the per-operator composition issues 12 and ~28.  float16 autocast mode with float16 containers
+# only; every other mode keeps the per-operator path.
+# Each operator has one host body, in the extension (csrc/mdx_fast.cpp *_fwd / *_bwd): it normalises the operands, allocates the buffers,
+# fills the argument block, launches and runs the segment sums.  The classes below marshal the index plans and call it.  Only the
+# parameter gradients leave a backward by one of two routes (_fused_backward):
+#   * inside a float16 sink that holds every parameter of the node (`all_in_sink`; Trainer.step), the C++ side queues the weight-gradient
+#     contractions and records the LayerNorm partial rows itself: no parameter gradient passes through autograd;
+#   * otherwise it hands the contractions and the LayerNorm slices back as tensors, and _fused_param_grads defers each into the sink
+#     or returns it through autograd, parameter by parameter.
 FUSED_MIN_ROWS = 1024   # below this the per-operator path runs (tests lower it to cover the fused path on small graphs)
-_FUSED = __import__('os').environ.get('MDX_TRAIN_FUSED', '1') != '0'
+_FUSED = os.environ.get('MDX_TRAIN_FUSED', '1') != '0'
+_FUSED_TAIL = True
+_FUSED_POS = True
+_FUSED_NODE = True
+
+
+def _fused_mode():
+    """the mode the fused kernels are built for: float16 autocast with float16 containers"""
+    return _FUSED and _AMP is not None and _AMP[0] == 2 and _AMP[1] and _AMP[2]
+
+
+def _wgrad_into(grads, need, ps, gy, xin, wi, bi):
+    """weight (+ bias) gradient of one Linear inside a fused node (parameters ps[wi], ps[bi]; bi < 0: no bias): deferred into the flat
+    gradient buffer when a sink holds the parameter, else returned through `grads`"""
+    if not need[wi]:
+        return
+    w = ps[wi]
+    want_b = bi >= 0 and need[bi]
+    dst_w = _sink_dst(w)
+    dst_b = _sink_dst(ps[bi]) if want_b else None
+    sp = _splits_for(gy.shape[0], gy.shape[1], xin.shape[1], _h(gy) and _h(xin))
+    if dst_w is not None and (not want_b or dst_b is not None):
+        sgemm_tn(gy, xin, sp, want_bias=want_b, defer=(dst_w, w.stride(0), dst_b))
+    else:
+        r = sgemm_tn(gy, xin, sp, want_bias=want_b)
+        grads[wi], gb_ = r if want_b else (r, None)
+        if want_b:
+            grads[bi] = gb_
+
+
+def _fused_param_grads(ps, need, contractions, lnp, slices):
+    """The Python route of a fused backward's parameter gradients -> one gradient (or None) per parameter of `ps`.  contractions:
+    [(gy, xin, weight index, bias index)]; slices: [(parameter index, float offset in lnp, width)] of the LayerNorm-parameter
+    gradients, one partial row per workgroup in lnp."""
+    grads = [None] * len(ps)
+    for gy, xin, wi, bi in contractions:
+        _wgrad_into(grads, need, ps, gy, xin, wi, bi)
+    nwg, lnf = lnp.shape
+    for pi, off, F in slices:
+        if not need[pi]:
+            continue
+        dst = _sink_dst(ps[pi])
+        if dst is not None:
+            _sink_record(lnp.data_ptr() + 4 * off, dst, nwg, 1, F, F, lnf, 0, lnp)
+        else:
+            grads[pi] = lnp[:, off:off + F].sum(0)
+    return grads
+
+
+def _fused_backward(ctx, n_in, bwd):
+    """backward of a fused node whose first three inputs of n_in are differentiable tensors and whose parameters (ctx.ps) follow them.
+    bwd(F, needs_input_grad, dispose) calls the operator's F.*_bwd, in the precision of the forward."""
+    ni, ps = ctx.needs_input_grad, ctx.ps
+    with precision(ctx.prec):
+        F = _cpp()
+        if F is not None and F.all_in_sink(ps):
+            g, pgrads = bwd(F, ni, True), [None] * len(ps)
+        else:
+            g, contractions, lnp, slices = bwd(_fast(), ni, False)
+            pgrads = _fused_param_grads(ps, ni[n_in:], contractions, lnp, slices)
+    gx = g[0]
+    if gx is not None and gx.dtype != ctx.x_dtype:
+        gx = gx.to(ctx.x_dtype)
+    ctx.saved = None
+    return (gx, g[1], g[2]) + (None,) * (n_in - 3) + tuple(pgrads)
 
 
 def bondffn_fused_ok(bond_in, node_lin, gate_node, dims):
     """dims = (bond, inter, out, gate hidden, node columns of the gate): the kernel is built for (64, 128, 64, 32, any)."""
-    return (_FUSED and _AMP is not None and _AMP[0] == 2 and _AMP[1] and _AMP[2] and bond_in.dtype == torch.float16 and bond_in.dim() == 2
+    return (_fused_mode() and bond_in.dtype == torch.float16 and bond_in.dim() == 2
             and bond_in.shape[0] >= FUSED_MIN_ROWS and dims[:4] == (64, 128, 64, 32) and node_lin.dtype == torch.float16
             and gate_node.dtype == torch.float32)
-
-
-def _wslice(w):
-    """a weight or a column slice of one: fp32, unit column stride (row stride arbitrary)"""
-    w = w.detach()
-    assert w.dtype == torch.float32 and w.stride(-1) == 1
-    return w
 
 
 class _BondFfnScatter(torch.autograd.Function):
@@ -946,122 +1004,29 @@ class _BondFfnScatter(torch.autograd.Function):
     PARAMS = ('Wb', 'Wi1', 'bi1', 'g1', 'be1', 'Wi2', 'bi2', 'Wg1', 'bg1', 'gg', 'gbe', 'Wt', 'Wg2', 'bg2')
 
     @staticmethod
-    def _args(x, NL, GN, time, plan_in, P, bufs, E):
-        a = _lib.MdxBondFfnArgs()
-        a.X, a.ldx = x.data_ptr(), x.stride(0)
-        for nm, ld in (('Wb', 'ldwb'), ('Wi1', 'ldwi1'), ('Wi2', 'ldwi2'), ('Wg1', 'ldwg1'), ('Wg2', 'ldwg2')):
-            setattr(a, nm, P[nm].data_ptr())
-            setattr(a, ld, P[nm].stride(0))
-        a.Wt, a.ldwt = P['Wt'].data_ptr(), P['Wt'].stride(0)
-        for nm in ('bi1', 'g1', 'be1', 'bi2', 'bg1', 'gg', 'gbe', 'bg2'):
-            setattr(a, nm, P[nm].data_ptr())
-        a.NL, a.ldnl, a.GN, a.ldgn = NL.data_ptr(), NL.stride(0), GN.data_ptr(), GN.stride(0)
-        a.idx, a.te = plan_in.index.data_ptr(), time.data_ptr()
-        for nm, t in bufs.items():
-            setattr(a, nm, t.data_ptr())
-        a.E = E
-        return a
-
-    @staticmethod
     def forward(ctx, bond_in, NL, GN, time, plan_in, plan_out, *params):
-        import ctypes
-        x = _rows(bond_in)
-        if x.stride(0) % 8 or x.data_ptr() % 16:
-            x = x.contiguous()
-        NLc, GNc = _rows(NL), _rows(GN)
-        tc = _c(time).reshape(-1)
-        P = {k: _wslice(v) if v.dim() == 2 else _c(v) for k, v in zip(_BondFfnScatter.PARAMS, params)}
-        E, dev = x.shape[0], x.device
-        h = lambda f: torch.empty(E, f, dtype=torch.float16, device=dev)
-        bufs = {'prod': h(128), 'pre1': h(128), 'post1': h(128), 'inter': h(64), 'gpre': h(32), 'gpost': h(32), 'gate': h(64), 'out': h(64)}
-        a = _BondFfnScatter._args(x, NLc, GNc, tc, plan_in, P, bufs, E)
-        check(_L().mdx_op_bondffn_fwd(ctypes.byref(a), stream()))
-        ctx.x, ctx.NL, ctx.GN, ctx.time, ctx.P, ctx.bufs = x, NLc, GNc, tc, P, bufs
-        ctx.plan_in, ctx.plan_out = plan_in, plan_out
-        ctx.refs = {k: v.detach() for k, v in zip(_BondFfnScatter.PARAMS, params)}     # (views of the parameters: addresses for the gradient sink)
-        ctx.time2d = time.detach()
-        ctx.prec = _AMP
-        ctx.x_dtype = bond_in.dtype
-        return _segsum_raw(bufs['out'], plan_out)
+        ps = list(params)
+        r = _fast().bondffn_fwd(bond_in, NL, GN, time, plan_in.index, plan_out.order, plan_out.ptr, plan_out.n, ps)
+        ctx.saved, ctx.ps, ctx.plan_in, ctx.plan_out = r[1:], ps, plan_in, plan_out
+        t2 = time.detach()
+        ctx.time2d = t2 if t2.dim() == 2 else t2.reshape(-1, 1)
+        ctx.prec, ctx.x_dtype = _AMP, bond_in.dtype
+        return r[0]
 
     @staticmethod
     def backward(ctx, gS):
-        import ctypes
-        x, P, bufs, E, dev = ctx.x, ctx.P, ctx.bufs, ctx.x.shape[0], ctx.x.device
-        gS = _c(gS)
-        h = lambda f: torch.empty(E, f, dtype=torch.float16, device=dev)
-        g = {'g_inter': h(64), 'g_gate': h(64), 'g_pre1': h(128), 'g_bf': h(128), 'g_nl': h(128), 'g_gpre': h(32), 'g_x': h(64)}
-        nwg, lnf = int(_L().mdx_op_bondffn_workgroups()), int(_L().mdx_op_bondffn_lnp_floats())
-        lnp = torch.empty(nwg, lnf, dtype=torch.float32, device=dev)
-        b = _lib.MdxBondFfnBwdArgs()
-        b.f = _BondFfnScatter._args(x, ctx.NL, ctx.GN, ctx.time, ctx.plan_in, P, bufs, E)
-        b.gS, b.ldgs, b.oidx = gS.data_ptr(), gS.stride(0), ctx.plan_out.index.data_ptr()
-        for nm, t in g.items():
-            setattr(b, nm, t.data_ptr())
-        b.lnp = lnp.data_ptr()
-        check(_L().mdx_op_bondffn_bwd(ctypes.byref(b), stream()))
-        need = dict(zip(_BondFfnScatter.PARAMS, ctx.needs_input_grad[6:]))
-        grads = {k: None for k in _BondFfnScatter.PARAMS}
-        with precision(ctx.prec):
-            wgrad = lambda gy, xin, wname, bname: _wgrad_into(grads, need, ctx.refs, E, gy, xin, wname, bname)
-            wgrad(g['g_inter'], bufs['post1'], 'Wi2', 'bi2')
-            wgrad(g['g_gate'], bufs['gpost'], 'Wg2', 'bg2')
-            wgrad(g['g_pre1'], bufs['prod'], 'Wi1', 'bi1')
-            wgrad(g['g_bf'], x, 'Wb', None)
-            wgrad(g['g_gpre'], x, 'Wg1', 'bg1')
-            wgrad(g['g_gpre'], ctx.time2d if ctx.time2d.dim() == 2 else ctx.time2d.reshape(-1, 1), 'Wt', None)
-        # LayerNorm-parameter gradients: one partial row per workgroup
-        for nm, off, F in (('g1', 0, 128), ('be1', 128, 128), ('gg', 256, 32), ('gbe', 288, 32)):
-            if not need[nm]:
-                continue
-            dst = _sink_dst(ctx.refs[nm])
-            if dst is not None:
-                _sink_record(lnp.data_ptr() + 4 * off, dst, nwg, 1, F, F, lnf, 0, lnp)
-            else:
-                grads[nm] = lnp[:, off:off + F].sum(0)
-        ni = ctx.needs_input_grad
-        g_x = g['g_x'] if ni[0] else None
-        if g_x is not None and g_x.dtype != ctx.x_dtype:
-            g_x = g_x.to(ctx.x_dtype)
-        g_NL = _segsum_raw(g['g_nl'], ctx.plan_in, torch.float16) if ni[1] else None
-        g_GN = _segsum_raw(g['g_gpre'], ctx.plan_in, torch.float32) if ni[2] else None
-        ctx.bufs = ctx.P = None
-        return (g_x, g_NL, g_GN, None, None, None) + tuple(grads[k] for k in _BondFfnScatter.PARAMS)
+        pi = ctx.plan_in
+        return _fused_backward(ctx, 6, lambda F, ni, dispose: F.bondffn_bwd(
+            gS, ctx.saved, pi.index, pi.order, pi.ptr, pi.n, ctx.plan_out.index, ctx.time2d, ctx.ps, ni[0], ni[1], ni[2], dispose))
 
 
 def bondffn_scatter(bond_in, node_lin, gate_node, time, plan_in, plan_out, params):
     """params: dict with the keys of _BondFfnScatter.PARAMS (parameters or column slices of them)"""
-    ps = [params[k] for k in _BondFfnScatter.PARAMS]
-    F = _fast_for(ps)
-    if F is not None:
-        return _BondFfnScatterF.apply(F, bond_in, node_lin, gate_node, time, plan_in, plan_out, *ps)
-    return _BondFfnScatter.apply(bond_in, node_lin, gate_node, time, plan_in, plan_out, *ps)
-
-
-def _wgrad_into(grads, need, refs, E, gy, xin, wname, bname):
-    """weight (+ bias) gradient of one Linear inside a fused node: deferred into the flat gradient buffer when a sink holds the parameter,
-    else returned through `grads`"""
-    if not need[wname]:
-        return
-    w = refs[wname]
-    want_b = bname is not None and need[bname]
-    dst_w = _sink_dst(w)
-    dst_b = _sink_dst(refs[bname]) if want_b else None
-    sp = _splits_for(E, gy.shape[1], xin.shape[1], _h(gy) and _h(xin))
-    if dst_w is not None and (not want_b or dst_b is not None):
-        sgemm_tn(gy, xin, sp, want_bias=want_b, defer=(dst_w, w.stride(0), dst_b))
-    else:
-        r = sgemm_tn(gy, xin, sp, want_bias=want_b)
-        grads[wname], gb_ = r if want_b else (r, None)
-        if want_b:
-            grads[bname] = gb_
-
-
-_FUSED_TAIL = True
+    return _BondFfnScatter.apply(bond_in, node_lin, gate_node, time, plan_in, plan_out, *[params[k] for k in _BondFfnScatter.PARAMS])
 
 
 def edge_tail_fused_ok(h_bond, by_left, by_right):
-    return (_FUSED and _FUSED_TAIL and _AMP is not None and _AMP[0] == 2 and _AMP[1] and _AMP[2] and h_bond.dtype == torch.float16 and h_bond.dim() == 2
+    return (_fused_mode() and _FUSED_TAIL and h_bond.dtype == torch.float16 and h_bond.dim() == 2
             and h_bond.shape[1] == 64 and h_bond.shape[0] >= FUSED_MIN_ROWS and by_left.dtype == torch.float16 and by_right.dtype == torch.float16
             and by_left.shape[1] == 64 and by_right.shape[1] == 64)
 
@@ -1072,87 +1037,27 @@ class _EdgeTail(torch.autograd.Function):
     PARAMS = ('Ws', 'bs', 'lng', 'lnb', 'Wo', 'bo')
 
     @staticmethod
-    def _args(x, BL, BR, pl, pr, P, pre, post, out, E):
-        a = _lib.MdxEdgeTailArgs()
-        a.H, a.ldh, a.BL, a.ldbl, a.BR, a.ldbr = x.data_ptr(), x.stride(0), BL.data_ptr(), BL.stride(0), BR.data_ptr(), BR.stride(0)
-        a.il, a.ir = pl.index.data_ptr(), pr.index.data_ptr()
-        a.Ws, a.ldws, a.Wo, a.ldwo = P['Ws'].data_ptr(), P['Ws'].stride(0), P['Wo'].data_ptr(), P['Wo'].stride(0)
-        for nm in ('bs', 'lng', 'lnb', 'bo'):
-            setattr(a, nm, P[nm].data_ptr())
-        a.pre, a.post, a.out = pre.data_ptr(), post.data_ptr(), (out.data_ptr() if out is not None else None)
-        a.E = E
-        return a
-
-    @staticmethod
     def forward(ctx, h, BL, BR, plan_l, plan_r, *params):
-        import ctypes
-        x = _rows(h)
-        if x.stride(0) % 8 or x.data_ptr() % 16:
-            x = x.contiguous()
-        BLc, BRc = _rows(BL), _rows(BR)
-        P = {k: _wslice(v) if v.dim() == 2 else _c(v) for k, v in zip(_EdgeTail.PARAMS, params)}
-        E, dev = x.shape[0], x.device
-        pre, post, out = (torch.empty(E, 64, dtype=torch.float16, device=dev) for _ in range(3))
-        a = _EdgeTail._args(x, BLc, BRc, plan_l, plan_r, P, pre, post, out, E)
-        check(_L().mdx_op_edge_tail_fwd(ctypes.byref(a), stream()))
-        ctx.x, ctx.BL, ctx.BR, ctx.P, ctx.pre, ctx.post = x, BLc, BRc, P, pre, post
-        ctx.plan_l, ctx.plan_r, ctx.prec, ctx.x_dtype = plan_l, plan_r, _AMP, h.dtype
-        ctx.refs = {k: v.detach() for k, v in zip(_EdgeTail.PARAMS, params)}
-        return out
+        ps = list(params)
+        r = _fast().edge_tail_fwd(h, BL, BR, plan_l.index, plan_r.index, ps)
+        ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r = r[1:], ps, plan_l, plan_r
+        ctx.prec, ctx.x_dtype = _AMP, h.dtype
+        return r[0]
 
     @staticmethod
     def backward(ctx, g_out):
-        import ctypes
-        x, P, E, dev = ctx.x, ctx.P, ctx.x.shape[0], ctx.x.device
-        g_out = _rows(g_out)
-        if g_out.dtype != torch.float16:
-            g_out = g_out.to(torch.float16)
-        if g_out.stride(0) % 4 or g_out.data_ptr() % 8:
-            g_out = g_out.contiguous()
-        g_pre, g_h = torch.empty(E, 64, dtype=torch.float16, device=dev), torch.empty(E, 64, dtype=torch.float16, device=dev)
-        nwg, lnf = int(_L().mdx_op_bondffn_workgroups()), int(_L().mdx_op_edge_tail_lnp_floats())
-        lnp = torch.empty(nwg, lnf, dtype=torch.float32, device=dev)
-        b = _lib.MdxEdgeTailBwdArgs()
-        b.f = _EdgeTail._args(x, ctx.BL, ctx.BR, ctx.plan_l, ctx.plan_r, P, ctx.pre, ctx.post, None, E)
-        b.g_out, b.ldg, b.g_pre, b.g_h, b.lnp = g_out.data_ptr(), g_out.stride(0), g_pre.data_ptr(), g_h.data_ptr(), lnp.data_ptr()
-        check(_L().mdx_op_edge_tail_bwd(ctypes.byref(b), stream()))
-        need = dict(zip(_EdgeTail.PARAMS, ctx.needs_input_grad[5:]))
-        grads = {k: None for k in _EdgeTail.PARAMS}
-        with precision(ctx.prec):
-            _wgrad_into(grads, need, ctx.refs, E, g_out, ctx.post, 'Wo', 'bo')
-            _wgrad_into(grads, need, ctx.refs, E, g_pre, x, 'Ws', 'bs')
-        for nm, off in (('lng', 0), ('lnb', 64)):
-            if not need[nm]:
-                continue
-            dst = _sink_dst(ctx.refs[nm])
-            if dst is not None:
-                _sink_record(lnp.data_ptr() + 4 * off, dst, nwg, 1, 64, 64, lnf, 0, lnp)
-            else:
-                grads[nm] = lnp[:, off:off + 64].sum(0)
-        ni = ctx.needs_input_grad
-        gh = g_h if ni[0] else None
-        if gh is not None and gh.dtype != ctx.x_dtype:
-            gh = gh.to(ctx.x_dtype)
-        gBL = _segsum_raw(g_pre, ctx.plan_l, torch.float16) if ni[1] else None
-        gBR = _segsum_raw(g_pre, ctx.plan_r, torch.float16) if ni[2] else None
-        ctx.pre = ctx.post = ctx.P = None
-        return (gh, gBL, gBR, None, None) + tuple(grads[k] for k in _EdgeTail.PARAMS)
+        pl, pr = ctx.plan_l, ctx.plan_r
+        return _fused_backward(ctx, 5, lambda F, ni, dispose: F.edge_tail_bwd(
+            g_out, ctx.saved, pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr, pl.n, ctx.ps, ni[0], ni[1], ni[2], dispose))
 
 
 def edge_tail(h, by_left, by_right, plan_l, plan_r, params):
-    ps = [params[k] for k in _EdgeTail.PARAMS]
-    F = _fast_for(ps)
-    if F is not None:
-        return _EdgeTailF.apply(F, h, by_left, by_right, plan_l, plan_r, *ps)
-    return _EdgeTail.apply(h, by_left, by_right, plan_l, plan_r, *ps)
-
-
-_FUSED_POS = True
+    return _EdgeTail.apply(h, by_left, by_right, plan_l, plan_r, *[params[k] for k in _EdgeTail.PARAMS])
 
 
 def posffn_fused_ok(h_edge, lf, rf, dims):
     """dims = (bond, node, inter, gate hidden, out): the kernel is built for PosUpdate's BondFFN (64, 64, 256, 32, 1)"""
-    return (_FUSED and _FUSED_POS and _AMP is not None and _AMP[0] == 2 and _AMP[1] and _AMP[2] and h_edge.dtype == torch.float16 and h_edge.dim() == 2
+    return (_fused_mode() and _FUSED_POS and h_edge.dtype == torch.float16 and h_edge.dim() == 2
             and h_edge.shape[0] >= FUSED_MIN_ROWS and dims == (64, 64, 256, 32, 1) and lf.dtype == torch.float16 and rf.dtype == torch.float16
             and lf.shape[1] == 64 and rf.shape[1] == 64)
 
@@ -1164,102 +1069,32 @@ class _PosFfnFront(torch.autograd.Function):
     PARAMS = ('Wb', 'Wn', 'Wg1x', 'Wg1a', 'Wt', 'bg1', 'gg', 'gbe', 'Wg2', 'bg2')
 
     @staticmethod
-    def _args(x, LF, RF, tc, pl, pr, P, bufs, E):
-        a = _lib.MdxPosFfnArgs()
-        a.X, a.ldx, a.LF, a.ldlf, a.RF, a.ldrf = x.data_ptr(), x.stride(0), LF.data_ptr(), LF.stride(0), RF.data_ptr(), RF.stride(0)
-        a.il, a.ir, a.te = pl.index.data_ptr(), pr.index.data_ptr(), tc.data_ptr()
-        for nm, ld in (('Wb', 'ldwb'), ('Wn', 'ldwn'), ('Wg1x', 'ldwg1x'), ('Wg1a', 'ldwg1a'), ('Wt', 'ldwt')):
-            setattr(a, nm, P[nm].data_ptr())
-            setattr(a, ld, P[nm].stride(0))
-        for nm in ('bg1', 'gg', 'gbe', 'Wg2', 'bg2'):
-            setattr(a, nm, P[nm].data_ptr())
-        for nm, t in bufs.items():
-            setattr(a, nm, t.data_ptr())
-        a.E = E
-        return a
-
-    @staticmethod
     def forward(ctx, h_edge, LF, RF, time, plan_l, plan_r, *params):
-        import ctypes
-        al = lambda t: t if (t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0) else t.contiguous()
-        x, LFc, RFc = al(_rows(h_edge)), al(_rows(LF)), al(_rows(RF))
-        tc = _c(time).reshape(-1)
-        P = {}
-        for k, v in zip(_PosFfnFront.PARAMS, params):
-            P[k] = _wslice(v) if (v.dim() == 2 and k != 'Wg2') else _c(v).reshape(-1) if k in ('Wg2', 'bg2') else _c(v)
-        E, dev = x.shape[0], x.device
-        h = lambda *f: torch.empty(E, *f, dtype=torch.float16, device=dev)
-        bufs = {'a': h(64), 'prod': h(256), 'gpre': h(32), 'gpost': h(32), 'gate': h(1)}
-        a = _PosFfnFront._args(x, LFc, RFc, tc, plan_l, plan_r, P, bufs, E)
-        check(_L().mdx_op_posffn_fwd(ctypes.byref(a), stream()))
-        prod, gate = bufs.pop('prod'), bufs.pop('gate')
-        ctx.save_for_backward(prod, gate)     # (the outputs: on ctx itself they would form a cycle output -> grad_fn -> ctx -> output)
-        ctx.x, ctx.LF, ctx.RF, ctx.tc, ctx.P, ctx.bufs = x, LFc, RFc, tc, P, bufs
-        ctx.plan_l, ctx.plan_r, ctx.prec, ctx.x_dtype = plan_l, plan_r, _AMP, h_edge.dtype
-        ctx.refs = {k: v.detach() for k, v in zip(_PosFfnFront.PARAMS, params)}
+        ps = list(params)
+        r = _fast().posffn_fwd(h_edge, LF, RF, time, plan_l.index, plan_r.index, ps)
+        # the outputs [prod, gate] through save_for_backward (on ctx itself they would form a cycle output -> grad_fn -> ctx -> output),
+        # the rest [x, LF, RF, te, a, gpre, gpost] on ctx
+        ctx.save_for_backward(r[0], r[1])
+        ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r = r[2:], ps, plan_l, plan_r
         ctx.time2d = time.detach().reshape(-1, 1)
-        return prod, gate
+        ctx.prec, ctx.x_dtype = _AMP, h_edge.dtype
+        return r[0], r[1]
 
     @staticmethod
     def backward(ctx, g_prod, g_gate):
-        import ctypes
-        prod, gate = ctx.saved_tensors
-        x, P, bufs, E, dev = ctx.x, ctx.P, dict(ctx.bufs, prod=prod, gate=gate), ctx.x.shape[0], ctx.x.device
-        f16 = lambda t, f: (torch.zeros(E, f, dtype=torch.float16, device=dev) if t is None else
-                            (t if t.dtype == torch.float16 else t.to(torch.float16)).contiguous())
-        g_prod, g_gate = f16(g_prod, 256), f16(g_gate, 1)
-        h = lambda f: torch.empty(E, f, dtype=torch.float16, device=dev)
-        g = {'g_bf': h(256), 'g_nf': h(256), 'g_gpre': h(32), 'g_x': h(64), 'g_lf': h(64), 'g_rf': h(64)}
-        nwg, lnf = int(_L().mdx_op_bondffn_workgroups()), int(_L().mdx_op_posffn_lnp_floats())
-        lnp = torch.empty(nwg, lnf, dtype=torch.float32, device=dev)
-        b = _lib.MdxPosFfnBwdArgs()
-        b.f = _PosFfnFront._args(x, ctx.LF, ctx.RF, ctx.tc, ctx.plan_l, ctx.plan_r, P, bufs, E)
-        b.g_prod, b.ldgp, b.g_gate, b.lnp = g_prod.data_ptr(), g_prod.stride(0), g_gate.data_ptr(), lnp.data_ptr()
-        for nm, t in g.items():
-            setattr(b, nm, t.data_ptr())
-        check(_L().mdx_op_posffn_bwd(ctypes.byref(b), stream()))
-        need = dict(zip(_PosFfnFront.PARAMS, ctx.needs_input_grad[6:]))
-        grads = {k: None for k in _PosFfnFront.PARAMS}
-        with precision(ctx.prec):
-            wg = lambda gy, xin, wname, bname: _wgrad_into(grads, need, ctx.refs, E, gy, xin, wname, bname)
-            wg(g['g_bf'], x, 'Wb', None)
-            wg(g['g_nf'], bufs['a'], 'Wn', None)
-            wg(g['g_gpre'], x, 'Wg1x', 'bg1')
-            wg(g['g_gpre'], bufs['a'], 'Wg1a', None)
-            wg(g['g_gpre'], ctx.time2d, 'Wt', None)
-            wg(g_gate, bufs['gpost'], 'Wg2', 'bg2')
-        for nm, off in (('gg', 0), ('gbe', 32)):
-            if not need[nm]:
-                continue
-            dst = _sink_dst(ctx.refs[nm])
-            if dst is not None:
-                _sink_record(lnp.data_ptr() + 4 * off, dst, nwg, 1, 32, 32, lnf, 0, lnp)
-            else:
-                grads[nm] = lnp[:, off:off + 32].sum(0)
-        ni = ctx.needs_input_grad
-        g_x = g['g_x'] if ni[0] else None
-        if g_x is not None and g_x.dtype != ctx.x_dtype:
-            g_x = g_x.to(ctx.x_dtype)
-        g_LF = _segsum_raw(g['g_lf'], ctx.plan_l, torch.float16) if ni[1] else None
-        g_RF = _segsum_raw(g['g_rf'], ctx.plan_r, torch.float16) if ni[2] else None
-        ctx.bufs = ctx.P = None
-        return (g_x, g_LF, g_RF, None, None, None) + tuple(grads[k] for k in _PosFfnFront.PARAMS)
+        pl, pr = ctx.plan_l, ctx.plan_r
+        saved = ctx.saved + list(ctx.saved_tensors)
+        return _fused_backward(ctx, 6, lambda F, ni, dispose: F.posffn_bwd(
+            g_prod, g_gate, saved, pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr, pl.n, ctx.time2d, ctx.ps, ni[0], ni[1], ni[2], dispose))
 
 
 def posffn_front(h_edge, lf, rf, time, plan_l, plan_r, params):
-    ps = [params[k] for k in _PosFfnFront.PARAMS]
-    F = _fast_for(ps)
-    if F is not None and ps[8].is_contiguous() and ps[9].is_contiguous():
-        return _PosFfnFrontF.apply(F, h_edge, lf, rf, time, plan_l, plan_r, *ps)
-    return _PosFfnFront.apply(h_edge, lf, rf, time, plan_l, plan_r, *ps)
-
-
-_FUSED_NODE = True
+    return _PosFfnFront.apply(h_edge, lf, rf, time, plan_l, plan_r, *[params[k] for k in _PosFfnFront.PARAMS])
 
 
 def nodemsg_fused_ok(edge_attr, hn, pn, shapes):
     """shapes = (edge_net.0, edge_net.3, msg_net, gate.0 edge columns, gate.3 weight shapes): built for 64 -> 256 -> 256"""
-    return (_FUSED and _FUSED_NODE and _AMP is not None and _AMP[0] == 2 and _AMP[1] and _AMP[2] and edge_attr.dtype == torch.float16
+    return (_fused_mode() and _FUSED_NODE and edge_attr.dtype == torch.float16
             and edge_attr.dim() == 2 and edge_attr.shape[1] == 64 and edge_attr.shape[0] >= FUSED_MIN_ROWS and hn.dtype == torch.float16
             and hn.shape[1] == 256 and pn.dtype == torch.float32 and pn.shape[1] == 256
             and shapes == ((256, 64), (256, 256), (256, 256), (256, 64), (256, 256)))
@@ -1270,107 +1105,24 @@ class _NodeMsg(torch.autograd.Function):
     args = edge_attr (E,64) f16, HN = node_net(x) (N,256) f16, PN = gate.net.0[:, node + time columns](cat(x, t)) (N,256) fp32,
     plan_col (right), plan_row (left), then PARAMS."""
     PARAMS = ('W1e', 'b1e', 'lng_e', 'lnb_e', 'W2e', 'b2e', 'Wm', 'bm', 'Wg1', 'bg1', 'lng_g', 'lnb_g', 'Wg2', 'bg2')
-    # (name, weight, n_out, n_in, perm, trans) of the ten A-operand packs: five forward, five backward (transposes)
-    PACKS = (('pk_w1e', 'W1e', 256, 64, 0, 0), ('pk_w2e', 'W2e', 256, 256, 1, 0), ('pk_wm', 'Wm', 256, 256, 1, 0), ('pk_wg1', 'Wg1', 256, 64, 0, 0),
-             ('pk_wg2', 'Wg2', 256, 256, 1, 0), ('pk_wg2t', 'Wg2', 256, 256, 1, 1), ('pk_wg1t', 'Wg1', 64, 256, 1, 1), ('pk_wmt', 'Wm', 256, 256, 1, 1),
-             ('pk_w2et', 'W2e', 256, 256, 1, 1), ('pk_w1et', 'W1e', 64, 256, 1, 1))
-
-    @staticmethod
-    def _args(x, HN, PN, plan_col, P, packs, bufs, E):
-        a = _lib.MdxNodeMsgArgs()
-        a.X, a.ldx, a.HN, a.ldhn, a.PN, a.ldpn, a.col = x.data_ptr(), x.stride(0), HN.data_ptr(), HN.stride(0), PN.data_ptr(), PN.stride(0), plan_col.index.data_ptr()
-        for nm in ('pk_w1e', 'pk_w2e', 'pk_wm', 'pk_wg1', 'pk_wg2'):
-            setattr(a, nm, packs[nm])
-        for nm in ('b1e', 'lng_e', 'lnb_e', 'b2e', 'bm', 'bg1', 'lng_g', 'lnb_g', 'bg2'):
-            setattr(a, nm, P[nm].data_ptr())
-        for nm, t in bufs.items():
-            setattr(a, nm, t.data_ptr())
-        a.E = E
-        return a
 
     @staticmethod
     def forward(ctx, edge_attr, HN, PN, plan_col, plan_row, *params):
-        import ctypes
-        x = _rows(edge_attr)
-        if x.stride(0) % 8 or x.data_ptr() % 16:
-            x = x.contiguous()
-        HNc, PNc = _rows(HN), _rows(PN)
-        P = {k: _wslice(v) if v.dim() == 2 else _c(v) for k, v in zip(_NodeMsg.PARAMS, params)}
-        E, dev = x.shape[0], x.device
-        # the ten weight packs of this call: one buffer, one launch
-        sizes = [no * ni for _, _, no, ni, _, _ in _NodeMsg.PACKS]
-        buf = torch.empty(sum(sizes), dtype=torch.float16, device=dev)
-        jobs, packs, off = _lib.MdxPackJobs(), {}, 0
-        for i, (nm, wn, no, ni, perm, trans) in enumerate(_NodeMsg.PACKS):
-            j = jobs.job[i]
-            j.W, j.ld, j.n_out, j.n_in, j.perm, j.trans = P[wn].data_ptr(), P[wn].stride(0), no, ni, perm, trans
-            j.out = packs[nm] = buf.data_ptr() + 2 * off
-            off += sizes[i]
-        jobs.n = len(_NodeMsg.PACKS)
-        check(_L().mdx_op_pack_a(ctypes.byref(jobs), stream()))
-        h = lambda: torch.empty(E, 256, dtype=torch.float16, device=dev)
-        bufs = {k: h() for k in ('he_pre', 'he_post', 'he', 'p', 'm0', 'g_pre', 'g_post', 'gt', 'msg')}
-        a = _NodeMsg._args(x, HNc, PNc, plan_col, P, packs, bufs, E)
-        check(_L().mdx_op_nodemsg_fwd(ctypes.byref(a), stream()))
-        out = _segsum_raw(bufs['msg'], plan_row)
-        del bufs['msg']
-        ctx.x, ctx.HN, ctx.PN, ctx.P, ctx.bufs, ctx.packs, ctx.packbuf = x, HNc, PNc, P, bufs, packs, buf
-        ctx.plan_col, ctx.plan_row, ctx.prec, ctx.x_dtype = plan_col, plan_row, _AMP, edge_attr.dtype
-        ctx.refs = {k: v.detach() for k, v in zip(_NodeMsg.PARAMS, params)}
-        return out
+        ps = list(params)
+        r = _fast().nodemsg_fwd(edge_attr, HN, PN, plan_col.index, plan_row.order, plan_row.ptr, plan_row.n, ps)
+        ctx.saved, ctx.ps, ctx.plan_col, ctx.plan_row = r[1:], ps, plan_col, plan_row
+        ctx.prec, ctx.x_dtype = _AMP, edge_attr.dtype
+        return r[0]
 
     @staticmethod
     def backward(ctx, gA):
-        import ctypes
-        x, P, bufs, E, dev = ctx.x, ctx.P, ctx.bufs, ctx.x.shape[0], ctx.x.device
-        gA = _c(gA)
-        h = lambda f=256: torch.empty(E, f, dtype=torch.float16, device=dev)
-        g = {'g_m0': h(), 'g_gt': h(), 'g_gpre': h(), 'g_hne': h(), 'g_he': h(), 'g_pre': h(), 'g_x': h(64)}
-        nwg, lnf = int(_L().mdx_op_bondffn_workgroups()), int(_L().mdx_op_nodemsg_lnp_floats())
-        lnp = torch.empty(nwg, lnf, dtype=torch.float32, device=dev)
-        b = _lib.MdxNodeMsgBwdArgs()
-        fb = dict(bufs, msg=bufs['m0'])      # (the forward's msg buffer is gone; the backward does not read it)
-        b.f = _NodeMsg._args(x, ctx.HN, ctx.PN, ctx.plan_col, P, ctx.packs, fb, E)
-        b.gA, b.ldga, b.row = gA.data_ptr(), gA.stride(0), ctx.plan_row.index.data_ptr()
-        for nm in ('pk_wg2t', 'pk_wg1t', 'pk_wmt', 'pk_w2et', 'pk_w1et'):
-            setattr(b, nm, ctx.packs[nm])
-        for nm, t in g.items():
-            setattr(b, nm, t.data_ptr())
-        b.lnp = lnp.data_ptr()
-        check(_L().mdx_op_nodemsg_bwd(ctypes.byref(b), stream()))
-        need = dict(zip(_NodeMsg.PARAMS, ctx.needs_input_grad[5:]))
-        grads = {k: None for k in _NodeMsg.PARAMS}
-        with precision(ctx.prec):
-            wg = lambda gy, xin, wname, bname: _wgrad_into(grads, need, ctx.refs, E, gy, xin, wname, bname)
-            wg(g['g_m0'], bufs['p'], 'Wm', 'bm')
-            wg(g['g_gt'], bufs['g_post'], 'Wg2', 'bg2')
-            wg(g['g_gpre'], x, 'Wg1', 'bg1')
-            wg(g['g_he'], bufs['he_post'], 'W2e', 'b2e')
-            wg(g['g_pre'], x, 'W1e', 'b1e')
-        for nm, off in (('lng_e', 0), ('lnb_e', 256), ('lng_g', 512), ('lnb_g', 768)):
-            if not need[nm]:
-                continue
-            dst = _sink_dst(ctx.refs[nm])
-            if dst is not None:
-                _sink_record(lnp.data_ptr() + 4 * off, dst, nwg, 1, 256, 256, lnf, 0, lnp)
-            else:
-                grads[nm] = lnp[:, off:off + 256].sum(0)
-        ni = ctx.needs_input_grad
-        g_x = g['g_x'] if ni[0] else None
-        if g_x is not None and g_x.dtype != ctx.x_dtype:
-            g_x = g_x.to(ctx.x_dtype)
-        g_HN = _segsum_raw(g['g_hne'], ctx.plan_col, torch.float16) if ni[1] else None
-        g_PN = _segsum_raw(g['g_gpre'], ctx.plan_col, torch.float32) if ni[2] else None
-        ctx.bufs = ctx.P = ctx.packbuf = None
-        return (g_x, g_HN, g_PN, None, None) + tuple(grads[k] for k in _NodeMsg.PARAMS)
+        pc = ctx.plan_col
+        return _fused_backward(ctx, 5, lambda F, ni, dispose: F.nodemsg_bwd(
+            gA, ctx.saved, pc.index, pc.order, pc.ptr, pc.n, ctx.plan_row.index, ctx.ps, ni[0], ni[1], ni[2], dispose))
 
 
 def nodemsg(edge_attr, hn, pn, plan_col, plan_row, params):
-    ps = [params[k] for k in _NodeMsg.PARAMS]
-    F = _fast_for(ps)
-    if F is not None:
-        return _NodeMsgF.apply(F, edge_attr, hn, pn, plan_col, plan_row, *ps)
-    return _NodeMsg.apply(edge_attr, hn, pn, plan_col, plan_row, *ps)
+    return _NodeMsg.apply(edge_attr, hn, pn, plan_col, plan_row, *[params[k] for k in _NodeMsg.PARAMS])
 
 
 # ---- the categorical loss tail as one node (round 6; csrc/mdx_transition.hip cat_loss_kernel) -----------------------------------------
@@ -1403,103 +1155,3 @@ class _CatLoss(torch.autograd.Function):
 def cat_loss(transition, logits, log_vt, log_v0, t, batch):
     """torch.mean(transition.compute_v_Lt(q_v_posterior(log_v0, log_vt), q_v_posterior(log_softmax(logits), log_vt), log_v0)) * 100"""
     return _CatLoss.apply(logits, transition.q_mats, transition.transpopse_q_onestep_mats, log_vt, log_v0, t, batch)
-
-
-# ---- fused operators on the C++ fast path (csrc/mdx_fast.cpp): thin autograd shells --------------------------------------------------------
-# Same kernels, same buffers, same queue entries and sink records as the Python bodies above; the C++ side fills the argument structs,
-# allocates, launches, queues the weight gradients and runs the segment sums.  Parameter gradients never pass through autograd here (every
-# parameter lives in the gradient sink: `all_in_sink`), so the shells return None for them.
-def _fast_for(params):
-    F = _cpp()
-    return F if (F is not None and F.all_in_sink(params)) else None
-
-
-class _BondFfnScatterF(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, F, bond_in, NL, GN, time, plan_in, plan_out, *params):
-        ps = list(params)
-        ctx.prec = _AMP
-        r = F.bondffn_fwd(bond_in, NL, GN, time, plan_in.index, plan_out.order, plan_out.ptr, plan_out.n, ps)
-        ctx.F, ctx.saved, ctx.ps, ctx.plan_in, ctx.plan_out = F, r[1:], ps, plan_in, plan_out
-        t2 = time.detach()
-        ctx.time2d = t2 if t2.dim() == 2 else t2.reshape(-1, 1)
-        ctx.x_dtype = bond_in.dtype
-        return r[0]
-
-    @staticmethod
-    def backward(ctx, gS):
-        ni, pi = ctx.needs_input_grad, ctx.plan_in
-        with precision(ctx.prec):
-            g = ctx.F.bondffn_bwd(gS, ctx.saved, pi.index, pi.order, pi.ptr, pi.n, ctx.plan_out.index, ctx.time2d, ctx.ps, ni[1], ni[2], ni[3])
-        gx = g[0]
-        if gx is not None and gx.dtype != ctx.x_dtype:
-            gx = gx.to(ctx.x_dtype)
-        ctx.saved = None
-        return (None, gx, g[1], g[2], None, None, None) + (None,) * len(ctx.ps)
-
-
-class _EdgeTailF(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, F, h, BL, BR, plan_l, plan_r, *params):
-        ps = list(params)
-        ctx.prec = _AMP
-        r = F.edge_tail_fwd(h, BL, BR, plan_l.index, plan_r.index, ps)
-        ctx.F, ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r, ctx.x_dtype = F, r[1:], ps, plan_l, plan_r, h.dtype
-        return r[0]
-
-    @staticmethod
-    def backward(ctx, g_out):
-        ni, pl, pr = ctx.needs_input_grad, ctx.plan_l, ctx.plan_r
-        with precision(ctx.prec):
-            g = ctx.F.edge_tail_bwd(g_out, ctx.saved, pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr, pl.n, ctx.ps, ni[1], ni[2], ni[3])
-        gh = g[0]
-        if gh is not None and gh.dtype != ctx.x_dtype:
-            gh = gh.to(ctx.x_dtype)
-        ctx.saved = None
-        return (None, gh, g[1], g[2], None, None) + (None,) * len(ctx.ps)
-
-
-class _PosFfnFrontF(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, F, h_edge, LF, RF, time, plan_l, plan_r, *params):
-        ps = list(params)
-        ctx.prec = _AMP
-        r = F.posffn_fwd(h_edge, LF, RF, time, plan_l.index, plan_r.index, ps)
-        # saved for the backward: [x, LF, RF, te, a, gpre, gpost] on ctx, the outputs [prod, gate] through save_for_backward (no cycle)
-        ctx.save_for_backward(r[0], r[1])
-        ctx.F, ctx.saved, ctx.ps, ctx.plan_l, ctx.plan_r, ctx.x_dtype = F, r[2:], ps, plan_l, plan_r, h_edge.dtype
-        ctx.time2d = time.detach().reshape(-1, 1)
-        return r[0], r[1]
-
-    @staticmethod
-    def backward(ctx, g_prod, g_gate):
-        ni, pl, pr = ctx.needs_input_grad, ctx.plan_l, ctx.plan_r
-        with precision(ctx.prec):
-            g = ctx.F.posffn_bwd(g_prod, g_gate, ctx.saved + list(ctx.saved_tensors), pl.index, pr.index, pl.order, pl.ptr, pr.order, pr.ptr,
-                                 pl.n, ctx.time2d, ctx.ps, ni[1], ni[2], ni[3])
-        gx = g[0]
-        if gx is not None and gx.dtype != ctx.x_dtype:
-            gx = gx.to(ctx.x_dtype)
-        ctx.saved = None
-        return (None, gx, g[1], g[2], None, None, None) + (None,) * len(ctx.ps)
-
-
-class _NodeMsgF(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, F, edge_attr, HN, PN, plan_col, plan_row, *params):
-        ps = list(params)
-        ctx.prec = _AMP
-        r = F.nodemsg_fwd(edge_attr, HN, PN, plan_col.index, plan_row.order, plan_row.ptr, plan_row.n, ps)
-        ctx.F, ctx.saved, ctx.ps, ctx.plan_col, ctx.plan_row, ctx.x_dtype = F, r[1:], ps, plan_col, plan_row, edge_attr.dtype
-        return r[0]
-
-    @staticmethod
-    def backward(ctx, gA):
-        ni, pc = ctx.needs_input_grad, ctx.plan_col
-        with precision(ctx.prec):
-            g = ctx.F.nodemsg_bwd(gA, ctx.saved, pc.index, pc.order, pc.ptr, pc.n, ctx.plan_row.index, ctx.ps, ni[1], ni[2], ni[3])
-        gx = g[0]
-        if gx is not None and gx.dtype != ctx.x_dtype:
-            gx = gx.to(ctx.x_dtype)
-        ctx.saved = None
-        return (None, gx, g[1], g[2], None, None) + (None,) * len(ctx.ps)

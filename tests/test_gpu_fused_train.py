@@ -137,6 +137,29 @@ def test_fused_bondffn_with_the_gradient_sink_equals_autograd_accumulation():
         assert _rel(got, ref[k]) < 2e-3, (k, _rel(got, ref[k]))
 
 
+def test_fused_bondffn_with_a_sink_that_holds_some_of_its_parameters():
+    """A sink over the inter module alone: Wi1, bi1, g1, be1, Wi2 and bi2 are deferred into the flat gradient buffer, the other eight
+    parameters of the same fused node return through autograd.  Every parameter's gradient must be what the no-sink fused run gives."""
+    from moldiff_amd.trainer import FlatParams
+    m, x, h, te, gS, tg = _setup([5, 7, 4], 19)
+    _, _, _, ref = _run(m, x, h, te, gS, tg, fused=True)
+    m.zero_grad(set_to_none=True)
+    flat = FlatParams(m.inter_module)
+    inside = {id(p) for p in flat.params}
+    assert len(inside) == 6 and any(id(p) not in inside for p in m.parameters())
+    old, old_rows = T._FUSED, T.FUSED_MIN_ROWS
+    T._FUSED, T.FUSED_MIN_ROWS = True, 1
+    try:
+        with T.grad_sink(flat), T.precision('fp16'):
+            out = TG.bond_ffn_scatter(m, x.clone().requires_grad_(True), te, h.clone().requires_grad_(True), tg.left, tg.right)
+            out.backward(gS)
+    finally:
+        T._FUSED, T.FUSED_MIN_ROWS = old, old_rows
+    for k, p in m.named_parameters():
+        assert p.grad is not None, k
+        assert _rel(p.grad, ref[k]) < 2e-3, (k, _rel(p.grad, ref[k]))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # EdgeBlock (two fused BondFFNs + the fused tail with the residual) against the per-operator composition
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -297,8 +320,8 @@ def test_fused_node_block_equals_the_per_operator_composition(sizes):
 def test_posffn_front_outputs_are_freed_without_backward(sink):
     """The fused PosUpdate front keeps its outputs prod (E,256) and gate (E,1) for the backward.  Held on the autograd context they
     formed a cycle (output -> grad_fn -> ctx -> output): a forward that is never back-propagated kept them until the cyclic collector
-    ran.  Saved through save_for_backward they are freed as soon as the caller drops them -- on the C++ shell (fp16 sink) and on the
-    Python body (no sink)."""
+    ran.  Saved through save_for_backward they are freed as soon as the caller drops them -- inside a float16 sink and without one
+    (one autograd class serves both)."""
     import gc
     import weakref
     from moldiff_amd.trainer import FlatParams
@@ -326,7 +349,7 @@ def test_posffn_front_outputs_are_freed_without_backward(sink):
             refs = weakref.ref(prod), weakref.ref(gate)
             del prod, gate
         torch.cuda.synchronize()
-        assert name == ('_PosFfnFrontFBackward' if sink else '_PosFfnFrontBackward'), name
+        assert name == '_PosFfnFrontBackward', name
         assert refs[0]() is None and refs[1]() is None
     finally:
         T.FUSED_MIN_ROWS = old_rows

@@ -514,10 +514,12 @@ def test_fused_categorical_loss_equals_the_torch_tail():
 @pytest.mark.parametrize('fused_rows', [1024, 1])
 def test_cpp_nodes_are_bit_identical_to_the_python_bodies(fused_rows):
     """Round 6: csrc/mdx_fast.cpp (moldiff_amd/_mdx_fast.so) holds the training operators' host logic in C++ -- Linear / Linear+LayerNorm
-    / element-wise autograd nodes, the fused operators' bodies -- next to the gradient sink and weight-gradient queue it alone implements.
-    Same kernels, same buffers, same row ranges: the loss, the flat gradient buffer and the updated weights of two optimisation steps
-    must be BIT-identical with the C++ nodes (train_ops._CPP_NODES) on and off (fused_rows = 1: with the fused row-owner kernels forced
-    on at this size, so their C++ bodies run)."""
+    / element-wise autograd nodes, the route by which the fused operators' parameter gradients reach the sink -- next to the gradient
+    sink and weight-gradient queue it alone implements.  With train_ops._CPP_NODES off, the Python Linear / LayerNorm / element-wise
+    bodies and the Python route of the fused operators' parameter gradients run instead (the fused operators' launch code is shared:
+    nothing to compare there).  Same kernels, same buffers, same row ranges: the loss, the flat gradient buffer and the updated weights
+    of two optimisation steps must be BIT-identical with the C++ nodes on and off (fused_rows = 1: with the fused row-owner kernels
+    forced on at this size, so both routes of their parameter gradients run)."""
     import copy
     from moldiff_amd import train_ops
     base = U.moldiff('MolDiff', DEV)
