@@ -31,6 +31,17 @@ int mdx_set_error(int code, const char* msg) { return fail(code, "%s", msg); }  
     if (e_ != hipSuccess) return fail(MDX_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_));   \
   } while (0)
 
+// compute units of the current device (grid sizes of the persistent kernels; for the other translation units)
+int mdx_num_cus() {
+  static const int n = [] {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
+    return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+  }();
+  return n;
+}
+
 extern "C" const char* mdx_last_error(void) { return g_err; }
 extern "C" int mdx_version(void) { return 100; }
 extern "C" int mdx_device_count(int* count) {

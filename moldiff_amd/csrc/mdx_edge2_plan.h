@@ -1,5 +1,6 @@
-// Shared by the exact (mdx_edge2.hip) and the split-precision (mdx_edge2s.hip) row-owner edge kernel A: the LDS constant budget,
-// the static work plan with its section-cut tail, the work-queue item map and the one-unit-ahead prologue loads.
+// Host and device helpers of the row-owner edge kernel A (mdx_edge2_body.h; exact build mdx_edge2.hip, split build mdx_edge2s.hip):
+// the LDS constant budget, the static work plan with its section-cut tail, the work-queue item map and the one-unit-ahead
+// prologue loads.
 #pragma once
 #include "mdx_kernels.h"
 #include "mdx_row.h"

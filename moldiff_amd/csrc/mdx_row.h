@@ -283,7 +283,7 @@ __device__ __forceinline__ void row_dot(const f32x4 (&y)[FT][R], const float* __
   for (int rt = 0; rt < R; ++rt) out[rt] = red_q(s[rt]);
 }
 
-// ---- shared by the row-owner kernels (mdx_edge2.hip, mdx_bwd2.hip): tile shape, row indices, LDS constants ----
+// ---- shared by the row-owner kernels (mdx_edge2_body.h, mdx_edge2b_body.h, mdx_bwd2_body.h): tile shape, row indices, LDS constants ----
 // Rows per wave and waves per SIMD are build parameters of each kernel file.  Measured on the bench workload (ms per step,
 // kernel A / kernel B / backward): 32 rows x 1 wave  4.97 / 1.82 / 11.1;  16 rows x 2 waves  4.66 / 1.78 / 9.5 -- the second
 // wave covers the gather, store and LayerNorm phases of the first, and at 16 rows every kernel fits 256 registers.
@@ -335,6 +335,38 @@ __device__ __forceinline__ RowTile load_tile_u(const int* __restrict__ l, const 
   }
   t.cnt = cnt;
   return t;
+}
+
+// Work item u of an EA_AGG launch = the RR consecutive graph-aligned 16-row units RR u .. RR u + RR - 1 of the plan's table
+// (a.units: first edge, row count per unit), one per row tile: a wave with two row tiles shares every weight fragment between
+// two units, half the weight stream per edge.  Each row tile keeps its own unit's rows, row count (`cnt`, 0 for a tile past the
+// table's end) and partial-row index, so the partial rows -- and every result -- are the same whatever RR is.  (The argument
+// block is read here, field by field where it is used, as the kernels did inline: passed as six values the fields are loaded in
+// another order and the split kernel's register allocation comes out different.)
+template <class Args>  // EdgeAArgs: l, r, te, epo, the unit table (units, nunits)
+__device__ __forceinline__ RowTile load_tile_units(const Args& a, int u, int c, int (&cnt)[RR]) {
+  if constexpr (RR == 1) {
+    const int2 ue = reinterpret_cast<const int2*>(a.units)[u];
+    cnt[0] = ue.y;
+    return load_tile_u(a.l, a.r, a.te, a.epo, ue.x, ue.y, a.E, c);
+  } else {
+    RowTile t;
+#pragma unroll
+    for (int rt = 0; rt < RR; ++rt) {
+      const int uu = min(RR * u + rt, a.nunits - 1);
+      const int2 ue = reinterpret_cast<const int2*>(a.units)[uu];
+      const int n = (RR * u + rt < a.nunits) ? ue.y : 0;
+      cnt[rt] = n;
+      t.valid[rt] = c < n;
+      t.row[rt] = t.valid[rt] ? ue.x + c : ue.x;  // clamped to the unit's first row (always a row of the same graph)
+      t.li[rt] = a.l[t.row[rt]];
+      t.ri[rt] = a.r[t.row[rt]];
+      t.tt[rt] = a.te[t.row[rt]];
+      t.pf[rt] = a.epo[t.row[rt]];
+    }
+    t.cnt = cnt[0];
+    return t;
+  }
 }
 
 // unit of the guidance backward (round 5): `cnt` (<= 16) positions from j0 of the BY-RIGHT edge order (col_eids); the tile's rows

@@ -556,7 +556,7 @@ __global__ __launch_bounds__(512) void hgemm_nt_rows_kernel(const _Float16* __re
 }
 
 }  // namespace
-int mdx_num_cus();  // mdx_edge2.hip
+int mdx_num_cus();  // mdx_api.hip
 namespace {
 template <int KT, int FT, bool ROUND, bool LN = false>
 static void launch_hgemm_nt_rows(const _Float16* A, int lda, const float* B, int ldb, const float* bias, const TP& addend, int ldd,

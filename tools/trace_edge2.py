@@ -3,7 +3,7 @@
     tools/build_variant.sh trace2 -DMDX_TRACE2
     python tools/trace_edge2.py a          # on the GPU box
 
-Lane 0 of every wave stamps clock64() at the phase boundaries (STAMP in csrc/mdx_edge2.hip) and the 100 MHz wall clock at
+Lane 0 of every wave stamps clock64() at the phase boundaries (STAMP in csrc/mdx_edge2_body.h) and the 100 MHz wall clock at
 entry and exit.  Printed per phase: mean duration over all 32-edge units next to the time the phase's MFMAs alone need on
 the wave's SIMD (64 flop/clk at the measured shader clock).
 """

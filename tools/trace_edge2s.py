@@ -3,7 +3,8 @@
     tools/build_variant.sh trace2s -DMDX_TRACE2S mdx_edge2s.hip
     MOLDIFF_MATRIX_PATH=split_f16 python tools/trace_edge2s.py          # on the GPU box
 
-Lane 0 of every wave stamps clock64() around the GEMMs of the NodeBlock message path (STAMPS in csrc/mdx_edge2s.hip).  Printed per
+Lane 0 of every wave stamps clock64() at the phase boundaries (STAMP in csrc/mdx_edge2_body.h, 48 slots per work item; the BondFFN
+stamps 14..32 are recorded too and not printed here).  Printed per
 phase: mean cycles per work item (32 rows), and for GEMM phases the cycles per MFMA next to the ~17 the instruction needs.
 """
 import ctypes
@@ -22,10 +23,11 @@ import bench  # noqa: E402
 
 RR = 2
 # (name, first stamp, last stamp, MFMAs per wave: feature tiles x row tiles x k-groups x 3)
-PH = [('emb GEMM 80->64 (+ smear, split)', 0, 1, 4 * RR * 3 * 3), ('gate init: gx[r] gather, bias', 1, 2, 0),
-      ('gate GEMM1 64->256', 2, 3, 16 * RR * 2 * 3), ('LN256 + split + bias', 3, 4, 0), ('gate GEMM2 256->256', 4, 5, 16 * RR * 8 * 3),
-      ('sigmoid + park + bias', 5, 6, 0), ('en GEMM1 64->256', 6, 7, 16 * RR * 2 * 3), ('LN256 + split + bias', 7, 8, 0),
-      ('en GEMM2 256->256', 8, 9, 16 * RR * 8 * 3), ('H[r] gather, *, split, bias', 9, 10, 0), ('msg GEMM 256->256', 10, 11, 16 * RR * 8 * 3)]
+PH = [('emb GEMM 80->64 (+ smear, split)', 0, 2, 4 * RR * 3 * 3), ('gate init: gx[r] gather, bias', 2, 3, 0),
+      ('gate GEMM1 64->256', 3, 4, 16 * RR * 2 * 3), ('LN256 + split + bias', 4, 5, 0), ('gate GEMM2 256->256', 5, 6, 16 * RR * 8 * 3),
+      ('sigmoid + park + bias', 6, 7, 0), ('en GEMM1 64->256', 7, 8, 16 * RR * 2 * 3), ('LN256 + split + bias', 8, 9, 0),
+      ('en GEMM2 256->256', 9, 10, 16 * RR * 8 * 3), ('H[r] gather, *, split, bias', 10, 11, 0), ('msg GEMM 256->256', 11, 12, 16 * RR * 8 * 3)]
+SLOTS = 48
 
 
 def main():
@@ -40,13 +42,13 @@ def main():
     torch.cuda.synchronize()
     nunits = int(sum((int(n) * (int(n) - 1) + 15) // 16 for n in sizes))
     nitems = (nunits + RR - 1) // RR + 8
-    buf = torch.zeros(nitems * 32, dtype=torch.int64, device=dev)
+    buf = torch.zeros(nitems * SLOTS, dtype=torch.int64, device=dev)
     assert L.mdx_debug_set_trace2s(ctypes.c_void_p(buf.data_ptr())) == 0
     sm.step(3)
     torch.cuda.synchronize()
     L.mdx_debug_set_trace2s(ctypes.c_void_p(0))
-    tr = buf.cpu().numpy().reshape(nitems, 32).astype(np.int64)
-    ok = (tr[:, 11] > tr[:, 0]) & (tr[:, 11] - tr[:, 0] < 10_000_000)
+    tr = buf.cpu().numpy().reshape(nitems, SLOTS).astype(np.int64)
+    ok = (tr[:, 12] > tr[:, 0]) & (tr[:, 12] - tr[:, 0] < 10_000_000)
     for _, a, b, _ in PH:
         ok &= tr[:, b] >= tr[:, a]
     tr = tr[ok]
