@@ -666,6 +666,68 @@ int mdx_mol_kekulize(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr
                      const int32_t* charged_valence, uint32_t flexible, int32_t max_steps, int32_t* kek_order, int32_t* val,
                      int32_t* charge, int32_t* kek_h, int32_t* atom_flag, int32_t* mol_stats, void* stream);
 
+/* ---- Canonical labelling of decoded molecules: exact keys, symmetry classes, the canonical atom order -------------------
+ * The reference reports uniqueness and novelty from RDKit's canonical SMILES (utils/scoring_func.py:172-175).  mdx_mol_canon is THIS
+ * PROJECT'S OWN DEFINITION of a canonical form, without RDKit: it is NOT RDKit's canonical ranking (CanonicalRankAtoms) and what is
+ * written from it is not RDKit's canonical SMILES.  It is canonical among runs of this project.  Every output has one value whatever
+ * the order of the atoms or of the traversal, and a plain restatement (moldiff_amd/canon.py: canon_ref) must agree exactly.
+ *
+ * INPUT.  The compact layout of mdx_mol_rings (atom_ptr .. select: as there).  A molecule has n atoms and a list of bonds
+ *   (i, j, type); a bond with an index outside the molecule or with i = j is ignored, as everywhere.  Several bonds between one pair
+ *   of atoms are allowed: the bonds are a multiset and nothing below minds.  `type` is the low 8 bits of bond_type.  Every atom has a
+ *   label L(v) >= 0: atom_type[v], or atom_label[v] when the caller gives that array (device int32 in [0, 65536), the layout of
+ *   atom_type; it folds in charge or hydrogen count; the range is the caller's word and is checked by the Python wrappers on host
+ *   arrays).  mix is murmur3's fmix32, as in mdx_mol_fingerprint.
+ * COLOURS.  A colouring c gives every atom a number in [0, n): always "how many atoms have a strictly smaller key".  Equal keys share
+ *   a colour, and a cell of size s at colour k leaves k + 1 .. k + s - 1 unused.
+ *     initial:  the key is L(v).
+ *     a round:  h(v) = SUM over the valid bonds {v, u} of v of mix(mix(c(u) + 1) + type), a wrapping 32-bit sum;
+ *               key(v) = c(v) * 2^32 + h(v);  c'(v) = #{u : key(u) < key(v)};  repeat until c' = c.
+ *   A hash collision can only leave a cell unsplit and the search below is exact regardless; every step depends on nothing but the
+ *   graph.
+ * SEARCH TREE.  A node is a refined colouring.  If all colours are distinct it is a LEAF with rank(v) = c(v).  Otherwise its TARGET
+ *   CELL is the non-singleton cell of smallest colour k, and it has one child per atom v of that cell: from the node's colouring,
+ *   c(u) = k + 1 for every other atom u of the cell while v keeps k, then refinement.  The root is the refined initial colouring, at
+ *   depth 0.  There is NO PRUNING OF ANY KIND: the tree, its node count and its leaf count are properties of the graph alone, and so
+ *   is every status below.
+ * CERTIFICATE of a leaf: every valid bond as the word lo * 2^20 + hi * 2^8 + type, lo < hi the ranks of its atoms, the words sorted
+ *   ascending; certificates compare lexicographically.  The CANONICAL certificate is the smallest over all leaves.  The FULL
+ *   CERTIFICATE of the molecule is the int32 sequence n, the labels at ranks 0 .. n - 1, the number of valid bonds, the words: two
+ *   molecules are the same labelled graph iff their full certificates are equal.  cert_hash is FNV-1a-64 over those values taken as
+ *   uint32: h = 0xcbf29ce484222325, then h = (h xor w) * 0x100000001b3 mod 2^64 per value.  It is for grouping on the device;
+ *   equality of molecules is always decided on the full certificate.
+ * OUTPUTS (device, plain stores by the molecule's own workgroup: bit-reproducible, independent of the place in the batch):
+ *   mol_stats  [m][k], k < MDX_CANON_STATS = 5 (int32):
+ *     0 status         0 measured; 1 more than 256 atoms or 512 bonds (the caps of mdx_mol_rings; ignored bonds included); 2 search
+ *                      abandoned: the tree has more than max_nodes nodes (1 .. 2^20) or a node deeper than 64 -- one status, because
+ *                      whichever the walk meets first the answer is the same.
+ *     1 n_nodes  2 n_leaves   the size of the tree, the root counted
+ *     3 n_aut          the leaves that attain the canonical certificate = the order of the automorphism group of the labelled graph
+ *     4 canon_n_bonds  the valid bonds
+ *   cert_hash  (B) int64.
+ *   rank       per atom slot (N_cap): the rank vector of the optimal leaf whose vector (rank[0], rank[1], ..) is lexicographically
+ *              smallest among the optimal leaves (a minimum over a set: it looks at the input order, not at the traversal).
+ *   orbit      per atom slot: the smallest index of an atom that some automorphism maps v to = the smallest atom found at rank[v] in
+ *              any optimal leaf.
+ *   canon_atom_type, canon_atom_label (iff atom_label), canon_pos (iff atom_pos; 3 floats per slot): the atom of rank p in slot
+ *              atom_ptr[m] + p.  canon_bond_index (2 rows of Eh_stride: lo, hi) and canon_bond_type at bond_ptr[m] ..: the words of
+ *              the canonical certificate in order; the molecule's bond slots behind canon_n_bonds are 0.  Isomorphic inputs give
+ *              identical canonical arrays, the positions permuted alike.  The canonical arrays with canon_n_bonds are again a
+ *              compact molecule: mdx_mol_kekulize, mdx_mol_groups and mdx_mol_rings run on them directly.
+ *   With a non-zero status, under select, and for a molecule reaching past N_cap / Eh_stride (whose slots are not written): rank -1
+ *   and every other output 0, status as said (0 for the latter two).  Slots that belong to no molecule are not written.
+ * One workgroup of 256 threads per molecule, thread a = atom a, the whole state in about 30 KB of LDS (the stack of 64 colour
+ * snapshots is 16 KB of it).  There is no workspace.
+ * MDX_ERR_ARG, every output untouched: a null operand (select, atom_pos, atom_label and their two outputs excepted), atom_label
+ * without canon_atom_label or atom_pos without canon_pos or the reverse, a negative size, max_nodes outside 1 .. 2^20.
+ * B = 0 is accepted and writes nothing. */
+#define MDX_CANON_STATS 5
+int mdx_mol_canon(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                  const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                  const int32_t* select, const float* atom_pos, const int32_t* atom_label, int32_t max_nodes, int32_t* rank,
+                  int32_t* orbit, int32_t* canon_atom_type, int32_t* canon_atom_label, float* canon_pos, int32_t* canon_bond_index,
+                  int32_t* canon_bond_type, int32_t* mol_stats, int64_t* cert_hash, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -1,0 +1,525 @@
+"""Canonical labelling of decoded molecules: an exact molecule key (the full certificate), the order of the automorphism group, the
+symmetry class (orbit) of every atom, the molecule in canonical atom order, and a SMILES string written from that order.
+
+The device half is ``mdx_mol_canon`` (csrc/mdx_canon.hip), reached through ``canon_mols`` (a list of molecule dicts), ``launch`` (a
+``CompactMols``) and ``FeaturizeMol.canon_batch`` (the sampler's predictions).  ``canon_ref`` is the plain restatement for one molecule
+and needs no GPU; the GPU tests compare every output exactly.
+
+What it is: the reference reports uniqueness and novelty from RDKit's canonical SMILES (utils/scoring_func.py:172-175) and writes a
+SMILES per finished molecule (scripts/sample_drug3d.py:141-153).  RDKit is not available here, so this is THIS PROJECT'S OWN
+DEFINITION, stated exactly in include/moldiff_hip.h: NOT RDKit's canonical ranking, and the strings of ``smiles`` are NOT RDKit's
+canonical SMILES.  They are canonical among runs of this project, which is what uniqueness and novelty need.
+
+The definition in short.  Atom labels L(v) (the class index, or the caller's ``atom_label``); a colouring gives every atom "how many
+atoms have a strictly smaller key".  Initially the key is L(v); a refinement round takes key(v) = c(v) * 2^32 + h(v) with
+h(v) = sum over the valid bonds {v, u} of mix(mix(c(u) + 1) + type) (wrapping 32-bit; mix = murmur3's fmix32; type = the low 8 bits of
+the bond type), until the colouring stops changing.  The search tree: a node whose colours are all distinct is a leaf; otherwise one
+child per atom v of the non-singleton cell of smallest colour k (the others of the cell move to k + 1, then refinement).  No pruning.
+A leaf's certificate is the ascending list of lo * 2^20 + hi * 2^8 + type over the valid bonds (lo < hi the ranks of the ends); the
+smallest over all leaves is canonical, ``n_aut`` is the number of leaves that attain it, ``rank`` is the lexicographically smallest
+rank vector among those, and ``orbit[v]`` is the smallest atom found at rank[v] in any of them.
+
+    python -m moldiff_amd.canon stats samples_all.pt --out canon.npz [--ref] [--part finished]
+    python -m moldiff_amd.canon compare a.npz b.npz
+"""
+import argparse
+import json
+import sys
+
+import numpy as np
+
+from . import rings
+from .local3d import jsd_counts
+from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from .similarity import mix
+
+MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
+MAX_DEPTH = 64
+MAX_NODES_LIMIT, DEFAULT_MAX_NODES = 1 << 20, 1 << 16
+MAX_LABEL = 1 << 16
+STATUS_OK, STATUS_TOO_LARGE, STATUS_ABANDONED = 0, 1, 2
+# the columns of the device's per-molecule table, in its order (include/moldiff_hip.h: MDX_CANON_STATS)
+STAT_KEYS = ('status', 'n_nodes', 'n_leaves', 'n_aut', 'canon_n_bonds')
+MOL_KEYS = STAT_KEYS + ('cert_hash', 'n_atoms', 'n_bonds')
+ATOM_KEYS = ('rank', 'orbit', 'canon_atom_type')                  # + canon_atom_label, canon_pos when the inputs were given
+BOND_KEYS = ('canon_bond_type',)                                  # + canon_bond_index (2, bonds)
+NODE_BINS = 22                                                    # bin k: molecules whose n_nodes have bit length k
+FNV_OFFSET, FNV_PRIME = 0xcbf29ce484222325, 0x100000001b3
+SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+SMILES_VALENCES = {6: (4,), 7: (3, 5), 8: (2,), 9: (1,), 15: (3, 5), 16: (2, 4, 6), 17: (1,)}   # what a SMILES reader assumes
+_M = np.uint64(0xffffffff)
+
+
+def _check_nodes(max_nodes):
+    if not 1 <= int(max_nodes) <= MAX_NODES_LIMIT:
+        raise ValueError(f'max_nodes must lie in 1 .. 2^20, got {max_nodes}')
+    return int(max_nodes)
+
+
+def _check_label(label, n):
+    label = np.asarray(label, dtype=np.int64).reshape(-1)
+    if len(label) != n:
+        raise ValueError(f'atom_label holds {len(label)} values for {n} atoms')
+    if ((label < 0) | (label >= MAX_LABEL)).any():
+        raise ValueError('an atom label lies in 0 .. 65535')
+    return label
+
+
+# ---- one molecule on the host --------------------------------------------------------------------------------------------------------
+
+class _Abandoned(Exception):
+    pass
+
+
+def _ranks(keys):
+    """how many keys are strictly smaller, per key"""
+    return np.searchsorted(np.sort(keys), keys, side='left').astype(np.int64)
+
+
+def fnv1a64(values):
+    """FNV-1a-64 over int32 values taken as uint32, one step per value -> int (the int64 the device writes)"""
+    h = FNV_OFFSET
+    for w in values:
+        h = ((h ^ (int(w) & 0xffffffff)) * FNV_PRIME) & 0xffffffffffffffff
+    return h - (1 << 64) if h >= 1 << 63 else h
+
+
+def canon_ref(info, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers=DEFAULT_ATOMIC_NUMBERS):
+    """Plain restatement of ``mdx_mol_canon`` for one molecule dict (element = atomic numbers, bond_index (2, 2b) with every bond once
+    and then flipped, bond_type (2b), optionally atom_pos) -> dict: ``status`` (0 measured, 1 more than 256 atoms or 512 bonds, 2 search
+    abandoned: more than `max_nodes` nodes or a node deeper than 64), ``n_nodes``, ``n_leaves``, ``n_aut``, ``cert_hash``,
+    ``canon_n_bonds`` (the valid bonds), ``n_atoms``, ``n_bonds``; per atom ``rank``, ``orbit``, ``canon_atom_type`` (and
+    ``canon_atom_label`` with `atom_label`, ``canon_pos`` when the dict holds positions); per bond slot ``canon_bond_index`` (2, nb)
+    and ``canon_bond_type``, the valid bonds in certificate order and zeros behind them.  With a non-zero status rank is -1 and every
+    other output is 0.  A bond with an index outside the molecule or with i = j is ignored; several bonds between one pair of atoms
+    are a multiset.  atom_label: int in [0, 65536) per atom, else ValueError; an element outside `atomic_numbers` raises ValueError."""
+    max_nodes = _check_nodes(max_nodes)
+    cls, bi, bt = mol_graph(info, atomic_numbers)
+    n, nb = len(cls), bi.shape[1]
+    label = cls.astype(np.int64) if atom_label is None else _check_label(atom_label, n)
+    pos = np.asarray(info['atom_pos'], dtype=np.float32).reshape(n, 3) if 'atom_pos' in info else None
+    zi = lambda *k: np.zeros(k, dtype=np.int32)
+    out = dict({k: 0 for k in STAT_KEYS}, cert_hash=0, n_atoms=n, n_bonds=nb, rank=np.full(n, -1, dtype=np.int32), orbit=zi(n),
+               canon_atom_type=zi(n), canon_bond_index=zi(2, nb), canon_bond_type=zi(nb))
+    if atom_label is not None:
+        out['canon_atom_label'] = zi(n)
+    if pos is not None:
+        out['canon_pos'] = np.zeros((n, 3), dtype=np.float32)
+    if n > MAX_ATOMS or nb > MAX_BONDS:
+        return dict(out, status=STATUS_TOO_LARGE)
+    ok = (bi[0] >= 0) & (bi[0] < n) & (bi[1] >= 0) & (bi[1] < n) & (bi[0] != bi[1]) if nb else np.zeros(0, dtype=bool)
+    bx, by, btype = bi[0][ok], bi[1][ok], (bt[ok] & 0xff).astype(np.uint64)
+    src, dst, typ = np.concatenate([bx, by]), np.concatenate([by, bx]), np.concatenate([btype, btype])
+
+    def refine(c):
+        while True:
+            h = np.zeros(n, dtype=np.uint64)
+            np.add.at(h, src, mix(mix(c[dst].astype(np.uint64) + np.uint64(1)) + typ))
+            new = _ranks((c.astype(np.uint64) << np.uint64(32)) | (h & _M))
+            if np.array_equal(new, c):
+                return c
+            c = new
+
+    best = {'cert': None, 'n_aut': 0, 'rank': None, 'table': None}
+    count = {'nodes': 0, 'leaves': 0}
+
+    def visit(c, depth):
+        count['nodes'] += 1
+        if count['nodes'] > max_nodes or depth > MAX_DEPTH:
+            raise _Abandoned
+        cells = np.bincount(c, minlength=max(n, 1))
+        big = np.flatnonzero(cells > 1)
+        if len(big) == 0:
+            count['leaves'] += 1
+            lo, hi = np.minimum(c[bx], c[by]), np.maximum(c[bx], c[by])
+            cert = sorted((lo * (1 << 20) + hi * (1 << 8) + btype.astype(np.int64)).tolist())
+            if best['cert'] is None or cert < best['cert']:
+                best.update(cert=cert, n_aut=1, rank=c.copy(), table=np.argsort(c))
+            elif cert == best['cert']:
+                best['n_aut'] += 1
+                if c.tolist() < best['rank'].tolist():
+                    best['rank'] = c.copy()
+                best['table'] = np.minimum(best['table'], np.argsort(c))
+            return
+        k = int(big[0])
+        for v in np.flatnonzero(c == k):
+            child = np.where((c == k) & (np.arange(n) != v), k + 1, c)
+            visit(refine(child), depth + 1)
+
+    try:
+        visit(refine(_ranks(label)), 0)
+    except _Abandoned:
+        return dict(out, status=STATUS_ABANDONED)
+    rank, words = best['rank'], best['cert']
+    inv = np.argsort(rank)                                             # the atom of rank p
+    out.update(n_nodes=count['nodes'], n_leaves=count['leaves'], n_aut=best['n_aut'], canon_n_bonds=len(words),
+               rank=rank.astype(np.int32), orbit=best['table'][rank].astype(np.int32), canon_atom_type=cls[inv].astype(np.int32))
+    if atom_label is not None:
+        out['canon_atom_label'] = label[inv].astype(np.int32)
+    if pos is not None:
+        out['canon_pos'] = pos[inv]
+    w = np.asarray(words, dtype=np.int64)
+    out['canon_bond_index'][0, :len(w)], out['canon_bond_index'][1, :len(w)] = w >> 20, (w >> 8) & 0xfff
+    out['canon_bond_type'][:len(w)] = w & 0xff
+    out['cert_hash'] = fnv1a64([n] + label[inv].tolist() + [len(words)] + words)
+    return out
+
+
+def _keys(results):
+    """the per-atom and per-bond keys a results dict holds"""
+    atom = ATOM_KEYS + tuple(k for k in ('canon_atom_label', 'canon_pos') if k in results)
+    return atom, BOND_KEYS
+
+
+def stack_ref(mols, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers=DEFAULT_ATOMIC_NUMBERS):
+    """``canon_ref`` of every molecule of a list as the results dict ``canon_mols`` returns (numpy): one entry per molecule of every
+    key of MOL_KEYS (int32, cert_hash int64), the per-atom keys over the atoms and the per-bond keys over the bond slots of the list
+    in turn (canon_bond_index (2, bonds)), ``atom_ptr`` and ``bond_ptr``.  atom_label: one array per molecule, or None.  ``canon_pos``
+    is present when every molecule holds positions."""
+    positions = all('atom_pos' in m for m in mols)
+    refs = [canon_ref(m, None if atom_label is None else atom_label[k], max_nodes, atomic_numbers) for k, m in enumerate(mols)]
+    out = {k: np.asarray([r[k] for r in refs], dtype=np.int64 if k == 'cert_hash' else np.int32).reshape(len(refs)) for k in MOL_KEYS}
+    atom = ATOM_KEYS + (('canon_atom_label',) if atom_label is not None else ())
+    for k in atom + BOND_KEYS:
+        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
+    if positions:
+        out['canon_pos'] = np.concatenate([r['canon_pos'] for r in refs] + [np.zeros((0, 3), dtype=np.float32)]).astype(np.float32)
+    out['canon_bond_index'] = np.concatenate([r['canon_bond_index'] for r in refs] + [np.zeros((2, 0), dtype=np.int32)], axis=1).astype(np.int32)
+    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
+    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
+    return out
+
+
+# ---- the device path ----------------------------------------------------------------------------------------------------------------
+
+def launch(cm, max_nodes=DEFAULT_MAX_NODES, select=None, atom_label=None, positions=True):
+    """``mdx_mol_canon`` on the device arrays `cm` (a ``CompactMols``) -> dict of device tensors: the keys of STAT_KEYS (B) each (int32,
+    columns of one (B, 5) table), ``cert_hash`` (B, int64), ``rank`` / ``orbit`` / ``canon_atom_type`` (N_cap), ``canon_bond_index``
+    (2, Eh_stride) and ``canon_bond_type`` (Eh_stride) in the layout of the inputs, zero where no molecule has a slot;
+    ``canon_atom_label`` with `atom_label` (an int32 device tensor in the layout of atom_type, values in [0, 65536): the caller's
+    word, not checked on the device) and ``canon_pos`` (N_cap, 3) when `cm` holds positions and `positions` is set.  No sync."""
+    import torch
+    from . import _lib
+    max_nodes = _check_nodes(max_nodes)
+    B, dev = cm.B, cm.device
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
+    stats, N, E = z(B, len(STAT_KEYS)), max(cm.N_cap, 1), max(cm.Eh_stride, 1)
+    out = {'cert_hash': torch.zeros(B, dtype=torch.int64, device=dev), 'rank': z(N), 'orbit': z(N), 'canon_atom_type': z(N),
+           'canon_bond_index': z(2, E), 'canon_bond_type': z(E)}
+    pos = cm.atom_pos if positions else None
+    if atom_label is not None:
+        if atom_label.dtype != torch.int32 or atom_label.numel() < cm.N_cap:
+            raise ValueError('atom_label is an int32 tensor in the layout of atom_type')
+        atom_label = atom_label.contiguous()
+        out['canon_atom_label'] = z(N)
+    if pos is not None:
+        out['canon_pos'] = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+    if B > 0:
+        ops, at = cm.operands()
+        opt = lambda t: None if t is None else at(t)
+        _lib.check(_lib.lib().mdx_mol_canon(
+            *ops, _lib.ptr(select), opt(pos), opt(atom_label), max_nodes, at(out['rank']), at(out['orbit']), at(out['canon_atom_type']),
+            opt(out.get('canon_atom_label')), opt(out.get('canon_pos')), at(out['canon_bond_index']), at(out['canon_bond_type']),
+            at(stats), at(out['cert_hash']), _lib.stream()))
+    out.update({k: stats[:, c] for c, k in enumerate(STAT_KEYS)})
+    return out
+
+
+def canonical_compact(cm, results, select=None):
+    """The canonical arrays of ``launch``'s results as a ``CompactMols`` in the layout of `cm` (same atom_ptr / bond_ptr, the bond
+    counts ``canon_n_bonds``), and the `select` that leaves out every molecule without a canonical form (non-zero status) besides
+    those `select` already leaves out -> (CompactMols, select): what ``kekule.launch``, ``groups.launch`` and ``rings.launch`` take."""
+    import torch
+    keep = (results['status'] == 0).to(torch.int32)
+    if select is not None:
+        keep = keep * (select != 0).to(torch.int32)
+    canon = cm._replace(n_bonds=results['canon_n_bonds'].contiguous(), atom_type=results['canon_atom_type'], N_cap=cm.N_cap,
+                        bond_type=results['canon_bond_type'], bond_index=results['canon_bond_index'],
+                        Eh_stride=int(results['canon_bond_index'].shape[1]), atom_pos=results.get('canon_pos'))
+    return canon, keep.contiguous()
+
+
+def canon_mols(mols, device, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers=DEFAULT_ATOMIC_NUMBERS):
+    """Canonical labelling of a list of molecule dicts (finished molecules, or entries of ``samples_all.pt``) on the device: the list
+    is packed densely, copied and handed to ``mdx_mol_canon``.  -> the results dict of ``stack_ref`` with device tensors.  atom_label:
+    one array per molecule (checked here: int in [0, 65536)), or None."""
+    import torch
+    device = torch.device(device)
+    _check_nodes(max_nodes)
+    positions = all('atom_pos' in m for m in mols) and len(mols) > 0
+    p = pack_mols(mols, atomic_numbers, positions=positions)
+    lab = None
+    if atom_label is not None:
+        if len(atom_label) != len(mols):
+            raise ValueError('one label array per molecule')
+        lab = np.concatenate([_check_label(a, int(n)) for a, n in zip(atom_label, p['n_atoms'])] + [np.zeros(0, dtype=np.int64)])
+        lab = torch.from_numpy(lab.astype(np.int32)).to(device)
+    cm = CompactMols.from_packed(to_device(p, device))
+    out = launch(cm, max_nodes, atom_label=lab)
+    total = int(p['n_bonds'].sum())
+    for k in _keys(out)[0]:
+        out[k] = out[k][:cm.N_cap]
+    if len(mols) == 0:
+        out['canon_pos'] = torch.zeros(0, 3, dtype=torch.float32, device=device)
+    out['canon_bond_type'], out['canon_bond_index'] = out['canon_bond_type'][:total], out['canon_bond_index'][:, :total]
+    out.update(n_atoms=cm.n_atoms, n_bonds=cm.n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
+    return out
+
+
+def concat(parts):
+    """the results of consecutive batches (host or device arrays, not mixed) as one results dict"""
+    parts = [to_host(p) for p in parts]
+    atom, bond = _keys(parts[0])
+    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + atom + bond}
+    out['canon_bond_index'] = np.concatenate([p['canon_bond_index'] for p in parts], axis=1)
+    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
+    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
+    return out
+
+
+def empty():
+    return stack_ref([])
+
+
+# ---- the numbers -------------------------------------------------------------------------------------------------------------------
+
+def mol_result(results, m):
+    """molecule `m` of a results dict with host arrays as the dict ``canon_ref`` returns"""
+    a0, na, b0, nb = (int(results[k][m]) for k in ('atom_ptr', 'n_atoms', 'bond_ptr', 'n_bonds'))
+    atom, bond = _keys(results)
+    out = {k: int(results[k][m]) for k in MOL_KEYS}
+    out.update({k: results[k][a0:a0 + na] for k in atom})
+    out.update({k: results[k][b0:b0 + nb] for k in bond})
+    out['canon_bond_index'] = results['canon_bond_index'][:, b0:b0 + nb]
+    return out
+
+
+def certificate(results, m):
+    """The full certificate of molecule `m` of a results dict with host arrays, as bytes: the int32 sequence n, the labels at ranks
+    0 .. n - 1, the number of valid bonds, the words.  Two measured molecules are the same labelled graph iff these are equal.
+    None for a molecule that was not measured (non-zero status)."""
+    r = mol_result(results, m)
+    if r['status'] != STATUS_OK:
+        return None
+    k = r['canon_n_bonds']
+    labels = r['canon_atom_label'] if 'canon_atom_label' in r else r['canon_atom_type']
+    bi = r['canon_bond_index'][:, :k].astype(np.int64)
+    words = bi[0] * (1 << 20) + bi[1] * (1 << 8) + r['canon_bond_type'][:k]
+    return np.concatenate([[r['n_atoms']], labels, [k], words]).astype(np.int32).tobytes()
+
+
+def canonical_mol(info, result):
+    """The molecule dict `info` in canonical atom order from its result (``canon_ref``'s dict or a ``mol_result`` slice): ``element``,
+    ``bond_index`` (2, 2b) with the valid bonds in certificate order once and then flipped, ``bond_type`` (2b), ``atom_pos`` when
+    `info` holds positions.  Isomorphic inputs give identical dicts apart from the positions.  None without a canonical form."""
+    if int(result['status']) != STATUS_OK:
+        return None
+    inv = np.argsort(np.asarray(result['rank']))
+    k = int(result['canon_n_bonds'])
+    bi, bt = np.asarray(result['canon_bond_index'])[:, :k].astype(np.int64), np.asarray(result['canon_bond_type'])[:k].astype(np.int64)
+    out = {'element': np.asarray(info['element'], dtype=np.int64).reshape(-1)[inv],
+           'bond_index': np.concatenate([bi, bi[::-1]], axis=1), 'bond_type': np.concatenate([bt, bt])}
+    if 'atom_pos' in info:
+        out['atom_pos'] = np.asarray(info['atom_pos'])[inv]
+    return out
+
+
+def _certificates(results):
+    r = to_host(results)
+    return [certificate(r, m) for m in range(len(r['status']))]
+
+
+def summary(results):
+    """The numbers of a results dict (host or device arrays) -> dict: ``n_molecules``, ``n_measured`` (status 0), ``n_too_large``,
+    ``n_abandoned``; over the measured molecules ``n_distinct`` (distinct full certificates: EXACT, unlike the fingerprint key of
+    ``similarity.summary``), ``uniqueness`` = n_distinct / n_measured, ``mean_n_aut``, ``max_n_aut`` and ``nodes_hist`` (bin k:
+    n_nodes of bit length k, i.e. 1, 2-3, 4-7, ...).  NaN where nothing was counted.  The labelling is this project's own."""
+    r = to_host(results)
+    ok = r['status'] == STATUS_OK
+    k = int(ok.sum())
+    nan = float('nan')
+    certs = {c for c in _certificates(r) if c is not None}
+    bits = np.asarray([min(int(s).bit_length(), NODE_BINS - 1) for s in r['n_nodes'][ok]], dtype=np.int64)
+    return {'n_molecules': len(ok), 'n_measured': k, 'n_too_large': int((r['status'] == STATUS_TOO_LARGE).sum()),
+            'n_abandoned': int((r['status'] == STATUS_ABANDONED).sum()), 'n_distinct': len(certs),
+            'uniqueness': len(certs) / k if k else nan, 'mean_n_aut': float(r['n_aut'][ok].astype(np.int64).sum()) / k if k else nan,
+            'max_n_aut': int(r['n_aut'][ok].max()) if k else 0, 'nodes_hist': np.bincount(bits, minlength=NODE_BINS).tolist()}
+
+
+def novelty(results, reference_results):
+    """the fraction of the measured molecules of `results` whose full certificate occurs nowhere among the measured molecules of
+    `reference_results` (NaN when nothing was measured).  Both sides must have been labelled alike (atom_label or not)."""
+    known = {c for c in _certificates(reference_results) if c is not None}
+    mine = [c for c in _certificates(results) if c is not None]
+    return sum(c not in known for c in mine) / len(mine) if mine else float('nan')
+
+
+def compare(a, b):
+    """two results dicts -> dict: Jensen-Shannon divergence (``local3d.jsd_counts``) of ``nodes_hist``, both sides' ``uniqueness``
+    and ``mean_n_aut``, and the novelty of each side against the other by full certificate"""
+    sa, sb = summary(a), summary(b)
+    return {'nodes': jsd_counts(sa['nodes_hist'], sb['nodes_hist']), 'uniqueness': [sa['uniqueness'], sb['uniqueness']],
+            'mean_n_aut': [sa['mean_n_aut'], sb['mean_n_aut']], 'novelty': [novelty(a, b), novelty(b, a)]}
+
+
+# ---- SMILES -------------------------------------------------------------------------------------------------------------------------
+
+def assumed_hydrogens(z, bond_sum):
+    """what a SMILES reader assumes on an unbracketed atom: the smallest of the element's SMILES valences that is at least the
+    bond-order sum, minus that sum; 0 when the sum is above all of them"""
+    if int(z) not in SMILES_VALENCES:
+        raise ValueError(f'no SMILES valences for element {int(z)}')
+    return next((v - bond_sum for v in SMILES_VALENCES[int(z)] if v >= bond_sum), 0)
+
+
+def smiles(canon_mol, kekule_result):
+    """A SMILES string of the CANONICAL molecule (``canonical_mol``) from the Kekulé result of THAT molecule (``kekule.kekulize_ref``
+    of it, or a ``kekule.mol_result`` slice of ``kekule.launch`` on the canonical arrays): that is what makes the Kekulé structure,
+    and so the string, independent of the sampler's atom order.  THIS PROJECT'S OWN STRING: its grammar is unchecked against RDKit
+    offline, it is not RDKit's canonical SMILES and it is canonical only among this project's runs.
+
+    Kekulé form only: upper-case atoms, bond orders 1 / 2 / 3 from ``kek_order`` ('', '=', '#').  Every fragment starts at its atom
+    of lowest rank, fragments in rank order joined by '.'; depth-first, neighbours in ascending rank, all but the last in
+    parentheses.  Ring-closure digits are allotted in order of opening (at one atom: by the rank of the closing atom) and are free
+    again from the atom after the one that closes them; '%nn' from 10 on; at an atom the closing digits come first; the bond symbol
+    of a ring closure goes at its opening.  An atom is bracketed iff its charge is non-zero or its ``kek_h`` differs from
+    ``assumed_hydrogens``; a bracket atom writes H, H2, ... and +.  -> None when `canon_mol` is None, the molecule is not
+    kekulizable or a bond has no order (a type outside the featuriser's)."""
+    from . import kekule
+    if canon_mol is None:
+        return None
+    if not bool(kekule.kekulizable({k: np.asarray(kekule_result[k]) for k in ('status', 'n_failed', 'n_over_budget')})):
+        return None
+    ele = np.asarray(canon_mol['element'], dtype=np.int64).reshape(-1)
+    n = len(ele)
+    bi = np.asarray(canon_mol['bond_index'], dtype=np.int64).reshape(2, -1)
+    nb = bi.shape[1] // 2
+    order = np.asarray(kekule_result['kek_order'], dtype=np.int64)[:nb]
+    if len(order) != nb or (order < 1).any() or (order > 3).any():
+        return None
+    charge, kek_h = np.asarray(kekule_result['charge'], dtype=np.int64), np.asarray(kekule_result['kek_h'], dtype=np.int64)
+    nbr = [[] for _ in range(n)]
+    for e in range(nb):
+        x, y = int(bi[0, e]), int(bi[1, e])
+        nbr[x].append((y, int(order[e]), e)), nbr[y].append((x, int(order[e]), e))
+    for a in range(n):
+        nbr[a].sort()
+    # pass 1: the spanning forest and the ring closures (a closure opens at the atom visited first, an ancestor of the other)
+    seen, used = [False] * n, [False] * nb
+    children, opens, closes = [[] for _ in range(n)], [[] for _ in range(n)], [[] for _ in range(n)]
+    roots = []
+    for root in range(n):
+        if seen[root]:
+            continue
+        roots.append(root)
+        seen[root] = True
+        stack = [(root, 0)]
+        while stack:
+            a, k = stack.pop()
+            if k == len(nbr[a]):
+                continue
+            stack.append((a, k + 1))
+            b, o, e = nbr[a][k]
+            if used[e]:
+                continue
+            used[e] = True
+            if seen[b]:
+                opens[b].append((a, o)), closes[a].append(b)
+            else:
+                seen[b] = True
+                children[a].append((b, o))
+                stack.append((b, 0))
+    sym = {1: '', 2: '=', 3: '#'}
+    digit = lambda d: str(d) if d < 10 else '%%%02d' % d
+    free, taken = [], {}                                               # freed digits (kept sorted), (opener, closer) -> digit
+    nxt = [1]
+
+    def atom_text(a):
+        z, bond_sum = int(ele[a]), sum(o for _, o, _ in nbr[a])
+        if z not in SYMBOL:
+            raise ValueError(f'no symbol for element {z}')
+        h, q = int(kek_h[a]), int(charge[a])
+        if q == 0 and h == assumed_hydrogens(z, bond_sum):
+            return SYMBOL[z]
+        return '[' + SYMBOL[z] + ('H' + (str(h) if h > 1 else '') if h else '') + \
+            (('+' if q > 0 else '-') + (str(abs(q)) if abs(q) > 1 else '') if q else '') + ']'
+
+    def write(a):
+        text, freed = atom_text(a), []
+        for b in sorted(closes[a]):
+            d = taken.pop((b, a))
+            text += digit(d)
+            freed.append(d)
+        for b, o in sorted(opens[a]):
+            if free:
+                d = free.pop(0)
+            else:
+                d, nxt[0] = nxt[0], nxt[0] + 1
+            taken[(a, b)] = d
+            text += sym[o] + digit(d)
+        free.extend(freed)
+        free.sort()
+        for k, (b, o) in enumerate(children[a]):
+            sub = sym[o] + write(b)
+            text += sub if k == len(children[a]) - 1 else '(' + sub + ')'
+        return text
+    limit = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(limit, 4 * MAX_ATOMS + 100))
+    try:
+        return '.'.join(write(r) for r in roots)
+    finally:
+        sys.setrecursionlimit(limit)
+
+
+def smiles_mols(mols, results, device=None, tables=None):
+    """``smiles`` of every molecule of a list from its results dict (host arrays, one entry per molecule): the canonical molecules
+    are kekulized together, on `device` (``kekule.kekulize_mols``) or with ``kekule.kekulize_ref`` when it is None -> a list of
+    strings, None where a molecule has none"""
+    from . import kekule
+    canon = [canonical_mol(info, mol_result(results, m)) for m, info in enumerate(mols)]
+    have = [m for m, c in enumerate(canon) if c is not None]
+    out = [None] * len(mols)
+    if not have:
+        return out
+    if device is None:
+        kek = kekule.stack_ref([canon[m] for m in have], tables)
+    else:
+        kek = to_host(kekule.kekulize_mols([canon[m] for m in have], device, tables))
+    for k, m in enumerate(have):
+        out[m] = smiles(canon[m], kekule.mol_result(kek, k))
+    return out
+
+
+# ---- command line --------------------------------------------------------------------------------------------------------------------
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m moldiff_amd.canon', description=__doc__.split('\n\n')[0])
+    sub = ap.add_subparsers(dest='cmd', required=True)
+    s = sub.add_parser('stats', help='canonical labelling of the molecules stored in a samples_all.pt')
+    s.add_argument('samples')
+    s.add_argument('--out', required=True)
+    s.add_argument('--part', default='finished')
+    s.add_argument('--max_nodes', type=int, default=DEFAULT_MAX_NODES)
+    s.add_argument('--device', default='cuda:0')
+    s.add_argument('--ref', action='store_true', help='the Python path instead of the device')
+    c = sub.add_parser('compare', help='node-count divergence, uniqueness and mutual novelty of two files')
+    c.add_argument('a')
+    c.add_argument('b')
+    args = ap.parse_args(argv)
+    if args.cmd == 'stats':
+        mols = load_mols(args.samples, args.part)
+        if args.ref:
+            res = stack_ref(mols, max_nodes=args.max_nodes)
+        else:
+            import torch
+            torch.cuda.set_device(torch.device(args.device))
+            res = canon_mols(mols, args.device, max_nodes=args.max_nodes)
+        save_npz(res, args.out)
+        print(json.dumps(summary(res), indent=1))
+    else:
+        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -292,6 +292,28 @@ class FeaturizeMol(object):
         out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
         return out
 
+    def canon_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
+                    atom_label=None):
+        """``decode_batch``'s device part + the canonical labelling of every decoded molecule (``mdx_mol_canon``; see
+        ``moldiff_amd/canon.py``).  Nothing is copied to the host and nothing synchronises.  select: (n_graphs) device tensor; a
+        molecule with 0 keeps its place with status 0, n_atoms 0, rank -1 and every other output 0.  atom_label: int32 device tensor
+        in the decode's atom layout, values in [0, 65536), instead of the atom class.  -> (results, canonical, keep): the results dict
+        of device tensors (the per-molecule numbers of ``canon.STAT_KEYS``, cert_hash, n_atoms, n_bonds (B); rank, orbit and the
+        canonical arrays in the decode's own layout, molecule m at atom_ptr[m] / bond_ptr[m]); a ``CompactMols`` over the canonical
+        arrays (same pointers, the bond counts canon_n_bonds) and the `select` that leaves out the molecules without a canonical
+        form, for ``kekule.launch``, ``groups.launch`` and ``rings.launch``.  These are the molecules AS DECODED; the labelling is
+        this project's own, not RDKit's canonical ranking.  Like ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import canon
+        max_nodes = canon.DEFAULT_MAX_NODES if max_nodes is None else max_nodes
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        out = canon.launch(cm, max_nodes, select=select, atom_label=atom_label)
+        n_bonds = cm.n_bonds[:cm.B]
+        if select is not None:
+            n_bonds = torch.where(select != 0, n_bonds, torch.zeros_like(n_bonds))
+        canonical, keep = canon.canonical_compact(cm, out, select)
+        out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
+        return out, canonical, keep
+
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):
     """Split packed numpy outputs {'pred': [...], 'traj': [...]} per molecule (host, numpy -- like the reference)."""

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -53,6 +53,15 @@ not a charge-minimal one).  ``--kekulize`` writes ``kekule.npz`` (per-molecule, 
 ``kekule.json`` (their summary) and ``samples_kekule.sdf`` (the finished molecules that are kekulizable, bond orders 1 / 2 / 3 and
 ``M  CHG`` lines) beside ``samples_all.pt``; ``--accept kekule`` is 'valence' and kekulizable.  With either, pool entries carry
 ``kekulizable`` and ``quality.json`` (written with ``--accept`` / ``--largest_fragment``) gains its count.  Without both nothing changes.
+``--canonical`` (config key ``sample.canonical``; the flag wins), an addition beyond the reference: rank 0 labels the FINISHED molecules
+canonically on the device batch by batch (``moldiff_amd/canon.py``: this project's own canonical form, not RDKit's canonical ranking) and
+writes ``canon.npz`` (per-molecule arrays, ``rank``, ``orbit`` and the canonical arrays) and ``canon.json`` (their summary, with the
+EXACT uniqueness by full certificate) beside ``samples_all.pt``.  Together with ``--kekulize`` it also writes ``samples.smi``, one line
+``SMILES<TAB>mol_id`` per finished molecule that has a string, and pool entries gain ``smiles`` (this project's own string from the
+canonical order and the Kekulé structure of the canonical form; unchecked against RDKit).  ``kekule.npz`` and ``samples_kekule.sdf``
+stay what they are, from the molecule as decoded.  ``--canonical_max_nodes`` (``sample.canonical_max_nodes``) is the search budget: a
+molecule whose unpruned tree is larger is reported as abandoned (status 2), which is what the nearly complete bond graphs of untrained
+weights get.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -303,8 +312,23 @@ def build_parser():
     return ap
 
 
+def canonical_option(flag, sample_cfg):
+    """whether to write the canonical files: the command line's flag (None = not given) wins over the config's ``sample.canonical``"""
+    return bool(flag if flag is not None else sample_cfg.get('canonical'))
+
+
+def add_canonical_argument(ap):
+    """``--canonical`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--canonical', action='store_true', default=None,
+                    help='label the finished molecules canonically on the device and write canon.npz and canon.json, with --kekulize '
+                         'also samples.smi (overrides sample.canonical)')
+    ap.add_argument('--canonical_max_nodes', type=int, default=None,
+                    help='the node budget of the canonical search, 1 .. 2^20 (overrides sample.canonical_max_nodes; default 65536)')
+    return ap
+
+
 def main(argv=None):
-    args = add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))).parse_args(argv)
+    args = add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -387,6 +411,12 @@ def main(argv=None):
     if kek_active:
         from . import kekule
         kek_tables = kekule.KekuleTables(featurizer.atomic_numbers.tolist(), featurizer.num_bond_types)
+    canon_write, canon_parts = canonical_option(args.canonical, config.sample), []
+    if canon_write:
+        from . import canon
+        canon_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or canon.DEFAULT_MAX_NODES
+        if not 1 <= canon_nodes <= canon.MAX_NODES_LIMIT:
+            raise ValueError(f'canonical_max_nodes must lie in 1 .. 2^20, got {canon_nodes}')
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -487,6 +517,11 @@ def main(argv=None):
                 groups_parts.append(to_host(groups.groups_mols(gen, device, groups_set)))
             if kek_write and gen:
                 kek_parts.append(to_host(kekule.kekulize_mols(gen, device, kek_tables)))
+            if canon_write and gen:
+                canon_parts.append(to_host(canon.canon_mols(gen, device, max_nodes=canon_nodes, atomic_numbers=featurizer.atomic_numbers.tolist())))
+                if kek_write:
+                    for info, text in zip(gen, canon.smiles_mols(gen, canon_parts[-1], device, kek_tables)):
+                        info['smiles'] = text
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -519,6 +554,14 @@ def main(argv=None):
             with open(os.path.join(log_dir, 'kekule.json'), 'w') as f:
                 json.dump(kekule.summary(res), f, indent=1)
             kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)
+        if canon_write:
+            res = canon.concat(canon_parts) if canon_parts else canon.empty()
+            save_npz(res, os.path.join(log_dir, 'canon.npz'))
+            with open(os.path.join(log_dir, 'canon.json'), 'w') as f:
+                json.dump(canon.summary(res), f, indent=1)
+            if kek_write:
+                with open(os.path.join(log_dir, 'samples.smi'), 'w') as f:
+                    f.writelines('%s\t%d\n' % (m['smiles'], m['mol_id']) for m in pool['finished'] if m.get('smiles'))
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed']),
