@@ -728,6 +728,74 @@ int mdx_mol_canon(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, c
                   int32_t* orbit, int32_t* canon_atom_type, int32_t* canon_atom_label, float* canon_pos, int32_t* canon_bond_index,
                   int32_t* canon_bond_type, int32_t* mol_stats, int64_t* cert_hash, void* stream);
 
+/* ---- Frameworks and ring systems of decoded molecules: the skeleton without its decoration, as compact molecules ------
+ * The reference's `ring_type` metric (utils/evaluation.py: RingAnalyzer.get_count_ring, get_freq_rings, get_ring_topo, fr_bicyclic)
+ * reports which rings occur and how often, and scaffold uniqueness / diversity / novelty are the usual second half of a generative
+ * model's report.  mdx_mol_rings offers no ring SMILES because a ring basis is a choice; a RING SYSTEM and the FRAMEWORK are unique
+ * functions of the graph.  mdx_mol_framework cuts every molecule into framework, ring systems, linkers and side chains and hands the
+ * pieces back as compact molecules, so that mdx_mol_canon gives each an exact key with one more launch.  It is THIS PROJECT'S OWN
+ * DEFINITION in the spirit of Bemis and Murcko; it is NOT rdkit.Chem.Scaffolds.MurckoScaffold and is UNVERIFIED AGAINST RDKit.  Every
+ * output has one value whatever the order of the traversal, and a plain restatement (moldiff_amd/framework.py: framework_ref) must
+ * agree exactly.
+ *
+ * INPUT.  The compact layout of mdx_mol_rings (atom_ptr .. select: as there); atom_pos (3 floats per atom slot) is optional.  A bond
+ *   with an index outside the molecule or with i = j is ignored.  Two bonds between one pair of atoms are a PRECONDITION VIOLATION as
+ *   for mdx_mol_rings: results unspecified, the kernel stays in bounds and ends.  bond_ring_min (Eh_stride) and ring_status (B)
+ *   exactly as mdx_mol_rings wrote them for the same arrays (the convention of mdx_mol_groups).  mode: bit 0 MDX_FW_EXO, bit 1
+ *   MDX_FW_GENERIC.  sys_bins in 1 .. 16.
+ * DEFINITIONS.  G is the graph of the valid bonds.
+ *   A RING BOND is a valid bond with bond_ring_min != 0 (no bridge), a RING ATOM an atom with at least one ring bond.
+ *   The CORE F0 is what remains after deleting, until nothing changes, every atom that has at most one remaining bond: the 2-core of
+ *     G, the ring atoms and the atoms on paths between them.  An acyclic molecule has an empty core.  A core atom without a ring
+ *     bond is a LINKER ATOM.
+ *   With EXO an atom outside F0 is an EXO ATOM, and joins the framework with its bond, when it has exactly one valid bond, that bond
+ *     has type 2 and leads to an atom of F0 (carbonyl O on a ring or a linker; not acetone's O: no core).
+ *   The FRAMEWORK F is F0 plus the exo atoms, with every valid bond between two atoms of F0 and the exo bonds.
+ *   A RING SYSTEM is a connected component of (ring atoms, ring bonds).  Spiro and fused rings share atoms and form one system;
+ *     biphenyl has two.  Systems are numbered 0, 1, .. by their smallest atom index; one with a atoms and b bonds has b - a + 1 rings.
+ *   A FUSION ATOM is a ring atom with at least three ring bonds.
+ * OUTPUTS (device int32, fw_pos / sys_pos float and present iff atom_pos; plain stores by the molecule's own workgroup, every slot
+ *   written once: bit-reproducible, independent of the place in the batch):
+ *   atom_role    per atom slot (N_cap): 0 side chain, 1 linker, 2 ring, 3 exo.
+ *   atom_system  per atom slot: the ordinal of the atom's ring system, -1 for an atom in none.
+ *   bond_role    per bond slot (Eh_stride): 0 not in F (ignored bonds included), 1 framework bond that is no ring bond, 2 ring bond,
+ *                3 exo bond.
+ *   mol_stats    [m][k], k < MDX_FW_STATS = 10:
+ *     0 status   0 measured; 1 too large: n_atoms > 256 or n_bonds > 512 (the caps of mdx_mol_rings); 2 ring_status[m] != 0
+ *     1 framework atoms      2 framework bonds     3 ring systems     4 linker atoms     5 side-chain atoms     6 exo atoms
+ *     7 fusion atoms         8 atoms of the largest system            9 rings of the system with most rings
+ *   sys_hist     [m][k], k < sys_bins: the systems with 1 + k rings, the last bin also every larger one.  SUM = mol_stats[m][3].
+ *   THE FRAMEWORK AS A COMPACT MOLECULE in the molecule's own slots: fw_atom_type, fw_atom_map (the original local index) and fw_pos
+ *     from atom_ptr[m]; fw_bond_index (2 rows of Eh_stride: renumbered, direction kept) and fw_bond_type from bond_ptr[m].  Atoms and
+ *     bonds keep their relative order; the counts are mol_stats[m][1] and [2]; the molecule's atom and bond slots behind the counts
+ *     are 0.
+ *   THE RING SYSTEMS AS COMPACT MOLECULES, disjoint and so again in the molecule's own slots: system k of molecule m has its record
+ *     at slot atom_ptr[m] + k of sys_atom_ptr, sys_bond_ptr, sys_n_atoms, sys_n_bonds (N_cap each).  Its atoms lie contiguously from
+ *     sys_atom_ptr = atom_ptr[m] + the sizes of the earlier systems, its bonds likewise from bond_ptr[m]; within a system both keep
+ *     their relative order.  Per atom sys_atom_type, sys_atom_map (the original local index), sys_pos; per bond sys_bond_index (2
+ *     rows, local to the system, direction kept) and sys_bond_type.  Record slots of the molecule at or behind its system count hold
+ *     0 in all four arrays; so do the atom and bond slots behind the ring atoms / ring bonds.
+ *   GENERIC writes class 0 for every atom and type 1 for every bond in the fw_* and sys_* type arrays; roles, stats and maps are
+ *     unchanged.
+ *   With a non-zero status, under select, and for a molecule reaching past N_cap / Eh_stride (whose slots are not written): every
+ *   count is 0, atom_system -1, every other output 0, status as said (0 for the latter two).  Slots that belong to no molecule are
+ *   not written.
+ * One workgroup of 256 threads per molecule, thread a = atom a, the whole state in about 19 KB of LDS.  There is no workspace.
+ * MDX_ERR_ARG, every output untouched: a null operand (select, atom_pos and its two outputs excepted), atom_pos without fw_pos or
+ * sys_pos or the reverse, a negative size, mode bits above 1, sys_bins outside 1 .. 16.
+ * B = 0 is accepted and writes nothing. */
+#define MDX_FW_STATS 10
+#define MDX_FW_EXO 1
+#define MDX_FW_GENERIC 2
+int mdx_mol_framework(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                      const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                      const int32_t* select, const float* atom_pos, const int32_t* bond_ring_min, const int32_t* ring_status,
+                      int32_t mode, int32_t sys_bins, int32_t* atom_role, int32_t* atom_system, int32_t* bond_role, int32_t* mol_stats,
+                      int32_t* sys_hist, int32_t* fw_atom_type, int32_t* fw_atom_map, float* fw_pos, int32_t* fw_bond_index,
+                      int32_t* fw_bond_type, int32_t* sys_atom_ptr, int32_t* sys_bond_ptr, int32_t* sys_n_atoms, int32_t* sys_n_bonds,
+                      int32_t* sys_atom_type, int32_t* sys_atom_map, float* sys_pos, int32_t* sys_bond_index, int32_t* sys_bond_type,
+                      void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

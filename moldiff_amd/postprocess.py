@@ -314,6 +314,27 @@ class FeaturizeMol(object):
         out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
         return out, canonical, keep
 
+    def framework_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, mode=0, sys_bins=None, select=None):
+        """``decode_batch``'s device part + the framework and the ring systems of every decoded molecule (``mdx_mol_rings``, then
+        ``mdx_mol_framework``; see ``moldiff_amd/framework.py``).  mode: bit 0 EXO, bit 1 GENERIC.  Nothing is copied to the host and
+        nothing synchronises.  select: (n_graphs) device tensor; a molecule with 0 keeps its place with status 0, n_atoms 0, every
+        count 0 and atom_system -1.  -> (results, cm): the results dict of device tensors (the per-molecule numbers of
+        ``framework.STAT_KEYS``, sys_hist, n_atoms, n_bonds (B); roles, the framework and the ring systems in the decode's own layout,
+        molecule m at atom_ptr[m] / bond_ptr[m]) and the ``CompactMols`` of the decoded molecules, which is what
+        ``framework.framework_compact``, ``framework.systems_compact`` and ``framework.keys`` take with the results.  These are the
+        molecules AS DECODED; the definitions are this project's own, not RDKit's MurckoScaffold.  Like ``decode_batch``, it needs a
+        batch with at least one half-edge."""
+        from . import framework, rings
+        sys_bins = framework.DEFAULT_BINS if sys_bins is None else sys_bins
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        ring_data = rings.launch(cm, self.num_element, self.num_bond_types, select=select)
+        out = framework.launch(cm, ring_data, mode, sys_bins, select=select)
+        n_bonds = cm.n_bonds[:cm.B]
+        if select is not None:
+            n_bonds = torch.where(select != 0, n_bonds, torch.zeros_like(n_bonds))
+        out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
+        return out, cm
+
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):
     """Split packed numpy outputs {'pred': [...], 'traj': [...]} per molecule (host, numpy -- like the reference)."""

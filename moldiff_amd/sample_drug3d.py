@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--frameworks]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -62,6 +62,12 @@ canonical order and the Kekulé structure of the canonical form; unchecked again
 stay what they are, from the molecule as decoded.  ``--canonical_max_nodes`` (``sample.canonical_max_nodes``) is the search budget: a
 molecule whose unpruned tree is larger is reported as abandoned (status 2), which is what the nearly complete bond graphs of untrained
 weights get.  Without the option nothing changes.
+``--frameworks`` (config key ``sample.frameworks``; the flag wins), an addition beyond the reference: rank 0 cuts the FINISHED molecules
+into framework, ring systems, linkers and side chains on the device batch by batch (``moldiff_amd/framework.py``: this project's own
+definition, not RDKit's MurckoScaffold), keys the pieces with the canonical labelling and writes ``frameworks.npz`` (results and keys)
+and ``frameworks.json`` (their summary).  ``--frameworks_exo`` / ``--frameworks_generic`` (``sample.frameworks_exo`` /
+``sample.frameworks_generic``) set the mode bits; ``--canonical_max_nodes`` is the search budget of the keys: a piece whose search is
+abandoned has no key and is counted in the summary.  Without the option nothing changes.
 No pretrained checkpoint ships with the reference (Google-Drive download); ``--recipe-weights`` substitutes the
 deterministic synthetic weights used by the tests so the entry point can be exercised end to end.
 """
@@ -327,8 +333,27 @@ def add_canonical_argument(ap):
     return ap
 
 
+def frameworks_option(flag, generic, exo, sample_cfg):
+    """whether to write the framework files, and the mode of ``moldiff_amd/framework.py``: the command line's flags (None = not given)
+    win over the config's ``sample.frameworks``, ``sample.frameworks_generic`` and ``sample.frameworks_exo``"""
+    pick = lambda f, key: bool(f if f is not None else sample_cfg.get(key))
+    return pick(flag, 'frameworks'), (1 if pick(exo, 'frameworks_exo') else 0) | (2 if pick(generic, 'frameworks_generic') else 0)
+
+
+def add_frameworks_argument(ap):
+    """``--frameworks`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--frameworks', action='store_true', default=None,
+                    help='cut the finished molecules into framework, ring systems, linkers and side chains on the device and write '
+                         'frameworks.npz and frameworks.json (overrides sample.frameworks)')
+    ap.add_argument('--frameworks_generic', action='store_true', default=None,
+                    help='frameworks and ring systems with every atom as class 0 and every bond single (overrides sample.frameworks_generic)')
+    ap.add_argument('--frameworks_exo', action='store_true', default=None,
+                    help='double-bonded atoms on the core join the framework (overrides sample.frameworks_exo)')
+    return ap
+
+
 def main(argv=None):
-    args = add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))).parse_args(argv)
+    args = add_frameworks_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -417,6 +442,11 @@ def main(argv=None):
         canon_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or canon.DEFAULT_MAX_NODES
         if not 1 <= canon_nodes <= canon.MAX_NODES_LIMIT:
             raise ValueError(f'canonical_max_nodes must lie in 1 .. 2^20, got {canon_nodes}')
+    fw_write, fw_mode = frameworks_option(args.frameworks, args.frameworks_generic, args.frameworks_exo, config.sample)
+    fw_parts = []
+    if fw_write:
+        from . import framework
+        fw_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or framework.canon.DEFAULT_MAX_NODES
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -522,6 +552,9 @@ def main(argv=None):
                 if kek_write:
                     for info, text in zip(gen, canon.smiles_mols(gen, canon_parts[-1], device, kek_tables)):
                         info['smiles'] = text
+            if fw_write and gen:
+                fw_parts.append(framework.stats_mols(gen, device, fw_mode, max_nodes=fw_nodes, atomic_numbers=featurizer.atomic_numbers.tolist(),
+                                                     num_bond_types=featurizer.num_bond_types))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -562,6 +595,11 @@ def main(argv=None):
             if kek_write:
                 with open(os.path.join(log_dir, 'samples.smi'), 'w') as f:
                     f.writelines('%s\t%d\n' % (m['smiles'], m['mol_id']) for m in pool['finished'] if m.get('smiles'))
+        if fw_write:
+            res = framework.concat(fw_parts) if fw_parts else framework.empty(with_keys=True)
+            save_npz(res, os.path.join(log_dir, 'frameworks.npz'))
+            with open(os.path.join(log_dir, 'frameworks.json'), 'w') as f:
+                json.dump(dict(framework.summary(res, device=device, atomic_numbers=featurizer.atomic_numbers.tolist()), mode=fw_mode), f, indent=1)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed']),
