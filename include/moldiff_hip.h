@@ -815,13 +815,6 @@ int mdx_op_sgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, co
  *   reduction; db (may be NULL) receives the bias gradient = column sums of G from the same pass. */
 int mdx_op_sgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M, int64_t N,
                     int64_t K, int32_t splits, float* partial, void* stream);
-/* hgemm_nt / hgemm_tn: the same two products with bf16-rounded operands on v_mfma_f32_16x16x32_bf16 and fp32
- *   accumulation / outputs (mixed-precision training; the reference trains under fp16 autocast).  Tensors stay fp32 in
- *   memory.  hgemm_nt has no split-K form. */
-int mdx_op_hgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* addend, int64_t ldd,
-                    float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream);
-int mdx_op_hgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M, int64_t N,
-                    int64_t K, int32_t splits, float* partial, void* stream);
 /* The same Linear on MANY rows (the edge rows of a training batch) with the row-owner decomposition of the sampling kernels:
  * Y (M,N) = X (M,K) W^T + bias + addend with W (N,K) [transW = 0], or X W with W (K,N) [transW = 1: the grad_input GEMM, no
  * separate transpose].  K % 16 == 0, K/16 in {1,2,4,5,8,16}, N % 4 == 0, N <= 256 (mdx_op_linear_rows_supported); rows 16-byte
@@ -838,11 +831,7 @@ int mdx_op_transpose_batch(const int64_t* desc, int64_t n, int64_t max_tiles, vo
 int mdx_op_colreduce(const float* X, const float* Y, int64_t ld, int64_t M, int64_t N, float* out, float* ws, void* stream);
 /* y = relu?(LayerNorm(x) * gamma + beta) over F <= 1024 features (nn.LayerNorm eps 1e-5, models/common.py MLP);
  * stats (M,2) receives (mean, rstd) for the backward.  Backward: dx (M,F), dgb (2F) = [dgamma | dbeta]; ws =
- * mdx_op_ln_relu_bwd_ws(M, F) bytes. */
-int mdx_op_ln_relu_fwd(const float* x, const float* gamma, const float* beta, int64_t M, int32_t F, int32_t relu, float* y,
-                       float* stats, void* stream);
-int mdx_op_ln_relu_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* beta, int64_t M,
-                       int32_t F, int32_t relu, float* dx, float* dgb, float* ws, void* stream);
+ * mdx_op_ln_relu_bwd_ws(M, F) bytes.  Entry points: mdx_op_ln_relu_fwd_t / mdx_op_ln_relu_bwd_t below. */
 size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F);
 /* The same backward when the layer after the LayerNorm is a Linear to ONE output (PosUpdate's inter MLP, 256 -> 1, reference
  * models/graph.py:388-392 through models/common.py:191-198): the upstream gradient dy[row][c] = f16(g1[row] * f16(w1[c])) is formed
@@ -851,18 +840,12 @@ size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F);
  * (mdx_op_ln_relu_bwd_rows(M) rows of 2F floats) for mdx_op_reduce_deferred.  F in {32, 64, 128, 256}; dt bit 1: x, bit 2: dx float16. */
 int mdx_op_ln_relu_bwd_r1_t(const void* g1, const float* w1, const void* x, const float* stats, const float* gamma, const float* beta,
                             int64_t M, int32_t F, int32_t relu, void* dx, float* ws, int32_t dt, void* stream);
-/* element-wise pairs, op: 0 a+b, 1 a-b, 2 a*b, 3 a*sigmoid(b).  Backward writes da / db (either may be NULL). */
-int mdx_op_ew_fwd(int32_t op, const float* a, const float* b, float* out, int64_t n, void* stream);
-int mdx_op_ew_bwd(int32_t op, const float* a, const float* b, const float* g, float* da, float* db, int64_t n, void* stream);
-/* y[i] = x[idx[i]] (rows of F floats) and its adjoint out[r] = sum_{j in [ptr[r],ptr[r+1])} src[order[j]]
- * (torch_scatter.scatter_sum with `order` = stable argsort of the index; sequential per output -> deterministic). */
-int mdx_op_gather_rows(const float* x, const int64_t* idx, int64_t M, int32_t F, float* y, void* stream);
-int mdx_op_segsum_rows(const float* src, const int64_t* order, const int64_t* ptr, int64_t R, int32_t F, float* out, void* stream);
-/* y = a * t[idx] (product with a gathered per-node row, e.g. h_edge * h_node[col], models/graph.py:44) without the
- * gathered (rows x F) intermediate; backward: da = g * t[idx], dt[r] = sum over the rows of segment r of g * a. */
-int mdx_op_mul_gather_fwd(const float* a, const float* t, const int64_t* idx, int64_t M, int32_t F, float* y, void* stream);
-int mdx_op_mul_gather_bwd(const float* g, const float* a, const float* t, const int64_t* idx, const int64_t* order, const int64_t* ptr,
-                          int64_t M, int64_t R, int32_t F, float* da, float* dt, void* stream);
+/* The element-wise, gather / segment-sum and product-with-gathered-row operators exist in their `_t` forms only (below):
+ * ew: element-wise pairs, op: 0 a+b, 1 a-b, 2 a*b, 3 a*sigmoid(b).  Backward writes da / db (either may be NULL).
+ * gather_rows / segsum_rows: y[i] = x[idx[i]] (rows of F floats) and its adjoint out[r] = sum_{j in [ptr[r],ptr[r+1])} src[order[j]]
+ *   (torch_scatter.scatter_sum with `order` = stable argsort of the index; sequential per output -> deterministic).
+ * mul_gather: y = a * t[idx] (product with a gathered per-node row, e.g. h_edge * h_node[col], models/graph.py:44) without the
+ *   gathered (rows x F) intermediate; backward: da = g * t[idx], dt[r] = sum over the rows of segment r of g * a. */
 /* rel = pos[l] - pos[r], dist = |rel| (models/graph.py:349-350); backward: g (E,3) = drel + ddist * rel / dist, the
  * caller scatters +g to l and -g to r.  drel / ddist may be NULL. */
 int mdx_op_edge_geom_fwd(const float* pos, const int64_t* l, const int64_t* r, int64_t E, float* rel, float* dist, void* stream);
@@ -889,11 +872,8 @@ int mdx_op_adamw(float* p, const float* g, float* m, float* v, int64_t n, float 
  * scripts/train_drug3d.py:86-109): operands rounded to half_kind (1 = bfloat16, 2 = float16) on their way into LDS, half MFMAs,
  * fp32 accumulation; round_out != 0 rounds the result to the same type before it is stored in its fp32 container -- the value a
  * Linear (and the gradient of a weight autocast cast to half) has there; float16 overflows to +-inf beyond 65504.
- * mdx_op_ew_fwd: op | (kind << 8) and mdx_op_mul_gather_fwd: F | (kind << 16) round their products the same way. */
-int mdx_op_xgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* addend, int64_t ldd,
-                    float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t half_kind, int32_t round_out, void* stream);
-int mdx_op_xgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M, int64_t N,
-                    int64_t K, int32_t splits, float* partial, int32_t half_kind, int32_t round_out, void* stream);
+ * mdx_op_ew_fwd_t: op | (kind << 8) and mdx_op_mul_gather_fwd_t: F | (kind << 16) round their products the same way.
+ * Entry points: mdx_op_xgemm_nt_t / mdx_op_xgemm_tn_t below. */
 
 /* Half storage (round 3): the `_t` forms of the training operators take `dt`, a bit mask of the tensors that are stored as float16
  * instead of fp32 (element strides and feature counts are unchanged).  In the mixed-precision mode every Linear / LayerNorm / product
@@ -901,7 +881,7 @@ int mdx_op_xgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, fl
  * Bits, in argument order -- xgemm_nt_t: 0 A, 1 addend, 2 C (needs half_kind 2);  xgemm_tn_t: 0 G, 1 X (dW, db stay fp32);
  * ln_relu_fwd_t: 0 x, 1 y;  ln_relu_bwd_t: 0 dy, 1 x, 2 dx;  ew_fwd_t: 0 a, 1 b, 2 out;  ew_bwd_t: 0 a, 1 b, 2 g, 3 da, 4 db;
  * gather_rows_t: 0 x, 1 y;  segsum_rows_t: 0 src, 1 out;  mul_gather_fwd_t: 0 a, 1 t, 2 y;  mul_gather_bwd_t: 0 g, 1 a, 2 t, 3 da, 4 dt.
- * dt = 0 is the fp32 operator of the same name without `_t`.  Half storage needs feature counts that are multiples of 4. */
+ * dt = 0 is the fp32 operator (these operators have no other entry point).  Half storage needs feature counts that are multiples of 4. */
 int mdx_op_xgemm_nt_t(const void* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const void* addend, int64_t ldd,
                       void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t half_kind, int32_t round_out, int32_t dt, void* stream);
 int mdx_op_xgemm_tn_t(const void* G, int64_t ldg, const void* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M, int64_t N,
@@ -938,8 +918,8 @@ int mdx_op_mul_gather_fwd_t(const void* a, const void* t, const int64_t* idx, in
 int mdx_op_mul_gather_bwd_t(const void* g, const void* a, const void* t, const int64_t* idx, const int64_t* order, const int64_t* ptr,
                             int64_t M, int64_t R, int32_t F, void* da, void* dtab, int32_t dt, void* stream);
 
-/* Deferred gradient reduction: mdx_op_sgemm_tn / mdx_op_xgemm_tn(_t) with dW == NULL (db != NULL still requests the bias partials)
- * and mdx_op_ln_relu_bwd(_t) with dgb == NULL leave their split partials in the caller's buffer (layout: mdx_op_wgrad_layout -> number
+/* Deferred gradient reduction: mdx_op_sgemm_tn / mdx_op_xgemm_tn_t with dW == NULL (db != NULL still requests the bias partials)
+ * and mdx_op_ln_relu_bwd_t with dgb == NULL leave their split partials in the caller's buffer (layout: mdx_op_wgrad_layout -> number
  * of partials S and the float offset of the [S][N] bias partials; LayerNorm: mdx_op_ln_relu_bwd_rows(M) rows of 2F floats in ws).
  * mdx_op_reduce_deferred sums every record of a device table in ONE launch and ADDS it to its destination (a parameter's slot in a flat
  * gradient buffer): record = 8 x int64 {P, dst, S, rows, cols, ld, pstride, rkind | chunked << 6 | store << 7 | first_block << 8};

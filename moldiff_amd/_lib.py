@@ -27,11 +27,11 @@ EXPORTS = [
     'mdx_mol_groups', 'mdx_mol_groups_ws_bytes', 'mdx_mol_kekulize', 'mdx_mol_canon', 'mdx_mol_framework',
     'mdx_sample_jump_full', 'mdx_pos_posterior_jump', 'mdx_cat_posterior_jump', 'mdx_forward_jump',
     'mdx_profile_enable', 'mdx_profile_read', 'mdx_profile_kernel_name',
-    'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_hgemm_nt', 'mdx_op_hgemm_tn', 'mdx_op_xgemm_nt', 'mdx_op_xgemm_tn', 'mdx_op_amp_adamw',
+    'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_amp_adamw',
     'mdx_op_xgemm_nt_t', 'mdx_op_xgemm_nt_ln_t', 'mdx_op_xgemm_nt_ln_supported', 'mdx_op_xgemm_tn_t', 'mdx_op_ln_relu_fwd_t', 'mdx_op_ln_relu_bwd_t', 'mdx_op_ew_fwd_t', 'mdx_op_ew_bwd_t',
     'mdx_op_gather_rows_t', 'mdx_op_segsum_rows_t', 'mdx_op_mul_gather_fwd_t', 'mdx_op_mul_gather_bwd_t',
-    'mdx_op_wgrad_layout', 'mdx_op_wgrad_plan', 'mdx_op_wgrad_grouped', 'mdx_op_ln_relu_bwd_rows', 'mdx_op_reduce_deferred', 'mdx_op_transpose', 'mdx_op_transpose_batch', 'mdx_op_linear_rows', 'mdx_op_linear_rows_ws', 'mdx_op_linear_rows_supported', 'mdx_op_colreduce', 'mdx_op_ln_relu_fwd', 'mdx_op_ln_relu_bwd', 'mdx_op_ln_relu_bwd_ws',
-    'mdx_op_ew_fwd', 'mdx_op_ew_bwd', 'mdx_op_gather_rows', 'mdx_op_segsum_rows', 'mdx_op_mul_gather_fwd', 'mdx_op_mul_gather_bwd', 'mdx_op_edge_geom_fwd', 'mdx_op_edge_geom_bwd',
+    'mdx_op_wgrad_layout', 'mdx_op_wgrad_plan', 'mdx_op_wgrad_grouped', 'mdx_op_ln_relu_bwd_rows', 'mdx_op_reduce_deferred', 'mdx_op_transpose', 'mdx_op_transpose_batch', 'mdx_op_linear_rows', 'mdx_op_linear_rows_ws', 'mdx_op_linear_rows_supported', 'mdx_op_colreduce', 'mdx_op_ln_relu_bwd_ws',
+    'mdx_op_edge_geom_fwd', 'mdx_op_edge_geom_bwd',
     'mdx_op_smear_fwd', 'mdx_op_smear_bwd', 'mdx_op_force_fwd', 'mdx_op_force_bwd', 'mdx_op_sumsq', 'mdx_op_adamw',
     'mdx_op_bondffn_fwd', 'mdx_op_bondffn_bwd', 'mdx_op_bondffn_workgroups', 'mdx_op_bondffn_lnp_floats',
     'mdx_op_edge_tail_fwd', 'mdx_op_edge_tail_bwd', 'mdx_op_edge_tail_lnp_floats',
@@ -179,53 +179,31 @@ def lib():
         L.mdx_profile_read.argtypes = [c_int32, POINTER(c_int64), POINTER(ctypes.c_double)]
         L.mdx_profile_kernel_name.argtypes = [c_int32]
         L.mdx_profile_kernel_name.restype = c_char_p
-        # layer-level training operators
-        L.mdx_op_sgemm_nt.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_int64, c_int64, c_int32, c_void_p, c_void_p]
-        L.mdx_op_sgemm_tn.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
-                                      c_int32, c_void_p, c_void_p]
-        L.mdx_op_hgemm_nt.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
-                                      c_int64, c_int64, c_void_p]
-        L.mdx_op_hgemm_tn.argtypes = L.mdx_op_sgemm_tn.argtypes
-        L.mdx_op_xgemm_nt.argtypes = L.mdx_op_hgemm_nt.argtypes[:-1] + [c_int32, c_int32, c_void_p]
-        L.mdx_op_xgemm_tn.argtypes = L.mdx_op_sgemm_tn.argtypes[:-1] + [c_int32, c_int32, c_void_p]
+        # layer-level training operators.  The Linear / LayerNorm nodes, the gradient sink and the fused operators call the library from
+        # csrc/mdx_fast.cpp (mdx_op_sgemm_*, xgemm_nt*_t, transpose, linear_rows, colreduce, wgrad_*, reduce_deferred, bondffn_* / edge_tail_* /
+        # posffn_* / nodemsg_* / pack_a); only what Python (train_ops, trainer, tests) calls itself is declared here.
         L.mdx_op_amp_adamw.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_float,
                                        c_void_p, c_float, c_float, c_int32, c_void_p, c_void_p]
-        L.mdx_op_transpose.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]
         L.mdx_op_transpose_batch.argtypes = [c_void_p, c_int64, c_int64, c_void_p]
-        L.mdx_op_linear_rows.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                         c_int64, c_int64, c_int64, c_void_p, c_void_p]
-        L.mdx_op_linear_rows_ws.argtypes = [c_int64, c_int64]
-        L.mdx_op_linear_rows_ws.restype = ctypes.c_size_t
         L.mdx_op_linear_rows_supported.argtypes = [c_int64, c_int64]
-        L.mdx_op_colreduce.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
-        L.mdx_op_ln_relu_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-        L.mdx_op_ln_relu_bwd.argtypes = [c_void_p] * 5 + [c_int64, c_int32, c_int32] + [c_void_p] * 4
         L.mdx_op_ln_relu_bwd_ws.restype = c_size_t
         L.mdx_op_ln_relu_bwd_ws.argtypes = [c_int64, c_int32]
-        L.mdx_op_ew_fwd.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-        L.mdx_op_ew_bwd.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-        L.mdx_op_gather_rows.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]
-        L.mdx_op_segsum_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]
-        L.mdx_op_mul_gather_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]
-        L.mdx_op_mul_gather_bwd.argtypes = [c_void_p] * 6 + [c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]
-        L.mdx_op_wgrad_layout.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64)]
-        L.mdx_op_wgrad_plan.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, c_int64, c_int64, c_int32, POINTER(c_int64)]
-        L.mdx_op_wgrad_grouped.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_void_p]
         L.mdx_op_sum_n.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int32, c_void_p]
         L.mdx_op_plan_flip.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]
         L.mdx_op_ln_relu_bwd_r1_t.argtypes = [c_void_p] * 6 + [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
         L.mdx_op_ln_relu_bwd_rows.argtypes = [c_int64]
         L.mdx_op_ln_relu_bwd_rows.restype = c_int64
-        L.mdx_op_reduce_deferred.argtypes = [c_void_p, c_int32, c_int64, c_void_p]
-        # half-storage forms: the fp32 signature with an int32 `dt` mask in front of the stream
-        for name in ('xgemm_nt', 'xgemm_tn', 'ln_relu_fwd', 'ln_relu_bwd', 'ew_fwd', 'ew_bwd', 'gather_rows', 'segsum_rows', 'mul_gather_fwd',
-                     'mul_gather_bwd'):
-            base = getattr(L, 'mdx_op_' + name).argtypes
-            getattr(L, 'mdx_op_' + name + '_t').argtypes = list(base[:-1]) + [c_int32, c_void_p]
-        L.mdx_op_xgemm_nt_ln_supported.argtypes = [c_int64, c_int64, c_int64]
-        L.mdx_op_xgemm_nt_ln_t.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
-                                           c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p]
+        # (every operand that may be stored as float16 is a void pointer; `dt`, the int32 in front of the stream, says which are)
+        L.mdx_op_xgemm_tn_t.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                        c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]
+        L.mdx_op_ln_relu_fwd_t.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
+        L.mdx_op_ln_relu_bwd_t.argtypes = [c_void_p] * 5 + [c_int64, c_int32, c_int32] + [c_void_p] * 3 + [c_int32, c_void_p]
+        L.mdx_op_ew_fwd_t.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+        L.mdx_op_ew_bwd_t.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+        L.mdx_op_gather_rows_t.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p]
+        L.mdx_op_segsum_rows_t.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p]
+        L.mdx_op_mul_gather_fwd_t.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p]
+        L.mdx_op_mul_gather_bwd_t.argtypes = [c_void_p] * 6 + [c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
         L.mdx_op_edge_geom_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
         L.mdx_op_edge_geom_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
         L.mdx_op_smear_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_int64, c_void_p, c_void_p]
@@ -235,7 +213,6 @@ def lib():
         L.mdx_op_sumsq.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
         L.mdx_op_adamw.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                    c_int64, c_void_p, c_float, c_void_p]
-        # (the fused training operators mdx_op_bondffn_* / edge_tail_* / posffn_* / nodemsg_* / pack_a are called from csrc/mdx_fast.cpp alone)
         _lib = L
     return _lib
 

@@ -2015,10 +2015,6 @@ extern "C" int mdx_op_ln_relu_fwd_t(const void* xv, const float* gamma, const fl
                      (int)M, F, relu, (float*)yv, stats);
   return launched();
 }
-extern "C" int mdx_op_ln_relu_fwd(const float* x, const float* gamma, const float* beta, int64_t M, int32_t F, int32_t relu, float* y,
-                                  float* stats, void* stream) {
-  return mdx_op_ln_relu_fwd_t(x, gamma, beta, M, F, relu, y, stats, 0, stream);
-}
 
 // dx (M,F); dgb (2F) = [dgamma | dbeta].  ws: mdx_op_ln_relu_bwd_ws(M, F) bytes.
 extern "C" int mdx_op_ln_relu_bwd_t(const void* dyv, const void* xv, const float* stats, const float* gamma, const float* beta, int64_t M,
@@ -2072,10 +2068,6 @@ extern "C" int mdx_op_ln_relu_bwd_r1_t(const void* g1, const float* w1, const vo
 #undef MDX_LNB1
   return launched();
 }
-extern "C" int mdx_op_ln_relu_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* beta, int64_t M,
-                                  int32_t F, int32_t relu, float* dx, float* dgb, float* ws, void* stream) {
-  return mdx_op_ln_relu_bwd_t(dy, x, stats, gamma, beta, M, F, relu, dx, dgb, ws, 0, stream);
-}
 extern "C" size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F) {
   const int64_t nw = (M + MDX_LN_RPW - 1) / MDX_LN_RPW, nr = (nw + 3) / 4;   // one partial row per workgroup of four waves
   return ((size_t)std::max<int64_t>(nr, 1) * 2 * F + reduce_scratch_floats(nr, 2 * F)) * sizeof(float);
@@ -2118,9 +2110,6 @@ extern "C" int mdx_op_sum_n(const void* const* srcs, const int32_t* half, int32_
   else hipLaunchKernelGGL(sum_n1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, a, to, (size_t)n);
   return launched();
 }
-extern "C" int mdx_op_ew_fwd(int32_t op, const float* a, const float* b, float* out, int64_t n, void* stream) {
-  return mdx_op_ew_fwd_t(op, a, b, out, n, 0, stream);
-}
 extern "C" int mdx_op_ew_bwd_t(int32_t op, const void* a, const void* b, const void* g, void* da, void* db, int64_t n, int32_t dt,
                                void* stream) {
   if (n <= 0) return MDX_OK;
@@ -2138,9 +2127,6 @@ extern "C" int mdx_op_ew_bwd_t(int32_t op, const void* a, const void* b, const v
   }
   return launched();
 }
-extern "C" int mdx_op_ew_bwd(int32_t op, const float* a, const float* b, const float* g, float* da, float* db, int64_t n, void* stream) {
-  return mdx_op_ew_bwd_t(op, a, b, g, da, db, n, 0, stream);
-}
 extern "C" int mdx_op_gather_rows_t(const void* x, const int64_t* idx, int64_t M, int32_t F, void* y, int32_t dt, void* stream) {
   if (M <= 0 || F <= 0) return MDX_OK;
   const TP tx{x, dt & 1};
@@ -2152,9 +2138,6 @@ extern "C" int mdx_op_gather_rows_t(const void* x, const int64_t* idx, int64_t M
     hipLaunchKernelGGL(gather_rows_kernel, dim3(nblk((size_t)M * F)), dim3(256), 0, (hipStream_t)stream, (const float*)x, idx, M, F, (float*)y);
   }
   return launched();
-}
-extern "C" int mdx_op_gather_rows(const float* x, const int64_t* idx, int64_t M, int32_t F, float* y, void* stream) {
-  return mdx_op_gather_rows_t(x, idx, M, F, y, 0, stream);
 }
 extern "C" int mdx_op_segsum_rows_t(const void* src, const int64_t* order, const int64_t* ptr, int64_t R, int32_t F, void* out, int32_t dt,
                                     void* stream) {
@@ -2183,10 +2166,6 @@ extern "C" int mdx_op_segsum_rows_t(const void* src, const int64_t* order, const
                          (float*)out);
   }
   return launched();
-}
-extern "C" int mdx_op_segsum_rows(const float* src, const int64_t* order, const int64_t* ptr, int64_t R, int32_t F, float* out,
-                                  void* stream) {
-  return mdx_op_segsum_rows_t(src, order, ptr, R, F, out, 0, stream);
 }
 extern "C" int mdx_op_edge_geom_fwd(const float* pos, const int64_t* l, const int64_t* r, int64_t E, float* rel, float* dist, void* stream) {
   if (E <= 0) return MDX_OK;
@@ -2548,11 +2527,6 @@ extern "C" int mdx_op_xgemm_nt_ln_t(const void* Av, int64_t lda, const float* B,
 #undef MDX_HRL
   return launched();
 }
-extern "C" int mdx_op_xgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* addend,
-                               int64_t ldd, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t half_kind, int32_t round_out,
-                               void* stream) {
-  return mdx_op_xgemm_nt_t(A, lda, B, ldb, bias, addend, ldd, C, ldc, M, N, K, half_kind, round_out, 0, stream);
-}
 extern "C" int mdx_op_xgemm_tn_t(const void* Gv, int64_t ldg, const void* Xv, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M,
                                  int64_t N, int64_t K, int32_t splits, float* partial, int32_t half_kind, int32_t round_out, int32_t dt,
                                  void* stream) {
@@ -2676,18 +2650,6 @@ extern "C" int mdx_op_wgrad_grouped(const int64_t* desc, int32_t n, int64_t tota
   }
   return launched();
 }
-extern "C" int mdx_op_xgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M,
-                               int64_t N, int64_t K, int32_t splits, float* partial, int32_t half_kind, int32_t round_out, void* stream) {
-  return mdx_op_xgemm_tn_t(G, ldg, X, ldx, dW, ldw, db, M, N, K, splits, partial, half_kind, round_out, 0, stream);
-}
-extern "C" int mdx_op_hgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* addend,
-                               int64_t ldd, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
-  return mdx_op_xgemm_nt(A, lda, B, ldb, bias, addend, ldd, C, ldc, M, N, K, 1, 0, stream);
-}
-extern "C" int mdx_op_hgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M,
-                               int64_t N, int64_t K, int32_t splits, float* partial, void* stream) {
-  return mdx_op_xgemm_tn(G, ldg, X, ldx, dW, ldw, db, M, N, K, splits, partial, 1, 0, stream);
-}
 
 // y = a * t[idx] (rows of F floats, F % 4 == 0) and its gradients; see mulg_*_kernel.
 // F: feature count in its low 16 bits; bits 16.. = rounding kind of the product (0 fp32, 1 bfloat16, 2 float16; mixed precision)
@@ -2703,9 +2665,6 @@ extern "C" int mdx_op_mul_gather_fwd_t(const void* a, const void* t, const int64
   if (!(tp_vec_ok(a, ta.h, 4) && tp_vec_ok(t, tt.h, 4) && tp_vec_ok(y, ty.h, 4))) return bad("mul_gather: rows must be aligned");
   hipLaunchKernelGGL(mulg_fwd_kernel, dim3(nblk((size_t)M * (F / 4))), dim3(256), 0, (hipStream_t)stream, ta, tt, idx, M, F / 4, ty, rk);
   return launched();
-}
-extern "C" int mdx_op_mul_gather_fwd(const float* a, const float* t, const int64_t* idx, int64_t M, int32_t F, float* y, void* stream) {
-  return mdx_op_mul_gather_fwd_t(a, t, idx, M, F, y, 0, stream);
 }
 extern "C" int mdx_op_mul_gather_bwd_t(const void* g, const void* a, const void* t, const int64_t* idx, const int64_t* order,
                                        const int64_t* ptr, int64_t M, int64_t R, int32_t F, void* da, void* dtab, int32_t dt, void* stream) {
@@ -2727,8 +2686,4 @@ extern "C" int mdx_op_mul_gather_bwd_t(const void* g, const void* a, const void*
   if (want_dt)
     hipLaunchKernelGGL(mulg_segsum_kernel, dim3(nblk((size_t)R * (F / 4))), dim3(256), 0, s, tg, ta, order, ptr, R, F / 4, tdt);
   return launched();
-}
-extern "C" int mdx_op_mul_gather_bwd(const float* g, const float* a, const float* t, const int64_t* idx, const int64_t* order,
-                                     const int64_t* ptr, int64_t M, int64_t R, int32_t F, float* da, float* dt, void* stream) {
-  return mdx_op_mul_gather_bwd_t(g, a, t, idx, order, ptr, M, R, F, da, dt, 0, stream);
 }

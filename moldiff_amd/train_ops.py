@@ -7,11 +7,13 @@ gradients (MFMA SGEMM), LayerNorm(+ReLU), gates, gathers / segmented sums, edge 
 is no CPU fallback: CPU tensors raise.  Replaces, for training, ``torch.nn.functional.linear / layer_norm / relu``,
 ``torch_scatter.scatter_sum`` and index_select as used by the reference's models/graph.py and models/common.py.
 
-The per-operator nodes (Linear, LayerNorm, element-wise, gather / segment sum) have their host bodies here, over ctypes.  The
-four fused row-owner operators have ONE host body each, in the C++ extension (``csrc/mdx_fast.cpp``); their classes here
-marshal the index plans, call it, and choose between the two routes by which the parameter gradients leave a backward.
+Every operator whose host side matters for the step time -- Linear, LayerNorm(+ReLU), Linear+LayerNorm+ReLU, the element-wise pairs and
+the four fused row-owner operators -- has ONE host body, in the C++ extension (``csrc/mdx_fast.cpp``), for every precision mode and every
+route by which a parameter gradient leaves a backward.  The functions here are shells: they call the extension unconditionally
+(``linear``, ``ln_relu``, ``linear_ln_relu``, ``add`` ...), forward to the functions its nodes are made of (``sgemm_nt``, ``sgemm_tn``,
+``transpose`` ...), or, for the fused operators, marshal the index plans and choose between the two routes of their parameter gradients.
+The remaining nodes (gather / segment sum, edge geometry, smearing, force, the loss tail) have their host bodies here, over ctypes.
 """
-import bisect
 import ctypes
 import os
 
@@ -27,13 +29,12 @@ ADD, SUB, MUL, GATE = 0, 1, 2, 3
 # long as the GPU needs for the step.  `_mdx_fast` holds, against the same C ABI:
 #   * the gradient sink and the weight-gradient queue, which exist only there, as C++ state: every sink record and queue entry goes
 #     through it, in any precision mode;
-#   * Linear / Linear+LayerNorm+ReLU / element-wise nodes as C++ autograd functions for the float16 autocast mode with float16 containers
-#     inside a sink (Trainer.step, precision='fp16'); the Python bodies below serve every other mode;
+#   * the Linear / LayerNorm / Linear+LayerNorm+ReLU / element-wise nodes as C++ autograd functions, in every mode, with or without a sink;
 #   * the only host body of the four fused row-owner operators, in every mode that runs them (see "fused row-owner operators" below).
 # A missing extension is an error, not a silent slow path.
 _FASTMOD = None
-# False: the Python operator bodies, and the Python route of the fused operators' parameter gradients, also serve the float16 sink (the
-# sink and the queue stay in C++).  For the test that holds the two bit-identical (tests/test_gpu_trainer.py); not an environment switch.
+# False: the parameter gradients of the fused row-owner operators take their Python route (_fused_param_grads) in the float16 sink too.
+# For the test that holds the two routes bit-identical (tests/test_gpu_trainer.py); not an environment switch.
 _CPP_NODES = True
 
 
@@ -48,7 +49,7 @@ def _fast():
             raise RuntimeError('moldiff_amd/_mdx_fast.so (the C++ fast path of the training operators) is not built or does not load: run '
                                f'`python -c "import __graft_entry__ as g; g.build()"` (make -C moldiff_amd/csrc).  [{e}]') from e
         _FASTMOD = _mdx_fast
-        _FASTMOD.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
+        _FASTMOD.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES, ROWS_MIN)
         _fast_sync_precision()
     return _FASTMOD
 
@@ -115,11 +116,6 @@ def _round_kind():
     return _AMP[0] if (_AMP is not None and _AMP[1]) else 0
 
 
-def _store_dtype():
-    """container of a Linear / LayerNorm / product result in the current mode"""
-    return torch.float16 if (_AMP is not None and _AMP[2]) else torch.float32
-
-
 def _t(t):
     """device tensor, contiguous, in its own container type (fp32 or float16); anything else is converted to fp32"""
     _lib._need_gpu(t)
@@ -171,7 +167,7 @@ class grad_sink:
         _lib._need_gpu(f.data)
         F = _fast()
         _fast_sync_precision()
-        F.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES)
+        F.set_options(_WG_ON, WGRAD_ROWS, WGRAD_QUEUE_BYTES, ROWS_MIN)
         F.sink_begin(f.data, f.grad)          # (raises inside an active sink)
         _SINK = (f.data.data_ptr(), f.grad.data_ptr(), f.data.numel() * 4)
         return self
@@ -180,11 +176,6 @@ class grad_sink:
         global _SINK
         _SINK = None
         _FASTMOD.sink_end()                   # (flushes what is left)
-
-
-def _cpp():
-    """the extension where the C++ operator nodes may run (inside a gradient sink), else None"""
-    return _FASTMOD if (_SINK is not None and _CPP_NODES) else None
 
 
 def _sink_dst(t):
@@ -206,28 +197,13 @@ def flush_grad_sink():
         _FASTMOD.flush()
 
 
+# The functions below forward to the ones the extension's Linear / LayerNorm nodes are made of (csrc/mdx_fast.cpp); tests and the
+# scripts under tools/ call them by these names.
 def sgemm_nt(a, b, bias=None, splits=1, addend=None, keep32=False, out_dtype=None):
     """a (M,K) @ b (N,K)^T + bias + addend -> (M,N).  Rows of a / b may be strided (column slices of a wider matrix).
     keep32: in an autocast mode, do not round the result (it is a partial sum that enters another Linear as its addend).
     a / addend may be fp32 or float16 containers (mixed precision only); out_dtype: container of the result (default: the mode's)."""
-    M, K = a.shape
-    N = b.shape[0]
-    assert a.stride(1) == 1 and b.stride(1) == 1 and b.dtype == torch.float32
-    if _AMP is not None and splits <= 1:
-        if out_dtype is None:
-            out_dtype = torch.float32 if keep32 else _store_dtype()
-        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
-        rnd = int((_AMP[1] and not keep32) or out_dtype == torch.float16)
-        check(_L().mdx_op_xgemm_nt_t(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(bias), ptr(addend),
-                                     addend.stride(0) if addend is not None else 0, ptr(out), N, M, N, K, _AMP[0], rnd,
-                                     _h(a) | (_h(addend) << 1) | (_h(out) << 2), stream()))
-        return out
-    assert a.dtype == torch.float32 and (addend is None or addend.dtype == torch.float32)
-    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    part = torch.empty(splits * M * N, dtype=torch.float32, device=a.device) if splits > 1 else None
-    check(_L().mdx_op_sgemm_nt(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(bias), ptr(addend), N if addend is not None else 0, ptr(out),
-                               N, M, N, K, splits, ptr(part), stream()))
-    return out
+    return _fast().sgemm_nt(a, b, bias, splits, addend, keep32, -1 if out_dtype is None else int(out_dtype == torch.float16))
 
 
 ROWS_MIN = 16384   # from this many rows on a Linear runs on the row-owner kernel (one wave per 16 rows; the weight is re-packed per call)
@@ -235,37 +211,18 @@ ROWS_MIN = 16384   # from this many rows on a Linear runs on the row-owner kerne
 
 def linear_rows_ok(a, n, k, addend=None):
     """Can `a` (M,k) @ W -> (M,n) take the row-owner kernel?  Shape built, enough rows, 16-byte aligned rows, fp32 mode."""
-    return (_AMP is None and a.dtype == torch.float32 and a.shape[0] >= ROWS_MIN and a.stride(1) == 1 and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0
-            and (addend is None or (addend.stride(1) == 1 and addend.stride(0) % 4 == 0 and addend.data_ptr() % 16 == 0))
-            and _L().mdx_op_linear_rows_supported(n, k) == 1)
+    return _fast().linear_rows_ok(a, n, k, addend)
 
 
 def linear_rows(a, w, trans_w, bias=None, addend=None):
     """a (M,K) @ W^T (W (N,K), trans_w = False) or a @ W (W (K,N), trans_w = True) + bias + addend -> (M,N) on the row-owner
     kernel (csrc/mdx_linear_rows.hip)."""
-    M, K = a.shape
-    N = w.shape[1] if trans_w else w.shape[0]
-    assert w.stride(1) == 1 and (w.shape[0] if trans_w else w.shape[1]) == K
-    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    ws = torch.empty(_L().mdx_op_linear_rows_ws(N, K) // 4, dtype=torch.float32, device=a.device)
-    check(_L().mdx_op_linear_rows(ptr(a), a.stride(0), ptr(w), w.stride(0), 1 if trans_w else 0, ptr(bias), ptr(addend),
-                                  addend.stride(0) if addend is not None else 0, ptr(out), N, M, N, K, ptr(ws), stream()))
-    return out
-
-
-_LAYOUTS = {}
+    return _fast().linear_rows(a, w, bool(trans_w), bias, addend)
 
 
 def _wgrad_layout(M, N, K, splits, half):
-    """(row ranges actually used, offset of the bias partials) of a weight-gradient call: a pure function of its arguments, asked of the
-    library once per shape (it used to be a call per weight gradient per step)"""
-    key = (M, N, K, splits, half)
-    r = _LAYOUTS.get(key)
-    if r is None:
-        S, boff = ctypes.c_int64(), ctypes.c_int64()
-        check(_L().mdx_op_wgrad_layout(M, N, K, splits, half, ctypes.byref(S), ctypes.byref(boff)))
-        r = _LAYOUTS[key] = (S.value, boff.value)
-    return r
+    """(row ranges actually used, offset of the bias partials) of a weight-gradient call: a pure function of its arguments"""
+    return _fast().wgrad_layout(M, N, K, splits, half)
 
 
 # ---- queued weight gradients (round 6) -----------------------------------------------------------------------------------------
@@ -284,39 +241,11 @@ WGRAD_QUEUE_BYTES = int(float(os.environ.get('MDX_WGRAD_QUEUE_GB', '24')) * 2 **
 def sgemm_tn(g, x, splits, want_bias=False, defer=None):
     """g (M,N)^T @ x (M,K) -> (N,K): the weight gradient, straight from the row-major tensors; with want_bias also the
     column sums of g (the bias gradient) from the same pass -> (dW, db).
-    defer = (dst_w, ldw, dst_b): leave the split partials for `flush_grad_sink` (destinations in the flat gradient buffer) -> None."""
-    M, N = g.shape
-    K = x.shape[1]
-    splits = max(1, int(splits))
-    if defer is not None and _WG_ON and _SINK is not None and _AMP is not None and _AMP[0] == 2 and g.stride(1) == 1 and x.stride(1) == 1:
-        dst_w, ldw, dst_b = defer
-        _FASTMOD.wq_append(g, x, dst_w, ldw, (dst_b or 0) if want_bias else 0, _AMP[0] if _AMP[1] else 0)
-        return None
-    part = torch.empty((splits + (splits + 255) // 256) * (N * K + N), dtype=torch.float32, device=g.device)
-    if defer is not None:
-        dst_w, ldw, dst_b = defer
-        S, boff = _wgrad_layout(M, N, K, splits, 1 if _AMP is not None else 0)
-        wb = ptr(part) if want_bias else None        # any non-null pointer = "also write the bias partials"
-        if _AMP is not None:
-            check(_L().mdx_op_xgemm_tn_t(ptr(g), g.stride(0), ptr(x), x.stride(0), None, K, wb, M, N, K, splits, ptr(part), _AMP[0],
-                                         int(_AMP[1]), _h(g) | (_h(x) << 1), stream()))
-            rk = _AMP[0] if _AMP[1] else 0
-        else:
-            check(_L().mdx_op_sgemm_tn(ptr(g), g.stride(0), ptr(x), x.stride(0), None, K, wb, M, N, K, splits, ptr(part), stream()))
-            rk = 0
-        _sink_record(part.data_ptr(), dst_w, S, N, K, ldw, N * K, rk, part)
-        if want_bias:
-            _sink_record(part.data_ptr() + 4 * boff, dst_b, S, 1, N, N, N, rk, part)
-        return None
-    out = torch.empty(N, K, dtype=torch.float32, device=g.device)
-    db = torch.empty(N, dtype=torch.float32, device=g.device) if want_bias else None
-    if _AMP is not None:
-        check(_L().mdx_op_xgemm_tn_t(ptr(g), g.stride(0), ptr(x), x.stride(0), ptr(out), K, ptr(db), M, N, K, splits, ptr(part), _AMP[0],
-                                     int(_AMP[1]), _h(g) | (_h(x) << 1), stream()))
-    else:
-        assert g.dtype == torch.float32 and x.dtype == torch.float32
-        check(_L().mdx_op_sgemm_tn(ptr(g), g.stride(0), ptr(x), x.stride(0), ptr(out), K, ptr(db), M, N, K, splits, ptr(part), stream()))
-    return (out, db) if want_bias else out
+    defer = (dst_w, ldw, dst_b): queue the contraction (float16 kind, queue on) or leave its split partials for `flush_grad_sink`
+    (destinations in the flat gradient buffer) -> None.  The three routes are csrc/mdx_fast.cpp weight_grad."""
+    dst_w, ldw, dst_b = defer if defer is not None else (0, 0, 0)
+    dw, db = _fast().weight_grad(g, x, int(splits), bool(want_bias), dst_w, ldw, dst_b or 0)
+    return None if defer is not None else ((dw, db) if want_bias else dw)
 
 
 # Transposed weights of the step (Trainer.refresh_transposed): the flat parameter buffer's 2-D tensors, each transposed at its own
@@ -349,21 +278,20 @@ class TransposedParams:
     def refresh(self):
         check(_L().mdx_op_transpose_batch(ptr(self.desc), self.n, self.tiles, stream()))
 
+    def table(self):
+        """what the extension's lookup takes: (parameter buffer address, bytes, W^T buffer, sorted byte offsets, (off, R, C, dst off) per offset)"""
+        return self.base, self.nbytes, self.buf, self.offsets, [list(self.entries[o]) for o in self.offsets]
+
     def view(self, w):
-        """W^T of a parameter matrix or of a column slice of one, as a view into the transposed buffer; None if `w` is neither."""
-        rel = w.data_ptr() - self.base
-        if rel < 0 or rel >= self.nbytes or w.dim() != 2 or w.dtype != torch.float32 or w.stride(1) != 1:
+        """W^T of a parameter matrix or of a column slice of one, as a view into the transposed buffer; None if `w` is neither (or if
+        its rows there would not start on 16 bytes).  The lookup is the one the nodes use (csrc/mdx_fast.cpp wt_view).  For tests and
+        tools: every call hands the whole table over (O(entries)); the nodes look up in the copy that transposed_params installed."""
+        base, nbytes, buf, offsets, entries = self.table()
+        r = _fast().wt_view(base, nbytes, buf.data_ptr(), offsets, entries, w)
+        if r is None:
             return None
-        i = bisect.bisect_right(self.offsets, rel) - 1
-        if i < 0:
-            return None
-        off, R, C, doff = self.entries[self.offsets[i]]
-        col = rel // 4 - off
-        if col < 0 or col >= C or w.stride(0) != C or w.shape[0] != R or col + w.shape[1] > C:
-            return None
-        if (self.buf.data_ptr() + 4 * (doff + col * R)) % 16:
-            return None                                 # the GEMM's 16-byte operand loads want aligned rows
-        return self.buf[doff:doff + R * C].view(C, R)[col:col + w.shape[1]]
+        start, R = r
+        return buf[start:start + R * w.shape[1]].view(w.shape[1], R)
 
 
 class transposed_params:
@@ -388,104 +316,29 @@ def _fast_sync_wt():
     if F is not None:
         tp = _WT
         if tp is None:
-            F.set_wt(0, 0, 0, [], [])
+            F.set_wt(0, 0, None, [], [])
         else:
-            F.set_wt(tp.base, tp.nbytes, tp.buf.data_ptr(), tp.offsets, [list(tp.entries[o]) for o in tp.offsets])   # (off, R, C, dst off)
+            F.set_wt(*tp.table())
 
 
 def transpose(x, pad=4):
     """(R,C) -> contiguous-rows (C,R) view whose leading dimension is padded to a multiple of `pad` floats (so that the
-    SGEMM's 16-byte loads stay aligned for any R)."""
-    if _WT is not None:
-        v = _WT.view(x)
-        if v is not None:
-            return v
-    R, C = x.shape
-    ld = (R + pad - 1) // pad * pad
-    buf = torch.empty(C, ld, dtype=torch.float32, device=x.device)
-    check(_L().mdx_op_transpose(ptr(x), x.stride(0), R, C, ptr(buf), ld, stream()))
-    return buf[:, :R]
+    SGEMM's 16-byte loads stay aligned for any R); a view into the step's transposed parameters where `x` has one."""
+    return _fast().transpose(x, pad)
 
 
 def colreduce(x, y=None):
-    M, N = x.shape
-    out = torch.empty(N, dtype=torch.float32, device=x.device)
-    ws = torch.empty(((M + 511) // 512) * N, dtype=torch.float32, device=x.device) if M > 512 else None
-    check(_L().mdx_op_colreduce(ptr(x), ptr(y), x.stride(0), M, N, ptr(out), ptr(ws), stream()))
-    return out
+    return _fast().colreduce(x, y)
 
 
 def _splits_for(rows, n, k, half=False):
-    """row ranges of a weight gradient (the contraction runs over `rows`): enough of them to fill the chip with workgroups, each >= 128
-    rows.  fp32 / converting kernels: 64 x 64 tiles, ~1024 workgroups (flat between 512 and 4096; each loops over its rows in short
-    steps, many short loops hide the load latency better than few long ones).  float16 containers with tile-aligned widths take the
-    transpose-read kernel (csrc hgemm_tn_tr_kernel): 128-wide tiles where the layer allows, ~512 workgroups = one resident set
-    (two per CU); more ranges mean more split partials to write and reduce (measured per step: 384 -> 34.2, 512 -> 33.5, 768 -> 34.1, 1024 -> 34.8 ms)."""
-    if half and n % 64 == 0 and k % 64 == 0:
-        tiles = (n // (128 if n % 128 == 0 else 64)) * (k // (128 if k % 128 == 0 else 64))
-        return max(1, min(rows // 128, (512 + tiles - 1) // tiles))
-    tiles = ((n + 63) // 64) * ((k + 63) // 64)
-    return max(1, min(rows // 128, (1024 + tiles - 1) // tiles))
+    """row ranges of a weight gradient launched on its own (csrc/mdx_fast.cpp splits_for): enough to fill the chip, each >= 128 rows"""
+    return _fast().splits_for(rows, n, k, bool(half))
 
 
 def _rows(t):
     """device matrix (fp32 or float16 container) whose rows are contiguous (row stride arbitrary: column slices of a weight stay views)."""
-    _lib._need_gpu(t)
-    t = t.detach()
-    if t.dtype not in (torch.float32, torch.float16):
-        t = t.float()
-    return t if t.stride(-1) == 1 else t.contiguous()
-
-
-class _Linear(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, b, addend, keep32):
-        xc, wc = _rows(x), _rows(w)
-        if _AMP is None and xc.dtype != torch.float32:
-            xc = xc.float()
-        ctx.save_for_backward(xc, wc)
-        ctx.has_bias, ctx.has_addend = b is not None, addend is not None
-        ctx.b_ref = b.detach() if b is not None else None      # (a view of the parameter: only its address is used, see grad_sink)
-        ctx.x_dtype = x.dtype
-        ctx.addend_dtype = addend.dtype if addend is not None else None
-        ctx.prec = _AMP     # the backward of this layer runs in the forward's precision
-        bc = _c(b) if b is not None else None
-        ac = None
-        if addend is not None:
-            ac = _rows(addend) if _AMP is not None else _c(addend)
-        if linear_rows_ok(xc, wc.shape[0], wc.shape[1], ac):
-            return linear_rows(xc, wc, False, bc, ac)
-        return sgemm_nt(xc, wc, bc, addend=ac, keep32=keep32)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, w = ctx.saved_tensors
-        gy = _t(gy) if ctx.prec is not None else _c(gy)
-        gx = gw = gb = None
-        want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        with precision(ctx.prec):
-            if ctx.needs_input_grad[0]:
-                if linear_rows_ok(gy, w.shape[1], w.shape[0]):
-                    gx = linear_rows(gy, w, True)                     # (M,N) @ (N,K), the weight read transposed by the pack
-                else:                                                 # (M,N) @ (K,N)^T; the gradient lives in x's container type
-                    gx = sgemm_nt(gy, transpose(w), out_dtype=x.dtype if ctx.prec is not None else None)
-                if gx.dtype != ctx.x_dtype:
-                    gx = gx.to(ctx.x_dtype)
-            if ctx.needs_input_grad[1]:
-                dst_w = _sink_dst(w)
-                dst_b = _sink_dst(ctx.b_ref) if want_b else None
-                if dst_w is not None and (not want_b or dst_b is not None):
-                    sgemm_tn(gy, x, _splits_for(x.shape[0], gy.shape[1], x.shape[1], _h(gy) and _h(x) and _AMP is not None and _AMP[0] == 2), want_bias=want_b,
-                             defer=(dst_w, w.stride(0), dst_b))              # summed into the flat gradient buffer at flush time
-                else:
-                    r = sgemm_tn(gy, x, _splits_for(x.shape[0], gy.shape[1], x.shape[1], _h(gy) and _h(x) and _AMP is not None and _AMP[0] == 2), want_bias=want_b)
-                    gw, gb = r if want_b else (r, None)
-            elif want_b:
-                gb = colreduce(gy.float() if gy.dtype != torch.float32 else gy)
-        ga = None
-        if ctx.has_addend and ctx.needs_input_grad[3]:
-            ga = gy if gy.dtype == ctx.addend_dtype else gy.to(ctx.addend_dtype)
-        return gx, gw, gb, ga, None
+    return _fast().rows(t.detach())
 
 
 def linear(x, w, b=None, addend=None, keep32=False):
@@ -493,177 +346,33 @@ def linear(x, w, b=None, addend=None, keep32=False):
     (used for the per-node part of a layer whose reference input is a concatenation [edge part | node part | time]).
     keep32: the result is itself such a partial sum -- an autocast mode must not round it (the reference rounds the WHOLE layer's
     result once)."""
-    F = _cpp()
-    if F is not None and F.linear_fast_ok(x, w, b):
-        return F.linear(x, w, b, addend, bool(keep32))
-    return _Linear.apply(x, w, b, addend, keep32)
-
-
-class _LnRelu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, relu):
-        xc, g, b = _t(x), _c(gamma), _c(beta)
-        M, F = xc.shape
-        ctx.x_dtype = x.dtype
-        if F not in (32, 64, 128, 256):     # the half kernels cover the widths the networks use
-            xc = xc.float()
-        # the only consumers of a LayerNorm result are Linears, which round their operand to half anyway: a half container is exact
-        y = torch.empty(M, F, dtype=(_store_dtype() if (_AMP is not None and F in (32, 64, 128, 256)) else torch.float32), device=xc.device)
-        stats = torch.empty(M, 2, dtype=torch.float32, device=xc.device)
-        check(_L().mdx_op_ln_relu_fwd_t(ptr(xc), ptr(g), ptr(b), M, F, int(relu), ptr(y), ptr(stats), _h(xc) | (_h(y) << 1), stream()))
-        ctx.save_for_backward(xc, g, b, stats)
-        ctx.relu = int(relu)
-        ctx.gb_ref = (gamma.detach(), beta.detach())
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, g, b, stats = ctx.saved_tensors
-        gy = _t(gy)
-        M, F = x.shape
-        if F not in (32, 64, 128, 256):
-            gy = gy.float()
-        dx = torch.empty_like(x)
-        ws = torch.empty(_L().mdx_op_ln_relu_bwd_ws(M, F) // 4 + 1, dtype=torch.float32, device=x.device)
-        dst_g, dst_b = _sink_dst(ctx.gb_ref[0]), _sink_dst(ctx.gb_ref[1])
-        defer = dst_g is not None and dst_b is not None and M > 0 and ws.data_ptr() % 16 == 0
-        dgb = None if defer else torch.empty(2 * F, dtype=torch.float32, device=x.device)
-        check(_L().mdx_op_ln_relu_bwd_t(ptr(gy), ptr(x), ptr(stats), ptr(g), ptr(b), M, F, ctx.relu, ptr(dx), ptr(dgb), ptr(ws),
-                                        _h(gy) | (_h(x) << 1) | (_h(dx) << 2), stream()))
-        dx = dx if dx.dtype == ctx.x_dtype else dx.to(ctx.x_dtype)
-        if defer:       # [dgamma | dbeta] partial rows stay in ws: summed into the flat gradient buffer at flush time
-            rows = int(_L().mdx_op_ln_relu_bwd_rows(M))
-            _sink_record(ws.data_ptr(), dst_g, rows, 1, F, F, 2 * F, 0, ws)
-            _sink_record(ws.data_ptr() + 4 * F, dst_b, rows, 1, F, F, 2 * F, 0, ws)
-            return dx, None, None, None
-        return dx, dgb[:F], dgb[F:], None
+    return _fast().linear(x, w, b, addend, bool(keep32))
 
 
 def ln_relu(x, gamma, beta, relu=True):
-    return _LnRelu.apply(x, gamma, beta, relu)
-
-
-class _StageCtx:
-    """What _Linear / _LnRelu use of an autograd context, so that their backward bodies can run as the two halves of _LinearLnRelu's."""
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-
-_LN_OK = {}
+    return _fast().ln_relu(x, gamma, beta, bool(relu))
 
 
 def linear_ln_ok(x, w, addend):
     """Can Linear(x) -> LayerNorm -> ReLU take the fused launch (csrc mdx_op_xgemm_nt_ln_t)?  float16 mode, float16 rows of x, widths
     the row-owner kernel is built for."""
-    if _AMP is None or _AMP[0] != 2 or x.dtype != torch.float16 or x.dim() != 2 or _store_dtype() != torch.float16:
-        return False
-    M, K = x.shape
-    N = w.shape[0]
-    key = (M >= 1024, N, K)
-    r = _LN_OK.get(key)
-    if r is None:
-        r = _LN_OK[key] = _L().mdx_op_xgemm_nt_ln_supported(M, N, K) == 1
-    return (r and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and w.stride(1) == 1
-            and (addend is None or (addend.dim() == 2 and addend.stride(1) == 1)))
-
-
-class _LinearLnRelu(torch.autograd.Function):
-    """relu(LayerNorm(Linear(x) + addend)) as one launch forward (the LayerNorm runs in the GEMM's epilogue, csrc hgemm_nt_rows_kernel
-    <.., LN>): the first two layers of every common.MLP (reference models/common.py:191-196).  The Linear's result and the row
-    statistics are stored for the backward, which is the LayerNorm's backward followed by the Linear's -- the bodies of _LnRelu and
-    _Linear, unchanged."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, addend, gamma, beta):
-        xc, wc = _rows(x), _rows(w)
-        M, K = xc.shape
-        N = wc.shape[0]
-        bc = _c(b) if b is not None else None
-        ac = _rows(addend) if addend is not None else None
-        g, bt = _c(gamma), _c(beta)
-        pre = torch.empty(M, N, dtype=torch.float16, device=xc.device)
-        post = torch.empty(M, N, dtype=torch.float16, device=xc.device)
-        stats = torch.empty(M, 2, dtype=torch.float32, device=xc.device)
-        check(_L().mdx_op_xgemm_nt_ln_t(ptr(xc), xc.stride(0), ptr(wc), wc.stride(0), ptr(bc), ptr(ac), ac.stride(0) if ac is not None else 0,
-                                        ptr(pre), N, ptr(g), ptr(bt), ptr(post), N, ptr(stats), 1, M, N, K, _AMP[0], 1,
-                                        1 | (_h(ac) << 1) | 4 | 8, stream()))
-        lin, ln = _StageCtx(), _StageCtx()
-        lin.save_for_backward(xc, wc)
-        lin.has_bias, lin.has_addend = b is not None, addend is not None
-        lin.b_ref = b.detach() if b is not None else None
-        lin.x_dtype, lin.addend_dtype, lin.prec = x.dtype, (addend.dtype if addend is not None else None), _AMP
-        ln.save_for_backward(pre, g, bt, stats)
-        ln.relu, ln.x_dtype, ln.gb_ref = 1, torch.float16, (gamma.detach(), beta.detach())
-        ctx.lin, ctx.ln = lin, ln
-        return post
-
-    @staticmethod
-    def backward(ctx, gy):
-        need = ctx.needs_input_grad                       # x, w, b, addend, gamma, beta
-        lin, ln = ctx.lin, ctx.ln
-        ln.needs_input_grad = (True, need[4], need[5], False)
-        gpre, gg, gb_, _ = _LnRelu.backward(ln, gy)
-        lin.needs_input_grad = (need[0], need[1], need[2], need[3], False)
-        gx, gw, gb, ga, _ = _Linear.backward(lin, gpre)
-        ctx.lin = ctx.ln = None
-        return gx, gw, gb, ga, gg, gb_
+    return _fast().linear_ln_ok(x, w, addend)
 
 
 def linear_ln_relu(x, w, b, gamma, beta, addend=None):
     """relu(LayerNorm(x @ w.T + b + addend)): one launch where the fused kernel is built, the two operators otherwise"""
-    if linear_ln_ok(x, w, addend):
-        F = _cpp()
-        if F is not None and F.linear_ln_fast_ok(x, w, b, gamma, beta):
-            return F.linear_ln_relu(x, w, b, addend, gamma, beta)
-        return _LinearLnRelu.apply(x, w, b, addend, gamma, beta)
-    return ln_relu(linear(x, w, b, addend=addend), gamma, beta, True)
+    return _fast().linear_ln_relu(x, w, b, addend, gamma, beta)
 
 
 def linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2):
-    """linear(relu(LayerNorm(x @ w.T + b)), w2, b2) with w2 of ONE row -- common.MLP(…, 1) as PosUpdate's inter module uses it.  On the
-    C++ fast path (float16 mode inside a sink) one node whose backward forms the second Linear's rank-1 data gradient inside the LayerNorm
-    backward (csrc mdx_op_ln_relu_bwd_r1_t); otherwise the two operators."""
-    F = _cpp()
-    if (F is not None and b is not None and b2 is not None and linear_ln_ok(x, w, None)
-            and F.linear_ln_dot_fast_ok(x, w, b, gamma, beta, w2, b2)):
-        return F.linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2)
-    return linear(linear_ln_relu(x, w, b, gamma, beta), w2, b2)
-
-
-class _Ew(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, op, a, b):
-        ctx.dtypes = (a.dtype, b.dtype)
-        ac, bc = _same(a, b)
-        assert ac.shape == bc.shape, (ac.shape, bc.shape)
-        out = torch.empty_like(ac)
-        rk = _round_kind() if op in (MUL, GATE) else 0     # autocast: a product of two half tensors is a half tensor
-        check(_L().mdx_op_ew_fwd_t(op | (rk << 8), ptr(ac), ptr(bc), ptr(out), ac.numel(), _h(ac) | (_h(bc) << 1) | (_h(out) << 2), stream()))
-        ctx.op = op
-        ctx.save_for_backward(ac, bc)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        g = _t(g)
-        da = torch.empty_like(a) if ctx.needs_input_grad[1] else None
-        db = torch.empty_like(b) if ctx.needs_input_grad[2] else None
-        check(_L().mdx_op_ew_bwd_t(ctx.op, ptr(a), ptr(b), ptr(g), ptr(da), ptr(db), a.numel(),
-                                   _h(a) | (_h(b) << 1) | (_h(g) << 2) | (_h(da) << 3) | (_h(db) << 4), stream()))
-        if da is not None and da.dtype != ctx.dtypes[0]:
-            da = da.to(ctx.dtypes[0])
-        if db is not None and db.dtype != ctx.dtypes[1]:
-            db = db.to(ctx.dtypes[1])
-        return None, da, db
+    """linear(relu(LayerNorm(x @ w.T + b)), w2, b2) with w2 of ONE row -- common.MLP(…, 1) as PosUpdate's inter module uses it.  In the
+    float16 sink one node whose backward forms the second Linear's rank-1 data gradient inside the LayerNorm backward (csrc
+    mdx_op_ln_relu_bwd_r1_t); otherwise the two operators."""
+    return _fast().linear_ln_relu_dot(x, w, b, gamma, beta, w2, b2)
 
 
 def _ew(op, a, b):
-    F = _cpp()
-    if F is not None and a.is_cuda and F.fast_mode():
-        return F.ew(op, a, b)
-    return _Ew.apply(op, a, b)
+    return _fast().ew(op, a, b)
 
 
 def add(a, b):
@@ -853,7 +562,7 @@ class _EdgeGeom(torch.autograd.Function):
         with precision(ctx.prec):
             gl, gr = _segsum_raw(g, ctx.pl), _segsum_raw(g, ctx.pr)
         out = torch.empty_like(gl)
-        check(_L().mdx_op_ew_fwd(SUB, ptr(gl), ptr(gr), ptr(out), gl.numel(), stream()))
+        check(_L().mdx_op_ew_fwd_t(SUB, ptr(gl), ptr(gr), ptr(out), gl.numel(), 0, stream()))
         return out, None, None
 
 
@@ -977,11 +686,11 @@ def _fused_backward(ctx, n_in, bwd):
     bwd(F, needs_input_grad, dispose) calls the operator's F.*_bwd, in the precision of the forward."""
     ni, ps = ctx.needs_input_grad, ctx.ps
     with precision(ctx.prec):
-        F = _cpp()
-        if F is not None and F.all_in_sink(ps):
+        F = _fast()
+        if _CPP_NODES and F.all_in_sink(ps):
             g, pgrads = bwd(F, ni, True), [None] * len(ps)
         else:
-            g, contractions, lnp, slices = bwd(_fast(), ni, False)
+            g, contractions, lnp, slices = bwd(F, ni, False)
             pgrads = _fused_param_grads(ps, ni[n_in:], contractions, lnp, slices)
     gx = g[0]
     if gx is not None and gx.dtype != ctx.x_dtype:

@@ -329,14 +329,21 @@ def test_linear_with_layernorm_epilogue_equals_the_two_operators(K, N, addend_ki
         a = None if a0 is None else a0.detach().clone().requires_grad_(True)
         with T.precision('fp16'):
             assert T.linear_ln_ok(x, w, a)
+            # the nodes are C++ (csrc/mdx_fast.cpp) and do not show what they saved: the Linear's stored result and the row statistics
+            # come from the functions their forwards are made of, which repeat the same launch on the same operands
             if fused:
                 y = T.linear_ln_relu(x, w, b, gm, be, addend=a)
-                assert y.grad_fn.name().startswith('_LinearLnRelu')
-                pre, stats = y.grad_fn.ln.saved_tensors[0], y.grad_fn.ln.saved_tensors[3]
+                assert 'LinearLnReluFn' in y.grad_fn.name()
+                post, pre, stats = T._fast().linear_ln_fwd(x.detach(), w.detach(), b.detach(), None if a is None else a.detach(), gm.detach(),
+                                                           be.detach())
+                assert torch.equal(post, y)
             else:
                 pre_t = T.linear(x, w, b, addend=a)
                 y = T.ln_relu(pre_t, gm, be, True)
-                pre, stats = pre_t.detach(), y.grad_fn.saved_tensors[3]
+                assert 'LnReluFn' in y.grad_fn.name() and 'Linear' not in y.grad_fn.name()
+                post, stats = T._fast().ln_relu_fwd(pre_t.detach(), gm.detach(), be.detach(), True)
+                assert torch.equal(post, y)
+                pre = pre_t.detach()
             y.backward(gy)
         res.append(dict(y=y.detach(), pre=pre, stats=stats, gx=x.grad, gw=w.grad, gb=b.grad, gg=gm.grad, gbe=be.grad,
                         ga=None if a is None else a.grad))

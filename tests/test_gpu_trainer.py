@@ -513,13 +513,13 @@ def test_fused_categorical_loss_equals_the_torch_tail():
 
 @pytest.mark.parametrize('fused_rows', [1024, 1])
 def test_cpp_nodes_are_bit_identical_to_the_python_bodies(fused_rows):
-    """Round 6: csrc/mdx_fast.cpp (moldiff_amd/_mdx_fast.so) holds the training operators' host logic in C++ -- Linear / Linear+LayerNorm
-    / element-wise autograd nodes, the route by which the fused operators' parameter gradients reach the sink -- next to the gradient
-    sink and weight-gradient queue it alone implements.  With train_ops._CPP_NODES off, the Python Linear / LayerNorm / element-wise
-    bodies and the Python route of the fused operators' parameter gradients run instead (the fused operators' launch code is shared:
-    nothing to compare there).  Same kernels, same buffers, same row ranges: the loss, the flat gradient buffer and the updated weights
-    of two optimisation steps must be BIT-identical with the C++ nodes on and off (fused_rows = 1: with the fused row-owner kernels
-    forced on at this size, so both routes of their parameter gradients run)."""
+    """Round 6: csrc/mdx_fast.cpp (moldiff_amd/_mdx_fast.so) holds the training operators' host logic in C++.  The Linear / LayerNorm /
+    element-wise nodes have no Python body any more; train_ops._CPP_NODES selects only the route by which the fused row-owner operators'
+    parameter gradients leave a backward in the float16 sink: queued and recorded by the C++ side (on), or handed back as tensors and
+    deferred one by one through train_ops._fused_param_grads (off; the fused operators' launch code is shared: nothing to compare
+    there).  Same kernels, same buffers, same row ranges: the loss, the flat gradient buffer and the updated weights of two optimisation
+    steps must be BIT-identical with the switch on and off (fused_rows = 1: with the fused row-owner kernels forced on at this size, so
+    both routes run; fused_rows = 1024: no fused operator runs at this size and the switch selects nothing)."""
     import copy
     from moldiff_amd import train_ops
     base = U.moldiff('MolDiff', DEV)
@@ -584,3 +584,177 @@ def test_fused_categorical_add_noise_equals_the_torch_composition():
         assert float((~same).float().mean()) <= 1e-3, float((~same).float().mean())
         assert torch.equal(oh0[same], oh1[same]) and torch.equal(lvt0[same], lvt1[same])
         assert bool((oh1.sum(-1) == 1).all())
+
+
+def _le(name, got, ref, bound):
+    """every element of |got - ref| <= bound (float64)"""
+    err = (got.detach().double() - ref).abs()
+    bound = torch.as_tensor(bound, dtype=torch.float64, device=err.device).expand_as(err)
+    assert got.shape == ref.shape and bool(torch.isfinite(got).all()), name
+    assert bool((err <= bound).all()), (name, float((err - bound).max()), float(ref.abs().max()))
+
+
+def _relmax(name, got, ref, tol):
+    """tests/test_gpu_train_ops.py `_rel(got, ref) < tol`: the largest error relative to the largest reference value"""
+    r = float((got.detach().double() - ref).abs().max() / ref.abs().max().clamp(min=1e-12))
+    assert got.shape == ref.shape and r < tol, (name, r, tol)
+
+
+@pytest.mark.parametrize('kind', ['f32', 'bf16', 'fp16', 'fp16_f32store', 'bf16_autocast'])
+def test_cpp_operator_nodes_serve_every_mode_and_gradient_route(kind):
+    """The Linear / LayerNorm / Linear+LayerNorm+ReLU / element-wise nodes of csrc/mdx_fast.cpp are the only host bodies of these
+    operators: they run in every precision mode, and their parameter gradients leave a backward by whichever route applies -- (a) no
+    sink: returned to autograd; (b) a sink over every parameter: queued (float16 kind) or recorded; (c) a sink over the first Linear
+    only: both at once.  Chain: linear 80 -> 64 (80 is not tile-aligned: the converting weight-gradient kernel) -> ln_relu -> mul with a
+    second input -> linear_ln_relu 64 -> 64 -> linear 64 -> 1 (the rank-1 case) on 300 rows (two row ranges of >= 128), plus a sub on a
+    (7, 5) pair (the scalar element-wise kernels).  Leaf inputs lie on a 1/32 grid below 8: exact in float16 and in bfloat16.
+
+    1. The library launch counter of the extension advances on every route; the outputs of the three routes are bit-identical; (a) with
+       linear_ln_relu equals (a) with linear and ln_relu called one after the other, bit for bit (300 rows: the fused launch is not built).
+    2. Route (a) against float64, operator by operator of the chain: each operator's output and each of its gradients against the float64
+       restatement of THAT operator on the tensors the library handed it (its inputs in their containers, its upstream gradient), rounded
+       as the mode rounds them; the gradient an operator hands upstream is the next check's input, so every parameter and input gradient
+       of the chain is pinned.  Bounds, verbatim from the tests of the same mode and operator (r = rounding to the mode's half type):
+         Linear  f32            test_gpu_train_ops.test_linear_forward_and_all_gradients: relative to the largest value, y 2e-6, gx 2e-6,
+                                gw 5e-6, gb 5e-6
+                 bf16           test_gpu_train_ops.test_bf16_operand_linear_equals_fp32_gemm_of_bf16_rounded_operands, on r(x), r(w), r(gy)
+                                (the bias gradient sums r(gy) there too): 3e-6, 3e-6, 1e-5, 1e-5
+                 fp16 modes     y, gx: |ref| 2^-10 + 1e-3 per element (test_gpu_train_ops.test_float16_linear_on_many_rows_is_the_row_owner_
+                                kernel_and_equals_the_tile_kernel); gw: |ref| 2^-10 + 2^-24 + 2e-6 max(|g|^T |x|), gb the same with the
+                                largest column sum of |g| (test_gpu_train_ops.test_float16_weight_gradient_by_lds_transpose_reads; it
+                                holds 'fp16_f32store' to 'fp16' by the same bound)
+                 bf16_autocast  no test of this mode exists in either file: the fp16 bounds with float16's ulp 2^-10 replaced by
+                                bfloat16's 2^-7 (8 significant bits against 11), nothing else changed
+         LayerNorm              test_gpu_train_ops.test_layernorm_relu: 5e-6 of the largest value for y, 2e-5 for dx, dgamma, dbeta; where
+                                the result lives in a float16 container plus one rounding point 2^-11 |ref| + 2^-25
+                                (test_gpu_typed_ops, rounding model in its docstring and test_layernorm_relu_in_float16_containers)
+         mul, sub  fp32 arithmetic (f32, bf16; sub in every mode): test_gpu_train_ops.test_elementwise_pairs, out 1e-6, gradients 2e-6
+                   autocast modes, mul (test_gpu_typed_ops._ew_model / _ew_assert): all operands float16 containers -> out, da, db EQUAL
+                   the float64 product rounded to float16; else fp32 product 2e-6 |ref|, plus one rounding point where the result is
+                   rounded (out: to the mode's half type, 2^-11 resp. 2^-8 |ref|, + 2^-25; a gradient: only by a float16 container)
+    3. The gradients of (b) and (c) agree with (a) as test_deferred_gradient_sink_equals_autograd_accumulation demands of the whole model:
+       bit for bit in 'f32'; elsewhere within one rounding of the element's sum in another order, 2^-10 |g| + 2^-20 max |g|."""
+    import contextlib
+    import torch.nn.functional as F
+    from moldiff_amd import train_ops as T
+    g = U.rng(77)
+    grid = lambda *s: U.t32(np.clip(np.round(g.standard_normal(s) * 32), -255, 255) / 32).to(DEV)
+    init = dict(w1=g.standard_normal((64, 80)) * 80 ** -0.5, b1=g.standard_normal(64) * 0.1, g1=1 + 0.1 * g.standard_normal(64),
+                be1=0.1 * g.standard_normal(64), w2=g.standard_normal((64, 64)) * 0.125, b2=g.standard_normal(64) * 0.1,
+                g2=1 + 0.1 * g.standard_normal(64), be2=0.1 * g.standard_normal(64), w3=g.standard_normal((1, 64)) * 0.125,
+                b3=g.standard_normal(1) * 0.1)
+    x0, z0, gy = grid(300, 80), grid(300, 64), grid(300, 1)
+    p0, q0, gp = grid(7, 5), grid(7, 5), grid(7, 5)
+
+    class First(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w1, self.b1 = (torch.nn.Parameter(U.t32(init[k])) for k in ('w1', 'b1'))
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.first = First()
+            for k in ('g1', 'be1', 'w2', 'b2', 'g2', 'be2', 'w3', 'b3'):
+                setattr(self, k, torch.nn.Parameter(U.t32(init[k])))
+
+    def run(route, split=False):
+        net = Net().to(DEV)
+        flat = FlatParams(net.first if route == 'c' else net)
+        for p in net.parameters():
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        x, z, p, q = (t.clone().requires_grad_(True) for t in (x0, z0, p0, q0))
+        f = net.first
+        n0 = T._fast().launches()
+        with (contextlib.nullcontext() if route == 'a' else T.grad_sink(flat)):
+            with T.precision(kind):
+                h1 = T.linear(x, f.w1, f.b1)
+                h2 = T.ln_relu(h1, net.g1, net.be1)
+                zc = z.to(h2.dtype)
+                h3 = T.mul(h2, zc)
+                if split:
+                    h4 = T.linear(h3, net.w2, net.b2)
+                    h5 = T.ln_relu(h4, net.g2, net.be2, True)
+                else:
+                    h4, h5 = None, T.linear_ln_relu(h3, net.w2, net.b2, net.g2, net.be2)
+                y = T.linear(h5, net.w3, net.b3)
+                e = T.sub(p, q)
+            mid = dict(h1=h1, h2=h2, zc=zc, h3=h3, h4=h4, h5=h5)
+            for t in mid.values():
+                if t is not None:
+                    t.retain_grad()
+            torch.autograd.backward([y, e], [gy.to(y.dtype), gp.to(e.dtype)])
+            T.flush_grad_sink()
+        assert T._fast().launches() - n0 >= 15, (kind, route)              # the C++ bodies ran: 7 launches forward, 10 or more backward
+        grads = [t.grad.detach().float().clone() for t in list(net.parameters()) + [x, z, p, q]]
+        return [y.detach().clone(), e.detach().clone()], grads, dict(mid, net=net, x=x, z=z, p=p, q=q, y=y, e=e)
+
+    # ---- 1. routes and shells ----
+    out_a, grad_a, _ = run('a')
+    out_s, grad_s, t = run('a', split=True)
+    assert all(bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0 for v in out_a + grad_a)
+    assert all(torch.equal(u, v) for u, v in zip(out_a + grad_a, out_s + grad_s))
+
+    # ---- 2. route (a) against float64, operator by operator ----
+    amp = T.KINDS[kind]
+    hk, auto = (amp[0], amp[1]) if amp is not None else (0, False)
+    half_t = {0: None, 1: torch.bfloat16, 2: torch.float16}[hk]
+    d = lambda v: v.detach().double()
+    r = (lambda v: d(v)) if hk == 0 else (lambda v: v.detach().to(half_t).double())
+    ulp, point = {0: 0.0, 1: 2.0 ** -7, 2: 2.0 ** -10}[hk], {0: 0.0, 1: 2.0 ** -8, 2: 2.0 ** -11}[hk]
+    f16 = lambda v: v.dtype == torch.float16
+    net = t['net']
+
+    def check_linear(name, X, W, b, G, Y, gX, gW, gb):
+        Xr, Wr, Gr = r(X), r(W), r(G)
+        ref = dict(y=Xr @ Wr.t() + d(b), gx=Gr @ Wr, gw=Gr.t() @ Xr, gb=Gr.sum(0))
+        got = dict(y=Y, gx=gX, gw=gW, gb=gb)
+        if not auto:
+            for k, tol in zip(('y', 'gx', 'gw', 'gb'), (2e-6, 2e-6, 5e-6, 5e-6) if hk == 0 else (3e-6, 3e-6, 1e-5, 1e-5)):
+                _relmax(f'{name}.{k}', got[k], ref[k], tol)
+        else:
+            _le(f'{name}.y', Y, ref['y'], ref['y'].abs() * ulp + 1e-3)
+            _le(f'{name}.gx', gX, ref['gx'], ref['gx'].abs() * ulp + 1e-3)
+            _le(f'{name}.gw', gW, ref['gw'], ref['gw'].abs() * ulp + 2.0 ** -24 + 2e-6 * float((Gr.abs().t() @ Xr.abs()).max()))
+            _le(f'{name}.gb', gb, ref['gb'], ref['gb'].abs() * ulp + 2.0 ** -24 + 2e-6 * float(Gr.abs().sum(0).max()))
+
+    def check_ln(name, X, gam, bet, G, Y, dX, dgam, dbet):
+        x64, g64, b64 = (d(v).requires_grad_(True) for v in (X, gam, bet))
+        y64 = F.relu(F.layer_norm(x64, (X.shape[1],), g64, b64, 1e-5))
+        y64.backward(d(G))
+        for k, got, ref, tol in (('y', Y, y64.detach(), 5e-6), ('dx', dX, x64.grad, 2e-5), ('dgamma', dgam, g64.grad, 2e-5),
+                                 ('dbeta', dbet, b64.grad, 2e-5)):
+            _le(f'{name}.{k}', got, ref, tol * float(ref.abs().max()) + ((2.0 ** -11 * ref.abs() + 2.0 ** -25) if f16(got) else 0.0))
+
+    def check_mul(name, A, B, G, out, dA, dB):
+        a, b, gg = d(A), d(B), d(G)
+        if not auto:
+            _relmax(f'{name}.out', out, a * b, 1e-6), _relmax(f'{name}.da', dA, gg * b, 2e-6), _relmax(f'{name}.db', dB, gg * a, 2e-6)
+            return
+        for k, got, ref, factors, rounded in (('out', out, a * b, (A, B), True), ('da', dA, gg * b, (G, B), f16(dA)),
+                                              ('db', dB, gg * a, (G, A), f16(dB))):
+            if all(f16(v) for v in factors) and f16(got):
+                assert torch.equal(got.detach(), ref.half()), (name, k)
+            else:
+                pt = (point if k == 'out' else 2.0 ** -11) * ref.abs() + 2.0 ** -25
+                _le(f'{name}.{k}', got, ref, 2e-6 * ref.abs() + (pt if rounded else 0.0))
+
+    check_linear('linear1', t['x'], net.first.w1, net.first.b1, t['h1'].grad, t['h1'], t['x'].grad, net.first.w1.grad, net.first.b1.grad)
+    check_ln('ln1', t['h1'], net.g1, net.be1, t['h2'].grad, t['h2'], t['h1'].grad, net.g1.grad, net.be1.grad)
+    check_mul('mul', t['h2'], t['zc'], t['h3'].grad, t['h3'], t['h2'].grad, t['zc'].grad)
+    assert torch.equal(t['z'].grad, t['zc'].grad.float())
+    check_linear('linear2', t['h3'], net.w2, net.b2, t['h4'].grad, t['h4'], t['h3'].grad, net.w2.grad, net.b2.grad)
+    check_ln('ln2', t['h4'], net.g2, net.be2, t['h5'].grad, t['h5'], t['h4'].grad, net.g2.grad, net.be2.grad)
+    check_linear('linear3', t['h5'], net.w3, net.b3, gy.to(t['y'].dtype), t['y'], t['h5'].grad, net.w3.grad, net.b3.grad)
+    _relmax('sub.out', t['e'], d(p0) - d(q0), 1e-6), _relmax('sub.da', t['p'].grad, d(gp), 2e-6), _relmax('sub.db', t['q'].grad, -d(gp), 2e-6)
+
+    # ---- 3. the sink routes against (a) ----
+    for route in ('b', 'c'):
+        out, grad, _ = run(route)
+        assert all(torch.equal(u, v) for u, v in zip(out, out_a)), (kind, route)
+        for i, (u, v) in enumerate(zip(grad, grad_a)):
+            if kind == 'f32':
+                assert torch.equal(u, v), (kind, route, i)
+            else:
+                assert bool(((u - v).abs() <= 2.0 ** -10 * v.abs() + 2.0 ** -20 * float(v.abs().max())).all()), (kind, route, i)

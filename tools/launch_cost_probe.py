@@ -31,8 +31,8 @@ def main():
     o = torch.empty(64, device=dev)
     pa, pb, po = a.data_ptr(), b.data_ptr(), o.data_ptr()
     st = _lib.stream()
-    print('raw C-ABI call, tiny element-wise launch (hipLaunchKernel + ctypes): %.2f us' % per_call(lambda: L.mdx_op_ew_fwd(0, pa, pb, po, 64, st)))
-    print('  + stream() + check():                                             %.2f us' % per_call(lambda: _lib.check(L.mdx_op_ew_fwd(0, pa, pb, po, 64, _lib.stream()))))
+    print('raw C-ABI call, tiny element-wise launch (hipLaunchKernel + ctypes): %.2f us' % per_call(lambda: L.mdx_op_ew_fwd_t(0, pa, pb, po, 64, 0, st)))
+    print('  + stream() + check():                                             %.2f us' % per_call(lambda: _lib.check(L.mdx_op_ew_fwd_t(0, pa, pb, po, 64, 0, _lib.stream()))))
     print('torch.empty(64):                                                     %.2f us' % per_call(lambda: torch.empty(64, device=dev)))
     print('torch.empty(154666, 256, half):                                      %.2f us' % per_call(lambda: torch.empty(154666, 256, dtype=torch.float16, device=dev), 5000))
     print('torch add (a + b), tiny:                                             %.2f us' % per_call(lambda: a + b))

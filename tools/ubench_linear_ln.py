@@ -34,7 +34,7 @@ def main():
         w = torch.randn(N, K, device=dev) * K ** -0.5
         b, g, be = torch.randn(N, device=dev), torch.rand(N, device=dev) + 0.5, torch.randn(N, device=dev)
         with torch.no_grad(), T.precision('fp16'):
-            tf = timed(lambda: T._LinearLnRelu.apply(x, w, b, None, g, be))
+            tf = timed(lambda: T.linear_ln_relu(x, w, b, g, be))
             pre = T.linear(x, w, b)
             tl = timed(lambda: T.linear(x, w, b))
             tn = timed(lambda: T.ln_relu(pre, g, be, True))
