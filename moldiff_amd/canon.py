@@ -22,15 +22,12 @@ rank vector among those, and ``orbit[v]`` is the smallest atom found at rank[v] 
     python -m moldiff_amd.canon stats samples_all.pt --out canon.npz [--ref] [--part finished]
     python -m moldiff_amd.canon compare a.npz b.npz
 """
-import argparse
-import json
 import sys
 
 import numpy as np
 
-from . import rings
-from .local3d import jsd_counts
-from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from . import molpack, rings
+from .molpack import DEFAULT_ATOMIC_NUMBERS, jsd_counts, mol_graph, to_host
 from .similarity import mix
 
 MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
@@ -43,9 +40,11 @@ STAT_KEYS = ('status', 'n_nodes', 'n_leaves', 'n_aut', 'canon_n_bonds')
 MOL_KEYS = STAT_KEYS + ('cert_hash', 'n_atoms', 'n_bonds')
 ATOM_KEYS = ('rank', 'orbit', 'canon_atom_type')                  # + canon_atom_label, canon_pos when the inputs were given
 BOND_KEYS = ('canon_bond_type',)                                  # + canon_bond_index (2, bonds)
+LAYOUT = molpack.Layout(MOL_KEYS, atom=ATOM_KEYS, bond=BOND_KEYS, index=('canon_bond_index',), pos=('canon_pos',),
+                        optional=('canon_atom_label',), int64=('cert_hash',))          # the results table
 NODE_BINS = 22                                                    # bin k: molecules whose n_nodes have bit length k
 FNV_OFFSET, FNV_PRIME = 0xcbf29ce484222325, 0x100000001b3
-SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+SYMBOL = molpack.ELEMENT_SYMBOL
 SMILES_VALENCES = {6: (4,), 7: (3, 5), 8: (2,), 9: (1,), 15: (3, 5), 16: (2, 4, 6), 17: (1,)}   # what a SMILES reader assumes
 _M = np.uint64(0xffffffff)
 
@@ -165,29 +164,13 @@ def canon_ref(info, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers
     return out
 
 
-def _keys(results):
-    """the per-atom and per-bond keys a results dict holds"""
-    atom = ATOM_KEYS + tuple(k for k in ('canon_atom_label', 'canon_pos') if k in results)
-    return atom, BOND_KEYS
-
-
 def stack_ref(mols, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers=DEFAULT_ATOMIC_NUMBERS):
     """``canon_ref`` of every molecule of a list as the results dict ``canon_mols`` returns (numpy): one entry per molecule of every
     key of MOL_KEYS (int32, cert_hash int64), the per-atom keys over the atoms and the per-bond keys over the bond slots of the list
     in turn (canon_bond_index (2, bonds)), ``atom_ptr`` and ``bond_ptr``.  atom_label: one array per molecule, or None.  ``canon_pos``
     is present when every molecule holds positions."""
-    positions = all('atom_pos' in m for m in mols)
     refs = [canon_ref(m, None if atom_label is None else atom_label[k], max_nodes, atomic_numbers) for k, m in enumerate(mols)]
-    out = {k: np.asarray([r[k] for r in refs], dtype=np.int64 if k == 'cert_hash' else np.int32).reshape(len(refs)) for k in MOL_KEYS}
-    atom = ATOM_KEYS + (('canon_atom_label',) if atom_label is not None else ())
-    for k in atom + BOND_KEYS:
-        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    if positions:
-        out['canon_pos'] = np.concatenate([r['canon_pos'] for r in refs] + [np.zeros((0, 3), dtype=np.float32)]).astype(np.float32)
-    out['canon_bond_index'] = np.concatenate([r['canon_bond_index'] for r in refs] + [np.zeros((2, 0), dtype=np.int32)], axis=1).astype(np.int32)
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    return molpack.stack(refs, LAYOUT, optional=LAYOUT.optional if atom_label is not None else ())
 
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
@@ -201,28 +184,21 @@ def launch(cm, max_nodes=DEFAULT_MAX_NODES, select=None, atom_label=None, positi
     import torch
     from . import _lib
     max_nodes = _check_nodes(max_nodes)
-    B, dev = cm.B, cm.device
-    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    stats, N, E = z(B, len(STAT_KEYS)), max(cm.N_cap, 1), max(cm.Eh_stride, 1)
-    out = {'cert_hash': torch.zeros(B, dtype=torch.int64, device=dev), 'rank': z(N), 'orbit': z(N), 'canon_atom_type': z(N),
-           'canon_bond_index': z(2, E), 'canon_bond_type': z(E)}
     pos = cm.atom_pos if positions else None
     if atom_label is not None:
         if atom_label.dtype != torch.int32 or atom_label.numel() < cm.N_cap:
             raise ValueError('atom_label is an int32 tensor in the layout of atom_type')
         atom_label = atom_label.contiguous()
-        out['canon_atom_label'] = z(N)
-    if pos is not None:
-        out['canon_pos'] = torch.zeros(N, 3, dtype=torch.float32, device=dev)
-    if B > 0:
+    out, stats = molpack.zeros_for(cm, LAYOUT, stat_keys=STAT_KEYS,
+                                   held=(LAYOUT.optional if atom_label is not None else ()) + (LAYOUT.pos if pos is not None else ()))
+    if cm.B > 0:
         ops, at = cm.operands()
         opt = lambda t: None if t is None else at(t)
         _lib.check(_lib.lib().mdx_mol_canon(
             *ops, _lib.ptr(select), opt(pos), opt(atom_label), max_nodes, at(out['rank']), at(out['orbit']), at(out['canon_atom_type']),
             opt(out.get('canon_atom_label')), opt(out.get('canon_pos')), at(out['canon_bond_index']), at(out['canon_bond_type']),
             at(stats), at(out['cert_hash']), _lib.stream()))
-    out.update({k: stats[:, c] for c, k in enumerate(STAT_KEYS)})
-    return out
+    return molpack.split_stats(out, stats, STAT_KEYS)
 
 
 def canonical_compact(cm, results, select=None):
@@ -244,37 +220,20 @@ def canon_mols(mols, device, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomi
     is packed densely, copied and handed to ``mdx_mol_canon``.  -> the results dict of ``stack_ref`` with device tensors.  atom_label:
     one array per molecule (checked here: int in [0, 65536)), or None."""
     import torch
-    device = torch.device(device)
     _check_nodes(max_nodes)
-    positions = all('atom_pos' in m for m in mols) and len(mols) > 0
-    p = pack_mols(mols, atomic_numbers, positions=positions)
+    p, cm = molpack.packed(mols, atomic_numbers, device, positions=True, simple=False)
     lab = None
     if atom_label is not None:
         if len(atom_label) != len(mols):
             raise ValueError('one label array per molecule')
         lab = np.concatenate([_check_label(a, int(n)) for a, n in zip(atom_label, p['n_atoms'])] + [np.zeros(0, dtype=np.int64)])
-        lab = torch.from_numpy(lab.astype(np.int32)).to(device)
-    cm = CompactMols.from_packed(to_device(p, device))
-    out = launch(cm, max_nodes, atom_label=lab)
-    total = int(p['n_bonds'].sum())
-    for k in _keys(out)[0]:
-        out[k] = out[k][:cm.N_cap]
-    if len(mols) == 0:
-        out['canon_pos'] = torch.zeros(0, 3, dtype=torch.float32, device=device)
-    out['canon_bond_type'], out['canon_bond_index'] = out['canon_bond_type'][:total], out['canon_bond_index'][:, :total]
-    out.update(n_atoms=cm.n_atoms, n_bonds=cm.n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-    return out
+        lab = torch.from_numpy(lab.astype(np.int32)).to(cm.device)
+    return molpack.dense(launch(cm, max_nodes, atom_label=lab), cm, p, LAYOUT)
 
 
 def concat(parts):
     """the results of consecutive batches (host or device arrays, not mixed) as one results dict"""
-    parts = [to_host(p) for p in parts]
-    atom, bond = _keys(parts[0])
-    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + atom + bond}
-    out['canon_bond_index'] = np.concatenate([p['canon_bond_index'] for p in parts], axis=1)
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    return molpack.concat(parts, LAYOUT)
 
 
 def empty():
@@ -285,13 +244,7 @@ def empty():
 
 def mol_result(results, m):
     """molecule `m` of a results dict with host arrays as the dict ``canon_ref`` returns"""
-    a0, na, b0, nb = (int(results[k][m]) for k in ('atom_ptr', 'n_atoms', 'bond_ptr', 'n_bonds'))
-    atom, bond = _keys(results)
-    out = {k: int(results[k][m]) for k in MOL_KEYS}
-    out.update({k: results[k][a0:a0 + na] for k in atom})
-    out.update({k: results[k][b0:b0 + nb] for k in bond})
-    out['canon_bond_index'] = results['canon_bond_index'][:, b0:b0 + nb]
-    return out
+    return molpack.mol_slice(results, m, LAYOUT)
 
 
 def certificate(results, m):
@@ -355,7 +308,7 @@ def novelty(results, reference_results):
 
 
 def compare(a, b):
-    """two results dicts -> dict: Jensen-Shannon divergence (``local3d.jsd_counts``) of ``nodes_hist``, both sides' ``uniqueness``
+    """two results dicts -> dict: Jensen-Shannon divergence (``molpack.jsd_counts``) of ``nodes_hist``, both sides' ``uniqueness``
     and ``mean_n_aut``, and the novelty of each side against the other by full certificate"""
     sa, sb = summary(a), summary(b)
     return {'nodes': jsd_counts(sa['nodes_hist'], sb['nodes_hist']), 'uniqueness': [sa['uniqueness'], sb['uniqueness']],
@@ -493,32 +446,12 @@ def smiles_mols(mols, results, device=None, tables=None):
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog='python -m moldiff_amd.canon', description=__doc__.split('\n\n')[0])
-    sub = ap.add_subparsers(dest='cmd', required=True)
-    s = sub.add_parser('stats', help='canonical labelling of the molecules stored in a samples_all.pt')
-    s.add_argument('samples')
-    s.add_argument('--out', required=True)
-    s.add_argument('--part', default='finished')
-    s.add_argument('--max_nodes', type=int, default=DEFAULT_MAX_NODES)
-    s.add_argument('--device', default='cuda:0')
-    s.add_argument('--ref', action='store_true', help='the Python path instead of the device')
-    c = sub.add_parser('compare', help='node-count divergence, uniqueness and mutual novelty of two files')
-    c.add_argument('a')
-    c.add_argument('b')
-    args = ap.parse_args(argv)
-    if args.cmd == 'stats':
-        mols = load_mols(args.samples, args.part)
-        if args.ref:
-            res = stack_ref(mols, max_nodes=args.max_nodes)
-        else:
-            import torch
-            torch.cuda.set_device(torch.device(args.device))
-            res = canon_mols(mols, args.device, max_nodes=args.max_nodes)
-        save_npz(res, args.out)
-        print(json.dumps(summary(res), indent=1))
-    else:
-        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
-    return 0
+    return molpack.stats_main(
+        argv, 'canon', __doc__, ('canonical labelling of the molecules stored in a samples_all.pt',
+                                 'node-count divergence, uniqueness and mutual novelty of two files'),
+        [('--max_nodes', dict(type=int, default=DEFAULT_MAX_NODES))],
+        lambda mols, a, dev: stack_ref(mols, max_nodes=a.max_nodes) if dev is None else canon_mols(mols, dev, max_nodes=a.max_nodes),
+        summary, compare)
 
 
 if __name__ == '__main__':

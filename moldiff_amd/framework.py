@@ -27,9 +27,8 @@ import sys
 
 import numpy as np
 
-from . import canon, rings
-from .local3d import jsd_counts
-from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, check_simple, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from . import canon, molpack, rings
+from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, jsd_counts, load_mols, load_npz, mol_graph, save_npz, to_host
 
 MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
 MODE_EXO, MODE_GENERIC = 1, 2
@@ -44,6 +43,7 @@ ATOM_KEYS = ('atom_role', 'atom_system', 'fw_atom_type', 'fw_atom_map', 'sys_ato
 BOND_KEYS = ('bond_role', 'fw_bond_type', 'sys_bond_type')                          # + fw_bond_index, sys_bond_index (2, bonds)
 INDEX_KEYS = ('fw_bond_index', 'sys_bond_index')
 POS_KEYS = ('fw_pos', 'sys_pos')
+LAYOUT = molpack.Layout(MOL_KEYS, atom=ATOM_KEYS, bond=BOND_KEYS, index=INDEX_KEYS, pos=POS_KEYS, wide=('sys_hist',))   # the results table
 KEY_OK, KEY_NONE, KEY_ABANDONED = 0, 1, 2          # a piece's key: there; the molecule was not measured; the canonical search gave up
 KEY_ARRAYS = ('fw_key_status', 'fw_hash', 'fw_cert_ptr', 'fw_cert', 'sys_mol', 'sys_key_status', 'sys_hash', 'sys_cert_ptr', 'sys_cert')
 STAT_BINS = 33                                     # the distributions of ``summary``: bin k = the value k, the last bin every larger one
@@ -159,35 +159,18 @@ def framework_ref(info, mode=0, sys_bins=DEFAULT_BINS, atomic_numbers=DEFAULT_AT
     return out
 
 
-def _keys(results):
-    """the per-atom keys a results dict holds"""
-    return ATOM_KEYS + tuple(k for k in POS_KEYS if k in results)
-
-
 def stack_ref(mols, mode=0, sys_bins=DEFAULT_BINS, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, num_bond_types=4):
     """``framework_ref`` of every molecule of a list as the results dict ``framework_mols`` returns (numpy int32): one entry (or row, for
     ``sys_hist``) per molecule of every key of MOL_KEYS, the per-atom keys over the atoms and the per-bond keys over the bond slots of
     the list in turn (the two index arrays (2, bonds)), ``atom_ptr`` and ``bond_ptr``.  ``sys_atom_ptr`` / ``sys_bond_ptr`` count from
     the start of the list, as on the device.  ``fw_pos`` / ``sys_pos`` are present when every molecule holds positions."""
     mode, sys_bins = _check(mode, sys_bins)
-    positions = all('atom_pos' in m for m in mols)
-    refs = [framework_ref(m, mode, sys_bins, atomic_numbers, num_bond_types) for m in mols]
-    out = {k: np.asarray([r[k] for r in refs], dtype=np.int32).reshape((len(refs), sys_bins) if k == 'sys_hist' else (len(refs),))
-           for k in MOL_KEYS}
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    for m, r in enumerate(refs):   # the records point into the list's arrays
-        k = int(r['n_systems'])
-        r['sys_atom_ptr'][:k] += out['atom_ptr'][m]
-        r['sys_bond_ptr'][:k] += out['bond_ptr'][m]
-    for k in ATOM_KEYS + BOND_KEYS:
-        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    for k in INDEX_KEYS:
-        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros((2, 0), dtype=np.int32)], axis=1).astype(np.int32)
-    if positions:
-        for k in POS_KEYS:
-            out[k] = np.concatenate([r[k] for r in refs] + [np.zeros((0, 3), dtype=np.float32)]).astype(np.float32)
-    return out
+    out = molpack.stack([framework_ref(m, mode, sys_bins, atomic_numbers, num_bond_types) for m in mols], LAYOUT, {'sys_hist': sys_bins})
+    for a0, b0, k in zip(out['atom_ptr'], out['bond_ptr'], out['n_systems']):   # the records point into the list's arrays
+        out['sys_atom_ptr'][a0:a0 + k] += a0
+        out['sys_bond_ptr'][a0:a0 + k] += b0
+    order = MOL_KEYS + ('atom_ptr', 'bond_ptr') + ATOM_KEYS + BOND_KEYS + INDEX_KEYS + POS_KEYS     # the key order of the stored files
+    return {k: out[k] for k in order if k in out}
 
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
@@ -201,14 +184,8 @@ def launch(cm, ring_data, mode=0, sys_bins=DEFAULT_BINS, select=None, positions=
     import torch
     from . import _lib
     mode, sys_bins = _check(mode, sys_bins)
-    B, dev = cm.B, cm.device
-    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    stats, N, E = z(B, len(STAT_KEYS)), max(cm.N_cap, 1), max(cm.Eh_stride, 1)
-    out = {'sys_hist': z(B, sys_bins)}
-    out.update({k: z(N) for k in ATOM_KEYS}, **{k: z(E) for k in BOND_KEYS}, **{k: z(2, E) for k in INDEX_KEYS})
-    pos = cm.atom_pos if positions else None
-    if pos is not None:
-        out.update({k: torch.zeros(N, 3, dtype=torch.float32, device=dev) for k in POS_KEYS})
+    B, pos = cm.B, cm.atom_pos if positions else None
+    out, stats = molpack.zeros_for(cm, LAYOUT, {'sys_hist': sys_bins}, STAT_KEYS, held=POS_KEYS if pos is not None else ())
     if B > 0:
         brm, rstat = ring_data['bond_ring_min'], ring_data['status']
         if brm.dtype != torch.int32 or rstat.dtype != torch.int32 or brm.numel() < cm.Eh_stride or rstat.numel() < B:
@@ -224,8 +201,7 @@ def launch(cm, ring_data, mode=0, sys_bins=DEFAULT_BINS, select=None, positions=
             opt(out.get('sys_pos')), g('sys_bond_index'), g('sys_bond_type'), _lib.stream()))
     else:
         out['atom_system'] -= 1
-    out.update({k: stats[:, c] for c, k in enumerate(STAT_KEYS)})
-    return out
+    return molpack.split_stats(out, stats, STAT_KEYS)
 
 
 def framework_mols(mols, device, mode=0, sys_bins=DEFAULT_BINS, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, num_bond_types=4, with_cm=False):
@@ -233,26 +209,11 @@ def framework_mols(mols, device, mode=0, sys_bins=DEFAULT_BINS, atomic_numbers=D
     list is packed densely, copied and handed to ``mdx_mol_rings`` and then ``mdx_mol_framework``.  -> the results dict of ``stack_ref``
     with device tensors; with `with_cm` -> (that, the ``CompactMols`` of the list, ``launch``'s own dict): what ``keys`` takes.  Two
     bonds between the same pair of atoms and unknown elements raise ValueError."""
-    import torch
-    device = torch.device(device)
     mode, sys_bins = _check(mode, sys_bins)
     atomic_numbers = tuple(int(z) for z in atomic_numbers)
-    positions = all('atom_pos' in m for m in mols) and len(mols) > 0
-    p = pack_mols(mols, atomic_numbers, positions=positions)
-    check_simple(p)
-    cm = CompactMols.from_packed(to_device(p, device))
-    ring_data = rings.launch(cm, len(atomic_numbers), num_bond_types)
-    full = launch(cm, ring_data, mode, sys_bins)
-    out, total = dict(full), int(p['n_bonds'].sum())
-    for k in _keys(out):
-        out[k] = out[k][:cm.N_cap]
-    if len(mols) == 0:
-        out.update({k: torch.zeros(0, 3, dtype=torch.float32, device=device) for k in POS_KEYS})
-    for k in BOND_KEYS:
-        out[k] = out[k][:total]
-    for k in INDEX_KEYS:
-        out[k] = out[k][:, :total]
-    out.update(n_atoms=cm.n_atoms, n_bonds=cm.n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
+    p, cm = molpack.packed(mols, atomic_numbers, device, positions=True)
+    full = launch(cm, rings.launch(cm, len(atomic_numbers), num_bond_types), mode, sys_bins)
+    out = molpack.dense(dict(full), cm, p, LAYOUT)
     return (out, cm, full) if with_cm else out
 
 
@@ -363,12 +324,7 @@ def concat(parts):
     """the results of consecutive batches (host or device arrays, not mixed; with or without the arrays of ``keys`` merged in) as one
     results dict: the system records and ``sys_mol`` are moved to the joint numbering"""
     parts = [to_host(p) for p in parts]
-    atom = _keys(parts[0])
-    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + atom + BOND_KEYS}
-    for k in INDEX_KEYS:
-        out[k] = np.concatenate([p[k] for p in parts], axis=1)
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
+    out = molpack.concat(parts, LAYOUT)
     a0 = b0 = 0
     for p in parts:   # the records of a part point into the part's own arrays
         rec = slice(a0, a0 + len(p['atom_role']))
@@ -509,7 +465,7 @@ def novelty(results, reference, what='framework'):
 
 
 def compare(a, b):
-    """two results dicts with keys -> dict: Jensen-Shannon divergence (``local3d.jsd_counts``) of the system-ring distribution and of
+    """two results dicts with keys -> dict: Jensen-Shannon divergence (``molpack.jsd_counts``) of the system-ring distribution and of
     the framework-atom, linker-atom and system-count histograms, both sides' ``uniqueness`` and ``empty_fraction``, and the novelty of
     each side against the other for frameworks and for ring systems, by full certificate"""
     sa, sb = summary(a, top_k=0), summary(b, top_k=0)
@@ -526,14 +482,10 @@ def compare(a, b):
 def mol_result(results, m):
     """molecule `m` of a results dict with host arrays as the dict ``framework_ref`` returns (the records count from the molecule's
     own first atom / bond again)"""
-    a0, na, b0, nb = (int(results[k][m]) for k in ('atom_ptr', 'n_atoms', 'bond_ptr', 'n_bonds'))
-    out = {k: (results[k][m] if k == 'sys_hist' else int(results[k][m])) for k in MOL_KEYS}
-    out.update({k: results[k][a0:a0 + na].copy() for k in _keys(results)})
-    out.update({k: results[k][b0:b0 + nb] for k in BOND_KEYS})
-    out.update({k: results[k][:, b0:b0 + nb] for k in INDEX_KEYS})
-    k = out['n_systems']
-    out['sys_atom_ptr'][:k] -= a0
-    out['sys_bond_ptr'][:k] -= b0
+    out = molpack.mol_slice(results, m, LAYOUT)
+    for key, first in (('sys_atom_ptr', 'atom_ptr'), ('sys_bond_ptr', 'bond_ptr')):
+        out[key] = out[key].copy()
+        out[key][:out['n_systems']] -= results[first][m]
     return out
 
 

@@ -29,30 +29,27 @@ With no trained checkpoint offline this is an instrument, not a measurement of q
     python -m moldiff_amd.groups stats samples_all.pt --out groups.npz [--patterns P.yml] [--ref] [--part finished]
     python -m moldiff_amd.groups compare a.npz b.npz
 """
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-from . import rings
-from .local3d import jsd_counts
-from .molpack import check_simple, CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from . import molpack, rings
+from .molpack import check_steps, DEFAULT_ATOMIC_NUMBERS, DEFAULT_NORMAL_VALENCE, jsd_counts, mol_graph, OverBudget, to_host
 
 MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
 PAT_ATOMS, PAT_BONDS, MAX_PATTERNS, RECORD = 8, 12, 32, 90        # include/moldiff_hip.h: MDX_GROUPS_*
-MAX_STEPS_LIMIT, DEFAULT_MAX_STEPS = 1 << 20, 1 << 16
+MAX_STEPS_LIMIT, DEFAULT_MAX_STEPS = molpack.MAX_STEPS_LIMIT, 1 << 16
 MAX_ELEMENTS, MAX_BOND_TYPES = 32, 16
 ANY_RING = 0x7f
 STATUS_OK, STATUS_TOO_LARGE, STATUS_NO_RINGS, PAT_OVER_BUDGET = 0, 1, 2, 3
 MOL_KEYS = ('status', 'n_atoms', 'n_embed', 'n_anchor', 'steps', 'pat_status')
 SLOT_KEYS = ('atom_hit',)
 SET_KEYS = ('aut', 'names')
+# the results table (molpack.Layout): neither n_bonds nor bond_ptr; every wide key has one column per pattern
+LAYOUT = molpack.Layout(MOL_KEYS, atom=SLOT_KEYS, wide=('n_embed', 'n_anchor', 'steps', 'pat_status'))
 DEFAULT_PATTERNS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'configs', 'groups_default.yml')
-# this project's choice, unverified against RDKit: the valence from which implicit hydrogens are counted
-DEFAULT_NORMAL_VALENCE = {6: 4, 7: 3, 8: 2, 9: 1, 15: 3, 16: 2, 17: 1}
-SYMBOLS = {'C': 6, 'N': 7, 'O': 8, 'F': 9, 'P': 15, 'S': 16, 'Cl': 17}
+SYMBOLS = molpack.ELEMENT_NUMBER
 
 
 def ring_class(r):
@@ -294,17 +291,12 @@ def _no_ring_data(pset):
         raise ValueError('a pattern carries a ring constraint and there is no ring data')
 
 
-def _check_steps(max_steps):
-    if not 1 <= int(max_steps) <= MAX_STEPS_LIMIT:
-        raise ValueError(f'max_steps must lie in 1 .. 2^20, got {max_steps}')
-    return int(max_steps)
+def _set_keys(out, pset):
+    out['aut'], out['names'] = pset.automorphisms(), np.asarray(pset.names, dtype=str)
+    return out
 
 
 # ---- one molecule on the host --------------------------------------------------------------------------------------------------------
-
-class _OverBudget(Exception):
-    pass
-
 
 def groups_ref(info, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS, ring_data=None):
     """Plain Python restatement of ``mdx_mol_groups`` for one molecule dict (element = atomic numbers, bond_index (2, 2b) with every
@@ -317,7 +309,7 @@ def groups_ref(info, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS,
     index lies outside the molecule or with i = j is ignored; a bond type outside 1 .. num_bond_types adds no valence and matches no
     pattern bond; an element outside the set's atomic numbers and two bonds between the same pair of atoms raise ValueError."""
     pset = patterns
-    max_steps = _check_steps(max_steps)
+    max_steps = check_steps(max_steps)
     nv = pset.valence_table(normal_valence)
     nbt = pset.num_bond_types
     cls, bi, bt = mol_graph(info, pset.atomic_numbers)
@@ -374,7 +366,7 @@ def groups_ref(info, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS,
                         return
                     steps_at[a] += deg[img[pat.parent[k]]]
                     if steps_at[a] > max_steps:
-                        raise _OverBudget
+                        raise OverBudget
                     for v, t, rc in adj[img[pat.parent[k]]]:
                         if v in img or not bond_ok(pat.tree[k], t, rc) or not atom_ok(pat.atoms[k], v):
                             continue
@@ -383,7 +375,7 @@ def groups_ref(info, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS,
                             extend(k + 1)
                             img.pop()
                 extend(1)
-        except _OverBudget:
+        except OverBudget:
             out['pat_status'][p] = PAT_OVER_BUDGET
             continue
         out['n_embed'][p], out['steps'][p] = sum(embed_at), sum(steps_at)
@@ -398,14 +390,7 @@ def stack_ref(mols, patterns=None, normal_valence=None, max_steps=DEFAULT_MAX_ST
     molecule of every key of MOL_KEYS, ``atom_hit`` over the atoms of the list in turn, ``atom_ptr``, and the set's ``aut`` / ``names``"""
     pset = _patterns(patterns)
     refs = [groups_ref(m, pset, normal_valence, max_steps) for m in mols]
-    P = len(pset)
-    out = {k: np.asarray([r[k] for r in refs], dtype=np.int32).reshape((len(refs), P) if k not in ('status', 'n_atoms') else (len(refs),))
-           for k in MOL_KEYS}
-    out['atom_hit'] = np.concatenate([r['atom_hit'] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    na = out['n_atoms'].astype(np.int64)
-    out['atom_ptr'] = (np.cumsum(na) - na).astype(np.int32)
-    out['aut'], out['names'] = pset.automorphisms(), np.asarray(pset.names, dtype=str)
-    return out
+    return _set_keys(molpack.stack(refs, LAYOUT, dict.fromkeys(LAYOUT.wide, len(pset))), pset)
 
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
@@ -417,11 +402,10 @@ def launch(cm, patterns, normal_valence=None, max_steps=DEFAULT_MAX_STEPS, selec
     False = none, which a set with a ring constraint refuses."""
     import torch
     from . import _lib
-    pset, max_steps = patterns, _check_steps(max_steps)
-    P, B, dev = len(pset), cm.B, cm.device
-    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    out = {'status': z(B), 'n_embed': z(B, P), 'n_anchor': z(B, P), 'steps': z(B, P), 'pat_status': z(B, P), 'atom_hit': z(max(cm.N_cap, 1))}
-    if B == 0:
+    pset, max_steps = patterns, check_steps(max_steps)
+    P, dev = len(pset), cm.device
+    out, _ = molpack.zeros_for(cm, LAYOUT, dict.fromkeys(LAYOUT.wide, P))
+    if cm.B == 0:
         return out
     if ring_data is False:
         _no_ring_data(pset)
@@ -445,17 +429,10 @@ def groups_mols(mols, device, patterns=None, normal_valence=None, max_steps=DEFA
     packed densely, copied and handed to ``mdx_mol_groups`` (after ``mdx_mol_rings`` when a pattern carries a ring constraint).
     patterns: a PatternSet, a YAML path, a dict, or None for the default set.  -> the results dict of ``stack_ref`` with device tensors
     (``aut`` / ``names`` stay numpy).  Two bonds between the same pair of atoms and unknown elements raise ValueError."""
-    import torch
-    device = torch.device(device)
     pset = _patterns(patterns)
-    _check_steps(max_steps)
-    p = pack_mols(mols, pset.atomic_numbers)
-    check_simple(p)
-    cm = CompactMols.from_packed(to_device(p, device))
-    out = launch(cm, pset, normal_valence, max_steps)
-    out['atom_hit'] = out['atom_hit'][:cm.N_cap]
-    out.update(n_atoms=cm.n_atoms, atom_ptr=cm.atom_ptr, aut=pset.automorphisms(), names=np.asarray(pset.names, dtype=str))
-    return out
+    check_steps(max_steps)
+    p, cm = molpack.packed(mols, pset.atomic_numbers, device)
+    return _set_keys(molpack.dense(launch(cm, pset, normal_valence, max_steps), cm, p, LAYOUT), pset)
 
 
 def concat(parts):
@@ -463,11 +440,7 @@ def concat(parts):
     parts = [to_host(p) for p in parts]
     if any(not np.array_equal(p['names'], parts[0]['names']) or not np.array_equal(p['aut'], parts[0]['aut']) for p in parts):
         raise ValueError('the parts were made with different pattern sets')
-    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + SLOT_KEYS}
-    na = out['n_atoms'].astype(np.int64)
-    out['atom_ptr'] = (np.cumsum(na) - na).astype(np.int32)
-    out['aut'], out['names'] = parts[0]['aut'], parts[0]['names']
-    return out
+    return dict(molpack.concat(parts, LAYOUT), aut=parts[0]['aut'], names=parts[0]['names'])
 
 
 def empty(patterns=None):
@@ -508,7 +481,7 @@ def summary(results):
 
 
 def compare(a, b):
-    """Jensen-Shannon divergence (``local3d.jsd_counts``: base 2, in [0, 1], NaN when a side is empty) of the per-molecule match count
+    """Jensen-Shannon divergence (``molpack.jsd_counts``: base 2, in [0, 1], NaN when a side is empty) of the per-molecule match count
     distributions (0, 1, ..., 7, 8 or more) of two results dicts or two summaries, per pattern name -> {name: jsd}"""
     a, b = (x if 'patterns' in x else summary(x) for x in (a, b))
     if list(a['patterns']) != list(b['patterns']):
@@ -519,33 +492,14 @@ def compare(a, b):
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog='python -m moldiff_amd.groups', description=__doc__.split('\n\n')[0])
-    sub = ap.add_subparsers(dest='cmd', required=True)
-    s = sub.add_parser('stats', help='pattern counts of the molecules stored in a samples_all.pt')
-    s.add_argument('samples')
-    s.add_argument('--out', required=True)
-    s.add_argument('--patterns', default=None, help='pattern file (YAML); default: configs/groups_default.yml')
-    s.add_argument('--part', default='finished')
-    s.add_argument('--max_steps', type=int, default=DEFAULT_MAX_STEPS)
-    s.add_argument('--device', default='cuda:0')
-    s.add_argument('--ref', action='store_true', help='the Python path instead of the device')
-    c = sub.add_parser('compare', help='Jensen-Shannon divergence of the per-molecule match counts of two files, per pattern')
-    c.add_argument('a')
-    c.add_argument('b')
-    args = ap.parse_args(argv)
-    if args.cmd == 'stats':
-        mols, pset = load_mols(args.samples, args.part), _patterns(args.patterns)
-        if args.ref:
-            res = stack_ref(mols, pset, max_steps=args.max_steps)
-        else:
-            import torch
-            torch.cuda.set_device(torch.device(args.device))
-            res = groups_mols(mols, args.device, pset, max_steps=args.max_steps)
-        save_npz(res, args.out)
-        print(json.dumps(summary(res), indent=1))
-    else:
-        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
-    return 0
+    def run(mols, a, dev):
+        pset = _patterns(a.patterns)
+        return stack_ref(mols, pset, max_steps=a.max_steps) if dev is None else groups_mols(mols, dev, pset, max_steps=a.max_steps)
+    return molpack.stats_main(
+        argv, 'groups', __doc__, ('pattern counts of the molecules stored in a samples_all.pt',
+                                  'Jensen-Shannon divergence of the per-molecule match counts of two files, per pattern'),
+        [('--patterns', dict(default=None, help='pattern file (YAML); default: configs/groups_default.yml')),
+         ('--max_steps', dict(type=int, default=DEFAULT_MAX_STEPS))], run, summary, compare)
 
 
 if __name__ == '__main__':

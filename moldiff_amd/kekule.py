@@ -30,13 +30,12 @@ import sys
 
 import numpy as np
 
-from . import rings
-from .local3d import jsd_counts
-from .molpack import check_simple, CompactMols, DEFAULT_ATOMIC_NUMBERS, host, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from . import molpack, rings
+from .molpack import check_steps, DEFAULT_ATOMIC_NUMBERS, DEFAULT_NORMAL_VALENCE, host, jsd_counts, load_mols, load_npz, mol_graph, OverBudget, save_npz, to_host
 
 MAX_ATOMS, MAX_BONDS = rings.MAX_ATOMS, rings.MAX_BONDS           # include/moldiff_hip.h: the caps of mdx_mol_rings
 MAX_COMPONENT = 64                                                # atoms of one aromatic component
-MAX_STEPS_LIMIT, DEFAULT_MAX_STEPS = 1 << 20, 1 << 16
+MAX_STEPS_LIMIT, DEFAULT_MAX_STEPS = molpack.MAX_STEPS_LIMIT, 1 << 16
 MAX_ELEMENTS, MAX_BOND_TYPES, MAX_VALENCE = 32, 16, 64
 STATUS_OK, STATUS_TOO_LARGE = 0, 1
 ROLE_NONE, ROLE_NOT, ROLE_MUST, ROLE_MAY = 0, 1, 2, 3             # bits 0-1 of atom_flag; NONE: the atom has no aromatic bond
@@ -47,11 +46,11 @@ STAT_KEYS = ('status', 'n_arom_atoms', 'n_arom_bonds', 'n_components', 'n_failed
 MOL_KEYS = STAT_KEYS + ('n_atoms', 'n_bonds')
 ATOM_KEYS = ('val', 'charge', 'kek_h', 'atom_flag')
 BOND_KEYS = ('kek_order',)
-# this project's choice, unverified against RDKit
-DEFAULT_NORMAL_VALENCE = {6: 4, 7: 3, 8: 2, 9: 1, 15: 3, 16: 2, 17: 1}    # = groups.DEFAULT_NORMAL_VALENCE
+LAYOUT = molpack.Layout(MOL_KEYS, atom=ATOM_KEYS, bond=BOND_KEYS)         # the results table
+# this project's choice, unverified against RDKit (the normal valences are molpack.DEFAULT_NORMAL_VALENCE)
 DEFAULT_CHARGED_VALENCE = {7: 4, 16: 3}                                   # the valence with one positive charge; absent = none
 DEFAULT_FLEXIBLE = (7,)                                                   # takes a hydrogen instead of a double bond
-SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+SYMBOL = molpack.ELEMENT_SYMBOL
 MASS = {1: 1.008, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 15: 30.974, 16: 32.06, 17: 35.45}   # standard atomic weights, abridged
 STEP_BINS = 22                                                    # bin k: molecules whose steps have bit length k, the last bin also more
 
@@ -89,17 +88,7 @@ def _tables(tables):
     return KekuleTables() if tables is None else tables
 
 
-def _check_steps(max_steps):
-    if not 1 <= int(max_steps) <= MAX_STEPS_LIMIT:
-        raise ValueError(f'max_steps must lie in 1 .. 2^20, got {max_steps}')
-    return int(max_steps)
-
-
 # ---- one molecule on the host --------------------------------------------------------------------------------------------------------
-
-class _OverBudget(Exception):
-    pass
-
 
 def kekulize_ref(info, tables=None, max_steps=DEFAULT_MAX_STEPS):
     """Plain Python restatement of ``mdx_mol_kekulize`` for one molecule dict (element = atomic numbers, bond_index (2, 2b) with every
@@ -110,7 +99,7 @@ def kekulize_ref(info, tables=None, max_steps=DEFAULT_MAX_STEPS):
     nothing and is not aromatic (kek_order 0); an element outside the tables' atomic numbers and two bonds between the same pair of
     atoms raise ValueError.  A molecule is kekulizable iff status == 0 and n_failed == n_over_budget == 0 (``kekulizable``)."""
     tb = _tables(tables)
-    max_steps = _check_steps(max_steps)
+    max_steps = check_steps(max_steps)
     nbt = tb.num_bond_types
     cls, bi, bt = mol_graph(info, tb.atomic_numbers)
     n, nb = len(cls), bi.shape[1]
@@ -175,7 +164,7 @@ def kekulize_ref(info, tables=None, max_steps=DEFAULT_MAX_STEPS):
             options = ([None] if role[a] == ROLE_MAY else []) + [b for b in sorted(arom[a]) if b > a and role[b] != ROLE_NOT and b not in partner]
             for b in options:
                 if count[0] == max_steps:
-                    raise _OverBudget
+                    raise OverBudget
                 count[0] += 1
                 if b is not None:
                     partner[a], partner[b] = b, a
@@ -191,7 +180,7 @@ def kekulize_ref(info, tables=None, max_steps=DEFAULT_MAX_STEPS):
                 out['n_failed'] += 1
                 out['steps'] += count[0]
                 unsolved.add(root)
-        except _OverBudget:
+        except OverBudget:
             for a in atoms:
                 partner.pop(a, None)
             out['n_over_budget'] += 1
@@ -225,13 +214,7 @@ def stack_ref(mols, tables=None, max_steps=DEFAULT_MAX_STEPS):
     of every key of MOL_KEYS, the keys of ATOM_KEYS over the atoms and ``kek_order`` over the bonds of the list in turn, ``atom_ptr``
     and ``bond_ptr``"""
     tb = _tables(tables)
-    refs = [kekulize_ref(m, tb, max_steps) for m in mols]
-    out = {k: np.asarray([r[k] for r in refs], dtype=np.int32).reshape(len(refs)) for k in MOL_KEYS}
-    for k in ATOM_KEYS + BOND_KEYS:
-        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    return molpack.stack([kekulize_ref(m, tb, max_steps) for m in mols], LAYOUT)
 
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
@@ -240,50 +223,31 @@ def launch(cm, tables=None, max_steps=DEFAULT_MAX_STEPS, select=None):
     """``mdx_mol_kekulize`` on the device arrays `cm` (a ``CompactMols``) -> dict of int32 device tensors: the keys of STAT_KEYS (B)
     each, columns of one (B, 11) table), ``val`` / ``charge`` / ``kek_h`` / ``atom_flag`` (N_cap) and ``kek_order`` (Eh_stride) in the
     layout of the inputs, zero where no molecule has a slot; no sync"""
-    import torch
     from . import _lib
-    tb, max_steps = _tables(tables), _check_steps(max_steps)
-    B, dev = cm.B, cm.device
-    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    stats = z(B, len(STAT_KEYS))
-    out = {k: z(max(cm.N_cap, 1)) for k in ATOM_KEYS}
-    out['kek_order'] = z(max(cm.Eh_stride, 1))
-    if B > 0:
+    tb, max_steps = _tables(tables), check_steps(max_steps)
+    out, stats = molpack.zeros_for(cm, LAYOUT, stat_keys=STAT_KEYS)
+    if cm.B > 0:
         ops, at = cm.operands()
         _lib.check(_lib.lib().mdx_mol_kekulize(
             *ops, _lib.ptr(select), len(tb.atomic_numbers), tb.num_bond_types, tb.normal_valence.ctypes.data, tb.charged_valence.ctypes.data,
             tb.flexible, max_steps, at(out['kek_order']), at(out['val']), at(out['charge']), at(out['kek_h']), at(out['atom_flag']),
             at(stats), _lib.stream()))
-    out.update({k: stats[:, c] for c, k in enumerate(STAT_KEYS)})
-    return out
+    return molpack.split_stats(out, stats, STAT_KEYS)
 
 
 def kekulize_mols(mols, device, tables=None, max_steps=DEFAULT_MAX_STEPS):
     """Kekulé assignment of a list of molecule dicts (finished molecules, or entries of ``samples_all.pt``) on the device: the list is
     packed densely, copied and handed to ``mdx_mol_kekulize``.  -> the results dict of ``stack_ref`` with device tensors.  Two bonds
     between the same pair of atoms and unknown elements raise ValueError."""
-    import torch
-    device = torch.device(device)
     tb = _tables(tables)
-    _check_steps(max_steps)
-    p = pack_mols(mols, tb.atomic_numbers)
-    check_simple(p)
-    cm = CompactMols.from_packed(to_device(p, device))
-    out = launch(cm, tb, max_steps)
-    for k in ATOM_KEYS:
-        out[k] = out[k][:cm.N_cap]
-    out['kek_order'] = out['kek_order'][:len(cm.bond_type)]
-    out.update(n_atoms=cm.n_atoms, n_bonds=cm.n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-    return out
+    check_steps(max_steps)
+    p, cm = molpack.packed(mols, tb.atomic_numbers, device)
+    return molpack.dense(launch(cm, tb, max_steps), cm, p, LAYOUT)
 
 
 def concat(parts):
     """the results of consecutive batches (host or device arrays, not mixed) as one results dict"""
-    parts = [to_host(p) for p in parts]
-    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + ATOM_KEYS + BOND_KEYS}
-    na, nb = out['n_atoms'].astype(np.int64), out['n_bonds'].astype(np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    return molpack.concat(parts, LAYOUT)
 
 
 def empty():
@@ -300,11 +264,7 @@ def kekulizable(results):
 
 def mol_result(results, m):
     """molecule `m` of a results dict with host arrays as the dict ``kekulize_ref`` returns"""
-    a0, na, b0, nb = (int(results[k][m]) for k in ('atom_ptr', 'n_atoms', 'bond_ptr', 'n_bonds'))
-    out = {k: int(results[k][m]) for k in MOL_KEYS}
-    out.update({k: results[k][a0:a0 + na] for k in ATOM_KEYS})
-    out['kek_order'] = results['kek_order'][b0:b0 + nb]
-    return out
+    return molpack.mol_slice(results, m, LAYOUT)
 
 
 def summary(results):
@@ -332,7 +292,7 @@ def summary(results):
 
 
 def compare(a, b):
-    """two results dicts or two summaries -> dict: Jensen-Shannon divergence (``local3d.jsd_counts``: base 2, in [0, 1], NaN when a
+    """two results dicts or two summaries -> dict: Jensen-Shannon divergence (``molpack.jsd_counts``: base 2, in [0, 1], NaN when a
     side is empty) of ``steps_hist`` and ``charged_hist``, and both sides' ``fraction_kekulizable``"""
     a, b = (x if 'steps_hist' in x else summary(x) for x in (a, b))
     return {'steps': jsd_counts(a['steps_hist'], b['steps_hist']), 'charged': jsd_counts(a['charged_hist'], b['charged_hist']),
@@ -370,7 +330,6 @@ def kekule_mol_block(info, result, name='moldiff_amd'):
     lines (8 per line).  info: the molecule dict; result: its ``kekulize_ref`` dict or ``mol_result`` slice.  ``sample_drug3d.mol_block``
     writes the aromatic form and is unchanged; ``sample_drug3d.read_mol_block`` reads this block back (it does not read charges).
     Hydrogens stay implicit.  A molecule that is not kekulizable, or that holds an ignored bond, raises ValueError."""
-    from .sample_drug3d import ELEMENT_SYMBOL
     if not bool(kekulizable({k: np.asarray(result[k]) for k in ('status', 'n_failed', 'n_over_budget')})):
         raise ValueError('the molecule is not kekulizable: there is no Kekulé form to write')
     ele, pos = np.asarray(info['element']), np.asarray(info['atom_pos'])
@@ -381,7 +340,7 @@ def kekule_mol_block(info, result, name='moldiff_amd'):
         raise ValueError('an ignored bond or a bond type outside the featuriser has no order to write')
     lines = [name, '  moldiff_amd', '', '%3d%3d  0  0  0  0  0  0  0  0999 V2000' % (len(ele), nb)]
     for e, p in zip(ele, pos):
-        lines.append('%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0' % (p[0], p[1], p[2], ELEMENT_SYMBOL.get(int(e), 'X')))
+        lines.append('%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0' % (p[0], p[1], p[2], SYMBOL.get(int(e), 'X')))
     for k in range(nb):
         lines.append('%3d%3d%3d  0' % (bi[0, k] + 1, bi[1, k] + 1, order[k]))
     charged = [(a + 1, int(c)) for a, c in enumerate(np.asarray(result['charge'])) if c]

@@ -17,7 +17,7 @@ choice, not the reference's.  Bin k holds lo + k w <= v < lo + (k + 1) w and the
 outside [lo, hi], NaN included, is counted in ``outside``.  The device computes in fp32: which side a value within fp32 rounding of a
 bin edge falls on is not specified.
 
-The Jensen-Shannon divergence is defined once, in ``jsd_counts``: base-2 logarithm (range [0, 1]) over the normalised in-range counts,
+The Jensen-Shannon divergence is defined once, in ``molpack.jsd_counts``: base-2 logarithm (range [0, 1]) over the normalised in-range counts,
 NaN when either side is empty.
 
 No trained checkpoint is available offline, so this is an instrument: nothing here is a measurement of sample quality.
@@ -33,11 +33,10 @@ from collections import Counter
 
 import numpy as np
 
-from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, host, load_mols, mol_graph, pack_mols, to_device
+from .molpack import CompactMols, DEFAULT_ATOMIC_NUMBERS, ELEMENT_SYMBOL, host, jsd_counts, load_mols, mol_graph, pack_mols, to_device  # noqa: F401
 
 KINDS = ('lengths', 'angles', 'dihedrals')
 BOND_SYMBOL = {1: '-', 2: '=', 3: '#', 4: ':'}
-ELEMENT_SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}   # the featuriser's atomic numbers
 MAX_PATTERNS = 64          # per kind: the device keeps the table in LDS
 _FIELDS = {'lengths': 3, 'angles': 5, 'dihedrals': 7}
 
@@ -289,18 +288,6 @@ def frequent_patterns(mols, kind, top=20):
 
 
 # ---- statistics ---------------------------------------------------------------------------------------------------------------------
-
-def jsd_counts(p, q):
-    """Jensen-Shannon divergence of two count vectors over the same bins: base-2 logarithm, so in [0, 1]; each side is normalised by
-    its own sum (scaling a side's counts changes nothing); NaN when either side is empty."""
-    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
-    if p.sum() <= 0 or q.sum() <= 0:
-        return float('nan')
-    p, q = p / p.sum(), q / q.sum()
-    m = 0.5 * (p + q)
-    kl = lambda a: float((a[a > 0] * np.log2(a[a > 0] / m[a > 0])).sum())
-    return min(1.0, max(0.0, 0.5 * kl(p) + 0.5 * kl(q)))
-
 
 class Local3DStats:
     """Accumulated statistics: ``hist`` (flat int64, ``spec.hist_slice``'s layout), ``outside`` (one int64 per pattern), ``n_items``

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .molcheck import fragment_fraction, valence_table
+from .molpack import attach, CompactMols, on_device
 
 
 def _softmax(x):
@@ -176,8 +177,7 @@ class FeaturizeMol(object):
         These are the molecules AS DECODED, not RDKit's reconstruction of them: see moldiff_amd/local3d.py.  Like ``decode_batch``,
         it needs a batch with at least one half-edge (``mdx_decode_output`` refuses an empty prediction array)."""
         from . import local3d
-        if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
-            raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        self._same_featuriser(spec, 'the spec was')
         cm, graph, select, _ = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if out is None:
             out = local3d.device_stats(spec, cm.device)
@@ -187,11 +187,15 @@ class FeaturizeMol(object):
             return out
         return local3d.launch(cm, spec, out, select=select, ws=graph.workspace(cm.device))
 
+    def _same_featuriser(self, made, what):
+        """`made` (anything with atomic_numbers and num_bond_types: a spec, a pattern set, tables) was made for this featuriser"""
+        if tuple(made.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or made.num_bond_types != self.num_bond_types:
+            raise ValueError(f'{what} made for another featuriser (atomic_numbers / num_bond_types differ)')
+
     def _compact_mols(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select):
         """The prologue of the ``*_batch`` methods below: ``mdx_decode_output``, then its compact tensors as the operands of an
         evaluation entry point -> (cm: a ``molpack.CompactMols``; the graph; `select` as int32 on the device, or None; n_atoms (B) with
         0 for a molecule `select` leaves out)."""
-        from .molpack import CompactMols
         graph, d = self._decode_device(pred, batch_node, halfedge_index, n_graphs, graph)
         dev = d['atom_type'].device
         ptrs = self._mol_ptrs(graph, batch_node, batch_halfedge, dev)
@@ -222,8 +226,7 @@ class FeaturizeMol(object):
         These are the molecules AS DECODED; the fingerprint is this project's, not RDKit's.  Like ``decode_batch``, it needs a batch
         with at least one half-edge."""
         from . import similarity
-        if tuple(spec.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or spec.num_bond_types != self.num_bond_types:
-            raise ValueError('the spec was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        self._same_featuriser(spec, 'the spec was')
         cm, graph, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if cm.B == 0:
             return similarity.FingerprintSet.empty(spec).to(cm.device)
@@ -241,11 +244,8 @@ class FeaturizeMol(object):
         from . import rings
         cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if cm.B == 0:
-            return {k: torch.from_numpy(v).to(cm.device) for k, v in
-                    rings.empty(self.num_bond_types, self.atomic_numbers.tolist(), ring_bins).items()}
-        out = rings.launch(cm, self.num_element, self.num_bond_types, ring_bins, select=select)
-        out.update(n_atoms=n_atoms, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-        return out
+            return on_device(rings.empty(self.num_bond_types, self.atomic_numbers.tolist(), ring_bins), cm.device)
+        return attach(rings.launch(cm, self.num_element, self.num_bond_types, ring_bins, select=select), cm, select, n_atoms, rings.LAYOUT)
 
     def groups_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, patterns, graph=None, *, select=None,
                      max_steps=None, normal_valence=None):
@@ -257,14 +257,13 @@ class FeaturizeMol(object):
         ``aut`` / ``names`` as numpy.  These are the molecules AS DECODED; the pattern language is this project's, not SMARTS.  Like
         ``decode_batch``, it needs a batch with at least one half-edge."""
         from . import groups
-        if tuple(patterns.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or patterns.num_bond_types != self.num_bond_types:
-            raise ValueError('the pattern set was made for another featuriser (atomic_numbers / num_bond_types differ)')
+        self._same_featuriser(patterns, 'the pattern set was')
         max_steps = groups.DEFAULT_MAX_STEPS if max_steps is None else max_steps
         cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if cm.B == 0:
-            return {k: torch.from_numpy(v).to(cm.device) if k not in groups.SET_KEYS else v for k, v in groups.empty(patterns).items()}
-        out = groups.launch(cm, patterns, normal_valence, max_steps, select=select)
-        out.update(n_atoms=n_atoms, atom_ptr=cm.atom_ptr, aut=patterns.automorphisms(), names=np.asarray(patterns.names, dtype=str))
+            return on_device(groups.empty(patterns), cm.device, keep=groups.SET_KEYS)
+        out = attach(groups.launch(cm, patterns, normal_valence, max_steps, select=select), cm, select, n_atoms, groups.LAYOUT)
+        out.update(aut=patterns.automorphisms(), names=np.asarray(patterns.names, dtype=str))
         return out
 
     def kekulize_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, tables=None, graph=None, *, select=None,
@@ -279,18 +278,12 @@ class FeaturizeMol(object):
         batch with at least one half-edge."""
         from . import kekule
         tables = kekule.KekuleTables(self.atomic_numbers.tolist(), self.num_bond_types) if tables is None else tables
-        if tuple(tables.atomic_numbers) != tuple(self.atomic_numbers.tolist()) or tables.num_bond_types != self.num_bond_types:
-            raise ValueError('the tables were made for another featuriser (atomic_numbers / num_bond_types differ)')
+        self._same_featuriser(tables, 'the tables were')
         max_steps = kekule.DEFAULT_MAX_STEPS if max_steps is None else max_steps
         cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         if cm.B == 0:
-            return {k: torch.from_numpy(v).to(cm.device) for k, v in kekule.empty().items()}
-        out = kekule.launch(cm, tables, max_steps, select=select)
-        n_bonds = cm.n_bonds[:cm.B]
-        if select is not None:
-            n_bonds = torch.where(select != 0, n_bonds, torch.zeros_like(n_bonds))
-        out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-        return out
+            return on_device(kekule.empty(), cm.device)
+        return attach(kekule.launch(cm, tables, max_steps, select=select), cm, select, n_atoms, kekule.LAYOUT)
 
     def canon_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
                     atom_label=None):
@@ -307,12 +300,8 @@ class FeaturizeMol(object):
         max_nodes = canon.DEFAULT_MAX_NODES if max_nodes is None else max_nodes
         cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         out = canon.launch(cm, max_nodes, select=select, atom_label=atom_label)
-        n_bonds = cm.n_bonds[:cm.B]
-        if select is not None:
-            n_bonds = torch.where(select != 0, n_bonds, torch.zeros_like(n_bonds))
         canonical, keep = canon.canonical_compact(cm, out, select)
-        out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-        return out, canonical, keep
+        return attach(out, cm, select, n_atoms, canon.LAYOUT), canonical, keep
 
     def framework_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, mode=0, sys_bins=None, select=None):
         """``decode_batch``'s device part + the framework and the ring systems of every decoded molecule (``mdx_mol_rings``, then
@@ -328,12 +317,7 @@ class FeaturizeMol(object):
         sys_bins = framework.DEFAULT_BINS if sys_bins is None else sys_bins
         cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
         ring_data = rings.launch(cm, self.num_element, self.num_bond_types, select=select)
-        out = framework.launch(cm, ring_data, mode, sys_bins, select=select)
-        n_bonds = cm.n_bonds[:cm.B]
-        if select is not None:
-            n_bonds = torch.where(select != 0, n_bonds, torch.zeros_like(n_bonds))
-        out.update(n_atoms=n_atoms, n_bonds=n_bonds, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-        return out, cm
+        return attach(framework.launch(cm, ring_data, mode, sys_bins, select=select), cm, select, n_atoms, framework.LAYOUT), cm
 
 
 def seperate_outputs(outputs, n_graphs, batch_node, halfedge_index, batch_halfedge):

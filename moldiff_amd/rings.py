@@ -24,19 +24,23 @@ With no trained checkpoint offline this is an instrument, not a measurement of q
     python -m moldiff_amd.rings stats samples_all.pt --out rings.npz [--ref] [--part finished]
     python -m moldiff_amd.rings compare a.npz b.npz
 """
-import argparse
-import json
 import sys
 
 import numpy as np
 
-from .local3d import jsd_counts
-from .molpack import check_simple, CompactMols, DEFAULT_ATOMIC_NUMBERS, load_mols, load_npz, mol_graph, pack_mols, save_npz, to_device, to_host
+from . import molpack
+from .molpack import DEFAULT_ATOMIC_NUMBERS, jsd_counts, mol_graph, to_host
 
 MAX_ATOMS, MAX_BONDS, MAX_RINGS = 256, 512, 64      # include/moldiff_hip.h: beyond them a molecule gets a status, not a result
 STATUS_OK, STATUS_TOO_LARGE, STATUS_TOO_MANY_RINGS = 0, 1, 2
 MOL_KEYS = ('status', 'n_atoms', 'n_rings', 'ring_hist', 'n_ring_atoms', 'n_ring_bonds', 'n_rotatable', 'elem_count', 'bond_count')
 SLOT_KEYS = ('bond_ring_min', 'atom_ring_min')
+# the results table (molpack.Layout): bond_ptr but no n_bonds
+LAYOUT = molpack.Layout(MOL_KEYS, atom=('atom_ring_min',), bond=('bond_ring_min',), wide=('ring_hist', 'elem_count', 'bond_count'))
+
+
+def _widths(ring_bins, n_elements, num_bond_types):
+    return {'ring_hist': ring_bins, 'elem_count': n_elements, 'bond_count': num_bond_types}
 
 
 def _check_sizes(num_bond_types, n_elements, ring_bins):
@@ -157,15 +161,9 @@ def rings_ref(info, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, rin
 def stack_ref(mols, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, ring_bins=7):
     """``rings_ref`` of every molecule of a list as the results dict ``rings_mols`` returns (numpy): one entry per molecule of every
     key of MOL_KEYS, ``bond_ring_min`` / ``atom_ring_min`` over the bonds / atoms of the list in turn, ``atom_ptr`` / ``bond_ptr``"""
-    refs = [rings_ref(m, num_bond_types, atomic_numbers, ring_bins) for m in mols]
-    width = {'ring_hist': ring_bins, 'elem_count': len(tuple(atomic_numbers)), 'bond_count': num_bond_types}
-    out = {k: np.asarray([r[k] for r in refs], dtype=np.int32).reshape((len(refs), width[k]) if k in width else (len(refs),))
-           for k in MOL_KEYS}
-    for k in SLOT_KEYS:
-        out[k] = np.concatenate([r[k] for r in refs] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    na, nb = out['n_atoms'].astype(np.int64), np.asarray([len(r['bond_ring_min']) for r in refs], dtype=np.int64)
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    out = molpack.stack([rings_ref(m, num_bond_types, atomic_numbers, ring_bins) for m in mols], LAYOUT,
+                        _widths(ring_bins, len(tuple(atomic_numbers)), num_bond_types))
+    return {k: out[k] for k in MOL_KEYS + SLOT_KEYS + ('atom_ptr', 'bond_ptr')}   # the key order of the stored files
 
 
 # ---- the device path ----------------------------------------------------------------------------------------------------------------
@@ -174,15 +172,10 @@ def launch(cm, num_element, num_bond_types, ring_bins=7, select=None):
     """``mdx_mol_rings`` on the device arrays `cm` (a ``CompactMols``) -> dict of int32 device tensors: the keys of MOL_KEYS but n_atoms, one
     entry (or row) per molecule, and ``bond_ring_min`` (Eh_stride) / ``atom_ring_min`` (N_cap) in the layout of the inputs, zero
     where no molecule has a slot; no sync"""
-    import torch
     from . import _lib
     _check_sizes(num_bond_types, num_element, ring_bins)
-    B, dev = cm.B, cm.device
-    z = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)
-    out = {'status': z(B), 'n_rings': z(B), 'ring_hist': z(B, ring_bins), 'n_ring_atoms': z(B), 'n_ring_bonds': z(B), 'n_rotatable': z(B),
-           'elem_count': z(B, num_element), 'bond_count': z(B, num_bond_types), 'bond_ring_min': z(max(cm.Eh_stride, 1)),
-           'atom_ring_min': z(max(cm.N_cap, 1))}
-    if B == 0:
+    out, _ = molpack.zeros_for(cm, LAYOUT, _widths(ring_bins, num_element, num_bond_types))
+    if cm.B == 0:
         return out
     ops, at = cm.operands()
     _lib.check(_lib.lib().mdx_mol_rings(
@@ -196,27 +189,15 @@ def rings_mols(mols, device, num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUM
     """Ring and composition counts of a list of molecule dicts (finished molecules, or entries of ``samples_all.pt``) on the device: the
     list is packed densely, copied and handed to ``mdx_mol_rings``.  -> the results dict of ``stack_ref`` with device tensors.  Two
     bonds between the same pair of atoms and unknown elements raise ValueError."""
-    import torch
-    device = torch.device(device)
     atomic_numbers = tuple(int(z) for z in atomic_numbers)
     _check_sizes(num_bond_types, len(atomic_numbers), ring_bins)
-    p = pack_mols(mols, atomic_numbers)
-    check_simple(p)
-    cm = CompactMols.from_packed(to_device(p, device))
-    out = launch(cm, len(atomic_numbers), num_bond_types, ring_bins)
-    out['bond_ring_min'], out['atom_ring_min'] = out['bond_ring_min'][:len(cm.bond_type)], out['atom_ring_min'][:cm.N_cap]
-    out.update(n_atoms=cm.n_atoms, atom_ptr=cm.atom_ptr, bond_ptr=cm.bond_ptr)
-    return out
+    p, cm = molpack.packed(mols, atomic_numbers, device)
+    return molpack.dense(launch(cm, len(atomic_numbers), num_bond_types, ring_bins), cm, p, LAYOUT)
 
 
 def concat(parts):
     """the results of consecutive batches (host or device arrays, not mixed) as one results dict"""
-    parts = [to_host(p) for p in parts]
-    out = {k: np.concatenate([p[k] for p in parts]) for k in MOL_KEYS + SLOT_KEYS}
-    na = out['n_atoms'].astype(np.int64)
-    nb = np.concatenate([np.diff(np.append(p['bond_ptr'].astype(np.int64), len(p['bond_ring_min']))) for p in parts])
-    out['atom_ptr'], out['bond_ptr'] = (np.cumsum(na) - na).astype(np.int32), (np.cumsum(nb) - nb).astype(np.int32)
-    return out
+    return molpack.concat(parts, LAYOUT)
 
 
 def empty(num_bond_types=4, atomic_numbers=DEFAULT_ATOMIC_NUMBERS, ring_bins=7):
@@ -254,7 +235,7 @@ def summary(results):
 
 
 def compare(a, b):
-    """Jensen-Shannon divergence (``local3d.jsd_counts``: base 2, in [0, 1], NaN when a side is empty) of the ring-size, element and
+    """Jensen-Shannon divergence (``molpack.jsd_counts``: base 2, in [0, 1], NaN when a side is empty) of the ring-size, element and
     bond-type distributions of two results dicts or two summaries -> {'ring_size': .., 'element': .., 'bond_type': ..}"""
     a, b = (x if 'ring_size' in x else summary(x) for x in (a, b))
     out = {}
@@ -268,32 +249,12 @@ def compare(a, b):
 # ---- command line --------------------------------------------------------------------------------------------------------------------
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog='python -m moldiff_amd.rings', description=__doc__.split('\n\n')[0])
-    sub = ap.add_subparsers(dest='cmd', required=True)
-    s = sub.add_parser('stats', help='ring and composition counts of the molecules stored in a samples_all.pt')
-    s.add_argument('samples')
-    s.add_argument('--out', required=True)
-    s.add_argument('--part', default='finished')
-    s.add_argument('--ring_bins', type=int, default=7)
-    s.add_argument('--device', default='cuda:0')
-    s.add_argument('--ref', action='store_true', help='the Python path instead of the device')
-    c = sub.add_parser('compare', help='Jensen-Shannon divergence of the ring-size, element and bond-type distributions of two files')
-    c.add_argument('a')
-    c.add_argument('b')
-    args = ap.parse_args(argv)
-    if args.cmd == 'stats':
-        mols = load_mols(args.samples, args.part)
-        if args.ref:
-            res = stack_ref(mols, ring_bins=args.ring_bins)
-        else:
-            import torch
-            torch.cuda.set_device(torch.device(args.device))
-            res = rings_mols(mols, args.device, ring_bins=args.ring_bins)
-        save_npz(res, args.out)
-        print(json.dumps(summary(res), indent=1))
-    else:
-        print(json.dumps(compare(load_npz(args.a), load_npz(args.b)), indent=1))
-    return 0
+    return molpack.stats_main(
+        argv, 'rings', __doc__, ('ring and composition counts of the molecules stored in a samples_all.pt',
+                                 'Jensen-Shannon divergence of the ring-size, element and bond-type distributions of two files'),
+        [('--ring_bins', dict(type=int, default=7))],
+        lambda mols, a, dev: stack_ref(mols, ring_bins=a.ring_bins) if dev is None else rings_mols(mols, dev, ring_bins=a.ring_bins),
+        summary, compare)
 
 
 if __name__ == '__main__':

@@ -76,6 +76,7 @@ import json
 import os
 import shutil
 import time
+from typing import Any, Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -84,12 +85,22 @@ from . import BondPredictor, MolDiff, _lib
 from .distributed import balanced_order, gather_pred, shard_bounds
 from .harness import default_config, load_config, placeholder_from_sizes, recipe_state_dict, seed_all
 from .harness import GEOM_DRUGS_MEAN_ATOMS, GEOM_DRUGS_STD_ATOMS
-from .molpack import save_npz, to_host
+from .molpack import ELEMENT_SYMBOL, save_npz, to_host
 from .molcheck import accept_rule, fragment_fraction, judge, quality_summary
 from .postprocess import FeaturizeMol
 from .scaffold import scaffold_for_sizes
 
-ELEMENT_SYMBOL = {6: 'C', 7: 'N', 8: 'O', 9: 'F', 15: 'P', 16: 'S', 17: 'Cl'}
+
+class Feature(NamedTuple):
+    """One "parts, then files" evaluation of the finished molecules: `run` on every batch's finished molecules gives a results dict,
+    `module` joins the parts (``concat``; ``empty`` when there was none) and sums them up (``summary``), and STEM.npz / STEM.json hold
+    the two.  `empty` and `summary` stand in where the module's own need arguments; `after` writes any further file from the results."""
+    run: Callable
+    module: Any
+    stem: str
+    empty: Callable = None
+    summary: Callable = None
+    after: Callable = None
 
 
 def is_connected(n_atoms, bond_index):
@@ -421,32 +432,50 @@ def main(argv=None):
             sim_ref = similarity.FingerprintSet.load(sim_ref_path)
             if sim_ref.spec != sim_spec:
                 raise ValueError(f'{sim_ref_path} was made with another spec ({sim_ref.spec.to_dict()}) than this run\'s ({sim_spec.to_dict()})')
-    rings_active, rings_parts = rings_option(args.rings, config.sample), []
-    if rings_active:
+    Z, nbt = featurizer.atomic_numbers.tolist(), featurizer.num_bond_types
+    features = []   # in the order their files are written
+    if rings_option(args.rings, config.sample):
         from . import rings
+        features.append(Feature(lambda gen: rings.rings_mols(gen, device, nbt, Z), rings, 'rings', empty=lambda: rings.empty(nbt, Z)))
     groups_active, groups_path = groups_option(args.groups, config.sample)
-    groups_set, groups_parts = None, []
     if groups_active:   # read on every rank, so that a bad file stops all of them
         from . import groups
-        atomic_numbers = featurizer.atomic_numbers.tolist()
-        groups_set = (groups.PatternSet.from_yaml(groups_path, atomic_numbers, featurizer.num_bond_types) if groups_path else
-                      groups.PatternSet.default(atomic_numbers, featurizer.num_bond_types))
-    kek_write, kek_parts, kek_mols = kekulize_option(args.kekulize, config.sample), [], []
+        groups_set = groups.PatternSet.from_yaml(groups_path, Z, nbt) if groups_path else groups.PatternSet.default(Z, nbt)
+        features.append(Feature(lambda gen: groups.groups_mols(gen, device, groups_set), groups, 'groups', empty=lambda: groups.empty(groups_set)))
+    kek_write = kekulize_option(args.kekulize, config.sample)
     kek_active = kek_write or rule == 'kekule'
     if kek_active:
         from . import kekule
-        kek_tables = kekule.KekuleTables(featurizer.atomic_numbers.tolist(), featurizer.num_bond_types)
-    canon_write, canon_parts = canonical_option(args.canonical, config.sample), []
-    if canon_write:
+        kek_tables = kekule.KekuleTables(Z, nbt)
+    if kek_write:
+        features.append(Feature(lambda gen: kekule.kekulize_mols(gen, device, kek_tables), kekule, 'kekule',
+                                after=lambda res: kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)))
+    if canonical_option(args.canonical, config.sample):
         from . import canon
         canon_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or canon.DEFAULT_MAX_NODES
         if not 1 <= canon_nodes <= canon.MAX_NODES_LIMIT:
             raise ValueError(f'canonical_max_nodes must lie in 1 .. 2^20, got {canon_nodes}')
+
+        def run_canon(gen):
+            part = to_host(canon.canon_mols(gen, device, max_nodes=canon_nodes, atomic_numbers=Z))
+            if kek_write:   # the strings need the canonical part and the Kekulé tables of the same batch
+                for info, text in zip(gen, canon.smiles_mols(gen, part, device, kek_tables)):
+                    info['smiles'] = text
+            return part
+
+        def write_smi(res):
+            if kek_write:
+                with open(os.path.join(log_dir, 'samples.smi'), 'w') as f:
+                    f.writelines('%s\t%d\n' % (m['smiles'], m['mol_id']) for m in pool['finished'] if m.get('smiles'))
+        features.append(Feature(run_canon, canon, 'canon', after=write_smi))
     fw_write, fw_mode = frameworks_option(args.frameworks, args.frameworks_generic, args.frameworks_exo, config.sample)
-    fw_parts = []
     if fw_write:
         from . import framework
         fw_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or framework.canon.DEFAULT_MAX_NODES
+        features.append(Feature(lambda gen: framework.stats_mols(gen, device, fw_mode, max_nodes=fw_nodes, atomic_numbers=Z, num_bond_types=nbt),
+                                framework, 'frameworks', empty=lambda: framework.empty(with_keys=True),
+                                summary=lambda res: dict(framework.summary(res, device=device, atomic_numbers=Z), mode=fw_mode)))
+    parts = [[] for _ in features]
     scaffold_info = None
     if scaffold_path:
         with open(scaffold_path) as f:
@@ -541,20 +570,9 @@ def main(argv=None):
             if sim_spec is not None:
                 fps = similarity.fingerprint_mols(gen, sim_spec, device)
                 sim_set = fps if sim_set is None else sim_set.append(fps)
-            if rings_active and gen:
-                rings_parts.append(to_host(rings.rings_mols(gen, device, featurizer.num_bond_types, featurizer.atomic_numbers.tolist())))
-            if groups_set is not None and gen:
-                groups_parts.append(to_host(groups.groups_mols(gen, device, groups_set)))
-            if kek_write and gen:
-                kek_parts.append(to_host(kekule.kekulize_mols(gen, device, kek_tables)))
-            if canon_write and gen:
-                canon_parts.append(to_host(canon.canon_mols(gen, device, max_nodes=canon_nodes, atomic_numbers=featurizer.atomic_numbers.tolist())))
-                if kek_write:
-                    for info, text in zip(gen, canon.smiles_mols(gen, canon_parts[-1], device, kek_tables)):
-                        info['smiles'] = text
-            if fw_write and gen:
-                fw_parts.append(framework.stats_mols(gen, device, fw_mode, max_nodes=fw_nodes, atomic_numbers=featurizer.atomic_numbers.tolist(),
-                                                     num_bond_types=featurizer.num_bond_types))
+            if gen:
+                for f, done_parts in zip(features, parts):
+                    done_parts.append(to_host(f.run(gen)))
             print('[Pool] Finished %d | Failed %d' % (len(pool['finished']), len(pool['failed'])))
             counts[0], counts[1] = len(pool['finished']), len(pool['failed'])
         if dist is not None:  # one small all-reduce keeps the loop condition identical on every rank
@@ -571,35 +589,13 @@ def main(argv=None):
             sim_set.save(os.path.join(log_dir, 'fingerprints.npz'))
             with open(os.path.join(log_dir, 'similarity.json'), 'w') as f:
                 json.dump(similarity.summary(sim_set, sim_ref.to(device) if sim_ref is not None else None), f, indent=1)
-        if rings_active:
-            res = rings.concat(rings_parts) if rings_parts else rings.empty(featurizer.num_bond_types, featurizer.atomic_numbers.tolist())
-            save_npz(res, os.path.join(log_dir, 'rings.npz'))
-            with open(os.path.join(log_dir, 'rings.json'), 'w') as f:
-                json.dump(rings.summary(res), f, indent=1)
-        if groups_set is not None:
-            res = groups.concat(groups_parts) if groups_parts else groups.empty(groups_set)
-            save_npz(res, os.path.join(log_dir, 'groups.npz'))
-            with open(os.path.join(log_dir, 'groups.json'), 'w') as f:
-                json.dump(groups.summary(res), f, indent=1)
-        if kek_write:
-            res = kekule.concat(kek_parts) if kek_parts else kekule.empty()
-            save_npz(res, os.path.join(log_dir, 'kekule.npz'))
-            with open(os.path.join(log_dir, 'kekule.json'), 'w') as f:
-                json.dump(kekule.summary(res), f, indent=1)
-            kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)
-        if canon_write:
-            res = canon.concat(canon_parts) if canon_parts else canon.empty()
-            save_npz(res, os.path.join(log_dir, 'canon.npz'))
-            with open(os.path.join(log_dir, 'canon.json'), 'w') as f:
-                json.dump(canon.summary(res), f, indent=1)
-            if kek_write:
-                with open(os.path.join(log_dir, 'samples.smi'), 'w') as f:
-                    f.writelines('%s\t%d\n' % (m['smiles'], m['mol_id']) for m in pool['finished'] if m.get('smiles'))
-        if fw_write:
-            res = framework.concat(fw_parts) if fw_parts else framework.empty(with_keys=True)
-            save_npz(res, os.path.join(log_dir, 'frameworks.npz'))
-            with open(os.path.join(log_dir, 'frameworks.json'), 'w') as f:
-                json.dump(dict(framework.summary(res, device=device, atomic_numbers=featurizer.atomic_numbers.tolist()), mode=fw_mode), f, indent=1)
+        for f, done_parts in zip(features, parts):
+            res = f.module.concat(done_parts) if done_parts else (f.empty or f.module.empty)()
+            save_npz(res, os.path.join(log_dir, f.stem + '.npz'))
+            with open(os.path.join(log_dir, f.stem + '.json'), 'w') as fh:
+                json.dump((f.summary or f.module.summary)(res), fh, indent=1)
+            if f.after is not None:
+                f.after(res)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed']),

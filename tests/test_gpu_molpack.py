@@ -1,7 +1,8 @@
 """GPU test of what the four evaluation kernels share (csrc/mdx_mol.h, moldiff_amd/molpack.py): ONE designed list of molecule dicts goes
 through ``local3d_mols``, ``fingerprint_mols``, ``rings_mols`` and ``groups_mols`` and every output equals the Python restatement of its
 module exactly.  The sizes 64, 65 and 256 are the wave and workgroup boundaries of the shared scan of the degrees; a list without any bond
-exercises the shared stand-in for empty tensors.
+exercises the shared stand-in for empty tensors.  The last test is about what rings, groups, kekule, canon and framework share on the
+output side: the one results table of ``molpack.Layout``.
 
 The geometry histograms are compared exactly too, which the device's fp32 allows because the bins are few and wide: the test asserts, in
 float64 on the host, that no matched item lies within 1e-3 (degrees, or length units) of a bin edge -- far more than fp32 rounding of
@@ -9,7 +10,10 @@ values of this size moves it."""
 import numpy as np
 import pytest
 
+from moldiff_amd import canon as C
+from moldiff_amd import framework as F
 from moldiff_amd import groups as G
+from moldiff_amd import kekule as K
 from moldiff_amd import local3d as L3
 from moldiff_amd import molpack
 from moldiff_amd import rings as R
@@ -95,3 +99,16 @@ def test_a_list_without_any_bond_through_all_four_entry_points(l3_spec):
     p = molpack.pack_mols(BONDLESS, ELEMENTS, positions=True)
     assert p['bond_index'].shape == (2, 1) and p['bond_type'].size == 0
     check_all_four(BONDLESS, l3_spec, 'bondless')
+
+
+def test_the_five_results_tables_match_stack_ref_and_two_batches_concat_to_the_single_run():
+    """what rings, groups, kekule, canon and framework share on the output side (molpack.Layout): ``<name>_mols`` of a benzene, a
+    two-atom molecule and a single atom without bonds has exactly the keys, dtypes and shapes (and values) of ``stack_ref``, and
+    ``concat`` of the list run as two batches (2 + 1) equals the single run"""
+    mols = [mol([6] * 6, [(k, (k + 1) % 6, 4) for k in range(6)], 1), mol([6, 8], [(0, 1, 2)], 2), mol([7], [], 3)]
+    pset = G.PatternSet.default()
+    for mod, run in ((R, lambda ms: R.rings_mols(ms, DEV)), (G, lambda ms: G.groups_mols(ms, DEV, pset)), (K, lambda ms: K.kekulize_mols(ms, DEV)),
+                     (C, lambda ms: C.canon_mols(ms, DEV)), (F, lambda ms: F.framework_mols(ms, DEV))):
+        whole = molpack.to_host(run(mols))
+        same_results(whole, mod.stack_ref(mols), mod.__name__)
+        same_results(mod.concat([run(mols[:2]), run(mols[2:])]), whole, mod.__name__ + ' in two batches')

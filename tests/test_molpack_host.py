@@ -1,4 +1,5 @@
-"""Host tests of moldiff_amd/molpack.py: the one parser and packer of molecule dicts behind local3d, similarity, rings and groups.
+"""Host tests of moldiff_amd/molpack.py: the one parser and packer of molecule dicts behind local3d, similarity, rings and groups, and
+the one results table (``Layout``, ``stack``, ``concat``, ``mol_slice``) behind rings, groups, kekule, canon and framework.
 The expected arrays are written out; no GPU."""
 import numpy as np
 import pytest
@@ -105,3 +106,111 @@ def test_host_helpers_and_files(tmp_path):
     cm = molpack.CompactMols.from_packed(d)
     assert (cm.B, cm.N_cap, cm.Eh_stride) == (2, 4, 2) and cm.atom_pos.shape == (4, 3) and cm.bond_index is d['bond_index']
     assert molpack.CompactMols.from_packed(molpack.to_device(molpack.pack_mols([], ELEMENTS), 'cpu'))[:1] == (0,)
+
+
+# ---- the results table: a made-up layout, none of the five modules' -----------------------------------------------------------------
+
+TOY = molpack.Layout(mol=('score', 'tag', 'hist', 'n_atoms', 'n_bonds'), atom=('colour',), bond=('order',), index=('ends',), pos=('where',),
+                     optional=('mark',), wide=('hist',), int64=('tag',))
+W = {'hist': 3}
+I32, I64, F32 = np.int32, np.int64, np.float32
+
+
+def toy_ref(score, tag, hist, colour, order, ends, where, mark=None):
+    r = {'score': score, 'tag': tag, 'hist': np.asarray(hist, dtype=I32), 'n_atoms': len(colour), 'n_bonds': len(order),
+         'colour': np.asarray(colour, dtype=I32), 'order': np.asarray(order, dtype=I32), 'ends': np.asarray(ends, dtype=I32).reshape(2, len(order)),
+         'where': np.asarray(where, dtype=F32).reshape(len(colour), 3)}
+    if mark is not None:
+        r['mark'] = np.asarray(mark, dtype=I32)
+    return r
+
+
+def toy_refs(marked=True):
+    m = (lambda *v: list(v)) if marked else (lambda *v: None)
+    return [toy_ref(5, -(1 << 40), [1, 0, 2], [7], [], [[], []], [[1, 2, 3]], m(9)),
+            toy_ref(6, (1 << 40) + 1, [0, 4, 0], [1, 2, 3], [2, 1], [[0, 1], [1, 2]], [[0, 0, 0], [0, 0, 1.5], [0, 2, 0]], m(8, 7, 6)),
+            toy_ref(-1, 3, [9, 9, 9], [4, 5], [3], [[1], [0]], [[4, 4, 4], [5, 5, 5]], m(5, 4))]
+
+
+def same_table(got, want):
+    assert list(got) == list(want)
+    for k, (dtype, value) in want.items():
+        value = np.asarray(value)
+        assert isinstance(got[k], np.ndarray) and got[k].dtype == dtype and got[k].shape == value.shape and np.array_equal(got[k], value), k
+
+
+def test_ptr_is_the_exclusive_running_sum():
+    for counts, want in (([], []), ([3], [0]), ([2, 0, 5, 1], [0, 2, 2, 7]), (np.asarray([4, 4], dtype=np.int32), [0, 4])):
+        got = molpack.ptr(counts)
+        assert got.dtype == I32 and got.shape == (len(want),) and got.tolist() == want
+
+
+def test_stack_of_nothing_of_a_bondless_molecule_and_of_three():
+    z = lambda *shape: np.zeros(shape)
+    nothing = {'score': (I32, z(0)), 'tag': (I64, z(0)), 'hist': (I32, z(0, 3)), 'n_atoms': (I32, z(0)), 'n_bonds': (I32, z(0)),
+               'colour': (I32, z(0)), 'order': (I32, z(0)), 'where': (F32, z(0, 3)), 'ends': (I32, z(2, 0)), 'atom_ptr': (I32, z(0)),
+               'bond_ptr': (I32, z(0))}
+    same_table(molpack.stack([], TOY, W), nothing)
+    items = list(nothing.items())
+    same_table(molpack.stack([], TOY, W, optional=('mark',)), dict(items[:6] + [('mark', (I32, z(0)))] + items[6:]))
+    same_table(molpack.stack(toy_refs()[:1], TOY, W, optional=('mark',)),
+               {'score': (I32, [5]), 'tag': (I64, [-(1 << 40)]), 'hist': (I32, [[1, 0, 2]]), 'n_atoms': (I32, [1]), 'n_bonds': (I32, [0]),
+                'colour': (I32, [7]), 'mark': (I32, [9]), 'order': (I32, z(0)), 'where': (F32, [[1, 2, 3]]), 'ends': (I32, z(2, 0)),
+                'atom_ptr': (I32, [0]), 'bond_ptr': (I32, [0])})
+    three = {'score': (I32, [5, 6, -1]), 'tag': (I64, [-(1 << 40), (1 << 40) + 1, 3]), 'hist': (I32, [[1, 0, 2], [0, 4, 0], [9, 9, 9]]),
+             'n_atoms': (I32, [1, 3, 2]), 'n_bonds': (I32, [0, 2, 1]), 'colour': (I32, [7, 1, 2, 3, 4, 5]), 'mark': (I32, [9, 8, 7, 6, 5, 4]),
+             'order': (I32, [2, 1, 3]), 'where': (F32, [[1, 2, 3], [0, 0, 0], [0, 0, 1.5], [0, 2, 0], [4, 4, 4], [5, 5, 5]]),
+             'ends': (I32, [[0, 1, 1], [1, 2, 0]]), 'atom_ptr': (I32, [0, 1, 4]), 'bond_ptr': (I32, [0, 0, 2])}
+    same_table(molpack.stack(toy_refs(), TOY, W, optional=('mark',)), three)
+    del three['mark']
+    same_table(molpack.stack(toy_refs(marked=False), TOY, W), three)
+    # a position key is held only when every ref holds it
+    refs = toy_refs(marked=False)
+    del refs[1]['where']
+    del three['where']
+    same_table(molpack.stack(refs, TOY, W), three)
+
+
+def test_concat_equals_stack_of_the_joined_refs():
+    refs = toy_refs()
+    stack = lambda rs: molpack.stack(rs, TOY, W, optional=('mark',))
+    whole = {k: (v.dtype, v) for k, v in stack(refs).items()}
+    for cut in (1, 2, 0, 3):                                        # 0 and 3: one part is empty
+        same_table(molpack.concat([stack(refs[:cut]), stack(refs[cut:])], TOY), whole)
+    same_table(molpack.concat([stack(refs[:1]), stack([]), stack(refs[1:2]), stack(refs[2:])], TOY), whole)
+    same_table(molpack.concat([{k: torch.from_numpy(v) for k, v in stack(refs).items()}], TOY), whole)
+    with pytest.raises(KeyError, match='mark'):
+        molpack.concat([stack(refs[:2]), molpack.stack(toy_refs(marked=False)[2:], TOY, W)], TOY)
+
+
+def test_mol_slice_gives_every_ref_back():
+    for marked in (True, False):
+        refs = toy_refs(marked)
+        table = molpack.stack(refs, TOY, W, optional=('mark',) if marked else ())
+        for m, ref in enumerate(refs):
+            got = molpack.mol_slice(table, m, TOY)
+            assert set(got) == set(ref)
+            for k in ref:
+                if k in ('score', 'tag', 'n_atoms', 'n_bonds'):
+                    assert type(got[k]) is int and got[k] == ref[k], (m, k)
+                else:
+                    assert got[k].dtype == ref[k].dtype and got[k].shape == ref[k].shape and np.array_equal(got[k], ref[k]), (m, k)
+
+
+def test_a_layout_without_n_bonds_counts_bonds_by_bond_ptr_and_the_array_length():
+    bare = molpack.Layout(mol=('n_atoms',), atom=('colour',), bond=('order',))
+    assert not bare.has_n_bonds and bare.has_bond_ptr and TOY.has_n_bonds
+    assert not molpack.Layout(mol=('n_atoms',), atom=('colour',)).has_bond_ptr
+    refs = [{'n_atoms': 2, 'colour': np.asarray([1, 2], dtype=I32), 'order': np.asarray([5, 6, 7], dtype=I32)},
+            {'n_atoms': 0, 'colour': np.zeros(0, dtype=I32), 'order': np.zeros(0, dtype=I32)},
+            {'n_atoms': 1, 'colour': np.asarray([3], dtype=I32), 'order': np.asarray([8, 9], dtype=I32)}]
+    whole = {'n_atoms': (I32, [2, 0, 1]), 'colour': (I32, [1, 2, 3]), 'order': (I32, [5, 6, 7, 8, 9]), 'atom_ptr': (I32, [0, 2, 2]),
+             'bond_ptr': (I32, [0, 3, 3])}
+    same_table(molpack.stack(refs, bare), whole)
+    for cut in (0, 1, 2, 3):
+        same_table(molpack.concat([molpack.stack(refs[:cut], bare), molpack.stack(refs[cut:], bare)], bare), whole)
+    table = molpack.stack(refs, bare)
+    assert [molpack.mol_slice(table, m, bare)['order'].tolist() for m in range(3)] == [[5, 6, 7], [], [8, 9]]
+    # without any per-bond key there is no bond_ptr either
+    same_table(molpack.stack(refs, molpack.Layout(mol=('n_atoms',), atom=('colour',))),
+               {'n_atoms': (I32, [2, 0, 1]), 'colour': (I32, [1, 2, 3]), 'atom_ptr': (I32, [0, 2, 2])})
