@@ -97,6 +97,24 @@ int mdx_graph_destroy(mdx_graph_t g);
 int mdx_graph_plan_host(int64_t n_nodes, int64_t n_edges, const int64_t* h_edge_index, int32_t* left, int32_t* right,
                         int32_t* int2ref, int32_t* row_ptr, int32_t* col_ptr, int32_t* col_eids);
 
+/* ---- test aids of the persistent kernels' work distribution (tests/test_gpu_work_plan.py).  Not for production code. */
+/* Caps the compute-unit count the launchers size their grids by (edge kernels A and B, the guidance backward, linear_rows and the
+ * grid heuristics of the training GEMMs read it at launch time), so that a batch of a few hundred edges loops its persistent
+ * waves the way a full batch does on the whole device.  n <= 0, or n beyond the device's count, restores the device's own.
+ * Process-wide; results never depend on it. */
+int mdx_debug_set_num_cus(int32_t n);
+/* The static plan edge kernel A's launcher makes for nunits work items on nslots persistent waves: plan[5] = nslots, nf (full
+ * rounds), rem (items of the last round), split (0 none, 1, 2), m (units per BondFFN slot of a split round).  Host only. */
+int mdx_debug_work_plan_host(int32_t nunits, int32_t nslots, int32_t can_split, int32_t* plan);
+/* What the six row-owner launches of a batch (graph arguments as mdx_graph_create) do on a device of n_cus compute units
+ * (n_cus <= 0: the count the launchers read right now, i.e. the device's or the cap).
+ * launches[6][8], rows: edge kernel A exact / split build, edge kernel B exact / split, guidance backward exact / split; columns:
+ * work items, grid (workgroups of four waves), workgroup pairs of the work queue, then, of those pairs under kernel A's queue (its
+ * last `tail` items are cut by section): pairs whose range is shorter than the tail, equal to it, longer with one workgroup,
+ * longer with two.  Host only. */
+int mdx_debug_launch_units_host(int64_t n_nodes, int64_t n_edges, const int64_t* h_edge_index, const int64_t* h_batch_node,
+                                int64_t n_graphs, int32_t n_cus, int32_t* launches);
+
 size_t mdx_workspace_bytes(int64_t n_nodes, int64_t n_edges);
 
 /* ---- network (models/graph.py) ---------------------------------------------------------------- */

@@ -19,6 +19,7 @@ EXPORTS = [
     'mdx_model_create', 'mdx_model_destroy', 'mdx_model_set_param', 'mdx_model_finalize',
     'mdx_model_set_matrix_path', 'mdx_model_get_matrix_path', 'mdx_model_set_smear_start', 'mdx_gauss_posterior',
     'mdx_graph_create', 'mdx_graph_destroy', 'mdx_graph_plan_host', 'mdx_workspace_bytes',
+    'mdx_debug_set_num_cus', 'mdx_debug_work_plan_host', 'mdx_debug_launch_units_host',
     'mdx_net_forward', 'mdx_node_block', 'mdx_edge_block', 'mdx_bond_ffn', 'mdx_pos_update', 'mdx_segment_sum',
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
@@ -108,6 +109,9 @@ def lib():
         L.mdx_graph_create.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_void_p)]
         L.mdx_graph_destroy.argtypes = [c_void_p]
         L.mdx_graph_plan_host.argtypes = [c_int64, c_int64] + [c_void_p] * 7
+        L.mdx_debug_set_num_cus.argtypes = [c_int32]
+        L.mdx_debug_work_plan_host.argtypes = [c_int32, c_int32, c_int32, c_void_p]
+        L.mdx_debug_launch_units_host.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
         L.mdx_net_forward.argtypes = [c_void_p] * 10 + [c_void_p, c_size_t, c_void_p]
         L.mdx_node_block.argtypes = [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
         L.mdx_edge_block.argtypes = [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
@@ -353,6 +357,53 @@ def graph_for_halfedges(halfedge_index, batch_node, n_graphs):
         g._keepalive = (halfedge_index, batch_node)
         _cache_put(key, g)
     return g
+
+
+# ---- test aids of the persistent kernels' work distribution (include/moldiff_hip.h: mdx_debug_*) ---------------------------------
+_cu_cap = 0
+
+
+class cu_cap:
+    """`with cu_cap(2):` -- TEST AID: the launchers size their grids as on a device of 2 compute units, so that a small batch loops
+    the persistent waves of the row-owner kernels; the previous cap (none by default) is restored on exit.  Process-wide, results
+    do not depend on it.  n <= 0: the device's own count."""
+
+    def __init__(self, n):
+        self.n = max(int(n), 0)
+
+    def __enter__(self):
+        global _cu_cap
+        self.prev, _cu_cap = _cu_cap, self.n
+        check(lib().mdx_debug_set_num_cus(self.n))
+        return self
+
+    def __exit__(self, *exc):
+        global _cu_cap
+        _cu_cap = self.prev
+        check(lib().mdx_debug_set_num_cus(self.prev))
+
+
+def work_plan(nunits, nslots, can_split=True):
+    """The static plan of edge kernel A's launcher (csrc/mdx_plan.h make_plan) -> dict(nslots, nf, rem, split, m).  No GPU."""
+    out = (c_int32 * 5)()
+    check(lib().mdx_debug_work_plan_host(int(nunits), int(nslots), int(bool(can_split)), out))
+    return dict(zip(('nslots', 'nf', 'rem', 'split', 'm'), out))
+
+
+LAUNCHES = ('edge_a_exact', 'edge_a_split', 'edge_b_exact', 'edge_b_split', 'bwd_exact', 'bwd_split')
+
+
+def launch_units(edge_index, batch_node, n_graphs, n_cus=0):
+    """Work items, grid and work-queue pairs of the six row-owner launches of a batch on a device of n_cus compute units (0: the count
+    the launchers read right now, the device's or the cap) ->
+    {launch: dict(nunits, grid, npairs, short, equal, long1, long2)}; the last four count the pairs of kernel A's queue by their
+    range against the section-cut tail (shorter, equal, longer with one workgroup, longer with two).  No GPU."""
+    ei = edge_index.detach().to('cpu', torch.int64).contiguous()
+    bn = batch_node.detach().to('cpu', torch.int64).contiguous()
+    out = (c_int32 * 48)()
+    check(lib().mdx_debug_launch_units_host(int(bn.numel()), int(ei.shape[1]), ptr(ei), ptr(bn), int(n_graphs), int(n_cus), out))
+    keys = ('nunits', 'grid', 'npairs', 'short', 'equal', 'long1', 'long2')
+    return {name: dict(zip(keys, out[8 * k:8 * k + 7])) for k, name in enumerate(LAUNCHES)}
 
 
 # Matrix path of the per-edge Linear layers (include/moldiff_hip.h: MDX_MATRIX_*).  'exact_f32' is the default everywhere;

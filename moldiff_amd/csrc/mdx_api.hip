@@ -12,6 +12,7 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_kernels.h"
+#include "mdx_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -31,7 +32,10 @@ int mdx_set_error(int code, const char* msg) { return fail(code, "%s", msg); }  
     if (e_ != hipSuccess) return fail(MDX_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_));   \
   } while (0)
 
-// compute units of the current device (grid sizes of the persistent kernels; for the other translation units)
+// compute units of the current device (grid sizes of the persistent kernels; for the other translation units), read by the
+// launchers at every launch.  A test may cap it (mdx_debug_set_num_cus): nothing made at model or graph creation depends on it
+// (the work-queue counter sets hold MDX_WQ_PAIRS >= #CUs lines whatever the count), and a cap only lowers it.
+static int g_cu_cap = 0;  // 0: none
 int mdx_num_cus() {
   static const int n = [] {
     int dev = 0;
@@ -39,7 +43,12 @@ int mdx_num_cus() {
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
     return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
   }();
-  return n;
+  const int cap = g_cu_cap;
+  return cap > 0 && cap < n ? cap : n;
+}
+extern "C" int mdx_debug_set_num_cus(int32_t n) {
+  g_cu_cap = n > 0 ? n : 0;
+  return MDX_OK;
 }
 
 extern "C" const char* mdx_last_error(void) { return g_err; }
@@ -680,6 +689,21 @@ struct HostPlan {
   std::vector<int32_t> left, right, int2ref, ref2int, row_ptr, col_ptr, col_eids;
 };
 
+// Units of 16 positions of a CSR order (ptr = row_ptr: edges by left node, col_ptr: col_eids by right node) aligned to each graph's
+// first position: graph b owns the positions ptr[node_ptr[b]] .. ptr[node_ptr[b+1]] (batch_node is non-decreasing).  Two ints per
+// unit: first position, rows.
+std::vector<int32_t> aligned_units(const std::vector<int32_t>& ptr, const std::vector<int32_t>& node_ptr) {
+  std::vector<int32_t> units;
+  for (size_t b = 0; b + 1 < node_ptr.size(); ++b) {
+    const int32_t lo = ptr[node_ptr[b]], hi = ptr[node_ptr[b + 1]];
+    for (int32_t p0 = lo; p0 < hi; p0 += 16) {
+      units.push_back(p0);
+      units.push_back(std::min<int32_t>(16, hi - p0));
+    }
+  }
+  return units;
+}
+
 int plan_graph(int64_t N, int64_t E, const int64_t* ei, HostPlan& p) {
   if (N < 0 || E < 0 || N > INT32_MAX / 4 || E > INT32_MAX / 4) return fail(MDX_ERR_ARG, "graph too large");
   const int64_t* L = ei;
@@ -731,6 +755,48 @@ extern "C" int mdx_graph_plan_host(int64_t N, int64_t E, const int64_t* ei, int3
   return MDX_OK;
 }
 
+extern "C" int mdx_debug_work_plan_host(int32_t nunits, int32_t nslots, int32_t can_split, int32_t* plan) {
+  if (!plan || nunits < 0 || nslots <= 0) return fail(MDX_ERR_ARG, "work plan: null output, negative units or no slots");
+  const EdgePlan p = make_plan(nunits, nslots, can_split != 0);
+  plan[0] = p.nslots; plan[1] = p.nf; plan[2] = p.rem; plan[3] = p.split; plan[4] = p.m;
+  return MDX_OK;
+}
+
+extern "C" int mdx_debug_launch_units_host(int64_t N, int64_t E, const int64_t* ei, const int64_t* bn, int64_t B, int32_t n_cus,
+                                           int32_t* launches) {
+  if (!launches || (E > 0 && !ei) || (N > 0 && !bn) || B < 0) return fail(MDX_ERR_ARG, "launch units: bad argument");
+  if (n_cus <= 0) n_cus = mdx_num_cus();  // what the launchers see right now
+  HostPlan p;
+  int rc = plan_graph(N, E, ei, p);
+  if (rc) return rc;
+  std::vector<int32_t> node_ptr(B + 1, 0);
+  for (int64_t v = 0; v < N; ++v) {
+    if (bn[v] < 0 || bn[v] >= B || (v && bn[v] < bn[v - 1])) return fail(MDX_ERR_ARG, "batch_node must be non-decreasing in [0, n_graphs)");
+    node_ptr[bn[v] + 1]++;
+  }
+  for (int64_t b = 0; b < B; ++b) node_ptr[b + 1] += node_ptr[b];
+  const int ua = (int)aligned_units(p.row_ptr, node_ptr).size() / 2, ur = (int)aligned_units(p.col_ptr, node_ptr).size() / 2;
+  // work items as the launchers count them: kernel A RR graph-aligned units each (rows / 16), kernel B `rows` edges each, the
+  // backward one by-right unit each
+  const RowOwnerShape sh[6] = {shape_edge_a2(), shape_edge_a2s(), shape_edge_b2(), shape_edge_b2s(), shape_edge_bwd2(), shape_edge_bwd2s()};
+  for (int k = 0; k < 6; ++k) {
+    const int rr = sh[k].rows / 16;
+    const int nunits = k < 2 ? (ua + rr - 1) / rr : k < 4 ? (int)((E + sh[k].rows - 1) / sh[k].rows) : ur;
+    const int grid = nunits > 0 ? row_owner_grid(nunits, n_cus, sh[k].wps) : 0;
+    const WorkQ w = make_workq(nullptr, nunits, grid, n_cus);
+    int32_t* o = launches + 8 * k;
+    o[0] = nunits; o[1] = grid; o[2] = grid > 0 ? w.npairs : 0;
+    o[3] = o[4] = o[5] = o[6] = o[7] = 0;
+    for (int pr = 0; grid > 0 && pr < w.npairs; ++pr) {
+      int beg, end;
+      wq_range(w, xcd_remap(pr, w.npairs), beg, end);
+      const int waves = wq_waves(w, 4, (unsigned)grid, pr), cnt = end - beg, tail = waves * EA_WQ_TAIL8 >> 3;  // four waves per workgroup
+      o[cnt < tail ? 3 : cnt == tail ? 4 : waves == 4 ? 5 : 6]++;
+    }
+  }
+  return MDX_OK;
+}
+
 extern "C" int mdx_graph_create(int64_t N, int64_t E, const int64_t* ei, const int64_t* bn, int64_t B,
                                 const int64_t* mol_ids, mdx_graph_t* out) {
   if (!out || (E > 0 && !ei) || (N > 0 && !bn) || B < 0) return fail(MDX_ERR_ARG, "null argument");
@@ -779,17 +845,11 @@ extern "C" int mdx_graph_create(int64_t N, int64_t E, const int64_t* ei, const i
   for (int64_t h = 0; h < Eh; ++h) he_ptr[he_graph[h] + 1]++;
   for (int64_t b = 0; b < B; ++b) { node_ptr[b + 1] += node_ptr[b]; he_ptr[b + 1] += he_ptr[b]; }
   const size_t o_np = add(node_ptr), o_hp = add(he_ptr);
-  // Units of 16 edges aligned to each graph's first edge: graph b owns the edges row_ptr[node_ptr[b]] .. row_ptr[node_ptr[b+1]]
-  // (batch_node is non-decreasing and edges are sorted by left node).  A node's run is cut where a unit ends, so the cuts --
-  // and the association of the in-kernel sums -- are a function of the graph alone, not of its offset in the batch.
-  std::vector<int32_t> units, epo(E), pbase(N + 1, 0);
-  for (int64_t b = 0; b < B; ++b) {
-    const int32_t e_lo = p.row_ptr[node_ptr[b]], e_hi = p.row_ptr[node_ptr[b + 1]];
-    for (int32_t e0 = e_lo; e0 < e_hi; e0 += 16) {
-      units.push_back(e0);
-      units.push_back(std::min<int32_t>(16, e_hi - e0));
-    }
-  }
+  // Units of 16 edges aligned to each graph's first edge (aligned_units; edges are sorted by left node).  A node's run is cut
+  // where a unit ends, so the cuts -- and the association of the in-kernel sums -- are a function of the graph alone, not of its
+  // offset in the batch.
+  const std::vector<int32_t> units = aligned_units(p.row_ptr, node_ptr);
+  std::vector<int32_t> epo(E), pbase(N + 1, 0);
   {
     const int64_t U = (int64_t)units.size() / 2;
     int64_t u = 0;  // unit of the current edge (units are in edge order)
@@ -811,15 +871,9 @@ extern "C" int mdx_graph_create(int64_t N, int64_t E, const int64_t* ei, const i
   g->nparts = pbase[N];
   const size_t o_un = add(units), o_epo = add(epo), o_pb = add(pbase);
   // by-right twin: graph b owns the col positions col_ptr[node_ptr[b]] .. col_ptr[node_ptr[b+1]] (col_eids is ordered by right node)
-  std::vector<int32_t> units_r, epo_r(E), pbase_r(N + 1, 0), col_left(E), col_right(E);
+  const std::vector<int32_t> units_r = aligned_units(p.col_ptr, node_ptr);
+  std::vector<int32_t> epo_r(E), pbase_r(N + 1, 0), col_left(E), col_right(E);
   for (int64_t j = 0; j < E; ++j) { col_left[j] = p.left[p.col_eids[j]]; col_right[j] = p.right[p.col_eids[j]]; }
-  for (int64_t b = 0; b < B; ++b) {
-    const int32_t j_lo = p.col_ptr[node_ptr[b]], j_hi = p.col_ptr[node_ptr[b + 1]];
-    for (int32_t j0 = j_lo; j0 < j_hi; j0 += 16) {
-      units_r.push_back(j0);
-      units_r.push_back(std::min<int32_t>(16, j_hi - j0));
-    }
-  }
   {
     const int64_t U = (int64_t)units_r.size() / 2;
     int64_t u = 0;

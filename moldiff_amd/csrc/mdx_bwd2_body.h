@@ -77,9 +77,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void BW_KERNEL(const EdgeBwdArgs a
   } else {
     const int nslots = gridDim.x * 4;
     const int slot0 = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
-    const int per = (nunits + nslots - 1) / nslots;
-    ubeg = slot0 * per;
-    uend = min(nunits, ubeg + per);
+    static_range(nunits, nslots, slot0, ubeg, uend);
   }
   if (ubeg >= uend) {
     if (dyn) wq_leave(wp, lane);
@@ -385,9 +383,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void BW_TAIL_KERNEL(const EdgeTail
   } else {
     const int nslots = gridDim.x * 4;
     const int slot0 = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
-    const int per = (nunits + nslots - 1) / nslots;
-    ubeg = slot0 * per;
-    uend = min(nunits, ubeg + per);
+    static_range(nunits, nslots, slot0, ubeg, uend);
   }
   if (ubeg >= uend) {
     if (dyn) wq_leave(wp, lane);

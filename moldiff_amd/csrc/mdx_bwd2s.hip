@@ -23,10 +23,12 @@ namespace {
 #include "mdx_bwd2_body.h"
 }  // namespace
 
+RowOwnerShape shape_edge_bwd2s() { return {ROWS, MDX_WPS}; }  // rows per unit and workgroups per CU of this build (mdx_debug_launch_units_host)
+
 void launch_edge_tail_bwd2s(const EdgeTailBwdArgs& a, hipStream_t s) {
   if (a.E <= 0) return;
   const int nunits = (a.E + ROWS - 1) / ROWS;
-  const int grid = std::min((nunits + 3) / 4, mdx_num_cus() * MDX_WPS);
+  const int grid = row_owner_grid(nunits, mdx_num_cus(), MDX_WPS);
   hipLaunchKernelGGL(edge_tail_bwd2s_kernel, dim3(grid), dim3(MDX_WG), 0, s, a, nunits, make_workq(a.wq, nunits, grid, mdx_num_cus()));
 }
 
@@ -42,7 +44,7 @@ int launch_edge_bwd2s(const EdgeBwdArgs& a, hipStream_t s) {
   }
   const int nunits = a.nunits_r;  // graph-aligned units of the by-right order (mdx_graph_s units_r)
   if (nunits <= 0) return 0;
-  const int grid = std::min((nunits + 3) / 4, mdx_num_cus() * MDX_WPS);
+  const int grid = row_owner_grid(nunits, mdx_num_cus(), MDX_WPS);
   const WorkQ wq = make_workq(a.wq, nunits, grid, mdx_num_cus());
   if (a.fuse_tail) hipLaunchKernelGGL(edge_bwd2s_kernel<true>, dim3(grid), dim3(MDX_WG), lds, s, a, nunits, wq);
   else hipLaunchKernelGGL(edge_bwd2s_kernel<false>, dim3(grid), dim3(MDX_WG), lds, s, a, nunits, wq);

@@ -41,6 +41,8 @@ namespace {
 #include "mdx_edge2_body.h"
 }  // namespace
 
+RowOwnerShape shape_edge_a2() { return {ROWS, MDX_WPS}; }  // rows per unit and workgroups per CU of this build (mdx_debug_launch_units_host)
+
 int launch_edge_a2(const EdgeAArgs& a, hipStream_t s) {
   if (a.E <= 0) return MDX_OK;
   switch (a.flags) {

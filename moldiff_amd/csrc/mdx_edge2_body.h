@@ -95,7 +95,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
   if (dyn) {
     wp = wq_pair(wq.q);
     xcnt = wp.end - wp.beg;
-    xnt = min(xcnt, wp.waves * wq.tail8 >> 3);
+    xnt = wq_tail(xcnt, wp.waves, wq.tail8);
     const int i0 = wq_take(wq_request(wp.line, lane));
     nitems = i0 < xcnt + xnt ? 1 : 0;
     unit = wp.beg + wq_item(i0, xcnt, xnt, mode);
@@ -343,12 +343,11 @@ void launch_a2(const EdgeAArgs& a, hipStream_t s) {
   }
   const int nunits = (FLAGS & EA_AGG) ? (a.nunits + RR - 1) / RR : (a.E + ROWS - 1) / ROWS;  // work items (RR units each)
   if (nunits <= 0) return;
-  const int grid = std::min((nunits + 3) / 4, mdx_num_cus() * MDX_WPS);
+  const int grid = row_owner_grid(nunits, mdx_num_cus(), MDX_WPS);
   constexpr bool all = (FLAGS & ~(EA_AGG | EA_TAPE | EA_TAPE_FFN)) == (EA_EMB | EA_NODE | EA_FFN);
   const EdgePlan plan = make_plan(nunits, grid * 4, all);
   WorkQA wq{};
   wq.q = make_workq(a.wq, nunits, grid, mdx_num_cus());
-  if (a.wq && all) wq.tail8 = 10;  // units cut by section at the end of each pair's list: 10 eighths of a unit per wave (measured:
-                                   // none 6.99 ms per step, 8 eighths 6.92, 10 6.91, 16 7.01)
+  if (a.wq && all) wq.tail8 = EA_WQ_TAIL8;  // units cut by section at the end of each pair's list: 10 eighths of a unit per wave
   hipLaunchKernelGGL(E2_KERNEL<FLAGS>, dim3(grid), dim3(MDX_WG), lds, s, a, plan, wq);
 }

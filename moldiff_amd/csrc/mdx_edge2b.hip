@@ -36,6 +36,8 @@ namespace {
 #include "mdx_edge2b_body.h"
 }  // namespace
 
+RowOwnerShape shape_edge_b2() { return {ROWS, MDX_WPS}; }  // rows per unit and workgroups per CU of this build (mdx_debug_launch_units_host)
+
 int launch_edge_b2(const EdgeBArgs& a, hipStream_t s) {
   if (a.E <= 0) return MDX_OK;
   switch (a.flags) {

@@ -50,9 +50,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeBArgs a, 
   } else {
     const int nslots = gridDim.x * 4;
     const int slot0 = xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
-    const int per = (nunits + nslots - 1) / nslots;
-    ubeg = slot0 * per;
-    uend = min(nunits, ubeg + per);
+    static_range(nunits, nslots, slot0, ubeg, uend);
   }
   if (ubeg >= uend) {
     if (dyn) wq_leave(wp, lane);
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeBArgs a, 
 template <int FLAGS>
 void launch_b2(const EdgeBArgs& a, hipStream_t s) {
   const int nunits = (a.E + ROWS - 1) / ROWS;
-  const int grid = std::min((nunits + 3) / 4, mdx_num_cus() * MDX_WPS);
+  const int grid = row_owner_grid(nunits, mdx_num_cus(), MDX_WPS);
   hipLaunchKernelGGL(E2_KERNEL<FLAGS>, dim3(grid), dim3(MDX_WG), EB_CONST_FLOATS * 4, s, a, nunits,
                      make_workq(a.wq, nunits, grid, mdx_num_cus()));
 }

@@ -45,6 +45,8 @@ namespace {
 static_assert(EB_PAIR_FLOATS == split_stream_pair_floats(64), "pair stride of the split Wbl / Wnl packs");
 }  // namespace
 
+RowOwnerShape shape_edge_b2s() { return {ROWS, MDX_WPS}; }  // rows per unit and workgroups per CU of this build (mdx_debug_launch_units_host)
+
 int launch_edge_b2s(const EdgeBArgs& a, hipStream_t s) {
   if (a.E <= 0) return MDX_OK;
   switch (a.flags & ~EB_SPLIT) {

@@ -53,6 +53,8 @@ namespace {
 }  // namespace
 
 // same dispatch contract as launch_edge_a2 (flags without EA_SPLIT)
+RowOwnerShape shape_edge_a2s() { return {ROWS, MDX_WPS}; }  // rows per unit and workgroups per CU of this build (mdx_debug_launch_units_host)
+
 int launch_edge_a2s(const EdgeAArgs& a, hipStream_t s) {
   if (a.E <= 0) return MDX_OK;
   switch (a.flags & ~EA_SPLIT) {

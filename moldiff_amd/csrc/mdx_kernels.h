@@ -326,7 +326,12 @@ int launch_edge_b2(const EdgeBArgs& a, hipStream_t s);
 // split-precision builds of the two (mdx_edge2s.hip, mdx_edge2bs.hip): taken when the flags carry EA_SPLIT / EB_SPLIT
 int launch_edge_a2s(const EdgeAArgs& a, hipStream_t s);
 int launch_edge_b2s(const EdgeBArgs& a, hipStream_t s);
-int mdx_num_cus();
+int mdx_num_cus();  // compute units the launchers size their grids by (the device's, or mdx_debug_set_num_cus' cap)
+// rows per unit and workgroups per CU of each row-owner build, for the work-plan export (mdx_debug_launch_units_host)
+struct RowOwnerShape {
+  int rows, wps;
+};
+RowOwnerShape shape_edge_a2(), shape_edge_a2s(), shape_edge_b2(), shape_edge_b2s(), shape_edge_bwd2(), shape_edge_bwd2s();
 void launch_node(const NodeArgs& a, hipStream_t s);    // dispatches to launch_node_s when the flags carry ND_SPLIT
 void launch_node_s(const NodeArgs& a, hipStream_t s);
 

@@ -49,8 +49,8 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void linear_rows_kernel(const LinA
   auto W = [&](const float* p) { return make_ws(p, lane_off); };
   const int nslots = gridDim.x * 4;
   const int slot = blockIdx.x * 4 + wave;
-  const int per = (nunits + nslots - 1) / nslots;
-  const int ubeg = slot * per, uend = min(nunits, ubeg + per);
+  int ubeg, uend;
+  static_range(nunits, nslots, slot, ubeg, uend);
   if (ubeg >= uend) return;
   WRing ring;
   ring_prime(ring, W(a.Wp));
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void linear_rows_kernel(const LinA
 template <int KG, int FT>
 void launch_lin(const LinArgs& a, hipStream_t s) {
   const int nunits = (a.M + 15) / 16;
-  const int grid = std::min((nunits + 3) / 4, mdx_num_cus() * MDX_WPS);
+  const int grid = row_owner_grid(nunits, mdx_num_cus(), MDX_WPS);
   hipLaunchKernelGGL((linear_rows_kernel<KG, FT>), dim3(grid), dim3(MDX_WG), 0, s, a, nunits);
 }
 

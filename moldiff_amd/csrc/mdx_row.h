@@ -498,21 +498,7 @@ __device__ __forceinline__ const float* lds_put(float* base, const float* __rest
 // wave computes a unit does not enter any result (every unit owns its output rows).
 // The counters live in device memory that is all zero between launches: every wave counts itself out in the pair's second word
 // and the last one of the pair clears both for the next launch on the stream (launches sharing a set must be stream-ordered).
-constexpr int MDX_WQ_STRIDE = 32;  // ints per pair: [0] next unit (relative to the pair's first), [1] waves that have left
-struct WorkQ {
-  int* ctr;     // MDX_WQ_PAIRS lines of MDX_WQ_STRIDE ints; nullptr: static split
-  int npairs;   // min(grid, #CUs): workgroup b belongs to pair b % npairs
-  int nunits;
-};
-constexpr int MDX_WQ_PAIRS = 512;  // lines per counter set (>= #CUs)
-
-inline WorkQ make_workq(int* ctr, int nunits, int grid, int ncus) {
-  WorkQ w{};
-  w.npairs = std::max(1, std::min(std::min(grid, ncus), MDX_WQ_PAIRS));
-  w.ctr = ctr;
-  w.nunits = nunits;
-  return w;
-}
+// (WorkQ, make_workq and the pair's range arithmetic are plain integer logic: mdx_plan.h)
 
 // the pair's view: its counter line, its unit range [beg, end) and its wave count
 struct WorkPair {
@@ -522,12 +508,10 @@ struct WorkPair {
 __device__ __forceinline__ WorkPair wq_pair(const WorkQ& w) {
   const int p = blockIdx.x % w.npairs;
   const int ri = xcd_remap(p, w.npairs);  // ranges in XCD order: neighbouring units (same molecule, same node rows) share an L2
-  const int q = w.nunits / w.npairs, r = w.nunits % w.npairs;
   WorkPair k;
   k.line = w.ctr + (size_t)MDX_WQ_STRIDE * p;
-  k.beg = ri * q + min(ri, r);
-  k.end = k.beg + q + (ri < r ? 1 : 0);
-  k.waves = (blockDim.x >> 6) * (gridDim.x / w.npairs + (p < (int)(gridDim.x % w.npairs) ? 1 : 0));
+  wq_range(w, ri, k.beg, k.end);
+  k.waves = wq_waves(w, blockDim.x >> 6, gridDim.x, p);
   return k;
 }
 

@@ -18,6 +18,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "mdx_plan.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define MDX_WG 256
@@ -493,12 +495,4 @@ __device__ __forceinline__ void dot_rows(const f32x4 (&z)[FTW][ET], const float*
   }
 }
 
-// XCD-aware tile remap (MI355X: 8 XCDs, block b is dispatched to XCD b % 8): give every XCD a
-// contiguous range of tiles so neighbouring tiles (same molecule -> same node rows) share an L2.
-// Bijective for any ntiles.
-__device__ __forceinline__ int xcd_remap(int bid, int ntiles) {
-  const int q = ntiles >> 3, r = ntiles & 7;
-  const int xcd = bid & 7, k = bid >> 3;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + k;
-}
+// xcd_remap (XCD-aware tile remap) is plain integer logic: mdx_plan.h
