@@ -103,6 +103,20 @@ int mdx_graph_plan_host(int64_t n_nodes, int64_t n_edges, const int64_t* h_edge_
  * waves the way a full batch does on the whole device.  n <= 0, or n beyond the device's count, restores the device's own.
  * Process-wide; results never depend on it. */
 int mdx_debug_set_num_cus(int32_t n);
+/* Centred packs of the MolDiff denoiser's edge kernels: on = 1 (the default) packs every Linear that feeds
+ * a LayerNorm in edge kernels A and B with the mean over its output features taken out, on = 0 packs the weights as stored; the
+ * handle is re-packed either way (synchronises the device).  The two conventions differ in rounding only.  No effect on a
+ * bond-predictor or plain-network handle.  The weight arena is freed and allocated again: whatever holds device pointers into the
+ * old one -- a captured graph, a live sampler of this handle -- must be re-created after the call. */
+int mdx_debug_set_ln_centred(mdx_model_t model, int32_t on);
+/* Host only: what finalize would upload for the handle's parameters with centred packs on (1) or off (0).  arena: *n_floats floats;
+ * slots: one text line per pack, "kind offset floats F K col0 transposed centred key" (kind d dense, s stream, S split stream,
+ * D split dense, v vector; key "-" where the pack is not cut from one named parameter).  With arena / slots NULL only the sizes are
+ * returned; otherwise *n_floats / *n_slot_bytes are the buffers' capacities on entry.  The handle is not touched. */
+int mdx_debug_pack_host(mdx_model_t model, int32_t ln_centred, float* arena, size_t* n_floats, char* slots, size_t* n_slot_bytes);
+/* The centring itself, on the host alone: W (F x ldw, row-major) -> out, every column's mean over the F rows taken out in float64 and
+ * rounded to float once; *worst = the largest |residual column mean| / (2^-24 max|out[:, k]|) over the columns (<= 1). */
+int mdx_debug_centre_host(const float* W, int32_t F, int32_t ldw, float* out, double* worst);
 /* The static plan edge kernel A's launcher makes for nunits work items on nslots persistent waves: plan[5] = nslots, nf (full
  * rounds), rem (items of the last round), split (0 none, 1, 2), m (units per BondFFN slot of a split round).  Host only. */
 int mdx_debug_work_plan_host(int32_t nunits, int32_t nslots, int32_t can_split, int32_t* plan);

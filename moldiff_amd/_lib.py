@@ -20,6 +20,7 @@ EXPORTS = [
     'mdx_model_set_matrix_path', 'mdx_model_get_matrix_path', 'mdx_model_set_smear_start', 'mdx_gauss_posterior',
     'mdx_graph_create', 'mdx_graph_destroy', 'mdx_graph_plan_host', 'mdx_workspace_bytes',
     'mdx_debug_set_num_cus', 'mdx_debug_work_plan_host', 'mdx_debug_launch_units_host',
+    'mdx_debug_set_ln_centred', 'mdx_debug_centre_host', 'mdx_debug_pack_host',
     'mdx_net_forward', 'mdx_node_block', 'mdx_edge_block', 'mdx_bond_ffn', 'mdx_pos_update', 'mdx_segment_sum',
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
@@ -111,6 +112,9 @@ def lib():
         L.mdx_graph_plan_host.argtypes = [c_int64, c_int64] + [c_void_p] * 7
         L.mdx_debug_set_num_cus.argtypes = [c_int32]
         L.mdx_debug_work_plan_host.argtypes = [c_int32, c_int32, c_int32, c_void_p]
+        L.mdx_debug_set_ln_centred.argtypes = [c_void_p, c_int32]
+        L.mdx_debug_centre_host.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
+        L.mdx_debug_pack_host.argtypes = [c_void_p, c_int32, c_void_p, POINTER(c_size_t), c_void_p, POINTER(c_size_t)]
         L.mdx_debug_launch_units_host.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
         L.mdx_net_forward.argtypes = [c_void_p] * 10 + [c_void_p, c_size_t, c_void_p]
         L.mdx_node_block.argtypes = [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
@@ -383,6 +387,48 @@ class cu_cap:
         check(lib().mdx_debug_set_num_cus(self.prev))
 
 
+class ln_centred:
+    """`with ln_centred(model._engine(), False):` -- TEST AID: re-pack a MolDiff handle with the edge kernels' LayerNorm-feeding layers
+    as stored (False) or centred over their output features (True, the default of every handle), and back to
+    centred on exit.  Synchronises the device.  The two conventions differ in rounding only."""
+
+    def __init__(self, model, on):
+        self.model, self.on = model, bool(on)
+
+    def __enter__(self):
+        check(lib().mdx_debug_set_ln_centred(self.model.h, int(self.on)))
+        return self
+
+    def __exit__(self, *exc):
+        check(lib().mdx_debug_set_ln_centred(self.model.h, 1))
+
+
+def pack_host(model, centred):
+    """What finalize would upload for `model` (a Model whose parameters are set; it need not be finalized) with centred packs on or
+    off -> (arena as a float32 numpy array, [dict(kind, off, n, F, K, col0, transposed, centred, key)] one per pack).  No GPU."""
+    import numpy as np
+    nf, nb = c_size_t(0), c_size_t(0)
+    check(lib().mdx_debug_pack_host(model.h, int(bool(centred)), None, ctypes.byref(nf), None, ctypes.byref(nb)))
+    arena = np.zeros(nf.value, dtype=np.float32)
+    buf = ctypes.create_string_buffer(nb.value)
+    check(lib().mdx_debug_pack_host(model.h, int(bool(centred)), arena.ctypes.data, ctypes.byref(nf), buf, ctypes.byref(nb)))
+    slots = []
+    for line in buf.value.decode().splitlines():
+        kind, off, n, F, K, col0, tr, cen, key = line.split(' ', 8)
+        slots.append(dict(kind=kind, off=int(off), n=int(n), F=int(F), K=int(K), col0=int(col0), transposed=bool(int(tr)),
+                          centred=bool(int(cen)), key=None if key == '-' else key))
+    return arena, slots
+
+
+def centre_host(W):
+    """The pack code's centring of a Linear's weight (F, K) on the host: -> (centred float32 array, worst |residual column mean| over
+    its bound 2^-24 max|column|).  No GPU."""
+    W = torch.as_tensor(W).detach().to('cpu', torch.float32).contiguous()
+    out, worst = torch.empty_like(W), ctypes.c_double()
+    check(lib().mdx_debug_centre_host(ptr(W), int(W.shape[0]), int(W.shape[1]), ptr(out), ctypes.byref(worst)))
+    return out, worst.value
+
+
 def work_plan(nunits, nslots, can_split=True):
     """The static plan of edge kernel A's launcher (csrc/mdx_plan.h make_plan) -> dict(nslots, nf, rem, split, m).  No GPU."""
     out = (c_int32 * 5)()
@@ -476,13 +522,17 @@ class Model:
         if float(smear_start) != 0.0:   # GaussianSmearing(start != 0): models/graph.py:330-333
             check(lib().mdx_model_set_smear_start(h, float(smear_start)))
 
-    def upload(self, state_dict, prefix=''):
+    def set_params(self, state_dict, prefix=''):
+        """Hand the parameters to the handle without packing them (upload() = set_params() + finalize).  No GPU."""
         for k, v in state_dict.items():
             if not k.startswith(prefix) or v.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
                 continue
             t = v.detach().to('cpu', torch.float32).contiguous()
             shape = (c_int64 * max(t.dim(), 1))(*t.shape)
             check(lib().mdx_model_set_param(self.h, k[len(prefix):].encode(), ptr(t), shape, t.dim()))
+
+    def upload(self, state_dict, prefix=''):
+        self.set_params(state_dict, prefix)
         check(lib().mdx_model_finalize(self.h))
         # finalize drops a handle back to the exact path when the new weights cannot be held by the split packs (float16 range): the
         # cached name must follow the handle, or a later use_matrix_path('split_f16') would be a silent no-op on the exact path

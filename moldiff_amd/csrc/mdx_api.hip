@@ -97,7 +97,43 @@ struct mdx_model_s {
   int matrix_path = 0;
   bool split_ok = true;
   float split_wmax = 0.f;
+  // Centred packs (PackCtx::centred) for the MolDiff denoiser's edge kernels.  On by default; a test may
+  // turn them off and re-pack (mdx_debug_set_ln_centred).  Never for the bond predictor: its tape keeps pre-LayerNorm values that
+  // the guidance backward re-normalises against the un-centred transposed packs.
+  bool ln_centred = true;
 };
+
+// Centring of a Linear whose output feeds a LayerNorm over its F output features: the mean of W x + b over
+// the features is (column mean of W) . x + mean(b), so with the column means taken out of W (and mean(b) out of b) the
+// pre-activation has mean zero whatever x is, and the kernel's LayerNorm needs no mean (mdx_row.h row_layernorm_centred).  Done in
+// float64 from the fp32 weights and rounded to fp32 once.  What the rounding leaves: each entry is off by at most half an ulp,
+// 2^-24 |w|, so a column's residual mean is at most 2^-24 max|w| of that column -- checked here, column by column; the return value
+// is the worst residual / bound ratio (<= 1 when the pack is good).  W: F x ldw row-major, all ldw columns are centred.
+static double centre_columns(const float* W, int F, int ldw, float* out) {
+  double worst = 0.0;
+  for (int k = 0; k < ldw; ++k) {
+    double mu = 0.0;
+    for (int f = 0; f < F; ++f) mu += (double)W[(size_t)f * ldw + k];
+    mu /= F;
+    double res = 0.0, amax = 0.0;
+    for (int f = 0; f < F; ++f) {
+      const float c = (float)((double)W[(size_t)f * ldw + k] - mu);
+      out[(size_t)f * ldw + k] = c;
+      res += (double)c;
+      amax = std::max(amax, std::fabs((double)c));
+    }
+    const double bound = std::ldexp(amax, -24);
+    res = std::fabs(res / F);
+    if (res > 0.0) worst = std::max(worst, bound > 0.0 ? res / bound : 2.0);
+  }
+  return worst;
+}
+// the same on the host alone, for tests/test_ln_centred_pack.py
+extern "C" int mdx_debug_centre_host(const float* W, int32_t F, int32_t ldw, float* out, double* worst) {
+  if (!W || !out || !worst || F < 1 || ldw < 1) return MDX_ERR_ARG;
+  *worst = centre_columns(W, F, ldw, out);
+  return MDX_OK;
+}
 
 namespace {
 
@@ -116,6 +152,27 @@ struct PackCtx {
   mdx_model_s* m;
   Packer pk;
   std::string missing;
+  // What went where, for mdx_debug_pack_host (tests/test_ln_centred_pack.py reads the arena through it): one record per pack --
+  // kind (d dense, s stream, S split stream, D split dense, v vector), arena offset and size in floats, the packed matrix's F x K, and,
+  // where a wrapper named it (`name`), the parameter it was cut from, the first column, whether it was transposed and whether it
+  // came from a centred copy.
+  struct Slot {
+    char kind;
+    size_t off, n;
+    int F, K, col0, transposed, centred;
+    std::string key;
+  };
+  std::vector<Slot> slots;
+  Slot pending{0, 0, 0, 0, 0, 0, 0, 0, ""};
+  void name(const std::string& key, int col0 = 0, bool transposed = false, bool is_centred = false) {
+    pending.key = key; pending.col0 = col0; pending.transposed = transposed; pending.centred = is_centred;
+  }
+  void rec(char kind, size_t off, size_t n, int F, int K) {
+    Slot sl = pending;
+    sl.kind = kind; sl.off = off; sl.n = n; sl.F = F; sl.K = K;
+    slots.push_back(sl);
+    pending = Slot{0, 0, 0, 0, 0, 0, 0, 0, ""};
+  }
   const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape) {
     auto it = m->params.find(key);
     if (it == m->params.end()) {
@@ -141,11 +198,13 @@ struct PackCtx {
             const int f = 16 * ft + (lane & 15), k = 16 * g + 4 * (lane >> 4) + s;
             o[(((size_t)g * FT + ft) * 64 + lane) * 4 + s] = f < F ? W[(size_t)f * ldw + col0 + k] : 0.f;
           }
+    rec('d', off, (size_t)G * FT * 256, F, K);
     pk.bind(slot, off);
   }
   void packA(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
     const HostTensor* t = get(key, {F, ldw});
     if (!t) return;
+    name(key, col0);
     pack_dense(slot, t->data, F, ldw, col0, K);
   }
   // "stream pack" of the row-owner kernels (mdx_row.h rgemm): the same fragments in consumption order --
@@ -163,12 +222,49 @@ struct PackCtx {
               const int f = 16 * (2 * ftp + j) + (lane & 15), k = 16 * g + 4 * (lane >> 4) + s;
               o[((((size_t)ftp * KG + g) * 2 + j) * 64 + lane) * 4 + s] = f < F ? W[(size_t)f * ldw + col0 + k] : 0.f;
             }
+    rec('s', off, (size_t)FTP * KG * 512 + 4 * 512, F, K);
     pk.bind(slot, off);
   }
-  void packS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
+  // Centred copy of the Linear (wkey: F x ldw, bkey: F) -- centre_columns above -- made once per layer and shared by every pack cut
+  // from it: the stream packs of its column ranges, its time column, its rows of the node table, its bias.
+  struct Centred {
+    std::vector<float> W, b;
+  };
+  std::map<std::string, Centred> cen;
+  std::string centre_bad;  // first layer whose rounded pack missed the residual-mean bound (never, unless the arithmetic above is wrong)
+  const Centred* centred(const std::string& wkey, const std::string& bkey, int F, int ldw) {
+    auto it = cen.find(wkey);
+    if (it != cen.end()) return &it->second;
+    const HostTensor* t = get(wkey, {F, ldw});
+    const HostTensor* bt = get(bkey, {F});
+    if (!t || !bt) return nullptr;
+    Centred c;
+    c.W.resize(t->data.size());
+    c.b.resize(F);
+    const double w1 = centre_columns(t->data.data(), F, ldw, c.W.data());
+    const double w2 = centre_columns(bt->data.data(), F, 1, c.b.data());
+    if (!(w1 <= 1.0 && w2 <= 1.0) && centre_bad.empty()) centre_bad = wkey;
+    return &(cen[wkey] = std::move(c));
+  }
+  // (cbias non-empty: from the layer's centred copy; cbias is the key of its bias)
+  void packS(const float** slot, const std::string& key, int F, int ldw, int col0, int K, const std::string& cbias = "") {
+    if (!cbias.empty()) {
+      if (const Centred* c = centred(key, cbias, F, ldw)) {
+        name(key, col0, false, true);
+        pack_stream(slot, c->W, F, ldw, col0, K);
+      }
+      return;
+    }
     const HostTensor* t = get(key, {F, ldw});
     if (!t) return;
+    name(key, col0);
     pack_stream(slot, t->data, F, ldw, col0, K);
+  }
+  void vec_centred(const float** slot, const std::string& wkey, const std::string& bkey, int F, int ldw) {
+    if (const Centred* c = centred(wkey, bkey, F, ldw)) {
+      name(bkey, 0, false, true);
+      raw(slot, c->b);
+    }
   }
   // split float16 stream pack (mdx_split.h rgemm_s): W = hi + lo 2^-11 with hi = fp16(W), lo = fp16((W - hi) 2^11); half-step hs = (ftp*KG + g)*2 + h carries
   // the fragments of feature tiles 2 ftp + j, j = 0,1 (h = 0: hi, h = 1: lo), 64 lanes x 8 halves each:
@@ -198,6 +294,7 @@ struct PackCtx {
               hbuf[(((hs + 1) * 2 + j) * 64 + lane) * 8 + t] = ul;
             }
     std::memcpy(pk.host.data() + off, hbuf.data(), hbuf.size() * 2);
+    rec('S', off, (size_t)FTP * KG * 2 * 512 + 4 * 512, F, K);
     pk.bind(slot, off);
   }
   // dense split pack of the tile kernels (mdx_node_s.hip gemm_tile_s): 1-KiB fragment index (g*FT + ft)*2 + h, g = k/32, h = 0 hi /
@@ -224,16 +321,26 @@ struct PackCtx {
             hbuf[((fr + 1) * 64 + lane) * 8 + t] = ul;
           }
     std::memcpy(pk.host.data() + off, hbuf.data(), hbuf.size() * 2);
+    rec('D', off, (size_t)G * FT * 512, F, K);
     pk.bind(slot, off);
   }
   void packDS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
     const HostTensor* t = get(key, {F, ldw});
     if (!t) return;
+    name(key, col0);
     pack_dense_split(slot, t->data, F, ldw, col0, K);
   }
-  void packSS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
+  void packSS(const float** slot, const std::string& key, int F, int ldw, int col0, int K, const std::string& cbias = "") {
+    if (!cbias.empty()) {
+      if (const Centred* c = centred(key, cbias, F, ldw)) {
+        name(key, col0, false, true);
+        pack_stream_split(slot, c->W, F, ldw, col0, K);
+      }
+      return;
+    }
     const HostTensor* t = get(key, {F, ldw});
     if (!t) return;
+    name(key, col0);
     pack_stream_split(slot, t->data, F, ldw, col0, K);
   }
   // transpose pack: out[k][f] = W[f][col0 + k]  (contraction over the forward's output features, zero padded to 16)
@@ -244,6 +351,7 @@ struct PackCtx {
     std::vector<float> Wt((size_t)K * Fp, 0.f);
     for (int k = 0; k < K; ++k)
       for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
+    name(key, col0, true);
     pack_dense(slot, Wt, K, Fp, 0, Fp);
   }
   // transposed stream pack: out[k][f] = W[f][col0 + k] in rgemm consumption order
@@ -254,6 +362,7 @@ struct PackCtx {
     std::vector<float> Wt((size_t)K * Fp, 0.f);
     for (int k = 0; k < K; ++k)
       for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
+    name(key, col0, true);
     pack_stream(slot, Wt, K, Fp, 0, Fp);
   }
   // transposed dense split pack (node_bwd_s_kernel)
@@ -264,6 +373,7 @@ struct PackCtx {
     std::vector<float> Wt((size_t)K * Fp, 0.f);
     for (int k = 0; k < K; ++k)
       for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
+    name(key, col0, true);
     pack_dense_split(slot, Wt, K, Fp, 0, Fp);
   }
   // transposed split stream pack (mdx_bwd2s.hip)
@@ -274,6 +384,7 @@ struct PackCtx {
     std::vector<float> Wt((size_t)K * Fp, 0.f);
     for (int k = 0; k < K; ++k)
       for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
+    name(key, col0, true);
     pack_stream_split(slot, Wt, K, Fp, 0, Fp);
   }
   std::map<int, std::vector<float>> wcat_dense;  // block -> dense (960 x 256) concatenated node-table weights
@@ -282,23 +393,35 @@ struct PackCtx {
     if (!t) return;
     size_t off = pk.reserve(std::max(n, pad_to));
     std::copy(t->data.begin(), t->data.end(), pk.host.begin() + off);
+    name(key);
+    rec('v', off, std::max(n, pad_to), n, 1);
     pk.bind(slot, off);
   }
   void raw(const float** slot, const std::vector<float>& v) {
     size_t off = pk.reserve(v.size());
     std::copy(v.begin(), v.end(), pk.host.begin() + off);
+    rec('v', off, v.size(), (int)v.size(), 1);
     pk.bind(slot, off);
   }
-  void column(const float** slot, const std::string& key, int F, int ldw, int col) {
+  void column(const float** slot, const std::string& key, int F, int ldw, int col, const std::string& cbias = "") {
     const HostTensor* t = get(key, {F, ldw});
     if (!t) return;
+    const std::vector<float>* W = &t->data;
+    if (!cbias.empty()) {
+      const Centred* c = centred(key, cbias, F, ldw);
+      if (!c) return;
+      W = &c->W;
+    }
     std::vector<float> v(F);
-    for (int f = 0; f < F; ++f) v[f] = t->data[(size_t)f * ldw + col];
+    for (int f = 0; f < F; ++f) v[f] = (*W)[(size_t)f * ldw + col];
+    name(key, col, false, !cbias.empty());
     raw(slot, v);
   }
-  void mlp(MlpW* w, const std::string& pre, int in, int hid, int out, int out_pad = 0) {
+  // (centre1: the first layer's bias from its centred copy -- the row-owner kernels read W1 from their own stream packs)
+  void mlp(MlpW* w, const std::string& pre, int in, int hid, int out, int out_pad = 0, bool centre1 = false) {
     packA(&w->W1, pre + ".net.0.weight", hid, in, 0, in);
-    vec(&w->b1, pre + ".net.0.bias", hid);
+    if (centre1) vec_centred(&w->b1, pre + ".net.0.weight", pre + ".net.0.bias", hid, in);
+    else vec(&w->b1, pre + ".net.0.bias", hid);
     vec(&w->g, pre + ".net.1.weight", hid);
     vec(&w->be, pre + ".net.1.bias", hid);
     packA(&w->W2, pre + ".net.3.weight", out, hid, 0, hid);
@@ -306,7 +429,12 @@ struct PackCtx {
   }
 };
 
-int pack_model(mdx_model_s* m) {
+// host_out: pack on the host only -- the arena and the slot records go there, nothing is uploaded and the handle stays unfinalized
+struct HostPack {
+  std::vector<float> arena;
+  std::vector<PackCtx::Slot> slots;
+};
+int pack_model(mdx_model_s* m, HostPack* host_out = nullptr) {
   PackCtx c{m};
   m->split_ok = true;
   m->split_wmax = 0.f;
@@ -314,6 +442,8 @@ int pack_model(mdx_model_s* m) {
   const int ND = MDX_ND, ED = MDX_ED, GIN = ED + ND + 1;  // 321
   const std::string net = cf.kind == MDX_KIND_MOLDIFF ? "denoiser." : cf.kind == MDX_KIND_BONDPRED ? "encoder." : "";
   m->blocks.assign(cf.num_blocks, BlockW{});
+  // centred packs: the denoiser only (mdx_model_s::ln_centred)
+  const bool lnc = m->ln_centred && cf.kind == MDX_KIND_MOLDIFF;
   c.vec(&m->soff, net + "distance_expansion.offset", MDX_NG);
   c.vec(&m->scoef, net + "distance_expansion.coeff", MDX_NG);
   std::vector<float> scalars_bi2(cf.num_blocks, 0.f), scalars_bg2(cf.num_blocks, 0.f);
@@ -325,49 +455,55 @@ int pack_model(mdx_model_s* m) {
     c.packA(&b.ea.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
     c.vec(&b.ea.bemb, net + "edge_embs." + si + ".bias", ED);
     c.packA(&b.ea.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
-    c.vec(&b.ea.bg1, nb + ".gate.net.0.bias", ND);
-    c.column(&b.ea.wtg1, nb + ".gate.net.0.weight", ND, GIN, GIN - 1);
+    // centred when lnc (every addend of a pre-LayerNorm sum, or none): bias key of the layer, empty = as stored
+    const std::string cg = lnc ? nb + ".gate.net.0.bias" : "", ce = lnc ? nb + ".edge_net.net.0.bias" : "";
+    b.ea.lnc = lnc ? 1 : 0;
+    if (lnc) c.vec_centred(&b.ea.bg1, nb + ".gate.net.0.weight", cg, ND, GIN);
+    else c.vec(&b.ea.bg1, nb + ".gate.net.0.bias", ND);
+    c.column(&b.ea.wtg1, nb + ".gate.net.0.weight", ND, GIN, GIN - 1, cg);
     c.vec(&b.ea.gg, nb + ".gate.net.1.weight", ND);
     c.vec(&b.ea.gb, nb + ".gate.net.1.bias", ND);
     c.packA(&b.ea.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
     c.vec(&b.ea.bg2, nb + ".gate.net.3.bias", ND);
-    c.mlp(&b.ea.en, nb + ".edge_net", ED, ND, ND);
+    c.mlp(&b.ea.en, nb + ".edge_net", ED, ND, ND, 0, lnc);
     c.packA(&b.ea.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
     c.vec(&b.ea.bm, nb + ".msg_net.bias", ND);
     c.packS(&b.ea.s.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
-    c.packS(&b.ea.s.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
+    c.packS(&b.ea.s.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED, cg);
     c.packS(&b.ea.s.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-    c.packS(&b.ea.s.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED);
+    c.packS(&b.ea.s.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED, ce);
     c.packS(&b.ea.s.W2, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
     c.packS(&b.ea.s.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
     c.packSS(&b.ea.ss.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
-    c.packSS(&b.ea.ss.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
+    c.packSS(&b.ea.ss.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED, cg);
     c.packSS(&b.ea.ss.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-    c.packSS(&b.ea.ss.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED);
+    c.packSS(&b.ea.ss.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED, ce);
     c.packSS(&b.ea.ss.W2, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
     c.packSS(&b.ea.ss.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
     for (int s = 0; s < 2; ++s) {
       FfnW& f = b.ea.ffn[s];
       const std::string fp = eb + (s ? ".bond_ffn_right" : ".bond_ffn_left");
       c.packA(&f.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      c.mlp(&f.inter, fp + ".inter_module", 2 * ED, 2 * ED, ED);
+      const std::string cfg = lnc ? fp + ".gate.net.0.bias" : "", cfi = lnc ? fp + ".inter_module.net.0.bias" : "";
+      c.mlp(&f.inter, fp + ".inter_module", 2 * ED, 2 * ED, ED, 0, lnc);
       c.packA(&f.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-      c.vec(&f.bg1, fp + ".gate.net.0.bias", 32);
-      c.column(&f.wtg1, fp + ".gate.net.0.weight", 32, GIN, GIN - 1);
+      if (lnc) c.vec_centred(&f.bg1, fp + ".gate.net.0.weight", cfg, 32, GIN);
+      else c.vec(&f.bg1, fp + ".gate.net.0.bias", 32);
+      c.column(&f.wtg1, fp + ".gate.net.0.weight", 32, GIN, GIN - 1, cfg);
       c.vec(&f.gg, fp + ".gate.net.1.weight", 32);
       c.vec(&f.gb, fp + ".gate.net.1.bias", 32);
       c.packA(&f.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
       c.vec(&f.bg2, fp + ".gate.net.3.bias", ED);
       FfnS& fs = b.ea.s.ffn[s];
       c.packS(&fs.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      c.packS(&fs.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-      c.packS(&fs.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED);
+      c.packS(&fs.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED, cfg);
+      c.packS(&fs.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED, cfi);
       c.packS(&fs.W2, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
       c.packS(&fs.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
       FfnS& fss = b.ea.ss.ffn[s];
       c.packSS(&fss.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      c.packSS(&fss.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-      c.packSS(&fss.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED);
+      c.packSS(&fss.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED, cfg);
+      c.packSS(&fss.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED, cfi);
       c.packSS(&fss.W2, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
       c.packSS(&fss.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
     }
@@ -393,25 +529,35 @@ int pack_model(mdx_model_s* m) {
     c.packDS(&b.nds.nnW2, nb + ".node_net.net.3.weight", ND, ND, 0, ND);
     {  // concatenated per-node table weights (960 x 256) + bias
       std::vector<float> W((size_t)MDX_NTW * ND, 0.f), bias(MDX_NTW, 0.f);
-      auto put = [&](const std::string& key, int rows, int ldw, int col0, int dst_row, const std::string& bkey) {
+      // (cbias non-empty: rows of the layer's centred copy -- the gates' node parts, gathered by edge kernel A into centred sums)
+      auto put = [&](const std::string& key, int rows, int ldw, int col0, int dst_row, const std::string& bkey,
+                     const std::string& cbias = "") {
         const HostTensor* t = c.get(key, {rows, ldw});
         if (!t) return;
+        const std::vector<float>* src = &t->data;
+        if (!cbias.empty()) {
+          const PackCtx::Centred* cc = c.centred(key, cbias, rows, ldw);
+          if (!cc) return;
+          src = &cc->W;
+        }
         for (int r = 0; r < rows; ++r)
-          for (int k = 0; k < ND; ++k) W[(size_t)(dst_row + r) * ND + k] = t->data[(size_t)r * ldw + col0 + k];
+          for (int k = 0; k < ND; ++k) W[(size_t)(dst_row + r) * ND + k] = (*src)[(size_t)r * ldw + col0 + k];
         if (!bkey.empty()) {
           const HostTensor* bt = c.get(bkey, {rows});
           if (bt) std::copy(bt->data.begin(), bt->data.end(), bias.begin() + dst_row);
         }
       };
       put(nb + ".centroid_lin.weight", ND, ND, 0, MDX_NT_C, nb + ".centroid_lin.bias");
-      put(nb + ".gate.net.0.weight", ND, GIN, ED, MDX_NT_GX, "");
+      put(nb + ".gate.net.0.weight", ND, GIN, ED, MDX_NT_GX, "", cg);
       put(eb + ".bond_ffn_left.node_linear.weight", 2 * ED, ND, 0, MDX_NT_NLL, "");
       put(eb + ".bond_ffn_right.node_linear.weight", 2 * ED, ND, 0, MDX_NT_NLR, "");
       put(eb + ".node_ffn_left.weight", ED, ND, 0, MDX_NT_NFL, eb + ".node_ffn_left.bias");
       put(eb + ".node_ffn_right.weight", ED, ND, 0, MDX_NT_NFR, eb + ".node_ffn_right.bias");
-      put(eb + ".bond_ffn_left.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXL, "");
-      put(eb + ".bond_ffn_right.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXR, "");
+      put(eb + ".bond_ffn_left.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXL, "", lnc ? eb + ".bond_ffn_left.gate.net.0.bias" : "");
+      put(eb + ".bond_ffn_right.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXR, "", lnc ? eb + ".bond_ffn_right.gate.net.0.bias" : "");
+      c.name("wcat." + si, 0, false, lnc);  // (centred: its GX / GXL / GXR rows)
       c.pack_dense(&b.nd.Wcat, W, MDX_NTW, ND, 0, ND);
+      c.name("wcat." + si, 0, false, lnc);
       c.pack_dense_split(&b.nds.Wcat, W, MDX_NTW, ND, 0, ND);
       c.wcat_dense[i] = W;
       c.raw(&b.nd.bcat, bias);
@@ -427,7 +573,10 @@ int pack_model(mdx_model_s* m) {
       c.packA(&b.eb.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
       c.packA(&b.eb.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
       c.packA(&b.eb.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND);
-      c.vec(&b.eb.bi1, el + ".inter_module.net.0.bias", ND);
+      const std::string cpg = lnc ? el + ".gate.net.0.bias" : "", cpi = lnc ? el + ".inter_module.net.0.bias" : "";
+      b.eb.lnc = lnc ? 1 : 0;
+      if (lnc) c.vec_centred(&b.eb.bi1, el + ".inter_module.net.0.weight", cpi, ND, ND);
+      else c.vec(&b.eb.bi1, el + ".inter_module.net.0.bias", ND);
       c.vec(&b.eb.ig, el + ".inter_module.net.1.weight", ND);
       c.vec(&b.eb.ib, el + ".inter_module.net.1.bias", ND);
       if (const HostTensor* t = c.get(el + ".inter_module.net.3.weight", {1, ND})) c.raw(&b.eb.wi2, t->data);
@@ -436,16 +585,17 @@ int pack_model(mdx_model_s* m) {
       c.packA(&b.eb.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED);
       c.packS(&b.eb.s.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
       c.packS(&b.eb.s.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
-      c.packS(&b.eb.s.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND);
-      c.packS(&b.eb.s.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED);
-      c.packS(&b.eb.s.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED);
+      c.packS(&b.eb.s.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND, cpi);
+      c.packS(&b.eb.s.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED, cpg);
+      c.packS(&b.eb.s.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED, cpg);
       c.packSS(&b.eb.ss.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
       c.packSS(&b.eb.ss.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
-      c.packSS(&b.eb.ss.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND);
-      c.packSS(&b.eb.ss.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED);
-      c.packSS(&b.eb.ss.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED);
-      c.vec(&b.eb.bg1, el + ".gate.net.0.bias", 32);
-      c.column(&b.eb.wtg1, el + ".gate.net.0.weight", 32, 2 * ED + 1, 2 * ED);
+      c.packSS(&b.eb.ss.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND, cpi);
+      c.packSS(&b.eb.ss.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED, cpg);
+      c.packSS(&b.eb.ss.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED, cpg);
+      if (lnc) c.vec_centred(&b.eb.bg1, el + ".gate.net.0.weight", cpg, 32, 2 * ED + 1);
+      else c.vec(&b.eb.bg1, el + ".gate.net.0.bias", 32);
+      c.column(&b.eb.wtg1, el + ".gate.net.0.weight", 32, 2 * ED + 1, 2 * ED, cpg);
       c.vec(&b.eb.gg, el + ".gate.net.1.weight", 32);
       c.vec(&b.eb.gb, el + ".gate.net.1.bias", 32);
       if (const HostTensor* t = c.get(el + ".gate.net.3.weight", {1, 32})) c.raw(&b.eb.wg2, t->data);
@@ -569,6 +719,12 @@ int pack_model(mdx_model_s* m) {
     }
   }
   if (!c.missing.empty()) return fail(MDX_ERR_STATE, "missing or mis-shaped parameter: %s", c.missing.c_str());
+  if (!c.centre_bad.empty()) return fail(MDX_ERR_STATE, "centred pack of %s misses its residual-mean bound", c.centre_bad.c_str());
+  if (host_out) {
+    host_out->arena = std::move(c.pk.host);
+    host_out->slots = std::move(c.slots);
+    return MDX_OK;
+  }
   if (m->arena) hipFree(m->arena);
   m->arena = nullptr;
   m->arena_floats = c.pk.host.size();
@@ -643,6 +799,47 @@ extern "C" int mdx_model_set_matrix_path(mdx_model_t m, int32_t path) {
                   (double)m->split_wmax);
   }
   m->matrix_path = path;
+  return MDX_OK;
+}
+// TEST AID: pack the denoiser's edge-kernel layers centred (1, the default) or as stored (0) and re-pack the handle, so that a test
+// can run both conventions on one handle.  Not a tuning switch: the two differ in the last bits only.  The arena is freed and
+// allocated again, so whatever cached device pointers into it (a captured graph, a live sampler) must be re-created afterwards.
+extern "C" int mdx_debug_set_ln_centred(mdx_model_t m, int32_t on) {
+  if (!m) return fail(MDX_ERR_ARG, "null model");
+  if (!m->finalized) return fail(MDX_ERR_STATE, "model not finalized (call mdx_model_finalize)");
+  if (hipDeviceSynchronize() != hipSuccess) return fail(MDX_ERR_HIP, "device synchronize failed");  // the old arena may still be read
+  m->ln_centred = on != 0;
+  return pack_model(m);  // (the matrix path is kept: pack_model only leaves the split path when the weights do not fit it)
+}
+// TEST AID, host only: what pack_model would upload for this handle's parameters with centred packs on or off -- the arena (floats)
+// and one text line per pack, "kind offset floats F K col0 transposed centred key" (PackCtx::Slot).  Call with arena / slots null to
+// get the sizes.  The handle itself is not touched.
+extern "C" int mdx_debug_pack_host(mdx_model_t m, int32_t ln_centred, float* arena, size_t* n_floats, char* slots, size_t* n_slot_bytes) {
+  if (!m || !n_floats || !n_slot_bytes) return fail(MDX_ERR_ARG, "null argument");
+  mdx_model_s tmp;
+  tmp.cfg = m->cfg;
+  tmp.params = m->params;
+  tmp.ln_centred = ln_centred != 0;
+  HostPack hp;
+  const int rc = pack_model(&tmp, &hp);
+  if (rc != MDX_OK) return rc;
+  std::string txt;
+  for (const auto& sl : hp.slots) {
+    char line[512];
+    snprintf(line, sizeof(line), "%c %zu %zu %d %d %d %d %d %s\n", sl.kind, sl.off, sl.n, sl.F, sl.K, sl.col0, sl.transposed, sl.centred,
+             sl.key.empty() ? "-" : sl.key.c_str());
+    txt += line;
+  }
+  if (arena) {
+    if (*n_floats < hp.arena.size()) return fail(MDX_ERR_ARG, "arena buffer too small");
+    std::memcpy(arena, hp.arena.data(), hp.arena.size() * sizeof(float));
+  }
+  if (slots) {
+    if (*n_slot_bytes < txt.size() + 1) return fail(MDX_ERR_ARG, "slot buffer too small");
+    std::memcpy(slots, txt.c_str(), txt.size() + 1);
+  }
+  *n_floats = hp.arena.size();
+  *n_slot_bytes = txt.size() + 1;
   return MDX_OK;
 }
 extern "C" int mdx_model_set_smear_start(mdx_model_t m, float start) {

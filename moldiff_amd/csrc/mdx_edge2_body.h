@@ -38,6 +38,8 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
   // the tape is read back by the backward a whole forward later: streaming (non-temporal) stores keep its 870 MB per launch from
   // displacing weights and node rows in L2 (guided step 26.00 -> 25.90 ms)
   constexpr bool TAPE_NT = do_tape;
+  // centred packs (mdx_row.h row_layernorm_centred): never with the tape, whose pre-LayerNorm values the backward re-normalises
+  const bool lnc = !do_tape && a.w.lnc;
 #define TAPE_ST(p, v) do { if (TAPE_NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); else stg4(p, v); } while (0)
   // rows of item u: RR graph-aligned units of the plan's table, one per row tile (EA_AGG; load_tile_units, mdx_row.h), or 16 RR
   // consecutive rows of the batch
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
       STAMP(3);
       E2_GEMM(4, 16)(y, hx, W(S.Wg1e), ring, W(S.Wg2));
       STAMP(4);
-      row_layernorm<16, RR>(y, c_gg, c_gb, q);
+      row_layernorm_sel<16, RR>(lnc, y, c_gg, c_gb, q);
       {
         E2_OPERAND(16, ys, y);
         row_bias<16, RR>(z, c_bg2, q);
@@ -199,7 +201,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
       STAMP(7);
       E2_GEMM(4, 16)(y, hx, W(S.W1), ring, W(S.W2));
       STAMP(8);
-      row_layernorm<16, RR>(y, c_eg, c_ebe, q);
+      row_layernorm_sel<16, RR>(lnc, y, c_eg, c_ebe, q);
       {
         E2_OPERAND(16, ys, y);
         row_bias<16, RR>(z, c_eb2, q);
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
         mul_inplace<8>(bl, nl);
         E2_GEMM(4, 2)(g1, hx, W(ws.Wg1e), ring, W(ws.W1));
         STAMP(16 + 10 * s);
-        row_layernorm<2, RR>(g1, f_gg[s], f_gb[s], q);
+        row_layernorm_sel<2, RR>(lnc, g1, f_gg[s], f_gb[s], q);
         f32x4 h[8][RR];
         {
           E2_OPERAND(8, bs, bl);
@@ -287,7 +289,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeAArgs a, 
           STAMP(18 + 10 * s);
         }
         if constexpr (do_tape_ffn) row_store<8, RR, TAPE_NT>(h, a.tH1[s], t.row, t.valid, 128, q);
-        row_layernorm<8, RR>(h, f_ig[s], f_ibe[s], q);
+        row_layernorm_sel<8, RR>(lnc, h, f_ig[s], f_ibe[s], q);
         f32x4 o[4][RR], g2[4][RR];
         {
           E2_OPERAND(8, hs, h);

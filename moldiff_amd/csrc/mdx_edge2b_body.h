@@ -23,6 +23,9 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeBArgs a, 
   const unsigned lane_off = 16u * lane;
   auto W = [&](const float* p) { return make_ws(p, lane_off); };
   const EdgeBS& S = a.w.E2_S;  // stream packs of this build
+  // centred packs of the PosUpdate gate and inter layers (mdx_row.h row_layernorm_centred).  The EdgeBlock tail's LayerNorm keeps
+  // the two-pass form: its addends SL / SR are sums of gated products, which no weight pack can centre.
+  const bool lnc = a.w.lnc;
 
   float* cb = smem;
   const float *c_bself = cb, *c_lng = cb + 64, *c_lnb = cb + 128, *c_bout = cb + 192;
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeBArgs a, 
       E2_GEMM(4, 2)(g1, hx, W(S.Wg1h), ring, W(S.Wg1a));
       E2_GEMM(4, 2)(g1, ax, W(S.Wg1a), ring, W(S.Wi1));
       STAMPB(8);
-      row_layernorm<2, RR>(g1, c_gg, c_gb, q);
+      row_layernorm_sel<2, RR>(lnc, g1, c_gg, c_gb, q);
       float gate[RR], wd[RR];
       row_dot<2, RR>(g1, c_wg2, q, gate);
       row_bias<16, RR>(h, c_bi1, q);
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(MDX_WG, MDX_WPS) void E2_KERNEL(const EdgeBArgs a, 
       E2_GEMM(16, 16)(h, x, W(S.Wi1), ring, W(wfirst));
       STAMPB(10);
       row_gather<4, RR>(pr.he, a.Hep, pr.t.row, 64, q);  // next unit's He' rows: their latency hides under the LayerNorm below
-      row_layernorm<16, RR>(h, c_ig, c_ib, q);
+      row_layernorm_sel<16, RR>(lnc, h, c_ig, c_ib, q);
       row_dot<16, RR>(h, c_wi2, q, wd);
       if (q == 0) {
 #pragma unroll

@@ -64,6 +64,9 @@ struct EdgeAW {  // weights of edge kernel A for one block
   FfnW ffn[2];                                     // left, right
   EdgeAS s;
   EdgeAS ss;  // the same streams split into float16 hi / lo halves (mdx_split.h; EA_SPLIT launches)
+  // 1: every Linear that feeds a LayerNorm in this kernel (both gates' and edge_net's / inter's first layers, with their biases, time
+  // columns and the GX / GXL / GXR rows of the node table) was packed centred over its output features (mdx_api.hip PackCtx::centred)
+  int lnc;
 };
 
 struct EdgeBW {  // weights of edge kernel B for one block
@@ -78,6 +81,7 @@ struct EdgeBW {  // weights of edge kernel B for one block
   float bg2;
   EdgeBS s;
   EdgeBS ss;  // split float16 streams (EB_SPLIT launches)
+  int lnc;    // 1: the PosUpdate gate's and inter module's first layers were packed centred (see EdgeAW)
 };
 
 struct NodeW {  // weights of the node kernel

@@ -196,6 +196,41 @@ __device__ __forceinline__ void row_layernorm(f32x4 (&y)[FT][R], const float* __
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// The same LayerNorm + ReLU over a row whose mean over the features is zero by construction: every addend of the pre-activation
+// comes from a centred pack (host: PackCtx::centred, DESIGN.md section 3.1 -- the column means of the weights and the mean of the
+// bias were taken out once, in float64, when the model was packed).  The variance is then sum y^2 / n: one reduction per row
+// instead of two and 4 vector operations per element instead of 7 (on this core every one of them is additive to the MFMA time).
+template <int FT, int R>
+__device__ __forceinline__ void row_layernorm_centred(f32x4 (&y)[FT][R], const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, int q) {
+  constexpr float inv_n = 1.0f / (float)(FT * 16);
+  float rstd[R];
+#pragma unroll
+  for (int rt = 0; rt < R; ++rt) {
+    float s2 = 0.f;
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s2 = fmaf(y[ft][rt][r], y[ft][rt][r], s2);
+    rstd[rt] = 1.0f / sqrtf(red_q(s2) * inv_n + MDX_LN_EPS);
+  }
+#pragma unroll
+  for (int ft = 0; ft < FT; ++ft) {
+    if (ft % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+    const f32x4 gm = ldg4(gamma + 16 * ft + 4 * q), bt = ldg4(beta + 16 * ft + 4 * q);
+#pragma unroll
+    for (int rt = 0; rt < R; ++rt) y[ft][rt] = relu4(y[ft][rt] * splat4(rstd[rt]) * gm + bt);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+// LayerNorm of a layer whose packs may be centred (a wave-uniform property of the model handle)
+template <int FT, int R>
+__device__ __forceinline__ void row_layernorm_sel(bool centred, f32x4 (&y)[FT][R], const float* __restrict__ gamma,
+                                                  const float* __restrict__ beta, int q) {
+  if (centred) row_layernorm_centred<FT, R>(y, gamma, beta, q);
+  else row_layernorm<FT, R>(y, gamma, beta, q);
+}
+
 // ---- backward building blocks (guidance gradient), row-local versions of mdx_tile.h's ln_xhat / ln_apply_relu / ln_relu_bwd ----
 // x (pre-LayerNorm) -> x_hat in place, rstd per row tile
 template <int FT, int R>
