@@ -12,6 +12,7 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_kernels.h"
+#include "mdx_pack.h"
 #include "mdx_plan.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -63,72 +64,25 @@ extern "C" int mdx_device_count(int* count) {
 // ------------------------------------------------------------------------------------------------
 // model
 // ------------------------------------------------------------------------------------------------
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
-
-struct BlockW {
-  EdgeAW ea;
-  EdgeBW eb;
-  NodeW nd;  // mid fields = tail of this block, pre fields = pre-stage of this block
-  NodeWS nds;  // the same matrices as split float16 packs
-};
-
-struct mdx_model_s {
+struct mdx_model_s : ModelW {  // the weight blocks (mdx_pack.h): pointers into `arena` once finalized
   mdx_config cfg;
-  std::map<std::string, HostTensor> params;
+  ParamMap params;
   bool finalized = false;
   float smear_start = 0.f;  // lower clamp of the distance smearing (mdx_model_set_smear_start)
   float* arena = nullptr;  // device
   size_t arena_floats = 0;
-  std::vector<BlockW> blocks;
-  const float *soff = nullptr, *scoef = nullptr;  // distance smearing
-  // heads
-  const float *Wn = nullptr, *We = nullptr, *toff = nullptr, *tcoef = nullptr;
-  MlpW nodedec{}, edgedec{};
-  // bond predictor: decoder + transposed packs for the guidance backward
-  BondDecW dec{};
-  std::vector<EdgeBwdW> ebw;
-  std::vector<NodeBwdW> nbw;
-  std::vector<NodeBwdWS> nbws;
   // matrix path of the row-owner edge kernels: 0 = exact fp32 MFMA (default), 1 = split float16 (mdx_split.h).  Both weight
   // packs are always built; split_ok is false when a weight would overflow the scaled float16 range (the path is then refused).
   int matrix_path = 0;
   bool split_ok = true;
   float split_wmax = 0.f;
-  // Centred packs (PackCtx::centred) for the MolDiff denoiser's edge kernels.  On by default; a test may
-  // turn them off and re-pack (mdx_debug_set_ln_centred).  Never for the bond predictor: its tape keeps pre-LayerNorm values that
+  // Centred packs (mdx_pack.cpp Layer::centred) for the MolDiff denoiser's edge kernels.  On by default; a test
+  // may turn them off and re-pack (mdx_debug_set_ln_centred).  Never for the bond predictor: its tape keeps pre-LayerNorm values that
   // the guidance backward re-normalises against the un-centred transposed packs.
   bool ln_centred = true;
 };
 
-// Centring of a Linear whose output feeds a LayerNorm over its F output features: the mean of W x + b over
-// the features is (column mean of W) . x + mean(b), so with the column means taken out of W (and mean(b) out of b) the
-// pre-activation has mean zero whatever x is, and the kernel's LayerNorm needs no mean (mdx_row.h row_layernorm_centred).  Done in
-// float64 from the fp32 weights and rounded to fp32 once.  What the rounding leaves: each entry is off by at most half an ulp,
-// 2^-24 |w|, so a column's residual mean is at most 2^-24 max|w| of that column -- checked here, column by column; the return value
-// is the worst residual / bound ratio (<= 1 when the pack is good).  W: F x ldw row-major, all ldw columns are centred.
-static double centre_columns(const float* W, int F, int ldw, float* out) {
-  double worst = 0.0;
-  for (int k = 0; k < ldw; ++k) {
-    double mu = 0.0;
-    for (int f = 0; f < F; ++f) mu += (double)W[(size_t)f * ldw + k];
-    mu /= F;
-    double res = 0.0, amax = 0.0;
-    for (int f = 0; f < F; ++f) {
-      const float c = (float)((double)W[(size_t)f * ldw + k] - mu);
-      out[(size_t)f * ldw + k] = c;
-      res += (double)c;
-      amax = std::max(amax, std::fabs((double)c));
-    }
-    const double bound = std::ldexp(amax, -24);
-    res = std::fabs(res / F);
-    if (res > 0.0) worst = std::max(worst, bound > 0.0 ? res / bound : 2.0);
-  }
-  return worst;
-}
-// the same on the host alone, for tests/test_ln_centred_pack.py
+// the centring on the host alone, for tests/test_ln_centred_pack.py
 extern "C" int mdx_debug_centre_host(const float* W, int32_t F, int32_t ldw, float* out, double* worst) {
   if (!W || !out || !worst || F < 1 || ldw < 1) return MDX_ERR_ARG;
   *worst = centre_columns(W, F, ldw, out);
@@ -137,600 +91,20 @@ extern "C" int mdx_debug_centre_host(const float* W, int32_t F, int32_t ldw, flo
 
 namespace {
 
-struct Packer {
-  std::vector<float> host;
-  std::vector<std::pair<const float**, size_t>> fix;  // pointer slot <- arena offset
-  size_t reserve(size_t n) {
-    size_t off = (host.size() + 63) & ~size_t(63);
-    host.resize(off + n, 0.f);
-    return off;
-  }
-  void bind(const float** slot, size_t off) { fix.emplace_back(slot, off); }
-};
-
-struct PackCtx {
-  mdx_model_s* m;
-  Packer pk;
-  std::string missing;
-  // What went where, for mdx_debug_pack_host (tests/test_ln_centred_pack.py reads the arena through it): one record per pack --
-  // kind (d dense, s stream, S split stream, D split dense, v vector), arena offset and size in floats, the packed matrix's F x K, and,
-  // where a wrapper named it (`name`), the parameter it was cut from, the first column, whether it was transposed and whether it
-  // came from a centred copy.
-  struct Slot {
-    char kind;
-    size_t off, n;
-    int F, K, col0, transposed, centred;
-    std::string key;
-  };
-  std::vector<Slot> slots;
-  Slot pending{0, 0, 0, 0, 0, 0, 0, 0, ""};
-  void name(const std::string& key, int col0 = 0, bool transposed = false, bool is_centred = false) {
-    pending.key = key; pending.col0 = col0; pending.transposed = transposed; pending.centred = is_centred;
-  }
-  void rec(char kind, size_t off, size_t n, int F, int K) {
-    Slot sl = pending;
-    sl.kind = kind; sl.off = off; sl.n = n; sl.F = F; sl.K = K;
-    slots.push_back(sl);
-    pending = Slot{0, 0, 0, 0, 0, 0, 0, 0, ""};
-  }
-  const HostTensor* get(const std::string& key, std::initializer_list<int64_t> shape) {
-    auto it = m->params.find(key);
-    if (it == m->params.end()) {
-      if (missing.empty()) missing = key;
-      return nullptr;
-    }
-    std::vector<int64_t> s(shape);
-    if (it->second.shape != s) {
-      if (missing.empty()) missing = key + " (shape mismatch)";
-      return nullptr;
-    }
-    return &it->second;
-  }
-  // dense row-major (F x ldw) -> fragment order for gemm_tile: float index ((g*FT + ft)*64 + lane)*4 + s
-  void pack_dense(const float** slot, const std::vector<float>& W, int F, int ldw, int col0, int K) {
-    const int FT = (F + 15) / 16, G = K / 16;
-    size_t off = pk.reserve((size_t)G * FT * 256);
-    float* o = pk.host.data() + off;
-    for (int g = 0; g < G; ++g)
-      for (int ft = 0; ft < FT; ++ft)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int s = 0; s < 4; ++s) {
-            const int f = 16 * ft + (lane & 15), k = 16 * g + 4 * (lane >> 4) + s;
-            o[(((size_t)g * FT + ft) * 64 + lane) * 4 + s] = f < F ? W[(size_t)f * ldw + col0 + k] : 0.f;
-          }
-    rec('d', off, (size_t)G * FT * 256, F, K);
-    pk.bind(slot, off);
-  }
-  void packA(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    name(key, col0);
-    pack_dense(slot, t->data, F, ldw, col0, K);
-  }
-  // "stream pack" of the row-owner kernels (mdx_row.h rgemm): the same fragments in consumption order --
-  // float index ((((ftp*KG + g)*2 + j)*64 + lane)*4 + s) <- W[16*(2 ftp + j) + (lane & 15)][col0 + 16 g + 4 (lane >> 4) + s];
-  // F is padded to a multiple of 32 with zero rows, plus MDX_RING steps of zero tail so a ring may over-fetch
-  void pack_stream(const float** slot, const std::vector<float>& W, int F, int ldw, int col0, int K) {
-    const int FTP = (F + 31) / 32, KG = K / 16;
-    size_t off = pk.reserve((size_t)FTP * KG * 512 + 4 * 512);  // + MDX_RING_PAD zero steps
-    float* o = pk.host.data() + off;
-    for (int ftp = 0; ftp < FTP; ++ftp)
-      for (int g = 0; g < KG; ++g)
-        for (int j = 0; j < 2; ++j)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int s = 0; s < 4; ++s) {
-              const int f = 16 * (2 * ftp + j) + (lane & 15), k = 16 * g + 4 * (lane >> 4) + s;
-              o[((((size_t)ftp * KG + g) * 2 + j) * 64 + lane) * 4 + s] = f < F ? W[(size_t)f * ldw + col0 + k] : 0.f;
-            }
-    rec('s', off, (size_t)FTP * KG * 512 + 4 * 512, F, K);
-    pk.bind(slot, off);
-  }
-  // Centred copy of the Linear (wkey: F x ldw, bkey: F) -- centre_columns above -- made once per layer and shared by every pack cut
-  // from it: the stream packs of its column ranges, its time column, its rows of the node table, its bias.
-  struct Centred {
-    std::vector<float> W, b;
-  };
-  std::map<std::string, Centred> cen;
-  std::string centre_bad;  // first layer whose rounded pack missed the residual-mean bound (never, unless the arithmetic above is wrong)
-  const Centred* centred(const std::string& wkey, const std::string& bkey, int F, int ldw) {
-    auto it = cen.find(wkey);
-    if (it != cen.end()) return &it->second;
-    const HostTensor* t = get(wkey, {F, ldw});
-    const HostTensor* bt = get(bkey, {F});
-    if (!t || !bt) return nullptr;
-    Centred c;
-    c.W.resize(t->data.size());
-    c.b.resize(F);
-    const double w1 = centre_columns(t->data.data(), F, ldw, c.W.data());
-    const double w2 = centre_columns(bt->data.data(), F, 1, c.b.data());
-    if (!(w1 <= 1.0 && w2 <= 1.0) && centre_bad.empty()) centre_bad = wkey;
-    return &(cen[wkey] = std::move(c));
-  }
-  // (cbias non-empty: from the layer's centred copy; cbias is the key of its bias)
-  void packS(const float** slot, const std::string& key, int F, int ldw, int col0, int K, const std::string& cbias = "") {
-    if (!cbias.empty()) {
-      if (const Centred* c = centred(key, cbias, F, ldw)) {
-        name(key, col0, false, true);
-        pack_stream(slot, c->W, F, ldw, col0, K);
-      }
-      return;
-    }
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    name(key, col0);
-    pack_stream(slot, t->data, F, ldw, col0, K);
-  }
-  void vec_centred(const float** slot, const std::string& wkey, const std::string& bkey, int F, int ldw) {
-    if (const Centred* c = centred(wkey, bkey, F, ldw)) {
-      name(bkey, 0, false, true);
-      raw(slot, c->b);
-    }
-  }
-  // split float16 stream pack (mdx_split.h rgemm_s): W = hi + lo 2^-11 with hi = fp16(W), lo = fp16((W - hi) 2^11); half-step hs = (ftp*KG + g)*2 + h carries
-  // the fragments of feature tiles 2 ftp + j, j = 0,1 (h = 0: hi, h = 1: lo), 64 lanes x 8 halves each:
-  // half index ((hs*2 + j)*64 + lane)*8 + t <- W[16 (2 ftp + j) + (lane & 15)][col0 + 32 g + 16 (t / 4) + 4 (lane >> 4) + t % 4];
-  // F padded to 32 and K to 32 with zeros, plus 4 zero half-steps so a ring may over-fetch.  Same bytes as pack_stream for K % 32 == 0.
-  void pack_stream_split(const float** slot, const std::vector<float>& W, int F, int ldw, int col0, int K) {
-    const int FTP = (F + 31) / 32, KG = (K + 31) / 32;
-    size_t off = pk.reserve((size_t)FTP * KG * 2 * 512 + 4 * 512);
-    const float lo_up = 2048.0f;  // 2^MDX_LO_SHIFT
-    std::vector<uint16_t> hbuf((size_t)FTP * KG * 2 * 1024, 0);
-    for (int ftp = 0; ftp < FTP; ++ftp)
-      for (int g = 0; g < KG; ++g)
-        for (int j = 0; j < 2; ++j)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int t = 0; t < 8; ++t) {
-              const int f = 16 * (2 * ftp + j) + (lane & 15), k = 32 * g + 16 * (t / 4) + 4 * (lane >> 4) + t % 4;
-              const float w = (f < F && k < K) ? W[(size_t)f * ldw + col0 + k] : 0.f;
-              if (!(std::fabs(w) < 65504.0f)) m->split_ok = false;
-              m->split_wmax = std::max(m->split_wmax, std::fabs(w));
-              const _Float16 hi = (_Float16)w;
-              const _Float16 lo = (_Float16)((w - (float)hi) * lo_up);
-              uint16_t uh, ul;
-              std::memcpy(&uh, &hi, 2);
-              std::memcpy(&ul, &lo, 2);
-              const size_t hs = ((size_t)ftp * KG + g) * 2;
-              hbuf[((hs * 2 + j) * 64 + lane) * 8 + t] = uh;
-              hbuf[(((hs + 1) * 2 + j) * 64 + lane) * 8 + t] = ul;
-            }
-    std::memcpy(pk.host.data() + off, hbuf.data(), hbuf.size() * 2);
-    rec('S', off, (size_t)FTP * KG * 2 * 512 + 4 * 512, F, K);
-    pk.bind(slot, off);
-  }
-  // dense split pack of the tile kernels (mdx_node_s.hip gemm_tile_s): 1-KiB fragment index (g*FT + ft)*2 + h, g = k/32, h = 0 hi /
-  // 1 lo (x 2^11); lane (q, c) half t <- W[16 ft + c][col0 + 32 g + 16 (t / 4) + 4 q + t % 4]
-  void pack_dense_split(const float** slot, const std::vector<float>& W, int F, int ldw, int col0, int K) {
-    const int FT = (F + 15) / 16, G = (K + 31) / 32;
-    size_t off = pk.reserve((size_t)G * FT * 512);
-    std::vector<uint16_t> hbuf((size_t)G * FT * 1024, 0);
-    for (int g = 0; g < G; ++g)
-      for (int ft = 0; ft < FT; ++ft)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int t = 0; t < 8; ++t) {
-            const int f = 16 * ft + (lane & 15), k = 32 * g + 16 * (t / 4) + 4 * (lane >> 4) + t % 4;
-            const float w = (f < F && k < K) ? W[(size_t)f * ldw + col0 + k] : 0.f;
-            if (!(std::fabs(w) < 65504.0f)) m->split_ok = false;
-            m->split_wmax = std::max(m->split_wmax, std::fabs(w));
-            const _Float16 hi = (_Float16)w;
-            const _Float16 lo = (_Float16)((w - (float)hi) * 2048.0f);
-            uint16_t uh, ul;
-            std::memcpy(&uh, &hi, 2);
-            std::memcpy(&ul, &lo, 2);
-            const size_t fr = ((size_t)g * FT + ft) * 2;
-            hbuf[(fr * 64 + lane) * 8 + t] = uh;
-            hbuf[((fr + 1) * 64 + lane) * 8 + t] = ul;
-          }
-    std::memcpy(pk.host.data() + off, hbuf.data(), hbuf.size() * 2);
-    rec('D', off, (size_t)G * FT * 512, F, K);
-    pk.bind(slot, off);
-  }
-  void packDS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    name(key, col0);
-    pack_dense_split(slot, t->data, F, ldw, col0, K);
-  }
-  void packSS(const float** slot, const std::string& key, int F, int ldw, int col0, int K, const std::string& cbias = "") {
-    if (!cbias.empty()) {
-      if (const Centred* c = centred(key, cbias, F, ldw)) {
-        name(key, col0, false, true);
-        pack_stream_split(slot, c->W, F, ldw, col0, K);
-      }
-      return;
-    }
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    name(key, col0);
-    pack_stream_split(slot, t->data, F, ldw, col0, K);
-  }
-  // transpose pack: out[k][f] = W[f][col0 + k]  (contraction over the forward's output features, zero padded to 16)
-  void packT(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    const int Fp = (F + 15) / 16 * 16;
-    std::vector<float> Wt((size_t)K * Fp, 0.f);
-    for (int k = 0; k < K; ++k)
-      for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
-    name(key, col0, true);
-    pack_dense(slot, Wt, K, Fp, 0, Fp);
-  }
-  // transposed stream pack: out[k][f] = W[f][col0 + k] in rgemm consumption order
-  void packTS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    const int Fp = (F + 15) / 16 * 16;
-    std::vector<float> Wt((size_t)K * Fp, 0.f);
-    for (int k = 0; k < K; ++k)
-      for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
-    name(key, col0, true);
-    pack_stream(slot, Wt, K, Fp, 0, Fp);
-  }
-  // transposed dense split pack (node_bwd_s_kernel)
-  void packTDS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    const int Fp = (F + 15) / 16 * 16;
-    std::vector<float> Wt((size_t)K * Fp, 0.f);
-    for (int k = 0; k < K; ++k)
-      for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
-    name(key, col0, true);
-    pack_dense_split(slot, Wt, K, Fp, 0, Fp);
-  }
-  // transposed split stream pack (mdx_bwd2s.hip)
-  void packTSS(const float** slot, const std::string& key, int F, int ldw, int col0, int K) {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    const int Fp = (F + 15) / 16 * 16;
-    std::vector<float> Wt((size_t)K * Fp, 0.f);
-    for (int k = 0; k < K; ++k)
-      for (int f = 0; f < F; ++f) Wt[(size_t)k * Fp + f] = t->data[(size_t)f * ldw + col0 + k];
-    name(key, col0, true);
-    pack_stream_split(slot, Wt, K, Fp, 0, Fp);
-  }
-  std::map<int, std::vector<float>> wcat_dense;  // block -> dense (960 x 256) concatenated node-table weights
-  void vec(const float** slot, const std::string& key, int n, int pad_to = 0) {
-    const HostTensor* t = get(key, {n});
-    if (!t) return;
-    size_t off = pk.reserve(std::max(n, pad_to));
-    std::copy(t->data.begin(), t->data.end(), pk.host.begin() + off);
-    name(key);
-    rec('v', off, std::max(n, pad_to), n, 1);
-    pk.bind(slot, off);
-  }
-  void raw(const float** slot, const std::vector<float>& v) {
-    size_t off = pk.reserve(v.size());
-    std::copy(v.begin(), v.end(), pk.host.begin() + off);
-    rec('v', off, v.size(), (int)v.size(), 1);
-    pk.bind(slot, off);
-  }
-  void column(const float** slot, const std::string& key, int F, int ldw, int col, const std::string& cbias = "") {
-    const HostTensor* t = get(key, {F, ldw});
-    if (!t) return;
-    const std::vector<float>* W = &t->data;
-    if (!cbias.empty()) {
-      const Centred* c = centred(key, cbias, F, ldw);
-      if (!c) return;
-      W = &c->W;
-    }
-    std::vector<float> v(F);
-    for (int f = 0; f < F; ++f) v[f] = (*W)[(size_t)f * ldw + col];
-    name(key, col, false, !cbias.empty());
-    raw(slot, v);
-  }
-  // (centre1: the first layer's bias from its centred copy -- the row-owner kernels read W1 from their own stream packs)
-  void mlp(MlpW* w, const std::string& pre, int in, int hid, int out, int out_pad = 0, bool centre1 = false) {
-    packA(&w->W1, pre + ".net.0.weight", hid, in, 0, in);
-    if (centre1) vec_centred(&w->b1, pre + ".net.0.weight", pre + ".net.0.bias", hid, in);
-    else vec(&w->b1, pre + ".net.0.bias", hid);
-    vec(&w->g, pre + ".net.1.weight", hid);
-    vec(&w->be, pre + ".net.1.bias", hid);
-    packA(&w->W2, pre + ".net.3.weight", out, hid, 0, hid);
-    vec(&w->b2, pre + ".net.3.bias", out, out_pad);
-  }
-};
-
-// host_out: pack on the host only -- the arena and the slot records go there, nothing is uploaded and the handle stays unfinalized
-struct HostPack {
-  std::vector<float> arena;
-  std::vector<PackCtx::Slot> slots;
-};
-int pack_model(mdx_model_s* m, HostPack* host_out = nullptr) {
-  PackCtx c{m};
-  m->split_ok = true;
-  m->split_wmax = 0.f;
-  const mdx_config& cf = m->cfg;
-  const int ND = MDX_ND, ED = MDX_ED, GIN = ED + ND + 1;  // 321
-  const std::string net = cf.kind == MDX_KIND_MOLDIFF ? "denoiser." : cf.kind == MDX_KIND_BONDPRED ? "encoder." : "";
-  m->blocks.assign(cf.num_blocks, BlockW{});
-  // centred packs: the denoiser only (mdx_model_s::ln_centred)
-  const bool lnc = m->ln_centred && cf.kind == MDX_KIND_MOLDIFF;
-  c.vec(&m->soff, net + "distance_expansion.offset", MDX_NG);
-  c.vec(&m->scoef, net + "distance_expansion.coeff", MDX_NG);
-  std::vector<float> scalars_bi2(cf.num_blocks, 0.f), scalars_bg2(cf.num_blocks, 0.f);
-  for (int i = 0; i < cf.num_blocks; ++i) {
-    BlockW& b = m->blocks[i];
-    const std::string si = std::to_string(i);
-    const std::string nb = net + "node_blocks_with_edge." + si, eb = net + "edge_blocks." + si, pb = net + "pos_blocks." + si;
-    // ---- edge kernel A
-    c.packA(&b.ea.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
-    c.vec(&b.ea.bemb, net + "edge_embs." + si + ".bias", ED);
-    c.packA(&b.ea.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
-    // centred when lnc (every addend of a pre-LayerNorm sum, or none): bias key of the layer, empty = as stored
-    const std::string cg = lnc ? nb + ".gate.net.0.bias" : "", ce = lnc ? nb + ".edge_net.net.0.bias" : "";
-    b.ea.lnc = lnc ? 1 : 0;
-    if (lnc) c.vec_centred(&b.ea.bg1, nb + ".gate.net.0.weight", cg, ND, GIN);
-    else c.vec(&b.ea.bg1, nb + ".gate.net.0.bias", ND);
-    c.column(&b.ea.wtg1, nb + ".gate.net.0.weight", ND, GIN, GIN - 1, cg);
-    c.vec(&b.ea.gg, nb + ".gate.net.1.weight", ND);
-    c.vec(&b.ea.gb, nb + ".gate.net.1.bias", ND);
-    c.packA(&b.ea.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-    c.vec(&b.ea.bg2, nb + ".gate.net.3.bias", ND);
-    c.mlp(&b.ea.en, nb + ".edge_net", ED, ND, ND, 0, lnc);
-    c.packA(&b.ea.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
-    c.vec(&b.ea.bm, nb + ".msg_net.bias", ND);
-    c.packS(&b.ea.s.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
-    c.packS(&b.ea.s.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED, cg);
-    c.packS(&b.ea.s.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-    c.packS(&b.ea.s.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED, ce);
-    c.packS(&b.ea.s.W2, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
-    c.packS(&b.ea.s.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
-    c.packSS(&b.ea.ss.Wemb, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED + MDX_NG);
-    c.packSS(&b.ea.ss.Wg1e, nb + ".gate.net.0.weight", ND, GIN, 0, ED, cg);
-    c.packSS(&b.ea.ss.Wg2, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-    c.packSS(&b.ea.ss.W1, nb + ".edge_net.net.0.weight", ND, ED, 0, ED, ce);
-    c.packSS(&b.ea.ss.W2, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
-    c.packSS(&b.ea.ss.Wm, nb + ".msg_net.weight", ND, ND, 0, ND);
-    for (int s = 0; s < 2; ++s) {
-      FfnW& f = b.ea.ffn[s];
-      const std::string fp = eb + (s ? ".bond_ffn_right" : ".bond_ffn_left");
-      c.packA(&f.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      const std::string cfg = lnc ? fp + ".gate.net.0.bias" : "", cfi = lnc ? fp + ".inter_module.net.0.bias" : "";
-      c.mlp(&f.inter, fp + ".inter_module", 2 * ED, 2 * ED, ED, 0, lnc);
-      c.packA(&f.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-      if (lnc) c.vec_centred(&f.bg1, fp + ".gate.net.0.weight", cfg, 32, GIN);
-      else c.vec(&f.bg1, fp + ".gate.net.0.bias", 32);
-      c.column(&f.wtg1, fp + ".gate.net.0.weight", 32, GIN, GIN - 1, cfg);
-      c.vec(&f.gg, fp + ".gate.net.1.weight", 32);
-      c.vec(&f.gb, fp + ".gate.net.1.bias", 32);
-      c.packA(&f.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-      c.vec(&f.bg2, fp + ".gate.net.3.bias", ED);
-      FfnS& fs = b.ea.s.ffn[s];
-      c.packS(&fs.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      c.packS(&fs.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED, cfg);
-      c.packS(&fs.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED, cfi);
-      c.packS(&fs.W2, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
-      c.packS(&fs.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-      FfnS& fss = b.ea.ss.ffn[s];
-      c.packSS(&fss.Wbl, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-      c.packSS(&fss.Wg1e, fp + ".gate.net.0.weight", 32, GIN, 0, ED, cfg);
-      c.packSS(&fss.W1, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED, cfi);
-      c.packSS(&fss.W2, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
-      c.packSS(&fss.Wg2, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-    }
-    // ---- edge kernel B
-    c.packA(&b.eb.Wself, eb + ".self_ffn.weight", ED, ED, 0, ED);
-    c.vec(&b.eb.bself, eb + ".self_ffn.bias", ED);
-    c.vec(&b.eb.lng, eb + ".layer_norm.weight", ED);
-    c.vec(&b.eb.lnb, eb + ".layer_norm.bias", ED);
-    c.packA(&b.eb.Wout, eb + ".out_transform.weight", ED, ED, 0, ED);
-    c.vec(&b.eb.bout, eb + ".out_transform.bias", ED);
-    c.packS(&b.eb.s.Wself, eb + ".self_ffn.weight", ED, ED, 0, ED);
-    c.packS(&b.eb.s.Wout, eb + ".out_transform.weight", ED, ED, 0, ED);
-    c.packSS(&b.eb.ss.Wself, eb + ".self_ffn.weight", ED, ED, 0, ED);
-    c.packSS(&b.eb.ss.Wout, eb + ".out_transform.weight", ED, ED, 0, ED);
-    // ---- node kernel
-    c.vec(&b.nd.lng, nb + ".layer_norm.weight", ND);
-    c.vec(&b.nd.lnb, nb + ".layer_norm.bias", ND);
-    c.packA(&b.nd.Wout, nb + ".out_transform.weight", ND, ND, 0, ND);
-    c.vec(&b.nd.bout, nb + ".out_transform.bias", ND);
-    c.mlp(&b.nd.nn, nb + ".node_net", ND, ND, ND);
-    c.packDS(&b.nds.Wout, nb + ".out_transform.weight", ND, ND, 0, ND);
-    c.packDS(&b.nds.nnW1, nb + ".node_net.net.0.weight", ND, ND, 0, ND);
-    c.packDS(&b.nds.nnW2, nb + ".node_net.net.3.weight", ND, ND, 0, ND);
-    {  // concatenated per-node table weights (960 x 256) + bias
-      std::vector<float> W((size_t)MDX_NTW * ND, 0.f), bias(MDX_NTW, 0.f);
-      // (cbias non-empty: rows of the layer's centred copy -- the gates' node parts, gathered by edge kernel A into centred sums)
-      auto put = [&](const std::string& key, int rows, int ldw, int col0, int dst_row, const std::string& bkey,
-                     const std::string& cbias = "") {
-        const HostTensor* t = c.get(key, {rows, ldw});
-        if (!t) return;
-        const std::vector<float>* src = &t->data;
-        if (!cbias.empty()) {
-          const PackCtx::Centred* cc = c.centred(key, cbias, rows, ldw);
-          if (!cc) return;
-          src = &cc->W;
-        }
-        for (int r = 0; r < rows; ++r)
-          for (int k = 0; k < ND; ++k) W[(size_t)(dst_row + r) * ND + k] = (*src)[(size_t)r * ldw + col0 + k];
-        if (!bkey.empty()) {
-          const HostTensor* bt = c.get(bkey, {rows});
-          if (bt) std::copy(bt->data.begin(), bt->data.end(), bias.begin() + dst_row);
-        }
-      };
-      put(nb + ".centroid_lin.weight", ND, ND, 0, MDX_NT_C, nb + ".centroid_lin.bias");
-      put(nb + ".gate.net.0.weight", ND, GIN, ED, MDX_NT_GX, "", cg);
-      put(eb + ".bond_ffn_left.node_linear.weight", 2 * ED, ND, 0, MDX_NT_NLL, "");
-      put(eb + ".bond_ffn_right.node_linear.weight", 2 * ED, ND, 0, MDX_NT_NLR, "");
-      put(eb + ".node_ffn_left.weight", ED, ND, 0, MDX_NT_NFL, eb + ".node_ffn_left.bias");
-      put(eb + ".node_ffn_right.weight", ED, ND, 0, MDX_NT_NFR, eb + ".node_ffn_right.bias");
-      put(eb + ".bond_ffn_left.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXL, "", lnc ? eb + ".bond_ffn_left.gate.net.0.bias" : "");
-      put(eb + ".bond_ffn_right.gate.net.0.weight", 32, GIN, ED, MDX_NT_GXR, "", lnc ? eb + ".bond_ffn_right.gate.net.0.bias" : "");
-      c.name("wcat." + si, 0, false, lnc);  // (centred: its GX / GXL / GXR rows)
-      c.pack_dense(&b.nd.Wcat, W, MDX_NTW, ND, 0, ND);
-      c.name("wcat." + si, 0, false, lnc);
-      c.pack_dense_split(&b.nds.Wcat, W, MDX_NTW, ND, 0, ND);
-      c.wcat_dense[i] = W;
-      c.raw(&b.nd.bcat, bias);
-    }
-    if (cf.update_pos) {
-      c.mlp(&b.nd.left, pb + ".left_lin_edge", ND, ED, ED);
-      c.mlp(&b.nd.right, pb + ".right_lin_edge", ND, ED, ED);
-      c.packDS(&b.nds.leftW1, pb + ".left_lin_edge.net.0.weight", ED, ND, 0, ND);
-      c.packDS(&b.nds.leftW2, pb + ".left_lin_edge.net.3.weight", ED, ED, 0, ED);
-      c.packDS(&b.nds.rightW1, pb + ".right_lin_edge.net.0.weight", ED, ND, 0, ND);
-      c.packDS(&b.nds.rightW2, pb + ".right_lin_edge.net.3.weight", ED, ED, 0, ED);
-      const std::string el = pb + ".edge_lin";
-      c.packA(&b.eb.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
-      c.packA(&b.eb.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
-      c.packA(&b.eb.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND);
-      const std::string cpg = lnc ? el + ".gate.net.0.bias" : "", cpi = lnc ? el + ".inter_module.net.0.bias" : "";
-      b.eb.lnc = lnc ? 1 : 0;
-      if (lnc) c.vec_centred(&b.eb.bi1, el + ".inter_module.net.0.weight", cpi, ND, ND);
-      else c.vec(&b.eb.bi1, el + ".inter_module.net.0.bias", ND);
-      c.vec(&b.eb.ig, el + ".inter_module.net.1.weight", ND);
-      c.vec(&b.eb.ib, el + ".inter_module.net.1.bias", ND);
-      if (const HostTensor* t = c.get(el + ".inter_module.net.3.weight", {1, ND})) c.raw(&b.eb.wi2, t->data);
-      if (const HostTensor* t = c.get(el + ".inter_module.net.3.bias", {1})) b.eb.bi2 = t->data[0];
-      c.packA(&b.eb.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED);
-      c.packA(&b.eb.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED);
-      c.packS(&b.eb.s.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
-      c.packS(&b.eb.s.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
-      c.packS(&b.eb.s.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND, cpi);
-      c.packS(&b.eb.s.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED, cpg);
-      c.packS(&b.eb.s.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED, cpg);
-      c.packSS(&b.eb.ss.Wbl, el + ".bond_linear.weight", ND, ED, 0, ED);
-      c.packSS(&b.eb.ss.Wnl, el + ".node_linear.weight", ND, ED, 0, ED);
-      c.packSS(&b.eb.ss.Wi1, el + ".inter_module.net.0.weight", ND, ND, 0, ND, cpi);
-      c.packSS(&b.eb.ss.Wg1h, el + ".gate.net.0.weight", 32, 2 * ED + 1, 0, ED, cpg);
-      c.packSS(&b.eb.ss.Wg1a, el + ".gate.net.0.weight", 32, 2 * ED + 1, ED, ED, cpg);
-      if (lnc) c.vec_centred(&b.eb.bg1, el + ".gate.net.0.weight", cpg, 32, 2 * ED + 1);
-      else c.vec(&b.eb.bg1, el + ".gate.net.0.bias", 32);
-      c.column(&b.eb.wtg1, el + ".gate.net.0.weight", 32, 2 * ED + 1, 2 * ED, cpg);
-      c.vec(&b.eb.gg, el + ".gate.net.1.weight", 32);
-      c.vec(&b.eb.gb, el + ".gate.net.1.bias", 32);
-      if (const HostTensor* t = c.get(el + ".gate.net.3.weight", {1, 32})) c.raw(&b.eb.wg2, t->data);
-      if (const HostTensor* t = c.get(el + ".gate.net.3.bias", {1})) b.eb.bg2 = t->data[0];
-    }
-  }
-  if (cf.kind == MDX_KIND_MOLDIFF || cf.kind == MDX_KIND_BONDPRED) {
-    const int nd_emb = ND - cf.time_dim, ed_emb = ED - cf.time_dim;
-    const int ein = cf.kind == MDX_KIND_MOLDIFF ? cf.num_edge_types : 2 * cf.num_node_types;
-    if (const HostTensor* t = c.get("node_embedder.weight", {nd_emb, cf.num_node_types})) c.raw(&m->Wn, t->data);
-    if (const HostTensor* t = c.get("edge_embedder.weight", {ed_emb, ein})) c.raw(&m->We, t->data);
-    const std::string te = cf.kind == MDX_KIND_MOLDIFF ? "time_emb.0." : "time_emb.";
-    if (cf.time_dim > 0) {  // 0: the time-free bond predictor (models/bond_predictor.py:27-31) has no time embedding
-      c.vec(&m->toff, te + "offset", cf.time_dim);
-      c.vec(&m->tcoef, te + "coeff", cf.time_dim);
-    }
-  }
-  if (cf.kind == MDX_KIND_MOLDIFF) {
-    c.mlp(&m->nodedec, "node_decoder", ND, ND, cf.num_node_types, 16);
-    c.mlp(&m->edgedec, "edge_decoder", ED, ED, cf.num_edge_types, 16);
-  }
-  if (cf.kind == MDX_KIND_BONDPRED) {
-    const std::string d = "edge_decoder.net.";
-    BondDecW& w = m->dec;
-    c.packA(&w.W1e, d + "0.weight", ED, ED + ND, 0, ED);
-    c.packA(&w.W1n, d + "0.weight", ED, ED + ND, ED, ND);
-    c.vec(&w.b1, d + "0.bias", ED);
-    c.vec(&w.g1, d + "1.weight", ED);
-    c.vec(&w.be1, d + "1.bias", ED);
-    c.packA(&w.W2, d + "3.weight", ED, ED, 0, ED);
-    c.vec(&w.b2, d + "3.bias", ED);
-    c.vec(&w.g2, d + "4.weight", ED);
-    c.vec(&w.be2, d + "4.bias", ED);
-    c.packA(&w.W3, d + "6.weight", cf.num_edge_types, ED, 0, ED);
-    c.vec(&w.b3, d + "6.bias", cf.num_edge_types, 16);
-    c.packT(&w.W1eT, d + "0.weight", ED, ED + ND, 0, ED);
-    c.packT(&w.W1nT, d + "0.weight", ED, ED + ND, ED, ND);
-    c.packT(&w.W2T, d + "3.weight", ED, ED, 0, ED);
-    c.packT(&w.W3T, d + "6.weight", cf.num_edge_types, ED, 0, ED);
-    // transposed packs for the data-gradient backward (guidance)
-    m->ebw.assign(cf.num_blocks, EdgeBwdW{});
-    m->nbw.assign(cf.num_blocks, NodeBwdW{});
-    m->nbws.assign(cf.num_blocks, NodeBwdWS{});
-    for (int i = 0; i < cf.num_blocks; ++i) {
-      const std::string si = std::to_string(i);
-      const std::string nb = net + "node_blocks_with_edge." + si, eb = net + "edge_blocks." + si;
-      EdgeBwdW& e = m->ebw[i];
-      c.packT(&e.WembHT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED);
-      c.packT(&e.WembDT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, ED, MDX_NG);
-      c.packT(&e.Wg1eT, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
-      c.packT(&e.Wg2T, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-      c.packT(&e.W1T, nb + ".edge_net.net.0.weight", ND, ED, 0, ED);
-      c.packT(&e.W2T, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
-      c.packT(&e.WmT, nb + ".msg_net.weight", ND, ND, 0, ND);
-      for (int s = 0; s < 2; ++s) {
-        const std::string fp = eb + (s ? ".bond_ffn_right" : ".bond_ffn_left");
-        FfnWT& f = e.ffn[s];
-        c.packT(&f.WblT, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-        c.packT(&f.Wi1T, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED);
-        c.packT(&f.Wi2T, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
-        c.packT(&f.Wg1eT, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-        c.packT(&f.Wg2T, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-      }
-      c.packT(&e.WselfT, eb + ".self_ffn.weight", ED, ED, 0, ED);
-      c.packT(&e.WoutT, eb + ".out_transform.weight", ED, ED, 0, ED);
-      // the same transposes as stream packs for the row-owner backward kernel
-      c.packTS(&e.s.WembHT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED);
-      c.packTS(&e.s.WembDT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, ED, MDX_NG);
-      c.packTS(&e.s.Wg1eT, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
-      c.packTS(&e.s.Wg2T, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-      c.packTS(&e.s.W1T, nb + ".edge_net.net.0.weight", ND, ED, 0, ED);
-      c.packTS(&e.s.W2T, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
-      c.packTS(&e.s.WmT, nb + ".msg_net.weight", ND, ND, 0, ND);
-      c.packTS(&e.s.WselfT, eb + ".self_ffn.weight", ED, ED, 0, ED);
-      c.packTS(&e.s.WoutT, eb + ".out_transform.weight", ED, ED, 0, ED);
-      for (int s = 0; s < 2; ++s) {
-        const std::string fp = eb + (s ? ".bond_ffn_right" : ".bond_ffn_left");
-        FfnTS& f = e.s.ffn[s];
-        c.packTS(&f.WblT, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-        c.packTS(&f.Wi1T, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED);
-        c.packTS(&f.Wi2T, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
-        c.packTS(&f.Wg1eT, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-        c.packTS(&f.Wg2T, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-      }
-      // ... and as split float16 stream packs for the split build of that kernel (mdx_bwd2s.hip)
-      c.packTSS(&e.ss.WembHT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, 0, ED);
-      c.packTSS(&e.ss.WembDT, net + "edge_embs." + si + ".weight", ED, ED + MDX_NG, ED, MDX_NG);
-      c.packTSS(&e.ss.Wg1eT, nb + ".gate.net.0.weight", ND, GIN, 0, ED);
-      c.packTSS(&e.ss.Wg2T, nb + ".gate.net.3.weight", ND, ND, 0, ND);
-      c.packTSS(&e.ss.W1T, nb + ".edge_net.net.0.weight", ND, ED, 0, ED);
-      c.packTSS(&e.ss.W2T, nb + ".edge_net.net.3.weight", ND, ND, 0, ND);
-      c.packTSS(&e.ss.WmT, nb + ".msg_net.weight", ND, ND, 0, ND);
-      c.packTSS(&e.ss.WselfT, eb + ".self_ffn.weight", ED, ED, 0, ED);
-      c.packTSS(&e.ss.WoutT, eb + ".out_transform.weight", ED, ED, 0, ED);
-      for (int s = 0; s < 2; ++s) {
-        const std::string fp = eb + (s ? ".bond_ffn_right" : ".bond_ffn_left");
-        FfnTS& f = e.ss.ffn[s];
-        c.packTSS(&f.WblT, fp + ".bond_linear.weight", 2 * ED, ED, 0, ED);
-        c.packTSS(&f.Wi1T, fp + ".inter_module.net.0.weight", 2 * ED, 2 * ED, 0, 2 * ED);
-        c.packTSS(&f.Wi2T, fp + ".inter_module.net.3.weight", ED, 2 * ED, 0, 2 * ED);
-        c.packTSS(&f.Wg1eT, fp + ".gate.net.0.weight", 32, GIN, 0, ED);
-        c.packTSS(&f.Wg2T, fp + ".gate.net.3.weight", ED, 32, 0, 32);
-      }
-      NodeBwdW& n = m->nbw[i];
-      c.packT(&n.WoutT, nb + ".out_transform.weight", ND, ND, 0, ND);
-      c.packT(&n.W1T, nb + ".node_net.net.0.weight", ND, ND, 0, ND);
-      c.packT(&n.W2T, nb + ".node_net.net.3.weight", ND, ND, 0, ND);
-      const std::vector<float>& Wcat = c.wcat_dense[i];
-      if (!Wcat.empty())
-        for (int ch = 0; ch < 4; ++ch) {
-          const int kc = ch < 3 ? 256 : 192;
-          std::vector<float> Mt((size_t)ND * kc);
-          for (int f = 0; f < ND; ++f)
-            for (int k = 0; k < kc; ++k) Mt[(size_t)f * kc + k] = Wcat[(size_t)(256 * ch + k) * ND + f];
-          c.pack_dense(&n.WcatT[ch], Mt, ND, kc, 0, kc);
-          c.pack_dense_split(&m->nbws[i].WcatT[ch], Mt, ND, kc, 0, kc);
-        }
-      c.packTDS(&m->nbws[i].WoutT, nb + ".out_transform.weight", ND, ND, 0, ND);
-      c.packTDS(&m->nbws[i].W1T, nb + ".node_net.net.0.weight", ND, ND, 0, ND);
-      c.packTDS(&m->nbws[i].W2T, nb + ".node_net.net.3.weight", ND, ND, 0, ND);
-    }
-  }
-  if (!c.missing.empty()) return fail(MDX_ERR_STATE, "missing or mis-shaped parameter: %s", c.missing.c_str());
-  if (!c.centre_bad.empty()) return fail(MDX_ERR_STATE, "centred pack of %s misses its residual-mean bound", c.centre_bad.c_str());
-  if (host_out) {
-    host_out->arena = std::move(c.pk.host);
-    host_out->slots = std::move(c.slots);
-    return MDX_OK;
-  }
+// Packs the handle's parameters on the host (mdx_pack.cpp), uploads the arena and binds the weight blocks to it.
+int finalize_model(mdx_model_s* m) {
+  PackResult pk;
+  pack_model(m->cfg, m->params, m->ln_centred, m, &pk);
+  m->finalized = false;
+  if (!pk.error.empty()) return fail(MDX_ERR_STATE, "%s", pk.error.c_str());
+  m->split_ok = pk.split_ok;
+  m->split_wmax = pk.split_wmax;
   if (m->arena) hipFree(m->arena);
   m->arena = nullptr;
-  m->arena_floats = c.pk.host.size();
+  m->arena_floats = pk.arena.size();
   HIPCHK(hipMalloc((void**)&m->arena, m->arena_floats * sizeof(float)));
-  HIPCHK(hipMemcpy(m->arena, c.pk.host.data(), m->arena_floats * sizeof(float), hipMemcpyHostToDevice));
-  for (auto& f : c.pk.fix) *f.first = m->arena + f.second;
+  HIPCHK(hipMemcpy(m->arena, pk.arena.data(), m->arena_floats * sizeof(float), hipMemcpyHostToDevice));
+  for (auto& f : pk.fix) *f.first = m->arena + f.second;
   m->finalized = true;
   // a handle re-finalized with weights the split path cannot hold falls back to the exact path instead of silently running
   // float16 operands that overflowed at pack time (the caller's next mdx_model_set_matrix_path(split) is refused as usual)
@@ -782,7 +156,7 @@ extern "C" int mdx_model_set_param(mdx_model_t m, const char* key, const float* 
 
 extern "C" int mdx_model_finalize(mdx_model_t m) {
   if (!m) return fail(MDX_ERR_ARG, "null model");
-  return pack_model(m);
+  return finalize_model(m);
 }
 
 // Matrix path of the row-owner edge kernels (the products of models/common.py:181-201 MLP / models/graph.py:29-55,133-141,268-295
@@ -809,20 +183,17 @@ extern "C" int mdx_debug_set_ln_centred(mdx_model_t m, int32_t on) {
   if (!m->finalized) return fail(MDX_ERR_STATE, "model not finalized (call mdx_model_finalize)");
   if (hipDeviceSynchronize() != hipSuccess) return fail(MDX_ERR_HIP, "device synchronize failed");  // the old arena may still be read
   m->ln_centred = on != 0;
-  return pack_model(m);  // (the matrix path is kept: pack_model only leaves the split path when the weights do not fit it)
+  return finalize_model(m);  // (the matrix path is kept: finalize_model only leaves the split path when the weights do not fit it)
 }
-// TEST AID, host only: what pack_model would upload for this handle's parameters with centred packs on or off -- the arena (floats)
-// and one text line per pack, "kind offset floats F K col0 transposed centred key" (PackCtx::Slot).  Call with arena / slots null to
-// get the sizes.  The handle itself is not touched.
+// TEST AID, host only: what finalize would upload for this handle's parameters with centred packs on or off -- the arena (floats)
+// and one text line per pack, "kind offset floats F K col0 transposed centred key" (mdx_pack.h PackSlot).  Call with arena / slots null
+// to get the sizes.  The handle itself is not touched.
 extern "C" int mdx_debug_pack_host(mdx_model_t m, int32_t ln_centred, float* arena, size_t* n_floats, char* slots, size_t* n_slot_bytes) {
   if (!m || !n_floats || !n_slot_bytes) return fail(MDX_ERR_ARG, "null argument");
-  mdx_model_s tmp;
-  tmp.cfg = m->cfg;
-  tmp.params = m->params;
-  tmp.ln_centred = ln_centred != 0;
-  HostPack hp;
-  const int rc = pack_model(&tmp, &hp);
-  if (rc != MDX_OK) return rc;
+  ModelW w;
+  PackResult hp;
+  pack_model(m->cfg, m->params, ln_centred != 0, &w, &hp);
+  if (!hp.error.empty()) return fail(MDX_ERR_STATE, "%s", hp.error.c_str());
   std::string txt;
   for (const auto& sl : hp.slots) {
     char line[512];
@@ -1952,7 +1323,7 @@ extern "C" int mdx_bondpred_backward(mdx_model_t m, mdx_graph_t g, const float* 
     if (i == nb - 1) {
       EdgeTailBwdArgs et{};
       et.E = E; et.l = g->left; et.r = g->right; et.te = tp.te; et.Hep = k.Hep; et.gHe = gHe; et.SL = k.SL; et.SR = k.SR;
-      et.NT = k.NT; et.GU = GU; et.GHEP = GHEP; et.w = m->blocks[i].eb; et.WselfT = m->ebw[i].WselfT; et.WoutT = m->ebw[i].WoutT;
+      et.NT = k.NT; et.GU = GU; et.GHEP = GHEP; et.w = m->blocks[i].eb;
       et.sWselfT = m->ebw[i].s.WselfT; et.sWoutT = m->ebw[i].s.WoutT; et.wq = wq;
       et.ssWselfT = m->ebw[i].ss.WselfT; et.ssWoutT = m->ebw[i].ss.WoutT;
       et.split = split_bwd ? 1 : 0;

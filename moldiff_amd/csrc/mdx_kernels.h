@@ -6,9 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define MDX_ND 256  // node feature width (shipped configs; other widths are rejected at create)
-#define MDX_ED 64   // edge feature width
-#define MDX_NG 16   // distance gaussians
+#include "mdx_weights.h"  // MDX_ND / MDX_ED / MDX_NG, the node table's columns and the weight blocks: plain C++, shared with the host packer
 #ifndef MDX_ET
 #define MDX_ET 3    // edge tile = 16*MDX_ET rows per workgroup
 #endif
@@ -18,85 +16,6 @@
 #ifndef MDX_NT
 #define MDX_NT 1    // node tile = 16*MDX_NT rows per workgroup (N/16 tiles fill 256 CUs better than N/32)
 #endif
-
-// Column layout of the per-node table NT (N, MDX_NTW) written by the node kernel (PRE stage) and
-// gathered by the edge kernels:  everything that is Linear(h_node)[idx] in the reference is hoisted
-// to one per-node GEMM (exact for a plain Linear; for the first layer of the gate MLPs it splits the
-// 321-wide contraction into edge + node + time parts, see DESIGN.md "hoisting").
-#define MDX_NT_C 0       // centroid_lin(x) + bias                         (256)
-#define MDX_NT_GX 256    // gate.net.0.weight[:, 64:320] x   (no bias)      (256)
-#define MDX_NT_NLL 512   // bond_ffn_left.node_linear x                     (128)
-#define MDX_NT_NLR 640   // bond_ffn_right.node_linear x                    (128)
-#define MDX_NT_NFL 768   // node_ffn_left(x) + bias                         (64)
-#define MDX_NT_NFR 832   // node_ffn_right(x) + bias                        (64)
-#define MDX_NT_GXL 896   // bond_ffn_left.gate.net.0.weight[:, 64:320] x    (32)
-#define MDX_NT_GXR 928   // bond_ffn_right.gate.net.0.weight[:, 64:320] x   (32)
-#define MDX_NTW 960
-
-struct MlpW {  // Linear -> LN -> ReLU -> Linear, all packed for gemm_tile
-  const float *W1, *b1, *g, *be, *W2, *b2;
-};
-
-struct FfnW {  // BondFFN of the EdgeBlock (bond 64, node 256 hoisted, inter 128, gate hidden 32, out 64)
-  const float* Wbl;            // bond_linear (128 x 64), no bias
-  MlpW inter;                  // 128 -> 128 -> 64
-  const float *Wg1e, *bg1, *wtg1, *gg, *gb;  // gate first layer: edge part (32 x 64), bias, time column, LN
-  const float *Wg2, *bg2;      // gate second layer (64 x 32)
-};
-
-// "stream packs" of the row-owner kernels (mdx_row.h, mdx_edge2.hip): the same matrices in consumption order
-struct FfnS {
-  const float *Wbl, *Wg1e, *W1, *W2, *Wg2;
-};
-struct EdgeAS {
-  const float *Wemb, *Wg1e, *Wg2, *W1, *W2, *Wm;
-  FfnS ffn[2];
-};
-struct EdgeBS {
-  const float *Wself, *Wout, *Wbl, *Wnl, *Wg1h, *Wg1a, *Wi1;
-};
-
-struct EdgeAW {  // weights of edge kernel A for one block
-  const float *Wemb, *bemb;                        // edge_embs (64 x 80)
-  const float *Wg1e, *bg1, *wtg1, *gg, *gb, *Wg2, *bg2;  // NodeBlock gate: edge part (256x64), bias, time col, LN, 256x256
-  MlpW en;                                         // edge_net 64 -> 256 -> 256
-  const float *Wm, *bm;                            // msg_net 256 x 256
-  FfnW ffn[2];                                     // left, right
-  EdgeAS s;
-  EdgeAS ss;  // the same streams split into float16 hi / lo halves (mdx_split.h; EA_SPLIT launches)
-  // 1: every Linear that feeds a LayerNorm in this kernel (both gates' and edge_net's / inter's first layers, with their biases, time
-  // columns and the GX / GXL / GXR rows of the node table) was packed centred over its output features (mdx_api.hip PackCtx::centred)
-  int lnc;
-};
-
-struct EdgeBW {  // weights of edge kernel B for one block
-  const float *Wself, *bself, *lng, *lnb, *Wout, *bout;  // EdgeBlock tail
-  // PosUpdate.edge_lin (BondFFN bond 64, node 64, inter 256, out 1)
-  const float *Wbl, *Wnl;          // 256 x 64 each, no bias
-  const float *Wi1, *bi1, *ig, *ib;  // inter_module first layer 256x256 + LN
-  const float *wi2;                // (256) second layer row
-  float bi2;
-  const float *Wg1h, *Wg1a, *bg1, *wtg1, *gg, *gb;  // gate first layer split: He part (32x64), a part (32x64), bias, time col, LN
-  const float *wg2;                // (32)
-  float bg2;
-  EdgeBS s;
-  EdgeBS ss;  // split float16 streams (EB_SPLIT launches)
-  int lnc;    // 1: the PosUpdate gate's and inter module's first layers were packed centred (see EdgeAW)
-};
-
-struct NodeW {  // weights of the node kernel
-  // MID stage (block i): NodeBlock tail + PosUpdate per-node MLPs
-  const float *lng, *lnb, *Wout, *bout;
-  MlpW left, right;  // 256 -> 64 -> 64
-  // PRE stage (block i or i+1)
-  MlpW nn;                     // node_net 256 -> 256 -> 256
-  const float *Wcat, *bcat;    // concatenated (960 x 256) + bias (960, zeros where the reference has none)
-};
-
-struct NodeWS {  // the node kernel's matrices as dense split float16 packs (mdx_node_s.hip, PackCtx::pack_dense_split)
-  const float *Wout, *leftW1, *leftW2, *rightW1, *rightW2;  // MID stage
-  const float *nnW1, *nnW2, *Wcat;                          // PRE stage
-};
 
 struct EdgeAArgs {
   int E, flags;
@@ -185,31 +104,6 @@ struct NodeArgs {
 #define ND_SPLIT 16   // matrix products on the split float16 path (mdx_node_s.hip)
 
 // ---- backward (bond-predictor guidance gradient; dgrad only, no weight gradients) ---------------------
-struct FfnWT {
-  const float *WblT, *Wi1T, *Wi2T, *Wg1eT, *Wg2T;
-};
-struct FfnTS {  // stream packs (mdx_row.h) of the transposed BondFFN matrices
-  const float *WblT, *Wi1T, *Wi2T, *Wg1eT, *Wg2T;
-};
-struct EdgeBwdS {
-  const float *WembHT, *WembDT, *Wg1eT, *Wg2T, *W1T, *W2T, *WmT;
-  FfnTS ffn[2];
-  const float *WselfT, *WoutT;  // EdgeBlock tail
-};
-struct EdgeBwdW {  // transposed packs (contraction over the forward's output features)
-  const float *WembHT, *WembDT;                 // edge_embs^T: -> 64 (He part), -> 16 (distance part)
-  const float *Wg1eT, *Wg2T, *W1T, *W2T, *WmT;  // NodeBlock gate / edge_net / msg_net
-  FfnWT ffn[2];
-  const float *WselfT, *WoutT;                  // EdgeBlock tail
-  EdgeBwdS s;                                   // row-owner kernel (mdx_bwd2.hip)
-  EdgeBwdS ss;                                  // the same as split float16 streams (mdx_bwd2s.hip)
-};
-struct NodeBwdW {
-  const float* WoutT;      // NodeBlock out_transform^T
-  const float *W1T, *W2T;  // node_net^T
-  const float* WcatT[4];   // (960 x 256)^T in 4 K-chunks: 256, 256, 256, 192
-};
-
 struct EdgeTailBwdArgs {
   int E;
   const int *l, *r;
@@ -219,8 +113,7 @@ struct EdgeTailBwdArgs {
   float *GU, *GHEP;            // (E,64): dL/du ; gHe + self_ffn^T dL/du
   int* wq;                     // see EdgeAArgs
   EdgeBW w;
-  const float *WselfT, *WoutT;
-  const float *sWselfT, *sWoutT;  // the same as stream packs (row-owner kernel, mdx_bwd2.hip)
+  const float *sWselfT, *sWoutT;  // self_ffn^T / out_transform^T as stream packs (row-owner kernel, mdx_bwd2.hip)
   const float *ssWselfT, *ssWoutT;  // ... and as split float16 stream packs (mdx_bwd2s.hip)
   int split;                       // 1: run the split float16 build
 };
@@ -263,10 +156,6 @@ struct EdgeBwdArgs {
   EdgeBwdW wt;
 };
 
-struct NodeBwdWS {  // split float16 dense packs of NodeBwdW (mdx_bondpred.hip node_bwd_s_kernel)
-  const float *WoutT, *W1T, *W2T, *WcatT[4];
-};
-
 struct NodeBwdArgs {
   int N, flags;
   float* gHn;                  // (N,256) in/out
@@ -283,10 +172,6 @@ struct NodeBwdArgs {
 #define NB_PRE 2
 #define NB_SPLIT 4  // matrix products on the split float16 path
 
-struct BondDecW {
-  const float *W1e, *W1n, *b1, *g1, *be1, *W2, *b2, *g2, *be2, *W3, *b3;
-  const float *W1eT, *W1nT, *W2T, *W3T;
-};
 struct BondDecArgs {
   int Eh, Ke;
   const float *He, *Hn;        // (E,64) internal order, (N,256)

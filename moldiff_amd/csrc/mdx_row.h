@@ -12,7 +12,7 @@
 //     16 g + 4 q + s -- activations never leave the registers, LayerNorm is wave-local, there is no LDS tile and no
 //     __syncthreads() after the constant prologue;
 //   * weights stream L2 -> VGPR through a register ring of MDX_RING steps in consumption order ("stream pack", host:
-//     PackCtx::pack_stream): step p = ftp*KG + g carries the two fragments (2 ftp + j, g), j = 0,1, 2 KiB contiguous,
+//     mdx_pack.cpp PACK_STREAM): step p = ftp*KG + g carries the two fragments (2 ftp + j, g), j = 0,1, 2 KiB contiguous,
 //     fetched with buffer loads (scalar base + scalar fragment offset: no vector address arithmetic);
 //   * GEMM results are pinned at the end of rgemm (LLVM would otherwise sink MFMA chains away from their ring loads).
 #pragma once
@@ -197,7 +197,7 @@ __device__ __forceinline__ void row_layernorm(f32x4 (&y)[FT][R], const float* __
 }
 
 // The same LayerNorm + ReLU over a row whose mean over the features is zero by construction: every addend of the pre-activation
-// comes from a centred pack (host: PackCtx::centred, DESIGN.md section 3.1 -- the column means of the weights and the mean of the
+// comes from a centred pack (host: mdx_pack.cpp Layer::centred, DESIGN.md section 3.1 -- the column means of the weights and the mean of the
 // bias were taken out once, in float64, when the model was packed).  The variance is then sum y^2 / n: one reduction per row
 // instead of two and 4 vector operations per element instead of 7 (on this core every one of them is additive to the MFMA time).
 template <int FT, int R>

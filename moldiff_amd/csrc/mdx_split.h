@@ -13,7 +13,7 @@
 // the same 2-KiB-step register ring (WRing / ws_frag).  What changes:
 //   * the B operand of k-group g (32 k-values) is, per lane, 8 halves = the lane's accumulators of feature tiles 2g and 2g+1
 //     converted in place (to_xs) -- the accumulator-is-next-operand chaining survives, with the k permutation
-//     k(g, q, t) = 32 g + 16 (t / 4) + 4 q + t % 4  baked into the weight pack (host: PackCtx::pack_stream_split);
+//     k(g, q, t) = 32 g + 16 (t / 4) + 4 q + t % 4  baked into the weight pack (host: mdx_pack.cpp PACK_STREAM_SPLIT);
 //   * a stream step is a PAIR of half-steps of two 1-KiB fragments each: (hi of tiles 2ftp, 2ftp+1), then (lo of the same) --
 //     the same bytes as the fp32 stream for K a multiple of 32 (K is zero-padded to one otherwise);
 //   * the LOW halves are stored scaled by 2^MDX_LO_SHIFT (= 2^11): lo = fp16((x - hi) 2^11) is then a NORMAL float16 number for

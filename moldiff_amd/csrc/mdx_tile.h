@@ -183,7 +183,7 @@ __device__ __forceinline__ void gemm_tile_impl(f32x4 (&acc)[FTW][ET], f32x4 (&a0
 
 // ----------------------------------------------------------------------------------------------
 // acc[ft][et] += W[16*(ft0+ft) .. +16][0..K) * X[16*et .. +16][0..K)^T
-//   Wp : packed weights, float4 index ((g*FT + ft)*64 + lane), g = k/16   (host: PackCtx::pack_dense)
+//   Wp : packed weights, float4 index ((g*FT + ft)*64 + lane), g = k/16   (host: mdx_pack.cpp PACK_DENSE)
 //   X  : LDS tile, row-major, leading dimension ldx (floats, multiple of 4)
 // gemm_tile_pre: same, with the group-0 weight fragments already in `a0` (load_w0); a0 is clobbered.
 // ----------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@
 
 // acc[ft][et] += W[16 (ft0 + ft) .. + 16][0 .. K) X[16 et .. + 16][0 .. K)^T
 //   Wp : dense split pack, 1-KiB fragment index (g * FT + ft) * 2 + h (g = k / 32; h = 0 hi, 1 lo scaled by 2^11), lane (q, c) holds
-//        feature 16 ft + c, k = 32 g + 16 (t / 4) + 4 q + t % 4 (host: PackCtx::pack_dense_split) -- the k order of the two 16-byte
+//        feature 16 ft + c, k = 32 g + 16 (t / 4) + 4 q + t % 4 (host: mdx_pack.cpp PACK_DENSE_SPLIT) -- the k order of the two 16-byte
 //        LDS reads below
 //   X  : LDS tile, fp32, row-major, leading dimension ldx
 template <int FTW, int ET, int K, int D = 3>

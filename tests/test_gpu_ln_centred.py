@@ -1,4 +1,4 @@
-"""Centred against un-centred weight packs of the MolDiff denoiser's edge kernels, on ONE handle (csrc/mdx_api.hip PackCtx::centred,
+"""Centred against un-centred weight packs of the MolDiff denoiser's edge kernels, on ONE handle (csrc/mdx_pack.cpp Layer::centred,
 csrc/mdx_row.h row_layernorm_centred; the bound on what centring leaves is stated and asserted in
 tests/test_ln_centred_pack.py).
 

@@ -1,4 +1,4 @@
-"""Host-only checks of the centred weight packs (csrc/mdx_api.hip centre_columns).  No GPU.
+"""Host-only checks of the centred weight packs (csrc/mdx_pack.cpp centre_columns).  No GPU.
 
 A Linear W x + b that feeds a LayerNorm over its F output features is packed with the column means of W and the mean of b taken out
 (float64, rounded to float32 once), so that the pre-activation has mean zero over the features and the kernels' LayerNorm skips the
@@ -81,8 +81,8 @@ def test_random_and_degenerate_matrices():
 
 # ---- the packed arena itself (mdx_debug_pack_host): which packs pack_model centred, and that nothing else moved -----------------------
 #
-# Every pack is decoded from its fragment order back to a matrix (layouts: csrc/mdx_api.hip pack_dense / pack_stream /
-# pack_stream_split / pack_dense_split).  Split packs hold w as fp16 hi + fp16 lo 2^-11: re-rounding a centred fp32 entry costs at most
+# Every pack is decoded from its fragment order back to a matrix (layouts: csrc/mdx_pack.cpp Packer::pack, the two
+# index maps and two element formats).  Split packs hold w as fp16 hi + fp16 lo 2^-11: re-rounding a centred fp32 entry costs at most
 # 2^-11 of |w - hi| <= 2^-11 |w|, i.e. 2^-22 |w| (plus 2^-35 where lo is an fp16 subnormal), so a split pack's residual column mean
 # is bounded by (2^-24 + 2^-22) max|w| + 2^-35, not by 2^-24 max|w|.
 
