@@ -202,6 +202,11 @@ def lib():
         L.mdx_op_ln_relu_bwd_rows.argtypes = [c_int64]
         L.mdx_op_ln_relu_bwd_rows.restype = c_int64
         # (every operand that may be stored as float16 is a void pointer; `dt`, the int32 in front of the stream, says which are)
+        L.mdx_op_xgemm_nt_t.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                        c_int32, c_int32, c_int32, c_void_p]
+        L.mdx_op_xgemm_nt_ln_t.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_void_p, c_int64, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p]
+        L.mdx_op_xgemm_nt_ln_supported.argtypes = [c_int64, c_int64, c_int64]
         L.mdx_op_xgemm_tn_t.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                         c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]
         L.mdx_op_ln_relu_fwd_t.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]

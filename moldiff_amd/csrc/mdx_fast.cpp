@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/moldiff_hip.h"
+#include "mdx_train_plan.h"
 
 namespace {
 
@@ -67,8 +68,6 @@ inline Tensor aligned_rows(const Tensor& t, int64_t ld_mult, int64_t ptr_mult) {
   return r;
 }
 inline Tensor half_empty(int64_t E, int64_t F, const Tensor& like) { return at::empty({E, F}, like.options().dtype(at::kHalf)); }
-
-constexpr int64_t RED_CHUNK = 256;  // == csrc/mdx_train.hip
 
 struct Job {
   Tensor g, x;
@@ -128,7 +127,7 @@ void sink_add(std::vector<int64_t>& recs, int64_t& counter, int64_t Pp, int64_t 
               int64_t pstride, int64_t rkind, int64_t nchunks = 1) {
   const int64_t r[8] = {Pp, dst, Sn, rows_, cols, ld, pstride, rkind | (counter << 8)};
   recs.insert(recs.end(), r, r + 8);
-  counter += nchunks * ((rows_ * cols + 127) / 128);
+  counter += nchunks * red_blocks(rows_ * cols);
 }
 
 // one gradient record: a repeated destination flushes what is recorded first (the reduction's read-modify-writes are not atomic); more
@@ -139,9 +138,9 @@ void sink_record(int64_t Pp, int64_t dst, int64_t Sn, int64_t rows_, int64_t col
   if (S.seen.count(dst)) flush_sink();
   S.seen.insert(dst);
   if (Sn > RED_CHUNK) {
-    const int64_t nc = (Sn + RED_CHUNK - 1) / RED_CHUNK;
+    const int64_t nc = ceil_div(Sn, RED_CHUNK);
     sink_add(S.recs, S.blocks, Pp, dst, Sn, rows_, cols, ld, pstride, 64, nc);
-    sink_add(S.recs2, S.blocks2, Pp + 4 * Sn * pstride, dst, nc, rows_, cols, ld, pstride, rkind);
+    sink_add(S.recs2, S.blocks2, Pp + 4 * red_chunk_plane(Sn, 0) * pstride, dst, nc, rows_, cols, ld, pstride, rkind);
   } else {
     sink_add(S.recs, S.blocks, Pp, dst, Sn, rows_, cols, ld, pstride, rkind);
   }
@@ -383,7 +382,8 @@ std::pair<Tensor, Tensor> weight_grad(const Tensor& g, const Tensor& x, int64_t 
     return {};
   }
   const auto f32 = g.options().dtype(at::kFloat);
-  Tensor part = at::empty({(splits + (splits + 255) / 256) * (N * K + N)}, f32), dW, db;
+  const SplitLayout L = split_layout(M, N, K, splits, S.amp0 ? HW_MC : W_MC);   // (what the two kernels below compute for themselves)
+  Tensor part = at::empty({L.total}, f32), dW, db;
   float* pp = reinterpret_cast<float*>(part.data_ptr());
   if (!dst_w) dW = at::empty({N, K}, f32), db = want_bias ? at::empty({N}, f32) : Tensor();
   float* pw = reinterpret_cast<float*>(P(dW));
@@ -397,10 +397,8 @@ std::pair<Tensor, Tensor> weight_grad(const Tensor& g, const Tensor& x, int64_t 
   }
   ++S.n_launch;
   if (dst_w) {
-    int64_t Sn = 0, boff = 0;
-    chk(mdx_op_wgrad_layout(M, N, K, (int32_t)splits, S.amp0 ? 1 : 0, &Sn, &boff));
-    sink_record(A(part), dst_w, Sn, N, K, ldw, N * K, rk_now(), part);
-    if (want_bias) sink_record(A(part) + 4 * boff, dst_b, Sn, 1, N, N, N, rk_now(), part);
+    sink_record(A(part), dst_w, L.S, N, K, ldw, N * K, rk_now(), part);
+    if (want_bias) sink_record(A(part) + 4 * L.bias_off, dst_b, L.S, 1, N, N, N, rk_now(), part);
   }
   return {dW, db};
 }
@@ -418,14 +416,14 @@ std::pair<Tensor, Tensor> linear_param_grads(const Tensor& gy, const Tensor& x, 
 template <class Launch>
 std::pair<Tensor, Tensor> ln_param_grads(int64_t M, int64_t F, const Tensor& gamma, const Tensor& beta, const Tensor& like, Launch launch) {
   const auto f32 = like.options().dtype(at::kFloat);
-  Tensor ws = at::empty({(int64_t)(mdx_op_ln_relu_bwd_ws(M, (int32_t)F) / 4 + 1)}, f32);
+  Tensor ws = at::empty({ln_bwd_ws_floats(M, F) + 1}, f32);
   const int64_t dst_g = sink_dst(gamma), dst_b = sink_dst(beta);
   const bool defer = dst_g && dst_b && M > 0 && A(ws) % 16 == 0;
   Tensor dgb = defer ? Tensor() : at::empty({2 * F}, f32);
   launch(reinterpret_cast<float*>(P(dgb)), reinterpret_cast<float*>(ws.data_ptr()));
   ++S.n_launch;
   if (!defer) return {dgb.narrow(0, 0, F), dgb.narrow(0, F, F)};
-  const int64_t nrows = mdx_op_ln_relu_bwd_rows(M);
+  const int64_t nrows = ln_bwd_rows(M);
   sink_record(A(ws), dst_g, nrows, 1, F, F, 2 * F, 0, ws);
   sink_record(A(ws) + 4 * F, dst_b, nrows, 1, F, F, 2 * F, 0, ws);
   return {};

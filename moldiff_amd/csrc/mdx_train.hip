@@ -1,16 +1,29 @@
 // Layer-level operators of the training path (gfx950): every O(rows x features) piece of the loss forward/backward
-// (reference models/model.py:128-201 get_loss + torch.autograd) as an explicit forward/backward kernel pair, driven
-// one layer at a time from moldiff_amd/train_ops.py.  Unlike the sampling path these are NOT fused across layers:
-// activations live in HBM between operators (288 GB makes that a non-issue) so that every parameter gradient is a
-// plain contraction over stored tensors.  All arithmetic is fp32; contractions run on v_mfma_f32_16x16x4_f32.
+// (reference models/model.py:128-201 get_loss + torch.autograd) as an explicit forward/backward kernel pair, driven one
+// layer at a time from moldiff_amd/train_ops.py and csrc/mdx_fast.cpp.  Unlike the sampling path these are NOT fused across
+// layers (the fused training kernels are in mdx_train_fused.hip): activations live in HBM between operators so that every
+// parameter gradient is a plain contraction over stored tensors.  Three precisions share the file: exact fp32 (contractions on
+// v_mfma_f32_16x16x4_f32), and bfloat16 / float16 operands with fp32 accumulation (v_mfma_f32_16x16x32_*), the float16 mode also
+// with float16 CONTAINERS (`_t` entry points: a bit mask names the tensors stored as float16).
 //
-//   sgemm_nt      C[M,N] = A[M,K] B[N,K]^T (+ bias)     forward of nn.Linear, dgrad (B = W^T), wgrad (split-K over rows)
-//   transpose     out[C,R] = in[R,C]^T                   operand preparation for dgrad / wgrad
-//   colreduce     out[N] = sum_rows X (* Y)              bias / LayerNorm-parameter gradients (two deterministic stages)
-//   ln_relu       y = relu(LN(x) * gamma + beta)         forward (saves mean, rstd) and backward (dx, dgamma, dbeta)
-//   ew            add / sub / mul / a*sigmoid(b)         forward and backward
-//   gather/segsum y = x[idx] ; out[r] = sum_{j in seg r} src[order[j]]   (each is the other's backward; no atomics)
-//   edge_geom, smear, force                              rel/dist of an edge, Gaussian smearing, w*rel/d/(d+1) + backwards
+//   sgemm_nt / xgemm_nt     C[M,N] = A[M,K] B[N,K]^T + bias + addend: forward of nn.Linear and dgrad (B = W^T).  fp32 tiled kernel;
+//                           half tiled kernel (hgemm_nt_kernel, 64- or 128-wide column tile); row-owner kernel for float16 rows with
+//                           the whole weight in LDS (hgemm_nt_rows_kernel), optionally with the LayerNorm(+ReLU) that follows (xgemm_nt_ln)
+//   sgemm_tn / xgemm_tn     dW[N,K] = G[M,N]^T X[M,K] (+ db = column sums of G) over split row ranges: fp32 kernel, converting half
+//                           kernel (64 x 64 tiles), transpose-read kernel for float16 containers; partials summed in a fixed order
+//   wgrad_grouped           a device table of queued weight gradients, one launch per tile class (classes: mdx_train_plan.h)
+//   reduce_deferred         every split partial of a step (weights, biases, LayerNorm parameters) summed into the flat gradient buffer
+//   transpose(_batch)       out[C,R] = in[R,C]^T: W^T for the dgrad GEMMs
+//   colreduce               out[N] = sum_rows X (* Y): bias / LayerNorm-parameter gradients (two deterministic stages)
+//   ln_relu                 y = relu(LN(x) * gamma + beta): forward (saves mean, rstd), backward (dx, partial rows of dgamma | dbeta)
+//                           and the backward fused with a rank-1 Linear in front of it; generic fp32 kernels and 4-wide typed ones
+//   ew, sum_n               add / sub / mul / a * sigmoid(b), forward and backward; sum of up to 12 tensors
+//   gather / segsum, mul_gather, plan_flip      y = x[idx]; out[r] = sum_{j in seg r} src[order[j]] (each is the other's backward; no atomics)
+//   edge_geom, smear, force                     rel / dist of an edge, Gaussian smearing, w * rel / d / (d + 1), with backwards
+//   sumsq, adamw, amp_adamw                     gradient norm and the optimizer step (with the loss scaler's decision on the device)
+//
+// The host side's shared arithmetic -- split-partial layout, the queue's plan, LayerNorm partial rows, the deferred reduction's record
+// table, the row-owner GEMM's shapes -- is in mdx_train_plan.h (plain C++, also built by the host compiler alone).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -20,6 +33,7 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_tile.h"
+#include "mdx_train_plan.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
 
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(256) void sgemm_nt_kernel(const float* __restrict__
 // these kernels are bound by streaming their operands.  Lane (c = lane & 15, q = lane >> 4) feeds 8 consecutive k-values
 // starting at 8 q of its row/column; C/D mapping is the same as the fp32 16x16x4 form.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int W_T = 64, W_MC = 32, W_LD = W_T + 4;  // weight-gradient tile (both precisions)
+constexpr int W_T = 64, W_LD = W_T + 4;  // weight-gradient tile (both precisions; rows per step W_MC / HW_MC: mdx_train_plan.h)
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
   uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
@@ -239,8 +253,8 @@ __device__ __forceinline__ float round_kind(float a, int kind) { return kind == 
 
 constexpr int H_KC = 64, H_LD = H_KC + 8;  // bf16 elements per staged row (+8 = 16 bytes of padding)
 
-// TN = width of the workgroup's column tile (64, 128 or 256; the launcher picks the smallest TN >= N up to MDX_HGEMM_TN_MAX, default
-// 128): fewer passes over the big operand A (rows x K, fp32 in HBM); the weight slab (TN x 64 halves per K step) sits in LDS.
+// TN = width of the workgroup's column tile (64 or 128; the launcher picks 64 for N <= 64): fewer passes over the big operand A
+// (rows x K); the weight slab (TN x 64 halves per K step) sits in LDS.
 template <int HT, bool ROUND, int TN, bool AH>
 __global__ __launch_bounds__(256) void hgemm_nt_kernel(const TP A, int lda, const float* __restrict__ B, int ldb,
                                                         const float* __restrict__ bias, const TP addend,
@@ -579,15 +593,15 @@ static void launch_hgemm_nt_rows(const _Float16* A, int lda, const float* B, int
                      ln);
 }
 
-// bf16 weight gradient: 64 rows of G and X per step are transposed into LDS ([column][row], so that the 8 consecutive
+// bf16 weight gradient: HW_MC = 64 rows of G and X per step are transposed into LDS ([column][row], so that the 8 consecutive
 // contraction values a lane needs are one 16-byte read); otherwise the structure of sgemm_tn_split_kernel.
-constexpr int HW_MC = 64;
-// Workgroup tile TNW (columns of G) x TKW (columns of X), 64 or 128 each (round 3: 128 where the layer is that wide -- four times the
-// MFMAs per staged byte and per barrier of the 64 x 64 tile, half the passes over G and X).  Wave w owns the (TNW/2) x (TKW/2) quadrant.
-template <int HT, int TNW, int TKW>
+// Workgroup tile TNW (columns of G) x TKW (columns of X) = 64 x 64; wave w owns a 32 x 32 quadrant.  (128-wide tiles for this conversion
+// kernel measured slower: 47.9 vs 44.0 ms per step, occupancy 4 -> 2; the transpose-read kernel below has them.)
+template <int HT>
 __device__ __forceinline__ void hgemm_tn_split_body(const TP G, int ldg, const TP X, int ldx, int M, int N, int K, int mper,
                                                     float* __restrict__ P, float* __restrict__ Pb, const int bx, const int by,
                                                     const int bz) {
+  constexpr int TNW = 64, TKW = 64;
   __shared__ __attribute__((aligned(16))) uint16_t Gt[TNW * H_LD];
   __shared__ __attribute__((aligned(16))) uint16_t Xt[TKW * H_LD];
   constexpr int IN = TNW / 32, IK = TKW / 32;      // 16 x 16 tiles per wave along n / k
@@ -676,11 +690,11 @@ __device__ __forceinline__ void hgemm_tn_split_body(const TP G, int ldg, const T
       }
 }
 
-template <int HT, int TNW, int TKW>
+template <int HT>
 __global__ __launch_bounds__(256) void hgemm_tn_split_kernel(const TP G, int ldg, const TP X, int ldx,
                                                               int M, int N, int K, int mper, float* __restrict__ P,
                                                               float* __restrict__ Pb) {
-  hgemm_tn_split_body<HT, TNW, TKW>(G, ldg, X, ldx, M, N, K, mper, P, Pb, blockIdx.x, blockIdx.y, blockIdx.z);
+  hgemm_tn_split_body<HT>(G, ldg, X, ldx, M, N, K, mper, P, Pb, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // float16 weight gradient on float16 CONTAINERS (half storage, round 3): P[z][n][k] = sum_{m in split z} G[m][n] * X[m][k].
@@ -919,7 +933,7 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const long long* __r
   } else {
     const int dt = (int)d[13];
     const TP G{reinterpret_cast<const void*>(d[0]), dt & 1}, X{reinterpret_cast<const void*>(d[1]), (dt >> 1) & 1};
-    hgemm_tn_split_body<1, 64, 64>(G, ldg, X, ldx, M, N, K, mper, P, Pb, bx, by, bz);
+    hgemm_tn_split_body<1>(G, ldg, X, ldx, M, N, K, mper, P, Pb, bx, by, bz);
   }
 }
 
@@ -1111,8 +1125,7 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------------------------
 // LayerNorm (+ReLU), one wave per row, F <= 1024.  Lane holds features lane, lane+64, ...
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int LN_MAXJ = 16;
-#define MDX_LN_RPW 16  // rows per wave in the backward (16: 9.7 k waves for E = 155 k rows; 64 left the chip half empty)
+constexpr int LN_MAXJ = 16;   // (rows per wave in the backward, MDX_LN_RPW: mdx_train_plan.h)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -1358,20 +1371,6 @@ __global__ __launch_bounds__(256) void ln_relu_bwd4_kernel(const TP dy, const TP
 // ------------------------------------------------------------------------------------------------------------------
 // opr = op | (rkind << 8): rkind != 0 rounds the result (and the sigmoid of the gate) to bfloat16 / float16 -- the value the
 // reference's fp16 tensors hold under autocast (both factors of these products are Linear outputs there)
-__global__ void ew_fwd_kernel(int opr, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ o, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int op = opr & 255, rk = opr >> 8;
-  const float x = a[i], y = b[i];
-  float r;
-  switch (op) {
-    case 0: r = x + y; break;
-    case 1: r = x - y; break;
-    case 2: r = x * y; break;
-    default: r = x * round_kind(sigmoidf_(y), rk); break;
-  }
-  o[i] = round_kind(r, rk);
-}
 template <typename V>
 __device__ __forceinline__ V ew_apply(int op, V x, V y);
 template <>
@@ -1423,7 +1422,7 @@ __global__ void sum_n1_kernel(const SumN a, const TPW o, size_t n) {
   st1(o, i, s);
 }
 // any length / alignment, fp32 or float16 containers (round 6: an (E,1) gate product has E % 4 != 0 and used to go through two casts to
-// fp32 and back)
+// fp32 and back); also what an unaligned or odd-length fp32 tensor takes
 __global__ void ew_fwd1_kernel(int opr, const TP a, const TP b, const TPW o, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1461,25 +1460,6 @@ __global__ void ew_bwd4_kernel(int op, const TP a, const TP b, const TP g, const
   }
   if (da.p) st4(da, 4 * i, ga);
   if (db.p) st4(db, 4 * i, gb);
-}
-__global__ void ew_bwd_kernel(int op, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ g,
-                              float* __restrict__ da, float* __restrict__ db, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float go = g[i];
-  float ga, gb;
-  switch (op) {
-    case 0: ga = go; gb = go; break;
-    case 1: ga = go; gb = -go; break;
-    case 2: ga = go * b[i]; gb = go * a[i]; break;
-    default: {
-      const float s = sigmoidf_(b[i]);
-      ga = go * s;
-      gb = go * a[i] * s * (1.0f - s);
-    }
-  }
-  if (da) da[i] = ga;
-  if (db) db[i] = gb;
 }
 
 // y[i] = x[idx[i]]  (rows of F floats)
@@ -1886,10 +1866,13 @@ __global__ void adamw_amp_kernel(float* __restrict__ p, const float* __restrict_
 
 inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 inline int bad(const char* m) { return mdx_set_error(MDX_ERR_ARG, m); }
-// out (M x N, ld) = bias + sum over the S partial copies in P; more than 256 copies go through `scratch`
-// (ceil(S/256) * M * N floats) in two fixed-order stages.
-constexpr int RED_CHUNK = 256;
-inline size_t reduce_scratch_floats(int64_t S, int64_t total) { return S > RED_CHUNK ? (size_t)((S + RED_CHUNK - 1) / RED_CHUNK) * total : 0; }
+// A run-time integer as a template argument: calls f(std::integral_constant<int, V>{}) for the V among Vs that equals v; false if none does.
+template <int... Vs, class F>
+inline bool pick(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+// out (M x N, ld) = bias + sum over the S partial copies in P; more than RED_CHUNK copies go through `scratch`
+// (ceil(S / RED_CHUNK) * M * N floats) in two fixed-order stages.
 inline void launch_reduce_partials(const float* P, int S, int M, int N, const float* bias, float* out, int ld, float* scratch,
                                    hipStream_t s, int rkind = 0) {
   const size_t total = (size_t)M * N;
@@ -1898,9 +1881,22 @@ inline void launch_reduce_partials(const float* P, int S, int M, int N, const fl
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(gx, 1), dim3(256), 0, s, P, S, S, M, N, bias, out, ld, rkind);
     return;
   }
-  const int nc = (S + RED_CHUNK - 1) / RED_CHUNK;
+  const int nc = (int)ceil_div(S, RED_CHUNK);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(gx, nc), dim3(256), 0, s, P, S, RED_CHUNK, M, N, (const float*)nullptr, scratch, N, 0);
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(gx, 1), dim3(256), 0, s, (const float*)scratch, nc, nc, M, N, bias, out, ld, rkind);
+}
+// The end of a split weight gradient: dW (N x K, ldw) and, with db, db (N) from the partials a SplitLayout places in `partial`.
+inline void finish_split(float* partial, const SplitLayout& L, int N, int K, float* dW, int ldw, float* db, int rkind, hipStream_t s) {
+  const int S = (int)L.S;
+  float* pb = partial + L.bias_off;
+  if (db && S <= RED_CHUNK) {  // both reductions in one launch
+    const unsigned gxw = (unsigned)(((size_t)N * K + 31) / 32), gxb = (unsigned)((N + 31) / 32);
+    hipLaunchKernelGGL(reduce_partials2_kernel, dim3(gxw + gxb), dim3(256), 0, s, (const float*)partial, S, N, K, dW, ldw, (int)gxw,
+                       (const float*)pb, N, db, rkind);
+  } else {
+    launch_reduce_partials(partial, S, N, K, nullptr, dW, ldw, partial + L.stage_off, s, rkind);
+    if (db) launch_reduce_partials(pb, S, 1, N, nullptr, db, N, pb + (size_t)S * N, s, rkind);
+  }
 }
 inline int launched() {
   const hipError_t e = hipGetLastError();
@@ -2003,19 +1999,26 @@ extern "C" int mdx_op_ln_relu_fwd_t(const void* xv, const float* gamma, const fl
   const TP x{xv, dt & 1};
   const TPW y{yv, (dt >> 1) & 1};
   const bool al = tp_vec_ok(xv, x.h, 4) && tp_vec_ok(yv, y.h, 4);
-#define MDX_LNF(LPR)                                                                                                              \
-  case 4 * LPR:                                                                                                                   \
-    hipLaunchKernelGGL(ln_relu_fwd4_kernel<LPR>, dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), 0,         \
-                       (hipStream_t)stream, x, gamma, beta, (int)M, relu, y, stats);                                              \
+  if (al && F % 4 == 0 && pick<8, 16, 32, 64>(F / 4, [&](auto LPR) {   // LPR lanes per row, four features each
+        hipLaunchKernelGGL(ln_relu_fwd4_kernel<LPR>, dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), 0,
+                           (hipStream_t)stream, x, gamma, beta, (int)M, relu, y, stats);
+      }))
     return launched();
-  if (al) switch (F) { MDX_LNF(8) MDX_LNF(16) MDX_LNF(32) MDX_LNF(64) default: break; }
-#undef MDX_LNF
   if (dt) return bad("ln_relu: half storage needs F in {32, 64, 128, 256} and aligned rows");
   hipLaunchKernelGGL(ln_relu_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)xv, gamma, beta,
                      (int)M, F, relu, (float*)yv, stats);
   return launched();
 }
 
+// The 4-wide backward kernel for F in {32, 64, 128, 256} (false: not built for F), one workgroup per partial row of ws; w1 != NULL is the
+// rank-1 form (dy holds M values).  The callers check alignment.
+static bool launch_ln_bwd4(const TP& dy, const TP& x, const float* stats, const float* gamma, const float* beta, int64_t M, int32_t F,
+                           int32_t relu, const TPW& dx, float* ws, const float* w1, hipStream_t s) {
+  return F % 4 == 0 && pick<8, 16, 32, 64>(F / 4, [&](auto LPR) {
+    hipLaunchKernelGGL(ln_relu_bwd4_kernel<LPR>, dim3((unsigned)ln_bwd_rows(M)), dim3(256), 32 * F, s, dy, x, stats, gamma, beta, (int)M, relu,
+                       MDX_LN_RPW, dx, ws, w1);
+  });
+}
 // dx (M,F); dgb (2F) = [dgamma | dbeta].  ws: mdx_op_ln_relu_bwd_ws(M, F) bytes.
 extern "C" int mdx_op_ln_relu_bwd_t(const void* dyv, const void* xv, const float* stats, const float* gamma, const float* beta, int64_t M,
                                     int32_t F, int32_t relu, void* dxv, float* dgb, float* ws, int32_t dt, void* stream) {
@@ -2025,53 +2028,32 @@ extern "C" int mdx_op_ln_relu_bwd_t(const void* dyv, const void* xv, const float
   if (!ws) return bad("ln_relu_bwd: workspace required");
   const TP dy{dyv, dt & 1}, x{xv, (dt >> 1) & 1};
   const TPW dx{dxv, (dt >> 2) & 1};
-  const int RPW = MDX_LN_RPW;
-  const int nw = (int)((M + RPW - 1) / RPW);     // waves
-  const int nwp = (nw + 3) / 4 * 4;              // waves launched (whole workgroups); `part` gets one row per workgroup
+  const int nr = (int)ln_bwd_rows(M);            // workgroups of four waves; `ws` gets one partial row from each
   const bool al = tp_vec_ok(xv, x.h, 4) && tp_vec_ok(dyv, dy.h, 4) && tp_vec_ok(dxv, dx.h, 4) && ((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
-  bool done = false;
-#define MDX_LNB(LPR)                                                                                                              \
-  case 4 * LPR:                                                                                                                   \
-    hipLaunchKernelGGL(ln_relu_bwd4_kernel<LPR>, dim3((unsigned)(nwp / 4)), dim3(256), 32 * F, s, dy, x, stats, gamma, beta, (int)M, relu, \
-                       RPW, dx, ws);                                                                                              \
-    done = true;                                                                                                                  \
-    break;
-  if (al) switch (F) { MDX_LNB(8) MDX_LNB(16) MDX_LNB(32) MDX_LNB(64) default: break; }
-#undef MDX_LNB
-  if (!done) {
+  if (!(al && launch_ln_bwd4(dy, x, stats, gamma, beta, M, F, relu, dx, ws, nullptr, s))) {
     if (dt) return bad("ln_relu_bwd: half storage needs F in {32, 64, 128, 256} and aligned rows");
-    hipLaunchKernelGGL(ln_relu_bwd_kernel, dim3((unsigned)(nwp / 4)), dim3(256), 32 * F, s, (const float*)dyv, (const float*)xv, stats, gamma, beta,
-                       (int)M, F, relu, RPW, (float*)dxv, ws);
+    hipLaunchKernelGGL(ln_relu_bwd_kernel, dim3((unsigned)nr), dim3(256), 32 * F, s, (const float*)dyv, (const float*)xv, stats, gamma, beta,
+                       (int)M, F, relu, MDX_LN_RPW, (float*)dxv, ws);
   }
-  // [dgamma | dbeta] = sum over the nwp / 4 per-workgroup partial rows, fixed-order parallel reduction (dgb == NULL: deferred, the
-  // partial rows stay in ws for mdx_op_reduce_deferred)
-  if (dgb) launch_reduce_partials(ws, nwp / 4, 1, 2 * F, nullptr, dgb, 2 * F, ws + (size_t)(nwp / 4) * 2 * F, s);
+  // [dgamma | dbeta] = sum over the per-workgroup partial rows, fixed-order parallel reduction (dgb == NULL: deferred, the partial rows
+  // stay in ws for mdx_op_reduce_deferred)
+  if (dgb) launch_reduce_partials(ws, nr, 1, 2 * F, nullptr, dgb, 2 * F, ws + (size_t)nr * 2 * F, s);
   return launched();
 }
 extern "C" int mdx_op_ln_relu_bwd_r1_t(const void* g1, const float* w1, const void* xv, const float* stats, const float* gamma, const float* beta,
                                        int64_t M, int32_t F, int32_t relu, void* dxv, float* ws, int32_t dt, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
   if (M <= 0) return MDX_OK;
   if (!g1 || !w1 || !xv || !stats || !gamma || !beta || !dxv || !ws) return bad("ln_relu_bwd_r1: null operand");
   const TP dy{g1, dt & 1}, x{xv, (dt >> 1) & 1};
   const TPW dx{dxv, (dt >> 2) & 1};
-  const int RPW = MDX_LN_RPW;
-  const int nw = (int)((M + RPW - 1) / RPW), nwp = (nw + 3) / 4 * 4;
   if (!(tp_vec_ok(xv, x.h, 4) && tp_vec_ok(dxv, dx.h, 4) && ((reinterpret_cast<uintptr_t>(ws) & 15) == 0)))
     return mdx_set_error(MDX_ERR_UNSUPPORTED, "ln_relu_bwd_r1: aligned rows required");
-#define MDX_LNB1(LPR)                                                                                                             \
-  case 4 * LPR:                                                                                                                   \
-    hipLaunchKernelGGL(ln_relu_bwd4_kernel<LPR>, dim3((unsigned)(nwp / 4)), dim3(256), 32 * F, s, dy, x, stats, gamma, beta, (int)M, relu, \
-                       RPW, dx, ws, w1);                                                                                          \
-    break;
-  switch (F) { MDX_LNB1(8) MDX_LNB1(16) MDX_LNB1(32) MDX_LNB1(64) default: return mdx_set_error(MDX_ERR_UNSUPPORTED, "ln_relu_bwd_r1: F must be 32, 64, 128 or 256"); }
-#undef MDX_LNB1
+  if (!launch_ln_bwd4(dy, x, stats, gamma, beta, M, F, relu, dx, ws, w1, (hipStream_t)stream))
+    return mdx_set_error(MDX_ERR_UNSUPPORTED, "ln_relu_bwd_r1: F must be 32, 64, 128 or 256");
   return launched();
 }
-extern "C" size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F) {
-  const int64_t nw = (M + MDX_LN_RPW - 1) / MDX_LN_RPW, nr = (nw + 3) / 4;   // one partial row per workgroup of four waves
-  return ((size_t)std::max<int64_t>(nr, 1) * 2 * F + reduce_scratch_floats(nr, 2 * F)) * sizeof(float);
-}
+extern "C" size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F) { return (size_t)ln_bwd_ws_floats(M, F) * sizeof(float); }
+extern "C" int64_t mdx_op_ln_relu_bwd_rows(int64_t M) { return ln_bwd_rows(M); }  // partial rows mdx_op_ln_relu_bwd leaves in ws ([rows][2F])
 
 extern "C" int mdx_op_ew_fwd_t(int32_t op, const void* a, const void* b, void* out, int64_t n, int32_t dt, void* stream) {
   if (n <= 0) return MDX_OK;
@@ -2080,11 +2062,8 @@ extern "C" int mdx_op_ew_fwd_t(int32_t op, const void* a, const void* b, void* o
   const TPW to{out, (dt >> 2) & 1};
   if ((n & 3) == 0 && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(b, tb.h, 4) && tp_vec_ok(out, to.h, 4)) {
     hipLaunchKernelGGL(ew_fwd4_kernel, dim3(nblk((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, to, (size_t)n / 4);
-  } else if (dt) {
-    hipLaunchKernelGGL(ew_fwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, to, (size_t)n);
   } else {
-    hipLaunchKernelGGL(ew_fwd_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, (const float*)a, (const float*)b,
-                       (float*)out, (size_t)n);
+    hipLaunchKernelGGL(ew_fwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, to, (size_t)n);
   }
   return launched();
 }
@@ -2119,11 +2098,8 @@ extern "C" int mdx_op_ew_bwd_t(int32_t op, const void* a, const void* b, const v
   if ((n & 3) == 0 && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(b, tb.h, 4) && tp_vec_ok(g, tg.h, 4) && tp_vec_ok(da, tda.h, 4) &&
       tp_vec_ok(db, tdb.h, 4)) {
     hipLaunchKernelGGL(ew_bwd4_kernel, dim3(nblk((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, tg, tda, tdb, (size_t)n / 4);
-  } else if (dt) {
-    hipLaunchKernelGGL(ew_bwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, tg, tda, tdb, (size_t)n);
   } else {
-    hipLaunchKernelGGL(ew_bwd_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, (const float*)a, (const float*)b,
-                       (const float*)g, (float*)da, (float*)db, (size_t)n);
+    hipLaunchKernelGGL(ew_bwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, tg, tda, tdb, (size_t)n);
   }
   return launched();
 }
@@ -2247,32 +2223,19 @@ extern "C" int mdx_op_amp_adamw(float* p, const float* g, float* m, float* v, in
 
 // Weight gradient of a Linear layer: dW[N,K] = G[M,N]^T X[M,K] (row-major operands as stored by the forward/backward;
 // no transposes).  The M rows are cut into `splits` ranges whose partial products are summed in a fixed order
-// (partial: (splits + ceil(splits/256)) * (N*K + N) floats: the partial products plus the first reduction stage, for dW
-// and for the optional bias gradient db[N] = column sums of G, which rides along in the first k-tile's workgroups).
+// (partial: split_layout(M, N, K, splits, W_MC).total floats -- mdx_train_plan.h: the partial products plus the first reduction stage,
+// for dW and for the optional bias gradient db[N] = column sums of G, which rides along in the first k-tile's workgroups).
 extern "C" int mdx_op_sgemm_tn(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M,
                                int64_t N, int64_t K, int32_t splits, float* partial, void* stream) {
   if (N <= 0 || K <= 0) return MDX_OK;
   hipStream_t s = (hipStream_t)stream;
   if (!G || !X || !partial) return bad("sgemm_tn: null operand / partial buffer");
-  if (splits < 1) splits = 1;
-  int mper = (int)((std::max<int64_t>(M, 1) + splits - 1) / splits);
-  mper = (mper + W_MC - 1) / W_MC * W_MC;
-  const int S = (int)((std::max<int64_t>(M, 1) + mper - 1) / mper);
-  dim3 grid((unsigned)((K + W_T - 1) / W_T), (unsigned)((N + W_T - 1) / W_T), (unsigned)S);
-  // partial layout: [S][N*K] products | [ceil(S/256)][N*K] first reduction stage | [S][N] bias partials | [ceil(S/256)][N]
-  const size_t nc = (size_t)(S + RED_CHUNK - 1) / RED_CHUNK;
-  float* scratch = partial + (size_t)S * N * K;
-  float* pb = db ? scratch + nc * N * K : nullptr;
-  hipLaunchKernelGGL(sgemm_tn_split_kernel, grid, dim3(256), 0, s, G, (int)ldg, X, (int)ldx, (int)M, (int)N, (int)K, mper, partial, pb);
-  if (!dW) return launched();  // deferred: the partials stay where mdx_op_wgrad_layout says, mdx_op_reduce_deferred sums them later
-  if (db && S <= RED_CHUNK) {  // both reductions in one launch
-    const unsigned gxw = (unsigned)(((size_t)N * K + 31) / 32), gxb = (unsigned)((N + 31) / 32);
-    hipLaunchKernelGGL(reduce_partials2_kernel, dim3(gxw + gxb), dim3(256), 0, s, (const float*)partial, S, (int)N, (int)K, dW, (int)ldw,
-                       (int)gxw, (const float*)pb, (int)N, db, 0);
-  } else {
-    launch_reduce_partials(partial, S, (int)N, (int)K, nullptr, dW, (int)ldw, scratch, s);
-    if (db) launch_reduce_partials(pb, S, 1, (int)N, nullptr, db, (int)N, pb + (size_t)S * N, s);
-  }
+  const SplitLayout L = split_layout(M, N, K, splits, W_MC);
+  dim3 grid((unsigned)((K + W_T - 1) / W_T), (unsigned)((N + W_T - 1) / W_T), (unsigned)L.S);
+  hipLaunchKernelGGL(sgemm_tn_split_kernel, grid, dim3(256), 0, s, G, (int)ldg, X, (int)ldx, (int)M, (int)N, (int)K, (int)L.mper, partial,
+                     db ? partial + L.bias_off : nullptr);
+  // dW == NULL: deferred, the partials stay where mdx_op_wgrad_layout says and mdx_op_reduce_deferred sums them later
+  if (dW) finish_split(partial, L, (int)N, (int)K, dW, (int)ldw, db, 0, s);
   return launched();
 }
 
@@ -2284,19 +2247,10 @@ extern "C" int mdx_op_sgemm_tn(const float* G, int64_t ldg, const float* X, int6
 // buffer.  Record (8 x int64): P, dst, S (partials), rows, cols, ld (dst row stride), pstride (floats between consecutive partials),
 // rkind (0 fp32, 1 bfloat16, 2 float16 rounding of the sum, mixed precision) | first_block << 8.
 extern "C" int mdx_op_wgrad_layout(int64_t M, int64_t N, int64_t K, int32_t splits, int32_t half, int64_t* S_out, int64_t* bias_off) {
-  if (splits < 1) splits = 1;
-  const int mc = half ? HW_MC : W_MC;
-  int mper = (int)((std::max<int64_t>(M, 1) + splits - 1) / splits);
-  mper = (mper + mc - 1) / mc * mc;
-  const int64_t S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
-  const int64_t nc = (S + RED_CHUNK - 1) / RED_CHUNK;
-  if (S_out) *S_out = S;
-  if (bias_off) *bias_off = (S + nc) * N * K;   // floats from `partial` to the [S][N] bias partials
+  const SplitLayout L = split_layout(M, N, K, splits, half ? HW_MC : W_MC);
+  if (S_out) *S_out = L.S;
+  if (bias_off) *bias_off = L.bias_off;   // floats from `partial` to the [S][N] bias partials
   return MDX_OK;
-}
-extern "C" int64_t mdx_op_ln_relu_bwd_rows(int64_t M) {  // partial rows mdx_op_ln_relu_bwd leaves in ws ([rows][2F])
-  const int64_t nw = (M + MDX_LN_RPW - 1) / MDX_LN_RPW;
-  return (nw + 3) / 4;
 }
 namespace {
 // One lane per FOUR consecutive output elements: eight running sums over the partials k = z, z + 8, ... (z = 0..7), added up in the
@@ -2308,7 +2262,8 @@ namespace {
 // record; then a second launch over the chunk sums), so no chain is longer than 32 + S/2048 iterations, and a lane takes four
 // elements (one 16-byte load per partial when the record's planes are 16-byte aligned) so a wave reads 1 KB per partial and the
 // record look-up is paid once per 128 elements.  rkind bit 6: chunked; bit 7: store the sum instead of adding it.  The record table's
-// unit (`first_block`) is 128 elements per block; a chunked record takes ceil(S / 256) times the blocks of a plain one.
+// unit (`first_block`) is RED_ELEMS = 128 elements per block; a chunked record takes ceil(S / RED_CHUNK) times the blocks of a plain one
+// (red_blocks, red_chunk_plane: mdx_train_plan.h, which the host's record table uses too).
 template <bool VEC>
 __device__ __forceinline__ f32x4 reduce_deferred_sum(const float* p, size_t pstride, int S, int ne) {
   f32x4 acc[8];
@@ -2363,18 +2318,19 @@ __global__ __launch_bounds__(256) void reduce_deferred_kernel(const int64_t* __r
   long long rel = blk - (long long)(d[7] >> 8);
   if (d[7] & 64) {
     // chunked record (S > RED_CHUNK): its blocks are [chunk][block]; chunk c sums partials 256 c .. 256 c + 255 and STORES the sum in
-    // the scratch plane c behind the partials (P + (S + c) * pstride: where launch_reduce_partials keeps its chunk sums, and what the
+    // the scratch plane c behind the partials (red_chunk_plane: where launch_reduce_partials keeps its chunk sums, and what the
     // workspace / wgrad layouts reserve).  The caller's second table sums those planes into dst.
-    const long long nblk = (long long)((total + 127) / 128);
+    const long long nblk = (long long)red_blocks((int64_t)total);
     const int chunk = (int)(rel / nblk);
     rel -= chunk * nblk;
-    dst = const_cast<float*>(P) + ((size_t)S + chunk) * pstride;
+    dst = const_cast<float*>(P) + (size_t)red_chunk_plane(S, chunk) * pstride;
     P += (size_t)chunk * RED_CHUNK * pstride;
     S = min(RED_CHUNK, S - chunk * RED_CHUNK);
     ld = cols;
     rkind = 0;
     store = true;
   }
+  static_assert(RED_ELEMS == 32 * 4, "a block of the record table is 32 lanes of four elements");
   const size_t i = ((size_t)rel * 32 + (threadIdx.x & 31)) * 4;
   if (i >= total) return;
   const int ne = (int)min((size_t)4, total - i);
@@ -2398,6 +2354,10 @@ extern "C" int mdx_op_reduce_deferred(const int64_t* desc, int32_t n, int64_t to
   return launched();
 }
 
+// The row-owner GEMM takes this call: its shapes (mdx_train_plan.h), float16 arithmetic, A in a float16 container with rows on 16 bytes.
+static bool rows_gemm_ok(const void* Av, int64_t lda, int a_half, int32_t half_kind, int64_t M, int64_t N, int64_t K) {
+  return half_kind == 2 && a_half && rows_gemm_shape(M, N, K) && (lda & 7) == 0 && (reinterpret_cast<uintptr_t>(Av) & 15) == 0;
+}
 // Mixed-precision forms of sgemm_nt / sgemm_tn: operands rounded to `half_kind` (1 = bfloat16, 2 = float16) on their way into
 // LDS, products on the 16x16x32 half MFMAs, fp32 accumulation.  round_out != 0: the result is rounded to the same type before it
 // is stored (in an fp32 container) -- the value a Linear returns under torch.autocast (float16 overflows to infinity).  The forward
@@ -2416,65 +2376,45 @@ extern "C" int mdx_op_xgemm_nt_t(const void* Av, int64_t lda, const float* B, in
   hipStream_t s = (hipStream_t)stream;
   // float16 rows, widths the row-owner kernel is instantiated for: whole weight resident in LDS, no K loop over barriers (measured in
   // round 3: 84 -> 47 us on 256 -> 256 against the tiled kernel)
-  const int kt = (int)(K / 32), ftn = (int)(N / 16);
-  if (half_kind == 2 && A.h && M >= 1024 && K % 32 == 0 && N % 16 == 0 && (kt == 1 || kt == 2 || kt == 4 || kt == 8) &&
-      (ftn == 2 || ftn == 4 || ftn == 8 || ftn == 16) && (lda & 7) == 0 && (reinterpret_cast<uintptr_t>(Av) & 15) == 0) {
+  if (rows_gemm_ok(Av, lda, A.h, half_kind, M, N, K)) {
     const _Float16* Ah = reinterpret_cast<const _Float16*>(Av);
-#define MDX_HR(KTv, FTv)                                                                                                     \
-  do {                                                                                                                       \
-    if (round_out) launch_hgemm_nt_rows<KTv, FTv, true>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s); \
-    else launch_hgemm_nt_rows<KTv, FTv, false>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s);   \
-  } while (0)
-#define MDX_HRG(KTv, FTv, Gv)                                                                                                                 \
-  do {                                                                                                                                          \
-    if (round_out) launch_hgemm_nt_rows<KTv, FTv, true>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, LnEpi{}, Gv); \
-    else launch_hgemm_nt_rows<KTv, FTv, false>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, LnEpi{}, Gv);   \
-  } while (0)
-    // few rows (the per-node layers): column groups, see the kernel
+    // few rows (the per-node layers): column groups, see the kernel -- 64 columns as 2 x 32, 128 as 4 x 32, 256 as 4 x 64
     const bool few = (M + 127) / 128 <= mdx_num_cus() / 2;
-#define MDX_HR_F(KTv)                                  \
-  do {                                                 \
-    if (ftn == 2) MDX_HR(KTv, 2);                      \
-    else if (ftn == 4) { if (few) MDX_HRG(KTv, 2, 2); else MDX_HR(KTv, 4); }   \
-    else if (ftn == 8) { if (few) MDX_HRG(KTv, 2, 4); else MDX_HR(KTv, 8); }   \
-    else { if (few) MDX_HRG(KTv, 4, 4); else MDX_HR(KTv, 16); }                \
-  } while (0)
-    if (kt == 1) MDX_HR_F(1);
-    else if (kt == 2) MDX_HR_F(2);
-    else if (kt == 4) MDX_HR_F(4);
-    else MDX_HR_F(8);
-#undef MDX_HR_F
-#undef MDX_HRG
-#undef MDX_HR
+    pick<1, 2, 4, 8>((int)(K / 32), [&](auto KT) {
+      pick<2, 4, 8, 16>((int)(N / 16), [&](auto FT) {
+        pick<0, 1>(round_out ? 1 : 0, [&](auto R) {
+          constexpr int kt = decltype(KT)::value, ft = decltype(FT)::value, g = ft == 2 ? 1 : ft == 16 ? 4 : ft / 2;
+          constexpr bool r = decltype(R)::value != 0;
+          if (few && g > 1)
+            launch_hgemm_nt_rows<kt, ft / g, r>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, LnEpi{}, g);
+          else
+            launch_hgemm_nt_rows<kt, ft, r>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s);
+        });
+      });
+    });
     return launched();
   }
-  // measured on the training step (ms per step, fp16 mode): TN <= 64: 52.0, <= 128: 51.5, <= 256: 54.7 (one workgroup per CU) -- the
-  // re-reads of A were L2 hits all along; the kernel is bound by its short K loop (one 64-wide chunk in flight per workgroup)
-  constexpr int tn_max = 128;
-  const int tn = std::min(tn_max, N <= 64 ? 64 : N <= 128 ? 128 : 256);
-  dim3 grid((unsigned)((N + tn - 1) / tn), (unsigned)((M + G_TM - 1) / G_TM), 1);
-#define MDX_XNT3(HT, R, TNv)                                                                                                              \
-  do {                                                                                                                                    \
-    if (HT == 1 && A.h)                                                                                                                   \
-      hipLaunchKernelGGL((hgemm_nt_kernel<HT, R, TNv, (HT == 1)>), grid, dim3(256), 0, s, A, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, \
-                         (int)ldc, (int)M, (int)N, (int)K);                                                                               \
-    else                                                                                                                                  \
-      hipLaunchKernelGGL((hgemm_nt_kernel<HT, R, TNv, false>), grid, dim3(256), 0, s, A, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C,     \
-                         (int)ldc, (int)M, (int)N, (int)K);                                                                               \
-  } while (0)
-#define MDX_XNT(HT, R)                                  \
-  do {                                                  \
-    if (tn == 64) MDX_XNT3(HT, R, 64);                  \
-    else if (tn == 128) MDX_XNT3(HT, R, 128);           \
-    else MDX_XNT3(HT, R, 256);                          \
-  } while (0)
-  if (half_kind == 1) {
-    if (round_out) MDX_XNT(0, true); else MDX_XNT(0, false);
-  } else {
-    if (round_out) MDX_XNT(1, true); else MDX_XNT(1, false);
-  }
-#undef MDX_XNT3
-#undef MDX_XNT
+  // Column tile: 64 for N <= 64, else 128.  Measured on the training step (ms per step, fp16 mode) with tiles up to 64: 52.0, up to 128:
+  // 51.5, up to 256: 54.7 (one workgroup per CU) -- the re-reads of A were L2 hits all along; the kernel is bound by its short K loop (one
+  // 64-wide chunk in flight per workgroup)
+  pick<0, 1>(half_kind - 1, [&](auto HT) {
+    pick<0, 1>(round_out ? 1 : 0, [&](auto R) {
+      pick<64, 128>(N <= 64 ? 64 : 128, [&](auto TN) {
+        constexpr int ht = decltype(HT)::value, tn = decltype(TN)::value;
+        constexpr bool r = decltype(R)::value != 0;
+        dim3 grid((unsigned)((N + tn - 1) / tn), (unsigned)((M + G_TM - 1) / G_TM), 1);
+        if constexpr (ht == 1) {   // a float16 A is copied to LDS as it is
+          if (A.h) {
+            hipLaunchKernelGGL((hgemm_nt_kernel<ht, r, tn, true>), grid, dim3(256), 0, s, A, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C,
+                               (int)ldc, (int)M, (int)N, (int)K);
+            return;
+          }
+        }
+        hipLaunchKernelGGL((hgemm_nt_kernel<ht, r, tn, false>), grid, dim3(256), 0, s, A, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C,
+                           (int)ldc, (int)M, (int)N, (int)K);
+      });
+    });
+  });
   return launched();
 }
 // Linear + LayerNorm(+ReLU) in one launch (float16 rows on the row-owner kernel only; anything else: MDX_ERR_UNSUPPORTED, the caller
@@ -2484,21 +2424,14 @@ extern "C" int mdx_op_xgemm_nt_t(const void* Av, int64_t lda, const float* B, in
 // the two agree to rounding (a few fp32 ulp on the statistics), not bit for bit -- which one runs depends on M >= 1024 only.  It is
 // what mdx_op_ln_relu_bwd_t reads.  A float16 C with round_out = 0 is refused: the LayerNorm would see the unrounded values while C
 // stores rounded ones.
-static bool ln_rows_ok(const void* Av, int64_t lda, int64_t M, int64_t N, int64_t K, int32_t half_kind, int32_t dt) {
-  const int kt = (int)(K / 32), ftn = (int)(N / 16);
-  return half_kind == 2 && (dt & 1) && M >= 1024 && K % 32 == 0 && N % 16 == 0 && (kt == 1 || kt == 2 || kt == 4 || kt == 8) &&
-         (ftn == 2 || ftn == 4 || ftn == 8 || ftn == 16) && (lda & 7) == 0 && (reinterpret_cast<uintptr_t>(Av) & 15) == 0;
-}
-extern "C" int mdx_op_xgemm_nt_ln_supported(int64_t M, int64_t N, int64_t K) {
-  return ln_rows_ok(nullptr, 8, M, N, K, 2, 1) ? 1 : 0;
-}
+extern "C" int mdx_op_xgemm_nt_ln_supported(int64_t M, int64_t N, int64_t K) { return rows_gemm_shape(M, N, K) ? 1 : 0; }
 extern "C" int mdx_op_xgemm_nt_ln_t(const void* Av, int64_t lda, const float* B, int64_t ldb, const float* bias, const void* addendv,
                                     int64_t ldd, void* Cv, int64_t ldc, const float* gamma, const float* beta, void* postv, int64_t ldp,
                                     float* stats, int32_t relu, int64_t M, int64_t N, int64_t K, int32_t half_kind, int32_t round_out,
                                     int32_t dt, void* stream) {
   if (M <= 0 || N <= 0) return MDX_OK;
   if (!Av || !B || !Cv || !gamma || !beta || !postv || !stats) return bad("xgemm_nt_ln: null operand");
-  if (!ln_rows_ok(Av, lda, M, N, K, half_kind, dt)) return mdx_set_error(MDX_ERR_UNSUPPORTED, "xgemm_nt_ln: shape / container not built (use xgemm_nt + ln_relu_fwd)");
+  if (!rows_gemm_ok(Av, lda, dt & 1, half_kind, M, N, K)) return mdx_set_error(MDX_ERR_UNSUPPORTED, "xgemm_nt_ln: shape / container not built (use xgemm_nt + ln_relu_fwd)");
   if (((dt >> 2) & 1) && !round_out) return mdx_set_error(MDX_ERR_UNSUPPORTED, "xgemm_nt_ln: a float16 C needs round_out (LN must see the stored values)");
   const TP addend{addendv, (dt >> 1) & 1};
   const TPW C{Cv, (dt >> 2) & 1};
@@ -2506,25 +2439,13 @@ extern "C" int mdx_op_xgemm_nt_ln_t(const void* Av, int64_t lda, const float* B,
   if (!tp_vec_ok(postv, ln.post.h, ldp)) return bad("xgemm_nt_ln: post rows must be vector-aligned");
   hipStream_t s = (hipStream_t)stream;
   const _Float16* Ah = reinterpret_cast<const _Float16*>(Av);
-  const int kt = (int)(K / 32), ftn = (int)(N / 16);
-#define MDX_HRL(KTv, FTv)                                                                                                              \
-  do {                                                                                                                                 \
-    if (round_out) launch_hgemm_nt_rows<KTv, FTv, true, true>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, ln); \
-    else launch_hgemm_nt_rows<KTv, FTv, false, true>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, ln);   \
-  } while (0)
-#define MDX_HRL_F(KTv)                      \
-  do {                                      \
-    if (ftn == 2) MDX_HRL(KTv, 2);          \
-    else if (ftn == 4) MDX_HRL(KTv, 4);     \
-    else if (ftn == 8) MDX_HRL(KTv, 8);     \
-    else MDX_HRL(KTv, 16);                  \
-  } while (0)
-  if (kt == 1) MDX_HRL_F(1);
-  else if (kt == 2) MDX_HRL_F(2);
-  else if (kt == 4) MDX_HRL_F(4);
-  else MDX_HRL_F(8);
-#undef MDX_HRL_F
-#undef MDX_HRL
+  pick<1, 2, 4, 8>((int)(K / 32), [&](auto KT) {
+    pick<2, 4, 8, 16>((int)(N / 16), [&](auto FT) {
+      pick<0, 1>(round_out ? 1 : 0, [&](auto R) {
+        launch_hgemm_nt_rows<decltype(KT)::value, decltype(FT)::value, decltype(R)::value != 0, true>(Ah, (int)lda, B, (int)ldb, bias, addend, (int)ldd, C, (int)ldc, (int)M, s, ln);
+      });
+    });
+  });
   return launched();
 }
 extern "C" int mdx_op_xgemm_tn_t(const void* Gv, int64_t ldg, const void* Xv, int64_t ldx, float* dW, int64_t ldw, float* db, int64_t M,
@@ -2535,120 +2456,53 @@ extern "C" int mdx_op_xgemm_tn_t(const void* Gv, int64_t ldg, const void* Xv, in
   if (!Gv || !Xv || !partial) return bad("xgemm_tn: null operand / partial buffer");
   const TP G{Gv, dt & 1}, X{Xv, (dt >> 1) & 1};
   if (half_kind != 1 && half_kind != 2) return bad("xgemm_tn: half_kind must be 1 (bfloat16) or 2 (float16)");
-  if (splits < 1) splits = 1;
-  int mper = (int)((std::max<int64_t>(M, 1) + splits - 1) / splits);
-  mper = (mper + HW_MC - 1) / HW_MC * HW_MC;
-  const int S = (int)((std::max<int64_t>(M, 1) + mper - 1) / mper);
-  constexpr int wide = 64;   // (128-wide tiles for this conversion kernel measured slower: 47.9 vs 44.0 ms per step, occupancy 4 -> 2)
-  const int tnw = (wide >= 128 && N >= 128) ? 128 : 64, tkw = (wide >= 128 && K >= 128) ? 128 : 64;
-  dim3 grid((unsigned)((K + tkw - 1) / tkw), (unsigned)((N + tnw - 1) / tnw), (unsigned)S);
-  const size_t nc = (size_t)(S + RED_CHUNK - 1) / RED_CHUNK;
-  float* scratch = partial + (size_t)S * N * K;
-  float* pb = db ? scratch + nc * N * K : nullptr;
-  // float16 containers on both sides, tile-aligned widths: the transpose-read kernel (no conversion, no register transposes)
-  constexpr bool no_tr = false;
-  if (!no_tr && half_kind == 2 && G.h && X.h && N % 64 == 0 && K % 64 == 0 && ldg % 8 == 0 && ldx % 8 == 0 &&
+  const SplitLayout L = split_layout(M, N, K, splits, HW_MC);
+  const int mper = (int)L.mper;
+  float* pb = db ? partial + L.bias_off : nullptr;
+  // float16 containers on both sides, tile-aligned widths: the transpose-read kernel (no conversion, no register transposes), 128-wide
+  // tiles where the layer allows
+  if (half_kind == 2 && G.h && X.h && N % 64 == 0 && K % 64 == 0 && ldg % 8 == 0 && ldx % 8 == 0 &&
       (reinterpret_cast<uintptr_t>(Gv) & 15) == 0 && (reinterpret_cast<uintptr_t>(Xv) & 15) == 0) {
-    const int tn = N % 128 == 0 ? 128 : 64, tk = K % 128 == 0 ? 128 : 64;
-    dim3 gtr((unsigned)(K / tk), (unsigned)(N / tn), (unsigned)S);
     const _Float16 *Gh = reinterpret_cast<const _Float16*>(Gv), *Xh = reinterpret_cast<const _Float16*>(Xv);
-#define MDX_XTR(A_, B_) \
-  hipLaunchKernelGGL((hgemm_tn_tr_kernel<A_, B_>), gtr, dim3(256), 0, s, Gh, (int)ldg, Xh, (int)ldx, (int)M, (int)N, (int)K, mper, partial, pb)
-    if (tn == 128 && tk == 128) MDX_XTR(128, 128);
-    else if (tn == 128) MDX_XTR(128, 64);
-    else if (tk == 128) MDX_XTR(64, 128);
-    else MDX_XTR(64, 64);
-#undef MDX_XTR
-  } else {
-#define MDX_XTN(HTv, A_, B_) \
-  hipLaunchKernelGGL((hgemm_tn_split_kernel<HTv, A_, B_>), grid, dim3(256), 0, s, G, (int)ldg, X, (int)ldx, (int)M, (int)N, (int)K, mper, partial, pb)
-#define MDX_XTN2(HTv)                                   \
-  do {                                                  \
-    if (tnw == 128 && tkw == 128) MDX_XTN(HTv, 128, 128); \
-    else if (tnw == 128) MDX_XTN(HTv, 128, 64);         \
-    else if (tkw == 128) MDX_XTN(HTv, 64, 128);         \
-    else MDX_XTN(HTv, 64, 64);                          \
-  } while (0)
-  if (half_kind == 1) MDX_XTN2(0); else MDX_XTN2(1);
-#undef MDX_XTN2
-#undef MDX_XTN
+    pick<64, 128>(N % 128 == 0 ? 128 : 64, [&](auto TN) {
+      pick<64, 128>(K % 128 == 0 ? 128 : 64, [&](auto TK) {
+        constexpr int tn = decltype(TN)::value, tk = decltype(TK)::value;
+        hipLaunchKernelGGL((hgemm_tn_tr_kernel<tn, tk>), dim3((unsigned)(K / tk), (unsigned)(N / tn), (unsigned)L.S), dim3(256), 0, s, Gh,
+                           (int)ldg, Xh, (int)ldx, (int)M, (int)N, (int)K, mper, partial, pb);
+      });
+    });
+  } else {   // the converting kernel, 64 x 64 tiles
+    const dim3 grid((unsigned)((K + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)L.S);
+    pick<0, 1>(half_kind - 1, [&](auto HT) {
+      hipLaunchKernelGGL(hgemm_tn_split_kernel<HT>, grid, dim3(256), 0, s, G, (int)ldg, X, (int)ldx, (int)M, (int)N, (int)K, mper, partial, pb);
+    });
   }
-  const int rkind = round_out ? half_kind : 0;
-  if (!dW) return launched();  // deferred reduction (mdx_op_reduce_deferred)
-  if (db && S <= RED_CHUNK) {  // both reductions in one launch
-    const unsigned gxw = (unsigned)(((size_t)N * K + 31) / 32), gxb = (unsigned)((N + 31) / 32);
-    hipLaunchKernelGGL(reduce_partials2_kernel, dim3(gxw + gxb), dim3(256), 0, s, (const float*)partial, S, (int)N, (int)K, dW, (int)ldw,
-                       (int)gxw, (const float*)pb, (int)N, db, rkind);
-  } else {
-    launch_reduce_partials(partial, S, (int)N, (int)K, nullptr, dW, (int)ldw, scratch, s, rkind);
-    if (db) launch_reduce_partials(pb, S, 1, (int)N, nullptr, db, (int)N, pb + (size_t)S * N, s, rkind);
-  }
+  // dW == NULL: deferred reduction (mdx_op_reduce_deferred)
+  if (dW) finish_split(partial, L, (int)N, (int)K, dW, (int)ldw, db, round_out ? half_kind : 0, s);
   return launched();
 }
 // Queued weight gradients (float16 autocast mode; see wgrad_grouped_kernel).  mdx_op_wgrad_plan: which tile class a contraction takes
-// and its block / partial layout -- out[0..7] = kind, gx, gy, S, mper, offset of the bias partials (floats from P), floats of the whole
-// partial area (products, first reduction stage, bias partials and theirs: the layout of mdx_op_xgemm_tn_t), blocks.  `aligned` = both
-// operands start on 16 bytes.  mdx_op_wgrad_grouped: one launch over a device table of `n` records of one kind (16 x int64 each, layout
-// at the kernel), `total_blocks` = sum of their blocks; the partials are left for mdx_op_reduce_deferred.
+// and its block / partial layout (wgrad_plan, mdx_train_plan.h) -- out[0..7] = kind, gx, gy, S, mper, offset of the bias partials (floats
+// from P), floats of the whole partial area (products, first reduction stage, bias partials and theirs: the layout of mdx_op_xgemm_tn_t),
+// blocks.  `aligned` = both operands start on 16 bytes.  mdx_op_wgrad_grouped: one launch over a device table of `n` records of one kind
+// (16 x int64 each, layout at the kernel), `total_blocks` = sum of their blocks; the partials are left for mdx_op_reduce_deferred.
 extern "C" int mdx_op_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t splits, int32_t dt, int64_t ldg, int64_t ldx, int32_t aligned,
                                  int64_t* out) {
   if (!out || N <= 0 || K <= 0) return bad("wgrad_plan: bad arguments");
-  if (splits < 1) splits = 1;
-  int mper = (int)((std::max<int64_t>(M, 1) + splits - 1) / splits);
-  mper = (mper + HW_MC - 1) / HW_MC * HW_MC;
-  int64_t S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
-  int64_t nc = (S + RED_CHUNK - 1) / RED_CHUNK;
-  int kind = 4, tn = 64, tk = 64;
-  if ((dt & 3) == 3 && N % 64 == 0 && K % 64 == 0 && ldg % 8 == 0 && ldx % 8 == 0 && aligned) {
-    // 128-wide tiles where the layer allows (the 128 x 128 class runs at two waves per SIMD, 172 registers)
-    tn = N % 128 == 0 ? 128 : 64;
-    tk = K % 128 == 0 ? 128 : 64;
-    kind = (tn == 128 ? 0 : 2) + (tk == 128 ? 0 : 1);
-  } else if ((dt & 3) == 3 && ldg % 8 == 0 && ldx % 8 == 0 && aligned && ((N == 32 && K == 64) || (N == 64 && K == 32))) {
-    tn = (int)N, tk = (int)K;
-    kind = N == 32 ? 5 : 6;
-  } else if ((N == 1 && K % 4 == 0 && K <= 256) || (K == 1 && N % 4 == 0 && N <= 256)) {
-    tn = (int)N, tk = (int)K;   // one block per row range
-    kind = 7;
-  }
-  // Rows per block by tile class (0 = the caller's): the classes with few, small tiles per row range do not fill the chip at the queue's
-  // 2,048 rows per block.  Measured per class (us per step, 2,048 -> shipped): 64x128 170 -> 165, 64x64 171 -> 156, converting 64x64
-  // 318 -> 240, 32x64 133 -> 113, 64x32 72 -> 81; the deferred reduction 214 -> 227 (profiles/HISTORY.md, round 6 third session).
-  // A scaled column sum (class 7) has ONE block per row range and a partial of at most 256 floats: with 2,048 rows per block the six
-  // 154,666 x 256 jobs of a step were 456 blocks on 256 CUs (two blocks = 32 KB of loads in flight per CU, 1.6 TB/s); 256 rows per block
-  // give eight times the blocks for 0.6 MB of partials per job.
-  constexpr int krows[8] = {0, 0, 1024, 1024, 512, 1024, 1024, 256};
-  if (krows[kind] > 0 && mper > krows[kind]) {
-    mper = krows[kind];
-    S = (std::max<int64_t>(M, 1) + mper - 1) / mper;
-    nc = (S + RED_CHUNK - 1) / RED_CHUNK;
-  }
-  const int64_t gx = (K + tk - 1) / tk, gy = (N + tn - 1) / tn;
-  out[0] = kind, out[1] = gx, out[2] = gy, out[3] = S, out[4] = mper;
-  out[5] = (S + nc) * N * K;
-  out[6] = (S + nc) * (N * K + N);
-  out[7] = gx * gy * S;
+  const WgradPlan p = wgrad_plan(M, N, K, splits, dt, ldg, ldx, aligned != 0);
+  out[0] = p.kind, out[1] = p.gx, out[2] = p.gy, out[3] = p.lay.S, out[4] = p.lay.mper;
+  out[5] = p.lay.bias_off, out[6] = p.lay.total, out[7] = p.blocks;
   return MDX_OK;
 }
 extern "C" int mdx_op_wgrad_grouped(const int64_t* desc, int32_t n, int64_t total_blocks, int32_t kind, void* stream) {
   if (n <= 0 || total_blocks <= 0) return MDX_OK;
   if (!desc) return bad("wgrad_grouped: null record table");
   if (total_blocks > 0x7fffffffll) return bad("wgrad_grouped: too many blocks");
-  hipStream_t s = (hipStream_t)stream;
-  const long long* d = reinterpret_cast<const long long*>(desc);
-  const dim3 grid((unsigned)total_blocks);
-  switch (kind) {
-    case 0: hipLaunchKernelGGL(wgrad_grouped_kernel<0>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 1: hipLaunchKernelGGL(wgrad_grouped_kernel<1>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 2: hipLaunchKernelGGL(wgrad_grouped_kernel<2>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 3: hipLaunchKernelGGL(wgrad_grouped_kernel<3>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 4: hipLaunchKernelGGL(wgrad_grouped_kernel<4>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 5: hipLaunchKernelGGL(wgrad_grouped_kernel<5>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 6: hipLaunchKernelGGL(wgrad_grouped_kernel<6>, grid, dim3(256), 0, s, d, (int)n); break;
-    case 7: hipLaunchKernelGGL(wgrad_grouped_kernel<7>, grid, dim3(256), 0, s, d, (int)n); break;
-    default: return bad("wgrad_grouped: kind must be 0..7");
-  }
-  return launched();
+  const bool known = pick<0, 1, 2, 3, 4, 5, 6, 7>(kind, [&](auto KIND) {
+    hipLaunchKernelGGL(wgrad_grouped_kernel<KIND>, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const long long*>(desc), (int)n);
+  });
+  return known ? launched() : bad("wgrad_grouped: kind must be 0..7");
 }
 
 // y = a * t[idx] (rows of F floats, F % 4 == 0) and its gradients; see mulg_*_kernel.

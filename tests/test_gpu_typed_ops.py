@@ -11,6 +11,7 @@ Where the fp32 arithmetic is exact (a product of two float16 values has 22 signi
 cast to float16.  Each comparison prints `PARITY <case> <quantity> <largest error / bound>`; the table of one run is kept in
 profiles/typed_ops_parity.txt.  Shapes are the smallest that reach each kernel and each of its edges; no element is left out of any
 assertion."""
+import contextlib
 import ctypes
 import functools
 
@@ -480,7 +481,8 @@ def test_mul_gather_in_float16_containers(Fd):
 # 5. / 6. LayerNorm(+ReLU) and its rank-1 backward
 # ---------------------------------------------------------------------------------------------------------------------------------
 LN_F = (32, 64, 128, 256)                       # lanes per row 8, 16, 32, 64 (F = 32 alone takes the row_ror:8 step)
-LN_M = (1, 7, 16, 17, 63, 64, 65, 1003)         # below one row group; one wave of MDX_LN_RPW = 16 rows; one workgroup of four waves; one past each
+LN_M = (1, 7, 16, 17, 63, 64, 65, 67, 1003)     # below one row group; one wave of MDX_LN_RPW = 16 rows; one workgroup of four waves; one past each;
+                                                # two workgroups, the second with one short wave
 KINK_ROUNDS = 8
 
 
@@ -705,3 +707,133 @@ def test_wrappers_route_float16_rows_that_are_no_multiple_of_four_through_fp32()
     _check(case, 'layernorm', ln, want, 5e-6 * _tmax(want))
     assert mg.dtype == torch.float32
     _exact(case, 'mul_gather', mg, (_d(a) * _d(x)[idx]).half().double())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. every arm of the launchers' dispatch (csrc/mdx_train.hip `pick`), through the C ABI.  Bounds are those of the operators' own tests:
+#    fp32 accumulation 2e-6 * sum |terms| (tests/test_gpu_train_ops.py); a rounded output is the unrounded output rounded once (the
+#    kernel rounds the same fp32 value), so it must EQUAL it after the cast.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _xgemm_nt(x, w, b, M, N, K, half_kind, round_out, c_half, ln=None):
+    """mdx_op_xgemm_nt_t, or with ln = (gamma, beta, relu) mdx_op_xgemm_nt_ln_t -> (rc, C[, post, stats]) on the first M rows of x"""
+    L = _lib.lib()
+    c = torch.empty(M, N, dtype=torch.float16 if c_half else torch.float32, device=DEV)
+    dt = _h(x) | (4 if c_half else 0)
+    if ln is None:
+        return L.mdx_op_xgemm_nt_t(ptr(x), x.stride(0), ptr(w), K, ptr(b), None, 0, ptr(c), N, M, N, K, half_kind, round_out, dt, stream()), c
+    post, stats = torch.empty(M, N, dtype=torch.float16, device=DEV), torch.empty(M, 2, dtype=torch.float32, device=DEV)
+    rc = L.mdx_op_xgemm_nt_ln_t(ptr(x), x.stride(0), ptr(w), K, ptr(b), None, 0, ptr(c), N, ptr(ln[0]), ptr(ln[1]), ptr(post), N, ptr(stats),
+                                int(ln[2]), M, N, K, half_kind, round_out, dt | 8, stream())
+    return rc, c, post, stats
+
+
+@pytest.mark.parametrize('N', [32, 64, 128, 256])
+@pytest.mark.parametrize('K', [32, 64, 128, 256])
+def test_row_owner_gemm_arms_at_the_smallest_size_that_takes_it(K, N):
+    """M = 1,024 float16 rows: the row-owner kernel with column groups (few rows for the device) and, with the launchers capped to 8
+    compute units, at full width; both values of round_out; the LayerNorm form; M = 1,023 falls to the tiled kernel, which computes the
+    same products in the same order."""
+    g = U.rng(7000 + K + 3 * N)
+    M = 1024
+    x, w, b = _half(g, M, K), _f32(g, N, K, scale=K ** -0.5), _f32(g, N)
+    gam, bet = 1 + 0.3 * _f32(g, N), 0.2 * _f32(g, N)
+    case = f'rows_gemm[{K}x{N}]'
+    ref = _d(x) @ _d(w.half()).t() + _d(b)
+    mag = _d(x).abs() @ _d(w.half()).abs().t() + 1
+    assert _lib.lib().mdx_op_xgemm_nt_ln_supported(M, N, K) == 1 and _lib.lib().mdx_op_xgemm_nt_ln_supported(M - 1, N, K) == 0
+    outs = {}
+    for cap in (None, 8):
+        with (_lib.cu_cap(cap) if cap else contextlib.nullcontext()):
+            for ro in (0, 1):
+                rc, c = _xgemm_nt(x, w, b, M, N, K, 2, ro, bool(ro))
+                _lib.check(rc)
+                rc, cl, post, stats = _xgemm_nt(x, w, b, M, N, K, 2, ro, bool(ro), ln=(gam, bet, True))
+                _lib.check(rc)
+                outs[cap, ro] = (c, cl, post, stats)
+    c0 = outs[None, 0][0]
+    _check(case, 'C', c0, ref, ACC * mag)
+    assert torch.equal(outs[None, 1][0], c0.half())                              # rounded once
+    for (cap, ro), (c, cl, post, stats) in outs.items():
+        assert torch.equal(c, outs[None, ro][0]) and torch.equal(cl, c), (cap, ro)   # column groups, full width, LayerNorm form: same rows
+        want = F.relu(F.layer_norm(_d(c), (N,), _d(gam), _d(bet), 1e-5))
+        assert float((_d(post) - want).abs().max()) <= 4e-3 * float(want.abs().max()), (cap, ro)
+        assert float((_d(stats[:, 0]) - _d(c).mean(1)).abs().max()) <= 1e-5 * float(_d(c).abs().max()), (cap, ro)
+    # one row fewer: the tiled kernel (same products, same order), and the LayerNorm form is refused
+    for ro in (0, 1):
+        rc, c = _xgemm_nt(x, w, b, M - 1, N, K, 2, ro, bool(ro))
+        _lib.check(rc)
+        assert torch.equal(c, outs[None, ro][0][:M - 1])
+        assert _xgemm_nt(x, w, b, M - 1, N, K, 2, ro, bool(ro), ln=(gam, bet, True))[0] == MDX_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('N', [64, 192])                                       # 64-wide column tile; 128-wide, two of them, the second half empty
+@pytest.mark.parametrize('half_kind,a_half', [(1, False), (2, False), (2, True)])
+def test_tiled_gemm_arms(half_kind, a_half, N):
+    """hgemm_nt_kernel for bfloat16 and float16 arithmetic, an fp32 and a float16 A, both column tiles, both values of round_out: ragged
+    rows (200 = 128 + 72) and a ragged K loop (80 = 64 + 16)."""
+    g = U.rng(7100 + 10 * half_kind + N)
+    M, K = 200, 80
+    low = (lambda t: t.bfloat16()) if half_kind == 1 else (lambda t: t.half())
+    x, w, b = _f32(g, M, K), _f32(g, N, K, scale=K ** -0.5), _f32(g, N)
+    x = low(x) if a_half else x
+    rc, c0 = _xgemm_nt(x, w, b, M, N, K, half_kind, 0, False)
+    _lib.check(rc)
+    xr, wr = _d(low(x)), _d(low(w))
+    _check(f'tiled_gemm[{half_kind}-{int(a_half)}-{N}]', 'C', c0, xr @ wr.t() + _d(b), ACC * (xr.abs() @ wr.abs().t() + 1))
+    rc, c1 = _xgemm_nt(x, w, b, M, N, K, half_kind, 1, False)
+    _lib.check(rc)
+    assert torch.equal(c1, low(c0).float())                                      # rounded once, held in fp32
+    if half_kind == 2:
+        rc, ch = _xgemm_nt(x, w, b, M, N, K, half_kind, 1, True)
+        _lib.check(rc)
+        assert torch.equal(ch, c0.half())
+
+
+@pytest.mark.parametrize('with_db', [True, False])
+@pytest.mark.parametrize('splits', [1, 3])
+@pytest.mark.parametrize('N,K,half', [(64, 64, True), (64, 128, True), (128, 64, True), (128, 128, True), (54, 6, False)])
+def test_weight_gradient_arms(N, K, half, splits, with_db):
+    """mdx_op_xgemm_tn_t on 200 rows: the transpose-read kernel's four tile shapes (float16 containers) and the converting kernel (fp32
+    operands rounded to float16), one and three row ranges, with and without the bias gradient; no output rounding, so the error is fp32
+    summation error on exact products."""
+    g = U.rng(7200 + N + 3 * K)
+    M = 200
+    dy, x = _half(g, M, N), _half(g, M, K)
+    if not half:
+        dy, x = _f32(g, M, N), _f32(g, M, K)
+    dyr, xr = _d(dy.half()), _d(x.half())
+    part = torch.empty((splits + 1) * (N * K + N), dtype=torch.float32, device=DEV)
+    dw = torch.full((N, K), float('nan'), dtype=torch.float32, device=DEV)
+    db = torch.full((N,), float('nan'), dtype=torch.float32, device=DEV) if with_db else None
+    _lib.check(_lib.lib().mdx_op_xgemm_tn_t(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), K, ptr(db), M, N, K, splits, ptr(part), 2, 0,
+                                            _mask(dy, x), stream()))
+    case = f'wgrad[{N}x{K}-{splits}-{int(with_db)}]'
+    _check(case, 'dW', dw, dyr.t() @ xr, ACC * float((dyr.abs().t() @ xr.abs()).max()))
+    if with_db:
+        _check(case, 'db', db, dyr.sum(0), ACC * float(dyr.abs().sum(0).max()))
+
+
+@pytest.mark.parametrize('opname', list(OPS))
+@pytest.mark.parametrize('layout', ['odd', 'offset'])
+def test_elementwise_pair_in_fp32_containers_off_the_vector_path(opname, layout):
+    """fp32 tensors the 4-wide kernels do not take -- n = 1,237, or n = 2,048 from a base that is 4 bytes past 16 -- run the typed scalar
+    kernels with fp32 containers: add, sub, mul and their gradients are single fp32 operations and EQUAL torch's; the gate is within the
+    bound of test_gpu_train_ops.test_elementwise_pairs (1e-6 / 2e-6 of the largest value)."""
+    g = U.rng(7300)
+    n = 1237 if layout == 'odd' else 2048
+    off = 0 if layout == 'odd' else 1
+    a, b, gy, out, da, db = (_f32(g, n + off)[off:] for _ in range(6))
+    if off:
+        assert all(t.data_ptr() % 16 == 4 for t in (a, b, gy, out, da, db))
+    L, op = _lib.lib(), OPS[opname][1]
+    _lib.check(L.mdx_op_ew_fwd_t(op, ptr(a), ptr(b), ptr(out), n, 0, stream()))
+    _lib.check(L.mdx_op_ew_bwd_t(op, ptr(a), ptr(b), ptr(gy), ptr(da), ptr(db), n, 0, stream()))
+    sg = torch.sigmoid(b)
+    want = {'add': (a + b, gy, gy), 'sub': (a - b, gy, -gy), 'mul': (a * b, gy * b, gy * a),
+            'gate': (a * sg, gy * sg, gy * a * sg * (1 - sg))}[opname]
+    for name, got, ref, tol in zip(('out', 'da', 'db'), (out, da, db), want, (1e-6, 2e-6, 2e-6)):
+        if opname == 'gate':
+            assert float((_d(got) - _d(ref)).abs().max()) <= tol * float(_d(ref).abs().max()), name
+        else:
+            assert torch.equal(got, ref), name
