@@ -66,13 +66,48 @@ def _check_label(label, n):
 
 # ---- one molecule on the host --------------------------------------------------------------------------------------------------------
 
-class _Abandoned(Exception):
-    pass
+class Abandoned(Exception):
+    """the search tree has more than max_nodes nodes or a node deeper than 64"""
 
 
 def _ranks(keys):
     """how many keys are strictly smaller, per key"""
     return np.searchsorted(np.sort(keys), keys, side='left').astype(np.int64)
+
+
+def search(label, bx, by, btype, max_nodes, leaf):
+    """The search tree of the definition over the labels (n) and the valid bonds bx - by of types `btype` (uint64): ``leaf(c)`` is called
+    with the rank vector of every leaf, in the order of the walk (``canon_ref`` and ``stereo.stereo_ref`` are its two visitors) -> the
+    number of nodes, the root counted.  Raises ``Abandoned`` at node max_nodes + 1 or at a node deeper than 64."""
+    n = len(label)
+    src, dst, typ = np.concatenate([bx, by]), np.concatenate([by, bx]), np.concatenate([btype, btype])
+    nodes = [0]
+
+    def refine(c):
+        while True:
+            h = np.zeros(n, dtype=np.uint64)
+            np.add.at(h, src, mix(mix(c[dst].astype(np.uint64) + np.uint64(1)) + typ))
+            new = _ranks((c.astype(np.uint64) << np.uint64(32)) | (h & _M))
+            if np.array_equal(new, c):
+                return c
+            c = new
+
+    def visit(c, depth):
+        nodes[0] += 1
+        if nodes[0] > max_nodes or depth > MAX_DEPTH:
+            raise Abandoned
+        cells = np.bincount(c, minlength=max(n, 1))
+        big = np.flatnonzero(cells > 1)
+        if len(big) == 0:
+            leaf(c)
+            return
+        k = int(big[0])
+        for v in np.flatnonzero(c == k):
+            child = np.where((c == k) & (np.arange(n) != v), k + 1, c)
+            visit(refine(child), depth + 1)
+
+    visit(refine(_ranks(label)), 0)
+    return nodes[0]
 
 
 def fnv1a64(values):
@@ -108,46 +143,24 @@ def canon_ref(info, atom_label=None, max_nodes=DEFAULT_MAX_NODES, atomic_numbers
         return dict(out, status=STATUS_TOO_LARGE)
     ok = (bi[0] >= 0) & (bi[0] < n) & (bi[1] >= 0) & (bi[1] < n) & (bi[0] != bi[1]) if nb else np.zeros(0, dtype=bool)
     bx, by, btype = bi[0][ok], bi[1][ok], (bt[ok] & 0xff).astype(np.uint64)
-    src, dst, typ = np.concatenate([bx, by]), np.concatenate([by, bx]), np.concatenate([btype, btype])
-
-    def refine(c):
-        while True:
-            h = np.zeros(n, dtype=np.uint64)
-            np.add.at(h, src, mix(mix(c[dst].astype(np.uint64) + np.uint64(1)) + typ))
-            new = _ranks((c.astype(np.uint64) << np.uint64(32)) | (h & _M))
-            if np.array_equal(new, c):
-                return c
-            c = new
-
     best = {'cert': None, 'n_aut': 0, 'rank': None, 'table': None}
-    count = {'nodes': 0, 'leaves': 0}
+    count = {'leaves': 0}
 
-    def visit(c, depth):
-        count['nodes'] += 1
-        if count['nodes'] > max_nodes or depth > MAX_DEPTH:
-            raise _Abandoned
-        cells = np.bincount(c, minlength=max(n, 1))
-        big = np.flatnonzero(cells > 1)
-        if len(big) == 0:
-            count['leaves'] += 1
-            lo, hi = np.minimum(c[bx], c[by]), np.maximum(c[bx], c[by])
-            cert = sorted((lo * (1 << 20) + hi * (1 << 8) + btype.astype(np.int64)).tolist())
-            if best['cert'] is None or cert < best['cert']:
-                best.update(cert=cert, n_aut=1, rank=c.copy(), table=np.argsort(c))
-            elif cert == best['cert']:
-                best['n_aut'] += 1
-                if c.tolist() < best['rank'].tolist():
-                    best['rank'] = c.copy()
-                best['table'] = np.minimum(best['table'], np.argsort(c))
-            return
-        k = int(big[0])
-        for v in np.flatnonzero(c == k):
-            child = np.where((c == k) & (np.arange(n) != v), k + 1, c)
-            visit(refine(child), depth + 1)
+    def leaf(c):
+        count['leaves'] += 1
+        lo, hi = np.minimum(c[bx], c[by]), np.maximum(c[bx], c[by])
+        cert = sorted((lo * (1 << 20) + hi * (1 << 8) + btype.astype(np.int64)).tolist())
+        if best['cert'] is None or cert < best['cert']:
+            best.update(cert=cert, n_aut=1, rank=c.copy(), table=np.argsort(c))
+        elif cert == best['cert']:
+            best['n_aut'] += 1
+            if c.tolist() < best['rank'].tolist():
+                best['rank'] = c.copy()
+            best['table'] = np.minimum(best['table'], np.argsort(c))
 
     try:
-        visit(refine(_ranks(label)), 0)
-    except _Abandoned:
+        count['nodes'] = search(label, bx, by, btype, max_nodes, leaf)
+    except Abandoned:
         return dict(out, status=STATUS_ABANDONED)
     rank, words = best['rank'], best['cert']
     inv = np.argsort(rank)                                             # the atom of rank p
@@ -325,7 +338,56 @@ def assumed_hydrogens(z, bond_sum):
     return next((v - bond_sum for v in SMILES_VALENCES[int(z)] if v >= bond_sum), 0)
 
 
-def smiles(canon_mol, kekule_result):
+def _stereo_marks(n, nbr, kek_h, stereo):
+    """What ``smiles`` writes for a stereo result in the canonical frame -> (tetra, slash): tetra {atom: True when its neighbours in
+    ascending index, an implicit H first, run anticlockwise seen from the first}; slash {(lo, hi): +1 | -1}, the direction of the
+    single bond lo - hi written lo first ('/' for +1), for the reference bonds of the marked double bonds."""
+    codes = np.asarray(stereo['canon_tetra'], dtype=np.int64).reshape(-1)
+    bcodes = np.asarray(stereo['canon_bond_stereo'], dtype=np.int64).reshape(-1)
+    tetra = {}
+    for a in range(min(n, len(codes))):
+        if codes[a] in (1, 2) and len(nbr[a]) + int(kek_h[a]) == 4 and int(kek_h[a]) <= 1:
+            # code 1: the determinant of the definition is positive for the neighbours in ascending rank, which is CLOCKWISE seen from
+            # the first of them (or from the implicit H); hand-derived, unchecked against RDKit
+            tetra[a] = codes[a] == 2
+    var, refs, rules = {}, [], []                                      # dir(lo -> hi); reference bonds; (p, q, r, t, sign): dir(p->q) dir(r->t) = sign
+    key = lambda u, v: (min(u, v), max(u, v))
+    get = lambda u, v: None if key(u, v) not in var else var[key(u, v)] * (1 if u < v else -1)
+
+    def put(u, v, d):
+        var[key(u, v)] = d if u < v else -d
+    for a in range(n):
+        for b, o, e in nbr[a]:
+            if a < b and o == 2 and e < len(bcodes) and bcodes[e] in (1, 2):
+                xs, ys = [u for u in nbr[a] if u[0] != b], [u for u in nbr[b] if u[0] != a]
+                if not xs or not ys or any(u[1] != 1 for u in xs + ys):
+                    continue
+                refs += [key(a, xs[0][0]), key(b, ys[0][0])]
+                rules.append((a, xs[0][0], b, ys[0][0], 1 if bcodes[e] == 1 else -1))      # cis: both bonds point the same way
+                rules += [(c, us[0][0], c, us[1][0], -1) for c, us in ((a, xs), (b, ys)) if len(us) == 2]
+    pending = True
+    while pending:
+        pending = False
+        for p_, q, r, t, sign in rules:
+            d1, d2 = get(p_, q), get(r, t)
+            if d1 is not None and d2 is not None:
+                if d1 * d2 != sign:
+                    return tetra, {}                                   # contradictory codes around a ring: no slash is written
+            elif d1 is not None:
+                put(r, t, d1 * sign)
+                pending = True
+            elif d2 is not None:
+                put(p_, q, d2 * sign)
+                pending = True
+        if not pending:
+            seed = next((rule for rule in rules if get(rule[0], rule[1]) is None and key(rule[0], rule[1]) in refs), None)
+            if seed is not None:
+                put(seed[0], seed[1], -1)                              # the first reference bond reads '/' when its substituent is written first
+                pending = True
+    return tetra, {k: var[k] for k in refs if k in var}
+
+
+def smiles(canon_mol, kekule_result, stereo=None):
     """A SMILES string of the CANONICAL molecule (``canonical_mol``) from the Kekulé result of THAT molecule (``kekule.kekulize_ref``
     of it, or a ``kekule.mol_result`` slice of ``kekule.launch`` on the canonical arrays): that is what makes the Kekulé structure,
     and so the string, independent of the sampler's atom order.  THIS PROJECT'S OWN STRING: its grammar is unchecked against RDKit
@@ -337,7 +399,17 @@ def smiles(canon_mol, kekule_result):
     again from the atom after the one that closes them; '%nn' from 10 on; at an atom the closing digits come first; the bond symbol
     of a ring closure goes at its opening.  An atom is bracketed iff its charge is non-zero or its ``kek_h`` differs from
     ``assumed_hydrogens``; a bracket atom writes H, H2, ... and +.  -> None when `canon_mol` is None, the molecule is not
-    kekulizable or a bond has no order (a type outside the featuriser's)."""
+    kekulizable or a bond has no order (a type outside the featuriser's).
+
+    stereo: None, and the string is the constitutional one; or the stereo result of the molecule (``stereo.stereo_ref``'s dict or a
+    ``stereo.mol_result`` slice), and the string is ISOMERIC.  The canonical arrays are the same under every optimal leaf, so
+    `canon_mol` is also the molecule in the order of ``stereo_rank``, the frame in which ``canon_tetra`` and ``canon_bond_stereo`` (W)
+    are stated: the string is a function of the isomeric key.  A centre with a non-zero code becomes a bracket atom with '@' or '@@'
+    and its H (when its bonds and hydrogens make four neighbours, at most one of them H); the neighbour order of OpenSMILES is the
+    preceding atom, the implicit H, the ring-closure digits as written, the branches.  A candidate double bond with a non-zero code
+    gets '/' or '\\' on one single bond at each end (the other neighbour of smallest rank), ring closures at their opening; where
+    the codes around a ring of conjugated candidates contradict each other no slash is written at all.  The handedness convention and
+    the slash rule are HAND-DERIVED from the OpenSMILES text and UNCHECKED against RDKit."""
     from . import kekule
     if canon_mol is None:
         return None
@@ -382,23 +454,33 @@ def smiles(canon_mol, kekule_result):
                 seen[b] = True
                 children[a].append((b, o))
                 stack.append((b, 0))
+    tetra, slash = _stereo_marks(n, nbr, kek_h, stereo) if stereo is not None and int(stereo['status']) == 0 else ({}, {})
     sym = {1: '', 2: '=', 3: '#'}
+
+    def bond_text(a, b, o):
+        d = slash.get((min(a, b), max(a, b))) if o == 1 else None
+        return sym[o] if d is None else '/' if d * (1 if a < b else -1) > 0 else '\\'
     digit = lambda d: str(d) if d < 10 else '%%%02d' % d
     free, taken = [], {}                                               # freed digits (kept sorted), (opener, closer) -> digit
     nxt = [1]
 
-    def atom_text(a):
+    def atom_text(a, parent):
         z, bond_sum = int(ele[a]), sum(o for _, o, _ in nbr[a])
         if z not in SYMBOL:
             raise ValueError(f'no symbol for element {z}')
         h, q = int(kek_h[a]), int(charge[a])
-        if q == 0 and h == assumed_hydrogens(z, bond_sum):
+        mark = ''
+        if a in tetra:
+            listed = ([] if parent is None else [parent]) + [-1] * h + sorted(closes[a]) + [b for b, _ in sorted(opens[a])] + [b for b, _ in children[a]]
+            odd = sum(listed[i] > listed[j] for i in range(4) for j in range(i + 1, 4)) & 1
+            mark = '@' if tetra[a] != bool(odd) else '@@'
+        if q == 0 and h == assumed_hydrogens(z, bond_sum) and not mark:
             return SYMBOL[z]
-        return '[' + SYMBOL[z] + ('H' + (str(h) if h > 1 else '') if h else '') + \
+        return '[' + SYMBOL[z] + mark + ('H' + (str(h) if h > 1 else '') if h else '') + \
             (('+' if q > 0 else '-') + (str(abs(q)) if abs(q) > 1 else '') if q else '') + ']'
 
-    def write(a):
-        text, freed = atom_text(a), []
+    def write(a, parent=None):
+        text, freed = atom_text(a, parent), []
         for b in sorted(closes[a]):
             d = taken.pop((b, a))
             text += digit(d)
@@ -409,11 +491,11 @@ def smiles(canon_mol, kekule_result):
             else:
                 d, nxt[0] = nxt[0], nxt[0] + 1
             taken[(a, b)] = d
-            text += sym[o] + digit(d)
+            text += bond_text(a, b, o) + digit(d)
         free.extend(freed)
         free.sort()
         for k, (b, o) in enumerate(children[a]):
-            sub = sym[o] + write(b)
+            sub = bond_text(a, b, o) + write(b, a)
             text += sub if k == len(children[a]) - 1 else '(' + sub + ')'
         return text
     limit = sys.getrecursionlimit()
@@ -424,11 +506,13 @@ def smiles(canon_mol, kekule_result):
         sys.setrecursionlimit(limit)
 
 
-def smiles_mols(mols, results, device=None, tables=None):
+def smiles_mols(mols, results, device=None, tables=None, stereo=None):
     """``smiles`` of every molecule of a list from its results dict (host arrays, one entry per molecule): the canonical molecules
     are kekulized together, on `device` (``kekule.kekulize_mols``) or with ``kekule.kekulize_ref`` when it is None -> a list of
-    strings, None where a molecule has none"""
+    strings, None where a molecule has none.  stereo: the stereo results of the same list (``stereo.stack_ref`` / ``stereo_mols``,
+    host arrays) for isomeric strings, or None"""
     from . import kekule
+    from .stereo import mol_result as stereo_of
     canon = [canonical_mol(info, mol_result(results, m)) for m, info in enumerate(mols)]
     have = [m for m, c in enumerate(canon) if c is not None]
     out = [None] * len(mols)
@@ -439,7 +523,7 @@ def smiles_mols(mols, results, device=None, tables=None):
     else:
         kek = to_host(kekule.kekulize_mols([canon[m] for m in have], device, tables))
     for k, m in enumerate(have):
-        out[m] = smiles(canon[m], kekule.mol_result(kek, k))
+        out[m] = smiles(canon[m], kekule.mol_result(kek, k), None if stereo is None else stereo_of(stereo, m))
     return out
 
 

@@ -8,6 +8,7 @@
 // bonds, the adjacency as CSR (neighbour and type in 16 bits), the colours as bytes, the 64-bit keys of a refinement round, the
 // depth-first stack of at most 64 colour snapshots (16 KB) with the target colour and the cursor of every level, and the best and the
 // candidate certificate at 512 words each.  There is no workspace and no scratch: no array is indexed at run time outside LDS.
+// The staging, the refinement and the walk are those of mdx_canon_body.h, which mdx_stereo.hip walks too; this file is the leaf.
 //
 // A refinement round: thread a sums mix(mix(c(u) + 1) + type) over its neighbours, writes key = c << 32 | h, and after a barrier
 // counts the smaller and the equal keys over the n keys -- every lane reads the same address, a broadcast without bank conflicts.
@@ -22,16 +23,13 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_canon_args.h"
+#include "mdx_canon_body.h"
 #include "mdx_mol.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CN_ATOMS = 256, CN_BONDS = 512, CN_NONE = 1 << 16;
-constexpr unsigned CN_PAD = 0xffffffffu;  // sorts behind every word
 enum { C_STATUS, C_NODES, C_LEAVES, C_AUT, C_BONDS };
 static_assert(C_BONDS + 1 == CN_STATS && CN_STATS == MDX_CANON_STATS, "the columns of mol_stats");
 
@@ -42,35 +40,10 @@ struct CnArgs {
 };
 
 struct CnShared {
-  u64 key[CN_ATOMS];
+  CnGraph g;                           // the walk's own state (mdx_canon_body.h)
   unsigned best[CN_BONDS], cand[CN_BONDS];
-  unsigned bond[CN_BONDS];             // i | j << 8 | type << 16 | 1 << 24, or 0 for an ignored bond
-  int off[CN_ATOMS + 1], cur[CN_ATOMS], wave_total[4], red[4];
-  unsigned short adj[2 * CN_BONDS];    // neighbour | type << 8
-  unsigned short cursor[CN_MAX_DEPTH];
-  unsigned char snap[CN_MAX_DEPTH][CN_ATOMS];
-  unsigned char col[CN_ATOMS], best_rank[CN_ATOMS], table[CN_ATOMS];
-  unsigned char tcol[CN_MAX_DEPTH];
+  unsigned char best_rank[CN_ATOMS], table[CN_ATOMS];
 };
-
-__device__ inline unsigned mix(unsigned h) {  // murmur3 fmix32
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  return h ^ (h >> 16);
-}
-
-// the smallest v over the workgroup, the same in every thread; two barriers: what was written before is visible after, and `red` is
-// free again on return
-__device__ inline int block_min(int v, int* red) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = min(min(red[0], red[1]), min(red[2], red[3]));
-  __syncthreads();
-  return v;
-}
 
 // rank -1 and zeros for a molecule that is not measured; its per-atom and per-bond slots only when they are inside the arrays
 __device__ inline void write_unmeasured(const CnArgs& A, int m, int status, const MolView& v) {
@@ -87,30 +60,6 @@ __device__ inline void write_unmeasured(const CnArgs& A, int m, int status, cons
     A.o.canon_bond_index[e] = 0, A.o.canon_bond_index[A.mol.E_cap + e] = 0, A.o.canon_bond_type[e] = 0;
 }
 
-// Refinement of s.col (visible on entry) until no colour changes -> the size of this thread's cell.  Ends on a barrier.
-__device__ inline int refine(CnShared& s, int n) {
-  const int tid = threadIdx.x;
-  const int a0 = tid < n ? s.off[tid] : 0, a1 = tid < n ? s.off[tid + 1] : 0;
-  for (;;) {
-    const unsigned c = s.col[tid];
-    unsigned h = 0u;
-    for (int a = a0; a < a1; ++a) {
-      const unsigned w = s.adj[a];
-      h += mix(mix((unsigned)s.col[w & 0xffu] + 1u) + (w >> 8));
-    }
-    s.key[tid] = (u64)c << 32 | h;
-    __syncthreads();
-    const u64 k = s.key[tid];
-    int less = 0, eq = 0;
-    for (int u = 0; u < n; ++u) {
-      const u64 ku = s.key[u];
-      less += ku < k, eq += ku == k;
-    }
-    if (tid < n) s.col[tid] = (unsigned char)less;
-    if (!__syncthreads_or(tid < n && (unsigned)less != c)) return eq;
-  }
-}
-
 __global__ __launch_bounds__(256) void mol_canon_kernel(const CnArgs A) {
   __shared__ CnShared s;
   const int m = blockIdx.x, tid = threadIdx.x;
@@ -125,128 +74,42 @@ __global__ __launch_bounds__(256) void mol_canon_kernel(const CnArgs A) {
     write_unmeasured(A, m, 1, v);
     return;
   }
-  const int *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
   const bool in = tid < n;
   const int atype = in ? A.mol.atom_type[n0 + tid] : 0;
   const int label = in && A.o.atom_label ? A.o.atom_label[n0 + tid] : atype;
-
-  // ---- the molecule into LDS: bonds, degrees, CSR
-  s.cur[tid] = 0, s.col[tid] = 0;
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e];
-    if (!mol_bond_ok(i, j, n)) {
-      s.bond[e] = 0u;
-      continue;
-    }
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | ((unsigned)bt[e] & 0xffu) << 16 | 1u << 24;
-    atomicAdd(&s.cur[i], 1), atomicAdd(&s.cur[j], 1);
-  }
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, t = (bd >> 16) & 0xffu;
-    s.adj[atomicAdd(&s.cur[i], 1)] = (unsigned short)(j | t << 8);  // the order inside a row does not matter: h is a sum
-    s.adj[atomicAdd(&s.cur[j], 1)] = (unsigned short)(i | t << 8);
-  }
-  // ---- the initial colouring: how many labels are smaller
-  s.key[tid] = (u64)(unsigned)label;
-  __syncthreads();
-  const int nbv = s.off[CN_ATOMS] / 2;  // the valid bonds
-  {
-    int less = 0;
-    for (int u = 0; u < n; ++u) less += s.key[u] < (u64)(unsigned)label;
-    if (in) s.col[tid] = (unsigned char)less;
-  }
-  __syncthreads();
+  const int nbv = stage_molecule(s.g, A.mol, h0, n, nb, label);  // the valid bonds
   int P = 2;  // the words are sorted over the next power of two
   while (P < nb) P <<= 1;
 
-  int depth = 0, nodes = 1, leaves = 0, n_aut = 0, status = 0;  // uniform
-  int eq = refine(s, n);
-  for (;;) {
-    // ---- the node whose colouring is s.col, at `depth`, with `depth` snapshots below it
-    const int k = block_min(in && eq > 1 ? (int)s.col[tid] : CN_NONE, s.red);
-    if (k == CN_NONE) {  // a leaf: the certificate
-      ++leaves;
-      for (int e = tid; e < P; e += 256) {
-        const unsigned bd = e < nb ? s.bond[e] : 0u;
-        unsigned w = CN_PAD;
-        if (bd) {
-          const unsigned ci = s.col[bd & 0xffu], cj = s.col[(bd >> 8) & 0xffu];
-          w = min(ci, cj) << 20 | max(ci, cj) << 8 | ((bd >> 16) & 0xffu);
+  int nodes = 1, leaves = 0, n_aut = 0;  // uniform
+  const int status = canon_walk(s.g, n, A.max_nodes, nodes, [&]() {  // a leaf: the certificate
+    ++leaves;
+    for (int e = tid; e < P; e += 256) s.cand[e] = bond_word(e < nb ? s.g.bond[e] : 0u, s.g.col);
+    sort_words(s.cand, P);
+    int diff = CN_NONE;
+    if (n_aut > 0)
+      for (int e = tid; e < nbv; e += 256)
+        if (s.cand[e] != s.best[e]) {
+          diff = e;
+          break;
         }
-        s.cand[e] = w;
-      }
-      for (int kk = 2; kk <= P; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-          __syncthreads();
-          if (tid < P / 2) {
-            const int i = 2 * tid - (tid & (j - 1)), l = i | j;
-            const unsigned a = s.cand[i], b = s.cand[l];
-            if ((a > b) == ((i & kk) == 0)) s.cand[i] = b, s.cand[l] = a;
-          }
-        }
-      __syncthreads();
-      int diff = CN_NONE;
-      if (n_aut > 0)
-        for (int e = tid; e < nbv; e += 256)
-          if (s.cand[e] != s.best[e]) {
-            diff = e;
-            break;
-          }
-      diff = n_aut > 0 ? block_min(diff, s.red) : 0;
-      const bool better = n_aut == 0 || (diff != CN_NONE && s.cand[diff] < s.best[diff]);
-      __syncthreads();  // best[diff] has been read
-      if (better) {
-        n_aut = 1;
-        for (int e = tid; e < nbv; e += 256) s.best[e] = s.cand[e];
-        s.best_rank[tid] = s.col[tid];
-        if (in) s.table[s.col[tid]] = (unsigned char)tid;
-      } else if (diff == CN_NONE) {  // another optimal leaf
-        ++n_aut;
-        const int first = block_min(in && s.col[tid] != s.best_rank[tid] ? tid : CN_NONE, s.red);
-        const bool smaller = first != CN_NONE && s.col[first] < s.best_rank[first];
-        __syncthreads();  // best_rank[first] has been read
-        if (smaller) s.best_rank[tid] = s.col[tid];
-        if (in) s.table[s.col[tid]] = (unsigned char)min((int)s.table[s.col[tid]], tid);  // one thread per rank
-      }
-    } else {
-      if (depth == CN_MAX_DEPTH) {
-        status = 2;
-        break;
-      }
-      s.snap[depth][tid] = s.col[tid];
-      if (tid == 0) s.tcol[depth] = (unsigned char)k, s.cursor[depth] = 0;
-      ++depth;
+    diff = n_aut > 0 ? block_min(diff, s.g.red) : 0;
+    const bool better = n_aut == 0 || (diff != CN_NONE && s.cand[diff] < s.best[diff]);
+    __syncthreads();  // best[diff] has been read
+    if (better) {
+      n_aut = 1;
+      for (int e = tid; e < nbv; e += 256) s.best[e] = s.cand[e];
+      s.best_rank[tid] = s.g.col[tid];
+      if (in) s.table[s.g.col[tid]] = (unsigned char)tid;
+    } else if (diff == CN_NONE) {  // another optimal leaf
+      ++n_aut;
+      const int first = block_min(in && s.g.col[tid] != s.best_rank[tid] ? tid : CN_NONE, s.g.red);
+      const bool smaller = first != CN_NONE && s.g.col[first] < s.best_rank[first];
+      __syncthreads();  // best_rank[first] has been read
+      if (smaller) s.best_rank[tid] = s.g.col[tid];
+      if (in) s.table[s.g.col[tid]] = (unsigned char)min((int)s.table[s.g.col[tid]], tid);  // one thread per rank
     }
-    // ---- the next child of the deepest level that still has one
-    bool found = false;
-    while (depth > 0) {
-      __syncthreads();  // the snapshot, its cursor, and whatever the leaf wrote
-      const int L = depth - 1, kk = s.tcol[L], from = s.cursor[L];
-      const int c = s.snap[L][tid];
-      const int pick = block_min(in && c == kk && tid >= from ? tid : CN_NONE, s.red);
-      if (pick == CN_NONE) {
-        --depth;
-        continue;
-      }
-      if (++nodes > A.max_nodes) {
-        status = 2;
-        break;
-      }
-      if (tid == 0) s.cursor[L] = (unsigned short)(pick + 1);
-      s.col[tid] = (unsigned char)(c == kk && tid != pick ? kk + 1 : c);
-      __syncthreads();
-      found = true;
-      break;
-    }
-    if (status != 0 || !found) break;
-    eq = refine(s, n);
-  }
+  });
   __syncthreads();
   if (status != 0) {  // uniform
     write_unmeasured(A, m, status, v);
@@ -263,7 +126,7 @@ __global__ __launch_bounds__(256) void mol_canon_kernel(const CnArgs A) {
       float* q = A.o.canon_pos + 3 * (n0 + r);
       q[0] = p[0], q[1] = p[1], q[2] = p[2];
     }
-    s.cur[r] = label;  // the labels by rank, for the hash
+    s.g.cur[r] = label;  // the labels by rank, for the hash
   }
   for (int e = tid; e < nb; e += 256) {
     const unsigned w = e < nbv ? s.best[e] : 0u;
@@ -275,7 +138,7 @@ __global__ __launch_bounds__(256) void mol_canon_kernel(const CnArgs A) {
     u64 h = 0xcbf29ce484222325ull;
     const u64 prime = 0x100000001b3ull;
     h = (h ^ (u64)(unsigned)n) * prime;
-    for (int p = 0; p < n; ++p) h = (h ^ (u64)(unsigned)s.cur[p]) * prime;
+    for (int p = 0; p < n; ++p) h = (h ^ (u64)(unsigned)s.g.cur[p]) * prime;
     h = (h ^ (u64)(unsigned)nbv) * prime;
     for (int e = 0; e < nbv; ++e) h = (h ^ (u64)s.best[e]) * prime;
     A.o.cert_hash[m] = (int64_t)h;

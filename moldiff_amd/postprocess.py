@@ -303,6 +303,24 @@ class FeaturizeMol(object):
         canonical, keep = canon.canonical_compact(cm, out, select)
         return attach(out, cm, select, n_atoms, canon.LAYOUT), canonical, keep
 
+    def stereo_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
+                     atom_label=None, flat_tol=None, bond_tol=None):
+        """``decode_batch``'s device part + the canonical labelling and the stereo perception of every decoded molecule
+        (``mdx_mol_canon``, then ``mdx_mol_stereo``; see ``moldiff_amd/stereo.py``).  Nothing is copied to the host and nothing
+        synchronises.  select, max_nodes, atom_label: as for ``canon_batch``.  -> (canon results, stereo results): the dict of
+        ``canon_batch`` and the results dict of device tensors of ``stereo.launch`` (the per-molecule numbers of ``stereo.STAT_KEYS``,
+        the two hashes, n_atoms, n_bonds (B); the words, stereo_rank, atom_tetra and bond_stereo in the decode's own layout, molecule
+        m at atom_ptr[m] / bond_ptr[m]).  A masked molecule keeps its place with status 0, n_atoms 0, stereo_rank -1 and every other
+        output 0.  These are the molecules AS DECODED; the stereo model is this project's own, not RDKit's and not CIP.  Two bonds
+        between one pair of atoms cannot come out of the decode.  Like ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import canon, stereo
+        max_nodes = canon.DEFAULT_MAX_NODES if max_nodes is None else max_nodes
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        c = canon.launch(cm, max_nodes, select=select, atom_label=atom_label)
+        s = stereo.launch(cm, c, stereo.DEFAULT_FLAT_TOL if flat_tol is None else flat_tol, stereo.DEFAULT_BOND_TOL if bond_tol is None else bond_tol,
+                          max_nodes=max_nodes, select=select, atom_label=atom_label, atomic_numbers=self.atomic_numbers.tolist())
+        return attach(c, cm, select, n_atoms, canon.LAYOUT), attach(s, cm, select, n_atoms, stereo.LAYOUT)
+
     def framework_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, mode=0, sys_bins=None, select=None):
         """``decode_batch``'s device part + the framework and the ring systems of every decoded molecule (``mdx_mol_rings``, then
         ``mdx_mol_framework``; see ``moldiff_amd/framework.py``).  mode: bit 0 EXO, bit 1 GENERIC.  Nothing is copied to the host and

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--frameworks]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--frameworks]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -62,6 +62,13 @@ canonical order and the Kekulé structure of the canonical form; unchecked again
 stay what they are, from the molecule as decoded.  ``--canonical_max_nodes`` (``sample.canonical_max_nodes``) is the search budget: a
 molecule whose unpruned tree is larger is reported as abandoned (status 2), which is what the nearly complete bond graphs of untrained
 weights get.  Without the option nothing changes.
+``--stereo`` (config key ``sample.stereo``; the flag wins; it implies ``--canonical``), an addition beyond the reference: rank 0 perceives
+the stereo of the FINISHED molecules from their coordinates on the device batch by batch (``moldiff_amd/stereo.py``: this project's own
+model, not RDKit's perception and not CIP, unverified against RDKit, blind to allenes, atropisomers and nitrogen inversion) and writes
+``stereo.npz`` (per-molecule arrays, the canonical stereo words, ``stereo_rank``, ``atom_tetra``, ``bond_stereo``) and ``stereo.json``
+(their summary with the isomeric uniqueness, the share of chiral molecules and of flat centres).  ``--stereo_flat_tol`` /
+``--stereo_bond_tol`` (``sample.stereo_flat_tol`` / ``sample.stereo_bond_tol``; 0.1 each) are the two thresholds.  With ``--kekulize`` the
+strings of ``samples.smi`` are isomeric ('@', '/'); ``canon.npz`` and ``canon.json`` stay what they are.  Without the option nothing changes.
 ``--frameworks`` (config key ``sample.frameworks``; the flag wins), an addition beyond the reference: rank 0 cuts the FINISHED molecules
 into framework, ring systems, linkers and side chains on the device batch by batch (``moldiff_amd/framework.py``: this project's own
 definition, not RDKit's MurckoScaffold), keys the pieces with the canonical labelling and writes ``frameworks.npz`` (results and keys)
@@ -344,6 +351,26 @@ def add_canonical_argument(ap):
     return ap
 
 
+def stereo_option(flag, flat_tol, bond_tol, sample_cfg):
+    """whether to write the stereo files, and the two thresholds of ``moldiff_amd/stereo.py``: the command line (None = not given) wins
+    over the config's ``sample.stereo``, ``sample.stereo_flat_tol`` and ``sample.stereo_bond_tol``; 0.1 where neither says"""
+    from . import stereo
+    pick = lambda v, key, default: float(v if v is not None else sample_cfg.get(key) if sample_cfg.get(key) is not None else default)
+    flat, bond = pick(flat_tol, 'stereo_flat_tol', stereo.DEFAULT_FLAT_TOL), pick(bond_tol, 'stereo_bond_tol', stereo.DEFAULT_BOND_TOL)
+    stereo._check(flat, bond, 1)
+    return bool(flag if flag is not None else sample_cfg.get('stereo')), flat, bond
+
+
+def add_stereo_argument(ap):
+    """``--stereo`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--stereo', action='store_true', default=None,
+                    help='perceive the stereo of the finished molecules on the device and write stereo.npz and stereo.json; implies '
+                         '--canonical, and with --kekulize samples.smi is isomeric (overrides sample.stereo)')
+    ap.add_argument('--stereo_flat_tol', type=float, default=None, help='the flatness threshold of a centre (overrides sample.stereo_flat_tol; 0.1)')
+    ap.add_argument('--stereo_bond_tol', type=float, default=None, help='the cis / trans threshold (overrides sample.stereo_bond_tol; 0.1)')
+    return ap
+
+
 def frameworks_option(flag, generic, exo, sample_cfg):
     """whether to write the framework files, and the mode of ``moldiff_amd/framework.py``: the command line's flags (None = not given)
     win over the config's ``sample.frameworks``, ``sample.frameworks_generic`` and ``sample.frameworks_exo``"""
@@ -364,7 +391,7 @@ def add_frameworks_argument(ap):
 
 
 def main(argv=None):
-    args = add_frameworks_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))).parse_args(argv)
+    args = add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -450,24 +477,34 @@ def main(argv=None):
     if kek_write:
         features.append(Feature(lambda gen: kekule.kekulize_mols(gen, device, kek_tables), kekule, 'kekule',
                                 after=lambda res: kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)))
-    if canonical_option(args.canonical, config.sample):
-        from . import canon
+    stereo_on, flat_tol, bond_tol = stereo_option(args.stereo, args.stereo_flat_tol, args.stereo_bond_tol, config.sample)
+    if canonical_option(args.canonical, config.sample) or stereo_on:
+        from . import canon, stereo
+        held = {}   # the stereo part of the batch at hand, and the joined canon results for the stereo summary
         canon_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or canon.DEFAULT_MAX_NODES
         if not 1 <= canon_nodes <= canon.MAX_NODES_LIMIT:
             raise ValueError(f'canonical_max_nodes must lie in 1 .. 2^20, got {canon_nodes}')
 
         def run_canon(gen):
-            part = to_host(canon.canon_mols(gen, device, max_nodes=canon_nodes, atomic_numbers=Z))
+            if stereo_on:
+                part, held['stereo'] = (to_host(r) for r in stereo.stereo_mols(gen, device, None, flat_tol, bond_tol, max_nodes=canon_nodes,
+                                                                                 atomic_numbers=Z, with_canon=True))
+            else:
+                part = to_host(canon.canon_mols(gen, device, max_nodes=canon_nodes, atomic_numbers=Z))
             if kek_write:   # the strings need the canonical part and the Kekulé tables of the same batch
-                for info, text in zip(gen, canon.smiles_mols(gen, part, device, kek_tables)):
+                for info, text in zip(gen, canon.smiles_mols(gen, part, device, kek_tables, held.get('stereo'))):
                     info['smiles'] = text
             return part
 
         def write_smi(res):
+            held['canon'] = res
             if kek_write:
                 with open(os.path.join(log_dir, 'samples.smi'), 'w') as f:
                     f.writelines('%s\t%d\n' % (m['smiles'], m['mol_id']) for m in pool['finished'] if m.get('smiles'))
         features.append(Feature(run_canon, canon, 'canon', after=write_smi))
+        if stereo_on:   # behind canon: its batch part is there, and so are the joined canon results when the summary is written
+            features.append(Feature(lambda gen: held.pop('stereo'), stereo, 'stereo',
+                                    summary=lambda res: dict(stereo.summary(res, held['canon']), flat_tol=flat_tol, bond_tol=bond_tol)))
     fw_write, fw_mode = frameworks_option(args.frameworks, args.frameworks_generic, args.frameworks_exo, config.sample)
     if fw_write:
         from . import framework
