@@ -837,6 +837,55 @@ int mdx_mol_stereo(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, 
                    int32_t max_nodes, int32_t* canon_tetra, int32_t* canon_bond_stereo, int32_t* mirror_tetra,
                    int32_t* mirror_bond_stereo, int32_t* stereo_rank, int32_t* atom_tetra, int32_t* bond_stereo, int32_t* mol_stats, int64_t* stereo_hash, int64_t* mirror_hash, void* stream);
 
+/* ---- Symmetry-aware best RMSD between conformers of one constitution ------------------------------------------------------
+ * The reference's `global_3d` metric is get_rdkit_rmsd (utils/scoring_func.py:56-74): rdMolAlign.GetBestRMS(mol, mol3d), the RMSD
+ * after optimal rigid superposition, minimised over every atom mapping that the symmetry of the molecule allows.  mdx_mol_bestrms is
+ * the alignment half of it.  There is NO CONFORMER GENERATION here (the reference's ETKDG + UFF side comes from elsewhere), the atoms
+ * are the HEAVY ATOMS of the compact molecule, and the symmetry group is that of THIS PROJECT'S LABELLED GRAPH (mdx_mol_canon; aromatic
+ * bonds are a type of their own), which can be smaller than RDKit's substructure match on a kekulised input.  It is pure mathematics;
+ * a plain restatement (moldiff_amd/rmsd.py: best_rms_ref, numpy's SVD) agrees to a tolerance derived from float64 alone.  Agreement
+ * with RDKit's GetBestRMS beyond this shared definition is UNMEASURED.
+ *
+ * THE QUANTITY.  A probe molecule A and a target B with the same full certificate of mdx_mol_canon: the same n, the same canonical
+ *   atom labels and the same canonical bond words.
+ *   ATOM MAPS.  Every OPTIMAL LEAF of A's search tree (its certificate equals the canonical one) has a rank vector c; it gives the
+ *     atom map a -> B's canonical atom c[a].  Over all optimal leaves these are exactly the n_aut graph-preserving maps of A onto B.
+ *   ONE MAP, all in float64: both point sets are centred (p_a: A's atoms; q_k: B's atoms in canonical order);
+ *     Ga = sum |p_a|^2, Gb = sum |q_k|^2, H = sum p_a q_{c[a]}^T, s1 >= s2 >= s3 >= 0 the singular values of H;
+ *     msd        = max(0, Ga + Gb - 2 (s1 + s2 + sign(det H) s3)) / n     proper rotations only, as GetBestRMS
+ *     msd_mirror = max(0, Ga + Gb - 2 (s1 + s2 - sign(det H) s3)) / n     the same against the mirror image of B
+ *   PER PAIR: msd and msd_mirror are the minima over all maps; msd_first is msd of the map given by A's own canonical rank (no symmetry
+ *     search: msd_first - msd is what the search bought); n_maps the maps evaluated (canon's n_aut).  n = 0 and n = 1 give 0.
+ *     These are MEAN SQUARED deviations; the RMSD is their root and is taken on the host, so that a comparison is not amplified
+ *     near zero.  Non-finite coordinates give unspecified values.
+ * INPUT.  The compact layout of mdx_mol_rings for the probes (atom_ptr .. select: as there); atom_pos, rank, canon_status and the
+ *   optional atom_label exactly as for mdx_mol_stereo.  The pairs as CSR: probe m owns the pairs pair_ptr[m] .. pair_ptr[m + 1]
+ *   (pair_ptr holds B + 1 values), pair_target[p] is the pair's target in 0 .. T - 1, and the per-pair arrays hold P_cap rows.  The
+ *   targets: tgt_ptr (T), tgt_n (T) and tgt_pos (tgt_atoms x 3, float32) IN CANONICAL ATOM ORDER -- what canon_pos of mdx_mol_canon
+ *   holds.  That a target has the probe's constitution is the CALLER'S WORD: the kernel only guards memory.
+ * OUTPUTS (device, plain stores by the probe's own workgroup, every sum in a fixed order: bit-reproducible, independent of the place
+ *   in the batch):
+ *   msd, msd_mirror, msd_first (P_cap) float64.    pair_stats [p][2] (int32): n_maps, status.
+ *   mol_stats [m][k], k < MDX_BESTRMS_STATS = 3 (int32): status, the nodes of the walk, the optimal leaves seen (canon's n_nodes, n_aut).
+ *   status of a pair: 0 measured; 1 no canonical form: canon_status[m] != 0, more than 256 atoms or 512 bonds, or a rank that is
+ *     not canon's for these arrays (outside 0 .. n - 1, or no leaf attains its certificate); 2 the walk exceeded this call's
+ *     max_nodes (1 .. 2^20) or depth 64; 3 the target cannot be this probe's: pair_target outside 0 .. T - 1, tgt_n != n, or an
+ *     extent outside tgt_pos.  1 and 2 are the probe's and stand in its mol_stats too.  With a non-zero status the floats and n_maps
+ *     are 0.  A probe under select gets status 0 and zeros.  A probe reaching past N_cap / Eh_stride is not read and nothing is
+ *     written for it; a pair extent outside 0 .. P_cap is no pair at all.  Rows that belong to no probe are not written.
+ * One workgroup of 256 threads per probe, thread a = atom a, the walk of mdx_mol_canon (csrc/mdx_canon_body.h); at an optimal leaf
+ * wave w takes the pairs w, w + 4, ..., sums H over its lanes and solves Horn's 4 x 4 quaternion matrix by cyclic Jacobi.  About 59 KB
+ * of LDS; no workspace, no global atomics.
+ * MDX_ERR_ARG, every output untouched: a null operand (select and atom_label excepted), a negative size, P_cap or tgt_atoms from 2^31
+ * on, max_nodes outside 1 .. 2^20.  B = 0 is accepted and writes nothing. */
+#define MDX_BESTRMS_STATS 3
+int mdx_mol_bestrms(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                    const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                    const int32_t* select, const float* atom_pos, const int32_t* atom_label, const int32_t* rank,
+                    const int32_t* canon_status, const int32_t* pair_ptr, const int32_t* pair_target, int64_t P_cap, int32_t T,
+                    const int32_t* tgt_ptr, const int32_t* tgt_n, const float* tgt_pos, int64_t tgt_atoms, int32_t max_nodes,
+                    double* msd, double* msd_mirror, double* msd_first, int32_t* pair_stats, int32_t* mol_stats, void* stream);
+
 /* ---- Frameworks and ring systems of decoded molecules: the skeleton without its decoration, as compact molecules ------
  * The reference's `ring_type` metric (utils/evaluation.py: RingAnalyzer.get_count_ring, get_freq_rings, get_ring_topo, fr_bicyclic)
  * reports which rings occur and how often, and scaffold uniqueness / diversity / novelty are the usual second half of a generative

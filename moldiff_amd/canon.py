@@ -264,14 +264,18 @@ def certificate(results, m):
     """The full certificate of molecule `m` of a results dict with host arrays, as bytes: the int32 sequence n, the labels at ranks
     0 .. n - 1, the number of valid bonds, the words.  Two measured molecules are the same labelled graph iff these are equal.
     None for a molecule that was not measured (non-zero status)."""
-    r = mol_result(results, m)
-    if r['status'] != STATUS_OK:
+    return certificate_of(mol_result(results, m))
+
+
+def certificate_of(r):
+    """the full certificate of one molecule's result (``canon_ref``'s dict or a ``mol_result`` slice): the one definition of the bytes"""
+    if int(r['status']) != STATUS_OK:
         return None
-    k = r['canon_n_bonds']
+    k = int(r['canon_n_bonds'])
     labels = r['canon_atom_label'] if 'canon_atom_label' in r else r['canon_atom_type']
-    bi = r['canon_bond_index'][:, :k].astype(np.int64)
-    words = bi[0] * (1 << 20) + bi[1] * (1 << 8) + r['canon_bond_type'][:k]
-    return np.concatenate([[r['n_atoms']], labels, [k], words]).astype(np.int32).tobytes()
+    bi = np.asarray(r['canon_bond_index'])[:, :k].astype(np.int64)
+    words = bi[0] * (1 << 20) + bi[1] * (1 << 8) + np.asarray(r['canon_bond_type'])[:k]
+    return np.concatenate([[int(r['n_atoms'])], labels, [k], words]).astype(np.int32).tobytes()
 
 
 def canonical_mol(info, result):

@@ -1,7 +1,7 @@
-// The search tree of the canonical labelling, shared by mdx_canon.hip (mdx_mol_canon) and mdx_stereo.hip (mdx_mol_stereo): the molecule
+// The search tree of the canonical labelling, shared by mdx_canon.hip (mdx_mol_canon), mdx_stereo.hip (mdx_mol_stereo) and mdx_bestrms.hip (mdx_mol_bestrms): the molecule
 // staged into LDS, colour refinement, and the unpruned walk (target cell, individualise, refine) with the leaf handled by the caller's
-// visitor.  The definition is the one of include/moldiff_hip.h (mdx_mol_canon); both kernels walk the same nodes in the same order, so
-// node count, depth and the set of leaves are the same in both.  One workgroup of 256 threads per molecule, thread a = atom a.
+// visitor.  The definition is the one of include/moldiff_hip.h (mdx_mol_canon); all kernels walk the same nodes in the same order, so
+// node count, depth and the set of leaves are the same in all.  One workgroup of 256 threads per molecule, thread a = atom a.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,6 +128,18 @@ __device__ inline void sort_words(unsigned* w, int P) {
       }
     }
   __syncthreads();
+}
+
+// where `word` stands in cw[0 .. nbv) (ascending), -1 when it does not: a leaf is optimal iff every bond word of it stands in the
+// sorted canonical certificate (the bonds of a simple graph give distinct words, so equal counts make it a bijection)
+__device__ inline int find_word(const unsigned* cw, int nbv, unsigned word) {
+  int lo = 0, hi = nbv;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cw[mid] < word) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < nbv && cw[lo] == word ? lo : -1;
 }
 
 // The whole tree from the initial colouring in s.col: `leaf()` is called by all threads at every leaf, with the leaf's ranks in s.col

@@ -132,17 +132,6 @@ __device__ inline void write_unmeasured(const StArgs& A, int m, int status, cons
   for (long long e = v.h0 + tid; e < v.h0 + v.nb; e += 256) A.o.canon_bond_stereo[e] = 0, A.o.mirror_bond_stereo[e] = 0, A.o.bond_stereo[e] = 0;
 }
 
-// where `word` stands in cw[0 .. nbv) (ascending), -1 when it does not
-__device__ inline int find_word(const unsigned* cw, int nbv, unsigned word) {
-  int lo = 0, hi = nbv;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (cw[mid] < word) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < nbv && cw[lo] == word ? lo : -1;
-}
-
 __device__ inline unsigned char mirrored(unsigned char c, bool atom) { return atom && c ? (unsigned char)(3 - c) : c; }
 
 __device__ inline int64_t fnv_bytes(const unsigned char* w, int len) {

@@ -349,11 +349,12 @@ def on_device(host_results, device, keep=()):
     return {k: v if k in keep else torch.from_numpy(v).to(device) for k, v in host_results.items()}
 
 
-def stats_main(argv, name, doc, helps, options, run, summary, compare):
+def stats_main(argv, name, doc, helps, options, run, summary, compare, extra=()):
     """The ``stats`` / ``compare`` command line of an evaluation module `name` with docstring `doc`.  helps: the help lines of the two
     commands; options: [(flag, add_argument keywords)] of ``stats`` beside samples, --out, --part, --device and --ref;
     run(mols, args, device) -> a results dict, device None for the Python path.  ``stats`` writes the results to --out and prints
-    their summary; ``compare`` prints ``compare`` of two such files."""
+    their summary; ``compare`` prints ``compare`` of two such files.  extra: further commands of the module as (name, help line,
+    add_arguments(parser), run(args))."""
     ap = argparse.ArgumentParser(prog='python -m moldiff_amd.' + name, description=doc.split('\n\n')[0])
     sub = ap.add_subparsers(dest='cmd', required=True)
     s = sub.add_parser('stats', help=helps[0])
@@ -367,7 +368,13 @@ def stats_main(argv, name, doc, helps, options, run, summary, compare):
     c = sub.add_parser('compare', help=helps[1])
     c.add_argument('a')
     c.add_argument('b')
+    for cmd, text, add, _ in extra:
+        add(sub.add_parser(cmd, help=text))
     args = ap.parse_args(argv)
+    for cmd, _, _, handler in extra:
+        if args.cmd == cmd:
+            handler(args)
+            return 0
     if args.cmd == 'stats':
         mols = load_mols(args.samples, args.part)
         if not args.ref:

@@ -321,6 +321,22 @@ class FeaturizeMol(object):
                           max_nodes=max_nodes, select=select, atom_label=atom_label, atomic_numbers=self.atomic_numbers.tolist())
         return attach(c, cm, select, n_atoms, canon.LAYOUT), attach(s, cm, select, n_atoms, stereo.LAYOUT)
 
+    def conformer_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
+                        tol=None, max_group=None):
+        """``decode_batch``'s device part + the conformer statistics of the decoded batch (``mdx_mol_canon``, then ``mdx_mol_bestrms``
+        over all pairs inside every group of equal full certificate; see ``moldiff_amd/rmsd.py``) -> the summary dict of
+        ``rmsd.summary``.  The coordinates and the canonical positions stay on the device; the grouping is exact, so canon's integer
+        arrays are copied to the host, and so are the per-pair result columns the summary is made of: unlike the other ``*_batch``
+        methods this call synchronises, and more than the summary crosses to the host.  tol: the RMSD in
+        Angstrom up to which two conformers are one (0.5: a convention, not tuned).  These are the molecules AS DECODED.  Like
+        ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import canon, rmsd
+        max_nodes = canon.DEFAULT_MAX_NODES if max_nodes is None else max_nodes
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        c = attach(canon.launch(cm, max_nodes, select=select), cm, select, n_atoms, canon.LAYOUT)
+        return rmsd.conformers(cm, c, rmsd.DEFAULT_TOL if tol is None else tol, rmsd.DEFAULT_MAX_GROUP if max_group is None else max_group,
+                               max_nodes=max_nodes, select=select)
+
     def framework_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, mode=0, sys_bins=None, select=None):
         """``decode_batch``'s device part + the framework and the ring systems of every decoded molecule (``mdx_mol_rings``, then
         ``mdx_mol_framework``; see ``moldiff_amd/framework.py``).  mode: bit 0 EXO, bit 1 GENERIC.  Nothing is copied to the host and

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--frameworks]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -371,6 +371,25 @@ def add_stereo_argument(ap):
     return ap
 
 
+def conformers_option(flag, tol, sample_cfg):
+    """whether to write the conformer files, and the RMSD in Angstrom up to which two conformers count as one
+    (``moldiff_amd/rmsd.py``): the command line (None = not given) wins over the config's ``sample.conformers`` and
+    ``sample.conformer_tol``; 0.5 where neither says -- a convention, not tuned"""
+    from . import rmsd
+    tol = float(tol if tol is not None else sample_cfg.get('conformer_tol') if sample_cfg.get('conformer_tol') is not None else rmsd.DEFAULT_TOL)
+    return bool(flag if flag is not None else sample_cfg.get('conformers')), rmsd._check_tol(tol)
+
+
+def add_conformers_argument(ap):
+    """``--conformers`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--conformers', action='store_true', default=None,
+                    help='measure the best RMSD between the finished molecules of equal constitution on the device and write '
+                         'conformers.npz and conformers.json; implies --canonical (overrides sample.conformers)')
+    ap.add_argument('--conformer_tol', type=float, default=None,
+                    help='two conformers are the same up to this RMSD in Angstrom (overrides sample.conformer_tol; 0.5: a convention, not tuned)')
+    return ap
+
+
 def frameworks_option(flag, generic, exo, sample_cfg):
     """whether to write the framework files, and the mode of ``moldiff_amd/framework.py``: the command line's flags (None = not given)
     win over the config's ``sample.frameworks``, ``sample.frameworks_generic`` and ``sample.frameworks_exo``"""
@@ -391,7 +410,7 @@ def add_frameworks_argument(ap):
 
 
 def main(argv=None):
-    args = add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))))).parse_args(argv)
+    args = add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -478,7 +497,8 @@ def main(argv=None):
         features.append(Feature(lambda gen: kekule.kekulize_mols(gen, device, kek_tables), kekule, 'kekule',
                                 after=lambda res: kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)))
     stereo_on, flat_tol, bond_tol = stereo_option(args.stereo, args.stereo_flat_tol, args.stereo_bond_tol, config.sample)
-    if canonical_option(args.canonical, config.sample) or stereo_on:
+    conformers_on, conformer_tol = conformers_option(args.conformers, args.conformer_tol, config.sample)
+    if canonical_option(args.canonical, config.sample) or stereo_on or conformers_on:
         from . import canon, stereo
         held = {}   # the stereo part of the batch at hand, and the joined canon results for the stereo summary
         canon_nodes = args.canonical_max_nodes or config.sample.get('canonical_max_nodes') or canon.DEFAULT_MAX_NODES
@@ -633,6 +653,12 @@ def main(argv=None):
                 json.dump((f.summary or f.module.summary)(res), fh, indent=1)
             if f.after is not None:
                 f.after(res)
+        if conformers_on:   # over the whole pool at once: the groups of equal constitution run across the batches
+            from . import rmsd
+            res = rmsd.conformer_results(pool['finished'], None, conformer_tol, device=device, max_nodes=canon_nodes, atomic_numbers=Z)
+            save_npz(res, os.path.join(log_dir, 'conformers.npz'))
+            with open(os.path.join(log_dir, 'conformers.json'), 'w') as fh:
+                json.dump(rmsd.summary(res), fh, indent=1)
         if checked:
             with open(os.path.join(log_dir, 'quality.json'), 'w') as f:
                 json.dump(dict(quality_summary(pool['finished'] + pool['failed'], len(pool['finished']), len(pool['failed']),
