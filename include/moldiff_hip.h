@@ -954,6 +954,75 @@ int mdx_mol_framework(int32_t B, const int32_t* atom_ptr, const int32_t* bond_pt
                       int32_t* sys_atom_type, int32_t* sys_atom_map, float* sys_pos, int32_t* sys_bond_index, int32_t* sys_bond_type,
                       void* stream);
 
+/* ---- Explicit hydrogens with 3D coordinates for decoded molecules, and their contacts ------------------------------------
+ * Every molecule this project writes is heavy-atom only; the reference itself reaches hydrogens only through Chem.AddHs inside
+ * get_rdkit_rmsd (utils/scoring_func.py:56-74).  mdx_mol_hydrogens places the hydrogens that a Kekulé assignment counts from the local
+ * geometry of the heavy atoms and measures the all-atom contacts of what it placed.  It is THIS PROJECT'S OWN IDEALISED PLACEMENT: NOT
+ * RDKit's AddHs(addCoords=True) and UNVERIFIED AGAINST IT.  Torsions of rotors (methyl, hydroxyl, amine) are fixed by the rule below,
+ * not by an energy; a pyramidal nitrogen takes the side set by the order of its neighbours; an atom without neighbours, and an atom
+ * whose only neighbour has no other, use fixed world axes, so such hydrogens do not turn with the molecule (WORLD_FRAME).  The length
+ * table and clash_tol are conventions.  Every output has exactly one value, and a plain restatement (moldiff_amd/hydrogens.py:
+ * addh_ref) agrees in the integers exactly and in the floats to float64 rounding.
+ *
+ * INPUT.  The compact layout of mdx_mol_rings (atom_ptr .. select: as there); a bond with an index outside the molecule or with i = j
+ *   is ignored.  atom_pos: 3 floats per atom slot, widened to float64 once; everything below is float64.  n_h (N_cap) and order
+ *   (Eh_stride): int32 device arrays, normally kek_h and kek_order of mdx_mol_kekulize, but any caller's arrays are legal: h =
+ *   n_h clamped to 0 .. 4 (CLAMPED when that changes it; an atom of a class outside 0 .. num_element - 1 has h = 0); the order of a
+ *   valid bond is `order` clamped to 1 .. 3, so 0 counts as 1.  A bond of type num_bond_types is AROMATIC whatever its order.  Two
+ *   bonds between one pair of atoms are a precondition violation as for mdx_mol_rings: unspecified results, in bounds.
+ *   HOST tables by atom class, validated by the call and sent as kernel arguments: xh_length[c] in Angstrom, 0 < L <= 4 (the shipped
+ *   defaults, moldiff_amd/hydrogens.py: C 1.09, N 1.01, O 0.96, F 0.92, P 1.42, S 1.34, Cl 1.27: this project's choice of textbook
+ *   values); planar_mask: bit c set = class c flattens next to a pi system (default {N}).  deg_tol in (0, 1), default 1e-3.
+ *   clash_tol in [0, 1000] Angstrom, default 1.5: a convention, untuned.
+ * GEOMETRY of an atom with d valid bonds (neighbours) and h hydrogens:
+ *   LINEAR (2, room 2)       it has a bond of order 3, or two of order 2;
+ *   TRIGONAL (1, room 3)     else, if it has a bond of order 2 or an aromatic bond; or its class is in planar_mask, it is not
+ *                            trigonal or linear by the rules so far, and some neighbour is (by those rules alone);
+ *   TETRAHEDRAL (0, room 4)  else.
+ *   NO_ROOM: h >= 1 and d + h > room.  None of the atom's hydrogens is placed.
+ * PLACEMENT of an atom a at p with h >= 1 that has room.  u_k: the unit vectors (v / sqrt(v.v), v = neighbour - p) to the neighbours
+ *   in ascending atom index; L: the class's length; hydrogen k stands at p + L dir_k.  (x.y = (x0 y0 + x1 y1) + x2 y2; |x| = sqrt(x.x);
+ *   x X y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0).)  theta = acos(-1/3), or 120 degrees for TRIGONAL.
+ *   d = 0  dir_k = the k-th fixed world direction.  TETRAHEDRAL: (1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1), each / sqrt 3; TRIGONAL:
+ *          (1,0,0), (-1/2, sqrt 3 / 2, 0), (-1/2, -sqrt 3 / 2, 0); LINEAR: (1,0,0), (-1,0,0).  WORLD_FRAME.
+ *   d = 1  e = u_1, n1 the neighbour.  LINEAR: dir_0 = -e.  Otherwise the reference w: walk n1's neighbours r != a in ascending
+ *          index, skip one that coincides with n1 or is not finite, w = the unit vector from n1 to r, take the first with
+ *          |e X w| >= deg_tol.  With none, w = the world axis with the smallest |e . axis|, the first of x, y, z among equals, and
+ *          WORLD_FRAME.  f1 = (w - (w.e) e) normalised, f2 = e X f1, dir_k = cos theta e + sin theta (cos phi_k f1 + sin phi_k f2);
+ *          TETRAHEDRAL phi_k = 180 + 120 k degrees (the first H anti to r), TRIGONAL phi = 180, then 0.
+ *   d = 2  s = u_1 + u_2, c = u_1 X u_2.  TRIGONAL (h = 1): dir_0 = -s / |s|; needs |s| >= deg_tol.  TETRAHEDRAL: needs |c| >= deg_tol
+ *          and |s| > 0; b = -s / |s|, n = c / |c|, beta = theta / 2: dir_0 = cos beta b + sin beta n, dir_1 = cos beta b - sin beta n.
+ *   d = 3  TETRAHEDRAL (h = 1): s = (u_1 + u_2) + u_3, dir_0 = -s / |s|; needs |s| >= deg_tol.
+ *   DEGENERATE: a needed condition fails, or a or a neighbour of it has a coordinate that is not finite, or a neighbour coincides
+ *   with a.  None of the atom's hydrogens is placed.  WORLD_FRAME is reported for atoms whose hydrogens are placed only.
+ *   The operation order of the restatement is part of the definition.
+ * CONTACTS.  A contact is a pair (placed H, another atom of the molecule: a heavy atom with finite coordinates, or a placed H), each
+ *   unordered pair once, without the 1-2 and 1-3 pairs: the H's parent, the parent's neighbours and the parent's other hydrogens.
+ *   Its length is |other - H|.
+ * OUTPUTS (device, plain stores by the molecule's own workgroup: bit-reproducible, independent of the place in the batch):
+ *   h_pos        [N_cap][4][3] float64: atom slot a's k-th hydrogen, k < h_count[a]; the rest 0.
+ *   h_count      per atom slot (int32): h when placed, else 0.
+ *   atom_flag    bits 0-1 the geometry, 4 NO_ROOM, 8 DEGENERATE, 16 WORLD_FRAME, 32 CLAMPED.
+ *   mol_stats    [m][k], k < MDX_HYDROGENS_STATS = 7 (int32):
+ *     0 status        0 measured; 1 too large: n_atoms > 256 or n_bonds > 512.  Every other output of the molecule is then 0.
+ *     1 n_h_wanted    the sum of h                      2 n_h_placed     the sum of h_count
+ *     3 n_no_room     atoms flagged NO_ROOM             4 n_degenerate   atoms flagged DEGENERATE
+ *     5 n_world_frame atoms flagged WORLD_FRAME         6 n_clash        contacts shorter than clash_tol
+ *   min_contact  [m] float64: the shortest contact, +inf when a measured molecule has none.
+ *   select, and a molecule reaching past N_cap / Eh_stride, as for mdx_mol_kekulize: status 0, all outputs 0, min_contact included
+ *   (the slots of the latter are not written).  Slots that belong to no molecule are not written.
+ * One workgroup of 256 threads per molecule; positions, adjacency and the 1024 x 3 table of hydrogens in LDS (about 41 KB); the
+ * pairs are dealt over the threads and reduced with wave shuffles.  No workspace, no global atomics.
+ * MDX_ERR_ARG, every output untouched: a null operand (select excepted), a negative size, num_element outside 1 .. 32, num_bond_types
+ * outside 1 .. 16, a length outside (0, 4], a planar_mask bit at or above num_element, deg_tol outside (0, 1), clash_tol outside
+ * [0, 1000].  B = 0 is accepted and writes nothing. */
+#define MDX_HYDROGENS_STATS 7
+int mdx_mol_hydrogens(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                      const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                      const int32_t* select, const float* atom_pos, const int32_t* n_h, const int32_t* order, int32_t num_element,
+                      int32_t num_bond_types, const double* xh_length, uint32_t planar_mask, double deg_tol, double clash_tol,
+                      double* h_pos, int32_t* h_count, int32_t* atom_flag, int32_t* mol_stats, double* min_contact, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -285,6 +285,28 @@ class FeaturizeMol(object):
             return on_device(kekule.empty(), cm.device)
         return attach(kekule.launch(cm, tables, max_steps, select=select), cm, select, n_atoms, kekule.LAYOUT)
 
+    def addh_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, tables=None, graph=None, *, select=None,
+                   deg_tol=None, clash_tol=None):
+        """``decode_batch``'s device part + the Kekulé assignment and the explicit hydrogens of every decoded molecule
+        (``mdx_mol_kekulize`` with the default chemistry, then ``mdx_mol_hydrogens``; see ``moldiff_amd/hydrogens.py``).  tables: a
+        ``hydrogens.HydrogenTables`` made for this featuriser (None = the defaults).  Nothing is copied to the host and nothing
+        synchronises.  select: (n_graphs) device tensor; a molecule with 0 keeps its place with status 0, n_atoms 0 and every output
+        0.  -> (kekule results, hydrogen results): the dict of ``kekulize_batch`` and the results dict of device tensors of
+        ``hydrogens.launch`` (the per-molecule numbers of ``hydrogens.STAT_KEYS`` and n_atoms (B, int32), min_contact (B, float64);
+        h_count, atom_flag and h_pos (4 x 3 float64 per atom) in the decode's own layout, molecule m at atom_ptr[m]).  These are the
+        molecules AS DECODED; the placement is this project's idealised rule, not RDKit's AddHs and unverified against it, and
+        clash_tol (1.5 Angstrom) is a convention.  Like ``decode_batch``, it needs a batch with at least one half-edge."""
+        from . import hydrogens, kekule
+        tables = hydrogens.HydrogenTables(self.atomic_numbers.tolist(), self.num_bond_types) if tables is None else tables
+        self._same_featuriser(tables, 'the tables were')
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        if cm.B == 0:
+            return on_device(kekule.empty(), cm.device), on_device(hydrogens.empty(), cm.device)
+        kek = kekule.launch(cm, kekule.KekuleTables(tables.atomic_numbers, tables.num_bond_types), select=select)
+        out = hydrogens.launch(cm, kek['kek_h'], kek['kek_order'], tables, hydrogens.DEFAULT_DEG_TOL if deg_tol is None else deg_tol,
+                               hydrogens.DEFAULT_CLASH_TOL if clash_tol is None else clash_tol, select=select)
+        return attach(kek, cm, select, n_atoms, kekule.LAYOUT), attach(out, cm, select, n_atoms, hydrogens.LAYOUT)
+
     def canon_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
                     atom_label=None):
         """``decode_batch``'s device part + the canonical labelling of every decoded molecule (``mdx_mol_canon``; see

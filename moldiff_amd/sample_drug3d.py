@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks] [--hydrogens]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -69,6 +69,13 @@ model, not RDKit's perception and not CIP, unverified against RDKit, blind to al
 (their summary with the isomeric uniqueness, the share of chiral molecules and of flat centres).  ``--stereo_flat_tol`` /
 ``--stereo_bond_tol`` (``sample.stereo_flat_tol`` / ``sample.stereo_bond_tol``; 0.1 each) are the two thresholds.  With ``--kekulize`` the
 strings of ``samples.smi`` are isomeric ('@', '/'); ``canon.npz`` and ``canon.json`` stay what they are.  Without the option nothing changes.
+``--hydrogens`` (config key ``sample.hydrogens``; the flag wins; implies ``--kekulize``), an addition beyond the reference: rank 0 places
+the hydrogens of the Kekulé assignment on the FINISHED molecules on the device batch by batch (``moldiff_amd/hydrogens.py``: this
+project's own idealised placement, not RDKit's AddHs, unverified against RDKit; rotor torsions by rule, lengths by convention) and writes
+``hydrogens.npz`` (counts, flags, positions, shortest contacts), ``hydrogens.json`` (their summary) and ``samples_allatom.sdf`` (the
+kekulizable finished molecules as all-atom mol blocks) beside ``samples_all.pt``.  ``--clash_tol`` (``sample.clash_tol``; 1.5 Angstrom: a
+convention, untuned) is the contact length below which a pair counts as a clash.  No acceptance rule is added; without the option
+nothing changes.
 ``--frameworks`` (config key ``sample.frameworks``; the flag wins), an addition beyond the reference: rank 0 cuts the FINISHED molecules
 into framework, ring systems, linkers and side chains on the device batch by batch (``moldiff_amd/framework.py``: this project's own
 definition, not RDKit's MurckoScaffold), keys the pieces with the canonical labelling and writes ``frameworks.npz`` (results and keys)
@@ -309,6 +316,27 @@ def add_kekulize_argument(ap):
     return ap
 
 
+def hydrogens_option(flag, clash_tol, sample_cfg):
+    """whether to write the all-atom files, and the clash threshold of ``moldiff_amd/hydrogens.py`` in Angstrom: the command line
+    (None = not given) wins over the config's ``sample.hydrogens`` and ``sample.clash_tol``; 1.5 where neither says -- a convention,
+    untuned"""
+    from . import hydrogens
+    tol = float(clash_tol if clash_tol is not None else sample_cfg.get('clash_tol') if sample_cfg.get('clash_tol') is not None
+                else hydrogens.DEFAULT_CLASH_TOL)
+    return bool(flag if flag is not None else sample_cfg.get('hydrogens')), hydrogens._check(hydrogens.DEFAULT_DEG_TOL, tol)[1]
+
+
+def add_hydrogens_argument(ap):
+    """``--hydrogens`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--hydrogens', action='store_true', default=None,
+                    help='place the hydrogens of the Kekulé assignment on the finished molecules on the device and write hydrogens.npz, '
+                         'hydrogens.json and samples_allatom.sdf; implies --kekulize (overrides sample.hydrogens)')
+    ap.add_argument('--clash_tol', type=float, default=None,
+                    help='a contact of a placed hydrogen below this many Angstrom is a clash (overrides sample.clash_tol; 1.5: a '
+                         'convention, untuned)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -410,7 +438,7 @@ def add_frameworks_argument(ap):
 
 
 def main(argv=None):
-    args = add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))))).parse_args(argv)
+    args = add_hydrogens_argument(add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -488,14 +516,26 @@ def main(argv=None):
         from . import groups
         groups_set = groups.PatternSet.from_yaml(groups_path, Z, nbt) if groups_path else groups.PatternSet.default(Z, nbt)
         features.append(Feature(lambda gen: groups.groups_mols(gen, device, groups_set), groups, 'groups', empty=lambda: groups.empty(groups_set)))
-    kek_write = kekulize_option(args.kekulize, config.sample)
+    hydrogens_on, clash_tol = hydrogens_option(args.hydrogens, args.clash_tol, config.sample)
+    kek_write = kekulize_option(args.kekulize, config.sample) or hydrogens_on   # --hydrogens implies --kekulize
     kek_active = kek_write or rule == 'kekule'
     if kek_active:
         from . import kekule
         kek_tables = kekule.KekuleTables(Z, nbt)
     if kek_write:
-        features.append(Feature(lambda gen: kekule.kekulize_mols(gen, device, kek_tables), kekule, 'kekule',
-                                after=lambda res: kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)))
+        kek_held = {}   # the joined Kekulé results, for the all-atom file of --hydrogens
+
+        def write_kekule_sdf(res):
+            kek_held['kekule'] = res
+            kekule.write_sdf(os.path.join(log_dir, 'samples_kekule.sdf'), pool['finished'], res)
+        features.append(Feature(lambda gen: kekule.kekulize_mols(gen, device, kek_tables), kekule, 'kekule', after=write_kekule_sdf))
+    if hydrogens_on:   # behind kekule: the joined Kekulé results are there when the all-atom file is written
+        from . import hydrogens
+        h_tables = hydrogens.HydrogenTables(Z, nbt)
+        features.append(Feature(lambda gen: hydrogens.addh_mols(gen, device, tables=h_tables, clash_tol=clash_tol), hydrogens, 'hydrogens',
+                                summary=lambda res: hydrogens.summary(res, clash_tol),
+                                after=lambda res: hydrogens.write_sdf(os.path.join(log_dir, 'samples_allatom.sdf'), pool['finished'],
+                                                                      kek_held['kekule'], res)))
     stereo_on, flat_tol, bond_tol = stereo_option(args.stereo, args.stereo_flat_tol, args.stereo_bond_tol, config.sample)
     conformers_on, conformer_tol = conformers_option(args.conformers, args.conformer_tol, config.sample)
     if canonical_option(args.canonical, config.sample) or stereo_on or conformers_on:
