@@ -27,8 +27,6 @@
 #include "mdx_canon_body.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 enum { R_STATUS, R_NODES, R_AUT };
@@ -44,11 +42,11 @@ struct BrArgs {
 
 struct BrShared {
   CnGraph g;                         // the walk's own state (mdx_canon_body.h)
-  double p[3][CN_ATOMS];             // the probe, centred
+  double p[3][MOL_ATOMS];            // the probe, centred
   double q[3][BR_STAGE_ATOMS];       // the staged targets, centred: pair k at k n
   double Gb[BR_STAGE_PAIRS];
-  unsigned cw[CN_BONDS];             // the canonical certificate, from the given rank
-  unsigned char crank[CN_ATOMS];
+  unsigned cw[MOL_BONDS];            // the canonical certificate, from the given rank
+  unsigned char crank[MOL_ATOMS];
 };
 
 struct Frame {
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(256) void mol_bestrms_kernel(const BrArgs A) {
     write_unmeasured(A, m, 0, p0, np);
     return;
   }
-  if (A.o.canon_status[m] != 0 || n > CN_ATOMS || nb > CN_BONDS) {  // uniform
+  if (A.o.canon_status[m] != 0 || n > MOL_ATOMS || nb > MOL_BONDS) {  // uniform
     write_unmeasured(A, m, 1, p0, np);
     return;
   }
@@ -231,9 +229,6 @@ extern "C" int mdx_mol_bestrms(int32_t B, const int32_t* atom_ptr, const int32_t
     return mdx_set_error(MDX_ERR_ARG, why);
   a.o = BestrmsOperands{atom_pos, atom_label, rank, canon_status, pair_ptr, pair_target, tgt_ptr, tgt_n, tgt_pos, msd, msd_mirror, msd_first, pair_stats, mol_stats};
   if (const char* why = bestrms_check(a.o, P_cap, T, tgt_atoms, max_nodes)) return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.P_cap = P_cap, a.tgt_atoms = tgt_atoms, a.T = T, a.max_nodes = max_nodes;
-  hipLaunchKernelGGL(mol_bestrms_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_bestrms_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_bestrms_kernel, "mol_bestrms_kernel", B, stream, a);
 }

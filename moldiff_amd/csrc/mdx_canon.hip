@@ -26,8 +26,6 @@
 #include "mdx_canon_body.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 enum { C_STATUS, C_NODES, C_LEAVES, C_AUT, C_BONDS };
@@ -41,8 +39,8 @@ struct CnArgs {
 
 struct CnShared {
   CnGraph g;                           // the walk's own state (mdx_canon_body.h)
-  unsigned best[CN_BONDS], cand[CN_BONDS];
-  unsigned char best_rank[CN_ATOMS], table[CN_ATOMS];
+  unsigned best[MOL_BONDS], cand[MOL_BONDS];
+  unsigned char best_rank[MOL_ATOMS], table[MOL_ATOMS];
 };
 
 // rank -1 and zeros for a molecule that is not measured; its per-atom and per-bond slots only when they are inside the arrays
@@ -66,12 +64,8 @@ __global__ __launch_bounds__(256) void mol_canon_kernel(const CnArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform
-    write_unmeasured(A, m, 0, v);
-    return;
-  }
-  if (n > CN_ATOMS || nb > CN_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
   const bool in = tid < n;
@@ -160,9 +154,6 @@ extern "C" int mdx_mol_canon(int32_t B, const int32_t* atom_ptr, const int32_t* 
   a.o = CanonOperands{atom_pos, atom_label, rank, orbit, canon_atom_type, canon_atom_label, canon_bond_index, canon_bond_type, mol_stats,
                       canon_pos, cert_hash};
   if (const char* why = canon_check(a.o, max_nodes)) return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.max_nodes = max_nodes;
-  hipLaunchKernelGGL(mol_canon_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_canon_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_canon_kernel, "mol_canon_kernel", B, stream, a);
 }

@@ -13,19 +13,19 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int CN_ATOMS = 256, CN_BONDS = 512, CN_NONE = 1 << 16;
+constexpr int CN_NONE = 1 << 16;
 constexpr unsigned CN_PAD = 0xffffffffu;  // sorts behind every word
 
 // what the walk keeps in LDS, 25,124 B: the bonds, the adjacency as CSR (neighbour and type in 16 bits), the colours as bytes, the
 // 64-bit keys of a refinement round, the depth-first stack of at most 64 colour snapshots with the target colour and cursor of a level
 struct CnGraph {
-  u64 key[CN_ATOMS];
-  unsigned bond[CN_BONDS];             // i | j << 8 | type << 16 | 1 << 24, or 0 for an ignored bond
-  int off[CN_ATOMS + 1], cur[CN_ATOMS], wave_total[4], red[4];
-  unsigned short adj[2 * CN_BONDS];    // neighbour | type << 8
+  u64 key[MOL_ATOMS];
+  unsigned bond[MOL_BONDS];             // the bond word of mdx_mol.h, payload = the low byte of the type
+  int off[MOL_ATOMS + 1], cur[MOL_ATOMS], wave_total[4], red[4];
+  unsigned short adj[2 * MOL_BONDS];   // neighbour | type << 8
   unsigned short cursor[CN_MAX_DEPTH];
-  unsigned char snap[CN_MAX_DEPTH][CN_ATOMS];
-  unsigned char col[CN_ATOMS];
+  unsigned char snap[CN_MAX_DEPTH][MOL_ATOMS];
+  unsigned char col[MOL_ATOMS];
   unsigned char tcol[CN_MAX_DEPTH];
 };
 
@@ -49,38 +49,20 @@ __device__ inline int block_min(int v, int* red) {
 }
 
 // The molecule into LDS (bonds, degrees, CSR) and the initial colouring, how many labels are smaller -> the number of valid bonds.
-// n <= 256 and nb <= 512.  Ends on a barrier.
+// The molecule is past mol_guard.  Ends on a barrier.
 __device__ inline int stage_molecule(CnGraph& s, const MolArrays& M, long long h0, int n, int nb, int label) {
   const int tid = threadIdx.x;
-  const int *bi = M.bond_i + h0, *bj = M.bond_j + h0, *bt = M.bond_type + h0;
-  s.cur[tid] = 0, s.col[tid] = 0;
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e];
-    if (!mol_bond_ok(i, j, n)) {
-      s.bond[e] = 0u;
-      continue;
-    }
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | ((unsigned)bt[e] & 0xffu) << 16 | 1u << 24;
-    atomicAdd(&s.cur[i], 1), atomicAdd(&s.cur[j], 1);
-  }
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, t = (bd >> 16) & 0xffu;
-    s.adj[atomicAdd(&s.cur[i], 1)] = (unsigned short)(j | t << 8);  // the order inside a row does not matter: h is a sum
-    s.adj[atomicAdd(&s.cur[j], 1)] = (unsigned short)(i | t << 8);
-  }
+  const int* bt = M.bond_type + h0;
+  s.col[tid] = 0;
+  mol_stage_bonds(M, h0, n, nb, s.bond, s.off, s.cur, s.wave_total, [&](int e, int, int) { return (unsigned)bt[e]; });
   s.key[tid] = (u64)(unsigned)label;
-  __syncthreads();
+  // the order inside a row does not matter: refine's h is a sum
+  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int, unsigned bd) { return (unsigned short)(other | mol_bond_payload(bd) << 8); });
   int less = 0;
   for (int u = 0; u < n; ++u) less += s.key[u] < (u64)(unsigned)label;
   if (tid < n) s.col[tid] = (unsigned char)less;
   __syncthreads();
-  return s.off[CN_ATOMS] / 2;
+  return s.off[MOL_ATOMS] / 2;
 }
 
 // Refinement of s.col (visible on entry) until no colour changes -> the size of this thread's cell.  Ends on a barrier.
@@ -110,8 +92,8 @@ __device__ inline int refine(CnGraph& s, int n) {
 // the bond word of a certificate from the colours (ranks) `col`, CN_PAD for an ignored bond
 __device__ inline unsigned bond_word(unsigned bd, const unsigned char* col) {
   if (!bd) return CN_PAD;
-  const unsigned ci = col[bd & 0xffu], cj = col[(bd >> 8) & 0xffu];
-  return min(ci, cj) << 20 | max(ci, cj) << 8 | ((bd >> 16) & 0xffu);
+  const unsigned ci = col[mol_bond_i(bd)], cj = col[mol_bond_j(bd)];
+  return min(ci, cj) << 20 | max(ci, cj) << 8 | mol_bond_payload(bd);
 }
 
 // w[0 .. P) ascending across the workgroup: bitonic, P a power of two in 2 .. 512, two words per thread.  What was written to w before

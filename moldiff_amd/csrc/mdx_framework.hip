@@ -24,12 +24,10 @@
 #include "mdx_framework_args.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
-constexpr int FW_ATOMS = 256, FW_BONDS = 512, FW_NONE = 0x7fff;
-constexpr unsigned FW_VALID = 1u << 16, FW_RING = 1u << 17;
+constexpr int FW_NONE = 0x7fff;
+constexpr unsigned FW_RING = 1u, FW_ADJ_RING = 1u << 17;  // a ring bond: in the payload of the bond word, in an adjacency entry
 enum { ROLE_SIDE, ROLE_LINKER, ROLE_RING, ROLE_EXO };
 enum { F_STATUS, F_ATOMS, F_BONDS, F_SYSTEMS, F_LINKER, F_SIDE, F_EXO, F_FUSION, F_LARGEST, F_MOST_RINGS };
 static_assert(F_MOST_RINGS + 1 == FW_STATS && FW_STATS == MDX_FW_STATS, "the columns of mol_stats");
@@ -41,17 +39,17 @@ struct FwArgs {
 };
 
 struct FwShared {
-  unsigned bond[FW_BONDS];             // i | j << 8 | FW_VALID | FW_RING, or 0 for an ignored bond
-  unsigned adj[2 * FW_BONDS];          // neighbour | bond << 8 | FW_RING
-  int off[FW_ATOMS + 1], cur[FW_ATOMS];  // adjacency offsets; degree, then fill cursor
-  int pre[FW_ATOMS + 1], cnt[FW_ATOMS];  // the scans of (c) and (d)
+  unsigned bond[MOL_BONDS];             // the bond word of mdx_mol.h, payload = FW_RING or 0
+  unsigned adj[2 * MOL_BONDS];          // neighbour | bond << 8 | FW_ADJ_RING
+  int off[MOL_ATOMS + 1], cur[MOL_ATOMS];  // adjacency offsets; degree, then fill cursor
+  int pre[MOL_ATOMS + 1], cnt[MOL_ATOMS];  // the scans of (c) and (d)
   int wave_total[4], hist[FW_MAX_BINS], top[2];
-  short label[FW_ATOMS];               // the smallest atom of the ring system, FW_NONE outside every system
-  short asys[FW_ATOMS], bsys[FW_BONDS];  // the system ordinal of an atom / a ring bond, -1 without one
-  unsigned short sys_a0[FW_ATOMS], sys_b0[FW_ATOMS], sys_na[FW_ATOMS], sys_nb[FW_ATOMS];  // per system, molecule-local
-  unsigned short fw_atom[FW_ATOMS], fw_atom_inv[FW_ATOMS], fw_bond_inv[FW_BONDS];         // new number of an atom; atom / bond of a new number
-  unsigned short sys_atom[FW_ATOMS], sys_atom_inv[FW_ATOMS], sys_bond_inv[FW_BONDS];      // place of an atom in the system arrays; the inverses
-  unsigned char alive[FW_ATOMS], role[FW_ATOMS], brole[FW_BONDS];
+  short label[MOL_ATOMS];              // the smallest atom of the ring system, FW_NONE outside every system
+  short asys[MOL_ATOMS], bsys[MOL_BONDS];  // the system ordinal of an atom / a ring bond, -1 without one
+  unsigned short sys_a0[MOL_ATOMS], sys_b0[MOL_ATOMS], sys_na[MOL_ATOMS], sys_nb[MOL_ATOMS];  // per system, molecule-local
+  unsigned short fw_atom[MOL_ATOMS], fw_atom_inv[MOL_ATOMS], fw_bond_inv[MOL_BONDS];      // new number of an atom; atom / bond of a new number
+  unsigned short sys_atom[MOL_ATOMS], sys_atom_inv[MOL_ATOMS], sys_bond_inv[MOL_BONDS];   // place of an atom in the system arrays; the inverses
+  unsigned char alive[MOL_ATOMS], role[MOL_ATOMS], brole[MOL_BONDS];
 };
 
 // status and zeros for a molecule that is not measured; its per-atom and per-bond slots only when they are inside the arrays
@@ -83,50 +81,30 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform
-    write_unmeasured(A, m, 0, v);
-    return;
-  }
-  if (n > FW_ATOMS || nb > FW_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
   if (o.ring_status[m] != 0) {  // uniform
     write_unmeasured(A, m, 2, v);
     return;
   }
-  const int *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
+  const int* bt = A.mol.bond_type + h0;
   const bool in = tid < n, generic = (A.mode & FW_MODE_GENERIC) != 0;
 
   // ---- (a) the molecule into LDS: bonds with their ring flag, degrees, adjacency lists
-  s.cur[tid] = 0;
   if (tid < FW_MAX_BINS) s.hist[tid] = 0;
   if (tid < 2) s.top[tid] = 0;
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e];
-    if (!mol_bond_ok(i, j, n)) {
-      s.bond[e] = 0u;
-      continue;
-    }
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | FW_VALID | (o.bond_ring_min[h0 + e] != 0 ? FW_RING : 0u);
-    atomicAdd(&s.cur[i], 1), atomicAdd(&s.cur[j], 1);
-  }
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, rest = (unsigned)e << 8 | (bd & FW_RING);
-    s.adj[atomicAdd(&s.cur[i], 1)] = j | rest;  // the order inside a row does not matter: rows are only counted and minimised over
-    s.adj[atomicAdd(&s.cur[j], 1)] = i | rest;
-  }
+  mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total,
+                  [&](int e, int, int) { return o.bond_ring_min[h0 + e] != 0 ? FW_RING : 0u; });
   s.alive[tid] = in;
-  __syncthreads();
+  // the order inside a row does not matter: rows are only counted and minimised over
+  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int e, unsigned bd) {
+    return other | (unsigned)e << 8 | (mol_bond_payload(bd) & FW_RING ? FW_ADJ_RING : 0u);
+  });
   const int a0 = in ? s.off[tid] : 0, a1 = in ? s.off[tid + 1] : 0;
   int ring_deg = 0;
-  for (int p = a0; p < a1; ++p) ring_deg += (s.adj[p] & FW_RING) != 0;
+  for (int p = a0; p < a1; ++p) ring_deg += (s.adj[p] & FW_ADJ_RING) != 0;
   const bool ring = ring_deg > 0;
 
   // ---- (b) the core: an atom with at most one live neighbour dies; at most n / 2 rounds
@@ -157,7 +135,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
     if (ring)
       for (int p = a0; p < a1; ++p) {
         const unsigned ent = s.adj[p];
-        if (ent & FW_RING) least = min(least, (int)s.label[ent & 0xffu]);
+        if (ent & FW_ADJ_RING) least = min(least, (int)s.label[ent & 0xffu]);
       }
     __syncthreads();  // every label of the round has been read
     if (least < mine) s.label[tid] = (short)least;
@@ -169,7 +147,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
   __syncthreads();
   block_exclusive_scan_256(s.pre, s.cnt, s.wave_total);
   __syncthreads();
-  const int n_fw = s.pre[FW_ATOMS];
+  const int n_fw = s.pre[MOL_ATOMS];
   s.fw_atom[tid] = (unsigned short)(in_fw ? s.pre[tid] : 0);
   if (in_fw) s.fw_atom_inv[s.pre[tid]] = (unsigned short)tid;
   __syncthreads();
@@ -179,7 +157,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
   __syncthreads();
   block_exclusive_scan_256(s.pre, s.cnt, s.wave_total);
   __syncthreads();
-  const int n_sys = s.pre[FW_ATOMS];
+  const int n_sys = s.pre[MOL_ATOMS];
   const int sys = ring ? s.pre[s.label[tid]] : -1;  // the roots before a root = its ordinal
   s.asys[tid] = (short)sys;
   __syncthreads();  // role, asys
@@ -188,9 +166,9 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
     const unsigned bd = s.bond[e];
     int br = 0, bs = -1;
     if (bd) {
-      const int ri = s.role[bd & 0xffu], rj = s.role[(bd >> 8) & 0xffu];
-      if (bd & FW_RING)
-        br = 2, bs = s.asys[bd & 0xffu];
+      const int ri = s.role[mol_bond_i(bd)], rj = s.role[mol_bond_j(bd)];
+      if (mol_bond_payload(bd) & FW_RING)
+        br = 2, bs = s.asys[mol_bond_i(bd)];
       else if (in_core(ri) && in_core(rj))
         br = 1;
       else if ((ri == ROLE_EXO && in_core(rj)) || (rj == ROLE_EXO && in_core(ri)))
@@ -205,7 +183,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
   __syncthreads();
   block_exclusive_scan_256(s.pre, s.cnt, s.wave_total);
   __syncthreads();
-  const int n_fw_bonds = s.pre[FW_ATOMS];
+  const int n_fw_bonds = s.pre[MOL_ATOMS];
   if (keep0) s.fw_bond_inv[s.pre[tid]] = (unsigned short)e0;
   if (keep1) s.fw_bond_inv[s.pre[tid] + (int)keep0] = (unsigned short)(e0 + 1);
   __syncthreads();
@@ -220,13 +198,13 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
   __syncthreads();
   block_exclusive_scan_256(s.pre, s.cnt, s.wave_total);
   __syncthreads();
-  const int first_atom = s.pre[tid], n_ring_atoms = s.pre[FW_ATOMS];
+  const int first_atom = s.pre[tid], n_ring_atoms = s.pre[MOL_ATOMS];
   __syncthreads();
   s.cnt[tid] = nbk;
   __syncthreads();
   block_exclusive_scan_256(s.pre, s.cnt, s.wave_total);
   __syncthreads();
-  const int first_bond = s.pre[tid], n_ring_bonds = s.pre[FW_ATOMS];
+  const int first_bond = s.pre[tid], n_ring_bonds = s.pre[MOL_ATOMS];
   s.sys_a0[tid] = (unsigned short)first_atom, s.sys_b0[tid] = (unsigned short)first_bond;
   s.sys_na[tid] = (unsigned short)na, s.sys_nb[tid] = (unsigned short)nbk;
   if (tid < n_sys) {
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
     if (e < n_fw_bonds) {
       const int src = s.fw_bond_inv[e];
       const unsigned bd = s.bond[src];
-      x = s.fw_atom[bd & 0xffu], y = s.fw_atom[(bd >> 8) & 0xffu], t = generic ? 1 : bt[src];
+      x = s.fw_atom[mol_bond_i(bd)], y = s.fw_atom[mol_bond_j(bd)], t = generic ? 1 : bt[src];
     }
     o.fw_bond_index[q] = x, o.fw_bond_index[A.mol.E_cap + q] = y, o.fw_bond_type[q] = t;
     x = y = t = 0;
@@ -277,7 +255,7 @@ __global__ __launch_bounds__(256) void mol_framework_kernel(const FwArgs A) {
       const int src = s.sys_bond_inv[e];
       const unsigned bd = s.bond[src];
       const int base = s.sys_a0[s.bsys[src]];
-      x = s.sys_atom[bd & 0xffu] - base, y = s.sys_atom[(bd >> 8) & 0xffu] - base, t = generic ? 1 : bt[src];
+      x = s.sys_atom[mol_bond_i(bd)] - base, y = s.sys_atom[mol_bond_j(bd)] - base, t = generic ? 1 : bt[src];
     }
     o.sys_bond_index[q] = x, o.sys_bond_index[A.mol.E_cap + q] = y, o.sys_bond_type[q] = t;
   }
@@ -309,9 +287,6 @@ extern "C" int mdx_mol_framework(int32_t B, const int32_t* atom_ptr, const int32
                           sys_n_atoms,  sys_n_bonds,   sys_atom_type, sys_atom_map, sys_bond_index, sys_bond_type, fw_pos,
                           sys_pos};
   if (const char* why = framework_check(a.o, mode, sys_bins)) return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.mode = mode, a.sys_bins = sys_bins;
-  hipLaunchKernelGGL(mol_framework_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_framework_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_framework_kernel, "mol_framework_kernel", B, stream, a);
 }

@@ -25,13 +25,11 @@
 #include "mdx_groups_args.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int GP_MOL_ATOMS = 256, GP_MOL_BONDS = 512, GP_WAVES = 4;
+constexpr int GP_WAVES = 4;
 constexpr int GP_CHUNK = 448;  // table words carried by one launch of the upload kernel, as kernel arguments
 
 struct GpArgs {
@@ -44,11 +42,11 @@ struct GpArgs {
 
 struct GpShared {
   unsigned table[GP_TABLE_WORDS];
-  unsigned bond[GP_MOL_BONDS];            // i | j << 8 | type << 16 | ring class << 21 | 1 << 24, or 0 for an ignored bond
-  unsigned attr[GP_MOL_ATOMS];            // class | min(deg, 7) << 5 | min(h, 4) << 8 | ring class << 11 | aromatic << 14 | class known << 15
-  int off[GP_MOL_ATOMS + 1], cur[GP_MOL_ATOMS], val2[GP_MOL_ATOMS];
+  unsigned bond[MOL_BONDS];               // the bond word of mdx_mol.h, payload = type | ring class << 5: the high byte of an adj entry
+  unsigned attr[MOL_ATOMS];               // class | min(deg, 7) << 5 | min(h, 4) << 8 | ring class << 11 | aromatic << 14 | class known << 15
+  int off[MOL_ATOMS + 1], cur[MOL_ATOMS], val2[MOL_ATOMS];
   int red[2][GP_WAVES][4], wave_total[GP_WAVES];
-  unsigned short adj[2 * GP_MOL_BONDS];   // neighbour | type << 8 | ring class << 13; type 0 = outside 1 .. num_bond_types
+  unsigned short adj[2 * MOL_BONDS];      // neighbour | type << 8 | ring class << 13; type 0 = outside 1 .. num_bond_types
 };
 
 struct GpChunkArgs {
@@ -101,45 +99,31 @@ __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform: status 0, everything 0
-    write_unmeasured(A, m, 0, v);
-    return;
-  }
-  if (n > GP_MOL_ATOMS || nb > GP_MOL_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
   if (A.ring_status && A.ring_status[m] != 0) {  // uniform
     write_unmeasured(A, m, 2, v);
     return;
   }
-  const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
+  const int *atype = A.mol.atom_type + n0, *bt = A.mol.bond_type + h0;
   const int nbt = A.num_bond_types;
 
   // ---- the molecule and the table into LDS
   for (int k = tid; k < GP_WORDS * (1 + A.P); k += 256) s.table[k] = A.table[k];
-  s.cur[tid] = 0, s.val2[tid] = 0, s.attr[tid] = 0u;
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e];
-    if (!mol_bond_ok(i, j, n)) {
-      s.bond[e] = 0u;
-      continue;
-    }
-    int t = bt[e];
-    t = t >= 1 && t <= nbt ? t : 0;
-    const unsigned rc = A.bond_ring_min ? ring_class(A.bond_ring_min[h0 + e]) : 0u;
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | (unsigned)t << 16 | rc << 21 | 1u << 24;
-    atomicAdd(&s.cur[i], 1);
-    atomicAdd(&s.cur[j], 1);
-    const int w = t == 0 ? 0 : t == nbt ? 3 : 2 * t;  // mdx_mol_check's valence2
-    atomicAdd(&s.val2[i], w);
-    atomicAdd(&s.val2[j], w);
-    if (t == nbt) atomicOr(&s.attr[i], 1u << 14), atomicOr(&s.attr[j], 1u << 14);
-  }
-  __syncthreads();
+  s.val2[tid] = 0, s.attr[tid] = 0u;
   {
-    const int deg = block_exclusive_scan_256(s.off, s.cur, s.wave_total);  // an atom past n has degree 0: off[n] is the total whatever n is
+    const int deg = mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total, [&](int e, int i, int j) {
+      int t = bt[e];
+      t = t >= 1 && t <= nbt ? t : 0;
+      const unsigned rc = A.bond_ring_min ? ring_class(A.bond_ring_min[h0 + e]) : 0u;
+      const int w = t == 0 ? 0 : t == nbt ? 3 : 2 * t;  // mdx_mol_check's valence2
+      atomicAdd(&s.val2[i], w);
+      atomicAdd(&s.val2[j], w);
+      if (t == nbt) atomicOr(&s.attr[i], 1u << 14), atomicOr(&s.attr[j], 1u << 14);
+      return (unsigned)t | rc << 5;
+    });
     if (tid < n) {
       const int cls = atype[tid];
       const bool known = (unsigned)cls < (unsigned)A.num_element;
@@ -149,15 +133,7 @@ __global__ __launch_bounds__(256) void mol_groups_kernel(const GpArgs A) {
                     rc << 11 | (known ? 1u << 15 : 0u);
     }
   }
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, rest = (bd >> 16) & 0xffu;  // type | ring class << 5
-    s.adj[atomicAdd(&s.cur[i], 1)] = (unsigned short)(j | rest << 8);
-    s.adj[atomicAdd(&s.cur[j], 1)] = (unsigned short)(i | rest << 8);
-  }
-  __syncthreads();
+  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int, unsigned bd) { return (unsigned short)(other | mol_bond_payload(bd) << 8); });
 
   // ---- the patterns: thread a searches the embeddings that send pattern atom 0 to atom a
   unsigned hit = 0u;
@@ -287,7 +263,5 @@ extern "C" int mdx_mol_groups(int32_t B, const int32_t* atom_ptr, const int32_t*
   a.table = (const unsigned*)ws;
   a.num_element = num_element, a.num_bond_types = num_bond_types, a.P = P, a.max_steps = max_steps;
   a.n_embed = n_embed, a.n_anchor = n_anchor, a.steps = steps, a.pat_status = pat_status, a.status = status, a.atom_hit = atom_hit;
-  hipLaunchKernelGGL(mol_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_groups_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_groups_kernel, "mol_groups_kernel", B, stream, a);
 }

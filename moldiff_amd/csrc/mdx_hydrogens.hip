@@ -7,7 +7,7 @@
 // restatement's.
 //
 // One workgroup of 256 threads (4 waves) per molecule over the compact arrays of mdx_mol.h; at most 256 atoms and 512 bonds.  Staged
-// once in LDS: the positions widened to float64, the bonds, and the adjacency as CSR (block_exclusive_scan_256), every row then sorted
+// once in LDS: the positions widened to float64, the bonds, and the adjacency as CSR (the staging of mdx_mol.h), every row then sorted
 // by its owner so that "ascending neighbour index" is what a walk of the row gives.  Thread a decides atom a's geometry, places its
 // hydrogens into the LDS table of 1024 x 3 doubles and writes its own slots.  The placed slots are then listed (a second scan) and the
 // pairs (placed H) x (heavy atom or later placed H) are dealt round-robin over the threads; an H is only ever placed on an atom with at
@@ -22,11 +22,9 @@
 #include "mdx_hydrogens_args.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
-constexpr int HY_ATOMS = 256, HY_BONDS = 512, HY_SLOTS = HY_ATOMS * HY_MAX_H;
+constexpr int HY_SLOTS = MOL_ATOMS * HY_MAX_H;
 enum { GEOM_TETRAHEDRAL = 0, GEOM_TRIGONAL = 1, GEOM_LINEAR = 2 };
 enum { FLAG_NO_ROOM = 4, FLAG_DEGENERATE = 8, FLAG_WORLD_FRAME = 16, FLAG_CLAMPED = 32 };
 // the columns of mol_stats: MDX_HYDROGENS_* of include/moldiff_hip.h
@@ -51,18 +49,18 @@ struct D3 {
 };
 
 struct HyShared {
-  D3 pos[HY_ATOMS];               // the heavy atoms, float64
+  D3 pos[MOL_ATOMS];              // the heavy atoms, float64
   D3 hpos[HY_SLOTS];              // slot 4 a + k: atom a's k-th hydrogen
-  unsigned bond[HY_BONDS];        // i | j << 8 | order (1 .. 3) << 16 | aromatic << 18 | 1 << 24, or 0 for an ignored bond
-  unsigned nb3[HY_ATOMS];         // the first three neighbours in ascending index, a byte each | min(degree, 255) << 24
-  int off[HY_ATOMS + 1], cur[HY_ATOMS], wave_total[4];
+  unsigned bond[MOL_BONDS];       // the bond word of mdx_mol.h, payload = order (1 .. 3) | aromatic << 2: the low bits of an adj entry
+  unsigned nb3[MOL_ATOMS];        // the first three neighbours in ascending index, a byte each | min(degree, 255) << 24
+  int off[MOL_ATOMS + 1], cur[MOL_ATOMS], wave_total[4];
   int red[4][HY_STATS];
   double wmin[4];
   double len[HY_MAX_ELEMENTS];        // the X-H length per class
-  unsigned short adj[2 * HY_BONDS];   // neighbour << 3 | aromatic << 2 | order: a row sorted by the word is sorted by neighbour
+  unsigned short adj[2 * MOL_BONDS];  // neighbour << 3 | aromatic << 2 | order: a row sorted by the word is sorted by neighbour
   unsigned short hlist[HY_SLOTS];     // the placed slots in (atom, k) order
-  unsigned char g1[HY_ATOMS];         // the geometry by the first rule
-  unsigned char fin[HY_ATOMS];        // every coordinate finite
+  unsigned char g1[MOL_ATOMS];        // the geometry by the first rule
+  unsigned char fin[MOL_ATOMS];       // every coordinate finite
 };
 
 __device__ inline D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -195,16 +193,12 @@ __global__ __launch_bounds__(256) void mol_hydrogens_kernel(const HyArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform: status 0, everything 0
-    write_unmeasured(A, m, 0, v);
-    return;
-  }
-  if (n > HY_ATOMS || nb > HY_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
   const bool in = tid < n;
-  const int *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0, *bo = A.o.order + h0;
+  const int *bt = A.mol.bond_type + h0, *bo = A.o.order + h0;
   const int nbt = A.num_bond_types;
 
   // ---- the molecule into LDS: positions, bonds, the adjacency as CSR with sorted rows
@@ -217,33 +211,14 @@ __global__ __launch_bounds__(256) void mol_hydrogens_kernel(const HyArgs A) {
       fin = isfinite(x) && isfinite(y) && isfinite(z);
       p = {(double)x, (double)y, (double)z};
     }
-    s.pos[tid] = p, s.fin[tid] = fin ? 1 : 0, s.cur[tid] = 0;
+    s.pos[tid] = p, s.fin[tid] = fin ? 1 : 0;
     if (tid < HY_MAX_ELEMENTS) s.len[tid] = A.tab.length[tid];
 #pragma unroll
     for (int k = 0; k < HY_MAX_H; ++k) s.hpos[HY_MAX_H * tid + k] = {0.0, 0.0, 0.0};
   }
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e];
-    if (!mol_bond_ok(i, j, n)) {
-      s.bond[e] = 0u;
-      continue;
-    }
-    const int o = min(max(bo[e], 1), 3);
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | (unsigned)o << 16 | (bt[e] == nbt ? 1u : 0u) << 18 | 1u << 24;
-    atomicAdd(&s.cur[i], 1), atomicAdd(&s.cur[j], 1);
-  }
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, t = (bd >> 16) & 0x7u;
-    s.adj[atomicAdd(&s.cur[i], 1)] = (unsigned short)(j << 3 | t);  // off[256] <= 2 nb <= 1024
-    s.adj[atomicAdd(&s.cur[j], 1)] = (unsigned short)(i << 3 | t);
-  }
-  __syncthreads();
+  mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total,
+                  [&](int e, int, int) { return (unsigned)min(max(bo[e], 1), 3) | (bt[e] == nbt ? 4u : 0u); });
+  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int, unsigned bd) { return (unsigned short)(other << 3 | mol_bond_payload(bd)); });
   int d = 0;
   {
     const int r0 = in ? s.off[tid] : 0, r1 = in ? s.off[tid + 1] : 0;
@@ -309,7 +284,7 @@ __global__ __launch_bounds__(256) void mol_hydrogens_kernel(const HyArgs A) {
   __syncthreads();
 
   // ---- contacts: (placed H) x (heavy atom, or a later placed H), without the 1-2 and 1-3 pairs
-  const int nH = s.off[HY_ATOMS], M = n + nH, total = nH * M;  // at most 1024 * 1280
+  const int nH = s.off[MOL_ATOMS], M = n + nH, total = nH * M;  // at most 1024 * 1280
   double mn = INFINITY;
   int clash = 0;
   for (int it = tid; it < total; it += 256) {
@@ -363,9 +338,6 @@ extern "C" int mdx_mol_hydrogens(int32_t B, const int32_t* atom_ptr, const int32
   const char* why = "";
   if (hydrogens_prepare(&a.tab, xh_length, planar_mask, num_element, num_bond_types, deg_tol, clash_tol, &why) != HY_PREP_OK)
     return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.num_element = num_element, a.num_bond_types = num_bond_types;
-  hipLaunchKernelGGL(mol_hydrogens_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_hydrogens_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_hydrogens_kernel, "mol_hydrogens_kernel", B, stream, a);
 }

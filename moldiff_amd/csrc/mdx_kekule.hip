@@ -32,13 +32,11 @@
 #include "mdx_kekule_args.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int KK_ATOMS = 256, KK_BONDS = 512, KK_COMPONENT = 64;
+constexpr int KK_COMPONENT = 64;
 constexpr unsigned KK_NONE = 0xffu;                       // no neighbour in this slot
 constexpr unsigned short KK_FREE = 0xffff;                // partner of an unmatched atom
 enum { ROLE_NONE = 0, ROLE_NOT = 1, ROLE_MUST = 2, ROLE_MAY = 3 };
@@ -55,15 +53,15 @@ struct KkArgs {
 };
 
 struct KkShared {
-  unsigned bond[KK_BONDS];         // i | j << 8 | type << 16 | 1 << 24 (type 0: outside 1 .. num_bond_types), or 0 for an ignored bond
-  unsigned nbrw[KK_ATOMS];         // by place in `list`: the ranks of the candidate neighbours, ascending, bytes 0 .. 2 (0xff: none) | role << 24
-  unsigned cand[KK_ATOMS];         // by atom: the candidate neighbours (atoms) as they arrive, bytes 0 .. 2
-  int sigma[KK_ATOMS], adeg[KK_ATOMS], label[KK_ATOMS], ncand[KK_ATOMS], place[KK_ATOMS], csteps[KK_ATOMS];
+  unsigned bond[MOL_BONDS];        // the bond word of mdx_mol.h, payload = type (0: outside 1 .. num_bond_types)
+  unsigned nbrw[MOL_ATOMS];        // by place in `list`: the ranks of the candidate neighbours, ascending, bytes 0 .. 2 (0xff: none) | role << 24
+  unsigned cand[MOL_ATOMS];        // by atom: the candidate neighbours (atoms) as they arrive, bytes 0 .. 2
+  int sigma[MOL_ATOMS], adeg[MOL_ATOMS], label[MOL_ATOMS], ncand[MOL_ATOMS], place[MOL_ATOMS], csteps[MOL_ATOMS];
   int red[KK_STATS], changed, too_big;
-  unsigned short partner[KK_ATOMS];
+  unsigned short partner[MOL_ATOMS];
   unsigned short vtab[KK_MAX_ELEMENTS];
-  unsigned char list[KK_ATOMS];    // the aromatic atoms sorted by (component, atom)
-  unsigned char role[KK_ATOMS], rank[KK_ATOMS], cstat[KK_ATOMS];
+  unsigned char list[MOL_ATOMS];   // the aromatic atoms sorted by (component, atom)
+  unsigned char role[MOL_ATOMS], rank[MOL_ATOMS], cstat[MOL_ATOMS];
 };
 
 // status and zeros for a molecule that is not measured; its per-atom and per-bond slots only when they are inside the arrays
@@ -89,12 +87,8 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform: status 0, everything 0
-    write_unmeasured(A, m, 0, v);
-    return;
-  }
-  if (n > KK_ATOMS || nb > KK_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
   const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
     }
     int t = bt[e];
     t = t >= 1 && t <= nbt ? t : 0;
-    s.bond[e] = (unsigned)i | (unsigned)j << 8 | (unsigned)t << 16 | 1u << 24;
+    s.bond[e] = mol_bond_word(i, j, (unsigned)t);
     if (t == 0) continue;
     const int w = t == nbt ? 1 : t;
     atomicAdd(&s.sigma[i], w);
@@ -142,14 +136,14 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
 
   // ---- the components of the aromatic bonds, each labelled by its smallest atom.  A round lowers every label that is not yet the
   // smallest of its component or ends the loop, and labels only fall: at most 255 rounds.
-  for (int round = 0; round < KK_ATOMS; ++round) {
+  for (int round = 0; round < MOL_ATOMS; ++round) {
     __syncthreads();  // the previous round's `changed` has been read (and, first, the roles are visible)
     if (tid == 0) s.changed = 0;
     __syncthreads();
     for (int e = tid; e < nb; e += 256) {
       const unsigned bd = s.bond[e];
-      if ((int)((bd >> 16) & 0x1fu) != nbt || !bd) continue;
-      const int i = bd & 0xffu, j = (bd >> 8) & 0xffu;
+      if ((int)mol_bond_payload(bd) != nbt || !bd) continue;
+      const int i = mol_bond_i(bd), j = mol_bond_j(bd);
       const int li = ((volatile int*)s.label)[i], lj = ((volatile int*)s.label)[j];
       if (li == lj) continue;
       atomicMin(&s.label[li < lj ? j : i], min(li, lj));
@@ -167,8 +161,8 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
   // ---- the candidate neighbours of every atom that may be matched: the aromatic neighbours of higher index that are not NOT
   for (int e = tid; e < nb; e += 256) {
     const unsigned bd = s.bond[e];
-    if ((int)((bd >> 16) & 0x1fu) != nbt || !bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu, lo = min(i, j), hi = max(i, j);
+    if ((int)mol_bond_payload(bd) != nbt || !bd) continue;
+    const unsigned i = mol_bond_i(bd), j = mol_bond_j(bd), lo = min(i, j), hi = max(i, j);
     if (s.role[lo] == ROLE_NOT || s.role[hi] == ROLE_NOT) continue;
     const int slot = atomicAdd(&s.ncand[lo], 1);
     if (slot < 3) atomicOr(&s.cand[lo], hi << (8 * slot));  // adeg <= 3 here: a fourth arrives only with the precondition violated
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
         const unsigned c = get2(clo, chi, r);
         if (!c) continue;
         const unsigned nr = (s.nbrw[base + r] >> (8 * (c - 1u))) & 0x3fu;
-        const unsigned x = s.list[base + r], y = s.list[min(base + (int)nr, KK_ATOMS - 1)];
+        const unsigned x = s.list[base + r], y = s.list[min(base + (int)nr, MOL_ATOMS - 1)];
         s.partner[x] = (unsigned short)y, s.partner[y] = (unsigned short)x;
       }
     }
@@ -303,10 +297,10 @@ __global__ __launch_bounds__(256) void mol_kekulize_kernel(const KkArgs A) {
   }
   for (int e = tid; e < nb; e += 256) {
     const unsigned bd = s.bond[e];
-    const int t = (bd >> 16) & 0x1fu;
+    const int t = mol_bond_payload(bd);
     int order = 0;
     if (bd && t > 0) {
-      const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu;
+      const unsigned i = mol_bond_i(bd), j = mol_bond_j(bd);
       if (t < nbt) {
         order = t;
       } else {
@@ -341,10 +335,7 @@ extern "C" int mdx_mol_kekulize(int32_t B, const int32_t* atom_ptr, const int32_
   const char* why = "";
   if (kekule_prepare(&a.tab, normal_valence, charged_valence, flexible, num_element, num_bond_types, max_steps, &why) != KK_PREP_OK)
     return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.num_element = num_element, a.num_bond_types = num_bond_types, a.max_steps = max_steps;
   a.kek_order = kek_order, a.val = val, a.charge = charge, a.kek_h = kek_h, a.atom_flag = atom_flag, a.stats = mol_stats;
-  hipLaunchKernelGGL(mol_kekulize_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_kekulize_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_kekulize_kernel, "mol_kekulize_kernel", B, stream, a);
 }

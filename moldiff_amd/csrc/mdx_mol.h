@@ -1,8 +1,8 @@
-// The compact molecule arrays every evaluation kernel walks (mdx_mol_local3d, mdx_mol_fingerprint, mdx_mol_rings, mdx_mol_groups, mdx_mol_kekulize), defined
-// once: molecule m has its atoms at atom_ptr[m] .. + n_atoms[m] and its bonds at bond_ptr[m] .. + n_bonds[m], one direction per bond,
+// The compact molecule arrays every evaluation kernel walks (the mdx_mol_* entry points of include/moldiff_hip.h), defined once:
+// molecule m has its atoms at atom_ptr[m] .. + n_atoms[m] and its bonds at bond_ptr[m] .. + n_bonds[m], one direction per bond,
 // molecule-local atom indices -- what mdx_decode_output leaves and what moldiff_amd/molpack.py packs from a list of molecule dicts.
 // The first part is plain C++ (mdx_local3d_args.h includes it and tools/local3d_host_check.cpp builds that without HIP); the second
-// holds the device helpers the kernels share.
+// holds the device helpers the kernels share, the molecule staged in LDS among them, and the launch tail of the entry points.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -29,6 +29,10 @@ inline const char* mol_arrays_fill(MolArrays* a, int32_t B, const int32_t* atom_
 }
 
 #ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include "../../include/moldiff_hip.h"
 
 struct MolView {
   long long n0, h0;  // first atom, first bond
@@ -102,6 +106,87 @@ __device__ inline int block_exclusive_scan_256(int* off, int* cur, int* wave_tot
   cur[tid] = before + inc - deg;
   if (tid == 255) off[256] = before + inc;
   return deg;
+}
+
+// ---- The staged molecule of the kernels that run one workgroup of 256 threads per molecule with thread a = atom a (rings, groups,
+// kekule, canon / stereo / bestrms, framework, hydrogens): its limits, the guard, the bond word, and the adjacency as CSR in LDS.  Every
+// kernel keeps its own __shared__ struct and hands the arrays in as pointers.
+constexpr int MOL_ATOMS = 256, MOL_BONDS = 512;  // an atom index is a byte of the bond word, a bond index 9 bits of an adjacency word
+constexpr int MOL_MEASURE = -1;
+
+// -> MOL_MEASURE, or the status the kernel reports with every output of the molecule 0: 0 when it is outside the arrays or masked, 1
+// when it is above the limits.  Uniform over the workgroup.  Past it n <= MOL_ATOMS, nb <= MOL_BONDS and the extents may be read.
+__device__ inline int mol_guard(const MolView& v) {
+  if (v.outside || v.masked) return 0;
+  return v.n > MOL_ATOMS || v.nb > MOL_BONDS ? 1 : MOL_MEASURE;
+}
+
+// The bond word: i | j << 8 | payload << 16 | MOL_BOND_VALID, and 0 for an ignored bond (mol_bond_ok), so that `!word` tests for one
+// whatever the payload is.  The 8 payload bits are the kernel's own.
+constexpr unsigned MOL_BOND_VALID = 1u << 24;
+__device__ inline unsigned mol_bond_word(int i, int j, unsigned payload) {
+  return (unsigned)i | (unsigned)j << 8 | (payload & 0xffu) << 16 | MOL_BOND_VALID;
+}
+__device__ inline unsigned mol_bond_i(unsigned word) { return word & 0xffu; }
+__device__ inline unsigned mol_bond_j(unsigned word) { return (word >> 8) & 0xffu; }
+__device__ inline unsigned mol_bond_payload(unsigned word) { return (word >> 16) & 0xffu; }
+
+// Bonds, degrees and row offsets of a molecule past mol_guard: bond[e] = the word of bond e for e < nb, off[a] .. off[a + 1] = the row
+// of atom a in the adjacency, cur[a] = off[a] (the fill cursor of mol_stage_rows).  -> this thread's degree, 0 for tid >= n.
+// payload(e, i, j) -> the payload bits; it runs once per VALID bond, in the thread of the bond.  It may read the caller's global arrays
+// and update LDS words of the caller's, zeroed before the call, with integer atomics or with stores of one value: the first barrier
+// here makes the zeros visible, the last one what the bonds left.
+// A degree is counted exactly for the bonds with a non-zero word, which are the bonds mol_stage_rows places: a count without its entry
+// would leave a slot of the row unwritten, an entry without its count would land in the next row.  An atom past n has degree 0, so
+// off[MOL_ATOMS] is the total, 2 x the valid bonds, whatever n is.  Ends on a barrier.
+template <class Payload>
+__device__ inline int mol_stage_bonds(const MolArrays& M, long long h0, int n, int nb, unsigned* bond, int* off, int* cur, int* wave_total,
+                                      Payload&& payload) {
+  const int tid = threadIdx.x;
+  const int *bi = M.bond_i + h0, *bj = M.bond_j + h0;
+  cur[tid] = 0;
+  __syncthreads();  // no degree is added before every cursor is 0
+  for (int e = tid; e < nb; e += 256) {
+    const int i = bi[e], j = bj[e];
+    if (!mol_bond_ok(i, j, n)) {
+      bond[e] = 0u;
+      continue;
+    }
+    bond[e] = mol_bond_word(i, j, payload(e, i, j));
+    atomicAdd(&cur[i], 1), atomicAdd(&cur[j], 1);
+  }
+  __syncthreads();  // the degrees are complete
+  const int deg = block_exclusive_scan_256(off, cur, wave_total);
+  __syncthreads();  // the offsets, the cursors and the bond words are visible
+  return deg;
+}
+
+// The rows: for every valid bond e = (i, j), entry(j, e, word) into the row of i and entry(i, e, word) into the row of j.  The order
+// inside a row is whatever the atomics give: a consumer sorts the row or does not depend on it.  Every slot lies below
+// off[MOL_ATOMS] <= 2 nb <= 2 MOL_BONDS, the size of adj.  Ends on a barrier.
+template <class T, class Entry>
+__device__ inline void mol_stage_rows(int nb, const unsigned* bond, int* cur, T* adj, Entry&& entry) {
+  for (int e = threadIdx.x; e < nb; e += 256) {
+    const unsigned bd = bond[e];
+    if (!bd) continue;
+    const unsigned i = mol_bond_i(bd), j = mol_bond_j(bd);
+    adj[atomicAdd(&cur[i], 1)] = entry(j, e, bd);
+    adj[atomicAdd(&cur[j], 1)] = entry(i, e, bd);
+  }
+  __syncthreads();
+}
+
+// The tail of the mdx_mol_* entry points, after every argument check: one workgroup of 256 threads per molecule on the caller's stream.
+// B == 0 is MDX_OK without a call into the runtime; a launch that fails is MDX_ERR_HIP with the kernel's name.
+int mdx_set_error(int code, const char* msg);  // mdx_api.hip
+template <class Args>
+inline int mol_launch(void (*kernel)(Args), const char* name, int32_t B, void* stream, const Args& a) {
+  if (B == 0) return MDX_OK;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+  if (hipGetLastError() == hipSuccess) return MDX_OK;
+  char msg[96];
+  snprintf(msg, sizeof msg, "%s: launch failed", name);
+  return mdx_set_error(MDX_ERR_HIP, msg);
 }
 
 #endif  // __HIPCC__

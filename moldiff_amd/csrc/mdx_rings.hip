@@ -30,13 +30,11 @@
 #include "../../include/moldiff_hip.h"
 #include "mdx_mol.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int RG_ATOMS = 256, RG_BONDS = 512, RG_RINGS = 64, RG_WAVES = 4;
+constexpr int RG_RINGS = 64, RG_WAVES = 4;
 constexpr int RG_MAX_ELEMENTS = 255, RG_MAX_BOND_TYPES = 254;
 constexpr unsigned short RG_FAR = 0xffff;  // depth of an atom not reached; parent bond of a root
 constexpr int RG_INF = 1 << 30;
@@ -51,18 +49,18 @@ struct RgArgs {
 enum { S_MU, S_NRINGS, S_RANK, S_NEXT, S_LMIN, S_RING_ATOMS, S_RING_BONDS, S_ROTATABLE, S_COUNT };
 
 struct RgShared {
-  u64 word[RG_WAVES][RG_ATOMS];             // per wave: XOR of the numbered bonds on the tree path to the atom
+  u64 word[RG_WAVES][MOL_ATOMS];            // per wave: XOR of the numbered bonds on the tree path to the atom
   u64 basis[RG_RINGS];                      // by leading bit; 0 = none
-  unsigned adj[2 * RG_BONDS];               // neighbour << 16 | bond
-  unsigned bond[RG_BONDS];                  // i | j << 8 | 1 << 16, or 0 for an ignored bond
-  int off[RG_ATOMS + 1], cur[RG_ATOMS];     // adjacency offsets; degree, then fill cursor
+  unsigned adj[2 * MOL_BONDS];              // neighbour << 16 | bond
+  unsigned bond[MOL_BONDS];                 // the bond word of mdx_mol.h, no payload
+  int off[MOL_ATOMS + 1], cur[MOL_ATOMS];   // adjacency offsets; degree, then fill cursor
   int elem[RG_MAX_ELEMENTS + 1], btc[RG_MAX_BOND_TYPES + 2], hist[RG_RINGS];
   int scal[S_COUNT], wave_total[RG_WAVES];
-  unsigned short depth[RG_WAVES][RG_ATOMS];  // per wave
-  unsigned short brm[RG_BONDS];              // bond_ring_min
-  unsigned short pbond[RG_ATOMS];            // forest: the bond to the parent
-  unsigned char bnum[RG_BONDS];              // number of a bond outside the forest, 255 for every other bond
-  unsigned char triple[RG_ATOMS];            // the atom carries a bond of type 3
+  unsigned short depth[RG_WAVES][MOL_ATOMS];  // per wave
+  unsigned short brm[MOL_BONDS];             // bond_ring_min
+  unsigned short pbond[MOL_ATOMS];           // forest: the bond to the parent
+  unsigned char bnum[MOL_BONDS];             // number of a bond outside the forest, 255 for every other bond
+  unsigned char triple[MOL_ATOMS];           // the atom carries a bond of type 3
 };
 
 // status and zeros for a molecule that is not measured; its slots of the per-bond / per-atom arrays only when they are inside the arrays
@@ -86,9 +84,9 @@ __device__ inline void write_unmeasured(const RgArgs& A, int m, int status, cons
 template <bool WORDS, bool PARENT>
 __device__ inline void bfs_levels(RgShared& s, int n, int lane, volatile unsigned short* depth, volatile u64* word, int skip, int target) {
   volatile unsigned short* pbond = s.pbond;
-  for (int level = 1; level < RG_ATOMS; ++level) {  // a level reaches a new atom or is the last: never more than n - 1
+  for (int level = 1; level < MOL_ATOMS; ++level) {  // a level reaches a new atom or is the last: never more than n - 1
     bool found = false;
-    for (int k = 0; k < RG_ATOMS / 64; ++k) {
+    for (int k = 0; k < MOL_ATOMS / 64; ++k) {
       const int a = lane + 64 * k;
       if (a >= n || depth[a] != RG_FAR) continue;
       unsigned best = ~0u;
@@ -114,7 +112,7 @@ __device__ inline void bfs_levels(RgShared& s, int n, int lane, volatile unsigne
 }
 
 __device__ inline void bfs_init(int n, int lane, volatile unsigned short* depth, volatile u64* word, int root) {
-  for (int k = 0; k < RG_ATOMS / 64; ++k) {
+  for (int k = 0; k < MOL_ATOMS / 64; ++k) {
     const int a = lane + 64 * k;
     if (a >= n) continue;
     depth[a] = a == root ? 0 : RG_FAR;
@@ -134,7 +132,7 @@ __device__ inline void insert_candidates(RgShared& s, int nb, int lane, const vo
     u64 vec = 0ull;
     const unsigned bd = e < nb ? s.bond[e] : 0u;
     if (bd) {
-      const int x = bd & 0xffu, y = (bd >> 8) & 0xffu;
+      const int x = mol_bond_i(bd), y = mol_bond_j(bd);
       const unsigned dx = depth[x], dy = depth[y];
       if (dx != RG_FAR && dy != RG_FAR) {
         const unsigned bn = s.bnum[e];
@@ -174,51 +172,32 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform: status 0, everything 0
-    write_unmeasured(A, m, 0, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
-  if (n > RG_ATOMS || nb > RG_BONDS) {  // uniform
-    write_unmeasured(A, m, 1, v);
-    return;
-  }
-  const int *atype = A.mol.atom_type + n0, *bi = A.mol.bond_i + h0, *bj = A.mol.bond_j + h0, *bt = A.mol.bond_type + h0;
+  const int *atype = A.mol.atom_type + n0, *bt = A.mol.bond_type + h0;
 
   // ---- (a) adjacency lists and the two histograms
-  s.cur[tid] = 0, s.triple[tid] = 0, s.elem[tid] = 0, s.btc[tid] = 0;
+  s.triple[tid] = 0, s.elem[tid] = 0, s.btc[tid] = 0;
   if (tid < RG_RINGS) s.hist[tid] = 0, s.basis[tid] = 0ull;
   if (tid < S_COUNT) s.scal[tid] = tid == S_LMIN || tid == S_NEXT ? RG_INF : 0;
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const int i = bi[e], j = bj[e], t = bt[e];
-    const bool valid = mol_bond_ok(i, j, n);
-    s.bond[e] = valid ? (unsigned)i | (unsigned)j << 8 | 1u << 16 : 0u;
-    if (!valid) continue;
-    atomicAdd(&s.cur[i], 1);
-    atomicAdd(&s.cur[j], 1);
+  mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total, [&](int e, int i, int j) {
+    const int t = bt[e];
     if (t == 3) s.triple[i] = 1, s.triple[j] = 1;
     if (t >= 1 && t <= A.num_bond_types) atomicAdd(&s.btc[t - 1], 1);
-  }
+    return 0u;
+  });
   for (int a = tid; a < n; a += 256) {
     const int c = atype[a];
     if ((unsigned)c < (unsigned)A.num_element) atomicAdd(&s.elem[c], 1);
   }
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);  // the degrees: an atom past n has 0, so off[n] is the total whatever n is
-  __syncthreads();
-  for (int e = tid; e < nb; e += 256) {
-    const unsigned bd = s.bond[e];
-    if (!bd) continue;
-    const unsigned i = bd & 0xffu, j = (bd >> 8) & 0xffu;
-    s.adj[atomicAdd(&s.cur[i], 1)] = j << 16 | (unsigned)e;
-    s.adj[atomicAdd(&s.cur[j], 1)] = i << 16 | (unsigned)e;
-  }
-  __syncthreads();
+  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int e, unsigned) { return other << 16 | (unsigned)e; });
 
   // ---- (b) wave 0: the forest, the fragments, the numbering of the bonds outside the forest
   if (wave == 0) {
     volatile unsigned short *depth = s.depth[0], *pbond = s.pbond;
-    for (int k = 0; k < RG_ATOMS / 64; ++k) {
+    for (int k = 0; k < MOL_ATOMS / 64; ++k) {
       const int a = lane + 64 * k;
       if (a < n) depth[a] = RG_FAR, pbond[a] = RG_FAR;
     }
@@ -226,7 +205,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
     int fragments = 0;
     for (;;) {
       int root = -1;
-      for (int k = 0; k < RG_ATOMS / 64 && root < 0; ++k) {
+      for (int k = 0; k < MOL_ATOMS / 64 && root < 0; ++k) {
         const int a = lane + 64 * k;
         const u64 open = __ballot(a < n && depth[a] == RG_FAR);
         if (open) root = 64 * k + __ffsll((long long)open) - 1;
@@ -243,7 +222,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
     for (int e0 = 0; e0 < nb; e0 += 64) {
       const int e = e0 + lane;
       const unsigned bd = e < nb ? s.bond[e] : 0u;
-      const bool outside_forest = bd && pbond[bd & 0xffu] != e && pbond[(bd >> 8) & 0xffu] != e;
+      const bool outside_forest = bd && pbond[mol_bond_i(bd)] != e && pbond[mol_bond_j(bd)] != e;
       const u64 mo = __ballot(outside_forest);
       if (e < nb) s.bnum[e] = outside_forest ? (unsigned char)min(numbered + __popcll(mo & below), 255) : (unsigned char)255;
       numbered += __popcll(mo);
@@ -268,7 +247,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
       const unsigned bd = s.bond[e];  // uniform in the wave
       int size = 0;
       if (bd) {
-        const int x = bd & 0xffu, y = (bd >> 8) & 0xffu;
+        const int x = mol_bond_i(bd), y = mol_bond_j(bd);
         bfs_init(n, lane, depth, nullptr, x);
         bfs_levels<false, false>(s, n, lane, depth, nullptr, e, y);
         const unsigned d = depth[y];
@@ -297,7 +276,7 @@ __global__ __launch_bounds__(256) void mol_rings_kernel(const RgArgs A) {
       const int r = bd ? s.brm[e] : 0;
       A.bond_ring_min[h0 + e] = r;
       if (!bd) continue;
-      const int x = bd & 0xffu, y = (bd >> 8) & 0xffu;
+      const int x = mol_bond_i(bd), y = mol_bond_j(bd);
       if (r > 0) ++ring_bonds, lmin = min(lmin, r);
       rotatable += bt[e] == 1 && r == 0 && s.off[x + 1] - s.off[x] >= 2 && s.off[y + 1] - s.off[y] >= 2 && !s.triple[x] && !s.triple[y];
     }
@@ -373,7 +352,5 @@ extern "C" int mdx_mol_rings(int32_t B, const int32_t* atom_ptr, const int32_t* 
   a.n_rings = n_rings, a.ring_hist = ring_hist, a.n_ring_atoms = n_ring_atoms, a.n_ring_bonds = n_ring_bonds;
   a.n_rotatable = n_rotatable, a.elem_count = elem_count, a.bond_count = bond_count, a.status = status;
   a.bond_ring_min = bond_ring_min, a.atom_ring_min = atom_ring_min;
-  if (B > 0) hipLaunchKernelGGL(mol_rings_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_rings_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_rings_kernel, "mol_rings_kernel", B, stream, a);
 }

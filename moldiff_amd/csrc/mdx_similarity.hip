@@ -280,9 +280,7 @@ extern "C" int mdx_mol_fingerprint(int32_t B, const int32_t* atom_ptr, const int
   a.radius = radius, a.key_rounds = key_rounds, a.nbits = nbits;
   a.bits = reinterpret_cast<unsigned*>(bits), a.n_on = n_on, a.key = reinterpret_cast<long long*>(key);
   a.ws_id = reinterpret_cast<unsigned*>(ws), a.ws_acc = a.ws_id + std::max<int64_t>(N_cap, 1);
-  if (B > 0) hipLaunchKernelGGL(mol_fingerprint_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_fingerprint_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_fingerprint_kernel, "mol_fingerprint_kernel", B, stream, a);
 }
 
 extern "C" size_t mdx_fp_tanimoto_ws_bytes(int64_t Na) { return 8 * (size_t)std::max<int64_t>(Na, 1); }

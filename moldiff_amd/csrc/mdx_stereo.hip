@@ -27,13 +27,11 @@
 #include "mdx_mol.h"
 #include "mdx_stereo_args.h"
 
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
-
 namespace {
 
 enum { S_STATUS, S_CAND, S_CENTRES, S_FLAT, S_BOND_CAND, S_STEREO_BONDS, S_STEREOGENIC, S_CHIRAL, S_AUT };
 static_assert(S_AUT + 1 == ST_STATS && ST_STATS == MDX_STEREO_STATS, "the columns of mol_stats");
-constexpr int ST_WORD = CN_ATOMS + CN_BONDS;
+constexpr int ST_WORD = MOL_ATOMS + MOL_BONDS;
 enum { A_NONE, A_FLAT, A_PLUS, A_MINUS };  // an atom's geometry code: no candidate; candidate with g = 0; g = +1; g = -1
 
 struct StArgs {
@@ -46,13 +44,13 @@ struct StArgs {
 
 struct StShared {
   CnGraph g;                        // the walk's own state (mdx_canon_body.h)
-  unsigned cw[CN_BONDS];            // the canonical certificate, from the given rank
-  unsigned others[CN_BONDS];        // x0 | x1 << 8 | y0 << 16 | y1 << 24: the other neighbours of a candidate bond's ends, x0 <= x1, y0 <= y1
-  unsigned nbr4[CN_ATOMS];          // the 3 or 4 neighbours of a candidate atom in ascending index, a byte each
-  unsigned short bpos[CN_BONDS];    // where the bond's word stands in the canonical certificate, per leaf
-  unsigned short dt[CN_BONDS];      // bit 8: a candidate; bits 2 (2 xi + yi) ..: d(x_xi, y_yi)
+  unsigned cw[MOL_BONDS];           // the canonical certificate, from the given rank
+  unsigned others[MOL_BONDS];       // x0 | x1 << 8 | y0 << 16 | y1 << 24: the other neighbours of a candidate bond's ends, x0 <= x1, y0 <= y1
+  unsigned nbr4[MOL_ATOMS];         // the 3 or 4 neighbours of a candidate atom in ascending index, a byte each
+  unsigned short bpos[MOL_BONDS];   // where the bond's word stands in the canonical certificate, per leaf
+  unsigned short dt[MOL_BONDS];     // bit 8: a candidate; bits 2 (2 xi + yi) ..: d(x_xi, y_yi)
   unsigned char w[ST_WORD], W[ST_WORD], M[ST_WORD];
-  unsigned char acode[CN_ATOMS], srank[CN_ATOMS], table[CN_ATOMS], crank[CN_ATOMS];
+  unsigned char acode[MOL_ATOMS], srank[MOL_ATOMS], table[MOL_ATOMS], crank[MOL_ATOMS];
 };
 
 struct D3 {
@@ -146,11 +144,11 @@ __global__ __launch_bounds__(256) void mol_stereo_kernel(const StArgs A) {
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
   const int n = v.n, nb = v.nb;
-  if (v.outside || v.masked) {  // uniform
-    write_unmeasured(A, m, 0, v);
+  if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
+    write_unmeasured(A, m, unmeasured, v);
     return;
   }
-  if (A.o.canon_status[m] != 0 || n > CN_ATOMS || nb > CN_BONDS) {  // uniform
+  if (A.o.canon_status[m] != 0) {  // uniform
     write_unmeasured(A, m, 1, v);
     return;
   }
@@ -200,12 +198,12 @@ __global__ __launch_bounds__(256) void mol_stereo_kernel(const StArgs A) {
 
   // ---- geometry: the bonds
   int n_bond_cand = 0;
-  for (int e0 = 0; e0 < CN_BONDS; e0 += 256) {  // uniform trip count: the count below is a barrier
+  for (int e0 = 0; e0 < MOL_BONDS; e0 += 256) {  // uniform trip count: the count below is a barrier
     const int e = e0 + tid;
     unsigned dt = 0u, oth = 0u;
     const unsigned bd = e < nb ? s.g.bond[e] : 0u;
-    if (bd && ((bd >> 16) & 0xffu) == 2u) {
-      const unsigned a = bd & 0xffu, b = (bd >> 8) & 0xffu;
+    if (bd && mol_bond_payload(bd) == 2u) {
+      const unsigned a = mol_bond_i(bd), b = mol_bond_j(bd);
       const int da = s.g.off[a + 1] - s.g.off[a], db = s.g.off[b + 1] - s.g.off[b];
       unsigned x0 = a, x1 = a, y0 = b, y1 = b;
       if (da >= 2 && da <= 3 && db >= 2 && db <= 3 && bond_end(s, a, b, x0, x1) && bond_end(s, b, a, y0, y1)) {
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(256) void mol_stereo_kernel(const StArgs A) {
         oth = x0 | x1 << 8 | y0 << 16 | y1 << 24;
       }
     }
-    if (e < CN_BONDS) s.dt[e] = (unsigned short)dt, s.others[e] = oth;
+    if (e < MOL_BONDS) s.dt[e] = (unsigned short)dt, s.others[e] = oth;
     n_bond_cand += __syncthreads_count(dt != 0u);
   }
 
@@ -319,7 +317,7 @@ __global__ __launch_bounds__(256) void mol_stereo_kernel(const StArgs A) {
     const int r = s.srank[tid];
     A.o.stereo_rank[n0 + tid] = r, A.o.canon_tetra[n0 + tid] = s.W[tid], A.o.mirror_tetra[n0 + tid] = s.M[tid], A.o.atom_tetra[n0 + tid] = s.W[r];
   }
-  for (int e0 = 0; e0 < CN_BONDS; e0 += 256) {  // uniform trip count
+  for (int e0 = 0; e0 < MOL_BONDS; e0 += 256) {  // uniform trip count
     const int e = e0 + tid;
     int cb = 0;
     if (e < nb) {
@@ -359,9 +357,6 @@ extern "C" int mdx_mol_stereo(int32_t B, const int32_t* atom_ptr, const int32_t*
   a.o = StereoOperands{atom_pos, atom_label, rank, canon_status, canon_tetra, canon_bond_stereo, mirror_tetra, mirror_bond_stereo, stereo_rank, atom_tetra, bond_stereo, mol_stats,
                        stereo_hash, mirror_hash};
   if (const char* why = stereo_check(a.o, flat_tol, bond_tol, max_nodes)) return mdx_set_error(MDX_ERR_ARG, why);
-  if (B == 0) return MDX_OK;
   a.centre4 = centre4_mask, a.centre3 = centre3_mask, a.flat_tol = flat_tol, a.bond_tol = bond_tol, a.max_nodes = max_nodes;
-  hipLaunchKernelGGL(mol_stereo_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) return mdx_set_error(MDX_ERR_HIP, "mol_stereo_kernel: launch failed");
-  return MDX_OK;
+  return mol_launch(mol_stereo_kernel, "mol_stereo_kernel", B, stream, a);
 }
