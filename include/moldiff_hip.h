@@ -1023,6 +1023,80 @@ int mdx_mol_hydrogens(int32_t B, const int32_t* atom_ptr, const int32_t* bond_pt
                       int32_t num_bond_types, const double* xh_length, uint32_t planar_mask, double deg_tol, double clash_tol,
                       double* h_pos, int32_t* h_count, int32_t* atom_flag, int32_t* mol_stats, double* min_contact, void* stream);
 
+/* ---- Force-field relaxation of the all-atom molecule: strain energy and heavy-atom displacement ---------------------------
+ * The reference's global_3d metric relaxes every molecule with UFFOptimizeMolecule between AddHs and GetBestRMS.  mdx_mol_relax
+ * relaxes the all-atom molecule of mdx_mol_hydrogens in a force field of UFF's FUNCTIONAL FORMS by L-BFGS and reports the energy
+ * before and after, the final gradient and how far the heavy atoms moved.  It is THIS PROJECT'S OWN MODEL: NOT RDKit's
+ * UFFOptimizeMolecule and UNVERIFIED AGAINST IT; the shipped rows (configs/forcefield_default.yml) are a transcription from memory of
+ * Rappe et al. 1992 and UNVERIFIED; hypervalent P and S use their tetrahedral row; there are no charges.  A plain restatement
+ * (moldiff_amd/relax.py: energy_ref, relax_ref) repeats every operation in the same order.  Units: kcal/mol and Angstrom; float64.
+ *
+ * INPUT.  The compact layout of mdx_mol_rings; atom_pos, order as for mdx_mol_hydrogens; h_pos, h_count, atom_flag as
+ *   mdx_mol_hydrogens wrote them (h = h_count clamped to 0 .. 4).  THE MOLECULE: the n heavy atoms in their order, then the hydrogens in
+ *   (atom, k) order, n_all atoms; the valid compact bonds plus one X-H bond per hydrogen.  n > 256, n_bonds > 512 or n_all > 256:
+ *   status TOO_LARGE.  A heavy atom's VARIANT is bits 0-1 of atom_flag (0 TETRAHEDRAL, 1 TRIGONAL, 2 LINEAR; 3 counts as 0), or RESONANT
+ *   (3) when it has a bond of type num_bond_types; a class outside 0 .. num_element - 1 is clamped into it.  The ORDER n of a bond is 1.5
+ *   for type num_bond_types, else `order` clamped to 1 .. 3, and 1 for X-H.
+ *   ff_rows: HOST, n_rows x 11 doubles: class (-1 = hydrogen: exactly one row), variant, r, theta0 (degrees), x, D, Z, chi, V, U, K_inv;
+ *   at most 32 rows, one per (class, variant), every class with its variant-0 row; a missing (class, variant) falls back to the
+ *   class's variant-0 row (counted in n_fallback).  The host takes c0 = cos theta0 (-1 for 180), sqrt chi, sqrt D and ln n.
+ * ENERGY.  (x.y = (x0 y0 + x1 y1) + x2 y2; every formula is evaluated as moldiff_amd/relax.py writes it.)
+ *   BOND a-b: E = 1/2 k (r - r_ab)^2; r_ab = (ri + rj) - 0.1332 (ri + rj) ln n - ri rj (sqrt chi_i - sqrt chi_j)^2 / (chi_i ri + chi_j rj),
+ *     k = 664.12 Zi Zj / r_ab^3, the lower atom index first.
+ *   ANGLE i-j-k (i < k in the row of j), c = cos theta: K = 664.12 Zi Zk / r_ik^5 [3 r_ij r_jk (1 - c0^2) - r_ik^2 c0] with
+ *     r_ik^2 = r_ij^2 + r_jk^2 - 2 r_ij r_jk c0 and c0 of the centre's row.  Centre LINEAR or c0 = -1: E = K (1 + c); TRIGONAL or
+ *     RESONANT: E = K/9 (1 - (4 c^3 - 3 c)); else E = K (C0 + C1 c + C2 (2 c^2 - 1)), C2 = 1 / (4 (1 - c0^2)), C1 = -4 C2 c0,
+ *     C0 = C2 (2 c0^2 + 1).
+ *   TORSION about a bond j-k whose ends both have >= 2 neighbours and are not LINEAR; every quadruple i-j-k-l with i != l contributes
+ *     with Vq = V / ((deg j - 1)(deg k - 1)); c = A.B / (|A||B|), A = (xi - xj) X (xj - xk), B = (xl - xk) X (xj - xk); skipped when
+ *     |A| or |B| < deg_tol.  Neither end planar (TRIGONAL, RESONANT): 1/2 Vq (1 + (4 c^3 - 3 c)), V = sqrt(Vj Vk); both planar:
+ *     1/2 Vq (1 - (2 c^2 - 1)), V = 5 sqrt(Uj Uk) (1 + 4.18 ln n); mixed: 1/2 Vq (1 - (32 c^6 - 48 c^4 + 18 c^2 - 1)), V = 1.
+ *   INVERSION at a TRIGONAL or RESONANT centre j with exactly three neighbours and K_inv > 0 (shipped: C and N, 6): for each apex l of
+ *     the three, the others i < k: E = (K_inv / 3)(1 - sqrt(1 - y^2)), y the cosine between xl - xj and (xi - xj) X (xk - xj); skipped
+ *     when that normal is shorter than deg_tol or the apex lies on the centre.
+ *   VAN DER WAALS, every pair a < b that is neither bonded nor shares a neighbour, no cutoff: E = D (q^12 - 2 q^6), q^2 = xa xb / r^2,
+ *     D = sqrt Da sqrt Db.
+ *   ACCUMULATION.  Thread a gathers the gradient on atom a in this order, rows ascending by neighbour: its bonds; the angles centred
+ *     on it (q1 < q2); the angles it ends (its neighbour j, j's other neighbours k); the torsions about its bonds (k, then i, then l);
+ *     the torsions it ends (j, k, l); the inversions centred on it (apex = neighbour 0, 1, 2); those of its neighbours; the pairs
+ *     b = 0 .. n_all - 1.  A term's energy is added once, by the lower atom of a bond or pair, the centre of an angle or inversion,
+ *     the lower central atom of a torsion, in the same walk.  Every sum over atoms (the five components, every dot product) is the
+ *     per-thread value, a xor butterfly (32, 16, .. 1) in each wave of 64, then ((w0 + w1) + w2) + w3; total = (((bond + angle) +
+ *     torsion) + inversion) + vdw.  No floating-point atomics: every output is bit-reproducible and independent of the batch.
+ * MINIMISER.  L-BFGS, history 8.  Loop: rms = sqrt(g.g / (3 n_all)); rms <= gtol: stop CONVERGED; iterations = max_iters: stop
+ *   MAXITER.  Direction: -g without history, else the two-loop recursion (alpha_i = s_i.q / s_i.y_i, newest first; r = (s.y / y.y of
+ *   the newest) q; r += (alpha_i - y_i.r / s_i.y_i) s_i, oldest first; d = -r); g.d >= 0 drops the history, d = -g.  Step cap: with
+ *   big = the largest |d_a|, big > max_step scales d by max_step / big.  Line search: t = 1, 1/2, .. at most 20 trials, accept when
+ *   E(x + t d) is finite and <= E + (1e-4 t) g.d.  Exhausted: with a history, drop it and search once more along -g; else stop
+ *   LINESEARCH.  Accepted: s = x_new - x, y = g_new - g are stored when s.y > 1e-10 sqrt(s.s y.y).  max_iters = 0 is a plain
+ *   energy / gradient evaluation.  A starting energy or g.g that is not finite: status NONFINITE.
+ *   Only the starting g.g is tested for finiteness.  A later accepted point has a finite energy; should its gradient not be finite, no
+ *   comparison with it holds any more (rms <= gtol, g.d < 0 and every acceptance test are false with a NaN), the largest |d_a| is taken
+ *   with fmax, which drops a NaN, and the run ends LINESEARCH at that point, the same on the device and in the restatement.
+ * OUTPUTS (device, plain stores by the molecule's own workgroup):
+ *   pos_out, grad_out [N_cap][3]; h_pos_out, h_grad_out [N_cap][4][3] float64: the relaxed point and the gradient there, hydrogen
+ *     slots k >= h are 0.
+ *   mol_stats [m][k], k < MDX_RELAX_STATS = 11 (int32): 0 status (0 relaxed, 1 TOO_LARGE, 2 NONFINITE; every other output of the
+ *     molecule is 0 for 1 and 2)  1 stop reason (0 CONVERGED, 1 MAXITER, 2 LINESEARCH)  2 iterations  3 energy evaluations  4 n_all
+ *     5 bonds  6 angles  7 torsion quadruples that contribute  8 inversion terms that contribute  9 pairs  10 atoms on a fall-back row
+ *     (5 .. 9 at the starting point).
+ *   mol_energy [m][k], k < MDX_RELAX_ENERGIES = 14 (float64): 0-4 bond, angle, torsion, inversion, vdw and 5 their total at the start;
+ *     6-11 the same at the end; 12 the final rms gradient; 13 rmsd_heavy = sqrt(sum |x_a - x0_a|^2 / n) over the heavy atoms, unaligned.
+ *   select, and a molecule reaching past N_cap / Eh_stride, as for mdx_mol_hydrogens.
+ * ws: B x 16 x 768 doubles of device memory (the history; each thread touches its own atom's entries), ws_bytes its size.
+ * One workgroup of 256 threads per molecule, about 53 KB of LDS.  MDX_ERR_ARG, every output untouched: a null operand (select
+ * excepted), a negative size, a workspace too small, num_element outside 1 .. 32, num_bond_types outside 1 .. 16, a bad row (see
+ * csrc/mdx_relax_args.h), deg_tol outside (0, 1), gtol outside (0, 1e6], max_step outside (0, 10], max_iters outside 0 .. 100000.
+ * B = 0 is accepted and writes nothing. */
+#define MDX_RELAX_STATS 11
+#define MDX_RELAX_ENERGIES 14
+int mdx_mol_relax(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                  const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                  const int32_t* select, const float* atom_pos, const int32_t* order, const double* h_pos, const int32_t* h_count,
+                  const int32_t* atom_flag, int32_t num_element, int32_t num_bond_types, const double* ff_rows, int32_t n_rows,
+                  double deg_tol, double gtol, double max_step, int32_t max_iters, double* pos_out, double* h_pos_out, double* grad_out,
+                  double* h_grad_out, int32_t* mol_stats, double* mol_energy, double* ws, size_t ws_bytes, void* stream);
+
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,
  * models/bond_predictor.py:84-124 + torch.autograd) is composed from these forward/backward pairs, one layer at a

@@ -307,6 +307,28 @@ class FeaturizeMol(object):
                                hydrogens.DEFAULT_CLASH_TOL if clash_tol is None else clash_tol, select=select)
         return attach(kek, cm, select, n_atoms, kekule.LAYOUT), attach(out, cm, select, n_atoms, hydrogens.LAYOUT)
 
+    def relax_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, tables=None, graph=None, *, select=None,
+                    max_iters=None, gtol=None):
+        """``addh_batch`` + the force-field relaxation of every decoded all-atom molecule (``mdx_mol_kekulize``, ``mdx_mol_hydrogens``
+        with the default chemistry, then ``mdx_mol_relax``; see ``moldiff_amd/relax.py``).  tables: a ``relax.ForceFieldTables`` made
+        for this featuriser (None = the defaults).  Nothing is copied to the host and nothing synchronises.  select: (n_graphs) device
+        tensor; a molecule with 0 keeps its place with status 0, n_atoms 0 and every output 0.  -> (kekule results, hydrogen results,
+        relax results): the dicts of ``addh_batch`` and the results dict of device tensors of ``relax.launch`` with n_atoms, in the
+        decode's own layout, molecule m at atom_ptr[m].  These are the molecules AS DECODED; the force field is this project's own
+        UFF-form model over an unverified table, not RDKit's UFFOptimizeMolecule.  Like ``decode_batch``, it needs a batch with at
+        least one half-edge."""
+        from . import hydrogens, kekule, relax
+        tables = relax.ForceFieldTables(self.atomic_numbers.tolist(), self.num_bond_types) if tables is None else tables
+        self._same_featuriser(tables, 'the tables were')
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        if cm.B == 0:
+            return on_device(kekule.empty(), cm.device), on_device(hydrogens.empty(), cm.device), on_device(relax.empty(), cm.device)
+        kek = kekule.launch(cm, kekule.KekuleTables(tables.atomic_numbers, tables.num_bond_types), select=select)
+        hyd = hydrogens.launch(cm, kek['kek_h'], kek['kek_order'], hydrogens.HydrogenTables(tables.atomic_numbers, tables.num_bond_types), select=select)
+        out = relax.launch(cm, kek['kek_order'], hyd['h_pos'], hyd['h_count'], hyd['atom_flag'], tables,
+                           relax.DEFAULT_MAX_ITERS if max_iters is None else max_iters, relax.DEFAULT_GTOL if gtol is None else gtol, select=select)
+        return attach(kek, cm, select, n_atoms, kekule.LAYOUT), attach(hyd, cm, select, n_atoms, hydrogens.LAYOUT), attach(out, cm, select, n_atoms, relax.LAYOUT)
+
     def canon_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
                     atom_label=None):
         """``decode_batch``'s device part + the canonical labelling of every decoded molecule (``mdx_mol_canon``; see

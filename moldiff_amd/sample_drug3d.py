@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks] [--hydrogens]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks] [--hydrogens] [--relax]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -76,6 +76,13 @@ project's own idealised placement, not RDKit's AddHs, unverified against RDKit; 
 kekulizable finished molecules as all-atom mol blocks) beside ``samples_all.pt``.  ``--clash_tol`` (``sample.clash_tol``; 1.5 Angstrom: a
 convention, untuned) is the contact length below which a pair counts as a clash.  No acceptance rule is added; without the option
 nothing changes.
+``--relax`` (config key ``sample.relax``; the flag wins; implies ``--hydrogens``), an addition beyond the reference: rank 0 relaxes the
+all-atom FINISHED molecules in a UFF-form force field on the device batch by batch (``moldiff_amd/relax.py``: this project's own model
+over an unverified parameter table, not RDKit's UFFOptimizeMolecule, unverified against RDKit) and writes ``relax.npz`` (statuses,
+energies before and after, relaxed positions), ``relax.json`` (their summary: strain, convergence shares, histograms) and
+``samples_relaxed.sdf`` (the kekulizable, relaxed molecules as all-atom mol blocks) beside ``samples_all.pt``.  ``--relax_iters``
+(``sample.relax_iters``; 200) and ``--relax_gtol`` (``sample.relax_gtol``; 1e-2 kcal/mol/Angstrom: a convention) bound the minimiser.  No
+acceptance rule is added; without the option nothing changes.
 ``--frameworks`` (config key ``sample.frameworks``; the flag wins), an addition beyond the reference: rank 0 cuts the FINISHED molecules
 into framework, ring systems, linkers and side chains on the device batch by batch (``moldiff_amd/framework.py``: this project's own
 definition, not RDKit's MurckoScaffold), keys the pieces with the canonical labelling and writes ``frameworks.npz`` (results and keys)
@@ -337,6 +344,27 @@ def add_hydrogens_argument(ap):
     return ap
 
 
+def relax_option(flag, iters, gtol, sample_cfg):
+    """whether to write the relaxation files, and the iteration limit and rms-gradient threshold of ``moldiff_amd/relax.py``: the command
+    line (None = not given) wins over the config's ``sample.relax``, ``sample.relax_iters`` and ``sample.relax_gtol``; 200 and 1e-2
+    kcal/mol/Angstrom where neither says"""
+    from . import relax
+    pick = lambda v, key, default: v if v is not None else sample_cfg.get(key) if sample_cfg.get(key) is not None else default
+    iters, gtol = relax._check(pick(iters, 'relax_iters', relax.DEFAULT_MAX_ITERS), pick(gtol, 'relax_gtol', relax.DEFAULT_GTOL))[:2]
+    return bool(flag if flag is not None else sample_cfg.get('relax')), iters, gtol
+
+
+def add_relax_argument(ap):
+    """``--relax`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--relax', action='store_true', default=None,
+                    help='relax the all-atom finished molecules in a UFF-form force field on the device and write relax.npz, relax.json '
+                         'and samples_relaxed.sdf; implies --hydrogens (overrides sample.relax)')
+    ap.add_argument('--relax_iters', type=int, default=None, help='L-BFGS iterations at most (overrides sample.relax_iters; 200)')
+    ap.add_argument('--relax_gtol', type=float, default=None,
+                    help='rms gradient in kcal/mol/Angstrom at which a molecule has converged (overrides sample.relax_gtol; 1e-2: a convention)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -438,7 +466,7 @@ def add_frameworks_argument(ap):
 
 
 def main(argv=None):
-    args = add_hydrogens_argument(add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))))))).parse_args(argv)
+    args = add_relax_argument(add_hydrogens_argument(add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -517,6 +545,8 @@ def main(argv=None):
         groups_set = groups.PatternSet.from_yaml(groups_path, Z, nbt) if groups_path else groups.PatternSet.default(Z, nbt)
         features.append(Feature(lambda gen: groups.groups_mols(gen, device, groups_set), groups, 'groups', empty=lambda: groups.empty(groups_set)))
     hydrogens_on, clash_tol = hydrogens_option(args.hydrogens, args.clash_tol, config.sample)
+    relax_on, relax_iters, relax_gtol = relax_option(args.relax, args.relax_iters, args.relax_gtol, config.sample)
+    hydrogens_on = hydrogens_on or relax_on   # --relax implies --hydrogens
     kek_write = kekulize_option(args.kekulize, config.sample) or hydrogens_on   # --hydrogens implies --kekulize
     kek_active = kek_write or rule == 'kekule'
     if kek_active:
@@ -532,10 +562,18 @@ def main(argv=None):
     if hydrogens_on:   # behind kekule: the joined Kekulé results are there when the all-atom file is written
         from . import hydrogens
         h_tables = hydrogens.HydrogenTables(Z, nbt)
+
+        def write_allatom_sdf(res):
+            kek_held['hydrogens'] = res
+            hydrogens.write_sdf(os.path.join(log_dir, 'samples_allatom.sdf'), pool['finished'], kek_held['kekule'], res)
         features.append(Feature(lambda gen: hydrogens.addh_mols(gen, device, tables=h_tables, clash_tol=clash_tol), hydrogens, 'hydrogens',
-                                summary=lambda res: hydrogens.summary(res, clash_tol),
-                                after=lambda res: hydrogens.write_sdf(os.path.join(log_dir, 'samples_allatom.sdf'), pool['finished'],
-                                                                      kek_held['kekule'], res)))
+                                summary=lambda res: hydrogens.summary(res, clash_tol), after=write_allatom_sdf))
+    if relax_on:   # behind hydrogens: the joined Kekulé and hydrogen results are there when the relaxed file is written
+        from . import relax
+        ff_tables = relax.ForceFieldTables(Z, nbt)
+        features.append(Feature(lambda gen: relax.relax_mols(gen, device, ff_tables, relax_iters, relax_gtol), relax, 'relax',
+                                after=lambda res: relax.write_sdf(os.path.join(log_dir, 'samples_relaxed.sdf'), pool['finished'],
+                                                                  kek_held['kekule'], kek_held['hydrogens'], res)))
     stereo_on, flat_tol, bond_tol = stereo_option(args.stereo, args.stereo_flat_tol, args.stereo_bond_tol, config.sample)
     conformers_on, conformer_tol = conformers_option(args.conformers, args.conformer_tol, config.sample)
     if canonical_option(args.canonical, config.sample) or stereo_on or conformers_on:
