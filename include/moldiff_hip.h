@@ -840,7 +840,8 @@ int mdx_mol_stereo(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, 
 /* ---- Symmetry-aware best RMSD between conformers of one constitution ------------------------------------------------------
  * The reference's `global_3d` metric is get_rdkit_rmsd (utils/scoring_func.py:56-74): rdMolAlign.GetBestRMS(mol, mol3d), the RMSD
  * after optimal rigid superposition, minimised over every atom mapping that the symmetry of the molecule allows.  mdx_mol_bestrms is
- * the alignment half of it.  There is NO CONFORMER GENERATION here (the reference's ETKDG + UFF side comes from elsewhere), the atoms
+ * the alignment half of it.  There is NO CONFORMER GENERATION in this entry: conformers come from mdx_mol_bounds + mdx_mol_embed and
+ * mdx_mol_relax below (this project's own distance geometry and force field, not the reference's ETKDG + UFF) or from another program, the atoms
  * are the HEAVY ATOMS of the compact molecule, and the symmetry group is that of THIS PROJECT'S LABELLED GRAPH (mdx_mol_canon; aromatic
  * bonds are a type of their own), which can be smaller than RDKit's substructure match on a kekulised input.  It is pure mathematics;
  * a plain restatement (moldiff_amd/rmsd.py: best_rms_ref, numpy's SVD) agrees to a tolerance derived from float64 alone.  Agreement
@@ -1096,6 +1097,82 @@ int mdx_mol_relax(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, c
                   const int32_t* atom_flag, int32_t num_element, int32_t num_bond_types, const double* ff_rows, int32_t n_rows,
                   double deg_tol, double gtol, double max_step, int32_t max_iters, double* pos_out, double* h_pos_out, double* grad_out,
                   double* h_grad_out, int32_t* mol_stats, double* mol_energy, double* ws, size_t ws_bytes, void* stream);
+
+/* ---- Conformer generation: distance bounds of the all-atom molecule and coordinates embedded from them ---------------------
+ * The reference's global_3d metric embeds n_conf conformers (EmbedMultipleConfs) between AddHs and UFFOptimizeMolecule.
+ * mdx_mol_bounds + mdx_mol_embed are that stage: distance geometry with random starting coordinates, in the spirit of RDKit's
+ * useRandomCoords embedding.  It is THIS PROJECT'S OWN MODEL: NOT ETKDG (no torsion preferences, no chiral-volume constraints, so a
+ * conformer may be the MIRROR IMAGE at a stereocentre) and UNVERIFIED AGAINST RDKit; its lengths and angles come from the UNVERIFIED
+ * rows of mdx_mol_relax.  A restatement (moldiff_amd/embed.py: bounds_ref, embed_ref) repeats every operation in the same order.
+ * Angstrom; float64.
+ *
+ * mdx_mol_bounds.  INPUT: the compact layout, order, h_count, atom_flag, ff_rows exactly as for mdx_mol_relax (same molecule, same
+ *   atom order, same typing, same rest lengths r_ab by relax_pair; no positions are read).  tol12, tol13, tol14 in [0, 1] Angstrom
+ *   (conventions: 0.01, 0.04, 0.06) and vdw_scale in (0, 2] (convention 0.6); na_cap in 1 .. 256.
+ *   THE INITIAL BOUNDS of a pair {a, d}, by the shortest bond path between them (a pair on several shortest paths takes the smallest
+ *   lower and the largest upper bound of them; every path is evaluated from its lower end atom to its higher one; a lower bound below
+ *   0 is 0):
+ *     1-2: r_ab -+ tol12.
+ *     1-3 a-b-d: l = sqrt((r1 r1 + r2 r2) - ((2 r1) r2) c), l -+ tol13, with c = cos theta0 of the centre b's row, or cos 60 / 90 /
+ *       108 degrees when the angle a-b-d lies in a ring of 3 / 4 / 5 atoms (a, d bonded; else a and d share a neighbour other than b;
+ *       else a neighbour x != b of a is bonded to a neighbour y != b of d): the shortest cycle through both bonds.  The host takes the
+ *       cosines (cos(deg pi / 180), as c0).
+ *     1-4 a-b-c-d: with c1, c2 the cosines at b and c as above, s = sqrt(1 - c c), dx = (r2 - r3 c2) - r1 c1: cis = sqrt(dx dx +
+ *       (r3 s2 - r1 s1)^2), trans = sqrt(dx dx + (r3 s2 + r1 s1)^2); [cis - tol14, trans + tol14].  No planarity preference: a stated
+ *       limitation, relaxation restores most of it.
+ *     every other pair: lower = vdw_scale (0.5 (x_a + x_b)) from the rows' x, upper = 1000.  The diagonal is 0.
+ *   SMOOTHING (Floyd-Warshall, k = 0 .. n_all - 1 outermost, a barrier per k): first U[i][j] = min(U[i][j], U[k][i] + U[k][j]), then with
+ *   the final U: L[i][j] = max(max(L[i][j], L[k][i] - U[k][j]), L[k][j] - U[k][i]).  Sums and min / max only.  L > U for some pair
+ *   afterwards: status INCONSISTENT.
+ *   bounds_ws (device): B x 2 x na_cap^2 doubles, [m][0] the lower and [m][1] the upper bounds as full symmetric matrices of row stride
+ *   na_cap (the lanes a of mdx_mol_embed read [b][a]: consecutive words), then B x na_cap^2 bytes, the class of every pair in the same
+ *   layout (0 other or diagonal, 1 1-2, 2 1-3, 3 1-4): ws_bytes >= 17 B na_cap^2.  Entries past n_all are not written.
+ *   mol_stats [m][k], k < MDX_BOUNDS_STATS = 7 (int32): 0 status (0 OK, 1 TOO_LARGE: n > 256, n_bonds > 512 or n_all > na_cap, 3
+ *   INCONSISTENT)  1 n_all  2-4 the 1-2 / 1-3 / 1-4 pairs  5 angles i-j-k (i < k in the row of j) in a ring of 3, 4 or 5  6 pairs whose
+ *   lower or upper bound smoothing changed.  A masked molecule or one past the arrays: all 0.  About 60 KB of LDS.
+ *
+ * mdx_mol_embed.  One workgroup of 256 threads per (molecule m, conformer c), thread a = atom a; h_count as above; bounds_ws, na_cap and
+ *   bounds_stats (the mol_stats above) from mdx_mol_bounds on the same arrays; mol_ids (int64, B) or NULL for id = m.
+ *   START (attempt t = 0, 1, ..): 4D coordinates uniform in [-L/2, L/2), L = 2 x the largest smoothed upper bound of the 1-2, 1-3 and
+ *   1-4 pairs.  Philox4x32-10, key = the 64-bit seed (low, high word), counter = (2 a + j, c, id low word, (id >> 32) << 8 | t), j = 0:
+ *   coordinates 0 and 1 from words (x, y) and (z, w), j = 1: coordinates 2 and 3.  Words (p, q) -> u = ((p >> 5) 2^26 + (q >> 6)) 2^-53,
+ *   exactly; coordinate = (u - 0.5) L.  The seed is the key and the conformer, the id and the attempt are counter words: every (seed, id,
+ *   conformer, attempt, atom) has its own block.  Only bits 0 .. 55 of an id enter the counter: ids that differ only above bit 55 share their numbers.
+ *   mol_ids is device memory, which this entry does not read on the host: embed.embed_mols refuses an id outside 0 .. 2^56 - 1.
+ *   ERROR.  d2 = (((dx dx + dy dy) + dz dz) + dw dw) of x_a - x_b; for every b = 0 .. n_all - 1 in order (the diagonal contributes
+ *   nothing): d2 > ub^2: v = d2 / ub^2 - 1, e = v v, g_a += ((4 v) / ub^2)(x_a - x_b); d2 < lb^2: q = lb^2 + d2, v = (2 lb^2) / q - 1,
+ *   e = v v, g_a += -(((8 lb^2) v) / (q q))(x_a - x_b); e is added by the lower atom; then e += w4 (x4 x4), g_a4 += (2 w4) x4.  Sums over
+ *   atoms as in mdx_mol_relax (butterfly, then ((w0 + w1) + w2) + w3), dot products ((x x' + y y') + z z') + w w'.  No atomics.
+ *   MINIMISER: the L-BFGS of mdx_mol_relax (history 8, step cap max_step, 20 Armijo halvings with 1e-4, curvature test 1e-10) over the
+ *   4 n_all coordinates, rms = sqrt(g.g / (4 n_all)) <= gtol; a second copy of that code.  Stage A with w4 = 0.1 and stage B with
+ *   w4 = 1.0 from A's end point, each with an empty history and at most max_iters iterations; then the fourth coordinate is dropped.
+ *   ACCEPTANCE.  In 3D, d = sqrt((dx dx + dy dy) + dz dz): the largest of (d - ub) / ub for d > ub and (lb - d) / lb for d < lb over
+ *   the 1-2 and 1-3 pairs and of (lb - d) / lb over the other pairs (1-4 pairs are not tested) must be <= viol_tol (convention 0.1);
+ *   otherwise the next attempt, at most max_attempts; then status FAILED with the last attempt's numbers and coordinates.
+ *   OUTPUTS: pos_out [c][N_cap][3], h_pos_out [c][N_cap][4][3] float64 in the layout of mdx_mol_relax's inputs with a leading conformer
+ *   axis, hydrogen slots k >= h are 0 (mdx_mol_relax takes float32 heavy positions: the CALLER rounds them once);
+ *   conf_stats [m][c][k], k < MDX_EMBED_STATS = 5 (int32): 0 status (0 OK, 1 TOO_LARGE, 2 NONFINITE: a starting error that is not finite,
+ *   3 INCONSISTENT, 4 FAILED; for 1, 2, 3 every other output is 0)  1 attempts used  2, 3 iterations of A and B of the last attempt  4
+ *   error evaluations over all attempts;  conf_values [m][c][k], k < MDX_EMBED_VALUES = 3 (float64): the final error of A, of B, the
+ *   largest violation.  select and a molecule past the arrays as for mdx_mol_relax.
+ *   hist: B x n_confs x 64 x na_cap doubles (the history), hist_bytes its size.
+ * MDX_ERR_ARG, every output untouched: a null operand (select, mol_ids excepted), a negative size, a workspace too small, na_cap
+ * outside 1 .. 256, a tolerance or vdw_scale outside its range, a bad row, n_confs outside 1 .. 65535, max_iters outside 0 .. 100000,
+ * max_attempts outside 1 .. 64, gtol outside (0, 1e6], max_step outside (0, 10], viol_tol outside (0, 10].  B = 0 writes nothing. */
+#define MDX_BOUNDS_STATS 7
+#define MDX_EMBED_STATS 5
+#define MDX_EMBED_VALUES 3
+int mdx_mol_bounds(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                   const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                   const int32_t* select, const int32_t* order, const int32_t* h_count, const int32_t* atom_flag, int32_t num_element,
+                   int32_t num_bond_types, const double* ff_rows, int32_t n_rows, double tol12, double tol13, double tol14, double vdw_scale,
+                   int32_t na_cap, void* bounds_ws, size_t ws_bytes, int32_t* mol_stats, void* stream);
+int mdx_mol_embed(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, const int32_t* n_atoms, const int32_t* n_bonds,
+                  const int32_t* atom_type, int64_t N_cap, const int32_t* bond_type, const int32_t* bond_index, int64_t Eh_stride,
+                  const int32_t* select, const int32_t* h_count, const int64_t* mol_ids, const void* bounds_ws, size_t ws_bytes, int32_t na_cap,
+                  const int32_t* bounds_stats, int32_t n_confs, uint64_t seed, int32_t max_iters, int32_t max_attempts, double gtol,
+                  double max_step, double viol_tol, double* pos_out, double* h_pos_out, int32_t* conf_stats, double* conf_values,
+                  double* hist, size_t hist_bytes, void* stream);
 
 /* ---- layer-level operators of the training path (next-row) ---------------------------------
  * The loss forward + backward of MolDiff.get_loss / BondPredictor.get_loss (models/model.py:128-201,

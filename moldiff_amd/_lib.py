@@ -26,7 +26,7 @@ EXPORTS = [
     'mdx_pos_posterior', 'mdx_cat_posterior', 'mdx_gumbel_argmax', 'mdx_prior_draw', 'mdx_noise',
     'mdx_guidance_uncertainty_grad', 'mdx_add_inplace', 'mdx_decode_output', 'mdx_mol_check', 'mdx_mol_keep_component', 'mdx_mol_local3d', 'mdx_mol_local3d_ws_bytes', 'mdx_scaffold_merge',
     'mdx_mol_fingerprint', 'mdx_mol_fingerprint_ws_bytes', 'mdx_fp_tanimoto', 'mdx_fp_tanimoto_ws_bytes', 'mdx_mol_rings',
-    'mdx_mol_groups', 'mdx_mol_groups_ws_bytes', 'mdx_mol_kekulize', 'mdx_mol_canon', 'mdx_mol_stereo', 'mdx_mol_bestrms', 'mdx_mol_framework', 'mdx_mol_hydrogens', 'mdx_mol_relax',
+    'mdx_mol_groups', 'mdx_mol_groups_ws_bytes', 'mdx_mol_kekulize', 'mdx_mol_canon', 'mdx_mol_stereo', 'mdx_mol_bestrms', 'mdx_mol_framework', 'mdx_mol_hydrogens', 'mdx_mol_relax', 'mdx_mol_bounds', 'mdx_mol_embed',
     'mdx_sample_jump_full', 'mdx_pos_posterior_jump', 'mdx_cat_posterior_jump', 'mdx_forward_jump',
     'mdx_profile_enable', 'mdx_profile_read', 'mdx_profile_kernel_name',
     'mdx_op_sgemm_nt', 'mdx_op_sgemm_tn', 'mdx_op_amp_adamw',
@@ -186,6 +186,11 @@ def lib():
                                          [c_int32, c_int32, c_void_p, c_uint32, c_double, c_double] + [c_void_p] * 5 + [c_void_p])
         L.mdx_mol_relax.argtypes = ([c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 6 +
                                      [c_int32, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_int32] + [c_void_p] * 7 + [c_size_t, c_void_p])
+        L.mdx_mol_bounds.argtypes = ([c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 4 +
+                                      [c_int32, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_double, c_int32, c_void_p, c_size_t, c_void_p, c_void_p])
+        L.mdx_mol_embed.argtypes = ([c_int32] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p, c_int64] + [c_void_p] * 4 +
+                                     [c_size_t, c_int32, c_void_p, c_int32, c_uint64, c_int32, c_int32, c_double, c_double, c_double] + [c_void_p] * 5 +
+                                     [c_size_t, c_void_p])
         L.mdx_scaffold_merge.argtypes = [c_void_p, POINTER(MdxScaffoldTables), c_int32, POINTER(MdxScaffold), POINTER(MdxStepNoise),
                                          POINTER(MdxState), c_float] + [c_void_p] * 6
         L.mdx_forward_jump.argtypes = [c_void_p, POINTER(MdxForwardTables), c_int32, c_void_p, c_void_p, c_void_p, POINTER(MdxStepNoise),

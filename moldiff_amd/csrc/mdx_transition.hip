@@ -8,6 +8,7 @@
 //                      molecule's noise does not depend on how the batch is sharded over GPUs.
 // Compiled with -ffp-contract=off: the reference evaluates these formulas with separate mul/add.
 #include "mdx_kernels.h"
+#include "mdx_philox.h"
 #include <algorithm>
 
 #define MDX_MAXK 8
@@ -253,21 +254,6 @@ __global__ void uncertainty_grad_kernel(const float* __restrict__ logits, int K,
 __global__ void add_inplace_kernel(float* __restrict__ dst, const float* __restrict__ src, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = dst[i] + src[i];
-}
-
-struct u4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u4 philox4x32_10(u4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    u4 n = {hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    c = n;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
 }
 
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }  // [0,1)

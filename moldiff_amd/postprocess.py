@@ -329,6 +329,26 @@ class FeaturizeMol(object):
                            relax.DEFAULT_MAX_ITERS if max_iters is None else max_iters, relax.DEFAULT_GTOL if gtol is None else gtol, select=select)
         return attach(kek, cm, select, n_atoms, kekule.LAYOUT), attach(hyd, cm, select, n_atoms, hydrogens.LAYOUT), attach(out, cm, select, n_atoms, relax.LAYOUT)
 
+    def embed_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, tables=None, graph=None, *, select=None, n_confs=None,
+                    seed=0, mol_ids=None, **kw):
+        """``addh_batch`` + conformers of every decoded all-atom molecule (``mdx_mol_kekulize``, ``mdx_mol_hydrogens`` with the default
+        chemistry, then ``mdx_mol_bounds`` and ``mdx_mol_embed``; see ``moldiff_amd/embed.py``).  tables: a ``relax.ForceFieldTables`` made
+        for this featuriser (None = the defaults); mol_ids: int64 device tensor of the ids that key the random numbers (None: the index
+        in the batch); kw: the settings of ``embed.launch``.  Nothing is copied to the host and nothing synchronises; the bounds take the
+        full stride of 256 atoms unless `na_cap` is given.  select: a molecule with 0 keeps its place with every output 0.
+        -> (kekule results, hydrogen results, the dict of device tensors of ``embed.launch`` with n_atoms and atom_ptr) in the decode's
+        own layout.  This project's own distance geometry, not ETKDG, unverified against RDKit; stereocentres are not constrained."""
+        from . import embed, hydrogens, kekule, relax
+        tables = relax.ForceFieldTables(self.atomic_numbers.tolist(), self.num_bond_types) if tables is None else tables
+        self._same_featuriser(tables, 'the tables were')
+        cm, _, select, n_atoms = self._compact_mols(pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph, select)
+        kek = kekule.launch(cm, kekule.KekuleTables(tables.atomic_numbers, tables.num_bond_types), select=select)
+        hyd = hydrogens.launch(cm, kek['kek_h'], kek['kek_order'], hydrogens.HydrogenTables(tables.atomic_numbers, tables.num_bond_types), select=select)
+        out = embed.launch(cm, kek['kek_order'], hyd['h_count'], hyd['atom_flag'], embed.DEFAULT_N_CONFS if n_confs is None else n_confs, seed, tables,
+                           mol_ids, select, **kw)
+        out['n_atoms'], out['atom_ptr'] = n_atoms, cm.atom_ptr
+        return attach(kek, cm, select, n_atoms, kekule.LAYOUT), attach(hyd, cm, select, n_atoms, hydrogens.LAYOUT), out
+
     def canon_batch(self, pred, batch_node, halfedge_index, batch_halfedge, n_graphs, graph=None, *, select=None, max_nodes=None,
                     atom_label=None):
         """``decode_batch``'s device part + the canonical labelling of every decoded molecule (``mdx_mol_canon``; see

@@ -1,7 +1,7 @@
 """Sampling entry point -- the MI355X counterpart of the reference's ``scripts/sample_drug3d.py``.
 
     python -m moldiff_amd.sample_drug3d --config configs/sample_MolDiff_simple.yml --outdir ./outputs \
-        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks] [--hydrogens] [--relax]
+        --device cuda:0 [--batch_size N] [--recipe-weights] [--scaffold scaffold.mol] [--accept valence] [--largest_fragment 0.8] [--kekulize] [--canonical] [--stereo] [--conformers] [--frameworks] [--hydrogens] [--relax] [--global3d N]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m moldiff_amd.sample_drug3d ...
 
 Same flags (--config --outdir --device --batch_size), same YAML keys (model.checkpoint, bond_predictor,
@@ -83,6 +83,14 @@ energies before and after, relaxed positions), ``relax.json`` (their summary: st
 ``samples_relaxed.sdf`` (the kekulizable, relaxed molecules as all-atom mol blocks) beside ``samples_all.pt``.  ``--relax_iters``
 (``sample.relax_iters``; 200) and ``--relax_gtol`` (``sample.relax_gtol``; 1e-2 kcal/mol/Angstrom: a convention) bound the minimiser.  No
 acceptance rule is added; without the option nothing changes.
+``--global3d N`` (config key ``sample.global3d``; the flag wins; implies ``--hydrogens``), an addition beyond the reference's sampling
+script: rank 0 generates N conformers of every FINISHED molecule on the device batch by batch (``moldiff_amd/embed.py``: distance
+bounds, embedding from random coordinates keyed by ``--global3d_seed`` (``sample.global3d_seed``; 0) and the molecule's id, then the
+relaxation of ``--relax`` with its defaults), takes the best RMSD of every conformer against the molecule and writes ``global3d.npz``
+(statuses, deviations, conformer coordinates), ``global3d.json`` (their summary) and ``conformers.sdf`` (the conformers that count
+as all-atom mol blocks) beside ``samples_all.pt``.  This project's own model, not ETKDG + UFF, unverified against RDKit; stereocentres
+are not constrained, so a conformer may be the mirror image and the mirror-image numbers are reported beside the plain ones.  Without
+the option nothing changes.
 ``--frameworks`` (config key ``sample.frameworks``; the flag wins), an addition beyond the reference: rank 0 cuts the FINISHED molecules
 into framework, ring systems, linkers and side chains on the device batch by batch (``moldiff_amd/framework.py``: this project's own
 definition, not RDKit's MurckoScaffold), keys the pieces with the canonical labelling and writes ``frameworks.npz`` (results and keys)
@@ -365,6 +373,27 @@ def add_relax_argument(ap):
     return ap
 
 
+def global3d_option(n_confs, seed, sample_cfg):
+    """how many conformers ``--global3d`` generates per finished molecule (0: off) and their seed: the command line (None = not given)
+    wins over the config's ``sample.global3d`` and ``sample.global3d_seed``; the seed defaults to 0"""
+    n = n_confs if n_confs is not None else sample_cfg.get('global3d')
+    seed = seed if seed is not None else sample_cfg.get('global3d_seed')
+    n, seed = int(n or 0), int(seed or 0)
+    if not 0 <= n <= 65535 or seed < 0:
+        raise ValueError(f'global3d must lie in 0 .. 65535 and its seed must not be negative, got {n} and {seed}')
+    return n, seed
+
+
+def add_global3d_argument(ap):
+    """``--global3d`` on a parser of ``build_parser``, whose own option set stays what it was"""
+    ap.add_argument('--global3d', type=int, default=None, metavar='N',
+                    help='generate N conformers of every finished molecule on the device (distance geometry, then the relaxation), take the best '
+                         'RMSD of each against the molecule and write global3d.npz, global3d.json and conformers.sdf; implies --hydrogens '
+                         '(overrides sample.global3d)')
+    ap.add_argument('--global3d_seed', type=int, default=None, help='seed of the starting coordinates (overrides sample.global3d_seed; 0)')
+    return ap
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, required=True)
@@ -466,7 +495,7 @@ def add_frameworks_argument(ap):
 
 
 def main(argv=None):
-    args = add_relax_argument(add_hydrogens_argument(add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser())))))))))).parse_args(argv)
+    args = add_global3d_argument(add_relax_argument(add_hydrogens_argument(add_conformers_argument(add_frameworks_argument(add_stereo_argument(add_canonical_argument(add_kekulize_argument(add_groups_argument(add_rings_argument(add_similarity_argument(build_parser()))))))))))).parse_args(argv)
     if args.accept is not None:
         accept_rule(args.accept)
     if args.largest_fragment is not None:
@@ -546,7 +575,8 @@ def main(argv=None):
         features.append(Feature(lambda gen: groups.groups_mols(gen, device, groups_set), groups, 'groups', empty=lambda: groups.empty(groups_set)))
     hydrogens_on, clash_tol = hydrogens_option(args.hydrogens, args.clash_tol, config.sample)
     relax_on, relax_iters, relax_gtol = relax_option(args.relax, args.relax_iters, args.relax_gtol, config.sample)
-    hydrogens_on = hydrogens_on or relax_on   # --relax implies --hydrogens
+    g3d_confs, g3d_seed = global3d_option(args.global3d, args.global3d_seed, config.sample)
+    hydrogens_on = hydrogens_on or relax_on or g3d_confs > 0   # --relax and --global3d imply --hydrogens
     kek_write = kekulize_option(args.kekulize, config.sample) or hydrogens_on   # --hydrogens implies --kekulize
     kek_active = kek_write or rule == 'kekule'
     if kek_active:
@@ -574,6 +604,13 @@ def main(argv=None):
         features.append(Feature(lambda gen: relax.relax_mols(gen, device, ff_tables, relax_iters, relax_gtol), relax, 'relax',
                                 after=lambda res: relax.write_sdf(os.path.join(log_dir, 'samples_relaxed.sdf'), pool['finished'],
                                                                   kek_held['kekule'], kek_held['hydrogens'], res)))
+    if g3d_confs:   # behind hydrogens: the joined Kekulé and hydrogen results are there when the conformers are written
+        from . import embed
+        g3d_tables = embed.relax.ForceFieldTables(Z, nbt)
+        features.append(Feature(lambda gen: embed.global3d_mols(gen, device, g3d_confs, g3d_seed, g3d_tables, mol_ids=[int(m['mol_id']) for m in gen]),
+                                embed, 'global3d', empty=lambda: embed.empty(g3d_confs),
+                                after=lambda res: embed.write_sdf(os.path.join(log_dir, 'conformers.sdf'), pool['finished'], kek_held['kekule'],
+                                                                  kek_held['hydrogens'], res)))
     stereo_on, flat_tol, bond_tol = stereo_option(args.stereo, args.stereo_flat_tol, args.stereo_bond_tol, config.sample)
     conformers_on, conformer_tol = conformers_option(args.conformers, args.conformer_tol, config.sample)
     if canonical_option(args.canonical, config.sample) or stereo_on or conformers_on:
