@@ -1144,7 +1144,7 @@ int mdx_mol_relax(int32_t B, const int32_t* atom_ptr, const int32_t* bond_ptr, c
  *   e = v v, g_a += -(((8 lb^2) v) / (q q))(x_a - x_b); e is added by the lower atom; then e += w4 (x4 x4), g_a4 += (2 w4) x4.  Sums over
  *   atoms as in mdx_mol_relax (butterfly, then ((w0 + w1) + w2) + w3), dot products ((x x' + y y') + z z') + w w'.  No atomics.
  *   MINIMISER: the L-BFGS of mdx_mol_relax (history 8, step cap max_step, 20 Armijo halvings with 1e-4, curvature test 1e-10) over the
- *   4 n_all coordinates, rms = sqrt(g.g / (4 n_all)) <= gtol; a second copy of that code.  Stage A with w4 = 0.1 and stage B with
+ *   4 n_all coordinates, rms = sqrt(g.g / (4 n_all)) <= gtol; the same code (csrc/mdx_lbfgs.h).  Stage A with w4 = 0.1 and stage B with
  *   w4 = 1.0 from A's end point, each with an empty history and at most max_iters iterations; then the fourth coordinate is dropped.
  *   ACCEPTANCE.  In 3D, d = sqrt((dx dx + dy dy) + dz dz): the largest of (d - ub) / ub for d > ub and (lb - d) / lb for d < lb over
  *   the 1-2 and 1-3 pairs and of (lb - d) / lb over the other pairs (1-4 pairs are not tested) must be <= viol_tol (convention 0.1);

@@ -4,10 +4,8 @@
 // RDKit's bounds matrix and unverified against it; include/moldiff_hip.h states it, moldiff_amd/embed.py (bounds_ref) restates it
 // operation by operation, and this file is built with -ffp-contract=off so that the float64 arithmetic is the restatement's.
 //
-// One workgroup of 256 threads per molecule over the compact arrays of mdx_mol.h, staged exactly as mdx_relax.hip stages them (bonds,
-// rows with the X-H bonds appended, sorted by neighbour, rest length per bond): that block below is A COPY of mdx_relax.hip's, kept
-// apart so that mdx_relax.hip stays byte for byte what its tests pinned; atom order and typing must stay identical in both, and the
-// bit-for-bit comparison of the bounds with the restatement (which stages through relax._stage) fails when they drift.  Thread a owns COLUMN a of the two matrices, the
+// One workgroup of 256 threads per molecule over the compact arrays of mdx_mol.h, staged by mdx_allatom.h as mdx_relax.hip stages them
+// (bonds, rows with the X-H bonds appended, sorted by neighbour, rest length per bond).  Thread a owns COLUMN a of the two matrices, the
 // entries [i][a] at i * na_cap + a: it writes the initial bounds of its pairs (both threads of a pair evaluate the same expression, the
 // path taken from its lower end atom, so the matrices are symmetric bit for bit) and smooths its own column, reading row k of step k
 // from LDS (row k = column k by symmetry, and step k leaves it unchanged).  No thread reads a global word another thread wrote.
@@ -16,12 +14,11 @@
 #include <stdint.h>
 
 #include "../../include/moldiff_hip.h"
-#include "mdx_mol.h"
+#include "mdx_allatom.h"
 #include "mdx_embed_args.h"
 
 namespace {
 
-constexpr int BD_BONDS = MOL_BONDS + MOL_ATOMS;
 enum { B_STATUS, B_NALL, B_N12, B_N13, B_N14, B_RING, B_TIGHT };
 static_assert(B_TIGHT + 1 == EB_STATS && EB_STATS == MDX_BOUNDS_STATS, "the columns of the table");
 
@@ -30,25 +27,14 @@ struct BdArgs {
   RelaxTable tab;
   BoundsParams p;
   BoundsOperands o;
-  int num_element, num_bond_types;
 };
 
-struct BdShared {
-  double br0[BD_BONDS];
-  double par[RX_MAX_TYPES][RX_NPAR];
+struct BdShared : AllAtomShared {
   double lrow[MOL_ATOMS], urow[MOL_ATOMS];
-  double ln_order[4];
   unsigned m12[8][MOL_ATOMS], m13[8][MOL_ATOMS], m14[8][MOL_ATOMS], tight[8][MOL_ATOMS];  // bit i of word [i >> 5][a]: the pair (i, a)
-  unsigned bond[BD_BONDS];
-  unsigned adj[2 * BD_BONDS];
-  int off[MOL_ATOMS + 1], cur[MOL_ATOMS], wave_total[4];
   int ired[4][8];
-  unsigned char typ[MOL_ATOMS], var[MOL_ATOMS], parent[MOL_ATOMS], arom[MOL_ATOMS];
-  unsigned char type_of[RX_MAX_ELEMENTS * 4];
 };
 
-__device__ inline int row_nbr(unsigned w) { return (int)(w >> 16); }
-__device__ inline int row_bond(unsigned w) { return (int)(w & 0xffffu); }
 __device__ inline bool has(const unsigned (*m)[MOL_ATOMS], int a, int i) { return (m[i >> 5][a] >> (i & 31)) & 1u; }
 __device__ inline void mark(unsigned (*m)[MOL_ATOMS], int a, int i) { m[i >> 5][a] |= 1u << (i & 31); }
 
@@ -83,87 +69,19 @@ __global__ __launch_bounds__(256) void mol_bounds_kernel(const BdArgs A) {
   __shared__ BdShared s;
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const MolView v = mol_view(A.mol, m);
-  const long long n0 = v.n0, h0 = v.h0;
-  const int n = v.n, nb = v.nb;
   if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
     write_unmeasured(A, m, unmeasured);
     return;
   }
-  const bool in = tid < n;
-  const int h = in ? min(max(A.o.h_count[n0 + tid], 0), RX_MAX_H) : 0;
-  s.cur[tid] = h;
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  const int hoff = s.off[tid], nH = s.off[MOL_ATOMS], n_all = n + nH;
-  __syncthreads();
-  const int cap = A.p.na_cap;
+  const AllAtomCount aa = allatom_count(A.o.h_count + v.n0, v.n, s.off, s.cur, s.wave_total);
+  const int n_all = aa.n_all, cap = A.p.na_cap;
   if (n_all > MOL_ATOMS || n_all > cap) {  // uniform
     write_unmeasured(A, m, EM_TOO_LARGE);
     return;
   }
-  // ---- the staged molecule: as mdx_relax.hip
-  {
-    s.arom[tid] = 0, s.parent[tid] = 0;
-    for (int q = tid; q < RX_MAX_TYPES * RX_NPAR; q += 256) s.par[q / RX_NPAR][q % RX_NPAR] = A.tab.par[q / RX_NPAR][q % RX_NPAR];
-    if (tid < RX_MAX_ELEMENTS * 4) s.type_of[tid] = A.tab.type_of[tid >> 2][tid & 3];
-    if (tid < 4) s.ln_order[tid] = A.tab.ln_order[tid];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) s.m12[c][tid] = 0u, s.m13[c][tid] = 0u, s.m14[c][tid] = 0u, s.tight[c][tid] = 0u;
-  }
-  __syncthreads();
-  if (in)
-    for (int k = 0; k < h; ++k) s.parent[n + hoff + k] = (unsigned char)tid;  // n + hoff + k < n_all <= 256
-  const int *bt = A.mol.bond_type + h0, *bo = A.o.order + h0;
-  const int nbt = A.num_bond_types;
-  const int deg_heavy = mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total, [&](int e, int i, int j) {
-    if (bt[e] == nbt) {
-      s.arom[i] = 1, s.arom[j] = 1;
-      return 1u;
-    }
-    const int o = min(max(bo[e], 1), 3);
-    return o == 1 ? 0u : (unsigned)o;
-  });
-  s.cur[tid] = in ? deg_heavy + h : tid < n_all ? 1 : 0;
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int e, unsigned) { return other << 16 | (unsigned)e; });
-  if (in) {
-    for (int k = 0; k < h; ++k) s.adj[s.off[tid] + deg_heavy + k] = (unsigned)(n + hoff + k) << 16 | (unsigned)(nb + hoff + k);
-  } else if (tid < n_all) {
-    const unsigned p = s.parent[tid];
-    s.adj[s.off[tid]] = p << 16 | (unsigned)(nb + tid - n);
-    s.bond[nb + tid - n] = mol_bond_word((int)p, tid, 0u);
-  }
-  if (in) {
-    const int cls = min(max(A.mol.atom_type[n0 + tid], 0), A.num_element - 1);
-    int var = A.o.atom_flag[n0 + tid] & 3;
-    var = s.arom[tid] ? RX_RESONANT : var == 3 ? RX_TETRAHEDRAL : var;
-    s.typ[tid] = (unsigned char)(s.type_of[4 * cls + var] & 0x7fu), s.var[tid] = (unsigned char)var;
-  } else {
-    s.typ[tid] = (unsigned char)A.tab.h_type, s.var[tid] = RX_HYDROGEN;
-  }
-  __syncthreads();
-  if (tid < n_all) {  // each thread sorts its own row by neighbour
-    const int r0 = s.off[tid], r1 = s.off[tid + 1];
-    for (int q = r0 + 1; q < r1; ++q) {
-      const unsigned x = s.adj[q];
-      int k = q - 1;
-      for (; k >= r0 && s.adj[k] > x; --k) s.adj[k + 1] = s.adj[k];
-      s.adj[k + 1] = x;
-    }
-  }
-  for (int e = tid; e < nb + nH; e += 256) {  // the rest length, the lower atom first
-    const unsigned w = s.bond[e];
-    double r0 = 0.0, k = 0.0;
-    if (w) {
-      const int i = mol_bond_i(w), j = mol_bond_j(w);
-      relax_pair(s.par[s.typ[min(i, j)]], s.par[s.typ[max(i, j)]], s.ln_order[mol_bond_payload(w) & 3u], &r0, &k);
-    }
-    s.br0[e] = r0;
-  }
-  __syncthreads();
+  for (int c = 0; c < 8; ++c) s.m12[c][tid] = 0u, s.m13[c][tid] = 0u, s.m14[c][tid] = 0u, s.tight[c][tid] = 0u;  // its own column
+  allatom_stage(s, A.mol, v, A.tab, A.o.order + v.h0, A.o.atom_flag + v.n0, aa, nullptr);
   const bool live = tid < n_all;
   const int r0 = s.off[tid], r1 = live ? s.off[tid + 1] : r0;
   for (int q = r0; q < r1; ++q) mark(s.m12, tid, row_nbr(s.adj[q]));
@@ -292,6 +210,5 @@ extern "C" int mdx_mol_bounds(int32_t B, const int32_t* atom_ptr, const int32_t*
   const char* why = "";
   if (relax_prepare(&a.tab, ff_rows, n_rows, num_element, num_bond_types, 1e-3, 1.0, 1.0, 0, &why) != RX_PREP_OK) return mdx_set_error(MDX_ERR_ARG, why);
   a.o = BoundsOperands{order, h_count, atom_flag, (double*)bounds_ws, (unsigned char*)bounds_ws + (size_t)B * 16u * (size_t)na_cap * (size_t)na_cap, mol_stats};
-  a.num_element = num_element, a.num_bond_types = num_bond_types;
   return mol_launch(mol_bounds_kernel, "mol_bounds_kernel", B, stream, a);
 }

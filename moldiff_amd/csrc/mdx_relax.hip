@@ -6,11 +6,11 @@
 // -ffp-contract=off so that the float64 arithmetic is the restatement's.
 //
 // One workgroup of 256 threads (4 waves) per molecule over the compact arrays of mdx_mol.h; thread a owns atom a of the all-atom
-// molecule (heavy atoms, then the hydrogens in (atom, k) order; at most 256 in all).  Staged once in LDS: the heavy bonds and their
-// degrees (mol_stage_bonds), then rows that also hold the X-H bonds (a second scan, mol_stage_rows, the hydrogens appended), every row
-// sorted by neighbour; the derived parameter rows, rest length and force constant per bond, and the 1-2 / 1-3 exclusions as a 256-bit
-// mask per atom, word-major so that the 64 lanes of a wave read 64 consecutive words.  Positions and the trial point are kept as three
-// arrays of 256 doubles each (a lane's own entry: consecutive 8-byte words, no bank conflict; a neighbour's entry: a gather).
+// molecule (heavy atoms, then the hydrogens in (atom, k) order; at most 256 in all).  Staged once in LDS: the molecule of
+// mdx_allatom.h (rows sorted by neighbour, the derived parameter rows, rest length and force constant per bond), and the 1-2 / 1-3
+// exclusions as a 256-bit mask per atom, word-major so that the 64 lanes of a wave read 64 consecutive words.  Positions and the trial
+// point are kept as three arrays of 256 doubles each (a lane's own entry: consecutive 8-byte words, no bank conflict; a neighbour's
+// entry: a gather).  The minimiser is mdx_lbfgs.h's; this file holds the terms, their evaluation and the outputs.
 //
 // DETERMINISM.  There is no floating-point atomic and no scatter: thread a GATHERS the gradient on atom a by walking every term atom a
 // takes part in, in the order the header states, so a term is evaluated by each of its atoms; the energy of a term is added by one
@@ -22,19 +22,15 @@
 #include <stdint.h>
 
 #include "../../include/moldiff_hip.h"
-#include "mdx_mol.h"
-#include "mdx_relax_args.h"
+#include "mdx_allatom.h"
+#include "mdx_lbfgs.h"
 
 namespace {
 
-constexpr int RX_BONDS = MOL_BONDS + MOL_ATOMS;  // the heavy bonds, then one X-H bond per hydrogen
-constexpr double RX_ARMIJO = 1e-4, RX_CURVATURE = 1e-10;
-constexpr int RX_TRIALS = 20;
 // the columns of mol_stats and mol_energy: MDX_RELAX_* of include/moldiff_hip.h
 enum { R_STATUS, R_REASON, R_ITERS, R_EVALS, R_NALL, R_BONDS, R_ANGLES, R_TORSIONS, R_INVERSIONS, R_PAIRS, R_FALLBACK };
 static_assert(R_FALLBACK + 1 == RX_STATS && RX_STATS == MDX_RELAX_STATS && RX_ENERGIES == MDX_RELAX_ENERGIES, "the columns of the tables");
 enum { STATUS_OK = 0, STATUS_TOO_LARGE = 1, STATUS_NONFINITE = 2 };
-enum { STOP_CONVERGED = 0, STOP_MAXITER = 1, STOP_LINESEARCH = 2 };
 enum { ANGLE_LINEAR = 0, ANGLE_TRIGONAL = 1, ANGLE_GENERAL = 2 };
 enum { TORSION_TT = 0, TORSION_PP = 1, TORSION_MIXED = 2 };
 
@@ -42,36 +38,25 @@ struct RxArgs {
   MolArrays mol;
   RelaxTable tab;
   RelaxOperands o;
-  int num_element, num_bond_types;
 };
 
-struct D3 {
-  double x, y, z;
-};
+using Pos3 = double[3][MOL_ATOMS];
 
-struct RxShared {
-  double x[3][MOL_ATOMS], xt[3][MOL_ATOMS];  // the point and the trial point
-  double g[3][MOL_ATOMS];                    // the final gradient: the parent writes out its hydrogens' (gradient, direction and the
-                                             // vectors of the recursion are a thread's own atom's and stay in its registers)
-  double br0[RX_BONDS], bk[RX_BONDS];        // rest length and force constant per bond
-  double par[RX_MAX_TYPES][RX_NPAR];
-  double red[4][8];
-  double ln_order[4], hsy[RX_HISTORY], hyy[RX_HISTORY], alpha[RX_HISTORY];
-  unsigned mask[8][MOL_ATOMS];               // bit b of word [b >> 5][a]: the pair (a, b) is excluded
-  unsigned bond[RX_BONDS];                   // the bond word of mdx_mol.h, payload = the order index (0: 1, 1: 1.5, 2: 2, 3: 3)
-  unsigned adj[2 * RX_BONDS];                // neighbour << 16 | bond: a row sorted by the word is sorted by neighbour
-  int off[MOL_ATOMS + 1], cur[MOL_ATOMS], wave_total[4];
+struct RxShared : AllAtomShared {
+  Pos3 x, xt;                   // the point and the trial point
+  Pos3 g;                       // the final gradient: the parent writes out its hydrogens' (gradient, direction and the vectors of
+                                // the recursion are a thread's own atom's and stay in its registers)
+  double bk[AA_BONDS];          // force constant per bond
+  double red[5][4];             // the wave totals of the five components
+  LbfgsShared lb;
+  unsigned mask[8][MOL_ATOMS];  // bit b of word [b >> 5][a]: the pair (a, b) is excluded
   int ired[4][8];
-  unsigned char typ[MOL_ATOMS], var[MOL_ATOMS], parent[MOL_ATOMS], arom[MOL_ATOMS];
-  unsigned char type_of[RX_MAX_ELEMENTS * 4];
 };
 
-__device__ inline D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ inline D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ inline D3 scaled(double f, D3 a) { return {f * a.x, f * a.y, f * a.z}; }
-__device__ inline D3 at(const double (*X)[MOL_ATOMS], int a) { return {X[0][a], X[1][a], X[2][a]}; }
-__device__ inline void put(double (*X)[MOL_ATOMS], int a, D3 v) { X[0][a] = v.x, X[1][a] = v.y, X[2][a] = v.z; }
+__device__ inline D3 add(D3 a, D3 b) {
+  return each<3>([&](int k) { return a[k] + b[k]; });
+}
+__device__ inline D3 cross(D3 a, D3 b) { return {{a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]}}; }
 
 // ---- the terms: the same operations in the same order as moldiff_amd/relax.py
 
@@ -105,8 +90,8 @@ __device__ inline void angle_term(D3 pi, D3 pj, D3 pk, double K, int kind, doubl
     e = K * ((c2 * ((2.0 * c0) * c0 + 1.0) + c1 * c) + c2 * ((2.0 * c) * c - 1.0)), de = K * (c1 + (4.0 * c2) * c);
   }
   const double fu = c / uu, fv = c / vv;
-  gi = {de * (v.x / luv - fu * u.x), de * (v.y / luv - fu * u.y), de * (v.z / luv - fu * u.z)};
-  gk = {de * (u.x / luv - fv * v.x), de * (u.y / luv - fv * v.y), de * (u.z / luv - fv * v.z)};
+  gi = each<3>([&](int x) { return de * (v[x] / luv - fu * u[x]); });
+  gk = each<3>([&](int x) { return de * (u[x] / luv - fv * v[x]); });
 }
 
 // -> false for a collinear triple; g0, g1: the gradients on p0 and p1
@@ -129,11 +114,11 @@ __device__ inline bool torsion_term(D3 p0, D3 p1, D3 p2, D3 p3, int kind, double
     e = hv * (1.0 - ((((32.0 * c4) * c2 - 48.0 * c4) + 18.0 * c2) - 1.0)), de = -(hv * (((192.0 * c4) * c - (192.0 * c2) * c) + 36.0 * c));
   }
   const double fa = c / aa, fb = c / bb;
-  const D3 tA = {B.x / lab - fa * A.x, B.y / lab - fa * A.y, B.z / lab - fa * A.z};
-  const D3 tB = {A.x / lab - fb * B.x, A.y / lab - fb * B.y, A.z / lab - fb * B.z};
+  const D3 tA = each<3>([&](int x) { return B[x] / lab - fa * A[x]; });
+  const D3 tB = each<3>([&](int x) { return A[x] / lab - fb * B[x]; });
   const D3 GA = cross(G, tA), AF = cross(tA, F), BH = cross(tB, H);
   g0 = scaled(de, GA);
-  g1 = {de * ((AF.x - GA.x) + BH.x), de * ((AF.y - GA.y) + BH.y), de * ((AF.z - GA.z) + BH.z)};
+  g1 = each<3>([&](int x) { return de * ((AF[x] - GA[x]) + BH[x]); });
   return true;
 }
 
@@ -150,8 +135,8 @@ __device__ inline bool inversion_term(D3 pj, D3 pi, D3 pk, D3 pl, double k3, dou
   e = k3 * (1.0 - sq);
   const double de = (k3 * y) / sq;
   const double fn = y / nn, fw = y / ww;
-  const D3 tn = {w.x / lnw - fn * n.x, w.y / lnw - fn * n.y, w.z / lnw - fn * n.z};
-  const D3 tw = {n.x / lnw - fw * w.x, n.y / lnw - fw * w.y, n.z / lnw - fw * w.z};
+  const D3 tn = each<3>([&](int x) { return w[x] / lnw - fn * n[x]; });
+  const D3 tw = each<3>([&](int x) { return n[x] / lnw - fw * w[x]; });
   gi = scaled(de, cross(v, tn)), gk = scaled(de, cross(tn, u)), gl = scaled(de, tw);
   return true;
 }
@@ -169,11 +154,9 @@ __device__ inline void vdw_term(D3 pa, D3 pb, double x2, double dij, double& e, 
 
 // ---- the staged molecule
 
-__device__ inline int row_nbr(unsigned w) { return (int)(w >> 16); }
-__device__ inline int row_bond(unsigned w) { return (int)(w & 0xffffu); }
 __device__ inline bool planar(int var) { return var == RX_TRIGONAL || var == RX_RESONANT; }
 
-__device__ inline void angle_at(const RxShared& s, const double (*X)[MOL_ATOMS], int i, int j, int k, int ei, int ek, double& e, D3& gi, D3& gk) {
+__device__ inline void angle_at(const RxShared& s, const Pos3& X, int i, int j, int k, int ei, int ek, double& e, D3& gi, D3& gk) {
   const double* pj = s.par[s.typ[j]];
   const double c0 = pj[RX_C0];
   const double K = angle_k(s.par[s.typ[i]][RX_Z], s.par[s.typ[k]][RX_Z], s.br0[ei], s.br0[ek], c0);
@@ -205,7 +188,7 @@ __device__ inline bool inverts(const RxShared& s, int j) {
 }
 
 // apex choice t of the inversion centred at j: -> false when it is skipped; wi, wk, wl: the atoms i, k and the apex
-__device__ inline bool inversion_at(const RxShared& s, const double (*X)[MOL_ATOMS], int j, int t, double deg_tol, int& wi, int& wk, int& wl, double& e, D3& gi, D3& gk,
+__device__ inline bool inversion_at(const RxShared& s, const Pos3& X, int j, int t, double deg_tol, int& wi, int& wk, int& wl, double& e, D3& gi, D3& gk,
                                     D3& gl) {
   const int r0 = s.off[j];
   const int n0 = row_nbr(s.adj[r0]), n1 = row_nbr(s.adj[r0 + 1]), n2 = row_nbr(s.adj[r0 + 2]);
@@ -214,8 +197,8 @@ __device__ inline bool inversion_at(const RxShared& s, const double (*X)[MOL_ATO
 }
 
 // The gradient on atom a and the energies this atom owns, at the point X.  e, cnt: bond, angle, torsion, inversion, van der Waals.
-__device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS], int a, int n_all, double deg_tol, D3& gout, double* e, int* cnt) {
-  D3 g = {0.0, 0.0, 0.0};
+__device__ inline void eval_atom(const RxShared& s, const Pos3& X, int a, int n_all, double deg_tol, D3& gout, double* e, int* cnt) {
+  D3 g = {};
 #pragma unroll
   for (int c = 0; c < 5; ++c) e[c] = 0.0, cnt[c] = 0;
   const int r0 = s.off[a], r1 = s.off[a + 1];
@@ -225,13 +208,13 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
   for (int q = r0; q < r1; ++q) {  // bonds
     const int b = row_nbr(s.adj[q]), eb = row_bond(s.adj[q]);
     bond_term(pa, at(X, b), s.br0[eb], s.bk[eb], en, ga);
-    g = {g.x + ga.x, g.y + ga.y, g.z + ga.z};
+    g = add(g, ga);
     if (a < b) e[0] = e[0] + en, ++cnt[0];
   }
   for (int q1 = r0; q1 < r1; ++q1)  // angles centred here
     for (int q2 = q1 + 1; q2 < r1; ++q2) {
       angle_at(s, X, row_nbr(s.adj[q1]), a, row_nbr(s.adj[q2]), row_bond(s.adj[q1]), row_bond(s.adj[q2]), en, ga, gb);
-      g = {g.x - (ga.x + gb.x), g.y - (ga.y + gb.y), g.z - (ga.z + gb.z)};
+      g = sub(g, add(ga, gb));
       e[1] = e[1] + en, ++cnt[1];
     }
   for (int q = r0; q < r1; ++q) {  // angles that end here
@@ -240,7 +223,7 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
       const int k = row_nbr(s.adj[p]);
       if (k == a) continue;
       angle_at(s, X, a, j, k, ej, row_bond(s.adj[p]), en, ga, gb);
-      g = {g.x + ga.x, g.y + ga.y, g.z + ga.z};
+      g = add(g, ga);
     }
   }
   for (int q = r0; q < r1; ++q) {  // torsions about a bond of this atom
@@ -257,7 +240,7 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
         const int l = row_nbr(s.adj[p]);
         if (l == a || l == i) continue;
         if (!torsion_term(pi, pa, pk, at(X, l), kind, vq, deg_tol, en, ga, gb)) continue;
-        g = {g.x + gb.x, g.y + gb.y, g.z + gb.z};
+        g = add(g, gb);
         if (a < k) e[2] = e[2] + en, ++cnt[2];
       }
     }
@@ -276,7 +259,7 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
         const int l = row_nbr(s.adj[p]);
         if (l == j || l == a) continue;
         if (!torsion_term(pa, pj, pk, at(X, l), kind, vq, deg_tol, en, ga, gb)) continue;
-        g = {g.x + ga.x, g.y + ga.y, g.z + ga.z};
+        g = add(g, ga);
       }
     }
   }
@@ -285,7 +268,7 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
   if (inverts(s, a))  // inversions centred here
     for (int t = 0; t < 3; ++t) {
       if (!inversion_at(s, X, a, t, deg_tol, wi, wk, wl, en, ga, gb, gc)) continue;
-      g = {g.x - ((ga.x + gb.x) + gc.x), g.y - ((ga.y + gb.y) + gc.y), g.z - ((ga.z + gb.z) + gc.z)};
+      g = sub(g, add(add(ga, gb), gc));
       e[3] = e[3] + en, ++cnt[3];
     }
   for (int q = r0; q < r1; ++q) {  // inversions of a neighbour
@@ -294,7 +277,7 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
     for (int t = 0; t < 3; ++t) {
       if (!inversion_at(s, X, j, t, deg_tol, wi, wk, wl, en, ga, gb, gc)) continue;
       const D3 mine = wi == a ? ga : wk == a ? gb : gc;
-      g = {g.x + mine.x, g.y + mine.y, g.z + mine.z};
+      g = add(g, mine);
     }
   }
   const double* qa = s.par[s.typ[a]];
@@ -305,49 +288,28 @@ __device__ inline void eval_atom(const RxShared& s, const double (*X)[MOL_ATOMS]
     if ((word >> (b & 31)) & 1u) continue;
     const double* qb = s.par[s.typ[b]];
     vdw_term(pa, at(X, b), xa * qb[RX_X], da * qb[RX_SQRT_D], en, ga);
-    g = {g.x + ga.x, g.y + ga.y, g.z + ga.z};
+    g = add(g, ga);
     if (a < b) e[4] = e[4] + en, ++cnt[4];
   }
   gout = g;
 }
 
-// the sum of one value per thread: a butterfly in each wave, then ((w0 + w1) + w2) + w3.  Two barriers.
-__device__ inline double block_sum(RxShared& s, double v) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double w = wave_sum(v);
-  if (lane == 0) s.red[wave][0] = w;
-  __syncthreads();
-  const double r = ((s.red[0][0] + s.red[1][0]) + s.red[2][0]) + s.red[3][0];
-  __syncthreads();
-  return r;
-}
-
-__device__ inline double block_max(RxShared& s, double v) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  if (lane == 0) s.red[wave][0] = v;
-  __syncthreads();
-  const double r = fmax(fmax(s.red[0][0], s.red[1][0]), fmax(s.red[2][0], s.red[3][0]));
-  __syncthreads();
-  return r;
-}
-
 // Energy and gradient at X: the gradient into g (this thread's atom), the five component sums into comp, -> the total
-__device__ inline double evaluate(RxShared& s, const double (*X)[MOL_ATOMS], int n_all, double deg_tol, D3& g, double* comp, int* cnt) {
+__device__ inline double evaluate(RxShared& s, const Pos3& X, int n_all, double deg_tol, D3& g, double* comp, int* cnt) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double e[5];
-  g = {0.0, 0.0, 0.0};
+  g = {};
 #pragma unroll
   for (int c = 0; c < 5; ++c) e[c] = 0.0, cnt[c] = 0;
   if (tid < n_all) eval_atom(s, X, tid, n_all, deg_tol, g, e, cnt);
 #pragma unroll
   for (int c = 0; c < 5; ++c) {
     const double w = wave_sum(e[c]);
-    if (lane == 0) s.red[wave][c] = w;
+    if (lane == 0) s.red[c][wave] = w;
   }
   __syncthreads();
 #pragma unroll
-  for (int c = 0; c < 5; ++c) comp[c] = ((s.red[0][c] + s.red[1][c]) + s.red[2][c]) + s.red[3][c];
+  for (int c = 0; c < 5; ++c) comp[c] = ((s.red[c][0] + s.red[c][1]) + s.red[c][2]) + s.red[c][3];
   __syncthreads();
   return (((comp[0] + comp[1]) + comp[2]) + comp[3]) + comp[4];
 }
@@ -369,97 +331,27 @@ __global__ __launch_bounds__(256) void mol_relax_kernel(const RxArgs A) {
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const MolView v = mol_view(A.mol, m);
   const long long n0 = v.n0, h0 = v.h0;
-  const int n = v.n, nb = v.nb;
+  const int n = v.n;
   if (const int unmeasured = mol_guard(v); unmeasured != MOL_MEASURE) {  // uniform
     write_unmeasured(A, m, unmeasured, v);
     return;
   }
   const bool in = tid < n;
-  const int h = in ? min(max(A.o.h_count[n0 + tid], 0), RX_MAX_H) : 0;
-
-  // ---- the hydrogens as atoms n .. n_all - 1 in (atom, k) order
-  s.cur[tid] = h;
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  const int hoff = s.off[tid], nH = s.off[MOL_ATOMS], n_all = n + nH;
-  __syncthreads();  // the offsets are read before the arrays are used again
+  const AllAtomCount aa = allatom_count(A.o.h_count + n0, n, s.off, s.cur, s.wave_total);
+  const int n_all = aa.n_all;
   if (n_all > MOL_ATOMS) {  // uniform
     write_unmeasured(A, m, STATUS_TOO_LARGE, v);
     return;
   }
   const double deg_tol = A.tab.deg_tol;
-  {
-    put(s.x, tid, D3{0.0, 0.0, 0.0});
-    s.arom[tid] = 0, s.parent[tid] = 0;
-    for (int q = tid; q < RX_MAX_TYPES * RX_NPAR; q += 256) s.par[q / RX_NPAR][q % RX_NPAR] = A.tab.par[q / RX_NPAR][q % RX_NPAR];
-    if (tid < RX_MAX_ELEMENTS * 4) s.type_of[tid] = A.tab.type_of[tid >> 2][tid & 3];
-    if (tid < 4) s.ln_order[tid] = A.tab.ln_order[tid];
-  }
-  __syncthreads();
-  if (in) {
+  if (tid >= n_all) put(s.x, tid, D3{});
+  if (in) {  // every entry of x has one writer; the barriers of the staging publish them
     const float* q = A.o.atom_pos + 3 * (n0 + tid);
-    put(s.x, tid, D3{(double)q[0], (double)q[1], (double)q[2]});
+    put(s.x, tid, D3{{(double)q[0], (double)q[1], (double)q[2]}});
     const double* hp = A.o.h_pos + 3 * RX_MAX_H * (n0 + tid);
-    for (int k = 0; k < h; ++k) {  // n + hoff + k < n_all <= 256
-      put(s.x, n + hoff + k, D3{hp[3 * k], hp[3 * k + 1], hp[3 * k + 2]});
-      s.parent[n + hoff + k] = (unsigned char)tid;
-    }
+    for (int k = 0; k < aa.h; ++k) put(s.x, n + aa.hoff + k, D3{{hp[3 * k], hp[3 * k + 1], hp[3 * k + 2]}});  // n + hoff + k < n_all <= 256
   }
-  const int *bt = A.mol.bond_type + h0, *bo = A.o.order + h0;
-  const int nbt = A.num_bond_types;
-  const int deg_heavy = mol_stage_bonds(A.mol, h0, n, nb, s.bond, s.off, s.cur, s.wave_total, [&](int e, int i, int j) {
-    if (bt[e] == nbt) {
-      s.arom[i] = 1, s.arom[j] = 1;
-      return 1u;
-    }
-    const int o = min(max(bo[e], 1), 3);
-    return o == 1 ? 0u : (unsigned)o;
-  });
-  // the rows of the all-atom molecule: the heavy neighbours, then the atom's own hydrogens; a hydrogen's row is its parent
-  s.cur[tid] = in ? deg_heavy + h : tid < n_all ? 1 : 0;
-  __syncthreads();
-  block_exclusive_scan_256(s.off, s.cur, s.wave_total);
-  __syncthreads();
-  mol_stage_rows(nb, s.bond, s.cur, s.adj, [](unsigned other, int e, unsigned) { return other << 16 | (unsigned)e; });
-  if (in) {
-    for (int k = 0; k < h; ++k) s.adj[s.off[tid] + deg_heavy + k] = (unsigned)(n + hoff + k) << 16 | (unsigned)(nb + hoff + k);
-  } else if (tid < n_all) {
-    const unsigned p = s.parent[tid];
-    s.adj[s.off[tid]] = p << 16 | (unsigned)(nb + tid - n);
-    s.bond[nb + tid - n] = mol_bond_word((int)p, tid, 0u);
-  }
-  int fallback = 0;
-  if (in) {
-    const int cls = min(max(A.mol.atom_type[n0 + tid], 0), A.num_element - 1);
-    int var = A.o.atom_flag[n0 + tid] & 3;
-    var = s.arom[tid] ? RX_RESONANT : var == 3 ? RX_TETRAHEDRAL : var;
-    const unsigned code = s.type_of[4 * cls + var];
-    s.typ[tid] = (unsigned char)(code & 0x7fu), s.var[tid] = (unsigned char)var;
-    fallback = (code & RX_FALLBACK) != 0;
-  } else {
-    s.typ[tid] = (unsigned char)A.tab.h_type, s.var[tid] = RX_HYDROGEN;
-  }
-  __syncthreads();
-  if (tid < n_all) {  // the rows arrive in any order: insertion sort by the word, the neighbour in its high bits, each thread its own row
-    const int r0 = s.off[tid], r1 = s.off[tid + 1];
-    for (int q = r0 + 1; q < r1; ++q) {
-      const unsigned x = s.adj[q];
-      int k = q - 1;
-      for (; k >= r0 && s.adj[k] > x; --k) s.adj[k + 1] = s.adj[k];
-      s.adj[k + 1] = x;
-    }
-  }
-  for (int e = tid; e < nb + nH; e += 256) {  // rest length and force constant, the lower atom first
-    const unsigned w = s.bond[e];
-    double r0 = 0.0, k = 0.0;
-    if (w) {
-      const int i = mol_bond_i(w), j = mol_bond_j(w);
-      relax_pair(s.par[s.typ[min(i, j)]], s.par[s.typ[max(i, j)]], s.ln_order[mol_bond_payload(w) & 3u], &r0, &k);
-    }
-    s.br0[e] = r0, s.bk[e] = k;
-  }
-  __syncthreads();
+  const int fallback = allatom_stage(s, A.mol, v, A.tab, A.o.order + h0, A.o.atom_flag + n0, aa, s.bk);
   {  // the excluded pairs of this atom: itself, its neighbours and theirs
     unsigned w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     auto mark = [&](int b) {
@@ -479,119 +371,41 @@ __global__ __launch_bounds__(256) void mol_relax_kernel(const RxArgs A) {
   }
   __syncthreads();
 
-  // ---- the starting point
-  double comp0[5], comp[5];
+  // ---- the starting point, then the minimiser
+  double comp0[5], comp[5], compt[5];
   int cnt0[5], cnt[5];
-  D3 g;
-  double E = evaluate(s, s.x, n_all, deg_tol, g, comp0, cnt0);
-  int evals = 1;
-  double gg = block_sum(s, dot(g, g));
-  if (!isfinite(E) || !isfinite(gg)) {  // uniform
+  D3 g0;
+  const double E0 = evaluate(s, s.x, n_all, deg_tol, g0, comp0, cnt0);
+  const double gg0 = block_sum(s.lb, dot(g0, g0));
+  if (!isfinite(E0) || !isfinite(gg0)) {  // uniform
     write_unmeasured(A, m, STATUS_NONFINITE, v);
     return;
   }
 #pragma unroll
   for (int c = 0; c < 5; ++c) comp[c] = comp0[c];
-  const double E0 = E;
   double* hist = A.o.ws + (size_t)m * RX_WS_DOUBLES + tid;  // slot q: s at hist[(2 q) * 768 + c * 256], y at hist[(2 q + 1) * 768 + c * 256]
-  auto hget = [&](int q, int which) { return D3{hist[(2 * q + which) * 768], hist[(2 * q + which) * 768 + 256], hist[(2 * q + which) * 768 + 512]}; };
-  auto hput = [&](int q, int which, D3 u) { hist[(2 * q + which) * 768] = u.x, hist[(2 * q + which) * 768 + 256] = u.y, hist[(2 * q + which) * 768 + 512] = u.z; };
-  const bool live = tid < n_all;
-  const double gtol = A.tab.gtol, max_step = A.tab.max_step;
-  const int max_iters = A.tab.max_iters;
-  int hc = 0, head = 0;  // the history holds slots head .. head + hc - 1 (mod 8), oldest first
-  int iters = 0, reason = STOP_CONVERGED;
-  double rms = 0.0;
-  for (;;) {
-    rms = n_all ? sqrt(gg / (3.0 * (double)n_all)) : 0.0;
-    if (rms <= gtol) {
-      reason = STOP_CONVERGED;
-      break;
-    }
-    if (iters >= max_iters) {
-      reason = STOP_MAXITER;
-      break;
-    }
-    D3 d = {-g.x, -g.y, -g.z};
-    if (hc > 0) {  // the two-loop recursion
-      D3 q = g;
-      for (int t = hc - 1; t >= 0; --t) {
-        const int slot = (head + t) & (RX_HISTORY - 1);
-        const D3 sv = hget(slot, 0), yv = hget(slot, 1);
-        const double al = block_sum(s, live ? dot(sv, q) : 0.0) / s.hsy[slot];
-        s.alpha[slot] = al;  // every thread stores the same value and reads its own store
-        q = {q.x - al * yv.x, q.y - al * yv.y, q.z - al * yv.z};
-      }
-      const int newest = (head + hc - 1) & (RX_HISTORY - 1);
-      const double gamma = s.hsy[newest] / s.hyy[newest];
-      D3 r = scaled(gamma, q);
-      for (int t = 0; t < hc; ++t) {
-        const int slot = (head + t) & (RX_HISTORY - 1);
-        const D3 sv = hget(slot, 0), yv = hget(slot, 1);
-        const double co = s.alpha[slot] - block_sum(s, live ? dot(yv, r) : 0.0) / s.hsy[slot];
-        r = {r.x + co * sv.x, r.y + co * sv.y, r.z + co * sv.z};
-      }
-      const D3 dl = {-r.x, -r.y, -r.z};
-      const double gd = block_sum(s, live ? dot(g, dl) : 0.0);
-      if (gd < 0.0) d = dl;
-      else hc = 0;
-    }
-    bool accepted = false;
-    D3 gt = g, xo = at(s.x, tid), xn = xo;
-    double Et = E, compt[5];
-    for (;;) {
-      const double big = sqrt(block_max(s, live ? dot(d, d) : 0.0));
-      if (big > max_step) d = scaled(max_step / big, d);
-      const double gd = block_sum(s, live ? dot(g, d) : 0.0);
-      double t = 1.0;
-      for (int trial = 0; trial < RX_TRIALS; ++trial) {
-        xn = {xo.x + t * d.x, xo.y + t * d.y, xo.z + t * d.z};
-        put(s.xt, tid, xn);
-        __syncthreads();
-        Et = evaluate(s, s.xt, n_all, deg_tol, gt, compt, cnt);
-        ++evals;
-        if (isfinite(Et) && Et <= E + (RX_ARMIJO * t) * gd) {
-          accepted = true;
-          break;
-        }
-        t = t * 0.5;
-      }
-      if (accepted || hc == 0) break;
-      hc = 0;
-      d = {-g.x, -g.y, -g.z};
-    }
-    if (!accepted) {
-      reason = STOP_LINESEARCH;
-      break;
-    }
-    const D3 sv = sub(xn, xo), yv = sub(gt, g);
-    const double sy = block_sum(s, live ? dot(sv, yv) : 0.0), ss = block_sum(s, live ? dot(sv, sv) : 0.0), yy = block_sum(s, live ? dot(yv, yv) : 0.0);
-    if (sy > RX_CURVATURE * sqrt(ss * yy)) {
-      int slot;
-      if (hc == RX_HISTORY) slot = head, head = (head + 1) & (RX_HISTORY - 1);
-      else slot = (head + hc) & (RX_HISTORY - 1), ++hc;
-      hput(slot, 0, sv), hput(slot, 1, yv);
-      s.hsy[slot] = sy, s.hyy[slot] = yy;
-    }
-    put(s.x, tid, xn);  // nobody reads x before the barriers of the next sum
-    g = gt, E = Et;
+  const Lbfgs<3> r = lbfgs_minimise(
+      s.lb, s.x, s.xt, n_all, A.tab.gtol, A.tab.max_step, A.tab.max_iters, E0, g0, gg0,
+      [&](const Pos3& P, D3& gp) { return evaluate(s, P, n_all, deg_tol, gp, compt, cnt); },
+      [&] {
 #pragma unroll
-    for (int c = 0; c < 5; ++c) comp[c] = compt[c];
-    ++iters;
-    gg = block_sum(s, dot(g, g));
-  }
+        for (int c = 0; c < 5; ++c) comp[c] = compt[c];
+      },
+      [&](int q, int which) { return each<3>([&](int k) { return hist[(2 * q + which) * 768 + k * 256]; }); },
+      [&](int q, int which, D3 u) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) hist[(2 * q + which) * 768 + k * 256] = u[k];
+      });
 
   // ---- the outputs
-  put(s.g, tid, g);
+  put(s.g, tid, r.g);
   double moved = 0.0;
-  D3 first = {0.0, 0.0, 0.0};
   if (in) {
     const float* q = A.o.atom_pos + 3 * (n0 + tid);
-    first = {(double)q[0], (double)q[1], (double)q[2]};
-    const D3 dx = sub(at(s.x, tid), first);
+    const D3 dx = sub(at(s.x, tid), D3{{(double)q[0], (double)q[1], (double)q[2]}});
     moved = dot(dx, dx);
   }
-  moved = block_sum(s, moved);  // its barriers also publish x and g
+  moved = block_sum(s.lb, moved);  // its barriers also publish x and g
   const int counted[6] = {cnt0[0], cnt0[1], cnt0[2], cnt0[3], cnt0[4], fallback};  // R_BONDS .. R_FALLBACK
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
@@ -601,24 +415,15 @@ __global__ __launch_bounds__(256) void mol_relax_kernel(const RxArgs A) {
   __syncthreads();
   if (tid < 6) A.o.mol_stats[(size_t)m * RX_STATS + R_BONDS + tid] = (s.ired[0][tid] + s.ired[1][tid]) + (s.ired[2][tid] + s.ired[3][tid]);
   if (in) {
-    const D3 px = at(s.x, tid), pg = at(s.g, tid);
-    double *po = A.o.pos_out + 3 * (n0 + tid), *go = A.o.grad_out + 3 * (n0 + tid);
-    po[0] = px.x, po[1] = px.y, po[2] = px.z, go[0] = pg.x, go[1] = pg.y, go[2] = pg.z;
-    double *ho = A.o.h_pos_out + 3 * RX_MAX_H * (n0 + tid), *hg = A.o.h_grad_out + 3 * RX_MAX_H * (n0 + tid);
-    for (int k = 0; k < RX_MAX_H; ++k) {
-      const bool there = k < h;
-      const int b = there ? n + hoff + k : 0;
-      const D3 qx = at(s.x, b), qg = at(s.g, b);
-      ho[3 * k] = there ? qx.x : 0.0, ho[3 * k + 1] = there ? qx.y : 0.0, ho[3 * k + 2] = there ? qx.z : 0.0;
-      hg[3 * k] = there ? qg.x : 0.0, hg[3 * k + 1] = there ? qg.y : 0.0, hg[3 * k + 2] = there ? qg.z : 0.0;
-    }
+    allatom_write(s.x, n, aa, A.o.pos_out + 3 * (n0 + tid), A.o.h_pos_out + 3 * RX_MAX_H * (n0 + tid));
+    allatom_write(s.g, n, aa, A.o.grad_out + 3 * (n0 + tid), A.o.h_grad_out + 3 * RX_MAX_H * (n0 + tid));
   }
   if (tid == 0) {
     int* st = A.o.mol_stats + (size_t)m * RX_STATS;
-    st[R_STATUS] = STATUS_OK, st[R_REASON] = reason, st[R_ITERS] = iters, st[R_EVALS] = evals, st[R_NALL] = n_all;
+    st[R_STATUS] = STATUS_OK, st[R_REASON] = r.reason, st[R_ITERS] = r.iters, st[R_EVALS] = 1 + r.evals, st[R_NALL] = n_all;
     double* en = A.o.mol_energy + (size_t)m * RX_ENERGIES;
     for (int c = 0; c < 5; ++c) en[c] = comp0[c], en[6 + c] = comp[c];
-    en[5] = E0, en[11] = E, en[12] = rms, en[13] = n ? sqrt(moved / (double)n) : 0.0;
+    en[5] = E0, en[11] = r.E, en[12] = r.rms, en[13] = n ? sqrt(moved / (double)n) : 0.0;
   }
 }
 
@@ -638,6 +443,5 @@ extern "C" int mdx_mol_relax(int32_t B, const int32_t* atom_ptr, const int32_t* 
   const char* why = "";
   if (relax_prepare(&a.tab, ff_rows, n_rows, num_element, num_bond_types, deg_tol, gtol, max_step, max_iters, &why) != RX_PREP_OK)
     return mdx_set_error(MDX_ERR_ARG, why);
-  a.num_element = num_element, a.num_bond_types = num_bond_types;
   return mol_launch(mol_relax_kernel, "mol_relax_kernel", B, stream, a);
 }

@@ -33,7 +33,7 @@ struct RelaxTable {
   double ln_order[4];                         // ln 1, ln 1.5, ln 2, ln 3: the order index of a bond
   double deg_tol, gtol, max_step;
   unsigned char type_of[RX_MAX_ELEMENTS][4];  // row of (class, variant) | RX_FALLBACK when it is the class's tetrahedral row instead
-  int32_t h_type, n_types, max_iters;
+  int32_t h_type, n_types, max_iters, num_element, num_bond_types;
 };
 
 // the caller's device operands beside the compact arrays: what is read, then what is written
@@ -116,5 +116,6 @@ inline int relax_prepare(RelaxTable* t, const double* rows, int32_t n_rows, int3
   }
   t->ln_order[0] = 0.0, t->ln_order[1] = log(1.5), t->ln_order[2] = log(2.0), t->ln_order[3] = log(3.0);
   t->deg_tol = deg_tol, t->gtol = gtol, t->max_step = max_step, t->max_iters = max_iters, t->n_types = n_rows;
+  t->num_element = num_element, t->num_bond_types = num_bond_types;
   return RX_PREP_OK;
 }

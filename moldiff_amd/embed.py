@@ -38,8 +38,7 @@ DEFAULT_GTOL = 1e-3                                                # rms gradien
 DEFAULT_MAX_STEP = 1.0                                             # Angstrom
 DEFAULT_N_CONFS = 10
 FAR, BOX, W4_A, W4_B = 1000.0, 2.0, 0.1, 1.0
-HISTORY, MAX_TRIALS, ARMIJO, CURVATURE = relax.HISTORY, relax.MAX_TRIALS, relax.ARMIJO, relax.CURVATURE
-HIST_PER_ATOM = 2 * HISTORY * 4
+HIST_PER_ATOM = 2 * relax.HISTORY * 4
 STATUS_OK, STATUS_TOO_LARGE, STATUS_NONFINITE, STATUS_INCONSISTENT, STATUS_FAILED = 0, 1, 2, 3, 4
 OTHER, P12, P13, P14 = 0, 1, 2, 3
 BOUNDS_KEYS = ('status', 'n_all', 'n_12', 'n_13', 'n_14', 'n_ring_angles', 'n_tightened')
@@ -229,13 +228,6 @@ def error_ref(X, L, U, w4):
     return block_sum(e.tolist()), g, e
 
 
-def _vdot(a, b):
-    """per-thread ((x x' + y y') + z z') + w w', then the device's block sum"""
-    if not len(a):
-        return 0.0
-    return block_sum((((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]) + a[:, 3] * b[:, 3]).tolist())
-
-
 def violation_ref(pos, bounds):
     """the largest relative violation in 3D of the 1-2 and 1-3 bounds and of the other pairs' lower bounds; pos: (n_all, 3)"""
     L, U, cls = bounds['lower'], bounds['upper'], bounds['cls']
@@ -252,87 +244,6 @@ def violation_ref(pos, bounds):
             elif cls[b, a] != OTHER and d[b] > U[b, a]:
                 worst = max(worst, (d[b] - U[b, a]) / U[b, a])
     return float(worst)
-
-
-def _minimise(x, L, U, w4, max_iters, gtol, max_step, trace, energies):
-    """the L-BFGS of ``relax.relax_ref`` over four coordinates -> (x, E, iterations, evaluations), or None when the start is not finite"""
-    na = len(x)
-    E, g, _ = error_ref(x, L, U, w4)
-    n_evals = 1
-    if not math.isfinite(E) or not math.isfinite(_vdot(g, g)):
-        return None
-    hist, iters = [], 0
-    while True:
-        gg = _vdot(g, g)
-        rms = math.sqrt(gg / (4.0 * na)) if na else 0.0
-        trace.append(('rms', rms, gtol))
-        if rms <= gtol or iters >= max_iters:
-            break
-        if hist:
-            q, alphas = g, []
-            for s, y, sy, _ in reversed(hist):
-                al = _vdot(s, q) / sy
-                alphas.append(al)
-                q = q - al * y
-            gamma = hist[-1][2] / hist[-1][3]
-            r = gamma * q
-            for (s, y, sy, _), al in zip(hist, reversed(alphas)):
-                co = al - _vdot(y, r) / sy
-                r = r + co * s
-            d = -r
-            gd = _vdot(g, d)
-            trace.append(('descent', gd, 0.0))
-            if not gd < 0.0:
-                hist = []
-        if not hist:
-            d = -g
-        accepted = None
-        while True:
-            big = relax._sqrt(block_max((((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) + d[:, 3] * d[:, 3]).tolist()))
-            trace.append(('cap', big, max_step))
-            if big > max_step:
-                d = (max_step / big) * d
-            gd = _vdot(g, d)
-            t = 1.0
-            for _ in range(MAX_TRIALS):
-                xt = x + t * d
-                Et, gt, _ = error_ref(xt, L, U, w4)
-                n_evals += 1
-                bound = E + (ARMIJO * t) * gd
-                if math.isfinite(Et):
-                    trace.append(('armijo', Et, bound))
-                if math.isfinite(Et) and Et <= bound:
-                    accepted = (Et, gt)
-                    break
-                t = t * 0.5
-            if accepted is not None or not hist:
-                break
-            hist = []
-            d = -g
-        if accepted is None:
-            break
-        s, y = xt - x, accepted[1] - g
-        sy, ss, yy = _vdot(s, y), _vdot(s, s), _vdot(y, y)
-        lim = CURVATURE * relax._sqrt(ss * yy)
-        trace.append(('curvature', sy, lim))
-        if sy > lim:
-            hist = (hist + [(s, y, sy, yy)])[-HISTORY:]
-        x, E, g = xt, accepted[0], accepted[1]
-        iters += 1
-        energies.append(E)
-    return x, E, iters, n_evals
-
-
-def _split(n, h, x3):
-    """(n_all, 3) of the all-atom molecule -> (n, 3) heavy and (n, 4, 3) hydrogen arrays"""
-    heavy = np.asarray(x3[:n], dtype=np.float64).reshape(n, 3)
-    hs = np.zeros((n, MAX_H, 3))
-    at = n
-    for a in range(n):
-        for k in range(h[a]):
-            hs[a, k] = x3[at]
-            at += 1
-    return heavy, hs
 
 
 def allatom(pos, h_pos, h):
@@ -360,29 +271,30 @@ def embed_ref(bounds, conf=0, seed=0, mol_id=0, max_iters=DEFAULT_MAX_ITERS, max
         x = start_coords(na, box, seed, mol_id, conf, attempt)
         errors, iters, err = [], [0, 0], [0.0, 0.0]
         for stage, w4 in enumerate((W4_A, W4_B)):
-            r = _minimise(x, L, U, w4, max_iters, gtol, max_step, trace, errors)
+            r = relax.lbfgs_ref(x, lambda p: error_ref(p, L, U, w4), max_iters, gtol, max_step, trace)
             if r is None:
                 return dict(zero, status=STATUS_NONFINITE)
-            x, err[stage], iters[stage] = r[0], r[1], r[2]
-            n_evals += r[3]
+            x, err[stage], iters[stage] = r['x'], r['energy'], r['iterations']
+            n_evals += r['n_evals']
+            errors += r['energies']
         viol = violation_ref(x[:, :3], bounds)
         trace.append(('violation', viol, viol_tol))
         if viol <= viol_tol:
             status = STATUS_OK
             break
-    heavy, hs = _split(n, h, x[:, :3])
+    heavy, hs = relax._split(n, h, x[:, :3])
     return dict(status=status, attempts=attempt + 1, iterations_a=iters[0], iterations_b=iters[1], n_evals=n_evals, error_a=err[0], error_b=err[1],
                 max_violation=viol, pos=heavy, h_pos=hs, errors=errors)
 
 
 def near_threshold(bounds, conf=0, seed=0, mol_id=0, max_iters=DEFAULT_MAX_ITERS, max_attempts=DEFAULT_MAX_ATTEMPTS, gtol=DEFAULT_GTOL,
                    max_step=DEFAULT_MAX_STEP, viol_tol=DEFAULT_VIOL_TOL, band=1e-9, trace=None):
-    """whether some decision of ``embed_ref`` lies within `band` (relative, or absolute against a threshold of 0) of its threshold: the
-    conformers a device comparison may leave out.  trace: the decision trace to judge instead of running ``embed_ref``."""
+    """whether some decision of ``embed_ref`` is ``relax.near`` its threshold: the conformers a device comparison may leave out.
+    trace: the decision trace to judge instead of running ``embed_ref``."""
     if trace is None:
         trace = []
         embed_ref(bounds, conf, seed, mol_id, max_iters, max_attempts, gtol, max_step, viol_tol, trace)
-    return any(math.isfinite(v) and abs(v - th) <= band * max(abs(v), abs(th), 1e-300 if th else 1.0) for _, v, th in trace)
+    return relax.near(trace, band)
 
 
 def stack_ref(mols, n_confs=DEFAULT_N_CONFS, seed=0, inputs=None, tables=None, mol_ids=None, max_iters=DEFAULT_MAX_ITERS,

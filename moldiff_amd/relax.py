@@ -4,7 +4,8 @@ UFF-form force field by L-BFGS, and the energy it loses (the strain) and the dis
 The device half is ``mdx_mol_relax`` (csrc/mdx_relax.hip), reached through ``relax_mols`` (a list of molecule dicts; runs ``kekule`` and
 ``hydrogens`` first), ``launch`` (a ``CompactMols`` with positions and the device arrays of ``hydrogens.launch``) and
 ``FeaturizeMol.relax_batch`` (the sampler's predictions).  ``energy_ref`` and ``relax_ref`` are the plain restatement for one molecule
-in Python floats, in the device's own order of operations and reduction tree, and need no GPU.
+in float64 (the terms in Python floats, the minimiser ``lbfgs_ref``, which ``embed.embed_ref`` shares, in element-wise numpy rows), in
+the device's own order of operations and reduction tree, and need no GPU.
 
 What it is: THIS PROJECT'S OWN MODEL, stated exactly in include/moldiff_hip.h: UFF's functional forms (harmonic bonds, cosine angle
 terms, cosine torsions, inversions, 12-6 van der Waals without cutoff, no electrostatics) over a small parameter table
@@ -282,9 +283,121 @@ def block_sum(vals):
     return ((w[0] + w[1]) + w[2]) + w[3]
 
 
+def _rowdot(a, b):
+    """one value per thread of two (atoms, D) arrays: (x x' + y y') + z z', then + w w' -> list"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if not len(a):
+        return []
+    p = a[:, 0] * b[:, 0]
+    for c in range(1, a.shape[1]):
+        p = p + a[:, c] * b[:, c]
+    return p.tolist()
+
+
 def _vdot(a, b):
-    """the dot product of two per-atom vector lists: per-thread (x x' + y y') + z z', then block_sum"""
-    return block_sum([_dot(p, q) for p, q in zip(a, b)])
+    """the dot product of two (atoms, D) arrays: ``_rowdot`` per thread, then block_sum"""
+    return block_sum(_rowdot(a, b))
+
+
+# ---- the minimiser of relax_ref and embed.embed_ref: csrc/mdx_lbfgs.h -----------------------------------------------------------------
+
+@np.errstate(all='ignore')
+def lbfgs_ref(x, evaluate, max_iters, gtol, max_step, trace):
+    """The L-BFGS of csrc/mdx_lbfgs.h from the point x, (atoms, D) float64, in element-wise float64 operations over the atoms (the
+    device's thread per atom) and the device's block sums.  evaluate(x) -> (energy, gradient (atoms, D), whatever else the caller wants
+    of that point).  trace receives every number a decision compares with a threshold as (kind, value, threshold): 'rms', 'descent',
+    'cap', 'armijo' (value = trial energy, threshold = the bound), 'curvature'.  -> None when the energy or gradient at x is not finite,
+    else dict: ``x``, ``energy``, ``grad``, ``extra`` at the last accepted point, ``first`` (the extra at x), ``rms``, ``iterations``,
+    ``n_evals``, ``stop_reason`` and ``energies``, the accepted energy after every iteration."""
+    x = np.asarray(x, dtype=np.float64)
+    na, D = x.shape
+    E, g, extra = evaluate(x)
+    first, n_evals = extra, 1
+    if not math.isfinite(E) or not math.isfinite(_vdot(g, g)):
+        return None
+    hist, iters, energies = [], 0, []                                  # hist: (s, y, s.y, y.y), oldest first
+    while True:
+        gg = _vdot(g, g)
+        rms = math.sqrt(gg / (float(D) * na)) if na else 0.0
+        trace.append(('rms', rms, gtol))
+        if rms <= gtol:
+            reason = STOP_CONVERGED
+            break
+        if iters >= max_iters:
+            reason = STOP_MAXITER
+            break
+        if hist:
+            q, alphas = g, []
+            for s, y, sy, _ in reversed(hist):
+                al = _vdot(s, q) / sy
+                alphas.append(al)
+                q = q - al * y
+            gamma = hist[-1][2] / hist[-1][3]
+            r = gamma * q
+            for (s, y, sy, _), al in zip(hist, reversed(alphas)):
+                co = al - _vdot(y, r) / sy
+                r = r + co * s
+            d = -r
+            gd = _vdot(g, d)
+            trace.append(('descent', gd, 0.0))
+            if not gd < 0.0:
+                hist = []
+        if not hist:
+            d = -g
+        accepted = None
+        while True:
+            big = _sqrt(block_max(_rowdot(d, d)))
+            trace.append(('cap', big, max_step))
+            if big > max_step:
+                d = (max_step / big) * d
+            gd = _vdot(g, d)
+            t = 1.0
+            for _ in range(MAX_TRIALS):
+                xt = x + t * d
+                new = evaluate(xt)
+                n_evals += 1
+                bound = E + (ARMIJO * t) * gd
+                if math.isfinite(new[0]):
+                    trace.append(('armijo', new[0], bound))
+                if math.isfinite(new[0]) and new[0] <= bound:
+                    accepted = new
+                    break
+                t = t * 0.5
+            if accepted is not None or not hist:
+                break
+            hist = []
+            d = -g
+        if accepted is None:
+            reason = STOP_LINESEARCH
+            break
+        s, y = xt - x, accepted[1] - g
+        sy, ss, yy = _vdot(s, y), _vdot(s, s), _vdot(y, y)
+        lim = CURVATURE * _sqrt(ss * yy)
+        trace.append(('curvature', sy, lim))
+        if sy > lim:
+            hist = (hist + [(s, y, sy, yy)])[-HISTORY:]
+        x, (E, g, extra) = xt, accepted
+        iters += 1
+        energies.append(E)
+    return dict(x=x, energy=E, grad=g, extra=extra, first=first, rms=rms, iterations=iters, n_evals=n_evals, stop_reason=reason, energies=energies)
+
+
+def near(trace, band=1e-9):
+    """whether some decision of a trace lies within `band` (relative to the larger of the two magnitudes, or absolute against a
+    threshold of 0) of its threshold: what a device comparison may leave out, because float64 rounding may differ"""
+    return any(math.isfinite(v) and abs(v - th) <= band * max(abs(v), abs(th), 1e-300 if th else 1.0) for _, v, th in trace)
+
+
+def _split(n, h, vecs):
+    """(n_all, 3) of the all-atom molecule -> (n, 3) heavy and (n, 4, 3) hydrogen arrays"""
+    heavy = np.asarray(vecs[:n], dtype=np.float64).reshape(n, 3)
+    hs = np.zeros((n, MAX_H, 3), dtype=np.float64)
+    at = n
+    for a in range(n):
+        for k in range(h[a]):
+            hs[a, k] = vecs[at]
+            at += 1
+    return heavy, hs
 
 
 # ---- the all-atom molecule -------------------------------------------------------------------------------------------------------------
@@ -506,25 +619,9 @@ def energy_ref(info, order, h_count, h_pos, atom_flag, tables=None, deg_tol=DEFA
     return out
 
 
-def _finite(x):
-    return math.isfinite(x)
-
-
-def _split(m, vecs):
-    """per-atom vectors of the all-atom molecule -> (n, 3) heavy and (n, 4, 3) hydrogen arrays"""
-    heavy = np.asarray(vecs[:m.n], dtype=np.float64).reshape(m.n, 3)
-    hs = np.zeros((m.n, MAX_H, 3), dtype=np.float64)
-    x = m.n
-    for a in range(m.n):
-        for k in range(m.h[a]):
-            hs[a, k] = vecs[x]
-            x += 1
-    return heavy, hs
-
-
 def relax_ref(info, order, h_count, h_pos, atom_flag, tables=None, max_iters=DEFAULT_MAX_ITERS, gtol=DEFAULT_GTOL, max_step=DEFAULT_MAX_STEP,
               deg_tol=DEFAULT_DEG_TOL, trace=None):
-    """Plain Python-float restatement of ``mdx_mol_relax`` for one molecule (the arguments of ``energy_ref``) -> dict: the numbers of
+    """Plain float64 restatement of ``mdx_mol_relax`` for one molecule (the arguments of ``energy_ref``) -> dict: the numbers of
     STAT_KEYS, ``n_atoms``, ``energy`` (14 float64: ENERGY_KEYS), ``pos`` / ``grad`` (n, 3) and ``h_pos`` / ``h_grad`` (n, 4, 3) float64,
     and ``energies``, the accepted total energy after every iteration.  With status 1 (TOO_LARGE) or 2 (NONFINITE) every other output is
     0.  trace: a list that receives every number a decision compares with a threshold, as (kind, value, threshold): 'deg', 'rms',
@@ -539,103 +636,33 @@ def relax_ref(info, order, h_count, h_pos, atom_flag, tables=None, max_iters=DEF
     if m is None:
         return dict(zero, status=STATUS_TOO_LARGE)
     na = m.n_all
-    degs = []
 
     def evaluate(x):
-        del degs[:]
-        r = _evaluate(m, x, deg_tol, degs)
+        degs = []
+        ev = _evaluate(m, [tuple(p) for p in x.tolist()], deg_tol, degs)
         trace.extend((k, v, deg_tol) for k, v in degs)
-        return r
-    x = list(m.pos)
-    cur = evaluate(x)
-    first, n_evals = cur, 1
-    E, g = cur['total'], cur['grad']
-    if not _finite(E) or not _finite(_vdot(g, g)):
+        return ev['total'], np.asarray(ev['grad'], dtype=np.float64).reshape(na, 3), ev
+    start = np.asarray(m.pos, dtype=np.float64).reshape(na, 3)
+    r = lbfgs_ref(start, evaluate, max_iters, gtol, max_step, trace)
+    if r is None:
         return dict(zero, status=STATUS_NONFINITE)
-    hist = []                                                          # (s, y, s.y, y.y), oldest first
-    iters, energies = 0, []
-    while True:
-        gg = _vdot(g, g)
-        rms = math.sqrt(gg / (3.0 * na)) if na else 0.0
-        trace.append(('rms', rms, gtol))
-        if rms <= gtol:
-            reason = STOP_CONVERGED
-            break
-        if iters >= max_iters:
-            reason = STOP_MAXITER
-            break
-        if hist:
-            q, alphas = list(g), []
-            for s, y, sy, _ in reversed(hist):
-                al = _vdot(s, q) / sy
-                alphas.append(al)
-                q = [tuple(qa[c] - al * ya[c] for c in range(3)) for qa, ya in zip(q, y)]
-            gamma = hist[-1][2] / hist[-1][3]
-            r = [tuple(gamma * qa[c] for c in range(3)) for qa in q]
-            for (s, y, sy, _), al in zip(hist, reversed(alphas)):
-                co = al - _vdot(y, r) / sy
-                r = [tuple(ra[c] + co * sa[c] for c in range(3)) for ra, sa in zip(r, s)]
-            d = [tuple(-ra[c] for c in range(3)) for ra in r]
-            gd = _vdot(g, d)
-            trace.append(('descent', gd, 0.0))
-            if not gd < 0.0:
-                hist = []
-        if not hist:
-            d = [tuple(-ga[c] for c in range(3)) for ga in g]
-        accepted = None
-        while True:
-            big = _sqrt(block_max(_dot(da, da) for da in d))
-            trace.append(('cap', big, max_step))
-            if big > max_step:
-                sc = max_step / big
-                d = [tuple(sc * da[c] for c in range(3)) for da in d]
-            gd = _vdot(g, d)
-            t = 1.0
-            for _ in range(MAX_TRIALS):
-                xt = [tuple(xa[c] + t * da[c] for c in range(3)) for xa, da in zip(x, d)]
-                new = evaluate(xt)
-                n_evals += 1
-                bound = E + (ARMIJO * t) * gd
-                if _finite(new['total']):
-                    trace.append(('armijo', new['total'], bound))
-                if _finite(new['total']) and new['total'] <= bound:
-                    accepted = new
-                    break
-                t = t * 0.5
-            if accepted is not None or not hist:
-                break
-            hist = []
-            d = [tuple(-ga[c] for c in range(3)) for ga in g]
-        if accepted is None:
-            reason = STOP_LINESEARCH
-            break
-        s = [tuple(ta[c] - xa[c] for c in range(3)) for ta, xa in zip(xt, x)]
-        y = [tuple(na_[c] - ga[c] for c in range(3)) for na_, ga in zip(accepted['grad'], g)]
-        sy, ss, yy = _vdot(s, y), _vdot(s, s), _vdot(y, y)
-        lim = CURVATURE * _sqrt(ss * yy)
-        trace.append(('curvature', sy, lim))
-        if sy > lim:
-            hist = (hist + [(s, y, sy, yy)])[-HISTORY:]
-        x, cur, E, g = xt, accepted, accepted['total'], accepted['grad']
-        iters += 1
-        energies.append(E)
-    heavy, hs = _split(m, x)
-    gh, ghs = _split(m, g)
-    moved = block_sum([_dot(_sub(x[a], m.pos[a]), _sub(x[a], m.pos[a])) for a in range(m.n)])
+    first, cur, x = r['first'], r['extra'], r['x']
+    heavy, hs = _split(m.n, m.h, x)
+    gh, ghs = _split(m.n, m.h, r['grad'])
+    moved = _vdot(x[:m.n] - start[:m.n], x[:m.n] - start[:m.n])
     c = first['counts']
-    energy = first['components'] + [first['total']] + cur['components'] + [cur['total'], rms, math.sqrt(moved / m.n) if m.n else 0.0]
-    return dict(zero, status=STATUS_OK, stop_reason=reason, iterations=iters, n_evals=n_evals, n_all=na, n_ff_bonds=c[0], n_angles=c[1], n_torsions=c[2],
-                n_inversions=c[3], n_pairs=c[4], n_fallback=m.n_fallback, energy=np.asarray(energy, dtype=np.float64), pos=heavy, h_pos=hs, grad=gh,
-                h_grad=ghs, energies=energies)
+    energy = first['components'] + [first['total']] + cur['components'] + [cur['total'], r['rms'], math.sqrt(moved / m.n) if m.n else 0.0]
+    return dict(zero, status=STATUS_OK, stop_reason=r['stop_reason'], iterations=r['iterations'], n_evals=r['n_evals'], n_all=na, n_ff_bonds=c[0],
+                n_angles=c[1], n_torsions=c[2], n_inversions=c[3], n_pairs=c[4], n_fallback=m.n_fallback, energy=np.asarray(energy, dtype=np.float64),
+                pos=heavy, h_pos=hs, grad=gh, h_grad=ghs, energies=r['energies'])
 
 
 def near_threshold(info, order, h_count, h_pos, atom_flag, tables=None, max_iters=DEFAULT_MAX_ITERS, gtol=DEFAULT_GTOL, max_step=DEFAULT_MAX_STEP,
                    deg_tol=DEFAULT_DEG_TOL, band=1e-9):
-    """whether some decision of ``relax_ref`` lies within `band` (relative to the larger of the two magnitudes, or absolute against a
-    threshold of 0) of its threshold: the molecules a device comparison may leave out, because float64 rounding may differ"""
+    """whether some decision of ``relax_ref`` is ``near`` its threshold: the molecules a device comparison may leave out"""
     trace = []
     relax_ref(info, order, h_count, h_pos, atom_flag, tables, max_iters, gtol, max_step, deg_tol, trace)
-    return any(math.isfinite(v) and abs(v - th) <= band * max(abs(v), abs(th), 1e-300 if th else 1.0) for _, v, th in trace)
+    return near(trace, band)
 
 
 def _inputs(mols, tb, kek=None, hyd=None):

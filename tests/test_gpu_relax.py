@@ -65,8 +65,7 @@ def test_evaluation_of_the_named_and_random_sets_as_one_batch():
 def test_runs_follow_the_restatement(max_iters):
     cases = RC.all_cases()
     refs = RC.refs(max_iters)
-    near = {m for m, (_, tr) in enumerate(refs)
-            if any(np.isfinite(v) and abs(v - th) <= 1e-9 * max(abs(v), abs(th), 1e-300 if th else 1.0) for _, v, th in tr)}
+    near = {m for m, (_, tr) in enumerate(refs) if R.near(tr, 1e-9)}
     assert len(near) <= len(cases) // 10
     got = run(cases, max_iters=max_iters)
     worst = 0.0
