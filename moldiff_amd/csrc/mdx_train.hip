@@ -826,7 +826,7 @@ __global__ __launch_bounds__(256) void hgemm_tn_tr_kernel(const _Float16* __rest
 // sum, not a matrix product (the 64 x 64 MFMA tile of the converting kernel spent 20 us per call on 63/64 zero columns).  256 threads =
 // 256 / (C/4) rows x C/4 lanes of four columns; row groups are combined through LDS in a fixed order.  Bias partials: the plain column
 // sums of dY (A = dY) or sum_m s[m] (s = dY).  C % 4 == 0, C <= 256.
-__device__ __forceinline__ void wgrad_colsum_body(const TP s_, const TP A_, int lda, int C, bool bias_is_A, int M, int mper, float* __restrict__ P,
+__device__ __forceinline__ void wgrad_colsum_body(const TP s_, int lds, const TP A_, int lda, int C, bool bias_is_A, int M, int mper, float* __restrict__ P,
                                                   float* __restrict__ Pb, const int bz) {
   // a thread owns 8 columns of float16 rows (one 16-byte load) or 4 of fp32 rows, and every (256 / lanes-per-row)-th row of the range
   __shared__ f32x4 red[2][256];
@@ -841,7 +841,7 @@ __device__ __forceinline__ void wgrad_colsum_body(const TP s_, const TP A_, int 
   if (rl < rows_it) {
 #pragma unroll 4
     for (int m = mbeg + rl; m < mend; m += rows_it) {
-      float sv = ld1(s_, (size_t)m);
+      float sv = ld1(s_, (size_t)m * lds);   // (the scalar operand may be one column of a wider matrix)
       // autocast arithmetic: operands of a Linear's contraction are float16 VALUES (the converting kernel rounds fp32 containers the same way)
       if (!s_.h) sv = round_half<1>(sv);
       f32x4 a0, a1 = splat4(0.f);
@@ -928,8 +928,8 @@ __global__ __launch_bounds__(256) void wgrad_grouped_kernel(const long long* __r
   } else if constexpr (KIND == 7) {                // N == 1 or K == 1: scaled column sums
     const int dt = (int)d[13];
     const TP G{reinterpret_cast<const void*>(d[0]), dt & 1}, X{reinterpret_cast<const void*>(d[1]), (dt >> 1) & 1};
-    if (N == 1) wgrad_colsum_body(G, X, ldx, K, false, M, mper, P, Pb, bz);
-    else wgrad_colsum_body(X, G, ldg, N, true, M, mper, P, Pb, bz);
+    if (N == 1) wgrad_colsum_body(G, ldg, X, ldx, K, false, M, mper, P, Pb, bz);
+    else wgrad_colsum_body(X, ldx, G, ldg, N, true, M, mper, P, Pb, bz);
   } else {
     const int dt = (int)d[13];
     const TP G{reinterpret_cast<const void*>(d[0]), dt & 1}, X{reinterpret_cast<const void*>(d[1]), (dt >> 1) & 1};
