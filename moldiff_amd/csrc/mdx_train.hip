@@ -1,8 +1,9 @@
-// Layer-level operators of the training path (gfx950): every O(rows x features) piece of the loss forward/backward
-// (reference models/model.py:128-201 get_loss + torch.autograd) as an explicit forward/backward kernel pair, driven one
-// layer at a time from moldiff_amd/train_ops.py and csrc/mdx_fast.cpp.  Unlike the sampling path these are NOT fused across
-// layers (the fused training kernels are in mdx_train_fused.hip): activations live in HBM between operators so that every
-// parameter gradient is a plain contraction over stored tensors.  Three precisions share the file: exact fp32 (contractions on
+// Layer-level operators of the training path (gfx950), part 1: the contractions and the reductions behind them.  Every
+// O(rows x features) piece of the loss forward/backward (reference models/model.py:128-201 get_loss + torch.autograd) is an explicit
+// forward/backward kernel pair, driven one layer at a time from moldiff_amd/train_ops.py and csrc/mdx_fast.cpp.  Unlike the sampling
+// path these are NOT fused across layers (the fused training kernels are in mdx_train_fused.hip): activations live in HBM between
+// operators so that every parameter gradient is a plain contraction over stored tensors.  The row operators between the contractions
+// (LayerNorm, element-wise, gather / segment sums, geometry, optimizer) are in mdx_train_rows.hip.  Three precisions share the file: exact fp32 (contractions on
 // v_mfma_f32_16x16x4_f32), and bfloat16 / float16 operands with fp32 accumulation (v_mfma_f32_16x16x32_*), the float16 mode also
 // with float16 CONTAINERS (`_t` entry points: a bit mask names the tensors stored as float16).
 //
@@ -15,12 +16,6 @@
 //   reduce_deferred         every split partial of a step (weights, biases, LayerNorm parameters) summed into the flat gradient buffer
 //   transpose(_batch)       out[C,R] = in[R,C]^T: W^T for the dgrad GEMMs
 //   colreduce               out[N] = sum_rows X (* Y): bias / LayerNorm-parameter gradients (two deterministic stages)
-//   ln_relu                 y = relu(LN(x) * gamma + beta): forward (saves mean, rstd), backward (dx, partial rows of dgamma | dbeta)
-//                           and the backward fused with a rank-1 Linear in front of it; generic fp32 kernels and 4-wide typed ones
-//   ew, sum_n               add / sub / mul / a * sigmoid(b), forward and backward; sum of up to 12 tensors
-//   gather / segsum, mul_gather, plan_flip      y = x[idx]; out[r] = sum_{j in seg r} src[order[j]] (each is the other's backward; no atomics)
-//   edge_geom, smear, force                     rel / dist of an edge, Gaussian smearing, w * rel / d / (d + 1), with backwards
-//   sumsq, adamw, amp_adamw                     gradient norm and the optimizer step (with the loss scaler's decision on the device)
 //
 // The host side's shared arithmetic -- split-partial layout, the queue's plan, LayerNorm partial rows, the deferred reduction's record
 // table, the row-owner GEMM's shapes -- is in mdx_train_plan.h (plain C++, also built by the host compiler alone).
@@ -33,9 +28,9 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_tile.h"
+#include "mdx_train_launch.h"
 #include "mdx_train_plan.h"
-
-int mdx_set_error(int code, const char* msg);  // mdx_api.hip
+#include "mdx_typed.h"
 
 namespace {
 
@@ -48,55 +43,17 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int G_TM = 128, G_TN = 64, G_KC = 32, G_LD = G_KC + 8;
 
-// Half storage (round 3): a tensor of the training operators is stored as fp32 (h = 0) or as float16 (h = 1; the mixed-precision
-// mode keeps every Linear / LayerNorm / product result -- float16 VALUES anyway -- in float16 containers).  The flag is wave-uniform,
-// one scalar branch per access; offsets are in elements.
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-struct TP {
-  const void* p;
-  int h;
-};
-struct TPW {
-  void* p;
-  int h;
-};
-__device__ __forceinline__ f32x4 ld4(const TP& t, size_t i) {
-  if (t.h) {
-    const f16x4_t v = *reinterpret_cast<const f16x4_t*>(reinterpret_cast<const _Float16*>(t.p) + i);
-    f32x4 r = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    return r;
-  }
-  return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(t.p) + i);
-}
-__device__ __forceinline__ float ld1(const TP& t, size_t i) {
-  return t.h ? (float)reinterpret_cast<const _Float16*>(t.p)[i] : reinterpret_cast<const float*>(t.p)[i];
-}
-__device__ __forceinline__ void st4(const TPW& t, size_t i, f32x4 v) {
-  if (t.h) {
-    f16x4_t r = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-    *reinterpret_cast<f16x4_t*>(reinterpret_cast<_Float16*>(t.p) + i) = r;
-  } else {
-    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(t.p) + i) = v;
-  }
-}
-__device__ __forceinline__ void st1(const TPW& t, size_t i, float v) {
-  if (t.h) reinterpret_cast<_Float16*>(t.p)[i] = (_Float16)v;
-  else reinterpret_cast<float*>(t.p)[i] = v;
-}
+// (typed operands -- fp32 or float16 containers: mdx_typed.h)
 // 4 consecutive k-values of row `row_off` (element offset of the row), zero beyond K or outside the matrix
 __device__ __forceinline__ f32x4 load4_guard_t(const TP& t, size_t row_off, int k, int K, bool row_ok, bool vec_ok) {
   if (!row_ok || k >= K) return splat4(0.f);
-  if (vec_ok && k + 3 < K) return ld4(t, row_off + k);
+  if (vec_ok && k + 3 < K) return ldv<4>(t, row_off + k);
   f32x4 v = splat4(0.f);
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (k + j < K) v[j] = ld1(t, row_off + k + j);
+    if (k + j < K) v[j] = ldv<1>(t, row_off + k + j);
   return v;
 }
-__host__ __device__ inline bool tp_vec_ok(const void* p, int h, int ld) {  // rows of 4 elements are naturally aligned
-  return ((ld & 3) == 0) && ((reinterpret_cast<uintptr_t>(p) & (h ? 7 : 15)) == 0);
-}
-
 __device__ __forceinline__ f32x4 load4_guard(const float* __restrict__ p, int k, int K, bool row_ok, bool vec_ok) {
   // 4 consecutive k-values of one row, zero beyond K or outside the matrix
   if (!row_ok || k >= K) return splat4(0.f);
@@ -219,11 +176,6 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
   ub += 0x7fffu + ((ub >> 16) & 1u);
   return (ua >> 16) | (ub & 0xffff0000u);
 }
-__device__ __forceinline__ uint16_t to_bf16(float a) {
-  uint32_t u = __float_as_uint(a);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 // The low-precision operand type of the mixed-precision GEMMs: HT = 0 bfloat16 (round 2's mode), HT = 1 IEEE half -- the type the
 // reference's torch.autocast(dtype=torch.float16) casts Linear operands to (scripts/train_drug3d.py:93).  cvt rounds to nearest
 // even; a float16 overflows to infinity beyond 65504 like the cast autocast inserts (GradScaler's found_inf then skips the step).
@@ -245,11 +197,7 @@ struct HalfT<1> {
   static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 };
 template <int HT>
-__device__ __forceinline__ float round_half(float a) { return HalfT<HT>::back(HalfT<HT>::cvt(a)); }
-template <int HT>
 __device__ __forceinline__ typename HalfT<HT>::v8 lds_h8(const uint16_t* p) { return *reinterpret_cast<const typename HalfT<HT>::v8*>(p); }
-// run-time form for the element-wise kernels: kind 0 = keep fp32, 1 = bf16, 2 = fp16
-__device__ __forceinline__ float round_kind(float a, int kind) { return kind == 2 ? round_half<1>(a) : kind == 1 ? round_half<0>(a) : a; }
 
 constexpr int H_KC = 64, H_LD = H_KC + 8;  // bf16 elements per staged row (+8 = 16 bytes of padding)
 
@@ -367,7 +315,7 @@ __global__ __launch_bounds__(256) void hgemm_nt_kernel(const TP A, int lda, cons
       if (addend.p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (col + r < N) v[r] += ld1(addend, (size_t)row * ldd + col + r);
+          if (col + r < N) v[r] += ldv<1>(addend, (size_t)row * ldd + col + r);
       }
       if (ROUND) {  // the Linear's output in the low-precision type, like autocast's fp16 / bf16 result (held in an fp32 container)
 #pragma unroll
@@ -375,11 +323,11 @@ __global__ __launch_bounds__(256) void hgemm_nt_kernel(const TP A, int lda, cons
       }
       const size_t o = (size_t)row * ldc + col;
       if (veco && col + 3 < N) {
-        st4(C, o, v);
+        stv<4>(C, o, v);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (col + r < N) st1(C, o + r, v[r]);
+          if (col + r < N) stv<1>(C, o + r, v[r]);
       }
     }
   }
@@ -511,10 +459,10 @@ __global__ __launch_bounds__(512) void hgemm_nt_rows_kernel(const _Float16* __re
         f32x4 v = acc[ft] + lds4(bs + col);
         if (addend.p) {
           if (vecd) {
-            v = v + ld4(addend, (size_t)row * ldd + col0 + col);
+            v = v + ldv<4>(addend, (size_t)row * ldd + col0 + col);
           } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += ld1(addend, (size_t)row * ldd + col0 + col + r);
+            for (int r = 0; r < 4; ++r) v[r] += ldv<1>(addend, (size_t)row * ldd + col0 + col + r);
           }
         }
         if (ROUND) {
@@ -525,10 +473,10 @@ __global__ __launch_bounds__(512) void hgemm_nt_rows_kernel(const _Float16* __re
         if (pairc) {
           if (ft & 1) st8h_pair(reinterpret_cast<_Float16*>(C.p) + (size_t)row * ldc + col0, ft >> 1, acc[ft - 1], v, q);
         } else if (veco) {
-          st4(C, o, v);
+          stv<4>(C, o, v);
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) st1(C, o + r, v[r]);
+          for (int r = 0; r < 4; ++r) stv<1>(C, o + r, v[r]);
         }
         if (LN || pairc) acc[ft] = v;     // (the finished values: the LayerNorm epilogue / the pair store of the next tile reads them)
       }
@@ -555,7 +503,7 @@ __global__ __launch_bounds__(512) void hgemm_nt_rows_kernel(const _Float16* __re
             if (ft & 1) st8h_pair(reinterpret_cast<_Float16*>(ln.post.p) + (size_t)row * ln.ldp, ft >> 1, acc[ft - 1], y, q);
             acc[ft] = y;
           } else {
-            st4(ln.post, (size_t)row * ln.ldp + col, y);
+            stv<4>(ln.post, (size_t)row * ln.ldp + col, y);
           }
         }
         if (q == 0) {
@@ -841,7 +789,7 @@ __device__ __forceinline__ void wgrad_colsum_body(const TP s_, int lds, const TP
   if (rl < rows_it) {
 #pragma unroll 4
     for (int m = mbeg + rl; m < mend; m += rows_it) {
-      float sv = ld1(s_, (size_t)m * lds);   // (the scalar operand may be one column of a wider matrix)
+      float sv = ldv<1>(s_, (size_t)m * lds);   // (the scalar operand may be one column of a wider matrix)
       // autocast arithmetic: operands of a Linear's contraction are float16 VALUES (the converting kernel rounds fp32 containers the same way)
       if (!s_.h) sv = round_half<1>(sv);
       f32x4 a0, a1 = splat4(0.f);
@@ -852,10 +800,10 @@ __device__ __forceinline__ void wgrad_colsum_body(const TP s_, int lds, const TP
         a1 = f32x4{(float)hi[0], (float)hi[1], (float)hi[2], (float)hi[3]};
       } else {
         if (vec) {
-          a0 = ld4(A_, (size_t)m * lda + 4 * cl);
+          a0 = ldv<4>(A_, (size_t)m * lda + 4 * cl);
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) a0[r] = ld1(A_, (size_t)m * lda + 4 * cl + r);
+          for (int r = 0; r < 4; ++r) a0[r] = ldv<1>(A_, (size_t)m * lda + 4 * cl + r);
         }
         if (!A_.h) {
 #pragma unroll
@@ -1121,760 +1069,13 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const float* __restrict_
   __syncthreads();
   if (ty == 0 && col < N) out[(size_t)blockIdx.y * N + col] = (sh[0][tx] + sh[1][tx]) + (sh[2][tx] + sh[3][tx]);
 }
+}  // namespace
 
-// ------------------------------------------------------------------------------------------------------------------
-// LayerNorm (+ReLU), one wave per row, F <= 1024.  Lane holds features lane, lane+64, ...
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int LN_MAXJ = 16;   // (rows per wave in the backward, MDX_LN_RPW: mdx_train_plan.h)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void ln_relu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, int M, int F, int relu,
-                                                           float* __restrict__ y, float* __restrict__ stats) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const int J = (F + 63) >> 6;
-  float v[LN_MAXJ];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < LN_MAXJ; ++j) {
-    const int f = lane + 64 * j;
-    v[j] = (j < J && f < F) ? x[(size_t)row * F + f] : 0.f;
-    s += v[j];
-  }
-  const float mean = wave_sum(s) / (float)F;
-  float d2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < LN_MAXJ; ++j) {
-    const int f = lane + 64 * j;
-    if (j < J && f < F) {
-      const float d = v[j] - mean;
-      d2 = fmaf(d, d, d2);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(d2) / (float)F + MDX_LN_EPS);
-#pragma unroll
-  for (int j = 0; j < LN_MAXJ; ++j) {
-    const int f = lane + 64 * j;
-    if (j < J && f < F) {
-      const float o = (v[j] - mean) * rstd * gamma[f] + beta[f];
-      y[(size_t)row * F + f] = relu ? fmaxf(o, 0.f) : o;
-    }
-  }
-  if (lane == 0) {
-    stats[2 * (size_t)row] = mean;
-    stats[2 * (size_t)row + 1] = rstd;
-  }
-}
-
-// The four waves' partials of [dgamma | dbeta] (ln_sh[4][2F], dynamic LDS) -> ONE partial row per workgroup, waves added in the fixed
-// order ((0 + 1) + 2) + 3.  (Round 5: per-wave rows were 8 % of the backward's traffic and, read back, most of the deferred reduction's.)
-extern __shared__ __attribute__((aligned(16))) float ln_sh[];
-__device__ __forceinline__ void ln_part_combine(const float* sh, int F, float* __restrict__ row) {
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * F; i += 256) row[i] = ((sh[i] + sh[2 * F + i]) + sh[4 * F + i]) + sh[6 * F + i];
-}
-
-// each wave walks `rows_per` consecutive rows: dx per row, and its own partial of dgamma / dbeta (registers); the workgroup's four
-// partials are combined and written to part[blockIdx.x][2F] (dgamma first); the caller column-reduces `part`.
-__global__ __launch_bounds__(256) void ln_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                           const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                           const float* __restrict__ beta, int M, int F, int relu, int rows_per,
-                                                           float* __restrict__ dx, float* __restrict__ part) {
-  const int lane = threadIdx.x & 63;
-  const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int r0 = wg * rows_per, r1 = min(M, r0 + rows_per);
-  const int J = (F + 63) >> 6;
-  float gm[LN_MAXJ], bt[LN_MAXJ], dg[LN_MAXJ], db[LN_MAXJ];
-#pragma unroll
-  for (int j = 0; j < LN_MAXJ; ++j) {
-    const int f = lane + 64 * j;
-    const bool ok = j < J && f < F;
-    gm[j] = ok ? gamma[f] : 0.f;
-    bt[j] = ok ? beta[f] : 0.f;
-    dg[j] = db[j] = 0.f;
-  }
-  for (int row = r0; row < r1; ++row) {
-    const float mean = stats[2 * (size_t)row], rstd = stats[2 * (size_t)row + 1];
-    float xh[LN_MAXJ], gh[LN_MAXJ];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-      const int f = lane + 64 * j;
-      xh[j] = gh[j] = 0.f;
-      if (j < J && f < F) {
-        xh[j] = (x[(size_t)row * F + f] - mean) * rstd;
-        float g = dy[(size_t)row * F + f];
-        if (relu && !(xh[j] * gm[j] + bt[j] > 0.f)) g = 0.f;
-        dg[j] = fmaf(g, xh[j], dg[j]);
-        db[j] += g;
-        gh[j] = g * gm[j];
-        s1 += gh[j];
-        s2 = fmaf(gh[j], xh[j], s2);
-      }
-    }
-    const float m1 = wave_sum(s1) / (float)F, m2 = wave_sum(s2) / (float)F;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-      const int f = lane + 64 * j;
-      if (j < J && f < F) dx[(size_t)row * F + f] = rstd * (gh[j] - m1 - xh[j] * m2);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < LN_MAXJ; ++j) {
-    const int f = lane + 64 * j;
-    if (j < J && f < F) {
-      ln_sh[(threadIdx.x >> 6) * 2 * F + f] = dg[j];
-      ln_sh[(threadIdx.x >> 6) * 2 * F + F + f] = db[j];
-    }
-  }
-  ln_part_combine(ln_sh, F, part + (size_t)blockIdx.x * 2 * F);
-}
-
-
-// ---- vectorised LayerNorm for the widths the networks use (F = 32, 64, 128, 256): a row is F/4 lanes x float4, a wave covers
-// 64 / (F/4) rows per step; the row sums are DPP / permlane butterflies over the row's lanes (the generic kernels above spend
-// twelve ds_bpermute round trips per row and a whole wave per row whatever its width).
-template <int LPR>  // lanes per row: 8, 16, 32, 64
-__device__ __forceinline__ float row_lanes_sum(float v) {
-  auto dpp = [](float x, auto ctrl) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, false));
-  };
-  v += dpp(v, std::integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
-  v += dpp(v, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-  v += dpp(v, std::integral_constant<int, 0x141>{});  // row_half_mirror: + the other quad of the 8-lane group
-  if (LPR >= 16) v += dpp(v, std::integral_constant<int, 0x140>{});  // row_mirror: + the other half of the 16-lane row
-  if (LPR >= 32) {
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  }
-  if (LPR >= 64) {
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-  }
-  return v;
-}
-
-template <int LPR>
-__global__ __launch_bounds__(256) void ln_relu_fwd4_kernel(const TP x, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int M, int relu, const TPW y,
-                                                            float* __restrict__ stats) {
-  constexpr int F = 4 * LPR, RPS = 64 / LPR;
-  const int lane = threadIdx.x & 63, wg = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int row = wg * RPS + lane / LPR, c4 = lane % LPR;
-  const bool ok = row < M;
-  const f32x4 v = ok ? ld4(x, (size_t)row * F + 4 * c4) : splat4(0.f);
-  const float mean = row_lanes_sum<LPR>((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / F);
-  const f32x4 d = v - splat4(mean);
-  const float rstd = 1.0f / sqrtf(row_lanes_sum<LPR>(fmaf(d[0], d[0], fmaf(d[1], d[1], fmaf(d[2], d[2], d[3] * d[3])))) * (1.0f / F) + MDX_LN_EPS);
-  if (!ok) return;
-  const f32x4 gmv = {gamma[4 * c4], gamma[4 * c4 + 1], gamma[4 * c4 + 2], gamma[4 * c4 + 3]};  // (parameters: any 4-byte offset)
-  const f32x4 btv = {beta[4 * c4], beta[4 * c4 + 1], beta[4 * c4 + 2], beta[4 * c4 + 3]};
-  f32x4 o = d * splat4(rstd) * gmv + btv;
-  if (relu) o = relu4(o);
-  st4(y, (size_t)row * F + 4 * c4, o);
-  if (c4 == 0) {
-    stats[2 * (size_t)row] = mean;
-    stats[2 * (size_t)row + 1] = rstd;
-  }
-}
-
-// backward: a wave walks `steps` consecutive row groups; dx per row; the workgroup's partial of dgamma / dbeta -> part[blockIdx.x][2F]
-// r1w != NULL (round 6): the upstream gradient is the rank-1 product dy[row][c] = f16(g1[row] * f16(r1w[c])) -- the data gradient of a
-// Linear to ONE output (PosUpdate's 256 -> 1) that follows this LayerNorm; dy.p then holds g1 (M values), and the (M,F) gradient
-// tensor, the K = 1 GEMM that formed it and the transpose of its weight never exist.
-template <int LPR>
-__global__ __launch_bounds__(256) void ln_relu_bwd4_kernel(const TP dy, const TP x,
-                                                            const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int M, int relu, int rows_per,
-                                                            const TPW dx, float* __restrict__ part, const float* __restrict__ r1w = nullptr) {
-  constexpr int F = 4 * LPR, RPS = 64 / LPR;
-  const int lane = threadIdx.x & 63, wg = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int sub = lane / LPR, c4 = lane % LPR;
-  const int r0 = wg * rows_per, r1 = min(M, r0 + rows_per);
-  const f32x4 gm = {gamma[4 * c4], gamma[4 * c4 + 1], gamma[4 * c4 + 2], gamma[4 * c4 + 3]};  // (parameters: any 4-byte offset)
-  const f32x4 bt = {beta[4 * c4], beta[4 * c4 + 1], beta[4 * c4 + 2], beta[4 * c4 + 3]};
-  f32x4 w1 = splat4(0.f);
-  if (r1w) w1 = f32x4{round_half<1>(r1w[4 * c4]), round_half<1>(r1w[4 * c4 + 1]), round_half<1>(r1w[4 * c4 + 2]), round_half<1>(r1w[4 * c4 + 3])};
-  f32x4 dg = splat4(0.f), db = splat4(0.f);
-#ifndef MDX_LNB_UNROLL
-#define MDX_LNB_UNROLL 2
-#endif
-#pragma unroll MDX_LNB_UNROLL
-  for (int rb = r0; rb < r1; rb += RPS) {
-    const int row = rb + sub;
-    const bool ok = row < r1;
-    const size_t o = (size_t)(ok ? row : r0) * F + 4 * c4;
-    const float mean = stats[2 * (size_t)(ok ? row : r0)], rstd = stats[2 * (size_t)(ok ? row : r0) + 1];
-    const f32x4 xh = (ld4(x, o) - splat4(mean)) * splat4(rstd);
-    f32x4 g = splat4(0.f);
-    if (r1w) {
-      if (ok) {
-        const float gv = round_half<1>(ld1(dy, (size_t)row));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) g[k] = round_half<1>(gv * w1[k]);
-      }
-    } else if (ok) {
-      g = ld4(dy, o);
-    }
-    if (relu) {
-      const f32x4 yv = xh * gm + bt;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (!(yv[k] > 0.f)) g[k] = 0.f;
-    }
-    dg = dg + g * xh;
-    db = db + g;
-    const f32x4 gh = g * gm;
-    const float m1 = row_lanes_sum<LPR>((gh[0] + gh[1]) + (gh[2] + gh[3])) * (1.0f / F);
-    const float m2 = row_lanes_sum<LPR>(fmaf(gh[0], xh[0], fmaf(gh[1], xh[1], fmaf(gh[2], xh[2], gh[3] * xh[3])))) * (1.0f / F);
-    if (ok) st4(dx, o, (gh - splat4(m1) - xh * splat4(m2)) * splat4(rstd));
-  }
-  // the 64 / LPR row groups of the wave hold the same features: combine them (lane bits >= LPR), then the first group writes
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    float a = dg[k], b = db[k];
-    if (LPR <= 8) {  // + lanes ^ 8 (row_ror:8 within the 16-lane row)
-      a += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0x128, 0xf, 0xf, false));
-      b += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b), 0x128, 0xf, 0xf, false));
-    }
-    if (LPR <= 16) {
-      const auto sa = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-      const auto sb = __builtin_amdgcn_permlane16_swap(__float_as_uint(b), __float_as_uint(b), false, false);
-      a = __uint_as_float(sa[0]) + __uint_as_float(sa[1]);
-      b = __uint_as_float(sb[0]) + __uint_as_float(sb[1]);
-    }
-    if (LPR <= 32) {
-      const auto sa = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-      const auto sb = __builtin_amdgcn_permlane32_swap(__float_as_uint(b), __float_as_uint(b), false, false);
-      a = __uint_as_float(sa[0]) + __uint_as_float(sa[1]);
-      b = __uint_as_float(sb[0]) + __uint_as_float(sb[1]);
-    }
-    dg[k] = a;
-    db[k] = b;
-  }
-  if (sub == 0) {
-    float* w = ln_sh + (threadIdx.x >> 6) * 2 * F;
-    *reinterpret_cast<f32x4*>(w + 4 * c4) = dg;
-    *reinterpret_cast<f32x4*>(w + F + 4 * c4) = db;
-  }
-  ln_part_combine(ln_sh, F, part + (size_t)blockIdx.x * 2 * F);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// element-wise pairs.  op: 0 add, 1 sub, 2 mul, 3 gate (a * sigmoid(b))
-// ------------------------------------------------------------------------------------------------------------------
-// opr = op | (rkind << 8): rkind != 0 rounds the result (and the sigmoid of the gate) to bfloat16 / float16 -- the value the
-// reference's fp16 tensors hold under autocast (both factors of these products are Linear outputs there)
-template <typename V>
-__device__ __forceinline__ V ew_apply(int op, V x, V y);
-template <>
-__device__ __forceinline__ f32x4 ew_apply<f32x4>(int op, f32x4 x, f32x4 y) {
-  switch (op) {
-    case 0: return x + y;
-    case 1: return x - y;
-    case 2: return x * y;
-    default: return x * sigmoid4(y);
-  }
-}
-__global__ void ew_fwd4_kernel(int opr, const TP a, const TP b, const TPW o, size_t n4) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const int op = opr & 255, rk = opr >> 8;
-  const f32x4 x = ld4(a, 4 * i), y = ld4(b, 4 * i);
-  if (rk == 0) {
-    st4(o, 4 * i, ew_apply<f32x4>(op, x, y));
-    return;
-  }
-  f32x4 r;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float v = op == 0 ? x[j] + y[j] : op == 1 ? x[j] - y[j] : op == 2 ? x[j] * y[j] : x[j] * round_kind(sigmoidf_(y[j]), rk);
-    r[j] = round_kind(v, rk);
-  }
-  st4(o, 4 * i, r);
-}
-// out = sum of up to 12 tensors of one shape (round 6): the gradient of a tensor with several consumers.  autograd would add the
-// consumers' gradients pairwise (k - 1 launches of an element-wise add, each rounding to the container); here they are summed in
-// fp32 in argument order and rounded ONCE.  Operands fp32 or float16 containers, 4 elements per thread.
-struct SumN {
-  const void* p[12];
-  int h[12];
-  int n;
-};
-__global__ void sum_n4_kernel(const SumN a, const TPW o, size_t n4) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 s = ld4(TP{a.p[0], a.h[0]}, 4 * i);
-  for (int j = 1; j < a.n; ++j) s = s + ld4(TP{a.p[j], a.h[j]}, 4 * i);
-  st4(o, 4 * i, s);
-}
-__global__ void sum_n1_kernel(const SumN a, const TPW o, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float s = ld1(TP{a.p[0], a.h[0]}, i);
-  for (int j = 1; j < a.n; ++j) s += ld1(TP{a.p[j], a.h[j]}, i);
-  st1(o, i, s);
-}
-// any length / alignment, fp32 or float16 containers (round 6: an (E,1) gate product has E % 4 != 0 and used to go through two casts to
-// fp32 and back); also what an unaligned or odd-length fp32 tensor takes
-__global__ void ew_fwd1_kernel(int opr, const TP a, const TP b, const TPW o, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int op = opr & 255, rk = opr >> 8;
-  const float x = ld1(a, i), y = ld1(b, i);
-  const float v = op == 0 ? x + y : op == 1 ? x - y : op == 2 ? x * y : x * round_kind(sigmoidf_(y), rk);
-  st1(o, i, round_kind(v, rk));
-}
-__global__ void ew_bwd1_kernel(int op, const TP a, const TP b, const TP g, const TPW da, const TPW db, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gv = ld1(g, i);
-  float ga, gb;
-  if (op == 0) { ga = gv; gb = gv; }
-  else if (op == 1) { ga = gv; gb = -gv; }
-  else if (op == 2) { ga = gv * ld1(b, i); gb = gv * ld1(a, i); }
-  else { const float sg = sigmoidf_(ld1(b, i)); ga = gv * sg; gb = gv * ld1(a, i) * sg * (1.0f - sg); }
-  if (da.p) st1(da, i, ga);
-  if (db.p) st1(db, i, gb);
-}
-__global__ void ew_bwd4_kernel(int op, const TP a, const TP b, const TP g, const TPW da, const TPW db, size_t n4) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const f32x4 go = ld4(g, 4 * i);
-  f32x4 ga, gb;
-  switch (op) {
-    case 0: ga = go; gb = go; break;
-    case 1: ga = go; gb = splat4(0.f) - go; break;
-    case 2: ga = go * ld4(b, 4 * i); gb = go * ld4(a, 4 * i); break;
-    default: {
-      const f32x4 sg = sigmoid4(ld4(b, 4 * i));
-      ga = go * sg;
-      gb = go * ld4(a, 4 * i) * sg * (splat4(1.f) - sg);
-    }
-  }
-  if (da.p) st4(da, 4 * i, ga);
-  if (db.p) st4(db, 4 * i, gb);
-}
-
-// y[i] = x[idx[i]]  (rows of F floats)
-__global__ void gather_rows_kernel(const float* __restrict__ x, const int64_t* __restrict__ idx, int64_t M, int F,
-                                   float* __restrict__ y) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * F) return;
-  const int64_t row = i / F;
-  const int f = (int)(i % F);
-  y[i] = x[(size_t)idx[row] * F + f];
-}
-// 16-byte variants (F % 4 == 0, 16-byte aligned bases): one thread per (row, 4 features)
-__global__ void gather_rows4_kernel(const TP x, const int64_t* __restrict__ idx, int64_t M, int F4, const TPW y) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * F4) return;
-  const int64_t row = i / F4;
-  st4(y, 4 * i, ld4(x, 4 * ((size_t)idx[row] * F4 + (int)(i % F4))));
-}
-__global__ void segsum_rows4_kernel(const TP src, const int64_t* __restrict__ order, const int64_t* __restrict__ ptr,
-                                    int64_t R, int F4, const TPW out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)R * F4) return;
-  const int64_t r = i / F4;
-  const int f = (int)(i % F4);
-  f32x4 s = splat4(0.f);
-  // four rows in flight (round 6): the loop was one dependent index load + one row load per iteration -- latency-bound at ~25 rows
-  // per node (30 us for 79 MB).  The additions keep their order (s + v0) + v1 ...: bit-identical sums.
-  int64_t j = ptr[r];
-  const int64_t e = ptr[r + 1];
-  for (; j + 4 <= e; j += 4) {
-    const int64_t o0 = order[j], o1 = order[j + 1], o2 = order[j + 2], o3 = order[j + 3];
-    const f32x4 v0 = ld4(src, 4 * ((size_t)o0 * F4 + f)), v1 = ld4(src, 4 * ((size_t)o1 * F4 + f));
-    const f32x4 v2 = ld4(src, 4 * ((size_t)o2 * F4 + f)), v3 = ld4(src, 4 * ((size_t)o3 * F4 + f));
-    s = s + v0;
-    s = s + v1;
-    s = s + v2;
-    s = s + v3;
-  }
-  for (; j < e; ++j) s = s + ld4(src, 4 * ((size_t)order[j] * F4 + f));
-  st4(out, 4 * i, s);
-}
-// The same sum with a segment's rows dealt to FOUR threads (round 6): thread k of an output element takes rows k, k + 4, ... of the segment
-// (four in flight each: sixteen row gathers per element instead of four), the four partial sums are combined through LDS in the fixed
-// order ((p0 + p1) + p2) + p3.  A node has ~28 rows; with one thread per element the kernel ran seven dependent gather rounds at ten
-// waves per CU (25 us for 20-80 MB).  Deterministic; NOT the summation order of segsum_rows4_kernel: used for float16 rows (the autocast
-// mode), fp32 rows keep the sequential order (see mdx_op_segsum_rows_t).
-__global__ __launch_bounds__(256) void segsum_rows4s_kernel(const TP src, const int64_t* __restrict__ order, const int64_t* __restrict__ ptr,
-                                                            int64_t R, int F4, const TPW out) {
-  __shared__ f32x4 part[3][64];
-  const int k = threadIdx.x >> 6, it = threadIdx.x & 63;
-  const size_t i = (size_t)blockIdx.x * 64 + it;
-  const bool live = i < (size_t)R * F4;
-  f32x4 s = splat4(0.f);
-  if (live) {
-    const int64_t r = i / F4;
-    const int f = (int)(i % F4);
-    int64_t j = ptr[r] + k;
-    const int64_t e = ptr[r + 1];
-    for (; j + 12 < e; j += 16) {
-      const int64_t o0 = order[j], o1 = order[j + 4], o2 = order[j + 8], o3 = order[j + 12];
-      const f32x4 v0 = ld4(src, 4 * ((size_t)o0 * F4 + f)), v1 = ld4(src, 4 * ((size_t)o1 * F4 + f));
-      const f32x4 v2 = ld4(src, 4 * ((size_t)o2 * F4 + f)), v3 = ld4(src, 4 * ((size_t)o3 * F4 + f));
-      s = s + v0;
-      s = s + v1;
-      s = s + v2;
-      s = s + v3;
-    }
-    for (; j < e; j += 4) s = s + ld4(src, 4 * ((size_t)order[j] * F4 + f));
-  }
-  if (k) part[k - 1][it] = s;
-  __syncthreads();
-  if (k == 0 && live) {
-    s = s + part[0][it];
-    s = s + part[1][it];
-    s = s + part[2][it];
-    st4(out, 4 * i, s);
-  }
-}
-// CSR order of the RIGHT end points from that of the LEFT ones when the directed edge list is [half-edges ; flipped half-edges]
-// (reference models/model.py:269, :143: edge_index = cat([he, he.flip(0)], 1)): right[i] = left[(i + Eh) mod E], so both index vectors
-// hold the same multiset (same segment starts) and the stable order of `right` inside a node's segment is: the entries j >= Eh of
-// the left order (as j - Eh, ascending), then the entries j < Eh (as j + Eh).  One thread per node; replaces a second stable sort
-// (11 launches of torch.sort + searchsorted) per training step.
-__global__ void plan_flip_kernel(const int64_t* __restrict__ order_l, const int64_t* __restrict__ ptr, int64_t R, int64_t Eh,
-                                 int64_t* __restrict__ order_r) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  const int64_t b = ptr[r], e = ptr[r + 1];
-  int64_t c = b;                       // first position whose entry is >= Eh (entries ascend inside a segment)
-  while (c < e && order_l[c] < Eh) ++c;
-  int64_t w = b;
-  for (int64_t j = c; j < e; ++j) order_r[w++] = order_l[j] - Eh;
-  for (int64_t j = b; j < c; ++j) order_r[w++] = order_l[j] + Eh;
-}
-// The same with EIGHT float16 features per thread (one 16-byte load per row; F % 8 == 0, float16 rows, 16-byte aligned): the sums per
-// feature and their order are those of segsum_rows4s_kernel (bit-identical), half the threads and load instructions.
-__global__ __launch_bounds__(256) void segsum_rows8s_kernel(const _Float16* __restrict__ src, const int64_t* __restrict__ order,
-                                                            const int64_t* __restrict__ ptr, int64_t R, int F8, const TPW out) {
-  __shared__ f32x4 part[3][2][64];
-  const int k = threadIdx.x >> 6, it = threadIdx.x & 63;
-  const size_t i = (size_t)blockIdx.x * 64 + it;
-  const bool live = i < (size_t)R * F8;
-  f32x4 s0 = splat4(0.f), s1 = splat4(0.f);
-  auto ld8 = [&](int64_t o, int f, f32x4& a, f32x4& b) {
-    const uint4 u = *reinterpret_cast<const uint4*>(src + 8 * ((size_t)o * F8 + f));
-    const f16x4_t lo = __builtin_bit_cast(f16x4_t, uint2{u.x, u.y}), hi = __builtin_bit_cast(f16x4_t, uint2{u.z, u.w});
-    a = f32x4{(float)lo[0], (float)lo[1], (float)lo[2], (float)lo[3]};
-    b = f32x4{(float)hi[0], (float)hi[1], (float)hi[2], (float)hi[3]};
-  };
-  if (live) {
-    const int64_t r = i / F8;
-    const int f = (int)(i % F8);
-    int64_t j = ptr[r] + k;
-    const int64_t e = ptr[r + 1];
-    for (; j + 12 < e; j += 16) {
-      const int64_t o0 = order[j], o1 = order[j + 4], o2 = order[j + 8], o3 = order[j + 12];
-      f32x4 a0, b0, a1, b1, a2, b2, a3, b3;
-      ld8(o0, f, a0, b0);
-      ld8(o1, f, a1, b1);
-      ld8(o2, f, a2, b2);
-      ld8(o3, f, a3, b3);
-      s0 = s0 + a0; s1 = s1 + b0;
-      s0 = s0 + a1; s1 = s1 + b1;
-      s0 = s0 + a2; s1 = s1 + b2;
-      s0 = s0 + a3; s1 = s1 + b3;
-    }
-    for (; j < e; j += 4) {
-      f32x4 a, b;
-      ld8(order[j], f, a, b);
-      s0 = s0 + a; s1 = s1 + b;
-    }
-  }
-  if (k) part[k - 1][0][it] = s0, part[k - 1][1][it] = s1;
-  __syncthreads();
-  if (k == 0 && live) {
-    s0 = s0 + part[0][0][it]; s1 = s1 + part[0][1][it];
-    s0 = s0 + part[1][0][it]; s1 = s1 + part[1][1][it];
-    s0 = s0 + part[2][0][it]; s1 = s1 + part[2][1][it];
-    st4(out, 8 * i, s0);
-    st4(out, 8 * i + 4, s1);
-  }
-}
-// y[i] = a[i] * t[idx[i]] and its two gradients (da = g * t[idx];  dt[r] = sum_{j in seg r} g[order[j]] * a[order[j]]):
-// the product with a gathered per-node row without materialising the gathered (rows x F) tensor.  F % 4 == 0.
-__global__ void mulg_fwd_kernel(const TP a, const TP t, const int64_t* __restrict__ idx, int64_t M, int F4, const TPW y, int rk) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)M * F4) return;
-  const int64_t row = i / F4;
-  const f32x4 tv = ld4(t, 4 * ((size_t)idx[row] * F4 + (int)(i % F4)));
-  f32x4 r = ld4(a, 4 * i) * tv;      // forward: a * t[idx];  backward wrt a: g * t[idx] (the caller passes g as `a`)
-  if (rk) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = round_kind(r[j], rk);
-  }
-  st4(y, 4 * i, r);
-}
-__global__ void mulg_segsum_kernel(const TP g, const TP a, const int64_t* __restrict__ order,
-                                   const int64_t* __restrict__ ptr, int64_t R, int F4, const TPW out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)R * F4) return;
-  const int64_t r = i / F4;
-  const int f = (int)(i % F4);
-  f32x4 s = splat4(0.f);
-  int64_t j = ptr[r];
-  const int64_t e = ptr[r + 1];
-  for (; j + 2 <= e; j += 2) {   // two rows in flight, additions in the same order
-    const size_t o0 = 4 * ((size_t)order[j] * F4 + f), o1 = 4 * ((size_t)order[j + 1] * F4 + f);
-    const f32x4 g0 = ld4(g, o0), a0 = ld4(a, o0), g1 = ld4(g, o1), a1 = ld4(a, o1);
-    s = s + g0 * a0;
-    s = s + g1 * a1;
-  }
-  for (; j < e; ++j) {
-    const size_t o = 4 * ((size_t)order[j] * F4 + f);
-    s = s + ld4(g, o) * ld4(a, o);
-  }
-  st4(out, 4 * i, s);
-}
-// out[r] = sum_{j in [ptr[r], ptr[r+1])} src[order[j]]   (sequential per element: bitwise deterministic)
-__global__ void segsum_rows_kernel(const float* __restrict__ src, const int64_t* __restrict__ order, const int64_t* __restrict__ ptr,
-                                   int64_t R, int F, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)R * F) return;
-  const int64_t r = i / F;
-  const int f = (int)(i % F);
-  float s = 0.f;
-  for (int64_t j = ptr[r]; j < ptr[r + 1]; ++j) s += src[(size_t)order[j] * F + f];
-  out[i] = s;
-}
-
-// The scalar form dealt to four threads per element (round 6; any F, fp32): the (E,3) force / position-gradient sums of the float16
-// mode ran one thread per (node, xyz) -- 19k threads, 28 dependent gathers each, 20 us per launch, 16 launches a step.  Only when the
-// caller allows another summation order (dt bit 2 of mdx_op_segsum_rows_t: the autocast mode; fp32 training keeps the sequential
-// order of the reference's index_add).
-__global__ __launch_bounds__(256) void segsum_rows1s_kernel(const float* __restrict__ src, const int64_t* __restrict__ order,
-                                                            const int64_t* __restrict__ ptr, int64_t R, int F, float* __restrict__ out) {
-  __shared__ float part[3][64];
-  const int k = threadIdx.x >> 6, it = threadIdx.x & 63;
-  const size_t i = (size_t)blockIdx.x * 64 + it;
-  const bool live = i < (size_t)R * F;
-  float s = 0.f;
-  if (live) {
-    const int64_t r = i / F;
-    const int f = (int)(i % F);
-    int64_t j = ptr[r] + k;
-    const int64_t e = ptr[r + 1];
-    for (; j + 12 < e; j += 16) {
-      const int64_t o0 = order[j], o1 = order[j + 4], o2 = order[j + 8], o3 = order[j + 12];
-      const float v0 = src[(size_t)o0 * F + f], v1 = src[(size_t)o1 * F + f], v2 = src[(size_t)o2 * F + f], v3 = src[(size_t)o3 * F + f];
-      s += v0;
-      s += v1;
-      s += v2;
-      s += v3;
-    }
-    for (; j < e; j += 4) s += src[(size_t)order[j] * F + f];
-  }
-  if (k) part[k - 1][it] = s;
-  __syncthreads();
-  if (k == 0 && live) out[i] = ((s + part[0][it]) + part[1][it]) + part[2][it];
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// edge geometry / smearing / force (reference models/graph.py:349-352, common.py GaussianSmearing, graph.py:391-394)
-// ------------------------------------------------------------------------------------------------------------------
-__global__ void edge_geom_fwd_kernel(const float* __restrict__ pos, const int64_t* __restrict__ l, const int64_t* __restrict__ r,
-                                     int64_t E, float* __restrict__ rel, float* __restrict__ dist) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const int64_t a = l[e], b = r[e];
-  const float dx = pos[3 * a] - pos[3 * b], dy = pos[3 * a + 1] - pos[3 * b + 1], dz = pos[3 * a + 2] - pos[3 * b + 2];
-  rel[3 * e] = dx; rel[3 * e + 1] = dy; rel[3 * e + 2] = dz;
-  dist[e] = sqrtf(dx * dx + dy * dy + dz * dz);
-}
-// g[e] = drel[e] + ddist[e] * rel[e] / dist[e]   (d|v|/dv = v/|v|; the reference's torch.norm has the 0/0 -> nan there too)
-__global__ void edge_geom_bwd_kernel(const float* __restrict__ rel, const float* __restrict__ dist, const float* __restrict__ drel,
-                                     const float* __restrict__ ddist, int64_t E, float* __restrict__ g) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const float k = ddist ? ddist[e] / dist[e] : 0.f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) g[3 * e + j] = (drel ? drel[3 * e + j] : 0.f) + k * rel[3 * e + j];
-}
-__global__ void smear_fwd_kernel(const float* __restrict__ d, const float* __restrict__ off, const float* __restrict__ coef, int G,
-                                 float lo, float hi, int64_t E, float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)E * G) return;
-  const int64_t e = i / G;
-  const int k = (int)(i % G);
-  const float u = fminf(fmaxf(d[e], lo), hi) - off[k];
-  out[i] = expf(coef[k] * (u * u));
-}
-__global__ void smear_bwd_kernel(const float* __restrict__ d, const float* __restrict__ off, const float* __restrict__ coef, int G,
-                                 float lo, float hi, int64_t E, const float* __restrict__ gout, float* __restrict__ gd) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const float dv = d[e];
-  float s = 0.f;
-  if (dv >= lo && dv <= hi) {  // clamp passes the gradient on the closed interval (torch.clamp semantics)
-    for (int k = 0; k < G; ++k) {
-      const float u = dv - off[k];
-      s += gout[(size_t)e * G + k] * expf(coef[k] * (u * u)) * 2.0f * coef[k] * u;
-    }
-  }
-  gd[e] = s;
-}
-// F = w * rel / d / (d + 1)
-__global__ void force_fwd_kernel(const float* __restrict__ w, const float* __restrict__ rel, const float* __restrict__ d, int64_t E,
-                                 float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const float dv = d[e], dp = dv + 1.0f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) out[3 * e + j] = w[e] * rel[3 * e + j] / dv / dp;
-}
-__global__ void force_bwd_kernel(const float* __restrict__ w, const float* __restrict__ rel, const float* __restrict__ d,
-                                 const float* __restrict__ g, int64_t E, float* __restrict__ gw, float* __restrict__ grel,
-                                 float* __restrict__ gd) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const float dv = d[e], dp = dv + 1.0f, wv = w[e];
-  const float inv = 1.0f / (dv * dp);
-  float dot = 0.f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    dot = fmaf(g[3 * e + j], rel[3 * e + j], dot);
-    grel[3 * e + j] = g[3 * e + j] * wv * inv;
-  }
-  gw[e] = dot * inv;
-  // d/dd [1/(d (d+1))] = -(2d + 1) / (d (d+1))^2
-  gd[e] = -wv * dot * (2.0f * dv + 1.0f) * inv * inv;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// optimizer step on the flat parameter buffer (torch.optim.AdamW semantics, utils/train.py:64-70 of the reference):
-//   sumsq   : sum of squares of the flat gradient in two fixed-order stages (-> global norm for clip_grad_norm_)
-//   adamw   : g *= gscale ; p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
-//             p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
-// ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
-  __shared__ float sh[4];
-  const size_t per = ((n + gridDim.x - 1) / gridDim.x + 1023) / 1024 * 1024;
-  const size_t i0 = min(n, (size_t)blockIdx.x * per), i1 = min(n, i0 + per);
-  float s = 0.f;
-  if ((per & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-    // 16-byte loads, four in flight per thread (round 6: one scalar load in flight made the 40 MB gradient norm a 107-us kernel)
-    f32x4 a0 = splat4(0.f), a1 = splat4(0.f), a2 = splat4(0.f), a3 = splat4(0.f);
-    size_t i = i0 + 4 * (size_t)threadIdx.x;
-    for (; i + 3 * 1024 + 3 < i1; i += 4096) {
-      const f32x4 v0 = ldg4(x + i), v1 = ldg4(x + i + 1024), v2 = ldg4(x + i + 2048), v3 = ldg4(x + i + 3072);
-      a0 = a0 + v0 * v0, a1 = a1 + v1 * v1, a2 = a2 + v2 * v2, a3 = a3 + v3 * v3;
-    }
-    for (; i + 3 < i1; i += 1024) {
-      const f32x4 v = ldg4(x + i);
-      a0 = a0 + v * v;
-    }
-    for (; i < i1; ++i) s = fmaf(x[i], x[i], s);     // (at most three elements of the buffer's tail, in the last block's last lane)
-    const f32x4 a = (a0 + a1) + (a2 + a3);
-    s += (a[0] + a[1]) + (a[2] + a[3]);
-  } else {
-    for (size_t i = i0 + threadIdx.x; i < i1; i += 256) s = fmaf(x[i], x[i], s);
-  }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-__global__ void sum_small_kernel(const float* __restrict__ x, int n, float* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < n; ++i) s += x[i];
-    out[0] = s;
-  }
-}
-// gnorm2: device scalar holding the squared global gradient norm (or NULL = no clipping)
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                             const float* __restrict__ gnorm2, float max_norm) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float gs = 1.0f;
-  if (gnorm2) {
-    // a non-finite gradient norm skips the whole update, like GradScaler / the reference's try-except around the
-    // iteration (scripts/train_drug3d.py:93-119): fminf(NaN, 1) would be 1 and write NaNs into p, m and v for good
-    if (!isfinite(gnorm2[0])) return;
-    gs = fminf(max_norm / (sqrtf(gnorm2[0]) + 1e-6f), 1.0f);
-  }
-  const float gi = g[i] * gs;
-  float pi = p[i] * (1.0f - lr * wd);
-  const float mi = b1 * m[i] + (1.0f - b1) * gi;
-  const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-  p[i] = pi;
-}
-
-// ---- GradScaler-equivalent step with its state on the device (scripts/train_drug3d.py:105-109: scaler.scale(loss).backward(),
-// unscale_, clip_grad_norm_, scaler.step, scaler.update) ----
-// state: [0] loss scale S  [1] growth tracker  [2] optimizer steps taken  [3] steps skipped  [4] unscaled squared gradient norm of the
-//        last step (inf / nan when a gradient overflowed)  [5] apply flag  [6] gradient multiplier (1/S x clip factor)  [7] 1 - b1^t
-//        [8] sqrt(1 - b2^t)
-constexpr int AMP_STATE = 16;
-__global__ void amp_decide_kernel(const float* __restrict__ part, int nparts, float* __restrict__ st, float b1, float b2, float max_norm,
-                                  float growth, float backoff, int growth_interval) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  float tot = 0.f;
-  for (int i = 0; i < nparts; ++i) tot += part[i];
-  const float S = st[0], inv = 1.0f / S;
-  const float n2 = tot * inv * inv;
-  st[4] = n2;
-  if (isfinite(n2)) {
-    const float t = st[2] + 1.0f;
-    st[2] = t;
-    st[5] = 1.0f;
-    st[6] = inv * fminf(max_norm / (sqrtf(n2) + 1e-6f), 1.0f);
-    st[7] = 1.0f - powf(b1, t);
-    st[8] = sqrtf(1.0f - powf(b2, t));
-    const float tr = st[1] + 1.0f;
-    if (growth_interval > 0 && tr >= (float)growth_interval) {
-      st[0] = S * growth;
-      st[1] = 0.f;
-    } else {
-      st[1] = tr;
-    }
-  } else {  // found_inf: the optimizer does not step (its step count and moments stay), the scale backs off
-    st[5] = 0.f;
-    st[3] += 1.0f;
-    st[0] = S * backoff;
-    st[1] = 0.f;
-  }
-}
-__global__ void adamw_amp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                 float lr, float b1, float b2, float eps, float wd, const float* __restrict__ st) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || st[5] == 0.f) return;
-  const float gi = g[i] * st[6];
-  float pi = p[i] * (1.0f - lr * wd);
-  const float mi = b1 * m[i] + (1.0f - b1) * gi;
-  const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  pi -= (lr / st[7]) * mi / (sqrtf(vi) / st[8] + eps);
-  p[i] = pi;
-}
-
-inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
-inline int bad(const char* m) { return mdx_set_error(MDX_ERR_ARG, m); }
-// A run-time integer as a template argument: calls f(std::integral_constant<int, V>{}) for the V among Vs that equals v; false if none does.
-template <int... Vs, class F>
-inline bool pick(int v, F&& f) {
-  return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
-}
 // out (M x N, ld) = bias + sum over the S partial copies in P; more than RED_CHUNK copies go through `scratch`
-// (ceil(S / RED_CHUNK) * M * N floats) in two fixed-order stages.
-inline void launch_reduce_partials(const float* P, int S, int M, int N, const float* bias, float* out, int ld, float* scratch,
-                                   hipStream_t s, int rkind = 0) {
+// (ceil(S / RED_CHUNK) * M * N floats) in two fixed-order stages.  (Declared in mdx_train_launch.h: the LayerNorm backward of
+// mdx_train_rows.hip ends in it.)
+void launch_reduce_partials(const float* P, int S, int M, int N, const float* bias, float* out, int ld, float* scratch, hipStream_t s,
+                            int rkind) {
   const size_t total = (size_t)M * N;
   const unsigned gx = (unsigned)((total + 31) / 32);
   if (S <= RED_CHUNK || !scratch) {
@@ -1886,7 +1087,7 @@ inline void launch_reduce_partials(const float* P, int S, int M, int N, const fl
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(gx, 1), dim3(256), 0, s, (const float*)scratch, nc, nc, M, N, bias, out, ld, rkind);
 }
 // The end of a split weight gradient: dW (N x K, ldw) and, with db, db (N) from the partials a SplitLayout places in `partial`.
-inline void finish_split(float* partial, const SplitLayout& L, int N, int K, float* dW, int ldw, float* db, int rkind, hipStream_t s) {
+static void finish_split(float* partial, const SplitLayout& L, int N, int K, float* dW, int ldw, float* db, int rkind, hipStream_t s) {
   const int S = (int)L.S;
   float* pb = partial + L.bias_off;
   if (db && S <= RED_CHUNK) {  // both reductions in one launch
@@ -1898,12 +1099,6 @@ inline void finish_split(float* partial, const SplitLayout& L, int N, int K, flo
     if (db) launch_reduce_partials(pb, S, 1, N, nullptr, db, N, pb + (size_t)S * N, s, rkind);
   }
 }
-inline int launched() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, hipGetErrorString(e));
-}
-
-}  // namespace
 
 extern "C" int mdx_op_sgemm_nt(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, const float* addend,
                                int64_t ldd, float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int32_t splits, float* partial,
@@ -1986,238 +1181,6 @@ extern "C" int mdx_op_colreduce(const float* X, const float* Y, int64_t ld, int6
   if (!ws) return bad("colreduce: workspace of ceil(M/512)*N floats required");
   hipLaunchKernelGGL(colreduce_kernel, dim3(gx, nb), dim3(256), 0, s, X, Y, (int)ld, (int)M, (int)N, RP, ws);
   hipLaunchKernelGGL(colreduce_kernel, dim3(gx, 1), dim3(256), 0, s, (const float*)ws, (const float*)nullptr, (int)N, nb, (int)N, nb, out);
-  return launched();
-}
-
-// `_t` forms of the row operators: dt = bit mask of the tensors stored as float16 (ln_relu_fwd: bit 0 x, 1 y; ln_relu_bwd: bit 0 dy, 1 x,
-// 2 dx; ew_fwd: 0 a, 1 b, 2 out; ew_bwd: 0 a, 1 b, 2 g, 3 da, 4 db; gather_rows: 0 x, 1 y; segsum_rows: 0 src, 1 out; mul_gather_fwd:
-// 0 a, 1 t, 2 y; mul_gather_bwd: 0 g, 1 a, 2 t, 3 da, 4 dt).  Half storage needs the 4-wide kernels (F % 4 == 0, aligned rows).
-extern "C" int mdx_op_ln_relu_fwd_t(const void* xv, const float* gamma, const float* beta, int64_t M, int32_t F, int32_t relu, void* yv,
-                                    float* stats, int32_t dt, void* stream) {
-  if (M <= 0) return MDX_OK;
-  if (F <= 0 || F > 64 * LN_MAXJ) return bad("ln_relu: feature count must be in 1..1024");
-  const TP x{xv, dt & 1};
-  const TPW y{yv, (dt >> 1) & 1};
-  const bool al = tp_vec_ok(xv, x.h, 4) && tp_vec_ok(yv, y.h, 4);
-  if (al && F % 4 == 0 && pick<8, 16, 32, 64>(F / 4, [&](auto LPR) {   // LPR lanes per row, four features each
-        hipLaunchKernelGGL(ln_relu_fwd4_kernel<LPR>, dim3((unsigned)((M + 4 * (64 / LPR) - 1) / (4 * (64 / LPR)))), dim3(256), 0,
-                           (hipStream_t)stream, x, gamma, beta, (int)M, relu, y, stats);
-      }))
-    return launched();
-  if (dt) return bad("ln_relu: half storage needs F in {32, 64, 128, 256} and aligned rows");
-  hipLaunchKernelGGL(ln_relu_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)xv, gamma, beta,
-                     (int)M, F, relu, (float*)yv, stats);
-  return launched();
-}
-
-// The 4-wide backward kernel for F in {32, 64, 128, 256} (false: not built for F), one workgroup per partial row of ws; w1 != NULL is the
-// rank-1 form (dy holds M values).  The callers check alignment.
-static bool launch_ln_bwd4(const TP& dy, const TP& x, const float* stats, const float* gamma, const float* beta, int64_t M, int32_t F,
-                           int32_t relu, const TPW& dx, float* ws, const float* w1, hipStream_t s) {
-  return F % 4 == 0 && pick<8, 16, 32, 64>(F / 4, [&](auto LPR) {
-    hipLaunchKernelGGL(ln_relu_bwd4_kernel<LPR>, dim3((unsigned)ln_bwd_rows(M)), dim3(256), 32 * F, s, dy, x, stats, gamma, beta, (int)M, relu,
-                       MDX_LN_RPW, dx, ws, w1);
-  });
-}
-// dx (M,F); dgb (2F) = [dgamma | dbeta].  ws: mdx_op_ln_relu_bwd_ws(M, F) bytes.
-extern "C" int mdx_op_ln_relu_bwd_t(const void* dyv, const void* xv, const float* stats, const float* gamma, const float* beta, int64_t M,
-                                    int32_t F, int32_t relu, void* dxv, float* dgb, float* ws, int32_t dt, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (F <= 0 || F > 64 * LN_MAXJ) return bad("ln_relu: feature count must be in 1..1024");
-  if (M <= 0) return !dgb || hipMemsetAsync(dgb, 0, (size_t)F * 8, s) == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "memset");
-  if (!ws) return bad("ln_relu_bwd: workspace required");
-  const TP dy{dyv, dt & 1}, x{xv, (dt >> 1) & 1};
-  const TPW dx{dxv, (dt >> 2) & 1};
-  const int nr = (int)ln_bwd_rows(M);            // workgroups of four waves; `ws` gets one partial row from each
-  const bool al = tp_vec_ok(xv, x.h, 4) && tp_vec_ok(dyv, dy.h, 4) && tp_vec_ok(dxv, dx.h, 4) && ((reinterpret_cast<uintptr_t>(ws) & 15) == 0);
-  if (!(al && launch_ln_bwd4(dy, x, stats, gamma, beta, M, F, relu, dx, ws, nullptr, s))) {
-    if (dt) return bad("ln_relu_bwd: half storage needs F in {32, 64, 128, 256} and aligned rows");
-    hipLaunchKernelGGL(ln_relu_bwd_kernel, dim3((unsigned)nr), dim3(256), 32 * F, s, (const float*)dyv, (const float*)xv, stats, gamma, beta,
-                       (int)M, F, relu, MDX_LN_RPW, (float*)dxv, ws);
-  }
-  // [dgamma | dbeta] = sum over the per-workgroup partial rows, fixed-order parallel reduction (dgb == NULL: deferred, the partial rows
-  // stay in ws for mdx_op_reduce_deferred)
-  if (dgb) launch_reduce_partials(ws, nr, 1, 2 * F, nullptr, dgb, 2 * F, ws + (size_t)nr * 2 * F, s);
-  return launched();
-}
-extern "C" int mdx_op_ln_relu_bwd_r1_t(const void* g1, const float* w1, const void* xv, const float* stats, const float* gamma, const float* beta,
-                                       int64_t M, int32_t F, int32_t relu, void* dxv, float* ws, int32_t dt, void* stream) {
-  if (M <= 0) return MDX_OK;
-  if (!g1 || !w1 || !xv || !stats || !gamma || !beta || !dxv || !ws) return bad("ln_relu_bwd_r1: null operand");
-  const TP dy{g1, dt & 1}, x{xv, (dt >> 1) & 1};
-  const TPW dx{dxv, (dt >> 2) & 1};
-  if (!(tp_vec_ok(xv, x.h, 4) && tp_vec_ok(dxv, dx.h, 4) && ((reinterpret_cast<uintptr_t>(ws) & 15) == 0)))
-    return mdx_set_error(MDX_ERR_UNSUPPORTED, "ln_relu_bwd_r1: aligned rows required");
-  if (!launch_ln_bwd4(dy, x, stats, gamma, beta, M, F, relu, dx, ws, w1, (hipStream_t)stream))
-    return mdx_set_error(MDX_ERR_UNSUPPORTED, "ln_relu_bwd_r1: F must be 32, 64, 128 or 256");
-  return launched();
-}
-extern "C" size_t mdx_op_ln_relu_bwd_ws(int64_t M, int32_t F) { return (size_t)ln_bwd_ws_floats(M, F) * sizeof(float); }
-extern "C" int64_t mdx_op_ln_relu_bwd_rows(int64_t M) { return ln_bwd_rows(M); }  // partial rows mdx_op_ln_relu_bwd leaves in ws ([rows][2F])
-
-extern "C" int mdx_op_ew_fwd_t(int32_t op, const void* a, const void* b, void* out, int64_t n, int32_t dt, void* stream) {
-  if (n <= 0) return MDX_OK;
-  if ((op & 255) > 3 || (op >> 8) < 0 || (op >> 8) > 2) return bad("ew: unknown op");
-  const TP ta{a, dt & 1}, tb{b, (dt >> 1) & 1};
-  const TPW to{out, (dt >> 2) & 1};
-  if ((n & 3) == 0 && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(b, tb.h, 4) && tp_vec_ok(out, to.h, 4)) {
-    hipLaunchKernelGGL(ew_fwd4_kernel, dim3(nblk((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, to, (size_t)n / 4);
-  } else {
-    hipLaunchKernelGGL(ew_fwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, to, (size_t)n);
-  }
-  return launched();
-}
-extern "C" int mdx_op_plan_flip(const int64_t* order_left, const int64_t* ptr, int64_t R, int64_t Eh, int64_t* order_right, void* stream) {
-  if (R <= 0) return MDX_OK;
-  if (!order_left || !ptr || !order_right || Eh < 0) return bad("plan_flip: null argument");
-  hipLaunchKernelGGL(plan_flip_kernel, dim3(nblk((size_t)R)), dim3(256), 0, (hipStream_t)stream, order_left, ptr, R, Eh, order_right);
-  return launched();
-}
-extern "C" int mdx_op_sum_n(const void* const* srcs, const int32_t* half, int32_t k, int64_t n, void* out, int32_t out_half, void* stream) {
-  if (n <= 0) return MDX_OK;
-  if (k < 1 || k > 12 || !srcs || !half || !out) return bad("sum_n: 1..12 operands");
-  SumN a;
-  bool vec = (n & 3) == 0 && tp_vec_ok(out, out_half, 4);
-  for (int j = 0; j < k; ++j) {
-    if (!srcs[j]) return bad("sum_n: null operand");
-    a.p[j] = srcs[j], a.h[j] = half[j] ? 1 : 0;
-    vec = vec && tp_vec_ok(srcs[j], a.h[j], 4);
-  }
-  a.n = k;
-  const TPW to{out, out_half ? 1 : 0};
-  if (vec) hipLaunchKernelGGL(sum_n4_kernel, dim3(nblk((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream, a, to, (size_t)n / 4);
-  else hipLaunchKernelGGL(sum_n1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, a, to, (size_t)n);
-  return launched();
-}
-extern "C" int mdx_op_ew_bwd_t(int32_t op, const void* a, const void* b, const void* g, void* da, void* db, int64_t n, int32_t dt,
-                               void* stream) {
-  if (n <= 0) return MDX_OK;
-  if (op < 0 || op > 3) return bad("ew: unknown op");
-  const TP ta{a, dt & 1}, tb{b, (dt >> 1) & 1}, tg{g, (dt >> 2) & 1};
-  const TPW tda{da, (dt >> 3) & 1}, tdb{db, (dt >> 4) & 1};
-  if ((n & 3) == 0 && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(b, tb.h, 4) && tp_vec_ok(g, tg.h, 4) && tp_vec_ok(da, tda.h, 4) &&
-      tp_vec_ok(db, tdb.h, 4)) {
-    hipLaunchKernelGGL(ew_bwd4_kernel, dim3(nblk((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, tg, tda, tdb, (size_t)n / 4);
-  } else {
-    hipLaunchKernelGGL(ew_bwd1_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, ta, tb, tg, tda, tdb, (size_t)n);
-  }
-  return launched();
-}
-extern "C" int mdx_op_gather_rows_t(const void* x, const int64_t* idx, int64_t M, int32_t F, void* y, int32_t dt, void* stream) {
-  if (M <= 0 || F <= 0) return MDX_OK;
-  const TP tx{x, dt & 1};
-  const TPW ty{y, (dt >> 1) & 1};
-  if ((F & 3) == 0 && tp_vec_ok(x, tx.h, 4) && tp_vec_ok(y, ty.h, 4)) {
-    hipLaunchKernelGGL(gather_rows4_kernel, dim3(nblk((size_t)M * (F / 4))), dim3(256), 0, (hipStream_t)stream, tx, idx, M, F / 4, ty);
-  } else {
-    if (dt) return bad("gather_rows: half storage needs F % 4 == 0 and aligned rows");
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(nblk((size_t)M * F)), dim3(256), 0, (hipStream_t)stream, (const float*)x, idx, M, F, (float*)y);
-  }
-  return launched();
-}
-extern "C" int mdx_op_segsum_rows_t(const void* src, const int64_t* order, const int64_t* ptr, int64_t R, int32_t F, void* out, int32_t dt,
-                                    void* stream) {
-  if (R <= 0 || F <= 0) return MDX_OK;
-  const TP ts{src, dt & 1};
-  const TPW to{out, (dt >> 1) & 1};
-  if ((F & 3) == 0 && tp_vec_ok(src, ts.h, 4) && tp_vec_ok(out, to.h, 4)) {
-    const size_t items = (size_t)R * (F / 4);
-    // float16 rows only: the fp32 mode keeps the sequential CSR order -- the order of torch's index_add on the CPU, i.e. of the reference
-    // and the oracle, which its parity tests rely on (a 32-wide LayerNorm gain's gradient moved from 4.8e-5 to 1.6e-4 of its norm at
-    // 256 molecules with the dealt order; both are fp32 rounding, but the contract there is 1e-4)
-    if (ts.h && (F & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && items < ((size_t)1 << 22))
-      hipLaunchKernelGGL(segsum_rows8s_kernel, dim3((unsigned)(((size_t)R * (F / 8) + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
-                         reinterpret_cast<const _Float16*>(src), order, ptr, R, F / 8, to);
-    else if ((ts.h || (dt & 4)) && items < ((size_t)1 << 22))
-      hipLaunchKernelGGL(segsum_rows4s_kernel, dim3((unsigned)((items + 63) / 64)), dim3(256), 0, (hipStream_t)stream, ts, order, ptr, R, F / 4, to);
-    else
-      hipLaunchKernelGGL(segsum_rows4_kernel, dim3(nblk(items)), dim3(256), 0, (hipStream_t)stream, ts, order, ptr, R, F / 4, to);
-  } else {
-    if (dt & 3) return bad("segsum_rows: half storage needs F % 4 == 0 and aligned rows");
-    if (dt & 4)
-      hipLaunchKernelGGL(segsum_rows1s_kernel, dim3((unsigned)(((size_t)R * F + 63) / 64)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
-                         order, ptr, R, F, (float*)out);
-    else
-      hipLaunchKernelGGL(segsum_rows_kernel, dim3(nblk((size_t)R * F)), dim3(256), 0, (hipStream_t)stream, (const float*)src, order, ptr, R, F,
-                         (float*)out);
-  }
-  return launched();
-}
-extern "C" int mdx_op_edge_geom_fwd(const float* pos, const int64_t* l, const int64_t* r, int64_t E, float* rel, float* dist, void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(edge_geom_fwd_kernel, dim3(nblk((size_t)E)), dim3(256), 0, (hipStream_t)stream, pos, l, r, E, rel, dist);
-  return launched();
-}
-extern "C" int mdx_op_edge_geom_bwd(const float* rel, const float* dist, const float* drel, const float* ddist, int64_t E, float* g,
-                                    void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(edge_geom_bwd_kernel, dim3(nblk((size_t)E)), dim3(256), 0, (hipStream_t)stream, rel, dist, drel, ddist, E, g);
-  return launched();
-}
-extern "C" int mdx_op_smear_fwd(const float* d, const float* off, const float* coef, int32_t G, float lo, float hi, int64_t E, float* out,
-                                void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(smear_fwd_kernel, dim3(nblk((size_t)E * G)), dim3(256), 0, (hipStream_t)stream, d, off, coef, G, lo, hi, E, out);
-  return launched();
-}
-extern "C" int mdx_op_smear_bwd(const float* d, const float* off, const float* coef, int32_t G, float lo, float hi, int64_t E,
-                                const float* gout, float* gd, void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(smear_bwd_kernel, dim3(nblk((size_t)E)), dim3(256), 0, (hipStream_t)stream, d, off, coef, G, lo, hi, E, gout, gd);
-  return launched();
-}
-extern "C" int mdx_op_force_fwd(const float* w, const float* rel, const float* d, int64_t E, float* out, void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(force_fwd_kernel, dim3(nblk((size_t)E)), dim3(256), 0, (hipStream_t)stream, w, rel, d, E, out);
-  return launched();
-}
-extern "C" int mdx_op_force_bwd(const float* w, const float* rel, const float* d, const float* g, int64_t E, float* gw, float* grel,
-                                float* gd, void* stream) {
-  if (E <= 0) return MDX_OK;
-  hipLaunchKernelGGL(force_bwd_kernel, dim3(nblk((size_t)E)), dim3(256), 0, (hipStream_t)stream, w, rel, d, g, E, gw, grel, gd);
-  return launched();
-}
-
-// out[0] = sum x[i]^2 over the flat buffer (two fixed-order stages; ws: 1024 floats).
-extern "C" int mdx_op_sumsq(const float* x, int64_t n, float* out, float* ws, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!out || !ws) return bad("sumsq: null output / workspace");
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 8191) / 8192));
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, s, x, (size_t)std::max<int64_t>(n, 0), ws);
-  hipLaunchKernelGGL(sum_small_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, nb, out);
-  return launched();
-}
-// One AdamW step over flat (p, g, m, v); step = 1, 2, ...  gnorm2 (device scalar, may be NULL) + max_norm apply
-// torch.nn.utils.clip_grad_norm_ to g on the fly (g itself is left unscaled).
-extern "C" int mdx_op_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                            float weight_decay, int64_t step, const float* gnorm2, float max_norm, void* stream) {
-  if (n <= 0) return MDX_OK;
-  if (step < 1) return bad("adamw: step counts from 1");
-  const float bc1 = 1.0f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(nblk((size_t)n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (size_t)n, lr, beta1, beta2, eps,
-                     weight_decay, bc1, bc2s, gnorm2, max_norm);
-  return launched();
-}
-
-// One optimisation step with torch.cuda.amp.GradScaler semantics, state on the device (see amp_decide_kernel): g holds the
-// gradient of (S x loss).  Unscales, measures the global norm (state[4], unscaled), clips to max_norm (<= 0 or inf: no clipping),
-// and applies AdamW -- or, if any gradient is not finite, skips the update (the step count does not advance) and multiplies S by
-// `backoff`; after `growth_interval` consecutive finite steps S is multiplied by `growth`.  With S = growth = backoff = 1 this is the
-// plain fp32 step.  ws: 1024 floats.  No host synchronisation.
-extern "C" int mdx_op_amp_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, float max_norm, float* state, float growth, float backoff, int32_t growth_interval,
-                                float* ws, void* stream) {
-  if (n <= 0) return MDX_OK;
-  if (!p || !g || !m || !v || !state || !ws) return bad("amp_adamw: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n + 8191) / 8192));
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, s, g, (size_t)n, ws);
-  const float mn = (max_norm > 0.f) ? max_norm : INFINITY;
-  hipLaunchKernelGGL(amp_decide_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, nb, state, beta1, beta2, mn, growth, backoff,
-                     (int)growth_interval);
-  hipLaunchKernelGGL(adamw_amp_kernel, dim3(nblk((size_t)n)), dim3(256), 0, s, p, g, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay,
-                     (const float*)state);
   return launched();
 }
 
@@ -2503,41 +1466,4 @@ extern "C" int mdx_op_wgrad_grouped(const int64_t* desc, int32_t n, int64_t tota
                        reinterpret_cast<const long long*>(desc), (int)n);
   });
   return known ? launched() : bad("wgrad_grouped: kind must be 0..7");
-}
-
-// y = a * t[idx] (rows of F floats, F % 4 == 0) and its gradients; see mulg_*_kernel.
-// F: feature count in its low 16 bits; bits 16.. = rounding kind of the product (0 fp32, 1 bfloat16, 2 float16; mixed precision)
-extern "C" int mdx_op_mul_gather_fwd_t(const void* a, const void* t, const int64_t* idx, int64_t M, int32_t F, void* y, int32_t dt,
-                                       void* stream) {
-  const int rk = F >> 16;
-  F &= 0xffff;
-  if (M <= 0 || F <= 0) return MDX_OK;
-  if (F & 3) return bad("mul_gather: F must be a multiple of 4");
-  if (rk < 0 || rk > 2) return bad("mul_gather: unknown rounding kind");
-  const TP ta{a, dt & 1}, tt{t, (dt >> 1) & 1};
-  const TPW ty{y, (dt >> 2) & 1};
-  if (!(tp_vec_ok(a, ta.h, 4) && tp_vec_ok(t, tt.h, 4) && tp_vec_ok(y, ty.h, 4))) return bad("mul_gather: rows must be aligned");
-  hipLaunchKernelGGL(mulg_fwd_kernel, dim3(nblk((size_t)M * (F / 4))), dim3(256), 0, (hipStream_t)stream, ta, tt, idx, M, F / 4, ty, rk);
-  return launched();
-}
-extern "C" int mdx_op_mul_gather_bwd_t(const void* g, const void* a, const void* t, const int64_t* idx, const int64_t* order,
-                                       const int64_t* ptr, int64_t M, int64_t R, int32_t F, void* da, void* dtab, int32_t dt, void* stream) {
-  if (F <= 0) return MDX_OK;
-  if (F & 3) return bad("mul_gather: F must be a multiple of 4");
-  hipStream_t s = (hipStream_t)stream;
-  const TP tg{g, dt & 1}, ta{a, (dt >> 1) & 1}, tt{t, (dt >> 2) & 1};
-  const TPW tda{da, (dt >> 3) & 1}, tdt{dtab, (dt >> 4) & 1};
-  const bool want_da = da && M > 0, want_dt = dtab && R > 0;
-  // operands of the launches below (no rows: every segment is empty and g / a are never read)
-  if (want_da && (!g || !t || !idx)) return bad("mul_gather_bwd: null operand");
-  if (want_dt && (!order || !ptr || (M > 0 && (!g || !a)))) return bad("mul_gather_bwd: null operand");
-  // the 4-wide kernels read and write 16-byte (float16: 8-byte) vectors: refuse a misaligned base like the forward does
-  if ((want_da && !(tp_vec_ok(g, tg.h, 4) && tp_vec_ok(t, tt.h, 4) && tp_vec_ok(da, tda.h, 4))) ||
-      (want_dt && !(tp_vec_ok(g, tg.h, 4) && tp_vec_ok(a, ta.h, 4) && tp_vec_ok(dtab, tdt.h, 4))))
-    return bad("mul_gather: rows must be aligned");
-  if (want_da)
-    hipLaunchKernelGGL(mulg_fwd_kernel, dim3(nblk((size_t)M * (F / 4))), dim3(256), 0, s, tg, tt, idx, M, F / 4, tda, 0);
-  if (want_dt)
-    hipLaunchKernelGGL(mulg_segsum_kernel, dim3(nblk((size_t)R * (F / 4))), dim3(256), 0, s, tg, ta, order, ptr, R, F / 4, tdt);
-  return launched();
 }

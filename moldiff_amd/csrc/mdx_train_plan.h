@@ -1,4 +1,4 @@
-// Host arithmetic of the training operators (mdx_train.hip) that more than one place has to agree on: where the split partials of a
+// Host arithmetic of the training operators (mdx_train.hip, mdx_train_rows.hip) that more than one place has to agree on: where the split partials of a
 // weight gradient live, which tile class a queued weight gradient takes, how many partial rows the LayerNorm backward leaves, how the
 // deferred reduction numbers its blocks, and which shapes the row-owner GEMM takes.  Plain C++17, no HIP and no torch: mdx_train.hip
 // (launchers and reduce_deferred_kernel) and mdx_fast.cpp (buffer sizes, the gradient sink's record table) include it, and

@@ -1,4 +1,4 @@
-"""Each layer operator of the training path (csrc/mdx_train.hip via moldiff_amd/train_ops.py) against the torch op it
+"""Each layer operator of the training path (csrc/mdx_train.hip, csrc/mdx_train_rows.hip via moldiff_amd/train_ops.py) against the torch op it
 replaces: forward values and every gradient, on awkward shapes (K, N not multiples of 4/16, ragged segments, empty
 segments).  fp32; tolerances relative to the magnitude of the quantity compared."""
 import numpy as np
@@ -394,7 +394,7 @@ def test_flipped_plan_equals_a_second_stable_sort():
 @pytest.mark.parametrize('half', [False, True])
 def test_fanout_sums_the_consumers_gradients_in_one_launch(half):
     """Round 6: T.fanout hands a tensor to k consumers as aliases of one node whose backward is a single k-input sum (csrc
-    sum_n4_kernel: fp32 accumulation, one rounding) -- equal to autograd's pairwise accumulation up to the rounding of the container."""
+    sum_n_kernel<4>: fp32 accumulation, one rounding) -- equal to autograd's pairwise accumulation up to the rounding of the container."""
     g = U.rng(5)
     x = _leaf(g, 515, 64)
     ws = [U.t32(g.standard_normal((515, 64))).to(DEV) for _ in range(7)]

@@ -1,4 +1,4 @@
-"""The typed row operators of the training path (csrc/mdx_train.hip `mdx_op_*_t`, reached through moldiff_amd/train_ops.py) with float16
+"""The typed row operators of the training path (csrc/mdx_train_rows.hip and csrc/mdx_train.hip `mdx_op_*_t`, reached through moldiff_amd/train_ops.py) with float16
 CONTAINERS, one operator at a time, against a float64 restatement of that operator on the same float16-representable inputs.
 
 Rounding model of every bound below: the kernels compute in fp32 and round to nearest even ONCE into the container at each stated
@@ -145,7 +145,7 @@ def _gate_rounds_the_sigmoid(case, a, b, got):
 @pytest.mark.parametrize('shape', [(1024, 8), (1237, 1), (333, 7)])
 def test_elementwise_pair_in_float16_containers(opname, shape):
     """out, da, db of add / sub / mul / gate on float16 containers under precision('fp16'): (1024, 8) takes the 4-wide kernels
-    (ew_fwd4 / ew_bwd4), (1237, 1) and (333, 7) the scalar float16 kernels (ew_fwd1 / ew_bwd1: n % 4 != 0).
+    (ew_fwd_kernel<4> / ew_bwd_kernel<4>), (1237, 1) and (333, 7) the scalar float16 kernels (ew_fwd_kernel<1> / ew_bwd_kernel<1>: n % 4 != 0).
     Model: add / sub = one fp32 addition, one rounding; their gradients are copies (exact).  mul and its gradients = the exact product of
     two float16 values rounded once: must EQUAL f16(a b).  gate = f16(a * f16(sigmoid(b))): see _ew_model; b holds +-12 and +-20."""
     g = U.rng(101)
@@ -219,7 +219,7 @@ def test_elementwise_backward_with_one_gradient_only(opname, shape):
 
 
 @pytest.mark.parametrize('opname', ['mul', 'gate'])
-@pytest.mark.parametrize('n', [2048, 1237])          # ew_fwd4_kernel / ew_fwd1_kernel
+@pytest.mark.parametrize('n', [2048, 1237])          # ew_fwd_kernel<4> / ew_fwd_kernel<1>
 def test_float16_product_into_an_fp32_container_is_still_a_float16_value(opname, n):
     """mdx_op_ew_fwd_t with float16 operands and an fp32 result (dt = 3, a mask the wrappers do not produce) and rounding kind 2: the
     container does not round, so only the kernel's own rounding makes the result a float16 value -- f16(a b) exactly for mul."""
@@ -256,7 +256,7 @@ def _sum_n_bound(srcs, out_half):
 
 
 @pytest.mark.parametrize('k', [3, 12])
-@pytest.mark.parametrize('shape', [(256, 8), (515, 3)])       # sum_n4_kernel / sum_n1_kernel (n % 4 != 0)
+@pytest.mark.parametrize('shape', [(256, 8), (515, 3)])       # sum_n_kernel<4> / sum_n_kernel<1> (n % 4 != 0)
 @pytest.mark.parametrize('half', [True, False])
 def test_fanout_gradient_is_one_fp32_sum_rounded_once(k, shape, half):
     """T.fanout's backward (mdx_op_sum_n): the fp32 sum of the k consumers' gradients in argument order, rounded ONCE into x's
@@ -340,7 +340,7 @@ def _segsum_direct(src, plan, out_dtype, extra=0):
 @pytest.mark.parametrize('Fd', [4, 12, 64, 256])
 def test_gather_and_segment_sum_of_float16_rows(Fd):
     """Every container mask the wrappers produce for float16 rows, on the designed segment lengths.  F % 8 != 0 (4, 12) takes
-    segsum_rows4s_kernel, F % 8 == 0 (64, 256) segsum_rows8s_kernel.
+    segsum_rows_kernel<4, 4>, F % 8 == 0 (64, 256) segsum_rows_kernel<8, 4>.
     gather forward float16 -> float16: a copy (exact).  Its backward, a segment sum float16 -> float16: fp32 sum of the segment's
     rows, one rounding.  scatter_sum forward float16 -> fp32: the fp32 sum, no rounding.  Its backward, a gather fp32 -> float16:
     the fp32 gradient rounded once (exact).  Empty segments are exact zeros (their bound is the subnormal term alone / zero)."""
@@ -368,7 +368,7 @@ def test_gather_and_segment_sum_of_float16_rows(Fd):
 @pytest.mark.parametrize('Fd', [3, 8])
 def test_segment_sum_of_fp32_rows_in_the_autocast_mode(Fd):
     """fp32 rows with the autocast bit (dt & 4; what train_ops sets under precision('fp16')): F = 3 takes the dealt scalar kernel
-    segsum_rows1s_kernel, F = 8 segsum_rows4s_kernel on fp32 rows.  Model: an fp32 sum (any order), fp32 result."""
+    segsum_rows_kernel<1, 4>, F = 8 segsum_rows_kernel<4, 4> on fp32 rows.  Model: an fp32 sum (any order), fp32 result."""
     g = U.rng(310 + Fd)
     plan = _designed_plan()
     idx, n = _designed_index()
@@ -381,8 +381,8 @@ def test_segment_sum_of_fp32_rows_in_the_autocast_mode(Fd):
 
 @pytest.mark.parametrize('out_dtype', [torch.float32, torch.float16])
 def test_eight_wide_and_four_wide_dealt_sums_are_bit_identical(out_dtype):
-    """The same F = 64 float16 rows through both dealt kernels, selected by the source base: 16-byte aligned -> segsum_rows8s_kernel,
-    8- but not 16-byte aligned (a larger allocation offset by 4 halves) -> segsum_rows4s_kernel.  The code promises the same sums in
+    """The same F = 64 float16 rows through both dealt kernels, selected by the source base: 16-byte aligned -> segsum_rows_kernel<8, 4>,
+    8- but not 16-byte aligned (a larger allocation offset by 4 halves) -> segsum_rows_kernel<4, 4>.  The code promises the same sums in
     the same order: torch.equal."""
     g = U.rng(320)
     plan = _designed_plan()
@@ -405,7 +405,7 @@ def test_eight_wide_and_four_wide_dealt_sums_are_bit_identical(out_dtype):
 @pytest.mark.parametrize('Fd', [3, 8])
 def test_fp32_segment_sum_keeps_the_sequential_csr_order(Fd):
     """fp32 mode (dt = 0): the sum of a segment is `s = 0; s += src[order[j]]` over the CSR order in float32 -- bit for bit (F = 8:
-    segsum_rows4_kernel, F = 3: segsum_rows_kernel)."""
+    segsum_rows_kernel<4, 1>, F = 3: segsum_rows_kernel<1, 1>)."""
     g = U.rng(330 + Fd)
     plan = _designed_plan()
     idx, n = _designed_index()
@@ -421,9 +421,71 @@ def test_fp32_segment_sum_keeps_the_sequential_csr_order(Fd):
     assert out.dtype == torch.float32 and torch.equal(out.cpu(), torch.from_numpy(want))
 
 
+ORDER_LENGTHS = (0, 1, 3, 4, 5, 12, 13, 16, 17, 33)   # empty; the tail alone; the main loop's first and second turn; every k of the dealt tail
+
+
+@functools.lru_cache(maxsize=None)
+def _order_plan():
+    """(plan, order, ptr): one segment of every length in ORDER_LENGTHS, source rows assigned by a permutation"""
+    idx = np.repeat(np.arange(len(ORDER_LENGTHS)), ORDER_LENGTHS)
+    U.rng(350).shuffle(idx)
+    plan = T.IndexPlan(torch.from_numpy(idx).to(DEV), len(ORDER_LENGTHS))
+    order, seg = plan.order.cpu().numpy(), plan.ptr.cpu().numpy()
+    assert sorted(order.tolist()) == list(range(idx.size)) and bool((order != np.arange(idx.size)).any())
+    assert tuple(np.diff(seg).tolist()) == ORDER_LENGTHS
+    return plan, order, seg
+
+
+def _order_models(s, order, seg):
+    """The two summation orders in float32, element by element.  sequential: s = 0; s = s + row over the segment in CSR order.
+    dealt: partial k = 0..3 takes rows k, k + 4, ... of the segment in that order; the result is ((p0 + p1) + p2) + p3."""
+    assert s.dtype == np.float32
+    n, Fd = len(seg) - 1, s.shape[1]
+    seq, dealt = np.zeros((n, Fd), dtype=np.float32), np.zeros((n, Fd), dtype=np.float32)
+    for r in range(n):
+        acc = np.zeros(Fd, dtype=np.float32)
+        for j in range(seg[r], seg[r + 1]):
+            acc = acc + s[order[j]]
+        seq[r] = acc
+        p = np.zeros((4, Fd), dtype=np.float32)
+        for k in range(4):
+            for j in range(seg[r] + k, seg[r + 1], 4):
+                p[k] = p[k] + s[order[j]]
+        dealt[r] = ((p[0] + p[1]) + p[2]) + p[3]
+    return seq, dealt
+
+
+@pytest.mark.parametrize('arm', ['f32_F3', 'f32_F8', 'f16_F4', 'f16_F64_on_16_bytes', 'f16_F64_off_by_4_halves'])
+def test_segment_sums_add_in_the_stated_order_bit_for_bit(arm):
+    """Both summation orders of mdx_op_segsum_rows_t as float32 numpy models, torch.equal on fp32 outputs (no rounding hides the order).
+    fp32 rows: the sequential order with dt = 0 and the dealt order with dt & 4, at F = 3 (one feature per thread) and F = 8 (four).
+    float16 rows are always dealt: F = 4 four-wide, F = 64 on a 16-byte base eight-wide, F = 64 offset by four halves four-wide.
+    Magnitudes spread over 2^-12 .. 2^12, so float32 addition depends on the order: the two models must differ."""
+    plan, order, seg = _order_plan()
+    g = U.rng(351)
+    half, Fd = arm.startswith('f16'), int(arm.split('_')[1][1:])
+    M = order.size
+    v = g.standard_normal((M, Fd)) * 2.0 ** g.integers(-12, 13, (M, Fd))
+    src = torch.from_numpy(v.astype(np.float32)).to(DEV)
+    if half:
+        src = src.half()
+        if arm.endswith('off_by_4_halves'):
+            buf = torch.zeros(M * Fd + 8, dtype=torch.float16, device=DEV)
+            buf[4:4 + M * Fd].view(M, Fd).copy_(src)
+            src = buf[4:4 + M * Fd].view(M, Fd)
+        assert src.data_ptr() % 16 == (8 if arm.endswith('off_by_4_halves') else 0)
+    seq, dealt = _order_models(src.float().cpu().numpy(), order, seg)
+    assert bool((seq != dealt).any())
+    if not half:
+        rc, out = _segsum_direct(src, plan, torch.float32)
+        assert rc == 0 and torch.equal(out.cpu(), torch.from_numpy(seq)), (arm, 'sequential')
+    rc, out = _segsum_direct(src, plan, torch.float32, extra=0 if half else 4)
+    assert rc == 0 and torch.equal(out.cpu(), torch.from_numpy(dealt)), (arm, 'dealt')
+
+
 def test_float16_segment_sum_beyond_2_to_22_items_takes_the_sequential_kernel():
     """R = 16400 targets x F = 1024 is 4,198,400 >= 2^22 four-wide items: float16 rows then fall back from the dealt kernels to
-    segsum_rows4_kernel.  600 source rows onto 40 targets; every other target is an exact zero; single-row segments are copies."""
+    segsum_rows_kernel<4, 1>.  600 source rows onto 40 targets; every other target is an exact zero; single-row segments are copies."""
     g = U.rng(340)
     R, Fd, M = 16400, 1024, 600
     assert R * (Fd // 4) >= 2 ** 22
@@ -710,7 +772,7 @@ def test_wrappers_route_float16_rows_that_are_no_multiple_of_four_through_fp32()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# 6. every arm of the launchers' dispatch (csrc/mdx_train.hip `pick`), through the C ABI.  Bounds are those of the operators' own tests:
+# 6. every arm of the launchers' dispatch (csrc/mdx_train.hip, csrc/mdx_train_rows.hip `pick`), through the C ABI.  Bounds are those of the operators' own tests:
 #    fp32 accumulation 2e-6 * sum |terms| (tests/test_gpu_train_ops.py); a rounded output is the unrounded output rounded once (the
 #    kernel rounds the same fp32 value), so it must EQUAL it after the cast.
 # ---------------------------------------------------------------------------------------------------------------------------------
