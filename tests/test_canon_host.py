@@ -12,6 +12,7 @@ from moldiff_amd import canon as C
 from moldiff_amd import kekule as K
 from moldiff_amd import similarity
 from .canon_cases import K5, NAMED, brute_force, cert, chain, fold, mol, permuted, random_mol, read_smiles, ring
+from .util import run_host_check
 
 SMALL = dict(NAMED, **{f'random{seed}': random_mol(seed) for seed in range(200)})
 SAME_KEYS = ('status', 'n_nodes', 'n_leaves', 'n_aut', 'cert_hash', 'canon_n_bonds', 'canon_atom_type', 'canon_bond_index', 'canon_bond_type')
@@ -252,3 +253,8 @@ def test_command_line(tmp_path, capsys):
     assert C.main(['compare', str(tmp_path / 'a.npz'), str(tmp_path / 'b.npz')]) == 0
     cmp = json.loads(capsys.readouterr().out)
     assert cmp['novelty'] == [2 / 3, 0.0] and cmp['uniqueness'] == [2 / 3, 1.0]
+
+
+def test_host_validation_under_the_host_sanitizers(tmp_path):
+    """tools/canon_host_check.cpp over csrc/mdx_canon_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
+    run_host_check('canon_host_check', tmp_path)

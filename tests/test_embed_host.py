@@ -8,6 +8,7 @@ from moldiff_amd import relax, rmsd
 from . import embed_cases as EC
 from . import philox_ref
 from . import relax_cases as RC
+from .util import run_host_check
 
 TRI_TOL = 1e-12
 
@@ -127,3 +128,8 @@ def test_the_statistics_over_conformers_equal_those_of_global_3d():
     assert np.isnan(got['rmsd_max'][2]) and got['n_matched'][2] == 0
     d = np.sqrt(msd[0][ok[0]])
     assert got['rmsd_max'][0] == d.max() and got['rmsd_min'][0] == d.min() and got['rmsd_median'][0] == np.median(d)
+
+
+def test_host_validation_under_the_host_sanitizers(tmp_path):
+    """tools/embed_host_check.cpp over csrc/mdx_embed_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
+    run_host_check('embed_host_check', tmp_path)

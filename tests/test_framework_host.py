@@ -11,6 +11,7 @@ from moldiff_amd import canon as C
 from moldiff_amd import framework as F
 from .canon_cases import ELEMENTS, mol, permuted, ring
 from .framework_cases import CASES, EXPECTED, sparse_graph
+from .util import run_host_check
 
 MEASURED = [k for k, v in EXPECTED.items() if v[0] == 0]
 SMALL = [k for k in MEASURED if k != 'fused_256']
@@ -228,3 +229,8 @@ def test_the_entry_point_is_declared_and_registered():
     if os.path.exists(_lib.LIB_PATH):
         L = _lib.lib()
         assert hasattr(L, 'mdx_mol_framework') and len(L.mdx_mol_framework.argtypes) == 36
+
+
+def test_host_validation_under_the_host_sanitizers(tmp_path):
+    """tools/framework_host_check.cpp over csrc/mdx_framework_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
+    run_host_check('framework_host_check', tmp_path)

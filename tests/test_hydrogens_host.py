@@ -3,9 +3,6 @@ restatement is checked against the geometry the definition promises -- lengths, 
 argument validation of the device entry runs as a stand-alone program under the host sanitizers."""
 import json
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,8 +11,8 @@ from moldiff_amd import hydrogens as H
 from moldiff_amd import kekule as K
 from moldiff_amd import molpack, rmsd
 from . import hydrogens_cases as HC
+from .util import run_host_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TET = math.degrees(math.acos(-1.0 / 3.0))
 
 
@@ -303,11 +300,4 @@ def test_table_validation_raises():
 
 def test_host_validation_under_the_host_sanitizers(tmp_path):
     """tools/hydrogens_host_check.cpp over csrc/mdx_hydrogens_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    exe = str(tmp_path / 'hydrogens_host_check')
-    r = subprocess.run([cxx, '-std=c++17', '-g', '-Wall', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                        os.path.join(ROOT, 'tools', 'hydrogens_host_check.cpp'), '-o', exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and 'hydrogens_host_check ok' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    run_host_check('hydrogens_host_check', tmp_path)

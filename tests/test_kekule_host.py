@@ -12,6 +12,7 @@ import torch
 
 from moldiff_amd import kekule as K
 from moldiff_amd import molpack
+from .util import run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -350,3 +351,8 @@ def test_kekulize_argument_and_the_acceptance_rule():
     assert 'kekulizable' not in plain['counts'] and with_k['counts']['kekulizable'] == 2 and with_k['fractions']['kekulizable'] == 2 / 3
     assert {k: v for k, v in with_k['counts'].items() if k != 'kekulizable'} == plain['counts']
     assert 'there is no kekulisation' not in molcheck.__doc__ and 'mdx_mol_kekulize' in molcheck.__doc__
+
+
+def test_host_validation_under_the_host_sanitizers(tmp_path):
+    """tools/kekule_host_check.cpp over csrc/mdx_kekule_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
+    run_host_check('kekule_host_check', tmp_path)

@@ -7,6 +7,7 @@ import pytest
 
 from moldiff_amd import local3d as L3
 from moldiff_amd import sample_drug3d
+from .util import run_host_check
 
 
 def mol(ele, bonds, pos):
@@ -176,3 +177,8 @@ def test_entry_point_option_the_flag_wins_and_absence_changes_nothing():
     assert {k: v for k, v in with_flag.items() if k != 'local3d'} == {k: v for k, v in without.items() if k != 'local3d'}
     assert set(without) == {'config', 'outdir', 'device', 'batch_size', 'recipe_weights', 'num_mols', 'scaffold', 'num_steps', 'resample',
                             'jump_length', 'accept', 'largest_fragment', 'local3d'}
+
+
+def test_host_validation_under_the_host_sanitizers(tmp_path):
+    """tools/local3d_host_check.cpp over csrc/mdx_local3d_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
+    run_host_check('local3d_host_check', tmp_path)

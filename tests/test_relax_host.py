@@ -2,17 +2,13 @@
 device entry (tools/relax_host_check.cpp under the host sanitizers).  No test depends on the parameter values being right: they check
 that the gradient is the energy's, that the energy has the invariances of an energy, that the minimiser descends and stops as stated."""
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from moldiff_amd import relax as R
 from . import relax_cases as RC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .util import run_host_check
 
 
 def _positions(c):
@@ -159,11 +155,4 @@ def test_summary_and_compare():
 
 def test_host_validation_under_the_host_sanitizers(tmp_path):
     """tools/relax_host_check.cpp over csrc/mdx_relax_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    exe = str(tmp_path / 'relax_host_check')
-    r = subprocess.run([cxx, '-std=c++17', '-g', '-Wall', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                        os.path.join(ROOT, 'tools', 'relax_host_check.cpp'), '-o', exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and 'relax_host_check ok' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    run_host_check('relax_host_check', tmp_path)

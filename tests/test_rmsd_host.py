@@ -3,8 +3,6 @@ invariances and relations at every fixture, ``conformers`` and ``global_3d`` on 
 header and the stand-alone host check.  No GPU."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ from moldiff_amd import rmsd as R
 from .canon_cases import mol
 from .rmsd_cases import brute_force, cases, flat, kabsch_3x3, neopentane, noisy, relabelled
 from .stereo_cases import centre_h, moved, reflected, with_pos
+from .util import run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = cases()
@@ -229,11 +228,4 @@ def test_the_entry_point_is_declared_and_registered():
 
 def test_host_validation_and_the_solver_under_the_host_sanitizers(tmp_path):
     """tools/bestrms_host_check.cpp over csrc/mdx_bestrms_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    exe = str(tmp_path / 'bestrms_host_check')
-    r = subprocess.run([cxx, '-std=c++17', '-g', '-Wall', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                        os.path.join(ROOT, 'tools', 'bestrms_host_check.cpp'), '-o', exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and 'bestrms_host_check ok' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    run_host_check('bestrms_host_check', tmp_path)

@@ -3,8 +3,6 @@ the isomeric key, the isomeric SMILES of ``canon.smiles`` and the argument check
 import itertools
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ from moldiff_amd import kekule as K
 from moldiff_amd import stereo as S
 from .canon_cases import mol
 from .stereo_cases import fixtures, moved, random_3d, reflected
+from .util import run_host_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIX = fixtures()
@@ -243,11 +242,4 @@ def test_command_line_and_files(tmp_path):
 
 def test_host_validation_under_the_host_sanitizers(tmp_path):
     """tools/stereo_host_check.cpp over csrc/mdx_stereo_args.h, a stand-alone program built with AddressSanitizer and UBSan"""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    exe = str(tmp_path / 'stereo_host_check')
-    r = subprocess.run([cxx, '-std=c++17', '-g', '-Wall', '-Werror', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                        os.path.join(ROOT, 'tools', 'stereo_host_check.cpp'), '-o', exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and 'stereo_host_check ok' in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    run_host_check('stereo_host_check', tmp_path)

@@ -1,29 +1,16 @@
 """Host tests of the work distribution of the persistent row-owner kernels: the stand-alone enumeration of the index maps
 (tools/work_plan_host_check.cpp over csrc/mdx_plan.h, the header the kernels compile) and the library's host exports of the plan.
 No GPU."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
 from moldiff_amd import _lib
 from tests import util as U
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_index_maps_enumerated_by_the_host_check(tmp_path):
     """every unit exactly once and every section bit exactly once for the static plan, the queue's item map, the pairs' ranges, the
     XCD remap and the equal split -- built from the real header with the host compiler"""
-    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    exe = str(tmp_path / 'work_plan_host_check')
-    r = subprocess.run([cxx, '-std=c++17', '-O1', '-Wall', '-Werror', os.path.join(ROOT, 'tools', 'work_plan_host_check.cpp'), '-o', exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and 'work_plan_host_check ok' in r.stdout, r.stdout[-3000:]
+    U.run_host_check('work_plan_host_check', tmp_path)
 
 
 def test_work_plan_export_is_the_launchers_plan():

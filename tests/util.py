@@ -202,6 +202,27 @@ def fp32_error_over_orders(eval32, ref64, orders=SUMMATION_ORDERS, extra=()):
     return {k: max(v) for k, v in per.items()}, per
 
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run_host_check(name, tmp_path, sources=(), sanitize=True):
+    """Build tools/<name>.cpp (plus `sources`, paths from the repository root) as a stand-alone program with the host compiler,
+    warnings as errors, under AddressSanitizer and UBSan unless `sanitize` is off; run it; it must exit 0 and print the line '<name> ok'."""
+    import shutil
+    import subprocess
+    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
+    assert cxx, 'no host C++ compiler'
+    exe = str(tmp_path / name)
+    flags = ['-std=c++17', '-O1', '-g', '-Wall', '-Werror']
+    if sanitize:
+        flags += ['-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+    r = subprocess.run([cxx] + flags + [os.path.join(ROOT, 'tools', name + '.cpp')] + [os.path.join(ROOT, s) for s in sources] + ['-o', exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and any(line.startswith(name + ' ok') for line in r.stdout.splitlines()), (r.stdout[-3000:], r.stderr[-2000:])
+
+
 def rmsdiff(a, b):
     a, b = torch.as_tensor(a).detach().cpu().double(), torch.as_tensor(b).detach().cpu().double()
     return float((a - b).pow(2).mean().sqrt()) if a.numel() else 0.0

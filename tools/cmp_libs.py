@@ -1,7 +1,7 @@
 # bit-compare two library builds on one forward + one guided step:  python cmp_libs.py libA libB
 import os, sys, subprocess, torch
 if len(sys.argv) == 4:
-    sys.path.insert(0, '/root/repo' if os.path.exists('/root/repo/bench.py') else os.getcwd())
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import moldiff_amd._lib as _lib
     _lib.LIB_PATH = os.path.abspath(sys.argv[1])
     import bench

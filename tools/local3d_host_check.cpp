@@ -88,6 +88,6 @@ int main() {
   EXPECT(prep(&a, {0, 1, 1, 0, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0}, {0, 2, 2, 2}, range, count) == L3_PREP_ARG);   // C-N and N-C
   EXPECT(prep(&a, {0, 1, 1, 0, 0, 0, 0, 0, 2, 1, 0, 0, 0, 0}, {0, 2, 2, 2}, range, count) == L3_PREP_OK);    // C-N and C=N
   EXPECT(local3d_ws_bytes(0, 0) == 12 && local3d_ws_bytes(10, 5) == 80);
-  std::printf(failures ? "local3d host check: %d FAILED\n" : "local3d host check: ok\n", failures);
+  std::printf(failures ? "local3d host check: %d FAILED\n" : "local3d_host_check ok\n", failures);
   return failures != 0;
 }

@@ -3,12 +3,12 @@
 SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles per wave; SQ_VALU_MFMA_* count cycles (MI355X_MICROARCH.md)."""
 import csv, glob, json, os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIBV = os.environ.get('MDX_LIB_VARIANT')   # e.g. moldiff_amd/libmoldiff_hip_ring4.so -> run through tools/bench_with_lib.py
+LIBV = os.environ.get('MDX_LIB')   # an alternative build (tools/build_variant.sh) -> run through tools/bench_with_lib.py
 CTRS = ['SQ_WAVE_CYCLES', 'SQ_WAIT_ANY', 'SQ_WAIT_INST_ANY', 'SQ_ACTIVE_INST_VALU', 'SQ_ACTIVE_INST_VMEM', 'SQ_ACTIVE_INST_LDS',
         'SQ_VALU_MFMA_COEXEC_CYCLES', 'SQ_VALU_MFMA_BUSY_CYCLES']
 KERNELS = ['edge_a2_kernel', 'edge_b2_kernel', 'edge_bwd2_kernel', 'edge_bwd_kernel', 'node_kernel(']
 work = tempfile.mkdtemp(dir='/tmp')
-cmd = ['rocprofv3', '--pmc'] + CTRS + ['--output-format', 'csv', '-d', work, '--', sys.executable] + ([os.path.join(ROOT, 'tools', 'bench_with_lib.py'), os.path.join(ROOT, LIBV)] if LIBV else [os.path.join(ROOT, 'bench.py')]) + [
+cmd = ['rocprofv3', '--pmc'] + CTRS + ['--output-format', 'csv', '-d', work, '--', sys.executable] + ([os.path.join(ROOT, 'tools', 'bench_with_lib.py'), os.path.abspath(LIBV)] if LIBV else [os.path.join(ROOT, 'bench.py')]) + [
                                        '--steps', '6', '--warmup', '2', '--headline-only'] + sys.argv[2:]
 subprocess.run(cmd, cwd='/tmp', env=dict(os.environ, TMPDIR='/tmp'), check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 acc = {}

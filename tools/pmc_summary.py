@@ -1,6 +1,7 @@
 """Collect the PMC evidence behind bench.py's `roofline.traffic` (run on the GPU box; development/measurement tool).
 
     python tools/pmc_summary.py profiles/r1_c_pmc_summary.json
+    MDX_LIB=moldiff_amd/libmoldiff_hip_x.so python tools/pmc_summary.py out.json      # an alternative build (tools/build_variant.sh)
 
 Three separate rocprofv3 --pmc passes over `bench.py --steps 6 --warmup 2 --headline-only [extra args, e.g. --guided]` (never combined with a trace
 domain), exactly as MI355X_MICROARCH.md prescribes: (1) SQ / GRBM counters, (2) FETCH_SIZE, (3) WRITE_SIZE.  Per-kernel,
@@ -21,6 +22,12 @@ PASSES = [['SQ_WAVE_CYCLES', 'SQ_VALU_MFMA_BUSY_CYCLES', 'SQ_ACTIVE_INST_ANY', '
 import re
 
 
+def bench_command():
+    """bench.py, or with MDX_LIB set tools/bench_with_lib.py on that library"""
+    lib = os.environ.get('MDX_LIB')
+    return [os.path.join(ROOT, 'tools', 'bench_with_lib.py'), os.path.abspath(lib)] if lib else [os.path.join(ROOT, 'bench.py')]
+
+
 def kernel_key(name):
     """'void (anonymous namespace)::edge_a2_kernel<15>(EdgeAArgs, ...)' -> 'edge_a2_kernel<15>' for the library's own block kernels
     (the keys bench.py looks up through mdx_profile_kernel_name); None for everything else."""
@@ -35,7 +42,7 @@ def main():
     acc = {}
     for i, ctrs in enumerate(PASSES):
         d = os.path.join(work, f'pass{i}')
-        cmd = ['rocprofv3', '--pmc'] + ctrs + ['--output-format', 'csv', '-d', d, '--', sys.executable, os.path.join(ROOT, 'bench.py'),
+        cmd = ['rocprofv3', '--pmc'] + ctrs + ['--output-format', 'csv', '-d', d, '--', sys.executable] + bench_command() + [
                                                '--steps', '6', '--warmup', '2', '--headline-only'] + sys.argv[2:]
         subprocess.run(cmd, cwd='/tmp', env=env, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         for f in glob.glob(os.path.join(d, '**', '*counter_collection.csv'), recursive=True):

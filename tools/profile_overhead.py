@@ -1,5 +1,7 @@
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+"""Step time of the bench workload with the library's per-kernel profiling (mdx_profile_enable) off and on, alternating: what the
+profiling events themselves cost (development tool; cited by bench.py).   python tools/profile_overhead.py"""
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from moldiff_amd import _lib
 dev = torch.device('cuda:0')

@@ -4,38 +4,29 @@ conformers, device events after a warm-up; alongside, the wall time of the resta
 1 conformer for scale.  Prints one JSON line and writes it to profiles/embed_timing.txt.  One measurement, no threshold; nothing is
 gated on it and nothing about throughput or sample quality is claimed beyond the line.
 
-    python tools/time_embed.py [--size 256] [--confs 10] [--reps 3] [--ref 4]
+    python tools/time_embed.py [--size 256] [--confs 10] [--reps 3] [--ref 4] [--out FILE]
 """
-import argparse
-import json
-import os
 import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from moldiff_amd import embed as E  # noqa: E402
-from moldiff_amd import hydrogens as H  # noqa: E402
-from moldiff_amd import kekule as K  # noqa: E402
-from moldiff_amd import molpack  # noqa: E402
-from moldiff_amd import relax as R  # noqa: E402
-from tests.relax_cases import random_mol  # noqa: E402
-from time_hydrogens import timed  # noqa: E402
+import evalbench as EB
+from moldiff_amd import embed as E
+from moldiff_amd import hydrogens as H
+from moldiff_amd import kekule as K
+from moldiff_amd import molpack
+from moldiff_amd import relax as R
+from tests.relax_cases import random_mol
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
+    ap = EB.parser(reps=3, out=EB.profile_path('embed_timing.txt'))
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--confs', type=int, default=10)
-    ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--ref', type=int, default=4)
-    ap.add_argument('--device', default='cuda:0')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'embed_timing.txt'))
-    args = ap.parse_args(argv)
-    torch.cuda.set_device(torch.device(args.device))
+    args = EB.parse(ap, argv)
     g = np.random.default_rng(0)
     mols = []
     while len(mols) < args.size:
@@ -43,14 +34,13 @@ def main(argv=None):
         if 20 <= len(m['element']) <= 30:
             mols.append(m)
     tb = R.ForceFieldTables()
-    p = molpack.pack_mols(mols, tb.atomic_numbers, positions=True)
-    cm = molpack.CompactMols.from_packed(molpack.to_device(p, args.device))
+    mols, p, cm, _ = EB.batch(args.size, None, args.device, mols=mols, elements=tb.atomic_numbers)
     kek = K.launch(cm, K.KekuleTables())
     hyd = H.launch(cm, kek['kek_h'], kek['kek_order'], H.HydrogenTables())
     hc = molpack.host(hyd['h_count'])
     n_all = [int(n) + int(np.clip(hc[int(a):int(a) + int(n)], 0, 4).sum()) for a, n in zip(p['atom_ptr'], p['n_atoms'])]
     cap = E._cap(max(n_all))
-    ms, out = timed(lambda: E.launch(cm, kek['kek_order'], hyd['h_count'], hyd['atom_flag'], args.confs, 0, tb, na_cap=cap), args.reps)
+    ms, out = EB.timed(lambda: E.launch(cm, kek['kek_order'], hyd['h_count'], hyd['atom_flag'], args.confs, 0, tb, na_cap=cap), args.reps)
     got = molpack.to_host(dict(out))
     st = got['status'].reshape(-1)
     inputs = R._inputs(mols[:args.ref], tb)
@@ -67,10 +57,7 @@ def main(argv=None):
            'ms_per_conformer': round(ms / max(args.size * args.confs, 1), 4), 'restatement_conformers': len(inputs),
            'restatement_s_total': round(ref_s, 3), 'restatement_agrees_in_the_integers': bool(agree),
            'includes': 'the zero-fill of the outputs and the allocation of the workspaces', 'device': torch.cuda.get_device_name(0)}
-    print(json.dumps(row))
-    if os.access(os.path.dirname(args.out), os.W_OK):
-        with open(args.out, 'w') as f:
-            f.write('tools/time_embed.py: one measurement, not gated\n' + json.dumps(row) + '\n')
+    EB.report([row], args.out, 'tools/time_embed.py: one measurement, not gated')
     return 0
 
 

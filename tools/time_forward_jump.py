@@ -8,31 +8,25 @@ library calls between two device events after `warmup` untimed ones; the windows
 the noise already in its buffers (draw < 0: the one launch named) and with the library's Philox launch in front (draw >= 0: two
 launches).  A window of `steps` whole down-moves gives the step time they are compared with.  Not part of bench.py.
 """
-import argparse
 import ctypes
-import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import evalbench as EB
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = EB.parser()
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--batch', type=int, default=256)
-    ap.add_argument('--out', type=str, default='')
-    args = ap.parse_args()
+    args = EB.parse(ap)
     import bench
     from moldiff_amd import Scaffold, _lib
-    dev = torch.device('cuda:0')
-    torch.cuda.set_device(dev)
+    dev = torch.device(args.device)
     model, ph, sizes = bench.build_workload(args.batch, 0, dev)
     model = model.to(dev)
     bn, hei, bh = ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge']
@@ -76,13 +70,7 @@ def main():
     us = {name: [] for name in jobs}
     for _ in range(args.repeats):
         for name, (fn, draw, n) in jobs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn(draw)
-            e1.record()
-            e1.synchronize()
-            us[name].append(1e3 * e0.elapsed_time(e1) / n)
+            us[name].append(1e3 * EB.timed(lambda: fn(draw), n, warmup=0)[0])
     lines = [f'# tools/time_forward_jump.py --calls {args.calls} --steps {args.steps} --warmup {args.warmup} --repeats {args.repeats} --batch {args.batch}',
              f'# {torch.cuda.get_device_name(0)}; {args.batch} molecules, {N} atoms, {Eh} half-edges; exact fp32 matrix path',
              '# microseconds per call: device events around each window of consecutive calls (back-to-back launches from Python, so a',
@@ -91,12 +79,7 @@ def main():
         lines.append(f'{name:32s} windows {" ".join("%.2f" % x for x in v)}   median {np.median(v):.2f}')
     step = np.median(us['down-move (whole step + merge)'])
     lines.append(f'forward_jump + philox / down-move (medians) {np.median(us["forward_jump + philox"]) / step:.5f}')
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(text)
+    EB.report(lines, args.out)
 
 
 if __name__ == '__main__':

@@ -4,53 +4,27 @@ framework and on the ring systems (``framework.keys`` without its copies to the 
 on the same batch in the same run; next to them ``framework_ref`` on this host.  Checks the batch against the host and prints one JSON
 line.  One measurement, no threshold: the numbers go into profiles/framework_timing.txt.
 
-    python tools/time_framework.py [--n 256] [--atoms 30] [--reps 50] [--mode 0]
+    python tools/time_framework.py [--n 256] [--atoms 30] [--reps 50] [--mode 0] [--out FILE]
 """
-import argparse
-import json
-import os
 import sys
 import time
 
 import numpy as np
-import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from moldiff_amd import canon as C  # noqa: E402
-from moldiff_amd import framework as F  # noqa: E402
-from moldiff_amd import molpack  # noqa: E402
-from moldiff_amd import rings as R  # noqa: E402
-from time_canon import extended  # noqa: E402
-from time_rings import ELEMENTS  # noqa: E402
-
-
-def window(call, reps):
-    for _ in range(5):
-        call()
-    torch.cuda.synchronize()
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(reps):
-        call()
-    stop.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(stop) / reps
+import evalbench as EB
+from evalbench import ELEMENTS
+from moldiff_amd import canon as C
+from moldiff_amd import framework as F
+from moldiff_amd import molpack
+from moldiff_amd import rings as R
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
+    ap = EB.parser(reps=50, atoms=30)
     ap.add_argument('--n', type=int, default=256)
-    ap.add_argument('--atoms', type=int, default=30)
-    ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--mode', type=int, default=0)
-    ap.add_argument('--device', default='cuda:0')
-    args = ap.parse_args(argv)
-    torch.cuda.set_device(torch.device(args.device))
-    g = np.random.default_rng(0)
-    mols = [extended(g, max(12, int(g.normal(args.atoms, 5)))) for _ in range(args.n)]
-    p = molpack.pack_mols(mols, ELEMENTS)
-    cm = molpack.CompactMols.from_packed(molpack.to_device(p, args.device))
+    args = EB.parse(ap, argv)
+    mols, p, cm, _ = EB.batch(args.n, args.atoms, args.device, gen=EB.extended)
     rings_only = lambda: R.launch(cm, len(ELEMENTS), 4)
     ring_data = rings_only()
     alone = lambda: F.launch(cm, ring_data, args.mode)
@@ -59,7 +33,8 @@ def main(argv=None):
         res = F.launch(cm, rings_only(), args.mode)
         sy, _ = F.systems_compact(cm, res)                              # synchronises once: the number of systems
         return res, C.launch(F.framework_compact(cm, res), positions=False), C.launch(sy, positions=False)
-    ms = {'rings_framework_two_canon': window(whole, args.reps), 'framework_alone': window(alone, args.reps), 'rings_alone': window(rings_only, args.reps)}
+    ms = {'rings_framework_two_canon': EB.timed(whole, args.reps)[0], 'framework_alone': EB.timed(alone, args.reps)[0],
+          'rings_alone': EB.timed(rings_only, args.reps)[0]}
     res, fw_canon, sys_canon = whole()
     t0 = time.perf_counter()
     want = F.stack_ref(mols, args.mode)
@@ -74,13 +49,14 @@ def main(argv=None):
     keys = F.keys(cm, res)
     same_keys = all(np.array_equal(keys[k], want_keys[k]) for k in keys)
     s = F.summary(want, want_keys, top_k=3)
-    print(json.dumps({'molecules': len(mols), 'atoms': N, 'bonds': E, 'mode': args.mode, 'systems': int(want['n_systems'].sum()),
-                      'framework_atoms': int(want['n_fw_atoms'].sum()), 'canon_nodes': int(fw_canon['n_nodes'].sum() + sys_canon['n_nodes'].sum()),
-                      'device_ms_per_batch': {k: round(v, 4) for k, v in ms.items()}, 'reps': args.reps,
-                      'includes': 'the zero-fill of the output tensors, the gather of the system records and its one sync',
-                      'host_framework_ref_s': round(host_s, 3), 'host_keys_ref_s': round(host_keys_s, 3), 'device_equals_host': bool(same),
-                      'keys_equal_host': bool(same_keys), 'n_distinct': s['n_distinct'], 'n_keyed': s['n_keyed'],
-                      'n_distinct_systems': s['n_distinct_systems'], 'top_systems': [(t['smiles'], t['count']) for t in s['top_systems']]}))
+    row = {'molecules': len(mols), 'atoms': N, 'bonds': E, 'mode': args.mode, 'systems': int(want['n_systems'].sum()),
+           'framework_atoms': int(want['n_fw_atoms'].sum()), 'canon_nodes': int(fw_canon['n_nodes'].sum() + sys_canon['n_nodes'].sum()),
+           'device_ms_per_batch': {k: round(v, 4) for k, v in ms.items()}, 'reps': args.reps,
+           'includes': 'the zero-fill of the output tensors, the gather of the system records and its one sync',
+           'host_framework_ref_s': round(host_s, 3), 'host_keys_ref_s': round(host_keys_s, 3), 'device_equals_host': bool(same),
+           'keys_equal_host': bool(same_keys), 'n_distinct': s['n_distinct'], 'n_keyed': s['n_keyed'],
+           'n_distinct_systems': s['n_distinct_systems'], 'top_systems': [(t['smiles'], t['count']) for t in s['top_systems']]}
+    EB.report([row], args.out, 'tools/time_framework.py: one measurement, not gated')
     return 0 if same and same_keys else 1
 
 

@@ -13,32 +13,25 @@ row doubles the bin counts, which puts the tables over the LDS budget and every 
 `calls` consecutive calls between two device events after `warmup` untimed ones; the windows of the variants alternate, `repeats` times;
 every call adds into the same statistics object, as the sampling entry point does.  Not part of bench.py.
 """
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import evalbench as EB
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = EB.parser()
     ap.add_argument('--calls', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--batches', type=int, nargs='+', default=[256, 2048])
     ap.add_argument('--bond_bias', type=float, nargs='+', default=[8.0, 2.5])
-    ap.add_argument('--out', type=str, default='')
-    args = ap.parse_args()
+    args = EB.parse(ap)
     from moldiff_amd import _lib
     from moldiff_amd import local3d as L3
     from moldiff_amd.harness import make_data_placeholder
     from moldiff_amd.postprocess import FeaturizeMol
-    dev = torch.device('cuda:0')
-    torch.cuda.set_device(dev)
+    dev = torch.device(args.device)
     feat = FeaturizeMol([6, 7, 8, 9, 15, 16, 17], [1, 2, 3, 4], use_mask_node=True, use_mask_edge=True)
     lines = []
     for bias in args.bond_bias:
@@ -73,26 +66,15 @@ def main():
             us = {name: [] for name in jobs}
             for _ in range(args.repeats):
                 for name, fn in jobs.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(args.calls):
-                        fn()
-                    e1.record()
-                    e1.synchronize()
-                    us[name].append(1000.0 * e0.elapsed_time(e1) / args.calls)
+                    us[name].append(1000.0 * EB.timed(fn, args.calls, warmup=0)[0])
             one = feat.local3d_batch(pred, bn, hei, bh, B, spec, graph).cpu()
             lines.append(f'no-bond bias {bias}: {B} molecules, {N} atoms, {Eh} half-edges, {int(one.n_items[0]) / max(N, 1):.1f} bonds per atom; per call {one.n_items.tolist()} lengths / angles / dihedrals, '
                          f'{int(one.hist.sum())} binned, {int(one.outside.sum())} outside, patterns {[len(p) for p in pats]}')
             for name, v in us.items():
                 lines.append(f'  {name:44s} median {np.median(v):8.1f} us per call   (windows of {args.calls}: ' +
                              ', '.join(f'{x:.1f}' for x in v) + ')')
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('tools/time_local3d.py: device time per call, hipEvents around windows of consecutive calls (allocations of the '
-                    'output tensors included)\n' + text)
+    EB.report(lines, args.out, 'tools/time_local3d.py: device time per call, hipEvents around windows of consecutive calls (allocations of the '
+              'output tensors included)')
 
 
 if __name__ == '__main__':

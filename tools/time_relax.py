@@ -5,48 +5,32 @@ iterations at most; the restatement runs on the first ``--ref`` molecules only, 
 status, stop reason and the iteration and evaluation counts.  Prints one JSON line and writes it to profiles/relax_timing.txt.  One
 measurement, no threshold; nothing is gated on it and nothing about throughput is claimed beyond the line.
 
-    python tools/time_relax.py [--size 256] [--atoms 30] [--iters 200] [--reps 5] [--ref 4]
+    python tools/time_relax.py [--size 256] [--atoms 30] [--iters 200] [--reps 5] [--ref 4] [--out FILE]
 """
-import argparse
-import json
-import os
 import sys
 import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from moldiff_amd import hydrogens as H  # noqa: E402
-from moldiff_amd import kekule as K  # noqa: E402
-from moldiff_amd import molpack  # noqa: E402
-from moldiff_amd import relax as R  # noqa: E402
-from time_groups import ELEMENTS, drug_like  # noqa: E402
-from time_hydrogens import timed  # noqa: E402
+import evalbench as EB
+from moldiff_amd import hydrogens as H
+from moldiff_amd import kekule as K
+from moldiff_amd import molpack
+from moldiff_amd import relax as R
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
+    ap = EB.parser(reps=5, atoms=30, out=EB.profile_path('relax_timing.txt'))
     ap.add_argument('--size', type=int, default=256)
-    ap.add_argument('--atoms', type=int, default=30)
     ap.add_argument('--iters', type=int, default=R.DEFAULT_MAX_ITERS)
-    ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ref', type=int, default=4)
-    ap.add_argument('--device', default='cuda:0')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'relax_timing.txt'))
-    args = ap.parse_args(argv)
-    torch.cuda.set_device(torch.device(args.device))
-    g = np.random.default_rng(0)
-    mols = [drug_like(g, max(12, int(g.normal(args.atoms, 5)))) for _ in range(args.size)]
-    for m in mols:
-        m['atom_pos'] = g.normal(0.0, 2.5, size=(len(m['element']), 3)).astype(np.float32)
-    p = molpack.pack_mols(mols, ELEMENTS, positions=True)
-    cm = molpack.CompactMols.from_packed(molpack.to_device(p, args.device))
+    args = EB.parse(ap, argv)
+    mols, p, cm, _ = EB.batch(args.size, args.atoms, args.device, pos_sigma=2.5)
     kek = K.launch(cm, K.KekuleTables())
     hyd = H.launch(cm, kek['kek_h'], kek['kek_order'], H.HydrogenTables())
     tb = R.ForceFieldTables()
-    ms, out = timed(lambda: R.launch(cm, kek['kek_order'], hyd['h_pos'], hyd['h_count'], hyd['atom_flag'], tb, args.iters), args.reps)
+    ms, out = EB.timed(lambda: R.launch(cm, kek['kek_order'], hyd['h_pos'], hyd['h_count'], hyd['atom_flag'], tb, args.iters), args.reps)
     got = R._dense({k: v for k, v in out.items()}, cm, p)
     got = molpack.to_host(got)
     hk, hh = molpack.to_host(molpack.dense(dict(kek), cm, p, K.LAYOUT)), molpack.to_host(H._dense(dict(hyd), cm, p))
@@ -63,10 +47,7 @@ def main(argv=None):
            'relax_ms_per_batch': round(ms, 3), 'relax_ms_per_molecule': round(ms / max(args.size, 1), 4),
            'restatement_molecules': n_ref, 'restatement_s_per_molecule': round(ref_s / max(n_ref, 1), 3), 'restatement_agrees': bool(agree),
            'includes': 'the zero-fill of the output tensors and the workspace allocation', 'device': torch.cuda.get_device_name(0)}
-    print(json.dumps(row))
-    if os.access(os.path.dirname(args.out), os.W_OK):
-        with open(args.out, 'w') as f:
-            f.write('tools/time_relax.py: one measurement, not gated\n' + json.dumps(row) + '\n')
+    EB.report([row], args.out, 'tools/time_relax.py: one measurement, not gated')
     return 0 if agree else 1
 
 

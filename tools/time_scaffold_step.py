@@ -10,31 +10,24 @@ hits both.  The scaffold fixes the first 8 atoms of every molecule and the bonds
 two only (for a kernel trace: the difference of the two traces' launch counts, divided by the number of steps, is the number of
 launches a conditioned step adds).  Not part of bench.py: the headline measures the unconditioned chain, which this leaves alone.
 """
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import evalbench as EB
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = EB.parser()
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--fixed', type=int, default=8, help='atoms held fixed at the front of every molecule')
     ap.add_argument('--mode', choices=('both', 'plain', 'scaffold'), default='both')
-    ap.add_argument('--out', type=str, default='')
-    args = ap.parse_args()
+    args = EB.parse(ap)
     import bench
     from moldiff_amd import Scaffold
-    dev = torch.device('cuda:0')
-    torch.cuda.set_device(dev)
+    dev = torch.device(args.device)
     model, ph, sizes = bench.build_workload(args.batch, 0, dev)
     model = model.to(dev)
     bn, hei, bh = ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge']
@@ -61,14 +54,9 @@ def main():
     ms = {name: [] for name in samplers}
     for _ in range(args.repeats):
         for name, sm in samplers.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(nxt[name], nxt[name] + args.steps):
-                sm.step(i)
-            e1.record()
-            e1.synchronize()
+            steps = iter(range(nxt[name], nxt[name] + args.steps))
+            ms[name].append(EB.timed(lambda: sm.step(next(steps)), args.steps, warmup=0)[0])
             nxt[name] += args.steps
-            ms[name].append(e0.elapsed_time(e1) / args.steps)
     lines = [f'# tools/time_scaffold_step.py --steps {args.steps} --warmup {args.warmup} --repeats {args.repeats} --batch {args.batch} '
              f'--fixed {args.fixed}',
              f'# {torch.cuda.get_device_name(0)}; {args.batch} molecules, {N} atoms, {Eh} half-edges; {int(mask.sum())} atoms and '
@@ -78,12 +66,7 @@ def main():
         lines.append(f'{name:9s} windows {" ".join("%.4f" % x for x in v)}   median {np.median(v):.4f}   min {min(v):.4f}   max {max(v):.4f}')
     if len(ms) == 2:
         lines.append(f'ratio scaffold / plain (medians) {np.median(ms["scaffold"]) / np.median(ms["plain"]):.4f}')
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(text)
+    EB.report(lines, args.out)
 
 
 if __name__ == '__main__':

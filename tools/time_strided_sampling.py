@@ -13,7 +13,6 @@ as a child under `rocprofv3 --kernel-trace` (plain / jump, 10 and 20 iterations)
 the traces' row counts divided by 10 is the number of launches of one iteration, whatever the set-up launches.
 Says nothing about sample QUALITY at reduced step counts: no trained checkpoint is available.  Not part of bench.py.
 """
-import argparse
 import csv
 import glob
 import os
@@ -25,21 +24,20 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import evalbench as EB
 JUMP_LEVELS = 250
 
 
-def _workload(batch):
+def _workload(batch, device):
     import bench
-    dev = torch.device('cuda:0')
+    dev = torch.device(device)
     torch.cuda.set_device(dev)
     model, ph, _ = bench.build_workload(batch, 0, dev)
     return model.to(dev), (ph['batch_node'], ph['halfedge_index'], ph['batch_halfedge'])
 
 
 def _child(args):
-    model, g = _workload(args.batch)
+    model, g = _workload(args.batch, args.device)
     sm = model.sampler(args.batch, *g, seed=1, return_traj=False, **({} if args.mode == 'plain' else {'num_steps': JUMP_LEVELS}))
     sm.init()
     for i in range(args.iters):
@@ -65,7 +63,7 @@ def _launches_per_iteration(mode, batch):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = EB.parser()
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--window', type=int, default=200)
     ap.add_argument('--repeats', type=int, default=3)
@@ -73,16 +71,15 @@ def main():
     ap.add_argument('--no-launch-count', action='store_true')
     ap.add_argument('--mode', choices=('all', 'plain', 'jump'), default='all')
     ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--out', type=str, default='')
     ap.add_argument('--note', type=str, action='append', default=[], help='line appended to the output (e.g. a figure measured on '
                                                                           'another build in the same session)')
-    args = ap.parse_args()
+    args = ap.parse_args()   # not EB.parse: the parent must not open the GPU before its traced children have run
     if args.mode != 'all':
         return _child(args)
     launches = None
     if not args.no_launch_count:   # children first: the parent has not opened the GPU yet
         launches = {mode: _launches_per_iteration(mode, args.batch) for mode in ('plain', 'jump')}
-    model, g = _workload(args.batch)
+    model, g = _workload(args.batch, args.device)
     T = model.num_timesteps
     N, Eh = int(g[0].numel()), int(g[2].numel())
     model.sample(args.batch, *g, seed=1, return_traj=False, num_steps=50)   # warm-up
@@ -109,14 +106,9 @@ def main():
             if nxt[name] + args.window > (T if name == 'plain' else JUMP_LEVELS) - 1:   # start the chain again, untimed
                 sm.init()
                 nxt[name] = 0
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(nxt[name], nxt[name] + args.window):
-                sm.step(i)
-            e1.record()
-            e1.synchronize()
+            steps = iter(range(nxt[name], nxt[name] + args.window))
+            ms[name].append(EB.timed(lambda: sm.step(next(steps)), args.window, warmup=0)[0])
             nxt[name] += args.window
-            ms[name].append(e0.elapsed_time(e1) / args.window)
     lines = [f'# tools/time_strided_sampling.py --batch {args.batch} --window {args.window} --repeats {args.repeats}',
              f'# {torch.cuda.get_device_name(0)}; {args.batch} molecules, {N} atoms, {Eh} half-edges; MolDiff_simple, exact fp32 matrix path, '
              f'T = {T}',
@@ -135,12 +127,7 @@ def main():
         lines.append(f'kernel launches per iteration (kernel trace, (20 iterations - 10 iterations) / 10): plain {launches["plain"]:.1f}   '
                      f'jump {launches["jump"]:.1f}')
     lines += args.note
-    text = '\n'.join(lines) + '\n'
-    print(text, end='')
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write(text)
+    EB.report(lines, args.out)
 
 
 if __name__ == '__main__':

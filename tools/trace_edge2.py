@@ -21,7 +21,7 @@ import moldiff_amd._lib as _lib  # noqa: E402
 _lib.LIB_PATH = os.path.join(ROOT, 'moldiff_amd', 'libmoldiff_hip_trace2.so')
 import bench  # noqa: E402
 
-ROWS = 16
+ROWS = 16   # rows per wave the kernels are built with
 PH_A = [('tile load + He + smear', 0, 1, 0), ('emb GEMM 80->64', 1, 2, 2 * 80 * 64), ('He store + gate init gathers', 2, 3, 0),
         ('gate GEMM1 64->256', 3, 4, 2 * 64 * 256), ('LN + bias', 4, 5, 0), ('gate GEMM2 256->256', 5, 6, 2 * 256 * 256),
         ('sigmoid + park + bias', 6, 7, 0), ('en GEMM1 64->256', 7, 8, 2 * 64 * 256), ('LN + bias', 8, 9, 0),
@@ -66,14 +66,13 @@ def main_bwd():
         sm.step(i)
     torch.cuda.synchronize()
     E = 2 * ph['halfedge_index'].shape[1]
-    rows = int(os.environ.get('MDX_BWD_ROWS', 16))
-    nunits = (E + rows - 1) // rows + 256      # graph-aligned units of the by-right order: at most one more per molecule
+    nunits = (E + ROWS - 1) // ROWS + 256      # graph-aligned units of the by-right order: at most one more per molecule
     buf = torch.zeros(nunits * 48, dtype=torch.int64, device=dev)
     assert L.mdx_debug_set_trace_bwd(ctypes.c_void_p(buf.data_ptr())) == 0
     sm.step(3)
     torch.cuda.synchronize()
     L.mdx_debug_set_trace_bwd(ctypes.c_void_p(0))
-    report('bwd', buf, nunits, PH_W, 40, rows)
+    report('bwd', buf, nunits, PH_W, 40)
 
 
 def main():
@@ -91,9 +90,8 @@ def main():
         sm.step(i)
     torch.cuda.synchronize()
     E = 2 * ph['halfedge_index'].shape[1]
-    rows = int(os.environ.get('MDX_ROWS', 16))   # rows per wave the kernels are built with (MDX_RR = 1)
-    nunits = (E + rows - 1) // rows
-    if which == 'a' and os.environ.get('MDX_NO_AGG') != '1':   # EA_AGG: units are aligned to each molecule's first edge
+    nunits = (E + ROWS - 1) // ROWS
+    if which == 'a':   # in-kernel aggregation: units are aligned to each molecule's first edge
         nunits = int(sum((int(n) * (int(n) - 1) + 15) // 16 for n in sizes))
     buf = torch.zeros(nunits * 48, dtype=torch.int64, device=dev)
     setter = (lambda p: L.mdx_debug_set_trace2(p, 0)) if which == 'a' else L.mdx_debug_set_trace2b
@@ -101,10 +99,10 @@ def main():
     sm.step(3)
     torch.cuda.synchronize()
     setter(ctypes.c_void_p(0))
-    report(which, buf, nunits, phases, last, rows)
+    report(which, buf, nunits, phases, last)
 
 
-def report(which, buf, nunits, phases, last, ROWS=ROWS):
+def report(which, buf, nunits, phases, last):
     tr = buf.cpu().numpy().reshape(nunits, 48).astype(np.int64)
     os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
     np.save(os.path.join(ROOT, 'gpurun_out', f'trace_edge2_{which}.npy'), tr)

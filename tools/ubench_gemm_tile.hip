@@ -1,10 +1,10 @@
 // Micro-benchmark of the fused-kernel building block gemm_tile<4,ET,256> (csrc/mdx_tile.h):
 // how close to the fp32-MFMA peak does the inner loop alone get, with the same LDS tile / packed-weight stream /
-// workgroup shape as edge kernel A, and 1..3 workgroups per CU?   hipcc --offload-arch=gfx950 -O3 -I moldiff_amd/csrc
+// workgroup shape as edge kernel A, and 1..3 workgroups per CU?   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o ubench_gemm_tile ubench_gemm_tile.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>
-#include "mdx_tile.h"
+#include "../moldiff_amd/csrc/mdx_tile.h"
 
 template <int ET, int WPS, int K, int FTW>
 __global__ __launch_bounds__(256, WPS) void k(const float* __restrict__ W, float* out, int reps, int nmat) {

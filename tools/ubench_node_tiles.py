@@ -9,17 +9,11 @@ hipEvents inside a sampling chain (mdx_profile_*).  If the time steps up from <=
 CUs) and stays flat in between, the launch time at the bench workload (393 tiles) is set by tile granularity, not by anything
 inside a tile; the per-tile efficiency is the 256-tile figure against 25 us.
 """
-import os
-import sys
-
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import moldiff_amd._lib as _lib  # noqa: E402
-if os.environ.get('MDX_LIB'):
-    _lib.LIB_PATH = os.path.abspath(os.environ['MDX_LIB'])   # an alternative build (tools/build_variant.sh)
+import evalbench as EB
+EB.use_lib_from_env()   # MDX_LIB: an alternative build (tools/build_variant.sh)
 import bench  # noqa: E402
 import moldiff_amd as M  # noqa: E402
 from moldiff_amd.harness import default_config, placeholder_from_sizes  # noqa: E402

@@ -3,29 +3,18 @@
 
     python tools/ubench_train_gemms.py            # on the GPU box
 """
-import os
 import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from moldiff_amd import train_ops as T  # noqa: E402
+import evalbench as EB
+from moldiff_amd import train_ops as T
 
 DEV = 'cuda:0'
 
 
-def timeit(fn, reps=20):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps * 1e3   # us
+def us(fn):
+    return EB.timed(fn, 20, warmup=3)[0] * 1e3
 
 
 def main():
@@ -39,10 +28,10 @@ def main():
             gy = torch.randn(M, N, device=DEV).half()
             wt = w.t().contiguous()
             floor = M * (K + N) * 2 / 5e12 * 1e6
-            t_f = timeit(lambda: T.sgemm_nt(x, w, b))
-            t_d = timeit(lambda: T.sgemm_nt(gy, wt, out_dtype=torch.float16))
+            t_f = us(lambda: T.sgemm_nt(x, w, b))
+            t_d = us(lambda: T.sgemm_nt(gy, wt, out_dtype=torch.float16))
             sp = T._splits_for(M, N, K, True)
-            t_w = timeit(lambda: T.sgemm_tn(gy, x, sp, want_bias=True))
+            t_w = us(lambda: T.sgemm_tn(gy, x, sp, want_bias=True))
             print(f'K {K:4d} N {N:4d}: forward {t_f:7.1f}  grad_input {t_d:7.1f}  weight_grad {t_w:7.1f} (splits {sp})   floor {floor:6.1f}')
 
 
