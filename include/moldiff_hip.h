@@ -98,10 +98,12 @@ int mdx_graph_plan_host(int64_t n_nodes, int64_t n_edges, const int64_t* h_edge_
                         int32_t* int2ref, int32_t* row_ptr, int32_t* col_ptr, int32_t* col_eids);
 
 /* ---- test aids of the persistent kernels' work distribution (tests/test_gpu_work_plan.py).  Not for production code. */
-/* Caps the compute-unit count the launchers size their grids by (edge kernels A and B, the guidance backward, linear_rows and the
- * grid heuristics of the training GEMMs read it at launch time), so that a batch of a few hundred edges loops its persistent
- * waves the way a full batch does on the whole device.  n <= 0, or n beyond the device's count, restores the device's own.
- * Process-wide; results never depend on it. */
+/* Caps the compute-unit count the launchers size their grids by (edge kernels A and B, the guidance backward, linear_rows, the
+ * grid heuristics of the training GEMMs and the eight fused float16 training kernels read it at launch time), so that a batch of
+ * a few hundred edges loops its persistent waves the way a full batch does on the whole device.  n <= 0, or n beyond the device's
+ * count, restores the device's own.  Process-wide; results never depend on it -- except that a fused training backward leaves one
+ * partial row of LayerNorm-parameter gradients per workgroup (mdx_op_bondffn_workgroups, = this count): keep one cap from a backward
+ * launch to the reduction of its rows. */
 int mdx_debug_set_num_cus(int32_t n);
 /* Centred packs of the MolDiff denoiser's edge kernels: on = 1 (the default) packs every Linear that feeds
  * a LayerNorm in edge kernels A and B with the mean over its output features taken out, on = 0 packs the weights as stored; the
@@ -128,6 +130,15 @@ int mdx_debug_work_plan_host(int32_t nunits, int32_t nslots, int32_t can_split, 
  * longer with two.  Host only. */
 int mdx_debug_launch_units_host(int64_t n_nodes, int64_t n_edges, const int64_t* h_edge_index, const int64_t* h_batch_node,
                                 int64_t n_graphs, int32_t n_cus, int32_t* launches);
+/* The grid of one of the eight fused float16 training kernels (mdx_op_bondffn / edge_tail / posffn / nodemsg _fwd / _bwd) for n_rows rows
+ * on a device of n_cus compute units (n_cus <= 0: the count the launchers read right now): the launchers' own arithmetic.  A wave owns
+ * 16-row tiles and walks them with a stride of grid x waves.  out[6] = grid (workgroups), waves per workgroup, tiles, rounds (trips of
+ * the first wave's tile loop), tiles in the last round, rows in the last tile.  Host only. */
+enum {
+  MDX_FUSED_BONDFFN_FWD = 0, MDX_FUSED_BONDFFN_BWD = 1, MDX_FUSED_EDGE_TAIL_FWD = 2, MDX_FUSED_EDGE_TAIL_BWD = 3,
+  MDX_FUSED_POSFFN_FWD = 4, MDX_FUSED_POSFFN_BWD = 5, MDX_FUSED_NODEMSG_FWD = 6, MDX_FUSED_NODEMSG_BWD = 7, MDX_FUSED_KERNELS = 8
+};
+int mdx_debug_fused_grid_host(int32_t kernel, int64_t n_rows, int32_t n_cus, int32_t* out);
 
 size_t mdx_workspace_bytes(int64_t n_nodes, int64_t n_edges);
 

@@ -19,7 +19,7 @@ EXPORTS = [
     'mdx_model_create', 'mdx_model_destroy', 'mdx_model_set_param', 'mdx_model_finalize',
     'mdx_model_set_matrix_path', 'mdx_model_get_matrix_path', 'mdx_model_set_smear_start', 'mdx_gauss_posterior',
     'mdx_graph_create', 'mdx_graph_destroy', 'mdx_graph_plan_host', 'mdx_workspace_bytes',
-    'mdx_debug_set_num_cus', 'mdx_debug_work_plan_host', 'mdx_debug_launch_units_host',
+    'mdx_debug_set_num_cus', 'mdx_debug_work_plan_host', 'mdx_debug_launch_units_host', 'mdx_debug_fused_grid_host',
     'mdx_debug_set_ln_centred', 'mdx_debug_centre_host', 'mdx_debug_pack_host',
     'mdx_net_forward', 'mdx_node_block', 'mdx_edge_block', 'mdx_bond_ffn', 'mdx_pos_update', 'mdx_segment_sum',
     'mdx_moldiff_forward', 'mdx_sample_step', 'mdx_sample_step_full', 'mdx_bondpred_forward', 'mdx_bondpred_backward', 'mdx_bondpred_tape_bytes',
@@ -116,6 +116,7 @@ def lib():
         L.mdx_debug_centre_host.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
         L.mdx_debug_pack_host.argtypes = [c_void_p, c_int32, c_void_p, POINTER(c_size_t), c_void_p, POINTER(c_size_t)]
         L.mdx_debug_launch_units_host.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p]
+        L.mdx_debug_fused_grid_host.argtypes = [c_int32, c_int64, c_int32, c_void_p]
         L.mdx_net_forward.argtypes = [c_void_p] * 10 + [c_void_p, c_size_t, c_void_p]
         L.mdx_node_block.argtypes = [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
         L.mdx_edge_block.argtypes = [c_void_p, c_void_p, c_int32] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
@@ -387,8 +388,14 @@ _cu_cap = 0
 
 class cu_cap:
     """`with cu_cap(2):` -- TEST AID: the launchers size their grids as on a device of 2 compute units, so that a small batch loops
-    the persistent waves of the row-owner kernels; the previous cap (none by default) is restored on exit.  Process-wide, results
-    do not depend on it.  n <= 0: the device's own count."""
+    the persistent waves of the row-owner kernels -- edge kernels A and B, the guidance backward, linear_rows, the training GEMMs'
+    grid heuristics and the eight fused float16 training kernels (bondffn, edge_tail, posffn, nodemsg; forward and backward).  The
+    previous cap (none by default) is restored on exit.  Process-wide, results do not depend on it.  n <= 0: the device's own count.
+
+    A fused training backward launches one workgroup per compute unit and leaves one partial row of LayerNorm-parameter gradients per
+    workgroup; the callers size and reduce those rows by the same count.  Keep ONE cap around forward, backward and the reduction of
+    the parameter gradients (inside a gradient sink: up to its flush) -- the rows are summed in another grouping under another count,
+    so parameter gradients agree across caps to rounding, not to the bit."""
 
     def __init__(self, n):
         self.n = max(int(n), 0)
@@ -468,6 +475,19 @@ def launch_units(edge_index, batch_node, n_graphs, n_cus=0):
     check(lib().mdx_debug_launch_units_host(int(bn.numel()), int(ei.shape[1]), ptr(ei), ptr(bn), int(n_graphs), int(n_cus), out))
     keys = ('nunits', 'grid', 'npairs', 'short', 'equal', 'long1', 'long2')
     return {name: dict(zip(keys, out[8 * k:8 * k + 7])) for k, name in enumerate(LAUNCHES)}
+
+
+FUSED_KERNELS = ('bondffn_fwd', 'bondffn_bwd', 'edge_tail_fwd', 'edge_tail_bwd', 'posffn_fwd', 'posffn_bwd', 'nodemsg_fwd', 'nodemsg_bwd')
+
+
+def fused_grid(kernel, n_rows, n_cus=0):
+    """The grid of a fused float16 training kernel (a name of FUSED_KERNELS; include/moldiff_hip.h: MDX_FUSED_*) for n_rows rows on a
+    device of n_cus compute units (0: the count the launchers read right now) -> dict(grid, waves, tiles, rounds, last_tiles,
+    last_rows): workgroups, waves per workgroup, 16-row tiles, trips of the first wave's tile loop, tiles of the last round, rows of
+    the last tile.  The launchers' own arithmetic (csrc/mdx_train_plan.h fused_grid).  No GPU."""
+    out = (c_int32 * 6)()
+    check(lib().mdx_debug_fused_grid_host(FUSED_KERNELS.index(kernel), int(n_rows), int(n_cus), out))
+    return dict(zip(('grid', 'waves', 'tiles', 'rounds', 'last_tiles', 'last_rows'), out))
 
 
 # Matrix path of the per-edge Linear layers (include/moldiff_hip.h: MDX_MATRIX_*).  'exact_f32' is the default everywhere;

@@ -34,8 +34,11 @@ int mdx_set_error(int code, const char* msg) { return fail(code, "%s", msg); }  
   } while (0)
 
 // compute units of the current device (grid sizes of the persistent kernels; for the other translation units), read by the
-// launchers at every launch.  A test may cap it (mdx_debug_set_num_cus): nothing made at model or graph creation depends on it
-// (the work-queue counter sets hold MDX_WQ_PAIRS >= #CUs lines whatever the count), and a cap only lowers it.
+// launchers at every launch: edge kernels A and B, the guidance backward, linear_rows, the training GEMMs' grid heuristics and the
+// eight fused float16 training kernels of mdx_train_fused.hip.  A test may cap it (mdx_debug_set_num_cus): nothing made at model or
+// graph creation depends on it (the work-queue counter sets hold MDX_WQ_PAIRS >= #CUs lines whatever the count), and a cap only
+// lowers it.  The fused training backwards leave one partial row of LayerNorm-parameter gradients per workgroup = per compute unit of
+// this count (mdx_op_bondffn_workgroups): a cap must not change between such a launch and the reduction of its rows.
 static int g_cu_cap = 0;  // 0: none
 int mdx_num_cus() {
   static const int n = [] {

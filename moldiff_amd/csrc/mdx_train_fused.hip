@@ -29,8 +29,10 @@
 
 #include "../../include/moldiff_hip.h"
 #include "mdx_tile.h"
+#include "mdx_train_plan.h"
 
 int mdx_set_error(int code, const char* msg);  // mdx_api.hip
+int mdx_num_cus();                             // mdx_api.hip: the device's compute units, or mdx_debug_set_num_cus' cap
 
 namespace {
 
@@ -1066,16 +1068,6 @@ __global__ __launch_bounds__(PF_THREADS) void posffn_bwd_kernel(const mdx_posffn
   }
 }
 
-int g_ncu = 0;
-int ncus() {
-  if (!g_ncu) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) g_ncu = p.multiProcessorCount;
-    if (g_ncu <= 0) g_ncu = 256;
-  }
-  return g_ncu;
-}
 bool g_attr_fwd = false, g_attr_bwd = false;
 
 int check_fwd(const mdx_bondffn_args& a, const char* who) {
@@ -1101,7 +1093,14 @@ int check_tail(const mdx_edge_tail_args& a) {
 
 }  // namespace
 
-extern "C" int mdx_op_bondffn_workgroups(void) { return ncus(); }
+// grid of fused kernel `kernel` (MDX_FUSED_*) for E rows on n_cus compute units: mdx_train_plan.h fused_grid with the kernel's waves
+// per workgroup and workgroups per CU (defined behind the last kernel, whose build parameters it reads)
+static FusedGrid fused_shape(int kernel, int64_t E, int n_cus);
+
+// Workgroups of every fused backward = partial rows of LayerNorm-parameter gradients it leaves.  The callers size the partial-row buffer
+// from this call right before the launch and reduce the rows the buffer has, so the two agree as long as the compute-unit count does not
+// change between them: a test's cap (mdx_debug_set_num_cus) must span a backward launch AND the reduction of its rows.
+extern "C" int mdx_op_bondffn_workgroups(void) { return mdx_num_cus(); }
 extern "C" int mdx_op_bondffn_lnp_floats(void) { return BF_LNP; }
 
 extern "C" int mdx_op_bondffn_fwd(const mdx_bondffn_args* a, void* stream) {
@@ -1115,8 +1114,7 @@ extern "C" int mdx_op_bondffn_fwd(const mdx_bondffn_args* a, void* stream) {
       return mdx_set_error(MDX_ERR_HIP, "bondffn_fwd: cannot reserve LDS");
     g_attr_fwd = true;
   }
-  const int ntiles = (int)((a->E + 15) / 16);
-  const int grid = std::max(1, std::min(ncus(), (ntiles + BF_FWD_WAVES - 1) / BF_FWD_WAVES));
+  const int grid = fused_shape(MDX_FUSED_BONDFFN_FWD, a->E, mdx_num_cus()).grid;
   hipLaunchKernelGGL(bondffn_fwd_kernel, dim3(grid), dim3(BF_FWD_THREADS), FwdLds::BYTES, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "bondffn_fwd: launch failed");
 }
@@ -1135,7 +1133,7 @@ extern "C" int mdx_op_bondffn_bwd(const mdx_bondffn_bwd_args* a, void* stream) {
   }
   // ALWAYS the full grid: the caller's reduction of the LayerNorm-parameter partials reads mdx_op_bondffn_workgroups() rows
   // (workgroups without tiles write zero rows)
-  hipLaunchKernelGGL(bondffn_bwd_kernel, dim3(ncus()), dim3(BF_THREADS), BwdLds::BYTES, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(bondffn_bwd_kernel, dim3(fused_shape(MDX_FUSED_BONDFFN_BWD, a->f.E, mdx_num_cus()).grid), dim3(BF_THREADS), BwdLds::BYTES, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "bondffn_bwd: launch failed");
 }
 
@@ -1146,8 +1144,7 @@ extern "C" int mdx_op_edge_tail_fwd(const mdx_edge_tail_args* a, void* stream) {
   if (a->E == 0) return MDX_OK;
   if (int rc = check_tail(*a)) return rc;
   if (!a->pre || !a->post || !a->out) return mdx_set_error(MDX_ERR_ARG, "edge_tail_fwd: null output");
-  const int ntiles = (int)((a->E + 15) / 16);
-  const int grid = std::max(1, std::min(2 * ncus(), (ntiles + ET_WAVES - 1) / ET_WAVES));
+  const int grid = fused_shape(MDX_FUSED_EDGE_TAIL_FWD, a->E, mdx_num_cus()).grid;
   hipLaunchKernelGGL(edge_tail_fwd_kernel, dim3(grid), dim3(ET_THREADS), 0, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "edge_tail_fwd: launch failed");
 }
@@ -1158,7 +1155,7 @@ extern "C" int mdx_op_edge_tail_bwd(const mdx_edge_tail_bwd_args* a, void* strea
   if (int rc = check_tail(a->f)) return rc;
   if (!a->f.pre || !a->g_out || !a->g_pre || !a->g_h || !a->lnp) return mdx_set_error(MDX_ERR_ARG, "edge_tail_bwd: null operand");
   if ((a->ldg & 3) || (reinterpret_cast<uintptr_t>(a->g_out) & 7)) return mdx_set_error(MDX_ERR_ARG, "edge_tail_bwd: gradient rows must be 8-byte aligned");
-  hipLaunchKernelGGL(edge_tail_bwd_kernel, dim3(ncus()), dim3(ET_THREADS), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(edge_tail_bwd_kernel, dim3(fused_shape(MDX_FUSED_EDGE_TAIL_BWD, a->f.E, mdx_num_cus()).grid), dim3(ET_THREADS), 0, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "edge_tail_bwd: launch failed");
 }
 
@@ -1185,8 +1182,7 @@ extern "C" int mdx_op_posffn_fwd(const mdx_posffn_args* a, void* stream) {
       return mdx_set_error(MDX_ERR_HIP, "posffn_fwd: cannot reserve LDS");
     g_attr_pf = true;
   }
-  const int ntiles = (int)((a->E + 15) / 16);
-  const int grid = std::max(1, std::min(ncus(), (ntiles + PF_WAVES - 1) / PF_WAVES));
+  const int grid = fused_shape(MDX_FUSED_POSFFN_FWD, a->E, mdx_num_cus()).grid;
   hipLaunchKernelGGL(posffn_fwd_kernel, dim3(grid), dim3(PF_THREADS), PfLds::BYTES, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "posffn_fwd: launch failed");
 }
@@ -1202,7 +1198,7 @@ extern "C" int mdx_op_posffn_bwd(const mdx_posffn_bwd_args* a, void* stream) {
       return mdx_set_error(MDX_ERR_HIP, "posffn_bwd: cannot reserve LDS");
     g_attr_pb = true;
   }
-  hipLaunchKernelGGL(posffn_bwd_kernel, dim3(ncus()), dim3(PF_THREADS), PbLds::BYTES, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(posffn_bwd_kernel, dim3(fused_shape(MDX_FUSED_POSFFN_BWD, a->f.E, mdx_num_cus()).grid), dim3(PF_THREADS), PbLds::BYTES, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "posffn_bwd: launch failed");
 }
 
@@ -1811,8 +1807,7 @@ extern "C" int mdx_op_nodemsg_fwd(const mdx_nodemsg_args* a, void* stream) {
   if (a->E == 0) return MDX_OK;
   if (int rc = check_nodemsg(*a)) return rc;
   if (!a->he_pre || !a->he_post || !a->he || !a->p || !a->m0 || !a->g_pre || !a->g_post || !a->gt || !a->msg) return mdx_set_error(MDX_ERR_ARG, "nodemsg_fwd: null output");
-  const int ntiles = (int)((a->E + 15) / 16);
-  const int grid = std::max(1, std::min(NMF_WG_PER_CU * ncus(), (ntiles + NMF_WAVES - 1) / NMF_WAVES));
+  const int grid = fused_shape(MDX_FUSED_NODEMSG_FWD, a->E, mdx_num_cus()).grid;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute((const void*)nodemsg_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NMF_WAVES * TS_BYTES) != hipSuccess)
@@ -1835,6 +1830,31 @@ extern "C" int mdx_op_nodemsg_bwd(const mdx_nodemsg_bwd_args* a, void* stream) {
       return mdx_set_error(MDX_ERR_HIP, "nodemsg_bwd: cannot reserve LDS");
     g_attr_nb = true;
   }
-  hipLaunchKernelGGL(nodemsg_bwd_kernel, dim3(ncus()), dim3(NM_THREADS), NM_BWD_LDS, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(nodemsg_bwd_kernel, dim3(fused_shape(MDX_FUSED_NODEMSG_BWD, a->f.E, mdx_num_cus()).grid), dim3(NM_THREADS), NM_BWD_LDS, (hipStream_t)stream, *a);
   return hipGetLastError() == hipSuccess ? MDX_OK : mdx_set_error(MDX_ERR_HIP, "nodemsg_bwd: launch failed");
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The one grid formula of the eight launchers above, and its host export (a test aid: which round regime a batch is in on a device of
+// n_cus compute units).
+// ------------------------------------------------------------------------------------------------------------------------------------
+static FusedGrid fused_shape(int kernel, int64_t E, int n_cus) {
+  switch (kernel) {
+    case MDX_FUSED_BONDFFN_FWD: return fused_grid(E, n_cus, 1, BF_FWD_WAVES, false);
+    case MDX_FUSED_BONDFFN_BWD: return fused_grid(E, n_cus, 1, BF_WAVES, true);
+    case MDX_FUSED_EDGE_TAIL_FWD: return fused_grid(E, n_cus, 2, ET_WAVES, false);
+    case MDX_FUSED_EDGE_TAIL_BWD: return fused_grid(E, n_cus, 1, ET_WAVES, true);
+    case MDX_FUSED_POSFFN_FWD: return fused_grid(E, n_cus, 1, PF_WAVES, false);
+    case MDX_FUSED_POSFFN_BWD: return fused_grid(E, n_cus, 1, PF_WAVES, true);
+    case MDX_FUSED_NODEMSG_FWD: return fused_grid(E, n_cus, NMF_WG_PER_CU, NMF_WAVES, false);
+    default: return fused_grid(E, n_cus, 1, NM_WAVES, true);   // MDX_FUSED_NODEMSG_BWD
+  }
+}
+
+extern "C" int mdx_debug_fused_grid_host(int32_t kernel, int64_t E, int32_t n_cus, int32_t* out) {
+  if (!out || kernel < 0 || kernel >= MDX_FUSED_KERNELS || E < 0) return mdx_set_error(MDX_ERR_ARG, "fused grid: null output, unknown kernel or negative row count");
+  if (n_cus <= 0) n_cus = mdx_num_cus();  // what the launchers see right now
+  const FusedGrid g = fused_shape(kernel, E, n_cus);
+  out[0] = g.grid; out[1] = g.waves; out[2] = g.tiles; out[3] = g.rounds; out[4] = g.last_tiles; out[5] = g.last_rows;
+  return MDX_OK;
 }

@@ -1,7 +1,7 @@
-// Host arithmetic of the training operators (mdx_train.hip, mdx_train_rows.hip) that more than one place has to agree on: where the split partials of a
+// Host arithmetic of the training operators (mdx_train.hip, mdx_train_rows.hip, mdx_train_fused.hip) that more than one place has to agree on: where the split partials of a
 // weight gradient live, which tile class a queued weight gradient takes, how many partial rows the LayerNorm backward leaves, how the
-// deferred reduction numbers its blocks, and which shapes the row-owner GEMM takes.  Plain C++17, no HIP and no torch: mdx_train.hip
-// (launchers and reduce_deferred_kernel) and mdx_fast.cpp (buffer sizes, the gradient sink's record table) include it, and
+// deferred reduction numbers its blocks, which shapes the row-owner GEMM takes, and the grid of the fused row-owner operators.  Plain C++17, no HIP and no torch: mdx_train.hip
+// (launchers and reduce_deferred_kernel), mdx_train_fused.hip (launchers) and mdx_fast.cpp (buffer sizes, the gradient sink's record table) include it, and
 // tools/train_plan_host_check.cpp builds it on its own with a host compiler and enumerates it.  The functions are constexpr, so the
 // device compiler accepts them inside a kernel as they are.
 #pragma once
@@ -91,4 +91,20 @@ constexpr int64_t red_chunk_plane(int64_t S, int64_t c) { return S + c; }
 // The shapes it is instantiated for and worth launching at: K in {32, 64, 128, 256}, N in {32, 64, 128, 256}, at least 1,024 rows.
 constexpr bool rows_gemm_shape(int64_t M, int64_t N, int64_t K) {
   return M >= 1024 && (K == 32 || K == 64 || K == 128 || K == 256) && (N == 32 || N == 64 || N == 128 || N == 256);
+}
+
+// ---- fused row-owner operators (mdx_train_fused.hip) ---------------------------------------------------------------------------------
+// A wave owns 16-row tiles and walks them with a stride of grid x waves.  A forward launches min(wg_per_cu x #CUs, ceil(tiles / waves))
+// workgroups, at least one; a backward always #CUs (one partial row of LayerNorm-parameter gradients per workgroup, whether it had a
+// tile or not).  rounds: trips of the tile loop of the grid's first wave; last_tiles: tiles of the last round (the other waves of that
+// round are past the end); last_rows: rows of the last tile.
+struct FusedGrid {
+  int grid, waves, tiles, rounds, last_tiles, last_rows;
+};
+constexpr FusedGrid fused_grid(int64_t E, int n_cus, int wg_per_cu, int waves, bool backward) {
+  const int64_t tiles = ceil_div(E > 0 ? E : 0, 16);
+  const int64_t want = ceil_div(tiles, waves), cap = (int64_t)wg_per_cu * n_cus;
+  const int64_t grid = backward ? n_cus : (want < cap ? (want > 1 ? want : 1) : cap);
+  const int64_t nw = grid * waves, rounds = ceil_div(tiles, nw);
+  return {(int)grid, waves, (int)tiles, (int)rounds, (int)(tiles ? tiles - (rounds - 1) * nw : 0), (int)(tiles ? E - 16 * (tiles - 1) : 0)};
 }

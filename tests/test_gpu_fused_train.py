@@ -9,6 +9,7 @@ import torch
 from moldiff_amd import graph as G
 from moldiff_amd import train_graph as TG
 from moldiff_amd import train_ops as T
+from tests import fused_train_cases as C
 from tests import util as U
 
 pytestmark = pytest.mark.gpu
@@ -16,51 +17,27 @@ DEV = 'cuda:0'
 
 
 def _setup(sizes, seed, scale=1.0):
-    g = U.rng(seed)
-    bn, hei, bh, ei, be = U.graph_from_sizes(sizes)
-    N, E = len(bn), ei.shape[1]
-    m = G.BondFFN(64, 256, 128, True).to(DEV)
-    with torch.no_grad():
-        for k, p in sorted(m.named_parameters()):
-            if p.dim() == 2:
-                p.copy_(torch.from_numpy((g.standard_normal(tuple(p.shape)) * (1.2 / np.sqrt(p.shape[1]))).astype(np.float32)))
-            elif 'net.1.' in k and k.endswith('weight'):
-                p.copy_(torch.from_numpy((1.0 + 0.4 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-            else:
-                p.copy_(torch.from_numpy((0.3 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-    x = torch.from_numpy((g.standard_normal((E, 64)) * scale).astype(np.float32)).to(DEV).half()
-    h = torch.from_numpy(g.standard_normal((N, 256)).astype(np.float32)).to(DEV).half()
-    te = torch.from_numpy(g.random((E, 1)).astype(np.float32)).to(DEV)
-    gS = torch.from_numpy(g.standard_normal((N, 64)).astype(np.float32)).to(DEV)
-    tg = TG.TrainGraph(ei.to(DEV), N)
-    return m, x, h, te, gS, tg
+    c = C.bond_ffn_case(sizes, seed, scale)
+    return c.m, c.leaves['x'], c.leaves['h'], c.consts['te'], c.g_out, c.tg
 
 
 def _run(m, x, h, te, gS, tg, fused):
     m.zero_grad(set_to_none=True)
     x = x.clone().requires_grad_(True)
     h = h.clone().requires_grad_(True)
-    old, old_rows = T._FUSED, T.FUSED_MIN_ROWS
-    T._FUSED, T.FUSED_MIN_ROWS = fused, 1
-    try:
-        with T.precision('fp16'):
-            out = TG.bond_ffn_scatter(m, x, te, h, tg.left, tg.right)
-            out.backward(gS)
-    finally:
-        T._FUSED, T.FUSED_MIN_ROWS = old, old_rows
+    with C.fused_path(fused), T.precision('fp16'):
+        out = TG.bond_ffn_scatter(m, x, te, h, tg.left, tg.right)
+        out.backward(gS)
     grads = {k: p.grad.detach().clone() for k, p in m.named_parameters()}
     return out.detach(), x.grad.detach(), h.grad.detach(), grads
 
 
-def _rel2(a, b):
-    """relative L2 distance"""
-    a, b = a.double(), b.double()
-    return float((a - b).norm() / b.norm().clamp(min=1e-12))
+_rel, _rel2 = C.rel, C.rel2
 
 
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / b.abs().max().clamp(min=1e-12))
+def _both_paths(case):
+    """(out, *input gradients, parameter gradients) of the fused and of the per-operator path"""
+    return [(o, *gl.values(), gp) for o, gl, gp in (case.run(True), case.run(False))]
 
 
 @pytest.mark.parametrize('sizes', [[5, 7, 4], [24, 31, 18, 27, 22, 25, 30, 19, 26, 23], [2, 2, 3]])
@@ -163,45 +140,12 @@ def test_fused_bondffn_with_a_sink_that_holds_some_of_its_parameters():
 # ---------------------------------------------------------------------------------------------------------------------------
 # EdgeBlock (two fused BondFFNs + the fused tail with the residual) against the per-operator composition
 # ---------------------------------------------------------------------------------------------------------------------------
-def _edge_block_run(m, x, h, te, g_out, tg, fused):
-    m.zero_grad(set_to_none=True)
-    x = x.clone().requires_grad_(True)
-    h = h.clone().requires_grad_(True)
-    old, old_rows = T._FUSED, T.FUSED_MIN_ROWS
-    T._FUSED, T.FUSED_MIN_ROWS = fused, 1
-    try:
-        with T.precision('fp16'):
-            out = TG.edge_block(m, x, tg, h, te, residual=True)
-            out.backward(g_out)
-    finally:
-        T._FUSED, T.FUSED_MIN_ROWS = old, old_rows
-    return out.detach(), x.grad.detach(), h.grad.detach(), {k: p.grad.detach().clone() for k, p in m.named_parameters()}
-
-
 @pytest.mark.parametrize('sizes', [[5, 7, 4], [24, 31, 18, 27, 22, 25, 30, 19, 26, 23]])
 def test_fused_edge_block_with_residual_equals_the_per_operator_composition(sizes):
     """h + EdgeBlock(h) (models/graph.py:268-294, :360) with both BondFFNs and the tail fused vs the per-operator path in the same float16
     arithmetic: output within 2 float16 ulp of its scale; gradients within 1 % in L2 (individual rows may sit on different sides of a ReLU kink once the
     two paths' LayerNorm statistics differ in the last bit)."""
-    g = U.rng(23)
-    bn, hei, bh, ei, be = U.graph_from_sizes(sizes)
-    N, E = len(bn), ei.shape[1]
-    m = G.EdgeBlock(64, 256).to(DEV)
-    with torch.no_grad():
-        for k, p in sorted(m.named_parameters()):
-            if p.dim() == 2:
-                p.copy_(torch.from_numpy((g.standard_normal(tuple(p.shape)) * (1.0 / np.sqrt(p.shape[1]))).astype(np.float32)))
-            elif ('net.1.' in k or 'layer_norm' in k) and k.endswith('weight'):
-                p.copy_(torch.from_numpy((1.0 + 0.3 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-            else:
-                p.copy_(torch.from_numpy((0.2 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-    x = torch.from_numpy(g.standard_normal((E, 64)).astype(np.float32)).to(DEV).half()
-    h = torch.from_numpy(g.standard_normal((N, 256)).astype(np.float32)).to(DEV).half()
-    te = torch.from_numpy(g.random((E, 1)).astype(np.float32)).to(DEV)
-    g_out = torch.from_numpy(g.standard_normal((E, 64)).astype(np.float32)).to(DEV).half()
-    tg = TG.TrainGraph(ei.to(DEV), N)
-    o1, gx1, gh1, gr1 = _edge_block_run(m, x, h, te, g_out, tg, True)
-    o0, gx0, gh0, gr0 = _edge_block_run(m, x, h, te, g_out, tg, False)
+    (o1, gx1, gh1, gr1), (o0, gx0, gh0, gr0) = _both_paths(C.edge_block_case(sizes))
     assert o1.dtype == o0.dtype == torch.float16 and gx1.dtype == gx0.dtype
     print(f'\n[fused EdgeBlock vs per-operator] out max {_rel(o1, o0):.2e}  dX L2 {_rel2(gx1, gx0):.2e}  dh L2 {_rel2(gh1, gh0):.2e}')
     for k in gr0:
@@ -220,41 +164,7 @@ def test_fused_edge_block_with_residual_equals_the_per_operator_composition(size
 def test_fused_pos_update_equals_the_per_operator_composition(sizes):
     """PosUpdate.forward (models/graph.py:384-396) with gather / product / bond_linear / node_linear / gate MLP fused into one launch each
     way: the position increment and every gradient against the per-operator path in the same float16 arithmetic."""
-    g = U.rng(29)
-    bn, hei, bh, ei, be = U.graph_from_sizes(sizes)
-    N, E = len(bn), ei.shape[1]
-    m = G.PosUpdate(256, 64, 64, True).to(DEV)
-    with torch.no_grad():
-        for k, p in sorted(m.named_parameters()):
-            if p.dim() == 2:
-                p.copy_(torch.from_numpy((g.standard_normal(tuple(p.shape)) * (1.0 / np.sqrt(p.shape[1]))).astype(np.float32)))
-            elif 'net.1.' in k and k.endswith('weight'):
-                p.copy_(torch.from_numpy((1.0 + 0.3 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-            else:
-                p.copy_(torch.from_numpy((0.2 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-    he = torch.from_numpy(g.standard_normal((E, 64)).astype(np.float32)).to(DEV).half()
-    hn = torch.from_numpy(g.standard_normal((N, 256)).astype(np.float32)).to(DEV).half()
-    pos = torch.from_numpy((g.standard_normal((N, 3)) * 2.0).astype(np.float32)).to(DEV)
-    te = torch.from_numpy(g.random((E, 1)).astype(np.float32)).to(DEV)
-    g_out = torch.from_numpy(g.standard_normal((N, 3)).astype(np.float32)).to(DEV)
-    tg = TG.TrainGraph(ei.to(DEV), N)
-
-    def run(fused):
-        m.zero_grad(set_to_none=True)
-        x, h, p = he.clone().requires_grad_(True), hn.clone().requires_grad_(True), pos.clone().requires_grad_(True)
-        old, old_rows = T._FUSED, T.FUSED_MIN_ROWS
-        T._FUSED, T.FUSED_MIN_ROWS = fused, 1
-        try:
-            with T.precision('fp16'):
-                rel, dist = T.edge_geom(p, tg.left, tg.right)
-                out = TG.pos_update(m, h, x, tg, rel, dist, te)
-                out.backward(g_out)
-        finally:
-            T._FUSED, T.FUSED_MIN_ROWS = old, old_rows
-        return out.detach(), x.grad.detach(), h.grad.detach(), p.grad.detach(), {k: q.grad.detach().clone() for k, q in m.named_parameters()}
-
-    o1, gx1, gh1, gp1, gr1 = run(True)
-    o0, gx0, gh0, gp0, gr0 = run(False)
+    (o1, gx1, gh1, gp1, gr1), (o0, gx0, gh0, gp0, gr0) = _both_paths(C.pos_update_case(sizes))
     print(f'\n[fused PosUpdate vs per-operator] out max {_rel(o1, o0):.2e}  dX L2 {_rel2(gx1, gx0):.2e}  dh L2 {_rel2(gh1, gh0):.2e}  dpos L2 {_rel2(gp1, gp0):.2e}')
     for k in gr0:
         print(f'    {k:40s} L2 {_rel2(gr1[k], gr0[k]):.2e}')
@@ -273,39 +183,7 @@ def test_fused_node_block_equals_the_per_operator_composition(sizes):
     """NodeBlock.forward (models/graph.py:29-55) with edge_net, the product with node_net(x)[col], msg_net, the gate MLP and the sigmoid
     product in one launch each way (weights streamed as float16 A-operand packs): output and every gradient against the per-operator
     path in the same float16 arithmetic."""
-    g = U.rng(31)
-    bn, hei, bh, ei, be = U.graph_from_sizes(sizes)
-    N, E = len(bn), ei.shape[1]
-    m = G.NodeBlock(256, 64, 256, True).to(DEV)
-    with torch.no_grad():
-        for k, p in sorted(m.named_parameters()):
-            if p.dim() == 2:
-                p.copy_(torch.from_numpy((g.standard_normal(tuple(p.shape)) * (1.0 / np.sqrt(p.shape[1]))).astype(np.float32)))
-            elif ('net.1.' in k or 'layer_norm' in k) and k.endswith('weight'):
-                p.copy_(torch.from_numpy((1.0 + 0.3 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-            else:
-                p.copy_(torch.from_numpy((0.2 * g.standard_normal(tuple(p.shape))).astype(np.float32)))
-    he = torch.from_numpy(g.standard_normal((E, 64)).astype(np.float32)).to(DEV).half()
-    hn = torch.from_numpy(g.standard_normal((N, 256)).astype(np.float32)).to(DEV).half()
-    tn = torch.from_numpy(g.random((N, 1)).astype(np.float32)).to(DEV)
-    g_out = torch.from_numpy(g.standard_normal((N, 256)).astype(np.float32)).to(DEV).half()
-    tg = TG.TrainGraph(ei.to(DEV), N)
-
-    def run(fused):
-        m.zero_grad(set_to_none=True)
-        x, h = he.clone().requires_grad_(True), hn.clone().requires_grad_(True)
-        old, old_rows = T._FUSED, T.FUSED_MIN_ROWS
-        T._FUSED, T.FUSED_MIN_ROWS = fused, 1
-        try:
-            with T.precision('fp16'):
-                out = TG.node_block(m, h, tg, x, tn)
-                out.backward(g_out)
-        finally:
-            T._FUSED, T.FUSED_MIN_ROWS = old, old_rows
-        return out.detach(), x.grad.detach(), h.grad.detach(), {k: q.grad.detach().clone() for k, q in m.named_parameters()}
-
-    o1, gx1, gh1, gr1 = run(True)
-    o0, gx0, gh0, gr0 = run(False)
+    (o1, gx1, gh1, gr1), (o0, gx0, gh0, gr0) = _both_paths(C.node_block_case(sizes))
     print(f'\n[fused NodeBlock vs per-operator] out max {_rel(o1, o0):.2e}  dX L2 {_rel2(gx1, gx0):.2e}  dh L2 {_rel2(gh1, gh0):.2e}')
     for k in gr0:
         print(f'    {k:40s} L2 {_rel2(gr1[k], gr0[k]):.2e}')

@@ -1,6 +1,7 @@
 // Stand-alone check of the training operators' host arithmetic (moldiff_amd/csrc/mdx_train_plan.h, the header mdx_train.hip and
 // mdx_fast.cpp compile): the split-partial layout, the weight-gradient queue's plan, the LayerNorm backward's partial rows and
-// workspace, the deferred reduction's record table and the row-owner GEMM's shapes.  No HIP, no GPU; tests/test_train_plan_host.py
+// workspace, the deferred reduction's record table, the row-owner GEMM's shapes and the grid of the fused row-owner operators
+// (mdx_train_fused.hip).  No HIP, no GPU; tests/test_train_plan_host.py
 // builds and runs it, and it can be built with a host sanitizer:
 //
 //     g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/train_plan_host_check.cpp -o /tmp/train_plan_host_check
@@ -116,6 +117,28 @@ int main() {
   // record table: blocks of RED_ELEMS outputs
   for (int64_t e : {1, 127, 128, 129, 256 * 256, 256 * 256 + 1, 2 * 1024})
     EXPECT(red_blocks(e) * RED_ELEMS >= e && (red_blocks(e) - 1) * RED_ELEMS < e, "elems %lld", (long long)e);
+
+  // fused row-owner operators: the rounds of the grid's waves tile the tiles (all rounds but the last are full, the last is not empty),
+  // a forward launches no workgroup without a tile in the first round and never more than wg_per_cu per CU, a backward one per CU
+  for (int64_t E : {0, 1, 15, 16, 17, 62, 64, 414, 512, 1744, 1788, 32768, 32769, 154666, (1 << 23) - 1})
+    for (int n_cus : {1, 2, 3, 5, 64, 256, 304})
+      for (int per_cu : {1, 2})
+        for (int waves : {4, 8, 12})
+          for (int bwd = 0; bwd < 2; ++bwd) {
+            const FusedGrid g = fused_grid(E, n_cus, per_cu, waves, bwd != 0);
+            const int64_t tiles = ceil_div(E, 16), nw = (int64_t)g.grid * g.waves;
+            EXPECT(g.waves == waves && g.tiles == tiles && g.grid >= 1, "E %lld grid %d", (long long)E, g.grid);
+            EXPECT(bwd ? g.grid == n_cus : g.grid <= per_cu * n_cus && (int64_t)(g.grid - 1) * waves < (tiles > 1 ? tiles : 1), "E %lld cus %d grid %d",
+                   (long long)E, n_cus, g.grid);
+            EXPECT(!bwd && tiles > (int64_t)(g.grid) * waves ? g.grid == per_cu * n_cus : true, "E %lld cus %d grid %d", (long long)E, n_cus, g.grid);
+            if (tiles == 0) {
+              EXPECT(g.rounds == 0 && g.last_tiles == 0 && g.last_rows == 0, "empty");
+            } else {
+              EXPECT(g.last_tiles >= 1 && g.last_tiles <= nw && (g.rounds - 1) * nw + g.last_tiles == tiles, "E %lld rounds %d last %d", (long long)E,
+                     g.rounds, g.last_tiles);
+              EXPECT(g.last_rows >= 1 && g.last_rows <= 16 && 16 * (tiles - 1) + g.last_rows == E, "E %lld last rows %d", (long long)E, g.last_rows);
+            }
+          }
 
   if (failures) {
     std::printf("train_plan_host_check: %d failures\n", failures);
